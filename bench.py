@@ -8,13 +8,15 @@ Inputs (the scheduled instance stream and the model) are resident in HBM when th
 starts; every pass performs all 100M sequentially-consistent SGD updates (the result is bit-identical
 to the reference's one-instance-at-a-time loop -- checked in-run on a prefix, see "parity").
 
-    python bench.py                       # 1 GPU, 5 timed passes, 1 warm-up, + the secondary workloads
+    python bench.py                       # 1 GPU, 5 timed passes, 1 warm-up: set-up, the timed passes and the line, nothing else
+    python bench.py --full                # + the in-run counters, CPU baseline, parity, quality figures and the secondary workloads
+    python bench.py --dump-outputs DIR    # + the model the timed passes trained, as DIR/<parameter>.npy (float32)
     python bench.py --gpus N              # spawns its own N ranks (torch.distributed.run) when WORLD_SIZE is unset
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --workload pairwise|svdpp|neighbourhood [--gpus N]   # the other BASELINE configs as the main line
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects (cpu_baseline, parity and secondary with --full):
   "roofline"      algorithmic HBM bytes (1072 B/instance at k=64) / HIP-event time of
                   the dominant kernel's launches, against the 8 TB/s HBM3E peak
   "cpu_baseline"  the reference's own solver (oracle/_ref/libsvdf_ref.so, kind "reference"; or the C
@@ -187,6 +189,27 @@ def rmse(pred, label):
     return float(np.sqrt(np.mean(d * d)))
 
 
+DUMP_BYTES = 60_000_000   # headers included, the files stay under 64 MB
+DUMP_PARAMS = ("W_user", "W_item", "u_bias", "i_bias", "g_bias", "W_ufeedback", "ufeedback_bias")
+
+
+def dump_outputs(tr, out_dir, log):
+    """--dump-outputs: the model parameters the timed passes trained -- what a caller of the training path receives -- as out_dir/<name>.npy,
+    float32.  The smallest arrays are written whole; when the rest would pass DUMP_BYTES in all, an array keeps a fixed sample of its rows
+    (seeded, sorted), the same in every run with the same arguments, so that two builds can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    views = [(name, tr.view(name)) for name in DUMP_PARAMS]
+    views = sorted([(name, v) for name, v in views if v is not None and v.size > 0], key=lambda nv: nv[1].nbytes)
+    left = DUMP_BYTES
+    for k, (name, v) in enumerate(views):
+        share, n = left // (len(views) - k), v.shape[0]
+        if v.nbytes > share:
+            v = v[np.sort(np.random.default_rng(0).choice(n, share // (v.nbytes // n), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+        left -= v.nbytes
+        log("dump-outputs: %s %s%s" % (name, "x".join(map(str, v.shape)), " (a sample of %d rows)" % n if v.shape[0] < n else ""))
+
+
 def make_trainer(sa, name, a, factor, device, oracle_kind=None, extra=()):
     fmt, act = WORKLOADS[name][0], WORKLOADS[name][1]
     if oracle_kind:
@@ -314,7 +337,7 @@ def run_workload(name, a, env, steps, warmup, main_line):
     log("%s: model init (libc rand) + upload: %.1fs" % (name, time.time() - t0))
 
     cpu_base, parity = None, None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         cpu_base, parity = cpu_baseline_and_parity(sa, name, a, factor, tr, sample, n, log)
         if world > 1:
             parity = None   # the N-rank result is window-synchronous SGD: accuracy contract, not bit parity
@@ -448,6 +471,8 @@ def run_workload(name, a, env, steps, warmup, main_line):
     elapsed = time.perf_counter() - t0
     ev_ms = ev.elapsed_ms(e0, e1)
     launches = tr.counter(1) - launches0
+    if main_line and rank == 0 and a.dump_outputs:
+        dump_outputs(tr, a.dump_outputs, log)
     per_rank = None
     if dist is not None:
         # every rank's own clock, stream time, algorithmic bytes and instance count of the timed region: the line reports the MAX clock
@@ -462,7 +487,7 @@ def run_workload(name, a, env, steps, warmup, main_line):
     # of launches are in flight (the launch call blocks when the queue is full, so both read ~ms_per_step).  Here a short prefix of the pass
     # (at most 256 launches: nothing can push back) is enqueued onto an idle stream and only the host side is timed.
     host_enq = None
-    if world == 1 and not exchanging and name in ("basicmf", "pairwise") and not os.environ.get("SVDF_BENCH_PMC_CHILD"):   # (not in the --pmc children: their launches are counted)
+    if a.full and world == 1 and not exchanging and name in ("basicmf", "pairwise") and not os.environ.get("SVDF_BENCH_PMC_CHILD"):   # (not in the --pmc children: their launches are counted)
         m = min(n, 4_000_000)
         tr_main, tr = tr, make_trainer(sa, name, a, factor, local_rank, extra=contrib)   # a trainer of its own: the measured model is not trained further
         tr.set_knob("use_graph", a.use_graph)
@@ -492,7 +517,7 @@ def run_workload(name, a, env, steps, warmup, main_line):
 
     # ---- one more pass with a HIP event after every phase (outside the timed region): stream time per phase of the exchange
     phase_ms = None
-    if exchanging and (name in ("basicmf", "pairwise") or minibatch):
+    if a.full and exchanging and (name in ("basicmf", "pairwise") or minibatch):
         marks = []
 
         def mark(phase):
@@ -530,7 +555,9 @@ def run_workload(name, a, env, steps, warmup, main_line):
         acc = torch.tensor(vals, dtype=torch.float64, device="cuda")
         dist.all_reduce(acc)
         return [float(x) for x in acc.tolist()]
-    if name == "basicmf":
+    if not a.full:
+        pass   # a check of the trained model, not part of the timed path
+    elif name == "basicmf":
         tu, ti, tl = test
         mine = (tu % world) == rank
         pred = tr.predict_batch(sa.CSRData.from_triples(tu[mine], ti[mine], tl[mine]))
@@ -580,7 +607,7 @@ def run_workload(name, a, env, steps, warmup, main_line):
 
     # ---- the dependency (DAG) bound of exact sequential semantics: levels x latency of ONE unit launched alone
     dag = None
-    if rank == 0 and world == 1 and name in ("svdpp", "neighbourhood", "pairwise"):
+    if a.full and rank == 0 and world == 1 and name in ("svdpp", "neighbourhood", "pairwise"):
         if name == "svdpp":
             one = tr.dataset_from_blocks(train.slice(0, 1))
         elif name == "pairwise":
@@ -1047,13 +1074,13 @@ def main():
     ap.add_argument("--knob", action="append", default=[], help="extra tuning knob name=value (svdf_set_knob), repeatable")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pmc", choices=["auto", "all", "off"], default="auto", nargs="?", const="all",
-                    help="N = 1: measure roofline.traffic in this run with two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over one pass of the workload in "
+                    help="--full, N = 1: measure roofline.traffic in this run with two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over one pass of the workload in "
                          "a child process.  auto (default): the MAIN workload, capped at --pmc-cap seconds (a pass that does not fit quotes the committed "
                          "profiles/hbm_traffic.json and says so); all: the secondary workloads too, no cap; off: quote the committed file")
     ap.add_argument("--pmc-cap", type=float, default=150.0, help="--pmc auto: seconds the in-run counter passes may take in total")
     ap.add_argument("--no-auto-schedule", action="store_true", help="N>1, --exchange auto: keep the stratified ring as the main line whatever the preflight measured")
     ap.add_argument("--no-preflight", action="store_true", help="N>1: skip the checked all_reduce / ring hand-over before the run")
-    ap.add_argument("--preflight-timeout", type=float, default=150.0, help="N>1: watchdog of rendezvous + preflight (seconds); on expiry the rank re-executes one ladder rung lower")
+    ap.add_argument("--preflight-timeout", type=float, default=150.0, help="N>1: watchdog of rendezvous + preflight (seconds); on expiry the rank starts again one ladder rung lower")
     ap.add_argument("--run-timeout", type=float, default=900.0, help="N>1: watchdog of the main workload (seconds)")
     ap.add_argument("--secondary-timeout", type=float, default=420.0, help="N>1: watchdog of each secondary (seconds); on expiry the contract line is printed without it")
     ap.add_argument("--data-seed", type=int, default=0, help="added to the generator seed of every synthetic stream (0 = the streams of SURVEY 8d2 / earlier rounds)")
@@ -1076,7 +1103,17 @@ def main():
     ap.add_argument("--use-graph", type=int, default=0, help="replay each resident dataset's pass as a captured hipGraph (0 = plain launches)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="debug: run the item-delta exchange path even with one rank (exercises the N>1 code on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the timed passes of the main line: the in-run PMC passes (--pmc), the CPU baseline and in-run parity, "
+                         "the host-enqueue, phase and DAG-bound figures, held-out quality and the sequential reference, and the secondary workloads "
+                         "(--secondary, window step, f3, orders; N>1: --multi-secondary).  Without it a run sets up, warms up, times the passes, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes: the main line's trained model (rank 0's copy) as DIR/<parameter>.npy, float32, at most "
+                         "%d MB in all (larger parameters as a fixed sample of rows)" % (DUMP_BYTES // 10 ** 6))
     a = ap.parse_args()
+    if a.secondary not in ("auto", "") and not a.full:
+        ap.error("--secondary %s needs --full" % a.secondary)
     if not a.factor and a.workload == "basicmf":
         a.factor = 64
 
@@ -1105,7 +1142,7 @@ def main():
               "neighbourhood": "training instances/sec (SGD updates/s), neighbourhood model k=%d" % (a.factor or 128)}[a.workload]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL across processes needs it on this driver
     a.pmc_results = {}
-    if a.pmc != "off" and world == 1 and not a.force_exchange:
+    if a.full and a.pmc != "off" and world == 1 and not a.force_exchange:
         # before this process opens the device, so that the counted child is alone on the GPU (the same commands as tools/profile_round.sh).
         # auto: the main workload only, under a 150 s cap (a pass that does not fit falls back to the committed profiles/hbm_traffic.json);
         # the children read this process's synthetic stream from /dev/shm instead of drawing it again
@@ -1141,10 +1178,12 @@ def main():
     schedule_choice = None
 
     def esc(reason):
+        if wd is not None:
+            wd.disarm()   # this process only waits for the next rung from here on
         escalate(reason, rank, world, attempt, metric)
     if world > 1:
-        # ---- the N > 1 ladder: rendezvous + preflight under a watchdog; a rung that fails or hangs is left through
-        # os.execv, so ONE driver command always ends in a JSON line
+        # ---- the N > 1 ladder: rendezvous + preflight under a watchdog; a rung that fails or hangs hands over to a
+        # child process one rung lower, so ONE driver command always ends in a JSON line
         wd = Watchdog(log)
         requested = a.exchange
         if attempt >= 1 and a.exchange in ("auto", "stratified"):
@@ -1255,7 +1294,7 @@ def main():
         out["secondary"] = secondary
     sec = a.secondary
     if sec == "auto":
-        sec = "pairwise,svdpp,neighbourhood" if (a.workload == "basicmf" and world == 1 and a.ratings == 100_000_000) else ""
+        sec = "pairwise,svdpp,neighbourhood" if (a.full and a.workload == "basicmf" and world == 1 and a.ratings == 100_000_000) else ""
     if wd is not None:
         wd.arm(a.secondary_timeout, "secondary workloads", finish_now)
     for name in [s for s in sec.split(",") if s]:
@@ -1294,7 +1333,7 @@ def main():
     # ---- N > 1, ratings: the other exchange designs on the SAME data in the SAME driver command
     if a.no_multi_secondary:
         a.multi_secondary = "none"
-    if world > 1 and a.workload == "basicmf" and a.multi_secondary != "none":
+    if a.full and world > 1 and a.workload == "basicmf" and a.multi_secondary != "none":
         import argparse as _ap
         main_step = (main_res or {}).get("exchange", {}).get("step") if rank == 0 else None
         # (1) north_star's step: RCCL all-reduce of the per-item sums every window (window-minibatch step), when the main line was the ring

@@ -1,22 +1,27 @@
 """bench.py --gpus N: what one driver command needs around the measured passes -- the watchdog, the rendezvous ladder
-(every rung a fresh process image of the same rank), the checked preflight of the transports, the agreement helpers, the schedule choice from
+(every rung a fresh child process of the same rank), the checked preflight of the transports, the agreement helpers, the schedule choice from
 the preflight numbers and the pass model the line is compared with.  No measurement happens here."""
+import ctypes
 import json
 import os
+import signal
+import subprocess
 import sys
+import threading
 import time
 
 import numpy as np
 
 ATTEMPT_ENV, FALLBACK_ENV = "SVDF_BENCH_ATTEMPT", "SVDF_BENCH_FALLBACK_LOG"
-# the ladder of one driver command: every rung is a fresh process image of THIS rank (os.execv keeps the pid, so the
-# torch.distributed.run agent sees nothing) that meets the others again under a new key prefix of the same TCP store
+# the ladder of one driver command: every rung is a fresh child process of THIS rank, which waits for it and exits with its
+# status (the torch.distributed.run agent keeps watching the pid it started), and meets the others again under a new key prefix of the same TCP
+# store.  Not os.execv: the process has opened the GPU by then, and replacing the program of such a process can take the device down.
 LADDER = ["as requested", "exchange = minibatch (RCCL all-reduce only, no point-to-point ring)", "backend = gloo (host-staged exchange), exchange = minibatch"]
 
 
 class Watchdog:
     """One deadline at a time, watched by a daemon thread: when the armed phase does not finish in time the thread dumps every Python
-    stack (faulthandler) and runs the phase's action -- which never returns (os.execv to the next ladder rung, or the JSON line + os._exit).
+    stack (faulthandler) and runs the phase's action -- which never returns (the next ladder rung as a child process, or the JSON line + os._exit).
     A hung RCCL call blocks the main thread inside C; this thread does not need it."""
 
     def __init__(self, log):
@@ -64,16 +69,26 @@ def fallback_log():
         return []
 
 
+_escalating = threading.Lock()
+_prctl = ctypes.CDLL(None).prctl   # looked up here: the child of a threaded process must not import between fork and exec
+
+
+def _die_with_parent():
+    _prctl(1, signal.SIGTERM)   # PR_SET_PDEATHSIG: when the torch.distributed.run agent stops this rank, its rung stops too
+
+
 def escalate(reason, rank, world, attempt, metric="training instances/sec (SGD updates/s), basicMF k=64"):
-    """This rank gives up the current ladder rung: re-execute bench.py one rung lower (the other ranks follow through their own
-    watchdogs / store timeouts), or, below the last rung, print the contract line with value 0 and the reasons -- a record is never lost."""
+    """This rank gives up the current ladder rung: run bench.py one rung lower as a child process and exit with its status (the other ranks
+    follow through their own watchdogs / store timeouts), or, below the last rung, print the contract line with value 0 and the reasons -- a
+    record is never lost.  Never returns; a second caller (the watchdog firing while the main thread is already here) waits for the first."""
+    if not _escalating.acquire(blocking=False):
+        threading.Event().wait()
     reasons = fallback_log() + [{"attempt": attempt, "rung": LADDER[min(attempt, len(LADDER) - 1)], "rank": rank, "reason": str(reason)[:400]}]
     print("[bench] rank %d attempt %d failed: %s" % (rank, attempt, reason), file=sys.stderr, flush=True)
     if attempt + 1 < len(LADDER):
-        os.environ[ATTEMPT_ENV] = str(attempt + 1)
-        os.environ[FALLBACK_ENV] = json.dumps(reasons)
+        env = dict(os.environ, **{ATTEMPT_ENV: str(attempt + 1), FALLBACK_ENV: json.dumps(reasons)})
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable] + sys.argv)
+        os._exit(subprocess.call([sys.executable] + sys.argv, env=env, preexec_fn=_die_with_parent))
     if rank == 0:
         from benchlib.contract import compact_line
         line, _ = compact_line({"metric": metric, "value": 0.0, "unit": "instances/s", "n_gpus": world, "steps": 0, "warmup": 0, "ms_per_step": None,
@@ -86,7 +101,7 @@ def escalate(reason, rank, world, attempt, metric="training instances/sec (SGD u
 
 def rendezvous(torch, rank, world, local_rank, attempt, share_gpu):
     """(dist, key-value store, backend): the process group of this ladder rung.  Under torch.distributed.run the agent hosts the TCP store
-    (workers are clients), so a re-executed rank can meet the others again: every rung uses its own key prefix."""
+    (workers are clients), so a rank started again one rung lower can meet the others again: every rung uses its own key prefix."""
     import datetime
     import torch.distributed as dist
     host, port = os.environ.setdefault("MASTER_ADDR", "127.0.0.1"), int(os.environ.setdefault("MASTER_PORT", "29533"))

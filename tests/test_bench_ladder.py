@@ -1,5 +1,5 @@
 """bench.py --gpus N must always end in ONE JSON line: rendezvous + preflight run under a watchdog, and a rung that
-fails or hangs is left through os.execv to the next one (RCCL ring -> RCCL all-reduce only -> gloo).  Here: the ladder itself on the CPU
+fails or hangs hands over to a child process one rung lower (RCCL ring -> RCCL all-reduce only -> gloo).  Here: the ladder itself on the CPU
 with two gloo processes under torch.distributed.run -- an injected failure and an injected hang on one rank both end one rung lower on
 every rank, with the reasons in the line; plus the model figures the N > 1 line carries."""
 import json
@@ -52,7 +52,7 @@ def test_a_failing_rank_takes_every_rank_one_rung_down():
 def test_a_hanging_rank_is_left_by_the_watchdog():
     line, err = _run("hang")
     assert line["rung"] == 1 and line["sum"] == 3.0
-    assert "WATCHDOG" in err   # the hanging rank's stacks were dumped before it re-executed
+    assert "WATCHDOG" in err   # the hanging rank's stacks were dumped before it handed over to the next rung
 
 
 def test_watchdog_fires_only_when_armed_and_late():

@@ -23,7 +23,7 @@ def _bench(args, extra_env=None, timeout=1500):
     for k in ("SVDF_BENCH_ATTEMPT", "SVDF_BENCH_FALLBACK_LOG", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     env.update(extra_env or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

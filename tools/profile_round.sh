@@ -8,9 +8,9 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.stderr.log
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.stderr.log
 tail -1 $OUT/bench.json | cut -c1-300
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --no-cpu-baseline --pmc off --no-orders --svdpp-users 40000 > $OUT/kt_bench.json 2> $OUT/kt.stderr.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --full --no-cpu-baseline --pmc off --no-orders --svdpp-users 40000 > $OUT/kt_bench.json 2> $OUT/kt.stderr.log
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/kt
 head -16 $OUT/kernel_stats.csv | cut -c1-200
