@@ -6,6 +6,9 @@ seeded data, trains both engines the same way and compares every parameter and t
 included).  Prints one JSON line; exits non-zero on the first mismatch with the configuration.
 
     python tests/fuzz_parity.py --iters 300 --seed 1
+    python tests/fuzz_parity.py --forms --iters 150 --seed 201     # the exact schedule forms (draw_forms)
+
+The JSON line carries a histogram of the resident data sets' kinds (ds.kind).
 """
 import argparse
 import json
@@ -143,7 +146,72 @@ def draw(rng, tmp, wide=False, big=False):
     return fmt, active, [(a, str(b)) for a, b in conf.items()] + extra, data, plan
 
 
-def run(make, fmt, active, conf, data, plan, is_hip):
+def draw_forms(rng, tmp=None, wide=False, big=False):
+    """the --forms stratum: plain triples (or user-grouped rank pairs) in a resident data set with the route knobs of one exact schedule form --
+    runs of an item's ratings (kind 10), hot rows walked as units (9), plain levels (0), user-run units of rank pairs (11) -- and widths / links
+    that form admits; every decay (rows, biases, the learning rate's) drawn independently for users and items"""
+    form = str(rng.choice(["runs", "runs", "runs", "pivot", "pivot", "pivot", "plain", "plain", "pairs", "pairs"]))
+    k_any = [1, 3, 4, 7, 8, 12, 16, 31, 32, 33, 64, 65, 100, 128, 130, 200, 256]
+    knobs = {}
+    conf = dict(num_global=0, learning_rate=float(rng.choice([0.005, 0.01, 0.02])), wd_user=float(rng.choice([0.0, 0.00005, 0.004, 0.02])),
+                wd_item=float(rng.choice([0.0, 0.00002, 0.004, 0.03])), wd_user_bias=float(rng.choice([0.0, 0.001, 0.01])),
+                wd_item_bias=float(rng.choice([0.0, 0.003, 0.02])), decay_learning_rate=int(rng.integers(0, 2)), decay_rate=float(rng.choice([0.9, 0.7])))
+    seed = int(rng.integers(0, 1 << 30))
+    if form == "runs":   # the contract configuration: linear link, reg 0, user bias, k 64 / 128
+        active, k = 0, int(rng.choice([64, 128]))
+        knobs.update(runs_exec=1, pivot_exec=0, runs_min_rows=0, runs_len=int(rng.integers(2, 8)), runs_sets=int(rng.integers(1, 3)),
+                     runs_block=int(rng.choice([64, 128, 256])))
+    elif form == "pivot":   # any link, k <= 256, reg 0, user bias
+        active, k = int(rng.choice([0, 0, 1, 2, 3, 5, 6, 7])), int(rng.choice(k_any))
+        knobs.update(pivot_exec=1, runs_exec=int(rng.integers(0, 2)), pivot_min=int(rng.choice([2, 16, 64])), pivot_run=int(rng.choice([2, 8, 64, 256])))
+    elif form == "plain":
+        active, k = int(rng.choice([0, 0, 1, 3, 5])), int(rng.choice(k_any))
+        knobs.update(runs_exec=0, pivot_exec=0, chain_width=int(rng.choice([0, 4, 128])))
+        conf["reg_method"] = int(rng.choice([0, 0, 1, 3]))
+    else:   # rank pairs in the generator's user-grouped order: reg_method <= 3, user bias on or off, k <= 256
+        active, k = int(rng.choice([3, 3, 0, 5])), int(rng.choice(k_any))
+        conf.update(reg_method=int(rng.choice([0, 1, 2, 3])), no_user_bias=int(rng.integers(0, 2)))
+        if conf["reg_method"] == 2:   # a bound on the squared row norm
+            conf.update(wd_user=float(rng.choice([0.0005, 0.002, 4.0])), wd_item=float(rng.choice([0.0003, 0.003, 4.0])))
+        knobs.update(pair_units=1, pair_unit_cap=int(rng.choice([1, 5, 16, 24, 64])))
+    conf.update(num_factor=k, active_type=active)
+    conf["base_score"] = float(rng.choice([0.3, 0.6])) if active in EXPF else float(rng.choice([-0.5, 0.4, 1.7, 3.0]))
+    if form == "pairs":
+        nu, ni, per = int(rng.integers(5, 200)), int(rng.integers(4, 400)), int(rng.integers(2, 60))
+        g = np.random.default_rng(seed)
+        pu = np.repeat(g.permutation(nu).astype(np.uint32), per)
+        if g.integers(0, 3) == 0:
+            cut = g.integers(0, len(pu), max(1, len(pu) // 50))
+            pu[cut] = g.integers(0, nu, len(cut)).astype(np.uint32)
+        pp = g.integers(0, ni, len(pu)).astype(np.uint32)
+        pq = ((pp + 1 + g.integers(0, ni - 1, len(pu))) % ni).astype(np.uint32)
+        data = dict(pairs=(pu, pp, pq))
+    else:
+        if form == "pivot":   # one side of at most 30 rows: its hottest row has >= n / 30 >= 64 ratings, a hot row whatever pivot_min (the
+            # builder may still keep plain levels when its cost estimate finds the units no cheaper: svdf_pivot.cpp)
+            hot, cold, n = int(rng.integers(2, 31)), int(rng.integers(20, 500)), int(rng.integers(1920, 4000))
+            hot_items = bool(rng.integers(0, 2))
+            nu, ni = (cold, hot) if hot_items else (hot, cold)
+            a, b, r = cases.planted_triples(n, cold, hot, seed, zipf=True)
+            u, i = (a, b) if hot_items else (b, a)
+        else:
+            nu, ni, n = int(rng.integers(8, 400)), int(rng.integers(6, 200)), int(rng.integers(50, 3000))
+            u, i, r = cases.planted_triples(n, nu, ni, seed, zipf=bool(rng.integers(0, 2)))
+            if rng.integers(0, 3) == 0:   # the same (user, item) twice in a row, the same user on consecutive ratings
+                u[1::7] = u[0::7][:len(u[1::7])]
+                i[1::7] = i[0::7][:len(i[1::7])]
+        if active != 0:
+            r = (r > 3).astype(np.float32)
+        else:
+            r = (r + np.random.default_rng(seed + 1).uniform(-0.5, 0.5, len(r)) - 2.25).astype(np.float32)
+        data = dict(train=sa.CSRData.from_triples(u, i, r))
+    conf.update(num_user=nu, num_item=ni)
+    plan = dict(rounds=int(rng.integers(1, 4)), chunk=0, window=0, resident=True, knobs=knobs, single=False, peek=False, reload=False,
+                extend=0, form=form)
+    return 0, active, [(a_, str(b_)) for a_, b_ in conf.items()], data, plan
+
+
+def run(make, fmt, active, conf, data, plan, is_hip, kinds=None):
     if "pairs" in data:   # the same instances either as three columns (HIP engine) or as CSR rows (everything else)
         pu, pp, pq = data["pairs"]
         csr = sa.pairs_as_csr(pu, pp, pq)
@@ -178,7 +246,10 @@ def run(make, fmt, active, conf, data, plan, is_hip):
                     if plan["peek"] and j % 37 == 5:
                         peeks.append(t.predict_csr(*d.row((j * 7) % d.num_row)))
             elif is_hip and plan["resident"]:
-                ds = ds or (t.dataset_from_pairs(*data["pairs"]) if "pairs" in data else t.dataset_from_csr(d))
+                if ds is None:
+                    ds = t.dataset_from_pairs(*data["pairs"]) if "pairs" in data else t.dataset_from_csr(d)
+                    if kinds is not None:
+                        kinds.append(ds.kind)
                 t.train_dataset(ds)
             elif plan["chunk"]:
                 for st in range(0, d.num_row, plan["chunk"]):
@@ -187,7 +258,10 @@ def run(make, fmt, active, conf, data, plan, is_hip):
                 t.update_batch(d)
         else:
             if is_hip and plan["resident"] and not plan["peek"]:
-                ds = ds or t.dataset_from_blocks(data["train_blocks"])
+                if ds is None:
+                    ds = t.dataset_from_blocks(data["train_blocks"])
+                    if kinds is not None:
+                        kinds.append(ds.kind)
                 t.train_dataset(ds)
             else:
                 for j, b in enumerate(data["train_blocks"]):
@@ -230,14 +304,19 @@ def main(argv=None):
     ap.add_argument("--only", type=int, default=-1, help="run only this iteration (the generator is advanced up to it)")
     ap.add_argument("--reference", action="store_true", help="compare the oracle port with the compiled reference instead of the GPU")
     ap.add_argument("--trace", default="", help="file that always holds the configuration being run (to locate a crash)")
+    ap.add_argument("--forms", action="store_true", help="the schedule-form stratum (draw_forms): runs, hot-row units, plain levels, pair units")
     a = ap.parse_args(argv)
     rng = np.random.default_rng(a.seed)
     stats = dict(iters=0, exact=0, tolerance=0, skipped=0)
+    kinds = []   # ds.kind of every resident data set the engine built
+    forms = {}
     for it in range(a.iters):
         with tempfile.TemporaryDirectory() as tmp:
-            fmt, active, conf, data, plan = draw(rng, tmp, a.wide, a.big)
+            fmt, active, conf, data, plan = (draw_forms if a.forms else draw)(rng, tmp, a.wide, a.big)
             if a.only >= 0 and it != a.only:
                 continue
+            if a.forms:
+                forms[plan["form"]] = forms.get(plan["form"], 0) + 1
             if a.trace:
                 with open(a.trace, "w") as f:
                     f.write("iteration %d format %d active %d\n%s\n%s\n%s\n" % (it, fmt, active, conf, plan,
@@ -254,7 +333,7 @@ def main(argv=None):
                 continue
             else:
                 try:
-                    hv, hp = run(lambda f, x, e=0: sa.Trainer(f, x, e), fmt, active, conf, data, plan, True)
+                    hv, hp = run(lambda f, x, e=0: sa.Trainer(f, x, e), fmt, active, conf, data, plan, True, kinds)
                 except sa.SvdfError as e:
                     print("iteration %d: engine refused what the oracle ran: %s\n%s %s" % (it, e, conf, plan), file=sys.stderr)
                     sys.exit(1)
@@ -272,6 +351,9 @@ def main(argv=None):
                 sys.exit(1)
             stats["iters"] += 1
             stats["tolerance" if tol else "exact"] += 1
+    stats["kinds"] = {str(x): kinds.count(x) for x in sorted(set(kinds))}
+    if a.forms:
+        stats["forms"] = forms
     print(json.dumps(stats))
     return stats
 

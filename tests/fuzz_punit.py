@@ -1,6 +1,6 @@
 """(not collected by pytest) Randomised differential run of the user-run units of rank pairs (svdf_punit.cpp, k_pair_units) against the level-by-level pass
 of the same engine (knob pair_units = 0: k_fewrow_slots / k_fused, itself bit-exact against the oracle): random users / items / pairs per user, widths
-1 .. 256, links, decays, user bias on / off, unit caps 1 .. 64, partially grouped streams; every parameter and every prediction compared bit for bit.
+1 .. 256, links, per-side row / bias decays and decayed learning rates, user bias on / off, unit caps 1 .. 64, partially grouped streams; every parameter and every prediction compared bit for bit.
 usage: python tests/fuzz_punit.py [--iters N] [--seed S]"""
 import argparse
 import json
@@ -37,8 +37,16 @@ def one(rng, case):
     reg = int(rng.choice([0, 0, 0, 1, 2, 3]))
     if reg:
         extra.append(("reg_method", str(reg)))
-    if reg == 2:
-        extra += [("wd_item", "4.0"), ("wd_user", "4.0")]
+    # the two sides' decays drawn apart: a walker that uses one side's decay for the other must show
+    if reg == 2:   # project(): a bound on the row's squared norm
+        wu, wi = rng.choice([4.0, 0.002, 0.0005], size=2, replace=False)
+    else:
+        wu, wi = rng.choice([0.0, 0.0005, 0.004, 0.02, 0.05], size=2, replace=False)
+    extra += [("wd_user", "%g" % wu), ("wd_item", "%g" % wi), ("wd_item_bias", "%g" % rng.choice([0.0, 0.003, 0.02]))]
+    if ("no_user_bias", "0") in extra:
+        extra.append(("wd_user_bias", "%g" % rng.choice([0.0, 0.001, 0.03])))
+    if rng.integers(0, 2) == 0:
+        extra += [("learning_rate", "%g" % rng.choice([0.01, 0.02])), ("decay_learning_rate", "1"), ("decay_rate", "%g" % rng.choice([0.9, 0.7]))]
     cap = int(rng.choice([1, 2, 5, 16, 16, 24, 64]))
     passes = int(rng.integers(1, 3))
     conf = cases.conf_with(cases.PAIR_CONF, num_user=nu, num_item=ni, num_factor=k) + extra
@@ -53,7 +61,8 @@ def one(rng, case):
         t.set_knob("pair_units", units)
         t.set_knob("pair_unit_cap", cap)
         ds = t.dataset_from_pairs(u, p, q)
-        for _ in range(passes):
+        for r in range(passes):
+            t.set_round(r)
             t.train_dataset(ds)
         pr = t.predict_dataset(ds)
         res.append((ds.kind, {nm: (None if t.view(nm) is None else t.view(nm).copy()) for nm in NAMES}, pr.copy()))

@@ -17,6 +17,16 @@ def test_random_configurations_match_the_oracle(seed):
     assert stats["iters"] == 250 and stats["exact"] > 50
 
 
+@pytest.mark.parametrize("seed", [201, 202])
+def test_random_schedule_form_configurations_match_the_oracle(seed):
+    """the --forms stratum: resident triples / grouped pairs routed to runs (kind 10), hot-row units (9), plain levels (0) and pair units (11),
+    with every decay drawn for users and items independently"""
+    stats = fuzz_parity.main(["--forms", "--iters", "150", "--seed", str(seed)])
+    kinds = stats["kinds"]
+    assert stats["iters"] == 150 and stats["exact"] == 150, stats
+    assert kinds.get("10", 0) >= 30 and kinds.get("9", 0) >= 30 and kinds.get("0", 0) >= 10, stats
+
+
 def test_random_ranker_streams_match_the_cpu_ranker(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["fuzz_ranker.py", "--iters", "60", "--seed", "5"])
     assert fuzz_ranker.main() == 0
