@@ -52,7 +52,9 @@ void svdf_destroy(svdf_trainer *t);
 
 /* ISVDTrainer::set_param (apex_svd.h:42; keys: apex_svd_base.h:126-136, apex_svd_model.h:350-368
  * and :456-476, ParameterSet prefixes up:/ip:/uip:/gp: apex_svd_base.h:48-67).  Unknown keys are
- * ignored, model-shape keys are ignored once the model is allocated. */
+ * ignored, model-shape keys are ignored once the model is allocated.  Extension keys (ignored by the reference): amd:gpus, amd:exchange,
+ * amd:step, amd:contrib, amd:window, amd:window_per_target(_max), amd:relax_* (see svdf_set_knob below) and amd:shared_user_from = B
+ * (shared user rows in the one-GPU window step). */
 int svdf_set_param(svdf_trainer *t, const char *name, const char *val);
 /* apex_random::seed (apex-tensor/apex_random.h:42-44) -> srand; process-global like the reference. */
 void svdf_seed(unsigned seed);
@@ -312,7 +314,7 @@ int svdf_synchronize(svdf_trainer *t);
  * more than 10 x slower than the streaming model), 27 / 28 the last noted data set's dag bound / stream model in microseconds,
  * 29 passes over rank pairs walked as user-run units */
 int64_t svdf_counter(svdf_trainer *t, int what);
-/* Tuning knobs (not part of the reference surface).  None changes a result bit except the five marked (*), which move the windows of the
+/* Tuning knobs (not part of the reference surface).  None changes a result bit except the six marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
  *   staging / launches
  *     stage_window        2^21   instances staged by svdf_update_* before an automatic flush (also set by the config key amd:window)
@@ -341,13 +343,17 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *   the opt-in window step (amd:step = minibatch / auto; N-rank handles)
  *     wunit_fast 2, wunit_inplace 1, wunit_defer_fb 1, window_slots 1, window_groups 0      kernel forms, same bits
  *     window_per_target (*) 24, window_per_target_fb (*) 16     updates a shared row / feedback row meets per window on average
+ *     window_per_target_shared (*) 12                           ... a shared user row (amd:shared_user_from; profiles/r07_sidefeat_window.md)
  *     window_per_target_max (*) 128                             ... and at most (N-rank steps, rank pairs, user units; plain ratings on one GPU with window_hot_sub = 0)
  *     window_hot_sub (*) 128, window_hot_max (*) 2048           one-GPU sequences of plain ratings (round 6): an item with more than window_hot_sub slots in a window
  *                                                               moves in ordered sub-steps of that many (k_window_apply; 0 = off) and meets at most window_hot_max
  *                                                               updates per window -- the hottest item no longer sets the number of windows
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
- * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results. */
+ * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
+ * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
+ * per row, walked exactly), ids >= B are shared attribute rows (any number per row, read as of the window start and moved once per window
+ * like item rows).  1 <= B <= num_user; refused with amd:gpus > 1, amd:contrib = bf16 and in svdf_dataset_window_from_csr. */
 int svdf_set_knob(svdf_trainer *t, const char *name, long value);
 
 /* ---- evaluation: RMSEEvaluator of svd_feature_infer.cpp:38-56,243-277 over a resident data set.  Predictions

@@ -112,7 +112,11 @@ void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:
     if (save_async_.active) save_model_end();   // (the asynchronous writer reads mp_ live)
     if (trainer_ready_ && !host_only_) flush();   // staged instances were issued under the old parameters
     // N GPUs behind one handle (svdf_multi.cpp): extension keys, ignored by the reference like any unknown key
-    if (!strcmp(name, "amd:gpus")) { check(!multi_ && !space_allocated_, "amd:gpus must be set before the model is created"); gpus_ = std::max(1, atoi(val)); }
+    if (!strcmp(name, "amd:gpus")) {
+        check(!multi_ && !space_allocated_, "amd:gpus must be set before the model is created");
+        check(atoi(val) <= 1 || !shared_user(), "amd:shared_user_from: one GPU only (amd:gpus = 1); the N-rank exchange has no place for user rows");
+        gpus_ = std::max(1, atoi(val));
+    }
     else if (!is_peer_) param_log_.emplace_back(name, val);
     if (!strcmp(name, "amd:delta_half")) delta_half_ = atoi(val) != 0;
     if (!strcmp(name, "amd:exchange")) {
@@ -155,6 +159,13 @@ void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:
     if (!strcmp(name, "amd:relax_feedback")) relax_feedback_ = atoi(val) != 0;
     if (!strcmp(name, "amd:relax_user_from")) relax_user_from_ = (unsigned)strtoul(val, nullptr, 10);
     if (!strcmp(name, "amd:relax_item_from")) relax_item_from_ = (unsigned)strtoul(val, nullptr, 10);
+    if (!strcmp(name, "amd:shared_user_from")) {   // window step: user ids >= B are shared attribute rows (svdf_wunit.cpp)
+        const long b = atol(val);
+        check(b >= 1 && b < 0xFFFFFFFFL, "amd:shared_user_from must be in 1 .. num_user");
+        check(gpus_ == 1 && !multi_, "amd:shared_user_from: one GPU only (amd:gpus = 1); the N-rank exchange has no place for user rows");
+        check(!space_allocated_ || b <= (long)mp_.num_user, "amd:shared_user_from must be in 1 .. num_user");   // else checked by init_trainer
+        shared_user_from_ = (unsigned)b;
+    }
     pair_sampler_.set_param(name, val);   // the reference hands every config pair to the data iterator too (svd_feature.cpp:128-143)
     config_set_train_param(tp_, name, val);
     u_param_.set_param(name, val);
@@ -245,6 +256,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "wunit_inplace")) { wunit_inplace_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_defer_fb")) { wunit_defer_fb_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_fast")) { check(value >= 0 && value <= 2, "wunit_fast must be 0, 1 or 2"); wunit_fast_ = (int)value; return 0; }
+    if (!strcmp(name, "window_per_target_shared")) { check(value >= 1, "window_per_target_shared must be positive"); wseq_per_target_shared_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_fb")) { check(value >= 1, "window_per_target_fb must be positive"); wseq_per_target_fb_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_sub")) { check(value >= 0 && value <= 4096, "window_hot_sub must be in 0 .. 4096"); wseq_hot_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_max")) { check(value >= 1, "window_hot_max must be positive"); wseq_hot_max_ = (int)value; return 0; }

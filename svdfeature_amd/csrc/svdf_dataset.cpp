@@ -428,12 +428,12 @@ Dataset *Engine::dataset_from_csr(long num_row, const float *row_label, const in
         struct Done { bool &f; ~Done() { f = false; } } done{auto_building_};
         if (num_row > AUTO_PROBE_MIN) {
             validate_csr_pointers(num_row, row_ptr);
-            if (wunit_config_ok() && wunit_rows_ok(0, num_row, row_ptr, feat_index) &&
+            if (wunit_config_ok() && wunit_rows_ok(0, num_row, row_ptr, feat_index, shared_user_for_auto()) &&
                 auto_probe_deep(dataset_from_csr(AUTO_PROBE_ROWS, row_label, row_ptr, feat_index, feat_value), num_row))
                 return auto_step(nullptr, true, [&]() { return wseq_from_csr(num_row, row_label, row_ptr, feat_index, feat_value); });
         }
         Dataset *exact = dataset_from_csr(num_row, row_label, row_ptr, feat_index, feat_value);   // validates the pointers
-        const bool ok = wunit_config_ok() && wunit_rows_ok(0, num_row, row_ptr, feat_index);
+        const bool ok = wunit_config_ok() && wunit_rows_ok(0, num_row, row_ptr, feat_index, shared_user_for_auto());
         return auto_step(exact, ok, [&]() { return wseq_from_csr(num_row, row_label, row_ptr, feat_index, feat_value); });
     }
     const long n = num_row;
@@ -690,6 +690,7 @@ uint64_t Engine::schedule_signature() const {
     mix(feat_user_.num_row()); mix(feat_user_.index.size()); mix(feat_item_.num_row()); mix(feat_item_.index.size());
     mix(user_group()); mix(lazy_decay()); mix((uint64_t)mp_.num_factor); mix(use_fused_); mix(use_simple_units_);
     mix((uint64_t)mtype_.extend_type);
+    if (shared_user()) mix(0x5u + ((uint64_t)shared_user_from_ << 8));   // amd:shared_user_from: the window layout of user entries
     return h;
 }
 void Engine::disown(Dataset *ds) {

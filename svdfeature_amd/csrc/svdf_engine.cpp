@@ -152,6 +152,7 @@ void Engine::init_trainer() {  // apex_svd_base.h:151-173, 499-503
     // the reference indexes children unchecked; validate once here instead
     for (unsigned c : feat_user_.index) check(c < (unsigned)mp_.num_user, "feature_user: child index exceed bound");
     for (unsigned c : feat_item_.index) check(c < (unsigned)mp_.num_item, "feature_item: child index exceed bound");
+    check(!shared_user() || (long)shared_user_from_ <= (long)mp_.num_user, "amd:shared_user_from must be in 1 .. num_user");   // the model's shape is known here
     check(tp_.reg_method >= 0 && tp_.reg_method <= 5, "unknown reg_method");
     check(tp_.reg_global == 0 || tp_.reg_global == 1 || tp_.reg_global == 4 || tp_.reg_global == 5, "unknown global decay method");
     if (mtype_.extend_type != 0 && !user_group())

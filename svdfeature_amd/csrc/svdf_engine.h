@@ -267,6 +267,9 @@ struct Dataset {
     long wu_gslots = 0;           // contribution words of the global biases = global entries
     int wu_estride = 0;           // > 0: every row has wu_estride - 1 global entries and one item entry (no row pointer array)
     bool wu_feedback = false;     // the units carry implicit-feedback lists (user-group trainer)
+    DevBuf<int> wu_uptr, wu_upos;  // shared user entries (amd:shared_user_from): per-row ranges into wu_uent and the private entry's position
+    DevBuf<WinEnt> wu_uent;
+    long wu_nshared = 0;           // > 0: the window has shared user entries; targets [.., + wu_nshared) are user rows B .. num_user - 1
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
     std::vector<Dataset *> wchild;
     // kind 6: a data set of an amd:gpus = N handle (svdf_multi.cpp): mchild[rank][window] lives in that rank's HBM
@@ -489,6 +492,11 @@ class Engine {
     void upload_globals(int stride);
     void download_globals(float *dst);
     unsigned relax_user_from_ = 0xFFFFFFFFu, relax_item_from_ = 0xFFFFFFFFu;
+    // extension key "amd:shared_user_from" = B (one GPU, window step only): user ids >= B are shared attribute rows, moved like item rows
+    unsigned shared_user_from_ = 0xFFFFFFFFu;
+    bool shared_user() const { return shared_user_from_ != 0xFFFFFFFFu; }
+    // what `auto` may hand to the window step as shared ids (wunit_rows_ok): none when their refusals would apply (bf16 contribution rows)
+    unsigned shared_user_for_auto() const { return shared_user() && !contrib_bf16_ ? shared_user_from_ : 0xFFFFFFFFu; }
     PairSampler pair_sampler_;
     RankPrefetch *rank_prefetch_ = nullptr;
     std::vector<Dataset *> datasets_;     // live datasets of this trainer (Dataset::owner back-pointers)
@@ -604,9 +612,10 @@ class Engine {
                      const unsigned *fb_index, const float *fb_value);
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                          const unsigned *fb_index, const float *fb_value) const;
+                          const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr) const;
     void wunit_adopt(Dataset *ds, const WUnitHost &H);
-    void wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) const;
+    void wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
+                             bool shared = false) const;
     void wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                                 const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) const;
     int wseq_build_threads_ = 32;         // knob "wseq_build_threads": host threads building the windows of a one-GPU window sequence (user units)
@@ -624,6 +633,8 @@ class Engine {
     bool wunit_inplace_build_ = false;    // set while wseq_from_csr / _from_blocks build their windows
     int wunit_fast_ = 2;                  // knob "wunit_fast": 0 = the general lane-group kernel for every shape, 1 = + the slot kernel, 2 = + one wave per unit (A/B and tests)
     int wseq_per_target_fb_ = 16;         // knob "window_per_target_fb": the same for feedback rows (instance-sized updates pushed by whole blocks)
+    int wseq_per_target_shared_ = 12;     // knob "window_per_target_shared": the same for shared user rows (amd:shared_user_from; calibrated on the
+                                          // SURVEY 8(d2) variant, 3 seeds: 24 -> |dRMSE| 1.3e-4, 16 -> 1.1e-4, 12 -> 6.1e-5; profiles/r07_sidefeat_window.md)
     int wseq_per_target_max_ = 128;       // knob "window_per_target_max": the MOST updates any shared row may meet per window (binds on skewed data only)
     // ordered sub-steps for hot items of a one-GPU window sequence of plain ratings (svdf_k_window.hip: k_window_apply; round 6)
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)

@@ -45,7 +45,7 @@ void validate_csr_pointers(long num_row, const int64_t *row_ptr);
 void validate_block_pointers(long num_block, const int64_t *fb_ptr, const int64_t *block_row_ptr);
 // the shapes the user-unit window step takes (svdf_wunit.cpp's builders fail on anything else): one user entry per row, one user per
 // block / START..END span, no id twice in a row's global or item entries, no feedback id twice in a block.  Pointers must be valid.
-bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index);
+bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index, unsigned shared_from = 0xFFFFFFFFu);
 bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const int64_t *block_row_ptr,
                      const int64_t *row_ptr, const unsigned *feat_index);
 

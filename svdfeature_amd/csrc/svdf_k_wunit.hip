@@ -25,6 +25,8 @@ namespace svdf {
 // FB: the trainer is SVDPPFeature (user-group format): a segment prepares tmp_ufeedback from its feedback list (:523-538), every row
 // goes through the update_svdpp hook (:512-520), the segment's end is update_ufeedback (:539-554) against the window-start rows.
 // General form: any width <= 256, any row shape (one user entry per row), every link and regulariser of the base solver.
+// Shared user rows (S.uptr, amd:shared_user_from): the row's other user entries are read as of the window start, in entry order around the
+// private one (calc_bias :313-353, prepare_tmp :354-381), and their change goes to a contribution slot like an item row's.
 template <int LPI, bool FB>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     constexpr int IPW = 64 / LPI;
@@ -61,18 +63,25 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             else { e0 = r * S.estride; e1 = e0 + S.estride - 1; e2 = e1 + 1; }
             const float label = S.label[r];
             const float ua = S.uval ? S.uval[r] : 1.0f;
+            int u0 = 0, um = 0, u1 = 0;   // shared user entries: [u0, um) before the private one, [um, u1) after it
+            if (S.uptr) { u0 = S.uptr[r]; um = u0 + S.upos[r]; u1 = S.uptr[r + 1]; }
+            const size_t srow0 = (size_t)P.user_off + S.shared_from;
             // ---- pred (:445-454): calc_bias in double, the hooks' terms where the reference adds them
             double bs = 0.0;
             for (int j = e0; j < e1; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.g_bias[e.idx]); }
             if (ub) {
+                for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * P.bias[srow0 + e.idx]); }
                 bs += (double)(ua * bu);
+                for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * P.bias[srow0 + e.idx]); }
                 bs += (double)(FB ? pp.tmp_bias : 0.0f);
             }
             bs += 0.0;
             for (int j = e1; j < e2; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.bias[P.item_off + e.idx]); }
             double sum = (double)P.base_score + bs;
             float4 tu = FB ? pp.tmp_fb : f4zero();
+            for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
             axpy4(tu, p, ua);
+            for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
             float4 ti = f4zero();
             for (int j = e1; j < e2; j++) { const WinEnt e = S.ent[j]; axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val); }
             sum += (double)group_dot<LPI>(tu, ti, L, k);
@@ -107,6 +116,25 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 } else {
                     store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)e.slot, pitch, L, k, wi);
                     if (L == 0) S.cbias[e.slot] = nbi - bi;
+                }
+            }
+            for (int j = u0; j < u1; j++) {   // shared user rows: update_no_decay + reg_user (:211-249) against the window-start row
+                const WinEnt e = S.uent[j];
+                const float ss = lr * err * e.val;
+                const size_t row = srow0 + e.idx;
+                const float4 w = load_row<LPI>(P.W, row, pitch, L, k);
+                float4 ws = w;
+                axpy4(ws, ti, ss);
+                reg_row<LPI>(P, ws, get_wd(P.u_rng, S.shared_from + e.idx, P.wd_user), false, L);
+                sub4(ws, w);
+                float cb = 0.0f, b = 0.0f;
+                if (ub) { b = P.bias[row]; float nb = b + ss; nb = nb * (1.0f - lr * P.wd_user_bias); cb = nb - b; }
+                if (e.slot < 0) {   // the row's only contribution of this window
+                    store_row<LPI>(P.W, row, pitch, L, k, apply_single(w, ws, false));
+                    if (ub && L == 0) P.bias[row] = apply_single(b, cb, false);
+                } else {
+                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, ws);
+                    if (L == 0) S.cbias[e.slot] = cb;
                 }
             }
             if (FB) pp.update(P, err, ti, ub);
@@ -413,13 +441,13 @@ __global__ __launch_bounds__(256) void k_wunit_fast(const DevParams P, const WUn
 // The global biases' sums (gptr over gcontrib) are taken by the same launch, one thread per global id.
 template <int LPI, bool HALF, bool LOCAL>
 __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float *W, float *bias, float *g_bias, unsigned fb_off, unsigned item_off,
-                                                   int pitch, int k, void *dst) {
+                                                   unsigned user_off, int pitch, int k, void *dst) {
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
     const int L = lane & (LPI - 1);
     const long stride = (long)gridDim.x * (blockDim.x >> 6) * IPW;
     const long first = ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * IPW + lane / LPI;
-    const long T = S.nfb_rows + S.nitem_rows;
+    const long T = S.nfb_rows + S.nitem_rows + (LOCAL ? S.nshared_rows : 0);   // shared user rows: one-GPU windows only (in place)
     // a target is a chain of dependent loads (its slot range, the records or rows of its slots, for deferred feedback rows the segments' deltas) and the
     // kernel is bound by how many such chains the resident waves hold, not by bytes: the next target's slot range is requested one iteration ahead
     // One-GPU windows bring the list of targets that have slots (a window touches a fraction of the rows, and a row's only contribution has been applied by
@@ -476,14 +504,16 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
         } else if (S.contrib_bf16) sum_contrib_slots<LPI, true, (LOCAL ? 4 : 8)>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
         else sum_contrib_slots<LPI, false, (LOCAL ? 4 : 8)>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
         if (LOCAL) {
-            const size_t row = t < S.nfb_rows ? (size_t)fb_off + (size_t)t : (size_t)item_off + (size_t)(t - S.nfb_rows);
+            const long ti = t - S.nfb_rows, ts = ti - S.nitem_rows;
+            const size_t row = t < S.nfb_rows ? (size_t)fb_off + (size_t)t
+                             : ts < 0 ? (size_t)item_off + (size_t)ti : (size_t)user_off + S.shared_from + (size_t)ts;
             if (owns) {
                 float4 *w = reinterpret_cast<float4 *>(W + row * pitch + (size_t)L * 4);
                 float4 c = *w;
                 c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
                 *w = c;
             }
-            if (L == 0) bias[row] = bias[row] + accb;
+            if (L == 0 && (ts < 0 || S.user_bias)) bias[row] = bias[row] + accb;
             continue;
         }
         if (owns) {
@@ -520,6 +550,7 @@ bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedbac
 }
 void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st) {
     if (S.nunits <= 0) return;
+    if (S.uptr) fast = 0;   // rows with shared user entries: the general walk (the fixed shapes have no user section)
     // fast: 0 = the general lane-group kernel, 1 = the slot kernel where it applies, 2 (default) = in addition one WAVE per unit for user-group
     // windows whose launch does not fill the chip anyway (its time is the longest unit's latency: svdf_k_wave.hip, k_wunit_wave)
     if (fast >= 2 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) { launch_wunit_wave(P, S, st); return; }
@@ -547,7 +578,7 @@ void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback
 }
 // dst == nullptr: add the sums to the model in place; else the wire buffer (half: fp16)
 void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int half, hipStream_t st) {
-    const long T = S.nfb_rows + S.nitem_rows;
+    const long T = S.nfb_rows + S.nitem_rows + (dst ? 0 : S.nshared_rows);
     if (T <= 0 && S.nglobal <= 0) return;
     const int lpi = lanes_per_instance(P.k);
     const long ipw = 64 / lpi;
@@ -557,9 +588,9 @@ void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int
     // (many short-lived waves beat one resident set walking several targets each: grid cap 2 048 -> 53.5 us, 4 096 -> 45.8, 16 384 -> 43.8 per SVD++ window)
     if (grid > 16384) grid = 16384;
     if (grid < 1) grid = 1;
-    if (!dst) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.pitch, P.k, (void *)nullptr)); }
-    else if (half) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, true, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.pitch, P.k, dst)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.pitch, P.k, dst)); }
+    if (!dst) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
+    else if (half) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, true, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, dst)); }
+    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, dst)); }
 }
 
 }  // namespace svdf

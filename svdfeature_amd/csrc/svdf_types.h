@@ -258,6 +258,13 @@ struct WUnitSchedule {
     int user_bias;              // 1 unless no_user_bias
     const WinTouched *touched;  // nullptr: every target is visited (wire buffers need the untouched rows' zeros); else [ntouched]
     long ntouched;
+    // shared user rows (amd:shared_user_from = B, one-GPU window sequences only): nullptr uptr = none.  Row r's user entries, in entry
+    // order, are uent[uptr[r] .. uptr[r] + upos[r]), the private user (registers), uent[uptr[r] + upos[r] .. uptr[r + 1]); uent.idx = id - B.
+    // They are targets [nfb_rows + nitem_rows, + nshared_rows) of tptr / touched, model row user_off + shared_from + j.
+    const int *uptr, *upos;
+    const WinEnt *uent;
+    long nshared_rows;
+    unsigned shared_from;
 };
 
 }  // namespace svdf

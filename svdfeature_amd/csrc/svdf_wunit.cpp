@@ -38,8 +38,10 @@ struct WUnitHost {
     std::vector<WinEnt> ent, fbent;
     std::vector<WinFbRec> fbrec;   // deferred feedback scatter (empty: contribution rows)
     std::vector<WinTouched> touched;   // one-GPU windows (inplace builds): the targets that keep slots
+    std::vector<int> uptr, upos;       // shared user entries (amd:shared_user_from), WUnitSchedule::uptr / upos / uent; empty: none in the window
+    std::vector<WinEnt> uent;
     bool has_touched = false;
-    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0;
+    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0;
     int fixed_ng = -2;
     bool unit_uval = true, feedback = false;
 };
@@ -57,6 +59,9 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     S.fbrec = ds->wu_defer_fb ? ds->wu_fbrec.p : nullptr; S.dvec = d_dvec_.p; S.dbias = d_dbias_.p;
     S.user_bias = mp_.no_user_bias ? 0 : 1;
     S.touched = ds->wu_ntouched >= 0 ? ds->wu_touched.p : nullptr; S.ntouched = std::max<long>(ds->wu_ntouched, 0);
+    const bool sh = ds->wu_nshared > 0;
+    S.uptr = sh ? ds->wu_uptr.p : nullptr; S.upos = sh ? ds->wu_upos.p : nullptr; S.uent = sh ? ds->wu_uent.p : nullptr;
+    S.nshared_rows = ds->wu_nshared; S.shared_from = sh ? shared_user_from_ : 0u;
     return S;
 }
 
@@ -71,6 +76,7 @@ void Engine::wunit_check_config(const char *what) const {
           "window data sets: no side tables, relaxed ids, lazy decay or shared latent space");
     check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
+    check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
     (void)what;
 }
 
@@ -86,9 +92,15 @@ void Engine::wunit_build(Dataset *ds, const void *segs_v, size_t nseg, const std
 }
 void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order,
                               long num_src_row, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                              const unsigned *fb_index, const float *fb_value) const {
+                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos) const {
     const HostSeg *segs = static_cast<const HostSeg *>(segs_v);
     const long NU = mp_.num_user, NI = mp_.num_item, NG = mp_.num_global, NF = user_group() ? (long)num_fb_rows() : 0;
+    // shared user rows (priv_pos: the private entry of every source row; the other user entries are ids >= amd:shared_user_from): targets after
+    // the item rows, only when the window holds such an entry -- otherwise the window is laid out exactly as without the key
+    bool has_shared = false;
+    if (priv_pos) for (long r = 0; r < num_src_row && !has_shared; r++) has_shared = row_ptr[3 * r + 2] - row_ptr[3 * r + 1] > 1;
+    const unsigned SB = has_shared ? shared_user_from_ : 0u;
+    const long NS = has_shared ? NU - (long)SB : 0, NT = NF + NI + NS;
     const bool feedback = user_group();
     H.feedback = feedback;
     // ---- units: the segments of one user, in file order; launch order by cost (rows + feedback entries), descending
@@ -170,16 +182,29 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         check(nent < (1L << 30), "window data sets: at most 2^30-1 feature entries per window");
         if (fixed_ng == -2) fixed_ng = (ni == 1) ? ng : -1;
         else if (fixed_ng >= 0 && !(ni == 1 && ng == fixed_ng)) fixed_ng = -1;
+        const int64_t pv = priv_pos ? priv_pos[r] : p1;
         w_label[(size_t)nr] = row_label[r];
-        w_uval[(size_t)nr] = feat_value[p1];
-        if (feat_value[p1] != 1.0f) unit_uval = false;
+        w_uval[(size_t)nr] = feat_value[pv];
+        if (feat_value[pv] != 1.0f) unit_uval = false;
+        if (has_shared) {   // the row's user entries in entry order, the private one by position
+            H.uptr.push_back((int)H.uent.size());
+            for (int64_t j = p1; j < p2; j++) {
+                if (j == pv) H.upos.push_back((int)H.uent.size() - H.uptr.back());
+                else H.uent.push_back(WinEnt{feat_index[j] - SB, feat_value[j], 0, 0});
+            }
+        }
     }
     rptr[(size_t)2 * nrow] = (int)nent;
+    if (has_shared) {
+        H.uptr.push_back((int)H.uent.size());
+        check((long)H.uent.size() < (1L << 30), "window data sets: at most 2^30-1 shared user entries per window");
+    }
     std::vector<WinEnt> &ent = H.ent;
     ent.assign((size_t)nent, WinEnt{0u, 0.0f, 0, 0});
     // ---- slots: counts per target, then file-order assignment
     std::vector<int> &tptr = H.tptr, &gptr = H.gptr;
-    tptr.assign((size_t)(NF + NI) + 1, 0); gptr.assign((size_t)NG + 1, 0);
+    tptr.assign((size_t)NT + 1, 0); gptr.assign((size_t)NG + 1, 0);
+    for (const WinEnt &u : H.uent) tptr[(size_t)(NF + NI + u.idx) + 1]++;
     std::vector<unsigned> seen;   // duplicate check inside a row / a list
     for (long nr = 0; nr < nrow; nr++) {
         const long r = src_of_new[(size_t)nr];
@@ -222,11 +247,11 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     const bool defer_fb = feedback && wunit_defer_fb_ != 0;
     std::vector<unsigned char> single;
     if (inplace) {
-        single.assign((size_t)(NF + NI), 0);
-        for (size_t t = defer_fb ? (size_t)NF : 0; t < (size_t)(NF + NI); t++) if (tptr[t + 1] == 1) { single[t] = 1; tptr[t + 1] = 0; }
+        single.assign((size_t)NT, 0);
+        for (size_t t = defer_fb ? (size_t)NF : 0; t < (size_t)NT; t++) if (tptr[t + 1] == 1) { single[t] = 1; tptr[t + 1] = 0; }
     }
     auto take_slot = [&](std::vector<int> &cur, size_t t) { return (!single.empty() && single[t]) ? -1 : cur[t]++; };
-    for (size_t t = 0; t < (size_t)(NF + NI); t++) tptr[t + 1] += tptr[t];
+    for (size_t t = 0; t < (size_t)NT; t++) tptr[t + 1] += tptr[t];
     for (size_t g = 0; g < (size_t)NG; g++) gptr[g + 1] += gptr[g];
     std::vector<int> tcur(tptr.begin(), tptr.end() - 1), gcur(gptr.begin(), gptr.end() - 1);
     if (defer_fb) H.fbrec.assign((size_t)tptr[(size_t)NF], WinFbRec{0, 0.0f});
@@ -236,6 +261,8 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         const int e0 = rptr[(size_t)2 * nr], e1 = e0 + ng, e2 = rptr[(size_t)2 * nr + 2];
         for (int e = e0; e < e1; e++) ent[(size_t)e].slot = gcur[ent[(size_t)e].idx]++;
         for (int e = e1; e < e2; e++) ent[(size_t)e].slot = take_slot(tcur, (size_t)NF + ent[(size_t)e].idx);
+        if (has_shared)
+            for (int e = H.uptr[(size_t)nr]; e < H.uptr[(size_t)nr + 1]; e++) H.uent[(size_t)e].slot = take_slot(tcur, (size_t)(NF + NI) + H.uent[(size_t)e].idx);
     };
     if (by_row_order) {
         for (long r = 0; r < num_src_row; r++) if (newrow_of_src[(size_t)r] >= 0) row_slots(newrow_of_src[(size_t)r]);
@@ -253,10 +280,11 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     }
     if (inplace) {   // the in-place sums visit only the targets that have slots (a window touches a fraction of the rows; singles keep none)
         H.has_touched = true;
-        for (size_t t = 0; t < (size_t)(NF + NI); t++) if (tptr[t + 1] > tptr[t]) H.touched.push_back(WinTouched{(int)t, tptr[t], tptr[t + 1]});
+        for (size_t t = 0; t < (size_t)NT; t++) if (tptr[t + 1] > tptr[t]) H.touched.push_back(WinTouched{(int)t, tptr[t], tptr[t + 1]});
     }
     for (size_t j = 0; j < nunit; j++) units[j].first = wsegs[(size_t)units[j].seg_begin];   // the first segment travels with the unit record
     H.nrow = nrow; H.nent = nent; H.nfbe = nfbe; H.fixed_ng = fixed_ng; H.unit_uval = unit_uval;
+    H.nshared = NS; H.shared_entries = (long)H.uent.size();
     for (long nr = 0; nr < nrow; nr++) { const int g = rptr[(size_t)2 * nr + 1] - rptr[(size_t)2 * nr]; H.global_entries += g; H.item_entries += rptr[(size_t)2 * nr + 2] - rptr[(size_t)2 * nr] - g; }
     (void)NU;
 }
@@ -296,13 +324,20 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
     ds->wu_defer_fb = !H.fbrec.empty();
     ds->wu_tptr.upload(tptr.data(), tptr.size(), stream_);
     ds->wu_gptr.upload(gptr.data(), gptr.size(), stream_);
+    ds->wu_nshared = H.nshared;
+    if (H.nshared > 0) {
+        ds->wu_uptr.upload(H.uptr.data(), H.uptr.size(), stream_);
+        ds->wu_upos.upload(H.upos.data(), H.upos.size(), stream_);
+        ds->wu_uent.upload(H.uent.data(), H.uent.size(), stream_);
+    }
     HIPCHECK(hipStreamSynchronize(stream_));   // the host columns go out of scope
     ds->sched.level_ptr = {0, nrow};
     ds->sched.max_level_size = nrow;
     // what the reference's step moves -- per row 8k (nu + ni) + 8 (nu_b + ni) + 8 ng + 16 + 8 (ng + nu + ni), per feedback entry 12k + 20
     const long k = mp_.num_factor, nub = mp_.no_user_bias ? 0 : 1;
     const long item_entries = H.item_entries, global_entries = H.global_entries;
-    ds->algorithmic_bytes = nrow * (8 * k + 8 * nub + 16 + 8) + item_entries * (8 * k + 8 + 8) + global_entries * 16 + nfbe * (12 * k + 20);
+    ds->algorithmic_bytes = nrow * (8 * k + 8 * nub + 16 + 8) + item_entries * (8 * k + 8 + 8) + global_entries * 16 + nfbe * (12 * k + 20) +
+                            H.shared_entries * (8 * k + 8 * nub + 8);   // a shared user entry: its row and bias read and written, id + value
 }
 
 // ---- one exchange window of rows of a random-order trainer: any number of global and item entries, exactly one user entry
@@ -311,13 +346,39 @@ void Engine::wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, co
     wunit_host_from_csr(H, wunit_inplace_build_, n, row_label, row_ptr, feat_index, feat_value);
     wunit_adopt(ds, H);
 }
+// shared: the one-GPU window sequence under amd:shared_user_from = B -- a row's user entries are ONE private id < B (the unit's user) and any
+// number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.
 void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
-                                 const float *feat_value) const {
+                                 const float *feat_value, bool shared) const {
     const long NU = mp_.num_user;
+    const unsigned B = shared_user_from_;
     std::vector<int> cnt((size_t)NU, 0);
+    std::vector<int64_t> priv;   // shared mode: the private entry of every row
+    if (shared && shared_user()) priv.resize((size_t)n);
+    std::vector<unsigned> seen;
     for (long r = 0; r < n; r++) {
-        check(row_ptr[3 * r + 2] - row_ptr[3 * r + 1] == 1, "window data sets: every row needs exactly one user entry");
-        const unsigned u = feat_index[row_ptr[3 * r + 1]];
+        const int64_t p1 = row_ptr[3 * r + 1], p2 = row_ptr[3 * r + 2];
+        if (priv.empty()) {
+            if (p2 - p1 != 1 && shared_user())
+                for (int64_t j = p1; j < p2; j++)
+                    check(feat_index[j] < B, "svdf_dataset_window_from_csr: shared user entries (amd:shared_user_from) are for the one-GPU window sequence; "
+                                             "the N-rank exchange has no place for user rows");
+            check(p2 - p1 == 1, "window data sets: every row needs exactly one user entry");
+        } else {
+            int64_t pv = -1;
+            seen.clear();
+            for (int64_t j = p1; j < p2; j++) {
+                const unsigned u = feat_index[j];
+                if (u >= (unsigned)NU) fail("user feature index exceed bound");
+                if (u < B) { check(pv < 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has two"); pv = j; continue; }
+                for (unsigned x : seen) if (x == u) fail("window data sets: a shared user id listed twice in one row");
+                seen.push_back(u);
+                check(!contrib_bf16_, "window data sets: shared user entries (amd:shared_user_from) need amd:contrib = fp32");
+            }
+            check(pv >= 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has none");
+            priv[(size_t)r] = pv;
+        }
+        const unsigned u = feat_index[priv.empty() ? p1 : priv[(size_t)r]];
         if (u >= (unsigned)NU) fail("user feature index exceed bound");
         cnt[u]++;
     }
@@ -325,16 +386,17 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
     std::vector<int> seg_of_user((size_t)NU, -1);
     std::vector<HostSeg> segs;
     for (long r = 0; r < n; r++) {
-        const unsigned u = feat_index[row_ptr[3 * r + 1]];
+        const unsigned u = feat_index[priv.empty() ? row_ptr[3 * r + 1] : priv[(size_t)r]];
         if (seg_of_user[u] < 0) { seg_of_user[u] = (int)segs.size(); HostSeg h; h.user = u; h.has_user = true; h.row_count = (size_t)cnt[u]; segs.push_back(h); }
     }
     { size_t acc = 0; for (auto &h : segs) { h.row_first = acc; acc += h.row_count; h.row_count = 0; } }
     std::vector<int64_t> seg_rows((size_t)n);
     for (long r = 0; r < n; r++) {
-        HostSeg &h = segs[(size_t)seg_of_user[feat_index[row_ptr[3 * r + 1]]]];
+        HostSeg &h = segs[(size_t)seg_of_user[feat_index[priv.empty() ? row_ptr[3 * r + 1] : priv[(size_t)r]]]];
         seg_rows[h.row_first + h.row_count++] = r;
     }
-    wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, true, n, row_label, row_ptr, feat_index, feat_value, nullptr, nullptr);
+    wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, true, n, row_label, row_ptr, feat_index, feat_value, nullptr, nullptr,
+                     priv.empty() ? nullptr : priv.data());
 }
 
 // ---- one exchange window of a user-group pass: blocks [b0, b1), every START closed by its END inside the window
@@ -512,11 +574,17 @@ static bool no_id_twice(const unsigned *a, int64_t n, std::vector<unsigned> &tmp
     std::sort(tmp.begin(), tmp.end());
     return std::adjacent_find(tmp.begin(), tmp.end()) == tmp.end();
 }
-bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index) {
+// shared_from (amd:shared_user_from, one-GPU window sequences): a row's user entries are one id < shared_from and shared ids, none twice
+bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index, unsigned shared_from) {
     std::vector<unsigned> tmp;
     for (long r = r0; r < r1; r++) {
         const int64_t *p = &row_ptr[(size_t)3 * r];
-        if (p[2] != p[1] + 1) return false;
+        if (shared_from != 0xFFFFFFFFu && p[2] > p[1] + 1) {
+            int priv = 0;
+            for (int64_t j = p[1]; j < p[2]; j++) priv += feat_index[j] < shared_from;
+            if (priv != 1 || !no_id_twice(feat_index + p[1], p[2] - p[1], tmp)) return false;
+        } else if (p[2] != p[1] + 1) return false;
+        if (shared_from != 0xFFFFFFFFu && feat_index[p[1]] >= shared_from && p[2] == p[1] + 1) return false;
         if (!no_id_twice(feat_index + p[0], p[1] - p[0], tmp) || !no_id_twice(feat_index + p[2], p[3] - p[2], tmp)) return false;
     }
     return true;
@@ -547,18 +615,27 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
     wunit_check_config("dataset_from_csr");
     validate_csr_pointers(n, row_ptr);
     std::vector<long> ci((size_t)mp_.num_item, 0), cg((size_t)mp_.num_global, 0);
+    std::vector<long> cs(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);   // shared user rows
     for (long r = 0; r < n; r++) {
         for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
         for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) { if (feat_index[j] >= (unsigned)mp_.num_item) fail("item feature index exceed bound"); ci[feat_index[j]]++; }
+        if (!cs.empty())
+            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++)
+                if (feat_index[j] >= shared_user_from_ && feat_index[j] < (unsigned)mp_.num_user) cs[feat_index[j] - shared_user_from_]++;
     }
-    const long W = wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio())});
+    // shared user rows are shared targets like item rows: the same rule (mean and most updates met per window), with a per-target mean of their
+    // own (window_per_target_shared, 12: a bucket row met by 1/64 of all rows is far hotter than the items the 24 was calibrated on, and 24 left
+    // |dRMSE| at 1.3e-4 on the SURVEY 8(d2) variant) and the common cap (window_per_target_max).  Expressed on the item term's scale.
+    const double shared_met = cs.empty() ? 0.0 : mean_updates_met(cs, (double)wseq_per_target_shared_ / (double)wseq_per_target_max_) *
+                                                  (double)wseq_per_target_ / (double)wseq_per_target_shared_;
+    const long W = wseq_windows(n, {std::max(mean_updates_met(ci, wseq_max_ratio()), shared_met), mean_updates_met(cg, wseq_max_ratio())});
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     const bool inplace = wunit_inplace_ != 0;   // a window is summed in place right after its walk (wseq_train): single contributions need no slot
     wseq_build_windows(W, wseq_build_threads_,
         [&](long w, WUnitHost &H) {
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value);
+            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true);
         },
         [&](long, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
