@@ -314,7 +314,7 @@ int svdf_synchronize(svdf_trainer *t);
  * more than 10 x slower than the streaming model), 27 / 28 the last noted data set's dag bound / stream model in microseconds,
  * 29 passes over rank pairs walked as user-run units */
 int64_t svdf_counter(svdf_trainer *t, int what);
-/* Tuning knobs (not part of the reference surface).  None changes a result bit except the six marked (*), which move the windows of the
+/* Tuning knobs (not part of the reference surface).  None changes a result bit except the seven marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
  *   staging / launches
  *     stage_window        2^21   instances staged by svdf_update_* before an automatic flush (also set by the config key amd:window)
@@ -344,6 +344,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     wunit_fast 2, wunit_inplace 1, wunit_defer_fb 1, window_slots 1, window_groups 0      kernel forms, same bits
  *     window_per_target (*) 24, window_per_target_fb (*) 16     updates a shared row / feedback row meets per window on average
  *     window_per_target_shared (*) 12                           ... a shared user row (amd:shared_user_from; profiles/r07_sidefeat_window.md)
+ *     window_per_target_child (*) 3                             ... a feature_user / feature_item child row (profiles/r08_sidetable_window.md)
  *     window_per_target_max (*) 128                             ... and at most (N-rank steps, rank pairs, user units; plain ratings on one GPU with window_hot_sub = 0)
  *     window_hot_sub (*) 128, window_hot_max (*) 2048           one-GPU sequences of plain ratings (round 6): an item with more than window_hot_sub slots in a window
  *                                                               moves in ordered sub-steps of that many (k_window_apply; 0 = off) and meets at most window_hot_max

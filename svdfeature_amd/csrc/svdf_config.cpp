@@ -256,6 +256,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "wunit_inplace")) { wunit_inplace_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_defer_fb")) { wunit_defer_fb_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_fast")) { check(value >= 0 && value <= 2, "wunit_fast must be 0, 1 or 2"); wunit_fast_ = (int)value; return 0; }
+    if (!strcmp(name, "window_per_target_child")) { check(value >= 1, "window_per_target_child must be positive"); wseq_per_target_child_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_shared")) { check(value >= 1, "window_per_target_shared must be positive"); wseq_per_target_shared_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_fb")) { check(value >= 1, "window_per_target_fb must be positive"); wseq_per_target_fb_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_sub")) { check(value >= 0 && value <= 4096, "window_hot_sub must be in 0 .. 4096"); wseq_hot_sub_ = (int)value; return 0; }

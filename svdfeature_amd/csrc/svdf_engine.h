@@ -270,6 +270,9 @@ struct Dataset {
     DevBuf<int> wu_uptr, wu_upos;  // shared user entries (amd:shared_user_from): per-row ranges into wu_uent and the private entry's position
     DevBuf<WinEnt> wu_uent;
     long wu_nshared = 0;           // > 0: the window has shared user entries; targets [.., + wu_nshared) are user rows B .. num_user - 1
+    DevBuf<int> wu_iptr;           // feature_item children of the window's item entries: per-row ranges into wu_ient
+    DevBuf<WinEnt> wu_ient;
+    bool wu_ichild = false;        // the window has feature_item children
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
     std::vector<Dataset *> wchild;
     // kind 6: a data set of an amd:gpus = N handle (svdf_multi.cpp): mchild[rank][window] lives in that rank's HBM
@@ -605,14 +608,18 @@ class Engine {
     DevBuf<float> d_gcontrib_;            // ... and one word per global entry (user-unit windows)
     // user-unit windows (svdf_wunit.cpp)
     WUnitSchedule wunit_view(const Dataset *ds) const;
-    void wunit_check_config(const char *what) const;
+    // side_tables: the caller is the one-GPU window sequence of random-order rows (wseq_from_csr), which takes feature_user / feature_item
+    // children as shared rows; every other window builder refuses loaded side tables
+    void wunit_check_config(const char *what, bool side_tables = false) const;
+    bool side_tables() const { return feat_user_.num_row() != 0 || feat_item_.num_row() != 0; }
+    void side_children_ok(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // svdf_wunit.cpp
     bool wunit_config_ok() const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
     void wunit_build(Dataset *ds, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                      const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                      const unsigned *fb_index, const float *fb_value);
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                          const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr) const;
+                          const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr, bool children = false) const;
     void wunit_adopt(Dataset *ds, const WUnitHost &H);
     void wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                              bool shared = false) const;
@@ -633,6 +640,8 @@ class Engine {
     bool wunit_inplace_build_ = false;    // set while wseq_from_csr / _from_blocks build their windows
     int wunit_fast_ = 2;                  // knob "wunit_fast": 0 = the general lane-group kernel for every shape, 1 = + the slot kernel, 2 = + one wave per unit (A/B and tests)
     int wseq_per_target_fb_ = 16;         // knob "window_per_target_fb": the same for feedback rows (instance-sized updates pushed by whole blocks)
+    int wseq_per_target_child_ = 3;       // knob "window_per_target_child": the same for side-table children (calibrated on the
+                                          // variant of profiles/r08_sidetable_window.md, 3 seeds at 2 M rows: 12 -> |dRMSE| 2.2e-4, 6 -> 1.1e-4, 4 -> 8.8e-5, 3 -> 5.7e-5)
     int wseq_per_target_shared_ = 12;     // knob "window_per_target_shared": the same for shared user rows (amd:shared_user_from; calibrated on the
                                           // SURVEY 8(d2) variant, 3 seeds: 24 -> |dRMSE| 1.3e-4, 16 -> 1.1e-4, 12 -> 6.1e-5; profiles/r07_sidefeat_window.md)
     int wseq_per_target_max_ = 128;       // knob "window_per_target_max": the MOST updates any shared row may meet per window (binds on skewed data only)

@@ -27,6 +27,9 @@ namespace svdf {
 // General form: any width <= 256, any row shape (one user entry per row), every link and regulariser of the base solver.
 // Shared user rows (S.uptr, amd:shared_user_from): the row's other user entries are read as of the window start, in entry order around the
 // private one (calc_bias :313-353, prepare_tmp :354-381), and their change goes to a contribution slot like an item row's.
+// Side-table children: feature_user children are shared user entries (the builder expands them); feature_item children
+// (S.iptr) follow their parent entry in every loop, with the reference's item-side forms for parent value ival and child value v: bias term
+// (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
 template <int LPI, bool FB>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     constexpr int IPW = 64 / LPI;
@@ -65,6 +68,8 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             const float ua = S.uval ? S.uval[r] : 1.0f;
             int u0 = 0, um = 0, u1 = 0;   // shared user entries: [u0, um) before the private one, [um, u1) after it
             if (S.uptr) { u0 = S.uptr[r]; um = u0 + S.upos[r]; u1 = S.uptr[r + 1]; }
+            int c0 = 0, c1 = 0;           // feature_item children: [c0, c1), parent by parent (ient.pad = the parent's entry)
+            if (S.iptr) { c0 = S.iptr[r]; c1 = S.iptr[r + 1]; }
             const size_t srow0 = (size_t)P.user_off + S.shared_from;
             // ---- pred (:445-454): calc_bias in double, the hooks' terms where the reference adds them
             double bs = 0.0;
@@ -76,14 +81,25 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 bs += (double)(FB ? pp.tmp_bias : 0.0f);
             }
             bs += 0.0;
-            for (int j = e1; j < e2; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.bias[P.item_off + e.idx]); }
+            for (int j = e1, c = c0; j < e2; j++) {
+                const WinEnt e = S.ent[j];
+                bs += (double)(e.val * P.bias[P.item_off + e.idx]);
+                for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
+            }
             double sum = (double)P.base_score + bs;
             float4 tu = FB ? pp.tmp_fb : f4zero();
             for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
             axpy4(tu, p, ua);
             for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
             float4 ti = f4zero();
-            for (int j = e1; j < e2; j++) { const WinEnt e = S.ent[j]; axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val); }
+            for (int j = e1, c = c0; j < e2; j++) {
+                const WinEnt e = S.ent[j];
+                axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+                for (; c < c1 && S.ient[c].pad == j; c++) {   // scalar formed in double
+                    const WinEnt ch = S.ient[c];
+                    axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+                }
+            }
             sum += (double)group_dot<LPI>(tu, ti, L, k);
             const float pred = map_active((float)sum, P.active_type);
             const float err = cal_grad(label, pred, P.active_type) * 1.0f;
@@ -116,6 +132,29 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 } else {
                     store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)e.slot, pitch, L, k, wi);
                     if (L == 0) S.cbias[e.slot] = nbi - bi;
+                }
+            }
+            for (int j = e1, c = c0; c < c1; j++) {   // feature_item children: update_no_decay + reg_item against the window-start rows
+                const float ival = S.ent[j].val;
+                for (; c < c1 && S.ient[c].pad == j; c++) {
+                    const WinEnt ch = S.ient[c];
+                    const float si = lr * err * ch.val * ival;
+                    const size_t row = (size_t)P.item_off + ch.idx;
+                    const float4 q = load_row<LPI>(P.W, row, pitch, L, k);
+                    const float bi = P.bias[row];
+                    float4 wi = q;
+                    axpy4(wi, tu, si);
+                    float nbi = bi + si;
+                    reg_row<LPI>(P, wi, get_wd(P.i_rng, ch.idx, P.wd_item), true, L);
+                    nbi = nbi * (1.0f - lr * P.wd_item_bias);
+                    sub4(wi, q);
+                    if (ch.slot < 0) {   // the row's only contribution of this window
+                        store_row<LPI>(P.W, row, pitch, L, k, apply_single(q, wi, false));
+                        if (L == 0) P.bias[row] = apply_single(bi, nbi - bi, false);
+                    } else {
+                        store_contrib<LPI>(S.contrib, 0, (size_t)ch.slot, pitch, L, k, wi);
+                        if (L == 0) S.cbias[ch.slot] = nbi - bi;
+                    }
                 }
             }
             for (int j = u0; j < u1; j++) {   // shared user rows: update_no_decay + reg_user (:211-249) against the window-start row
@@ -550,7 +589,7 @@ bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedbac
 }
 void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st) {
     if (S.nunits <= 0) return;
-    if (S.uptr) fast = 0;   // rows with shared user entries: the general walk (the fixed shapes have no user section)
+    if (S.uptr || S.iptr) fast = 0;   // rows with shared user entries or feature_item children: the general walk (the fixed shapes have neither)
     // fast: 0 = the general lane-group kernel, 1 = the slot kernel where it applies, 2 (default) = in addition one WAVE per unit for user-group
     // windows whose launch does not fill the chip anyway (its time is the longest unit's latency: svdf_k_wave.hip, k_wunit_wave)
     if (fast >= 2 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) { launch_wunit_wave(P, S, st); return; }

@@ -265,6 +265,11 @@ struct WUnitSchedule {
     const WinEnt *uent;
     long nshared_rows;
     unsigned shared_from;
+    // feature_item children (one-GPU window sequences only): nullptr iptr = none.  Row r's children are
+    // ient[iptr[r] .. iptr[r + 1]), parent by parent in entry order; ient.pad = the parent's position in ent, ient.idx = the child item id.
+    // They are item targets like the entries themselves.  (feature_user children are expanded into the shared user entries above.)
+    const int *iptr;
+    const WinEnt *ient;
 };
 
 }  // namespace svdf

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <memory>
 #include <cmath>
+#include <cstring>
 #include <numeric>
 #include <string>
 #include <thread>
@@ -40,8 +41,10 @@ struct WUnitHost {
     std::vector<WinTouched> touched;   // one-GPU windows (inplace builds): the targets that keep slots
     std::vector<int> uptr, upos;       // shared user entries (amd:shared_user_from), WUnitSchedule::uptr / upos / uent; empty: none in the window
     std::vector<WinEnt> uent;
+    std::vector<int> iptr;             // feature_item children, WUnitSchedule::iptr / ient; empty: none in the window
+    std::vector<WinEnt> ient;
     bool has_touched = false;
-    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0;
+    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
     int fixed_ng = -2;
     bool unit_uval = true, feedback = false;
 };
@@ -62,6 +65,7 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     const bool sh = ds->wu_nshared > 0;
     S.uptr = sh ? ds->wu_uptr.p : nullptr; S.upos = sh ? ds->wu_upos.p : nullptr; S.uent = sh ? ds->wu_uent.p : nullptr;
     S.nshared_rows = ds->wu_nshared; S.shared_from = sh ? shared_user_from_ : 0u;
+    S.iptr = ds->wu_ichild ? ds->wu_iptr.p : nullptr; S.ient = ds->wu_ichild ? ds->wu_ient.p : nullptr;
     return S;
 }
 
@@ -69,11 +73,22 @@ bool Engine::wunit_config_ok() const {
     return trainer_ready_ && mtype_.extend_type == 0 && !relaxed() && !lazy_decay() && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 &&
            feat_item_.num_row() == 0 && g_stride_ == 1 && mp_.num_factor <= 256 && (!user_group() || mp_.common_feedback_space == 0);
 }
-void Engine::wunit_check_config(const char *what) const {
+void Engine::wunit_check_config(const char *what, bool tables_ok) const {
     check(trainer_ready_, "dataset: init_trainer has not been called");
     check(mtype_.extend_type == 0, "window data sets: the base solvers only (extend_type 0)");
-    check(!relaxed() && !lazy_decay() && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 && feat_item_.num_row() == 0 && g_stride_ == 1,
+    if (side_tables()) {   // feature_user / feature_item: the one-GPU window sequence of random-order rows only
+        check(!user_group(), "window data sets: feature_user / feature_item side tables are not supported with user-group (SVD++) trainers");
+        check(strcmp(what, "dataset_window_from_csr") != 0,
+              "svdf_dataset_window_from_csr: feature_user / feature_item side tables are for the one-GPU window sequence (amd:step = minibatch); "
+              "the N-rank exchange has no place for their children");
+    }
+    check(!relaxed() && !lazy_decay() && mp_.common_latent_space == 0 && (tables_ok || !side_tables()) && g_stride_ == 1,
           "window data sets: no side tables, relaxed ids, lazy decay or shared latent space");
+    if (side_tables()) {
+        check(feat_user_.num_row() == 0 || shared_user(),
+              "window data sets: a feature_user side table needs amd:shared_user_from (its children are shared user rows, ids >= B)");
+        check(!contrib_bf16_, "window data sets: feature_user / feature_item side tables need amd:contrib = fp32");
+    }
     check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
@@ -92,13 +107,29 @@ void Engine::wunit_build(Dataset *ds, const void *segs_v, size_t nseg, const std
 }
 void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order,
                               long num_src_row, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos) const {
+                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children) const {
     const HostSeg *segs = static_cast<const HostSeg *>(segs_v);
     const long NU = mp_.num_user, NI = mp_.num_item, NG = mp_.num_global, NF = user_group() ? (long)num_fb_rows() : 0;
-    // shared user rows (priv_pos: the private entry of every source row; the other user entries are ids >= amd:shared_user_from): targets after
-    // the item rows, only when the window holds such an entry -- otherwise the window is laid out exactly as without the key
-    bool has_shared = false;
-    if (priv_pos) for (long r = 0; r < num_src_row && !has_shared; r++) has_shared = row_ptr[3 * r + 2] - row_ptr[3 * r + 1] > 1;
+    // side-table children (children: the one-GPU window sequence): [c0, c1) of an id into the table's columns
+    const SideTable &FU = feat_user_, &FI = feat_item_;
+    auto kids = [&](const SideTable &T, unsigned id, unsigned &c0, unsigned &c1) {
+        c0 = c1 = 0;
+        if (children && id < T.num_row()) { c0 = T.row_ptr[id]; c1 = T.row_ptr[id + 1]; }
+        return c1 > c0;
+    };
+    // shared user rows (priv_pos: the private entry of every source row; the other user entries are ids >= amd:shared_user_from, and so are
+    // feature_user children): targets after the item rows, only when the window holds such an entry -- otherwise the window is laid out exactly
+    // as without the key.  feature_item children: a child section, only when the window holds one.
+    bool has_shared = false, has_ichild = false;
+    unsigned c0, c1;
+    if (priv_pos)
+        for (long r = 0; r < num_src_row && !has_shared; r++) {
+            has_shared = row_ptr[3 * r + 2] - row_ptr[3 * r + 1] > 1;
+            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2] && !has_shared; j++) has_shared = kids(FU, feat_index[j], c0, c1);
+        }
+    if (children)
+        for (long r = 0; r < num_src_row && !has_ichild; r++)
+            for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3] && !has_ichild; j++) has_ichild = kids(FI, feat_index[j], c0, c1);
     const unsigned SB = has_shared ? shared_user_from_ : 0u;
     const long NS = has_shared ? NU - (long)SB : 0, NT = NF + NI + NS;
     const bool feedback = user_group();
@@ -188,9 +219,11 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         if (feat_value[pv] != 1.0f) unit_uval = false;
         if (has_shared) {   // the row's user entries in entry order, the private one by position
             H.uptr.push_back((int)H.uent.size());
-            for (int64_t j = p1; j < p2; j++) {
+            for (int64_t j = p1; j < p2; j++) {   // each entry followed by its feature_user children (the private one's: the front of [um, u1))
                 if (j == pv) H.upos.push_back((int)H.uent.size() - H.uptr.back());
                 else H.uent.push_back(WinEnt{feat_index[j] - SB, feat_value[j], 0, 0});
+                if (kids(FU, feat_index[j], c0, c1))
+                    for (unsigned c = c0; c < c1; c++) H.uent.push_back(WinEnt{FU.index[c] - SB, FU.value[c], 0, 0});
             }
         }
     }
@@ -219,13 +252,23 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
             gptr[(size_t)feat_index[j] + 1]++;
         }
         seen.clear();
+        if (has_ichild) H.iptr.push_back((int)H.ient.size());
         for (int64_t j = p2; j < p3; j++, e++) {
             if (feat_index[j] >= (unsigned)NI) fail("item feature index exceed bound");
             ent[(size_t)e].idx = feat_index[j]; ent[(size_t)e].val = feat_value[j];
             for (unsigned x : seen) if (x == feat_index[j]) fail("window data sets: an item id listed twice in one row");
             seen.push_back(feat_index[j]);
             tptr[(size_t)(NF + feat_index[j]) + 1]++;
+            if (has_ichild && kids(FI, feat_index[j], c0, c1))   // the entry's feature_item children; pad = the parent's position in ent
+                for (unsigned c = c0; c < c1; c++) {
+                    H.ient.push_back(WinEnt{FI.index[c], FI.value[c], 0, e});
+                    tptr[(size_t)(NF + FI.index[c]) + 1]++;
+                }
         }
+    }
+    if (has_ichild) {
+        H.iptr.push_back((int)H.ient.size());
+        check((long)H.ient.size() < (1L << 30), "window data sets: at most 2^30-1 feature_item children per window");
     }
     std::vector<WinEnt> &fbent = H.fbent;
     fbent.assign((size_t)nfbe, WinEnt{0u, 0.0f, 0, 0});
@@ -263,6 +306,8 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         for (int e = e1; e < e2; e++) ent[(size_t)e].slot = take_slot(tcur, (size_t)NF + ent[(size_t)e].idx);
         if (has_shared)
             for (int e = H.uptr[(size_t)nr]; e < H.uptr[(size_t)nr + 1]; e++) H.uent[(size_t)e].slot = take_slot(tcur, (size_t)(NF + NI) + H.uent[(size_t)e].idx);
+        if (has_ichild)
+            for (int e = H.iptr[(size_t)nr]; e < H.iptr[(size_t)nr + 1]; e++) H.ient[(size_t)e].slot = take_slot(tcur, (size_t)NF + H.ient[(size_t)e].idx);
     };
     if (by_row_order) {
         for (long r = 0; r < num_src_row; r++) if (newrow_of_src[(size_t)r] >= 0) row_slots(newrow_of_src[(size_t)r]);
@@ -284,7 +329,7 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     }
     for (size_t j = 0; j < nunit; j++) units[j].first = wsegs[(size_t)units[j].seg_begin];   // the first segment travels with the unit record
     H.nrow = nrow; H.nent = nent; H.nfbe = nfbe; H.fixed_ng = fixed_ng; H.unit_uval = unit_uval;
-    H.nshared = NS; H.shared_entries = (long)H.uent.size();
+    H.nshared = NS; H.shared_entries = (long)H.uent.size(); H.item_children = (long)H.ient.size();
     for (long nr = 0; nr < nrow; nr++) { const int g = rptr[(size_t)2 * nr + 1] - rptr[(size_t)2 * nr]; H.global_entries += g; H.item_entries += rptr[(size_t)2 * nr + 2] - rptr[(size_t)2 * nr] - g; }
     (void)NU;
 }
@@ -330,6 +375,11 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
         ds->wu_upos.upload(H.upos.data(), H.upos.size(), stream_);
         ds->wu_uent.upload(H.uent.data(), H.uent.size(), stream_);
     }
+    ds->wu_ichild = !H.iptr.empty();
+    if (ds->wu_ichild) {
+        ds->wu_iptr.upload(H.iptr.data(), H.iptr.size(), stream_);
+        ds->wu_ient.upload(H.ient.data(), H.ient.size(), stream_);
+    }
     HIPCHECK(hipStreamSynchronize(stream_));   // the host columns go out of scope
     ds->sched.level_ptr = {0, nrow};
     ds->sched.max_level_size = nrow;
@@ -337,7 +387,8 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
     const long k = mp_.num_factor, nub = mp_.no_user_bias ? 0 : 1;
     const long item_entries = H.item_entries, global_entries = H.global_entries;
     ds->algorithmic_bytes = nrow * (8 * k + 8 * nub + 16 + 8) + item_entries * (8 * k + 8 + 8) + global_entries * 16 + nfbe * (12 * k + 20) +
-                            H.shared_entries * (8 * k + 8 * nub + 8);   // a shared user entry: its row and bias read and written, id + value
+                            H.shared_entries * (8 * k + 8 * nub + 8) +  // a shared user entry: its row and bias read and written, id + value
+                            H.item_children * (8 * k + 8 + 8);          // a feature_item child: like an item entry
 }
 
 // ---- one exchange window of rows of a random-order trainer: any number of global and item entries, exactly one user entry
@@ -347,16 +398,19 @@ void Engine::wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, co
     wunit_adopt(ds, H);
 }
 // shared: the one-GPU window sequence under amd:shared_user_from = B -- a row's user entries are ONE private id < B (the unit's user) and any
-// number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.
+// number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.  The sequence also takes loaded
+// feature_user / feature_item tables: every child is a shared target, and no row may reach one target twice.
 void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
                                  const float *feat_value, bool shared) const {
     const long NU = mp_.num_user;
     const unsigned B = shared_user_from_;
+    const bool children = shared && side_tables();
     std::vector<int> cnt((size_t)NU, 0);
     std::vector<int64_t> priv;   // shared mode: the private entry of every row
     if (shared && shared_user()) priv.resize((size_t)n);
     std::vector<unsigned> seen;
     for (long r = 0; r < n; r++) {
+        if (children) side_children_ok(row_ptr + 3 * r, feat_index, seen);
         const int64_t p1 = row_ptr[3 * r + 1], p2 = row_ptr[3 * r + 2];
         if (priv.empty()) {
             if (p2 - p1 != 1 && shared_user())
@@ -396,7 +450,32 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
         seg_rows[h.row_first + h.row_count++] = r;
     }
     wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, true, n, row_label, row_ptr, feat_index, feat_value, nullptr, nullptr,
-                     priv.empty() ? nullptr : priv.data());
+                     priv.empty() ? nullptr : priv.data(), children);
+}
+// One row's side-table children (the one-GPU window sequence): a feature_user child is a shared user row (id >= amd:shared_user_from), and
+// a child must not reach a row the row already touches (its own entries or an earlier child) -- one contribution per target and row.  Two
+// plain entries with one id keep the builder's own messages.
+void Engine::side_children_ok(const int64_t *p, const unsigned *feat_index, std::vector<unsigned> &seen) const {
+    const unsigned B = shared_user_from_;
+    for (int side = 0; side < 2; side++) {
+        const SideTable &T = side == 0 ? feat_user_ : feat_item_;
+        const int64_t a = p[1 + side], b = p[2 + side];
+        if (T.num_row() == 0) continue;
+        seen.assign(feat_index + a, feat_index + b);
+        for (int64_t j = a; j < b; j++) {
+            const unsigned id = feat_index[j];
+            if (id >= T.num_row()) continue;
+            for (unsigned c = T.row_ptr[id]; c < T.row_ptr[id + 1]; c++) {
+                const unsigned x = T.index[c];
+                if (side == 0)
+                    check(x >= B, "window data sets: a feature_user child below amd:shared_user_from (it would be another unit's private user row)");
+                for (unsigned y : seen)
+                    if (y == x) fail(side == 0 ? "window data sets: a row reaches one user row twice through feature_user children (each row may touch a target once)"
+                                               : "window data sets: a row reaches one item row twice through feature_item children (each row may touch a target once)");
+                seen.push_back(x);
+            }
+        }
+    }
 }
 
 // ---- one exchange window of a user-group pass: blocks [b0, b1), every START closed by its END inside the window
@@ -612,23 +691,43 @@ bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_pt
 }
 
 Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
-    wunit_check_config("dataset_from_csr");
+    wunit_check_config("dataset_from_csr", true);
     validate_csr_pointers(n, row_ptr);
     std::vector<long> ci((size_t)mp_.num_item, 0), cg((size_t)mp_.num_global, 0);
     std::vector<long> cs(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);   // shared user rows
+    std::vector<unsigned char> ichild(feat_item_.num_row() ? (size_t)mp_.num_item : 0, 0);   // item rows that are a feature_item child somewhere
+    std::vector<unsigned char> uchild(feat_user_.num_row() ? cs.size() : 0, 0);               // shared user rows that are a feature_user child
+    const SideTable &FU = feat_user_, &FI = feat_item_;
     for (long r = 0; r < n; r++) {
         for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
-        for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) { if (feat_index[j] >= (unsigned)mp_.num_item) fail("item feature index exceed bound"); ci[feat_index[j]]++; }
+        for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) {
+            const unsigned i = feat_index[j];
+            if (i >= (unsigned)mp_.num_item) fail("item feature index exceed bound");
+            ci[i]++;
+            if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) { ci[FI.index[c]]++; ichild[FI.index[c]] = 1; }
+        }
         if (!cs.empty())
-            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++)
-                if (feat_index[j] >= shared_user_from_ && feat_index[j] < (unsigned)mp_.num_user) cs[feat_index[j] - shared_user_from_]++;
+            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++) {
+                const unsigned u = feat_index[j];
+                if (u >= shared_user_from_ && u < (unsigned)mp_.num_user) cs[u - shared_user_from_]++;
+                if (u < FU.num_row())
+                    for (unsigned c = FU.row_ptr[u]; c < FU.row_ptr[u + 1]; c++)
+                        if (FU.index[c] >= shared_user_from_) { cs[FU.index[c] - shared_user_from_]++; uchild[FU.index[c] - shared_user_from_] = 1; }
+            }
     }
+    // side-table children: a row that is a child anywhere -- a feature_user child among the shared user rows, a feature_item
+    // child among the item rows -- is a target of its own kind, with all its updates (as a plain entry too), at window_per_target_child
+    std::vector<long> cc;
+    for (size_t i = 0; i < ichild.size(); i++) if (ichild[i]) { cc.push_back(ci[i]); ci[i] = 0; }
+    for (size_t j = 0; j < uchild.size(); j++) if (uchild[j]) { cc.push_back(cs[j]); cs[j] = 0; }
     // shared user rows are shared targets like item rows: the same rule (mean and most updates met per window), with a per-target mean of their
     // own (window_per_target_shared, 12: a bucket row met by 1/64 of all rows is far hotter than the items the 24 was calibrated on, and 24 left
     // |dRMSE| at 1.3e-4 on the SURVEY 8(d2) variant) and the common cap (window_per_target_max).  Expressed on the item term's scale.
     const double shared_met = cs.empty() ? 0.0 : mean_updates_met(cs, (double)wseq_per_target_shared_ / (double)wseq_per_target_max_) *
                                                   (double)wseq_per_target_ / (double)wseq_per_target_shared_;
-    const long W = wseq_windows(n, {std::max(mean_updates_met(ci, wseq_max_ratio()), shared_met), mean_updates_met(cg, wseq_max_ratio())});
+    const double child_met = cc.empty() ? 0.0 : mean_updates_met(cc, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) *
+                                                 (double)wseq_per_target_ / (double)wseq_per_target_child_;
+    const long W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     const bool inplace = wunit_inplace_ != 0;   // a window is summed in place right after its walk (wseq_train): single contributions need no slot
