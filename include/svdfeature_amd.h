@@ -349,6 +349,14 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     window_hot_sub (*) 128, window_hot_max (*) 2048           one-GPU sequences of plain ratings (round 6): an item with more than window_hot_sub slots in a window
  *                                                               moves in ordered sub-steps of that many (k_window_apply; 0 = off) and meets at most window_hot_max
  *                                                               updates per window -- the hottest item no longer sets the number of windows
+ *     window_shared_sub (*) 0, window_shared_max (*) 512        one-GPU sequences of rows with shared user entries / feature_user children (amd:shared_user_from):
+ *                                                               a shared user row (id >= B) with more than window_shared_sub slots in a window moves in ordered sub-steps
+ *                                                               of that many (k_wunit_apply_shared; 0 = off, the default: the rule and bits of 6i / 6j) and meets at most
+ *                                                               window_shared_max updates per window; the class means (window_per_target_shared / _child) then bound
+ *                                                               min(updates per window, window_shared_sub).  Set before the data set is built: train_dataset refuses a
+ *                                                               sequence built with another window_shared_sub.  Refused with amd:contrib = bf16, user-group trainers,
+ *                                                               amd:gpus > 1 / svdf_dataset_window_from_csr.  12 with the defaults: 4.0x the 6i rule at |dRMSE| <= 6.9e-5
+ *                                                               on the side-feature variant (profiles/r09_shared_hot.md); does not pay on the 6j table variant
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is

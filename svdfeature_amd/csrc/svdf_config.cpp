@@ -259,6 +259,8 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_per_target_child")) { check(value >= 1, "window_per_target_child must be positive"); wseq_per_target_child_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_shared")) { check(value >= 1, "window_per_target_shared must be positive"); wseq_per_target_shared_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_fb")) { check(value >= 1, "window_per_target_fb must be positive"); wseq_per_target_fb_ = (int)value; return 0; }
+    if (!strcmp(name, "window_shared_sub")) { check(value >= 0 && value <= 4096, "window_shared_sub must be in 0 .. 4096"); wseq_shared_sub_ = (int)value; return 0; }
+    if (!strcmp(name, "window_shared_max")) { check(value >= 1, "window_shared_max must be positive"); wseq_shared_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_sub")) { check(value >= 0 && value <= 4096, "window_hot_sub must be in 0 .. 4096"); wseq_hot_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_max")) { check(value >= 1, "window_hot_max must be positive"); wseq_hot_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }

@@ -30,7 +30,8 @@ namespace svdf {
 // Side-table children: feature_user children are shared user entries (the builder expands them); feature_item children
 // (S.iptr) follow their parent entry in every loop, with the reference's item-side forms for parent value ival and child value v: bias term
 // (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
-template <int LPI, bool FB>
+// HOT: the window has hot shared user rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the code as it was.
+template <int LPI, bool FB, bool HOT = false>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
@@ -159,6 +160,12 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             }
             for (int j = u0; j < u1; j++) {   // shared user rows: update_no_decay + reg_user (:211-249) against the window-start row
                 const WinEnt e = S.uent[j];
+                if (HOT && e.pad) {   // a hot row of this window (ordered sub-steps, k_wunit_apply_shared): the slot takes what only this walk knows --
+                               // the private user's row and bias as they are before this data row's update
+                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
+                    if (L == 0) S.cbias[e.slot] = bu;
+                    continue;
+                }
                 const float ss = lr * err * e.val;
                 const size_t row = srow0 + e.idx;
                 const float4 w = load_row<LPI>(P.W, row, pitch, L, k);
@@ -478,7 +485,7 @@ __global__ __launch_bounds__(256) void k_wunit_fast(const DevParams P, const WUn
 //   else:  the wire buffer of the exchange, dst = [T rows of `pitch` | T biases | nglobal global biases] (the packed layout of
 //          Engine::delta_ranges for the whole item range), fp32 or fp16.
 // The global biases' sums (gptr over gcontrib) are taken by the same launch, one thread per global id.
-template <int LPI, bool HALF, bool LOCAL>
+template <int LPI, bool HALF, bool LOCAL, bool HOT = false>   // HOT: the touched list may hold hot shared user rows (in-place sums only)
 __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float *W, float *bias, float *g_bias, unsigned fb_off, unsigned item_off,
                                                    unsigned user_off, int pitch, int k, void *dst) {
     constexpr int IPW = 64 / LPI;
@@ -505,9 +512,15 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
         const int b = pb, e = pe;
         if (i + stride < N) request(i + stride);
         if (LOCAL && b == e) continue;
+        const bool owns = !(LPI * 4 > k && L * 4 >= k);
+        if (HOT && LOCAL && e < 0) {   // a hot shared user row (WinTouched): k_wunit_apply_shared left the row and bias it ends the window with in slot b
+            const size_t row = (size_t)user_off + S.shared_from + (size_t)(t - S.nfb_rows - S.nitem_rows);
+            if (owns) *reinterpret_cast<float4 *>(W + row * pitch + (size_t)L * 4) = *reinterpret_cast<const float4 *>(S.contrib + (size_t)b * pitch + (size_t)L * 4);
+            if (L == 0 && S.user_bias) bias[row] = S.cbias[b];
+            continue;
+        }
         float4 acc = f4zero();
         float accb = 0.0f;
-        const bool owns = !(LPI * 4 > k && L * 4 >= k);
         if (S.fbrec && t < S.nfb_rows) {
             // deferred feedback scatter: slot s names a segment and the entry's value; the contribution is what the unit's walk would have stored --
             // (w + d val) - w against the window-start row, rounded like a stored contribution row -- and the sum runs in slot (= file) order
@@ -582,6 +595,134 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
     }
 }
 
+// ------------------------------------------------------------------------------------------------- kernel C: hot shared user rows in ordered sub-steps
+// One workgroup per hot shared user row of the window (S.hot; knob window_shared_sub), between the walk and the sums.  The row and
+// its bias live in LDS; its slots are taken in file order, S.hot_sub at a time.  One lane group per slot of a sub-step redoes the data row's
+// update_inner the way k_wunit_walk does, statement for statement, with
+//   * the hot row and its bias as the previous sub-step left them (LDS),
+//   * the private user's row and bias as the walk held them when it reached the data row (the slot's record, written by the walk),
+//   * everything else from the model, which is still as of the window start: a window with a hot row has no in-place single applies (the builder
+//     gives every contribution a slot there), the sums run after this kernel, and this kernel does not write the model either -- another hot row of
+//     the same data row must read this one as of the window start, so the row's final value goes to its first slot and k_wunit_sum moves it in;
+// and parks new - current of the hot row (and bias) in LDS.  The parked changes of a sub-step are added in slot order (acc = +0 + c_1 + c_2 ...; every
+// column by one thread) and the row moves by the sum.  The workgroup is sized to the sub-step: min(hot_sub, 256 / LPI) lane groups.
+template <int LPI>
+__global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, const WUnitSchedule S) {
+    extern __shared__ __align__(16) float hot_lds[];
+    const int pitch = P.pitch, k = P.k, k4 = (k + 3) & ~3;
+    const int G = blockDim.x / LPI, tid = threadIdx.x;
+    const int g = tid / LPI, L = tid & (LPI - 1);
+    float *cur = hot_lds;                    // [pitch] the row as the previous sub-step left it
+    float *accv = cur + pitch;               // [pitch] the sub-step's sum so far
+    float *park = accv + pitch;              // [G][pitch] the changes of the slots in flight
+    float *pb = park + (size_t)G * pitch;    // [G] their bias changes
+    float *sc = pb + G;                      // the bias as the previous sub-step left it, the sub-step's bias sum
+    const WinHot h = S.hot[blockIdx.x];
+    const bool ub = P.no_user_bias == 0;
+    const bool owns = !(LPI * 4 > k && L * 4 >= k);
+    const float lr = P.lr;
+    const size_t srow0 = (size_t)P.user_off + S.shared_from;
+    const size_t hrow = srow0 + (size_t)h.j;
+    const float wd_s = get_wd(P.u_rng, S.shared_from + (unsigned)h.j, P.wd_user);
+    for (int c = tid; c < k4; c += blockDim.x) cur[c] = P.W[hrow * pitch + c];
+    if (tid == 0) sc[0] = ub ? P.bias[hrow] : 0.0f;
+    __syncthreads();
+    for (int s0 = h.b; s0 < h.e; s0 += S.hot_sub) {
+        const int s1 = min(s0 + S.hot_sub, h.e);
+        for (int c = tid; c < k4; c += blockDim.x) accv[c] = 0.0f;
+        if (tid == 0) sc[1] = 0.0f;
+        for (int q0 = s0; q0 < s1; q0 += G) {
+            const int slot = q0 + g;
+            if (slot < s1) {
+                const WinHotRec rc = S.hrec[h.rec + (slot - h.b)];
+                const int r = rc.row;
+                int e0, e1, e2;
+                if (S.rptr) { e0 = S.rptr[2 * (long)r]; e1 = S.rptr[2 * (long)r + 1]; e2 = S.rptr[2 * (long)r + 2]; }
+                else { e0 = r * S.estride; e1 = e0 + S.estride - 1; e2 = e1 + 1; }
+                const float label = S.label[r];
+                const float ua = S.uval ? S.uval[r] : 1.0f;
+                const int u0 = S.uptr[r], um = u0 + S.upos[r], u1 = S.uptr[r + 1];
+                int c0 = 0, c1 = 0;
+                if (S.iptr) { c0 = S.iptr[r]; c1 = S.iptr[r + 1]; }
+                const float4 p = load_row<LPI>(S.contrib, (size_t)slot, pitch, L, k);   // the walk's record
+                const float bu = ub ? S.cbias[slot] : 0.0f;
+                const float4 hw = owns ? *reinterpret_cast<const float4 *>(cur + L * 4) : f4zero();
+                const float hb = sc[0];
+                // ---- pred: k_wunit_walk's statements (FB = false), the hot entry's row and bias from LDS
+                double bs = 0.0;
+                for (int j = e0; j < e1; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.g_bias[e.idx]); }
+                if (ub) {
+                    for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == rc.pos ? hb : P.bias[srow0 + e.idx])); }
+                    bs += (double)(ua * bu);
+                    for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == rc.pos ? hb : P.bias[srow0 + e.idx])); }
+                    bs += (double)0.0f;
+                }
+                bs += 0.0;
+                for (int j = e1, c = c0; j < e2; j++) {
+                    const WinEnt e = S.ent[j];
+                    bs += (double)(e.val * P.bias[P.item_off + e.idx]);
+                    for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
+                }
+                double sum = (double)P.base_score + bs;
+                float4 tu = f4zero();
+                for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == rc.pos ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+                axpy4(tu, p, ua);
+                for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == rc.pos ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+                float4 ti = f4zero();
+                for (int j = e1, c = c0; j < e2; j++) {
+                    const WinEnt e = S.ent[j];
+                    axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+                    for (; c < c1 && S.ient[c].pad == j; c++) {
+                        const WinEnt ch = S.ient[c];
+                        axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+                    }
+                }
+                sum += (double)group_dot<LPI>(tu, ti, L, k);
+                const float pred = map_active((float)sum, P.active_type);
+                const float err = cal_grad(label, pred, P.active_type) * 1.0f;
+                // ---- the hot row's part of update_no_decay + reg_user: the walk's shared-row block against the current row
+                const float ss = lr * err * S.uent[rc.pos].val;
+                float4 ws = hw;
+                axpy4(ws, ti, ss);
+                reg_row<LPI>(P, ws, wd_s, false, L);
+                sub4(ws, hw);
+                float cb = 0.0f;
+                if (ub) { float nb = hb + ss; nb = nb * (1.0f - lr * P.wd_user_bias); cb = nb - hb; }
+                if (owns) *reinterpret_cast<float4 *>(park + (size_t)g * pitch + L * 4) = ws;
+                if (L == 0) pb[g] = cb;
+            }
+            __syncthreads();
+            const int m = min(G, s1 - q0);
+            for (int c = tid; c < k4; c += blockDim.x) {
+                float a = accv[c];
+                for (int q = 0; q < m; q++) a = a + park[(size_t)q * pitch + c];
+                accv[c] = a;
+            }
+            if (tid == 0) {
+                float a = sc[1];
+                for (int q = 0; q < m; q++) a = a + pb[q];
+                sc[1] = a;
+            }
+            __syncthreads();
+        }
+        for (int c = tid; c < k4; c += blockDim.x) cur[c] = cur[c] + accv[c];
+        if (tid == 0) sc[0] = sc[0] + sc[1];
+        __syncthreads();
+    }
+    for (int c = tid; c < k4; c += blockDim.x) S.contrib[(size_t)h.b * pitch + c] = cur[c];
+    if (tid == 0) S.cbias[h.b] = sc[0];
+}
+
+void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st) {
+    if (S.nhot <= 0) return;
+    const int lpi = lanes_per_instance(P.k);
+    const long want = (long)std::min(S.hot_sub, 256 / lpi) * lpi;
+    const int block = (int)std::min<long>(256, (want + 63) / 64 * 64);
+    const int G = block / lpi;
+    const size_t lds = ((size_t)(2 + G) * (size_t)P.pitch + (size_t)G + 2) * sizeof(float);
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_apply_shared<LPI>), dim3((unsigned)S.nhot), dim3((unsigned)block), lds, st, P, S));
+}
+
 bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedback) {
     if (!(P.k == 64 || P.k == 128) || S.rptr != nullptr || S.uval != nullptr || P.reg_method == 2) return false;
     const int ng = S.estride - 1;
@@ -613,6 +754,7 @@ void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback
     const long ipw = 64 / lpi;
     const long waves = (S.nunits + ipw - 1) / ipw;
     if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    else if (S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
 }
 // dst == nullptr: add the sums to the model in place; else the wire buffer (half: fp16)
@@ -627,7 +769,8 @@ void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int
     // (many short-lived waves beat one resident set walking several targets each: grid cap 2 048 -> 53.5 us, 4 096 -> 45.8, 16 384 -> 43.8 per SVD++ window)
     if (grid > 16384) grid = 16384;
     if (grid < 1) grid = 1;
-    if (!dst) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
+    if (!dst && S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
+    else if (!dst) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
     else if (half) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, true, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, dst)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, dst)); }
 }

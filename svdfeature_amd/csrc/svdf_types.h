@@ -237,7 +237,13 @@ struct WinEnt { unsigned idx; float val; int slot; int pad; };
 // from dvec[seg] -- and the entry's value; the contribution (w + d val) - w is formed by k_wunit_sum against the row it is about to update
 struct WinFbRec { int seg; float val; };
 // one-GPU windows: the targets that have slots at all (target, first slot, one past its last): the in-place sums walk this list instead of every row
+// (a HOT shared user row of the window -- ordered sub-steps, below -- carries e NEGATED: its slots are not summed, k_wunit_sum moves the row
+// k_wunit_apply_shared left in its first slot into the model)
 struct WinTouched { int t, b, e; };
+// ORDERED SUB-STEPS for hot shared user rows (knob window_shared_sub).  A hot row: shared row j (= id - B), its slots
+// [b, e) in file order, its records hrec[rec .. rec + e - b): which regrouped data row a slot belongs to and where in uent its hot entry sits.
+struct WinHot { int j, b, e, rec; };
+struct WinHotRec { int row, pos; };
 struct WUnitSchedule {
     const WinUnit *units;
     long nunits;
@@ -270,6 +276,14 @@ struct WUnitSchedule {
     // They are item targets like the entries themselves.  (feature_user children are expanded into the shared user entries above.)
     const int *iptr;
     const WinEnt *ient;
+    // hot shared user rows (window_shared_sub > 0, one-GPU window sequences only): nullptr hot = none in this window.  A hot entry is marked
+    // uent.pad = 1: the walk stores in its slot what the change is computed FROM that only the walk knows -- the private user's row and bias as
+    // it held them when it reached the data row -- and k_wunit_apply_shared walks the hot rows' slots in sub-steps of hot_sub.  Such a window has
+    // no in-place single applies, so everything else the apply kernel re-reads is still as of the window start.
+    const WinHot *hot;
+    const WinHotRec *hrec;
+    long nhot;
+    int hot_sub;
 };
 
 }  // namespace svdf

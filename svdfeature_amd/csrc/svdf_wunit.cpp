@@ -43,6 +43,8 @@ struct WUnitHost {
     std::vector<WinEnt> uent;
     std::vector<int> iptr;             // feature_item children, WUnitSchedule::iptr / ient; empty: none in the window
     std::vector<WinEnt> ient;
+    std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), WUnitSchedule::hot / hrec; empty: none in the window
+    std::vector<WinHotRec> hrec;
     bool has_touched = false;
     long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
     int fixed_ng = -2;
@@ -66,6 +68,7 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     S.uptr = sh ? ds->wu_uptr.p : nullptr; S.upos = sh ? ds->wu_upos.p : nullptr; S.uent = sh ? ds->wu_uent.p : nullptr;
     S.nshared_rows = ds->wu_nshared; S.shared_from = sh ? shared_user_from_ : 0u;
     S.iptr = ds->wu_ichild ? ds->wu_iptr.p : nullptr; S.ient = ds->wu_ichild ? ds->wu_ient.p : nullptr;
+    S.hot = ds->wu_nhot > 0 ? ds->wu_hot.p : nullptr; S.hrec = ds->wu_nhot > 0 ? ds->wu_hrec.p : nullptr; S.nhot = ds->wu_nhot; S.hot_sub = wseq_shared_sub_;
     return S;
 }
 
@@ -89,6 +92,13 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
               "window data sets: a feature_user side table needs amd:shared_user_from (its children are shared user rows, ids >= B)");
         check(!contrib_bf16_, "window data sets: feature_user / feature_item side tables need amd:contrib = fp32");
     }
+    if (wseq_shared_sub_ > 0) {   // ordered sub-steps for hot shared user rows: the one-GPU sequence of random-order rows, fp32 slots
+        check(!contrib_bf16_, "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) needs amd:contrib = fp32");
+        check(!user_group(), "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) is not supported with user-group (SVD++) trainers");
+        check(strcmp(what, "dataset_window_from_csr") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
+              "svdf_dataset_window_from_csr: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) is for the one-GPU window sequence "
+              "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) has no place for user rows");
+    }
     check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
@@ -107,7 +117,7 @@ void Engine::wunit_build(Dataset *ds, const void *segs_v, size_t nseg, const std
 }
 void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order,
                               long num_src_row, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children) const {
+                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children, int shared_sub) const {
     const HostSeg *segs = static_cast<const HostSeg *>(segs_v);
     const long NU = mp_.num_user, NI = mp_.num_item, NG = mp_.num_global, NF = user_group() ? (long)num_fb_rows() : 0;
     // side-table children (children: the one-GPU window sequence): [c0, c1) of an id into the table's columns
@@ -288,8 +298,14 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     // with the sum kernel's operations (apply_single, svdf_device.h) -- nobody else reads or writes that row inside the window
     // deferred feedback scatter: every feedback contribution keeps a slot (a record, not a row) -- the sum kernel forms (w + d val) - w itself
     const bool defer_fb = feedback && wunit_defer_fb_ != 0;
+    // ordered sub-steps (window_shared_sub): a shared user row with more than shared_sub contributions in this window is hot.
+    // A window with a hot row keeps a slot for EVERY contribution: k_wunit_apply_shared re-reads item rows, biases, globals and the other shared
+    // rows after the walk, and they must still be what they were at the window start.
+    if (shared_sub > 0 && has_shared)
+        for (long j = 0; j < NS; j++)
+            if (tptr[(size_t)(NF + NI + j) + 1] > shared_sub) H.hot.push_back(WinHot{(int)j, 0, 0, 0});
     std::vector<unsigned char> single;
-    if (inplace) {
+    if (inplace && H.hot.empty()) {
         single.assign((size_t)NT, 0);
         for (size_t t = defer_fb ? (size_t)NF : 0; t < (size_t)NT; t++) if (tptr[t + 1] == 1) { single[t] = 1; tptr[t + 1] = 0; }
     }
@@ -323,9 +339,36 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
             }
         }
     }
+    if (!H.hot.empty()) {   // the hot rows' slot ranges and records (slots are in file order: the record of a slot is found through its entry)
+        check(inplace, "window data sets: ordered sub-steps for shared user rows need the in-place sums (knob wunit_inplace = 1)");
+        std::vector<int> hot_of((size_t)NS, -1);
+        int rec = 0;
+        for (size_t q = 0; q < H.hot.size(); q++) {
+            WinHot &h = H.hot[q];
+            const size_t t = (size_t)(NF + NI) + (size_t)h.j;
+            h.b = tptr[t]; h.e = tptr[t + 1]; h.rec = rec;
+            rec += h.e - h.b;
+            hot_of[(size_t)h.j] = (int)q;
+        }
+        H.hrec.assign((size_t)rec, WinHotRec{0, 0});
+        for (long nr = 0; nr < nrow; nr++)
+            for (int e = H.uptr[(size_t)nr]; e < H.uptr[(size_t)nr + 1]; e++) {
+                WinEnt &u = H.uent[(size_t)e];
+                const int q = hot_of[u.idx];
+                if (q < 0) continue;
+                u.pad = 1;
+                H.hrec[(size_t)(H.hot[(size_t)q].rec + u.slot - H.hot[(size_t)q].b)] = WinHotRec{(int)nr, e};
+            }
+    }
     if (inplace) {   // the in-place sums visit only the targets that have slots (a window touches a fraction of the rows; singles keep none)
         H.has_touched = true;
-        for (size_t t = 0; t < (size_t)NT; t++) if (tptr[t + 1] > tptr[t]) H.touched.push_back(WinTouched{(int)t, tptr[t], tptr[t + 1]});
+        size_t q = 0;   // a hot row's entry carries e negated (WinTouched)
+        for (size_t t = 0; t < (size_t)NT; t++) {
+            if (tptr[t + 1] <= tptr[t]) continue;
+            const bool is_hot = q < H.hot.size() && (size_t)(NF + NI) + (size_t)H.hot[q].j == t;
+            q += is_hot;
+            H.touched.push_back(WinTouched{(int)t, tptr[t], is_hot ? -tptr[t + 1] : tptr[t + 1]});
+        }
     }
     for (size_t j = 0; j < nunit; j++) units[j].first = wsegs[(size_t)units[j].seg_begin];   // the first segment travels with the unit record
     H.nrow = nrow; H.nent = nent; H.nfbe = nfbe; H.fixed_ng = fixed_ng; H.unit_uval = unit_uval;
@@ -375,6 +418,11 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
         ds->wu_upos.upload(H.upos.data(), H.upos.size(), stream_);
         ds->wu_uent.upload(H.uent.data(), H.uent.size(), stream_);
     }
+    ds->wu_nhot = (long)H.hot.size();
+    if (ds->wu_nhot > 0) {
+        ds->wu_hot.upload(H.hot.data(), H.hot.size(), stream_);
+        ds->wu_hrec.upload(H.hrec.data(), H.hrec.size(), stream_);
+    }
     ds->wu_ichild = !H.iptr.empty();
     if (ds->wu_ichild) {
         ds->wu_iptr.upload(H.iptr.data(), H.iptr.size(), stream_);
@@ -401,7 +449,7 @@ void Engine::wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, co
 // number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.  The sequence also takes loaded
 // feature_user / feature_item tables: every child is a shared target, and no row may reach one target twice.
 void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
-                                 const float *feat_value, bool shared) const {
+                                 const float *feat_value, bool shared, int shared_sub) const {
     const long NU = mp_.num_user;
     const unsigned B = shared_user_from_;
     const bool children = shared && side_tables();
@@ -450,7 +498,7 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
         seg_rows[h.row_first + h.row_count++] = r;
     }
     wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, true, n, row_label, row_ptr, feat_index, feat_value, nullptr, nullptr,
-                     priv.empty() ? nullptr : priv.data(), children);
+                     priv.empty() ? nullptr : priv.data(), children, shared_sub);
 }
 // One row's side-table children (the one-GPU window sequence): a feature_user child is a shared user row (id >= amd:shared_user_from), and
 // a child must not reach a row the row already touches (its own entries or an earlier child) -- one contribution per target and row.  Two
@@ -690,6 +738,29 @@ bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_pt
     return !open;
 }
 
+// The window count the shared user rows ask for when hot ones move in ordered sub-steps (window_shared_sub > 0; modelled on wseq_windows_hot below).
+// Per class -- plain shared rows at window_per_target_shared, feature_user children at window_per_target_child -- the mean over entries of the
+// changes formed against ONE value of a row, sum_j min(c_j / W, window_shared_sub) c_j / sum_j c_j, stays at the class value; and no shared user row
+// meets more than window_shared_max updates per window (how stale everybody else's view of it gets: calibration in DESIGN.md section 6k).
+long Engine::wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child) const {
+    if (n <= 0) return 1;
+    long mx = 0;
+    for (long c : plain) mx = std::max(mx, c);
+    for (long c : child) mx = std::max(mx, c);
+    auto met = [&](const std::vector<long> &cnt, long W) {
+        double s = 0.0, s1 = 0.0;
+        for (long c : cnt) { s += std::min((double)c / (double)W, (double)wseq_shared_sub_) * (double)c; s1 += (double)c; }
+        return s1 > 0.0 ? s / s1 : 0.0;
+    };
+    auto ok = [&](long W) { return met(plain, W) <= (double)wseq_per_target_shared_ && met(child, W) <= (double)wseq_per_target_child_; };
+    long lo = std::max<long>(1, (mx + wseq_shared_max_ - 1) / wseq_shared_max_);
+    if (ok(lo)) return lo;
+    long hi = lo;
+    while (!ok(hi) && hi < n) hi *= 2;
+    while (lo + 1 < hi) { const long mid = (lo + hi) / 2; if (ok(mid)) hi = mid; else lo = mid; }
+    return hi;
+}
+
 Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
     wunit_check_config("dataset_from_csr", true);
     validate_csr_pointers(n, row_ptr);
@@ -717,9 +788,9 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
     }
     // side-table children: a row that is a child anywhere -- a feature_user child among the shared user rows, a feature_item
     // child among the item rows -- is a target of its own kind, with all its updates (as a plain entry too), at window_per_target_child
-    std::vector<long> cc;
+    std::vector<long> cc, ccu;   // (ccu: the feature_user children alone, for the rule with ordered sub-steps below)
     for (size_t i = 0; i < ichild.size(); i++) if (ichild[i]) { cc.push_back(ci[i]); ci[i] = 0; }
-    for (size_t j = 0; j < uchild.size(); j++) if (uchild[j]) { cc.push_back(cs[j]); cs[j] = 0; }
+    for (size_t j = 0; j < uchild.size(); j++) if (uchild[j]) { cc.push_back(cs[j]); ccu.push_back(cs[j]); cs[j] = 0; }
     // shared user rows are shared targets like item rows: the same rule (mean and most updates met per window), with a per-target mean of their
     // own (window_per_target_shared, 12: a bucket row met by 1/64 of all rows is far hotter than the items the 24 was calibrated on, and 24 left
     // |dRMSE| at 1.3e-4 on the SURVEY 8(d2) variant) and the common cap (window_per_target_max).  Expressed on the item term's scale.
@@ -727,14 +798,26 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
                                                   (double)wseq_per_target_ / (double)wseq_per_target_shared_;
     const double child_met = cc.empty() ? 0.0 : mean_updates_met(cc, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) *
                                                  (double)wseq_per_target_ / (double)wseq_per_target_child_;
-    const long W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
+    long W;
+    const int shared_sub = shared_user() ? wseq_shared_sub_ : 0;
+    if (shared_sub > 0) {
+        // ordered sub-steps for hot shared user rows: the user side leaves the common term -- its rows follow
+        // wseq_windows_shared -- and the item side keeps its own: item rows at window_per_target, feature_item children at window_per_target_child
+        cc.resize(cc.size() - ccu.size());
+        const double ichild_met = cc.empty() ? 0.0 : mean_updates_met(cc, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) *
+                                                      (double)wseq_per_target_ / (double)wseq_per_target_child_;
+        W = wseq_windows(n, {std::max(mean_updates_met(ci, wseq_max_ratio()), ichild_met), mean_updates_met(cg, wseq_max_ratio())});
+        if (!window_set_) W = std::max(W, wseq_windows_shared(n, cs, ccu));
+    } else
+        W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
+    ds->wseq_shared_sub = shared_sub;
     const bool inplace = wunit_inplace_ != 0;   // a window is summed in place right after its walk (wseq_train): single contributions need no slot
     wseq_build_windows(W, wseq_build_threads_,
         [&](long w, WUnitHost &H) {
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true);
+            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub);
         },
         [&](long, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
@@ -917,6 +1000,9 @@ void Engine::wseq_train(Dataset *ds) {
     const bool hot_lane = any_hot && wseq_hot_ok();
     if (any_hot) check(hot_lane, "train_dataset: the window sequence was built with ordered sub-steps for hot items (window_hot_sub); the configuration changed since");
     if (hot_lane) d_clabel_.reserve((size_t)max_slots);
+    if (ds->wseq_shared_sub >= 0)
+        check(ds->wseq_shared_sub == (shared_user() ? wseq_shared_sub_ : 0),
+              "train_dataset: the window sequence was built with another window_shared_sub (ordered sub-steps for hot shared user rows); build the data set again after changing the knob");
     for (Dataset *c : ds->wchild) {
         if (c->kind == 5) {
             d_contrib_.reserve((size_t)std::max<long>(c->win_slots, 1) * (size_t)pitch_);
@@ -928,6 +1014,9 @@ void Engine::wseq_train(Dataset *ds) {
             else launch_window_items_local(S, pitch_, mp_.num_factor, 0, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_, c->win_slots);
         } else {
             wunit_train(c);
+            // hot shared user rows in ordered sub-steps: after the walk (its records) and before the sums (which move the finished rows in); the
+            // workgroups run one hot row each, so the launch lasts as long as the hottest row's chain of sub-steps
+            if (c->wu_nhot > 0) { launch_wunit_apply_shared(P, wunit_view(c), stream_); n_launches_++; }
             wunit_sum(c, nullptr, 0);
         }
         n_launches_ += 2;
