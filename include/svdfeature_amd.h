@@ -54,7 +54,18 @@ void svdf_destroy(svdf_trainer *t);
  * and :456-476, ParameterSet prefixes up:/ip:/uip:/gp: apex_svd_base.h:48-67).  Unknown keys are
  * ignored, model-shape keys are ignored once the model is allocated.  Extension keys (ignored by the reference): amd:gpus, amd:exchange,
  * amd:step, amd:contrib, amd:window, amd:window_per_target(_max), amd:relax_* (see svdf_set_knob below) and amd:shared_user_from = B
- * (shared user rows in the one-GPU window step). */
+ * (shared user rows in the one-GPU window step).
+ * amd:step on ONE GPU (opt-in; not the reference's sequential result, contract |dRMSE| <= 1e-4): `minibatch` trains with the window step,
+ * `auto` decides between it and the exact levels from the data's dependency depth, `levels` (and no key) is the exact step.  The key covers
+ * resident data sets (svdf_dataset_from_* + svdf_train_dataset) AND the staged route (svdf_update_csr / _csr_batch / _block, what the
+ * reference's CLI drives): a chunk -- the rows staged between two flush points: stage_window rows, finish_round, predict,
+ * save_model, set_round, set_param, destroy -- trains exactly as svdf_dataset_from_X(chunk) + svdf_train_dataset + svdf_dataset_destroy would
+ * on the same handle state, X = triples (plain ratings), pairs (rank pairs in the generator's shape), csr (anything else on a random-order
+ * trainer; amd:shared_user_from, side tables and window_shared_sub as on the resident path) or blocks (user-group trainers: the automatic
+ * flush waits for the open user's END -- for at most 4 x stage_window staged rows, then it flushes like the default route; at any flush with
+ * a user still open, that user and its continuation keep the exact unit path, which is normal and not counted).  A chunk whose rows or configuration the
+ * window step does not cover keeps the exact flush -- never an error; the first one prints one stderr line naming the rule.  `auto` decides
+ * on the first chunk of at least device_schedule_min rows and keeps the decision until the next svdf_set_param. */
 int svdf_set_param(svdf_trainer *t, const char *name, const char *val);
 /* apex_random::seed (apex-tensor/apex_random.h:42-44) -> srand; process-global like the reference. */
 void svdf_seed(unsigned seed);
@@ -312,13 +323,18 @@ int svdf_synchronize(svdf_trainer *t);
  * 22 / 23 passes over hot-row units / runs, 24 microseconds the schedule of the last user-unit data set took, 25 whether the device built it,
  * 26 data sets whose DEFAULT (exact) step drew the depth warning (a stderr line naming `amd:step = auto`: the level schedule predicts the pass
  * more than 10 x slower than the streaming model), 27 / 28 the last noted data set's dag bound / stream model in microseconds,
- * 29 passes over rank pairs walked as user-run units */
+ * 29 passes over rank pairs walked as user-run units,
+ * 30 staged chunks trained by the window step (amd:step = minibatch / auto on the staged route of a one-GPU handle), 31 staged chunks kept
+ * exact under those keys because their rows or the configuration are outside the window step, 32 depth warnings of the DEFAULT step about
+ * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except the seven marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
  *   staging / launches
  *     stage_window        2^21   instances staged by svdf_update_* before an automatic flush (also set by the config key amd:window)
  *     async_flush         1      full staged windows are scheduled on a background thread
+ *     staged_pool         1      amd:step = minibatch / auto on the staged route: the per-chunk window sequence takes its device blocks from a
+ *                                pool kept on the handle (0 = hipMalloc / hipFree per chunk: A/B, same bits)
  *     use_graph           0      1 = a resident data set's pass is replayed as a captured hipGraph
  *     groups_per_wave     0      lane-group sets per wave of the contract / few-row kernels (0 = tuned per width; 1..6, 8)
  *     block_threads       0      workgroup size (0 = tuned per width; 64, 128, 256)

@@ -111,6 +111,7 @@ void config_set_model_param(ModelParam &p, const char *name, const char *val) { 
 void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:126-136
     if (save_async_.active) save_model_end();   // (the asynchronous writer reads mp_ live)
     if (trainer_ready_ && !host_only_) flush();   // staged instances were issued under the old parameters
+    staged_auto_decision_ = 0;                    // amd:step = auto on the staged route: the next chunk of at least device_schedule_min rows decides again
     // N GPUs behind one handle (svdf_multi.cpp): extension keys, ignored by the reference like any unknown key
     if (!strcmp(name, "amd:gpus")) {
         check(!multi_ && !space_allocated_, "amd:gpus must be set before the model is created");
@@ -130,6 +131,7 @@ void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:
         multi_step_levels_ = !strcmp(val, "levels");
         step_minibatch_set_ = !strcmp(val, "minibatch");   // one GPU: opt-in window-minibatch SGD (svdf_wunit.cpp: resident data sets become window sequences)
         step_auto_set_ = !strcmp(val, "auto");             // one GPU: opt-in, decided per resident data set from its level schedule (svdf_dataset.cpp: auto_step)
+        // both keys also apply to the rows staged by svdf_update_csr / _csr_batch / _block on a one-GPU handle (svdf_staged.cpp)
     }
     if (!strcmp(name, "amd:contrib")) {   // window-minibatch step: storage format of the contribution rows (sums are fp32 either way)
         check(!strcmp(val, "fp32") || !strcmp(val, "bf16"), "amd:contrib must be fp32 or bf16");
@@ -206,6 +208,10 @@ int64_t Engine::counter(int what) const {
     case 27: return (int64_t)(guard_last_.dag_ms * 1000.0);       // ... the last noted data set's dag bound / stream model, microseconds
     case 28: return (int64_t)(guard_last_.stream_ms * 1000.0);
     case 29: return n_punit_passes_;   // passes over rank pairs walked as user-run units (svdf_punit.cpp)
+    // amd:step = minibatch | auto on the staged route of a one-GPU handle (svdf_staged.cpp)
+    case 30: return n_staged_window_;  // staged chunks trained by the window step
+    case 31: return n_staged_exact_;   // staged chunks kept exact because their rows or the configuration are outside the window step
+    case 32: return n_staged_guard_;   // guard lines of the DEFAULT step about staged chunks (at most one per handle)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -253,6 +259,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "use_simple_units")) { use_simple_units_ = value != 0; return 0; }
     if (!strcmp(name, "rows_without_feedback")) { rows_without_feedback_ = value != 0; return 0; }
     if (!strcmp(name, "fewrow_gslots")) { fewrow_gslots_ = value != 0; launch_version_++; return 0; }
+    if (!strcmp(name, "staged_pool")) { check(value == 0 || value == 1, "staged_pool must be 0 or 1"); flush(); staged_pool_mode_ = (int)value; return 0; }
     if (!strcmp(name, "wunit_inplace")) { wunit_inplace_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_defer_fb")) { wunit_defer_fb_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_fast")) { check(value >= 0 && value <= 2, "wunit_fast must be 0, 1 or 2"); wunit_fast_ = (int)value; return 0; }

@@ -118,7 +118,7 @@ Dataset *Engine::dataset_from_blocks(long num_block, const int *extend_tag, cons
                      row_label + r0, ptr32.data(), feat_index + e0, feat_value + e0);
     }
     stage_window_ = saved_window;
-    auto drop = [&]() { staged_.clear(); staged_units_.clear(); staged_fb_index_.clear(); staged_fb_value_.clear(); unit_open_ = false; unit_open_on_device_ = false; };
+    auto drop = [&]() { staged_.clear(); staged_units_.clear(); staged_fb_index_.clear(); staged_fb_value_.clear(); staged_blks_w_.clear(); unit_open_ = false; unit_open_on_device_ = false; };
     if (unit_open_) { drop(); fail("dataset_from_blocks: the last user's END block is missing"); }
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 3; ds->num_row = staged_.num_row();

@@ -132,6 +132,10 @@ Engine::~Engine() {
             worker_.join();
         }
         (void)hipStreamSynchronize(stream_);
+        if ((getenv("SVDF_PROFILE") || getenv("SVDF_VERBOSE")) && n_staged_window_ + n_staged_exact_ > 0)   // what amd:step = minibatch | auto did on the staged route
+            fprintf(stderr, "[svdfeature_amd] staged route: %ld chunks trained by the window step, %ld kept exact (rows or configuration outside it); window build %.3fs of the flush time (user-unit windows: host regrouping %.3fs, allocations + uploads + synchronisations %.3fs); "
+                            "device blocks from the handle's pool %ld, from hipMalloc %ld\n",
+                    (long)n_staged_window_, (long)n_staged_exact_, ns_staged_build_ * 1e-9, ns_wseq_host_ * 1e-9, ns_wseq_adopt_ * 1e-9, (long)staged_pool_.n_taken, (long)staged_pool_.n_missed);
         if (pred_pin_) (void)hipHostFree(pred_pin_);
         save_pipe_free(save_pipe_);
         save_pipe_free(save_async_.pipe);
@@ -400,7 +404,13 @@ void Engine::update_block(int nfb, int tag, const unsigned *ifb, const float *vf
     } else {
         unit_open_ = true;
     }
-    if (staged_.num_row() >= stage_window_) flush();
+    // amd:step = minibatch | auto (svdf_staged.cpp): the blocks as handed over, and the automatic flush waits for the open user's END -- a window
+    // sequence holds whole START .. END spans
+    const bool window_live = staged_window_live();
+    if (window_live) staged_blks_w_.push_back(StagedBlk{tag, (int)staged_units_.size() - 1, h, h + num_row});
+    // (bounded: a user still open after staged_defer_factor_ x stage_window rows is flushed like on the default route -- its closed predecessors as
+    // windows, the open user through the exact unit path)
+    if (staged_.num_row() >= stage_window_ && !(window_live && unit_open_ && staged_.num_row() < staged_defer_factor_ * stage_window_)) flush();
 }
 
 // ---- extend_type 2: SVDPPMultiIMFB::update (apex_multi_imfb.h:173-192) staged as blocks; a unit is a run of blocks from an
@@ -491,7 +501,7 @@ void Engine::upload_iunits(UnitDev &d, const Schedule &sched) {
 }
 void Engine::drop_staged_units() {
     staged_.clear(); staged_units_.clear(); staged_fb_index_.clear(); staged_fb_value_.clear();
-    staged_blks_.clear(); staged_iunits_.clear();
+    staged_blks_.clear(); staged_iunits_.clear(); staged_blks_w_.clear();
 }
 void Engine::flush_iunits() {
     if (staged_iunits_.empty()) { drop_staged_units(); return; }

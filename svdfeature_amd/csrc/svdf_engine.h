@@ -21,6 +21,7 @@
 #include <deque>
 #include <functional>
 #include <future>
+#include <map>
 #include <vector>
 
 #include "svdf_types.h"
@@ -37,6 +38,35 @@ void pin_malloc_threshold();   // svdf_engine.cpp: glibc's dynamic mmap threshol
 struct MultiScope { MultiScope(); ~MultiScope(); MultiScope(const MultiScope &) = delete; MultiScope &operator=(const MultiScope &) = delete; };
 
 // --------------------------------------------------------------------------- device memory
+// A handle's cache of device blocks (svdf_staged.cpp): while a DevPoolScope is open on the calling thread, DevBuf takes its blocks from the
+// pool and gives them back to it instead of hipMalloc / hipFree (a hipFree waits for the device).  The transient window sequences of the
+// staged route are built, trained once and dropped every stage_window rows inside such a scope: their blocks go round.
+// The pool holds a WHOLE sequence, however many windows it has (blocks ordered by size; no cap on their number).  It is trimmed at the end
+// of every chunk: a block that no buffer took during the last two chunks is freed, so the pool follows the size of the recent sequences.
+// A hipMalloc that fails inside a scope empties the pool and is tried once more.
+// Everything that reads or writes a block is ordered on the handle's ONE stream, so a block may change hands while kernels are still queued.
+struct DevPool {
+    struct Block { void *p; long gen; };
+    std::multimap<size_t, Block> blocks;     // by size in bytes
+    long gen = 0;                            // chunks finished so far (end_chunk)
+    int64_t n_taken = 0, n_missed = 0;       // requests served from the pool / by hipMalloc inside a scope
+    DevPool() = default;
+    DevPool(const DevPool &) = delete;
+    DevPool &operator=(const DevPool &) = delete;
+    ~DevPool() { drop(); }
+    void drop();
+    void *take(size_t bytes, size_t &got);   // nullptr: nothing that fits
+    void give(void *p, size_t bytes);
+    void end_chunk();                        // trims what the last two chunks did not use
+};
+DevPool *dev_pool_current();                 // the pool of the calling thread's open scope, or nullptr
+struct DevPoolScope {
+    DevPool *prev;
+    explicit DevPoolScope(DevPool *p);
+    ~DevPoolScope();
+    DevPoolScope(const DevPoolScope &) = delete;
+    DevPoolScope &operator=(const DevPoolScope &) = delete;
+};
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
@@ -46,7 +76,10 @@ struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { release(); }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) {
+            if (DevPool *pool = dev_pool_current()) pool->give(p, cap * sizeof(T));
+            else (void)hipFree(p);
+        }
         p = nullptr;
         cap = 0;
     }
@@ -54,7 +87,17 @@ struct DevBuf {
         if (n <= cap && p) return;
         release();
         const size_t want = n ? n : 1;
+        DevPool *pool = dev_pool_current();
+        if (pool) {
+            size_t got = 0;
+            if (void *q = pool->take(want * sizeof(T), got)) { p = static_cast<T *>(q); cap = got / sizeof(T); return; }
+        }
         hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        if (e != hipSuccess && pool && !pool->blocks.empty()) {   // the cached blocks may be what is in the way
+            (void)hipGetLastError();
+            pool->drop();
+            e = hipMalloc((void **)&p, want * sizeof(T));
+        }
         if (e != hipSuccess) fail(std::string("HIP error: ") + hipGetErrorString(e) + " at hipMalloc (DevBuf::reserve)");
         cap = want;
     }
@@ -617,6 +660,7 @@ class Engine {
     void wunit_check_config(const char *what, bool side_tables = false) const;
     bool side_tables() const { return feat_user_.num_row() != 0 || feat_item_.num_row() != 0; }
     void side_children_ok(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // svdf_wunit.cpp
+    const char *side_children_rule(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;
     bool wunit_config_ok() const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
     void wunit_build(Dataset *ds, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                      const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
@@ -720,6 +764,29 @@ class Engine {
     DevBuf<double> d_partials_;
     struct Range { float *base; long n; };
     std::vector<Range> shared_ranges();
+    // ---- `amd:step = minibatch | auto` on the staged route of a one-GPU handle (svdf_staged.cpp): a chunk of staged
+    // rows is trained as the window sequence svdf_dataset_from_* would build from it; chunks the window step does not cover keep the exact flush
+    bool staged_step_wanted() const { return (step_minibatch_set_ || step_auto_set_) && gpus_ == 1 && !multi_ && !is_peer_ && !host_only_; }
+    const char *staged_config_rule(bool blocks) const;   // nullptr: the configuration is inside the window step, else the rule that keeps it out
+    bool staged_window_csr(HostCSR &src);                // true: the chunk was trained by the window step (src is cleared)
+    bool staged_window_units();                          // the same for the closed units of a user-group trainer (flush_units)
+    bool staged_window_live() const { return staged_step_wanted() && !auto_building_ && (!step_auto_set_ || staged_auto_decision_ == 0 || staged_auto_decision_ == 2); }
+    bool staged_auto_decide(long n, int kind, long units, long levels, long bytes, const char *rule, const std::function<Dataset *()> &build_window, Dataset *&out);
+    void flush_units_exact();                            // the level-scheduled unit flush (svdf_sched.cpp)
+    void staged_train(Dataset *seq);                     // trains and drops a transient window sequence
+    void staged_keep_exact(const char *rule);            // counter 31 and, once per handle, one stderr line naming the rule
+    void staged_guard(long n, long levels, double unit_us, long bytes);   // the default step's guard for staged chunks (counter 32)
+    struct StagedBlk { int tag, unit, row_begin, row_end; };   // unit: index into staged_units_
+    std::vector<StagedBlk> staged_blks_w_;               // user-group trainers: the staged blocks as handed over (wseq_from_blocks cuts windows in blocks)
+    int staged_auto_decision_ = 0;                       // amd:step = auto: 0 not taken yet, else auto_last_.decided of the chunk it was taken on
+    int64_t n_staged_window_ = 0, n_staged_exact_ = 0, n_staged_guard_ = 0;
+    int64_t ns_staged_build_ = 0;                        // host time of the per-chunk pre-check + window build (part of ns_flush_; SVDF_PROFILE prints it)
+    int64_t ns_wseq_host_ = 0, ns_wseq_adopt_ = 0;       // user-unit window sequences (wseq_build_windows): wall time of the host regrouping / of the windows' allocations + uploads + synchronisations
+    std::string staged_auto_rule_;                       // amd:step = auto, decision 3: the rule that keeps the chunks exact
+    long staged_defer_factor_ = 4;                       // a user still open after this many stage_window rows no longer holds back the automatic flush
+    bool staged_exact_said_ = false;
+    DevPool staged_pool_;
+    int staged_pool_mode_ = 1;                           // knob "staged_pool": 0 = hipMalloc / hipFree per chunk (A/B; same bits), 1 = the handle's pool
     // ---- N GPUs behind this handle (svdf_multi.cpp)
     int gpus_ = 1;
     bool is_peer_ = false, delta_half_ = true, window_set_ = false;

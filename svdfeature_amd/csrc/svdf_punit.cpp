@@ -150,6 +150,7 @@ bool Engine::punit_flush(HostCSR &src) {
     sample_counter_ += (unsigned)n;
     n_flushes_++;
     n_punit_passes_++;
+    staged_guard(n, (long)L, 3.0 + 0.7 * (double)n / (double)std::max<size_t>(sorted.size(), 1), n * (8L * mp_.num_factor * 3 + 8 * ((mp_.no_user_bias ? 0 : 1) + 2) + 16 + 8 * 3));
     src.clear();
     return true;
 }

@@ -106,6 +106,7 @@ void sort_batches(Schedule &sched, const unsigned *key) {
 void Engine::flush_csr(HostCSR &src) {
     const long n = src.num_row();
     if (n == 0) return;
+    if (staged_step_wanted() && staged_window_csr(src)) return;   // amd:step = minibatch | auto: the chunk as a window sequence (svdf_staged.cpp)
     if (punit_flush(src)) return;   // a window of user-grouped rank pairs: user-run units (svdf_punit.cpp)
     need_device("update");
     const DevParams &P = params();
@@ -150,6 +151,7 @@ void Engine::flush_csr(HostCSR &src) {
         n_instances_ += n;
         sample_counter_ += (unsigned)n;
         n_flushes_++;
+        staged_guard(n, (long)sc.num_levels(), 4.5, n * (8L * mp_.num_factor * 2 + 8 * (mp_.no_user_bias ? 1 : 2) + 16 + 16));
         src.clear();
         return;
     }
@@ -221,6 +223,11 @@ void Engine::flush_csr(HostCSR &src) {
     n_instances_ += n;
     sample_counter_ += (unsigned)n;
     n_flushes_++;
+    if ((double)sched.num_levels() * 4.5e-3 >= 50.0) {   // (the guard's floor: only a deep chunk is worth counting its entries)
+        long rows_ui = 0;
+        for (long r = 0; r < n; r++) rows_ui += src.row_ptr[(size_t)3 * r + 3] - src.row_ptr[(size_t)3 * r + 1];
+        staged_guard(n, (long)sched.num_levels(), 4.5, 8L * mp_.num_factor * rows_ui + n * (8L * (mp_.no_user_bias ? 1 : 2) + 16) + 8L * (long)src.feat_index.size());
+    }
     src.clear();
 }
 
@@ -480,8 +487,13 @@ bool Engine::schedule_units_on_device(UnitDev &d, Schedule &sched, std::vector<D
 }
 
 void Engine::flush_units() {
+    if (staged_units_.empty()) { staged_.clear(); staged_blks_w_.clear(); return; }
+    if (staged_step_wanted() && staged_window_units()) return;   // amd:step = minibatch | auto: the closed units as a window sequence (svdf_staged.cpp)
+    flush_units_exact();
+}
+void Engine::flush_units_exact() {
     const long nu = (long)staged_units_.size();
-    if (nu == 0) { staged_.clear(); return; }
+    if (nu == 0) { staged_.clear(); staged_blks_w_.clear(); return; }
     need_device("update");
     const DevParams &P = params();
     const int base = tracker_.base;
@@ -506,8 +518,11 @@ void Engine::flush_units() {
     n_instances_ += n;
     sample_counter_ += (unsigned)n;
     n_flushes_++;
+    staged_guard(n, (long)sched.num_levels(), 5.0 + 0.42 * (double)n / (double)nu,
+                 n * (8L * mp_.num_factor * 2 + 8 * (mp_.no_user_bias ? 1 : 2) + 16 + 16) + (long)staged_fb_index_.size() * (12L * mp_.num_factor + 20));
     if (unit_open_) unit_open_on_device_ = true;
     staged_.clear();
+    staged_blks_w_.clear();
     staged_units_.clear();
     staged_fb_index_.clear();
     staged_fb_value_.clear();

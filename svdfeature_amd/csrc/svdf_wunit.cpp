@@ -504,6 +504,10 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
 // a child must not reach a row the row already touches (its own entries or an earlier child) -- one contribution per target and row.  Two
 // plain entries with one id keep the builder's own messages.
 void Engine::side_children_ok(const int64_t *p, const unsigned *feat_index, std::vector<unsigned> &seen) const {
+    if (const char *rule = side_children_rule(p, feat_index, seen)) fail(rule);
+}
+// the same test as a predicate (the staged route decides without raising, svdf_staged.cpp): nullptr, or the message of the rule the row breaks
+const char *Engine::side_children_rule(const int64_t *p, const unsigned *feat_index, std::vector<unsigned> &seen) const {
     const unsigned B = shared_user_from_;
     for (int side = 0; side < 2; side++) {
         const SideTable &T = side == 0 ? feat_user_ : feat_item_;
@@ -515,15 +519,16 @@ void Engine::side_children_ok(const int64_t *p, const unsigned *feat_index, std:
             if (id >= T.num_row()) continue;
             for (unsigned c = T.row_ptr[id]; c < T.row_ptr[id + 1]; c++) {
                 const unsigned x = T.index[c];
-                if (side == 0)
-                    check(x >= B, "window data sets: a feature_user child below amd:shared_user_from (it would be another unit's private user row)");
+                if (side == 0 && x < B)
+                    return "window data sets: a feature_user child below amd:shared_user_from (it would be another unit's private user row)";
                 for (unsigned y : seen)
-                    if (y == x) fail(side == 0 ? "window data sets: a row reaches one user row twice through feature_user children (each row may touch a target once)"
-                                               : "window data sets: a row reaches one item row twice through feature_item children (each row may touch a target once)");
+                    if (y == x) return side == 0 ? "window data sets: a row reaches one user row twice through feature_user children (each row may touch a target once)"
+                                                 : "window data sets: a row reaches one item row twice through feature_item children (each row may touch a target once)";
                 seen.push_back(x);
             }
         }
     }
+    return nullptr;
 }
 
 // ---- one exchange window of a user-group pass: blocks [b0, b1), every START closed by its END inside the window
@@ -652,7 +657,7 @@ static double mean_updates_met(const std::vector<long> &cnt, double per_mean_ove
 // host's hardware threads, at most 32 and at most `wseq_build_threads`), a batch of windows at a time; uploads stay with the calling thread,
 // in window order.  A failure inside a worker is reported by the calling thread (the error text is thread-local).
 template <typename BuildFn, typename AdoptFn>
-static void wseq_build_windows(long W, int max_threads, BuildFn build, AdoptFn adopt_window) {
+static void wseq_build_windows(long W, int max_threads, BuildFn build, AdoptFn adopt_window, int64_t &ns_host, int64_t &ns_adopt) {
     const long hw = (long)std::thread::hardware_concurrency();
     const long T = std::max<long>(1, std::min<long>(std::min<long>(W, max_threads), std::max<long>(1, std::min<long>(32, hw / 4))));
     for (long w0 = 0; w0 < W; w0 += T) {
@@ -664,6 +669,7 @@ static void wseq_build_windows(long W, int max_threads, BuildFn build, AdoptFn a
             try { build(w0 + j, H[(size_t)j]); }
             catch (const std::exception &e) { failed[(size_t)j] = 1; err[(size_t)j] = e.what(); }
         };
+        std::unique_ptr<ScopedNs> timer(new ScopedNs(ns_host));   // wall time of the batch's host builds ...
         if (nb == 1) work(0);
         else {
             std::vector<std::thread> th;
@@ -671,7 +677,9 @@ static void wseq_build_windows(long W, int max_threads, BuildFn build, AdoptFn a
             work(0);
             for (auto &t : th) t.join();
         }
+        timer.reset();
         for (long j = 0; j < nb; j++) if (failed[(size_t)j]) fail(err[(size_t)j]);
+        ScopedNs adopt_timer(ns_adopt);                            // ... and of its windows' allocations, uploads and synchronisations
         for (long j = 0; j < nb; j++) { adopt_window(w0 + j, H[(size_t)j]); H[(size_t)j] = WUnitHost(); }
     }
 }
@@ -825,7 +833,7 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
             wunit_adopt(c.get(), H);
             ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
             ds->wchild.push_back(c.release());
-        });
+        }, ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
     return ds.release();
@@ -886,7 +894,7 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
             wunit_adopt(c.get(), H);
             ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
             ds->wchild.push_back(c.release());
-        });
+        }, ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = n;
     return ds.release();
