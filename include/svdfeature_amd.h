@@ -61,7 +61,7 @@ void svdf_destroy(svdf_trainer *t);
  * reference's CLI drives): a chunk -- the rows staged between two flush points: stage_window rows, finish_round, predict,
  * save_model, set_round, set_param, destroy -- trains exactly as svdf_dataset_from_X(chunk) + svdf_train_dataset + svdf_dataset_destroy would
  * on the same handle state, X = triples (plain ratings), pairs (rank pairs in the generator's shape), csr (anything else on a random-order
- * trainer; amd:shared_user_from, side tables and window_shared_sub as on the resident path) or blocks (user-group trainers: the automatic
+ * trainer; amd:shared_user_from, side tables, window_shared_sub and window_item_sub as on the resident path) or blocks (user-group trainers: the automatic
  * flush waits for the open user's END -- for at most 4 x stage_window staged rows, then it flushes like the default route; at any flush with
  * a user still open, that user and its continuation keep the exact unit path, which is normal and not counted).  A chunk whose rows or configuration the
  * window step does not cover keeps the exact flush -- never an error; the first one prints one stderr line naming the rule.  `auto` decides
@@ -328,7 +328,7 @@ int svdf_synchronize(svdf_trainer *t);
  * exact under those keys because their rows or the configuration are outside the window step, 32 depth warnings of the DEFAULT step about
  * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only) */
 int64_t svdf_counter(svdf_trainer *t, int what);
-/* Tuning knobs (not part of the reference surface).  None changes a result bit except the seven marked (*), which move the windows of the
+/* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
  *   staging / launches
  *     stage_window        2^21   instances staged by svdf_update_* before an automatic flush (also set by the config key amd:window)
@@ -373,6 +373,15 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               sequence built with another window_shared_sub.  Refused with amd:contrib = bf16, user-group trainers,
  *                                                               amd:gpus > 1 / svdf_dataset_window_from_csr.  12 with the defaults: 4.0x the 6i rule at |dRMSE| <= 6.9e-5
  *                                                               on the side-feature variant (profiles/r09_shared_hot.md); does not pay on the 6j table variant
+ *     window_item_sub (*) 0, window_item_max (*) 2048           the same lane for the ITEM range of such sequences (any row set that takes the csr path: global features, shared user
+ *                                                               ids, side tables): an item row -- a plain item entry's row, a feature_item child's row, or both --
+ *                                                               with more than window_item_sub (0 .. 128) slots in a window moves in ordered sub-steps of that many
+ *                                                               (k_wunit_apply_hot; 0 = off, the default: the rule and bits as before) and meets at most window_item_max
+ *                                                               updates per window; the class means (window_per_target / _child) then bound min(updates per window,
+ *                                                               window_item_sub).  Works with and without amd:shared_user_from and next to window_shared_sub.  Set before the
+ *                                                               data set is built: train_dataset refuses a sequence built with another window_item_sub.  Refused with
+ *                                                               amd:contrib = bf16, user-group trainers, amd:gpus > 1 / svdf_dataset_window_from_csr, wunit_inplace = 0.
+ *                                                               Calibration: profiles/r11_item_hot.md
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is

@@ -318,8 +318,10 @@ struct Dataset {
     bool wu_ichild = false;        // the window has feature_item children
     DevBuf<WinHot> wu_hot;         // hot shared user rows of the window (ordered sub-steps, knob window_shared_sub) and their records
     DevBuf<WinHotRec> wu_hrec;
-    long wu_nhot = 0;
+    long wu_nhot = 0;              // hot shared user rows: wu_hot[0 .. wu_nhot)
+    long wu_nihot = 0;             // hot item rows (knob window_item_sub): wu_hot[wu_nhot .. wu_nhot + wu_nihot), records in wu_hrec too
     int wseq_shared_sub = -1;      // kind 8 from wseq_from_csr (else -1): window_shared_sub when the sequence was built (train_dataset refuses another value)
+    int wseq_item_sub = -1;        // the same for window_item_sub
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
     std::vector<Dataset *> wchild;
     // kind 6: a data set of an amd:gpus = N handle (svdf_multi.cpp): mchild[rank][window] lives in that rank's HBM
@@ -667,10 +669,10 @@ class Engine {
                      const unsigned *fb_index, const float *fb_value);
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                          const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr, bool children = false, int shared_sub = 0) const;
+                          const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr, bool children = false, int shared_sub = 0, int item_sub = 0) const;
     void wunit_adopt(Dataset *ds, const WUnitHost &H);
     void wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                             bool shared = false, int shared_sub = 0) const;
+                             bool shared = false, int shared_sub = 0, int item_sub = 0) const;
     void wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                                 const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) const;
     int wseq_build_threads_ = 32;         // knob "wseq_build_threads": host threads building the windows of a one-GPU window sequence (user units)
@@ -696,12 +698,15 @@ class Engine {
     // ordered sub-steps for hot items of a one-GPU window sequence of plain ratings (svdf_k_window.hip: k_window_apply; round 6)
     int wseq_shared_sub_ = 0;             // knob "window_shared_sub": a shared user row (id >= amd:shared_user_from, feature_user children included) with more slots than this in a window of wseq_from_csr is applied in ordered sub-steps of this many (k_wunit_apply_shared); 0 = off
     int wseq_shared_max_ = 512;           // knob "window_shared_max": the most updates a hot shared user row may meet per window (how stale everybody else's view of it gets); side-feature variant at the 20 M-row prefix, window_shared_sub 12, 3 seeds: 256 max |dRMSE| 7.2e-5 / 191 ms per pass, 512 6.9e-5 / 172 ms, 1 024 1.06e-4 (profiles/r09_shared_hot.md)
+    int wseq_item_sub_ = 0;               // knob "window_item_sub" (0 .. 128): an item-range row (a plain item entry's row, a feature_item child's row) with more slots than this in a window of wseq_from_csr is applied in ordered sub-steps of this many (k_wunit_apply_hot<ITEM>); 0 = off
+    int wseq_item_max_ = 2048;            // knob "window_item_max": the most updates a hot item row may meet per window (how stale everybody else's view of it gets); the largest swept value: Zipf(0.7) items + 4 globals, 2 M rows, 3 seeds, sub 8 / 24 / 128: max |dRMSE| 6.0e-6 / 2.3e-6 / 2.2e-5 (profiles/r11_item_hot.md)
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)
     int wseq_hot_max_ = 2048;             // knob "window_hot_max": the most updates a hot row may meet per window (how stale the USERS' view of it gets); 3 seeds of Zipf(0.7) at the configs[1] size: 1 024 max |dRMSE| 4.2e-5 / 66 ms per pass, 2 048 6.6e-5 / 55 ms, 3 072 7.2e-5 / 52 ms (profiles/r06_hot_lane_calibration.txt)
     DevBuf<float> d_clabel_;
     bool wseq_hot_ok() const;             // the configuration has the hot lane (unit ratings, fp32 contribution rows, one GPU)
     long wseq_windows_hot(long n, const std::vector<long> &item_count) const;
-    long wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child) const;   // window_shared_sub > 0: what the shared user rows ask for
+    // ordered sub-steps of `sub` with at most `cap` updates per row and window: what the rows of two classes (means per_plain / per_child) ask for
+    long wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const;
     double wseq_max_ratio() const { return (double)wseq_per_target_ / (double)wseq_per_target_max_; }
     int wseq_per_target_ = 24;            // knob "window_per_target": updates a shared row meets per window when amd:window is not given
     bool single_minibatch() const { return step_minibatch_set_ && gpus_ == 1 && !multi_ && !is_peer_; }

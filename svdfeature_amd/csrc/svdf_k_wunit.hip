@@ -30,7 +30,8 @@ namespace svdf {
 // Side-table children: feature_user children are shared user entries (the builder expands them); feature_item children
 // (S.iptr) follow their parent entry in every loop, with the reference's item-side forms for parent value ival and child value v: bias term
 // (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
-// HOT: the window has hot shared user rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the code as it was.
+// HOT: the window has hot shared user rows or hot item rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the
+// code as it was.
 template <int LPI, bool FB, bool HOT = false>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     constexpr int IPW = 64 / LPI;
@@ -118,6 +119,11 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             float nbu = bu + su;
             for (int j = e1; j < e2; j++) {
                 const WinEnt e = S.ent[j];
+                if (HOT && e.pad) {   // a hot item row of this window (k_wunit_apply_hot<ITEM>): the same record as for a hot shared user row below
+                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
+                    if (L == 0) S.cbias[e.slot] = bu;
+                    continue;
+                }
                 const float si = lr * err * e.val;
                 const float4 q = load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k);
                 const float bi = P.bias[P.item_off + e.idx];
@@ -139,6 +145,11 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 const float ival = S.ent[j].val;
                 for (; c < c1 && S.ient[c].pad == j; c++) {
                     const WinEnt ch = S.ient[c];
+                    if (HOT && ch.slot < -1) {   // a hot child (its slot travels as -2 - slot: ient.pad is taken by the parent's position)
+                        store_contrib<LPI>(S.contrib, 0, (size_t)(-2 - ch.slot), pitch, L, k, p);
+                        if (L == 0) S.cbias[-2 - ch.slot] = bu;
+                        continue;
+                    }
                     const float si = lr * err * ch.val * ival;
                     const size_t row = (size_t)P.item_off + ch.idx;
                     const float4 q = load_row<LPI>(P.W, row, pitch, L, k);
@@ -485,7 +496,7 @@ __global__ __launch_bounds__(256) void k_wunit_fast(const DevParams P, const WUn
 //   else:  the wire buffer of the exchange, dst = [T rows of `pitch` | T biases | nglobal global biases] (the packed layout of
 //          Engine::delta_ranges for the whole item range), fp32 or fp16.
 // The global biases' sums (gptr over gcontrib) are taken by the same launch, one thread per global id.
-template <int LPI, bool HALF, bool LOCAL, bool HOT = false>   // HOT: the touched list may hold hot shared user rows (in-place sums only)
+template <int LPI, bool HALF, bool LOCAL, bool HOT = false>   // HOT: the touched list may hold hot shared user rows / hot item rows (in-place sums only)
 __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float *W, float *bias, float *g_bias, unsigned fb_off, unsigned item_off,
                                                    unsigned user_off, int pitch, int k, void *dst) {
     constexpr int IPW = 64 / LPI;
@@ -513,10 +524,11 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
         if (i + stride < N) request(i + stride);
         if (LOCAL && b == e) continue;
         const bool owns = !(LPI * 4 > k && L * 4 >= k);
-        if (HOT && LOCAL && e < 0) {   // a hot shared user row (WinTouched): k_wunit_apply_shared left the row and bias it ends the window with in slot b
-            const size_t row = (size_t)user_off + S.shared_from + (size_t)(t - S.nfb_rows - S.nitem_rows);
+        if (HOT && LOCAL && e < 0) {   // a hot shared user row or item row (WinTouched): k_wunit_apply_hot left the row and bias it ends the window with in slot b
+            const long ts = t - S.nfb_rows - S.nitem_rows;
+            const size_t row = ts < 0 ? (size_t)item_off + (size_t)(t - S.nfb_rows) : (size_t)user_off + S.shared_from + (size_t)ts;
             if (owns) *reinterpret_cast<float4 *>(W + row * pitch + (size_t)L * 4) = *reinterpret_cast<const float4 *>(S.contrib + (size_t)b * pitch + (size_t)L * 4);
-            if (L == 0 && S.user_bias) bias[row] = S.cbias[b];
+            if (L == 0 && (ts < 0 || S.user_bias)) bias[row] = S.cbias[b];
             continue;
         }
         float4 acc = f4zero();
@@ -595,19 +607,23 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
     }
 }
 
-// ------------------------------------------------------------------------------------------------- kernel C: hot shared user rows in ordered sub-steps
-// One workgroup per hot shared user row of the window (S.hot; knob window_shared_sub), between the walk and the sums.  The row and
-// its bias live in LDS; its slots are taken in file order, S.hot_sub at a time.  One lane group per slot of a sub-step redoes the data row's
+// ------------------------------------------------------------------------------------------------- kernel C: hot rows in ordered sub-steps
+// One workgroup per hot row of the window, between the walk and the sums: the hot shared user rows (ITEM = false: S.hot[0 .. nhot); knob
+// window_shared_sub) in one launch, the hot item rows (ITEM = true: S.hot[nhot ..); knob window_item_sub, section 6m) in another.
+// The row and its bias live in LDS; its slots are taken in file order, `sub` at a time.  One lane group per slot of a sub-step redoes the data row's
 // update_inner the way k_wunit_walk does, statement for statement, with
-//   * the hot row and its bias as the previous sub-step left them (LDS),
+//   * the hot row and its bias as the previous sub-step left them (LDS) -- at the hot entry's own position: in uent for a user row, in ent for a
+//     plain item entry, in ient for a feature_item child (whose parent entry is read as of the window start, like every other row),
 //   * the private user's row and bias as the walk held them when it reached the data row (the slot's record, written by the walk),
 //   * everything else from the model, which is still as of the window start: a window with a hot row has no in-place single applies (the builder
 //     gives every contribution a slot there), the sums run after this kernel, and this kernel does not write the model either -- another hot row of
-//     the same data row must read this one as of the window start, so the row's final value goes to its first slot and k_wunit_sum moves it in;
+//     the same data row (of either side) must read this one as of the window start, so the row's final value goes to its first slot and k_wunit_sum
+//     moves it in;
 // and parks new - current of the hot row (and bias) in LDS.  The parked changes of a sub-step are added in slot order (acc = +0 + c_1 + c_2 ...; every
-// column by one thread) and the row moves by the sum.  The workgroup is sized to the sub-step: min(hot_sub, 256 / LPI) lane groups.
-template <int LPI>
-__global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, const WUnitSchedule S) {
+// column by one thread) and the row moves by the sum.  The workgroup is sized to the sub-step: min(sub, 256 / LPI) lane groups; a larger sub-step
+// takes several rounds of them (k = 64, sub = 128: 8 rounds of 16), the parked changes joining the sum round by round, in slot order all the same.
+template <int LPI, bool ITEM>
+__global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, const WUnitSchedule S) {
     extern __shared__ __align__(16) float hot_lds[];
     const int pitch = P.pitch, k = P.k, k4 = (k + 3) & ~3;
     const int G = blockDim.x / LPI, tid = threadIdx.x;
@@ -617,18 +633,20 @@ __global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, c
     float *park = accv + pitch;              // [G][pitch] the changes of the slots in flight
     float *pb = park + (size_t)G * pitch;    // [G] their bias changes
     float *sc = pb + G;                      // the bias as the previous sub-step left it, the sub-step's bias sum
-    const WinHot h = S.hot[blockIdx.x];
+    const WinHot h = S.hot[(ITEM ? S.nhot : 0) + blockIdx.x];
+    const int sub = ITEM ? S.item_sub : S.hot_sub;
     const bool ub = P.no_user_bias == 0;
+    const bool hbias = ITEM || ub;           // the item bias is always there
     const bool owns = !(LPI * 4 > k && L * 4 >= k);
     const float lr = P.lr;
     const size_t srow0 = (size_t)P.user_off + S.shared_from;
-    const size_t hrow = srow0 + (size_t)h.j;
-    const float wd_s = get_wd(P.u_rng, S.shared_from + (unsigned)h.j, P.wd_user);
+    const size_t hrow = ITEM ? (size_t)P.item_off + (size_t)h.j : srow0 + (size_t)h.j;
+    const float wd_h = ITEM ? get_wd(P.i_rng, (unsigned)h.j, P.wd_item) : get_wd(P.u_rng, S.shared_from + (unsigned)h.j, P.wd_user);
     for (int c = tid; c < k4; c += blockDim.x) cur[c] = P.W[hrow * pitch + c];
-    if (tid == 0) sc[0] = ub ? P.bias[hrow] : 0.0f;
+    if (tid == 0) sc[0] = hbias ? P.bias[hrow] : 0.0f;
     __syncthreads();
-    for (int s0 = h.b; s0 < h.e; s0 += S.hot_sub) {
-        const int s1 = min(s0 + S.hot_sub, h.e);
+    for (int s0 = h.b; s0 < h.e; s0 += sub) {
+        const int s1 = min(s0 + sub, h.e);
         for (int c = tid; c < k4; c += blockDim.x) accv[c] = 0.0f;
         if (tid == 0) sc[1] = 0.0f;
         for (int q0 = s0; q0 < s1; q0 += G) {
@@ -636,12 +654,15 @@ __global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, c
             if (slot < s1) {
                 const WinHotRec rc = S.hrec[h.rec + (slot - h.b)];
                 const int r = rc.row;
+                // where the hot entry sits: hu in uent (user side), he in ent or hc in ient (item side); -1: not there
+                const int hu = ITEM ? -1 : rc.pos, he = (ITEM && rc.pos >= 0) ? rc.pos : -1, hc = (ITEM && rc.pos < 0) ? ~rc.pos : -1;
                 int e0, e1, e2;
                 if (S.rptr) { e0 = S.rptr[2 * (long)r]; e1 = S.rptr[2 * (long)r + 1]; e2 = S.rptr[2 * (long)r + 2]; }
                 else { e0 = r * S.estride; e1 = e0 + S.estride - 1; e2 = e1 + 1; }
                 const float label = S.label[r];
                 const float ua = S.uval ? S.uval[r] : 1.0f;
-                const int u0 = S.uptr[r], um = u0 + S.upos[r], u1 = S.uptr[r + 1];
+                int u0 = 0, um = 0, u1 = 0;
+                if (S.uptr) { u0 = S.uptr[r]; um = u0 + S.upos[r]; u1 = S.uptr[r + 1]; }
                 int c0 = 0, c1 = 0;
                 if (S.iptr) { c0 = S.iptr[r]; c1 = S.iptr[r + 1]; }
                 const float4 p = load_row<LPI>(S.contrib, (size_t)slot, pitch, L, k);   // the walk's record
@@ -652,42 +673,56 @@ __global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, c
                 double bs = 0.0;
                 for (int j = e0; j < e1; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.g_bias[e.idx]); }
                 if (ub) {
-                    for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == rc.pos ? hb : P.bias[srow0 + e.idx])); }
+                    for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == hu ? hb : P.bias[srow0 + e.idx])); }
                     bs += (double)(ua * bu);
-                    for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == rc.pos ? hb : P.bias[srow0 + e.idx])); }
+                    for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == hu ? hb : P.bias[srow0 + e.idx])); }
                     bs += (double)0.0f;
                 }
                 bs += 0.0;
                 for (int j = e1, c = c0; j < e2; j++) {
                     const WinEnt e = S.ent[j];
-                    bs += (double)(e.val * P.bias[P.item_off + e.idx]);
-                    for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
+                    bs += (double)(e.val * (j == he ? hb : P.bias[P.item_off + e.idx]));
+                    for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)((c == hc ? hb : P.bias[P.item_off + ch.idx]) * ch.val * e.val); }
                 }
                 double sum = (double)P.base_score + bs;
                 float4 tu = f4zero();
-                for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == rc.pos ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+                for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == hu ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
                 axpy4(tu, p, ua);
-                for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == rc.pos ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+                for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == hu ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
                 float4 ti = f4zero();
                 for (int j = e1, c = c0; j < e2; j++) {
                     const WinEnt e = S.ent[j];
-                    axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+                    axpy4(ti, j == he ? hw : load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
                     for (; c < c1 && S.ient[c].pad == j; c++) {
                         const WinEnt ch = S.ient[c];
-                        axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+                        axpy4(ti, c == hc ? hw : load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
                     }
                 }
                 sum += (double)group_dot<LPI>(tu, ti, L, k);
                 const float pred = map_active((float)sum, P.active_type);
                 const float err = cal_grad(label, pred, P.active_type) * 1.0f;
-                // ---- the hot row's part of update_no_decay + reg_user: the walk's shared-row block against the current row
-                const float ss = lr * err * S.uent[rc.pos].val;
                 float4 ws = hw;
-                axpy4(ws, ti, ss);
-                reg_row<LPI>(P, ws, wd_s, false, L);
-                sub4(ws, hw);
                 float cb = 0.0f;
-                if (ub) { float nb = hb + ss; nb = nb * (1.0f - lr * P.wd_user_bias); cb = nb - hb; }
+                if (ITEM) {
+                    // ---- the hot row's part of update_no_decay + reg_item: the walk's item block (a plain entry: lr err ival; a child (c, v) of a parent
+                    // with value ival: ((lr err) v) ival) against the current row
+                    float si;
+                    if (hc < 0) si = lr * err * S.ent[he].val;
+                    else { const WinEnt ch = S.ient[hc]; si = lr * err * ch.val * S.ent[ch.pad].val; }
+                    axpy4(ws, tu, si);
+                    float nb = hb + si;
+                    reg_row<LPI>(P, ws, wd_h, true, L);
+                    nb = nb * (1.0f - lr * P.wd_item_bias);
+                    sub4(ws, hw);
+                    cb = nb - hb;
+                } else {
+                    // ---- the hot row's part of update_no_decay + reg_user: the walk's shared-row block against the current row
+                    const float ss = lr * err * S.uent[hu].val;
+                    axpy4(ws, ti, ss);
+                    reg_row<LPI>(P, ws, wd_h, false, L);
+                    sub4(ws, hw);
+                    if (ub) { float nb = hb + ss; nb = nb * (1.0f - lr * P.wd_user_bias); cb = nb - hb; }
+                }
                 if (owns) *reinterpret_cast<float4 *>(park + (size_t)g * pitch + L * 4) = ws;
                 if (L == 0) pb[g] = cb;
             }
@@ -713,15 +748,20 @@ __global__ __launch_bounds__(256) void k_wunit_apply_shared(const DevParams P, c
     if (tid == 0) S.cbias[h.b] = sc[0];
 }
 
-void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st) {
-    if (S.nhot <= 0) return;
+// the workgroup of a sub-step of `sub` slots: whole waves, min(sub, 256 / lpi) lane groups rounded up; LDS = current row, sum, G parked changes
+template <bool ITEM>
+static void launch_wunit_apply_hot(const DevParams &P, const WUnitSchedule &S, long nrows, int sub, hipStream_t st) {
+    if (nrows <= 0 || sub <= 0) return;
     const int lpi = lanes_per_instance(P.k);
-    const long want = (long)std::min(S.hot_sub, 256 / lpi) * lpi;
+    const long want = (long)std::min(sub, 256 / lpi) * lpi;
     const int block = (int)std::min<long>(256, (want + 63) / 64 * 64);
     const int G = block / lpi;
     const size_t lds = ((size_t)(2 + G) * (size_t)P.pitch + (size_t)G + 2) * sizeof(float);
-    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_apply_shared<LPI>), dim3((unsigned)S.nhot), dim3((unsigned)block), lds, st, P, S));
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_apply_hot<LPI, ITEM>), dim3((unsigned)nrows), dim3((unsigned)block), lds, st, P, S));
 }
+void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st) { launch_wunit_apply_hot<false>(P, S, S.nhot, S.hot_sub, st); }
+// nitem_hot: the hot item rows of the window, S.hot[S.nhot .. S.nhot + nitem_hot)
+void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st) { launch_wunit_apply_hot<true>(P, S, nitem_hot, S.item_sub, st); }
 
 bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedback) {
     if (!(P.k == 64 || P.k == 128) || S.rptr != nullptr || S.uval != nullptr || P.reg_method == 2) return false;
@@ -730,7 +770,7 @@ bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedbac
 }
 void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st) {
     if (S.nunits <= 0) return;
-    if (S.uptr || S.iptr) fast = 0;   // rows with shared user entries or feature_item children: the general walk (the fixed shapes have neither)
+    if (S.uptr || S.iptr || S.hot) fast = 0;   // rows with shared user entries or feature_item children, windows with hot rows (the records of the ordered sub-steps): the general walk
     // fast: 0 = the general lane-group kernel, 1 = the slot kernel where it applies, 2 (default) = in addition one WAVE per unit for user-group
     // windows whose launch does not fill the chip anyway (its time is the longest unit's latency: svdf_k_wave.hip, k_wunit_wave)
     if (fast >= 2 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) { launch_wunit_wave(P, S, st); return; }

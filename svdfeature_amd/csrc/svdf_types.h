@@ -237,11 +237,14 @@ struct WinEnt { unsigned idx; float val; int slot; int pad; };
 // from dvec[seg] -- and the entry's value; the contribution (w + d val) - w is formed by k_wunit_sum against the row it is about to update
 struct WinFbRec { int seg; float val; };
 // one-GPU windows: the targets that have slots at all (target, first slot, one past its last): the in-place sums walk this list instead of every row
-// (a HOT shared user row of the window -- ordered sub-steps, below -- carries e NEGATED: its slots are not summed, k_wunit_sum moves the row
-// k_wunit_apply_shared left in its first slot into the model)
+// (a HOT row of the window -- ordered sub-steps, below: a shared user row or an item row -- carries e NEGATED: its slots are not summed,
+// k_wunit_sum moves the row k_wunit_apply_hot left in its first slot into the model)
 struct WinTouched { int t, b, e; };
-// ORDERED SUB-STEPS for hot shared user rows (knob window_shared_sub).  A hot row: shared row j (= id - B), its slots
-// [b, e) in file order, its records hrec[rec .. rec + e - b): which regrouped data row a slot belongs to and where in uent its hot entry sits.
+// ORDERED SUB-STEPS for hot shared user rows (knob window_shared_sub) and hot item rows (knob window_item_sub; section 6m).
+// A hot row: shared row j (= id - B) or item row j (= the item id), its slots [b, e) in file order, its records hrec[rec .. rec + e - b): which
+// regrouped data row a slot belongs to and where the hot entry sits.  User side: pos = the position in uent.  Item side: pos >= 0 = the
+// position in ent (a plain item entry), pos < 0 = ~pos is the position in ient (a feature_item child; its parent is ient[~pos].pad).
+// The hot list holds the user rows first ([0, nhot)), the item rows after them (the launch of k_wunit_apply_hot<ITEM> knows how many).
 struct WinHot { int j, b, e, rec; };
 struct WinHotRec { int row, pos; };
 struct WUnitSchedule {
@@ -280,10 +283,14 @@ struct WUnitSchedule {
     // uent.pad = 1: the walk stores in its slot what the change is computed FROM that only the walk knows -- the private user's row and bias as
     // it held them when it reached the data row -- and k_wunit_apply_shared walks the hot rows' slots in sub-steps of hot_sub.  Such a window has
     // no in-place single applies, so everything else the apply kernel re-reads is still as of the window start.
+    // Hot item rows (window_item_sub > 0; section 6m) follow the user rows in `hot` and take the same record from the walk, in sub-steps of
+    // item_sub.  A hot plain item entry is marked ent.pad = 1.  A hot feature_item child cannot be (ient.pad is its parent's position): it
+    // carries its slot as -2 - slot instead -- such a window has no slot -1 (no in-place singles), so slot <= -2 says "hot" and names the slot.
     const WinHot *hot;
     const WinHotRec *hrec;
-    long nhot;
+    long nhot;                  // hot shared user rows (hot item rows: hot + nhot, counted by the host)
     int hot_sub;
+    int item_sub;               // (in what was the struct's tail padding: the kernel argument keeps its size)
 };
 
 }  // namespace svdf

@@ -43,8 +43,9 @@ struct WUnitHost {
     std::vector<WinEnt> uent;
     std::vector<int> iptr;             // feature_item children, WUnitSchedule::iptr / ient; empty: none in the window
     std::vector<WinEnt> ient;
-    std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), WUnitSchedule::hot / hrec; empty: none in the window
+    std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), then hot item rows (window_item_sub): WUnitSchedule::hot / hrec; empty: none in the window
     std::vector<WinHotRec> hrec;
+    long nhot_user = 0;                // how many of `hot` are shared user rows
     bool has_touched = false;
     long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
     int fixed_ng = -2;
@@ -68,7 +69,8 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     S.uptr = sh ? ds->wu_uptr.p : nullptr; S.upos = sh ? ds->wu_upos.p : nullptr; S.uent = sh ? ds->wu_uent.p : nullptr;
     S.nshared_rows = ds->wu_nshared; S.shared_from = sh ? shared_user_from_ : 0u;
     S.iptr = ds->wu_ichild ? ds->wu_iptr.p : nullptr; S.ient = ds->wu_ichild ? ds->wu_ient.p : nullptr;
-    S.hot = ds->wu_nhot > 0 ? ds->wu_hot.p : nullptr; S.hrec = ds->wu_nhot > 0 ? ds->wu_hrec.p : nullptr; S.nhot = ds->wu_nhot; S.hot_sub = wseq_shared_sub_;
+    const bool hot = ds->wu_nhot + ds->wu_nihot > 0;
+    S.hot = hot ? ds->wu_hot.p : nullptr; S.hrec = hot ? ds->wu_hrec.p : nullptr; S.nhot = ds->wu_nhot; S.hot_sub = wseq_shared_sub_; S.item_sub = wseq_item_sub_;
     return S;
 }
 
@@ -99,6 +101,14 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
               "svdf_dataset_window_from_csr: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) is for the one-GPU window sequence "
               "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) has no place for user rows");
     }
+    if (wseq_item_sub_ > 0) {   // ordered sub-steps for hot item rows: the same ground as the user-side lane above
+        check(!contrib_bf16_, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs amd:contrib = fp32");
+        check(!user_group(), "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) is not supported with user-group (SVD++) trainers");
+        check(strcmp(what, "dataset_window_from_csr") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
+              "svdf_dataset_window_from_csr: window_item_sub > 0 (ordered sub-steps for hot item rows) is for the one-GPU window sequence "
+              "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) sums every slot on the wire");
+        check(wunit_inplace_ != 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)");
+    }
     check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
@@ -117,7 +127,7 @@ void Engine::wunit_build(Dataset *ds, const void *segs_v, size_t nseg, const std
 }
 void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order,
                               long num_src_row, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children, int shared_sub) const {
+                              const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children, int shared_sub, int item_sub) const {
     const HostSeg *segs = static_cast<const HostSeg *>(segs_v);
     const long NU = mp_.num_user, NI = mp_.num_item, NG = mp_.num_global, NF = user_group() ? (long)num_fb_rows() : 0;
     // side-table children (children: the one-GPU window sequence): [c0, c1) of an id into the table's columns
@@ -304,6 +314,11 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     if (shared_sub > 0 && has_shared)
         for (long j = 0; j < NS; j++)
             if (tptr[(size_t)(NF + NI + j) + 1] > shared_sub) H.hot.push_back(WinHot{(int)j, 0, 0, 0});
+    H.nhot_user = (long)H.hot.size();
+    // the same for the item range (window_item_sub, section 6m): a plain item entry's row, a feature_item child's row, or both -- the slots count
+    if (item_sub > 0)
+        for (long i = 0; i < NI; i++)
+            if (tptr[(size_t)(NF + i) + 1] > item_sub) H.hot.push_back(WinHot{(int)i, 0, 0, 0});
     std::vector<unsigned char> single;
     if (inplace && H.hot.empty()) {
         single.assign((size_t)NT, 0);
@@ -340,33 +355,56 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         }
     }
     if (!H.hot.empty()) {   // the hot rows' slot ranges and records (slots are in file order: the record of a slot is found through its entry)
-        check(inplace, "window data sets: ordered sub-steps for shared user rows need the in-place sums (knob wunit_inplace = 1)");
-        std::vector<int> hot_of((size_t)NS, -1);
+        check(inplace, H.nhot_user > 0 ? "window data sets: ordered sub-steps for shared user rows need the in-place sums (knob wunit_inplace = 1)"
+                                       : "window data sets: ordered sub-steps for item rows need the in-place sums (knob wunit_inplace = 1)");
+        std::vector<int> hot_of((size_t)(NI + NS), -1);   // by target - NF: item rows, then shared user rows
         int rec = 0;
         for (size_t q = 0; q < H.hot.size(); q++) {
             WinHot &h = H.hot[q];
-            const size_t t = (size_t)(NF + NI) + (size_t)h.j;
+            const size_t t = (size_t)NF + ((long)q < H.nhot_user ? (size_t)NI : 0) + (size_t)h.j;
             h.b = tptr[t]; h.e = tptr[t + 1]; h.rec = rec;
             rec += h.e - h.b;
-            hot_of[(size_t)h.j] = (int)q;
+            hot_of[t - (size_t)NF] = (int)q;
         }
         H.hrec.assign((size_t)rec, WinHotRec{0, 0});
-        for (long nr = 0; nr < nrow; nr++)
-            for (int e = H.uptr[(size_t)nr]; e < H.uptr[(size_t)nr + 1]; e++) {
-                WinEnt &u = H.uent[(size_t)e];
-                const int q = hot_of[u.idx];
+        auto record = [&](int q, int slot, long nr, int pos) { H.hrec[(size_t)(H.hot[(size_t)q].rec + slot - H.hot[(size_t)q].b)] = WinHotRec{(int)nr, pos}; };
+        for (long nr = 0; nr < nrow; nr++) {
+            if (H.nhot_user > 0)
+                for (int e = H.uptr[(size_t)nr]; e < H.uptr[(size_t)nr + 1]; e++) {
+                    WinEnt &u = H.uent[(size_t)e];
+                    const int q = hot_of[(size_t)NI + u.idx];
+                    if (q < 0) continue;
+                    u.pad = 1;
+                    record(q, u.slot, nr, e);
+                }
+            if ((long)H.hot.size() == H.nhot_user) continue;
+            // hot item rows (svdf_types.h, WinHotRec): a plain entry is marked pad = 1, position e; a child carries its slot as -2 - slot, position ~c
+            for (int e = rptr[(size_t)2 * nr + 1]; e < rptr[(size_t)2 * nr + 2]; e++) {
+                WinEnt &it = ent[(size_t)e];
+                const int q = hot_of[it.idx];
                 if (q < 0) continue;
-                u.pad = 1;
-                H.hrec[(size_t)(H.hot[(size_t)q].rec + u.slot - H.hot[(size_t)q].b)] = WinHotRec{(int)nr, e};
+                it.pad = 1;
+                record(q, it.slot, nr, e);
             }
+            if (has_ichild)
+                for (int c = H.iptr[(size_t)nr]; c < H.iptr[(size_t)nr + 1]; c++) {
+                    WinEnt &ch = H.ient[(size_t)c];
+                    const int q = hot_of[ch.idx];
+                    if (q < 0) continue;
+                    record(q, ch.slot, nr, ~c);
+                    ch.slot = -2 - ch.slot;
+                }
+        }
     }
     if (inplace) {   // the in-place sums visit only the targets that have slots (a window touches a fraction of the rows; singles keep none)
         H.has_touched = true;
-        size_t q = 0;   // a hot row's entry carries e negated (WinTouched)
+        // a hot row's entry carries e negated (WinTouched); the hot list holds the user rows first, both parts in target order
+        size_t qi = (size_t)H.nhot_user, qu = 0;
         for (size_t t = 0; t < (size_t)NT; t++) {
             if (tptr[t + 1] <= tptr[t]) continue;
-            const bool is_hot = q < H.hot.size() && (size_t)(NF + NI) + (size_t)H.hot[q].j == t;
-            q += is_hot;
+            bool is_hot;
+            if (t < (size_t)(NF + NI)) { is_hot = qi < H.hot.size() && (size_t)NF + (size_t)H.hot[qi].j == t; qi += is_hot; }
+            else { is_hot = qu < (size_t)H.nhot_user && (size_t)(NF + NI) + (size_t)H.hot[qu].j == t; qu += is_hot; }
             H.touched.push_back(WinTouched{(int)t, tptr[t], is_hot ? -tptr[t + 1] : tptr[t + 1]});
         }
     }
@@ -418,8 +456,9 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
         ds->wu_upos.upload(H.upos.data(), H.upos.size(), stream_);
         ds->wu_uent.upload(H.uent.data(), H.uent.size(), stream_);
     }
-    ds->wu_nhot = (long)H.hot.size();
-    if (ds->wu_nhot > 0) {
+    ds->wu_nhot = H.nhot_user;
+    ds->wu_nihot = (long)H.hot.size() - H.nhot_user;
+    if (!H.hot.empty()) {
         ds->wu_hot.upload(H.hot.data(), H.hot.size(), stream_);
         ds->wu_hrec.upload(H.hrec.data(), H.hrec.size(), stream_);
     }
@@ -449,7 +488,7 @@ void Engine::wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, co
 // number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.  The sequence also takes loaded
 // feature_user / feature_item tables: every child is a shared target, and no row may reach one target twice.
 void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
-                                 const float *feat_value, bool shared, int shared_sub) const {
+                                 const float *feat_value, bool shared, int shared_sub, int item_sub) const {
     const long NU = mp_.num_user;
     const unsigned B = shared_user_from_;
     const bool children = shared && side_tables();
@@ -498,7 +537,7 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
         seg_rows[h.row_first + h.row_count++] = r;
     }
     wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, true, n, row_label, row_ptr, feat_index, feat_value, nullptr, nullptr,
-                     priv.empty() ? nullptr : priv.data(), children, shared_sub);
+                     priv.empty() ? nullptr : priv.data(), children, shared_sub, item_sub);
 }
 // One row's side-table children (the one-GPU window sequence): a feature_user child is a shared user row (id >= amd:shared_user_from), and
 // a child must not reach a row the row already touches (its own entries or an earlier child) -- one contribution per target and row.  Two
@@ -746,22 +785,23 @@ bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_pt
     return !open;
 }
 
-// The window count the shared user rows ask for when hot ones move in ordered sub-steps (window_shared_sub > 0; modelled on wseq_windows_hot below).
-// Per class -- plain shared rows at window_per_target_shared, feature_user children at window_per_target_child -- the mean over entries of the
-// changes formed against ONE value of a row, sum_j min(c_j / W, window_shared_sub) c_j / sum_j c_j, stays at the class value; and no shared user row
-// meets more than window_shared_max updates per window (how stale everybody else's view of it gets: calibration in DESIGN.md section 6k).
-long Engine::wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child) const {
+// The window count one side's rows ask for when hot ones move in ordered sub-steps of `sub` (modelled on wseq_windows_hot below): the shared user
+// rows under window_shared_sub > 0 (cap window_shared_max), the item rows under window_item_sub > 0 (cap window_item_max; 6m).
+// Per class -- plain rows at per_plain (window_per_target_shared / window_per_target), side-table children at per_child (window_per_target_child) --
+// the mean over entries of the changes formed against ONE value of a row, sum_j min(c_j / W, sub) c_j / sum_j c_j, stays at the class value; and
+// no row of the side meets more than `cap` updates per window (how stale everybody else's view of it gets).
+long Engine::wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const {
     if (n <= 0) return 1;
     long mx = 0;
     for (long c : plain) mx = std::max(mx, c);
     for (long c : child) mx = std::max(mx, c);
     auto met = [&](const std::vector<long> &cnt, long W) {
         double s = 0.0, s1 = 0.0;
-        for (long c : cnt) { s += std::min((double)c / (double)W, (double)wseq_shared_sub_) * (double)c; s1 += (double)c; }
+        for (long c : cnt) { s += std::min((double)c / (double)W, (double)sub) * (double)c; s1 += (double)c; }
         return s1 > 0.0 ? s / s1 : 0.0;
     };
-    auto ok = [&](long W) { return met(plain, W) <= (double)wseq_per_target_shared_ && met(child, W) <= (double)wseq_per_target_child_; };
-    long lo = std::max<long>(1, (mx + wseq_shared_max_ - 1) / wseq_shared_max_);
+    auto ok = [&](long W) { return met(plain, W) <= (double)per_plain && met(child, W) <= (double)per_child; };
+    long lo = std::max<long>(1, (mx + cap - 1) / cap);
     if (ok(lo)) return lo;
     long hi = lo;
     while (!ok(hi) && hi < n) hi *= 2;
@@ -808,24 +848,32 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
                                                  (double)wseq_per_target_ / (double)wseq_per_target_child_;
     long W;
     const int shared_sub = shared_user() ? wseq_shared_sub_ : 0;
-    if (shared_sub > 0) {
-        // ordered sub-steps for hot shared user rows: the user side leaves the common term -- its rows follow
-        // wseq_windows_shared -- and the item side keeps its own: item rows at window_per_target, feature_item children at window_per_target_child
-        cc.resize(cc.size() - ccu.size());
-        const double ichild_met = cc.empty() ? 0.0 : mean_updates_met(cc, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) *
-                                                      (double)wseq_per_target_ / (double)wseq_per_target_child_;
-        W = wseq_windows(n, {std::max(mean_updates_met(ci, wseq_max_ratio()), ichild_met), mean_updates_met(cg, wseq_max_ratio())});
-        if (!window_set_) W = std::max(W, wseq_windows_shared(n, cs, ccu));
+    const int item_sub = wseq_item_sub_;
+    if (shared_sub > 0 || item_sub > 0) {
+        // ordered sub-steps (DESIGN.md sections 6k / 6m): a side whose hot rows ride a lane leaves the common term -- its rows follow
+        // wseq_windows_shared -- and the other side keeps its own: item rows at window_per_target, shared user rows at window_per_target_shared,
+        // either side's children at window_per_target_child.  The global biases keep their term.
+        cc.resize(cc.size() - ccu.size());   // (cc: the feature_item children alone from here on)
+        auto child_term = [&](const std::vector<long> &c) {
+            return c.empty() ? 0.0 : mean_updates_met(c, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) * (double)wseq_per_target_ / (double)wseq_per_target_child_;
+        };
+        const double item_term = item_sub > 0 ? 0.0 : std::max(mean_updates_met(ci, wseq_max_ratio()), child_term(cc));
+        // (a user side that stays in the common term keeps the children's term as it was: the mean over the children of BOTH sides)
+        const double user_term = shared_sub > 0 ? 0.0 : std::max(shared_met, ccu.empty() ? 0.0 : child_met);
+        W = wseq_windows(n, {std::max(item_term, user_term), mean_updates_met(cg, wseq_max_ratio())});
+        if (!window_set_ && shared_sub > 0) W = std::max(W, wseq_windows_shared(n, cs, ccu, shared_sub, wseq_shared_max_, wseq_per_target_shared_, wseq_per_target_child_));
+        if (!window_set_ && item_sub > 0) W = std::max(W, wseq_windows_shared(n, ci, cc, item_sub, wseq_item_max_, wseq_per_target_, wseq_per_target_child_));
     } else
         W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     ds->wseq_shared_sub = shared_sub;
+    ds->wseq_item_sub = item_sub;
     const bool inplace = wunit_inplace_ != 0;   // a window is summed in place right after its walk (wseq_train): single contributions need no slot
     wseq_build_windows(W, wseq_build_threads_,
         [&](long w, WUnitHost &H) {
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub);
+            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub, item_sub);
         },
         [&](long, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
@@ -1011,6 +1059,9 @@ void Engine::wseq_train(Dataset *ds) {
     if (ds->wseq_shared_sub >= 0)
         check(ds->wseq_shared_sub == (shared_user() ? wseq_shared_sub_ : 0),
               "train_dataset: the window sequence was built with another window_shared_sub (ordered sub-steps for hot shared user rows); build the data set again after changing the knob");
+    if (ds->wseq_item_sub >= 0)
+        check(ds->wseq_item_sub == wseq_item_sub_,
+              "train_dataset: the window sequence was built with another window_item_sub (ordered sub-steps for hot item rows); build the data set again after changing the knob");
     for (Dataset *c : ds->wchild) {
         if (c->kind == 5) {
             d_contrib_.reserve((size_t)std::max<long>(c->win_slots, 1) * (size_t)pitch_);
@@ -1025,6 +1076,7 @@ void Engine::wseq_train(Dataset *ds) {
             // hot shared user rows in ordered sub-steps: after the walk (its records) and before the sums (which move the finished rows in); the
             // workgroups run one hot row each, so the launch lasts as long as the hottest row's chain of sub-steps
             if (c->wu_nhot > 0) { launch_wunit_apply_shared(P, wunit_view(c), stream_); n_launches_++; }
+            if (c->wu_nihot > 0) { launch_wunit_apply_item(P, wunit_view(c), c->wu_nihot, stream_); n_launches_++; }   // hot item rows likewise (neither launch writes the model)
             wunit_sum(c, nullptr, 0);
         }
         n_launches_ += 2;
