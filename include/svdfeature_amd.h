@@ -382,6 +382,14 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               data set is built: train_dataset refuses a sequence built with another window_item_sub.  Refused with
  *                                                               amd:contrib = bf16, user-group trainers, amd:gpus > 1 / svdf_dataset_window_from_csr, wunit_inplace = 0.
  *                                                               Calibration: profiles/r11_item_hot.md
+ *     window_pair_sub (*) 0, window_pair_max (*) 4096           the same lane for RANK PAIRS (svdf_dataset_from_pairs and pair-shaped staged chunks under amd:step = minibatch /
+ *                                                               auto): an item with more than window_pair_sub (0 .. 128) slots in a window -- both signs counted --
+ *                                                               moves in ordered sub-steps of that many (k_window_apply_pairs; 0 = off, the default: the rule and bits as
+ *                                                               before), each slot evaluated against the pair's OTHER item as of the window start, and meets at most
+ *                                                               window_pair_max updates per window; window_per_target then bounds the mean of min(updates per window,
+ *                                                               window_pair_sub).  window_hot_sub keeps governing ratings only.  Set before the data set is built:
+ *                                                               train_dataset refuses a sequence built with another window_pair_sub.  Refused with amd:contrib = bf16,
+ *                                                               user-group trainers, amd:gpus > 1, svdf_dataset_window_from_pairs.  Calibration: profiles/r12_pair_hot.md
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is

@@ -270,6 +270,14 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_shared_max")) { check(value >= 1, "window_shared_max must be positive"); wseq_shared_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_item_sub")) { check(value >= 0 && value <= 128, "window_item_sub must be in 0 .. 128"); wseq_item_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_item_max")) { check(value >= 1, "window_item_max must be positive"); wseq_item_max_ = (int)value; return 0; }
+    if (!strcmp(name, "window_pair_sub")) {
+        check(value >= 0 && value <= 128, "window_pair_sub must be in 0 .. 128");
+        check(value == 0 || (gpus_ == 1 && !multi_ && !is_peer_),
+              "window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence; amd:gpus > 1 sums every slot on the wire");
+        wseq_pair_sub_ = (int)value;
+        return 0;
+    }
+    if (!strcmp(name, "window_pair_max")) { check(value >= 1, "window_pair_max must be positive"); wseq_pair_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_sub")) { check(value >= 0 && value <= 4096, "window_hot_sub must be in 0 .. 4096"); wseq_hot_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_max")) { check(value >= 1, "window_hot_max must be positive"); wseq_hot_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }

@@ -226,6 +226,7 @@ Dataset *Engine::dataset_from_triples(long n, const unsigned *user, const unsign
 Dataset *Engine::dataset_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg) {
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
+    if (wseq_pair_sub_ > 0 && ((multi_ && !in_multi_scope()) || (single_minibatch() && user_group()))) wseq_pair_check("dataset_from_pairs");   // (what never reaches wseq_from_pairs)
     if (multi_ && !in_multi_scope()) return multi_dataset_from_pairs(n, user, pos, neg);
     if (single_minibatch() && !user_group() && basic_fast_path_allowed()) return wseq_from_pairs(n, user, pos, neg);
     if (auto_step_active()) {

@@ -295,7 +295,7 @@ struct Dataset {
     bool pv_item_pivot = false;
     long pv_cold = 0, pv_hot_rows = 0;
     int64_t chained_levels = 0;   // levels the current launch sequence of this data set walks inside chained launches
-    bool win_hot = false;         // kind 5 inside a one-GPU sequence: some item has more than window_hot_sub slots in this window (ordered sub-steps: k_window_apply)
+    bool win_hot = false;         // kind 5 inside a one-GPU sequence: some item has more than window_hot_sub (rank pairs: window_pair_sub) slots in this window (ordered sub-steps: k_window_apply / k_window_apply_pairs)
     long win_slots = 0;           // contribution slots of the window = item entries (kind 7: + feedback entries)
     // kind 7: window-minibatch data set of user units (svdf_k_wunit.hip): user-group blocks / rows with global features
     DevBuf<WinUnit> wu_units;
@@ -322,6 +322,7 @@ struct Dataset {
     long wu_nihot = 0;             // hot item rows (knob window_item_sub): wu_hot[wu_nhot .. wu_nhot + wu_nihot), records in wu_hrec too
     int wseq_shared_sub = -1;      // kind 8 from wseq_from_csr (else -1): window_shared_sub when the sequence was built (train_dataset refuses another value)
     int wseq_item_sub = -1;        // the same for window_item_sub
+    int wseq_pair_sub = -1;        // kind 8 from wseq_from_pairs (else -1): window_pair_sub when the sequence was built (train_dataset refuses another value)
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
     std::vector<Dataset *> wchild;
     // kind 6: a data set of an amd:gpus = N handle (svdf_multi.cpp): mchild[rank][window] lives in that rank's HBM
@@ -700,11 +701,15 @@ class Engine {
     int wseq_shared_max_ = 512;           // knob "window_shared_max": the most updates a hot shared user row may meet per window (how stale everybody else's view of it gets); side-feature variant at the 20 M-row prefix, window_shared_sub 12, 3 seeds: 256 max |dRMSE| 7.2e-5 / 191 ms per pass, 512 6.9e-5 / 172 ms, 1 024 1.06e-4 (profiles/r09_shared_hot.md)
     int wseq_item_sub_ = 0;               // knob "window_item_sub" (0 .. 128): an item-range row (a plain item entry's row, a feature_item child's row) with more slots than this in a window of wseq_from_csr is applied in ordered sub-steps of this many (k_wunit_apply_hot<ITEM>); 0 = off
     int wseq_item_max_ = 2048;            // knob "window_item_max": the most updates a hot item row may meet per window (how stale everybody else's view of it gets); the largest swept value: Zipf(0.7) items + 4 globals, 2 M rows, 3 seeds, sub 8 / 24 / 128: max |dRMSE| 6.0e-6 / 2.3e-6 / 2.2e-5 (profiles/r11_item_hot.md)
+    int wseq_pair_sub_ = 0;               // knob "window_pair_sub" (0 .. 128): an item with more slots than this (both signs counted) in a window of rank pairs (wseq_from_pairs) is applied in ordered sub-steps of this many (k_window_apply_pairs); 0 = off
+    int wseq_pair_max_ = 4096;            // knob "window_pair_max": the most updates a hot item of rank pairs may meet per window (how stale everybody else's view of it gets); the largest swept value: Zipf(0.7) pairs at the configs[4] shape, 20 M-pair prefix, 3 seeds, sub 8 / 24 / 128: worst seed at 3 % of the pair contract (accuracy within 3e-3, margin within 2 %; profiles/r12_pair_hot.md)
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)
     int wseq_hot_max_ = 2048;             // knob "window_hot_max": the most updates a hot row may meet per window (how stale the USERS' view of it gets); 3 seeds of Zipf(0.7) at the configs[1] size: 1 024 max |dRMSE| 4.2e-5 / 66 ms per pass, 2 048 6.6e-5 / 55 ms, 3 072 7.2e-5 / 52 ms (profiles/r06_hot_lane_calibration.txt)
     DevBuf<float> d_clabel_;
     bool wseq_hot_ok() const;             // the configuration has the hot lane (unit ratings, fp32 contribution rows, one GPU)
     long wseq_windows_hot(long n, const std::vector<long> &item_count) const;
+    long wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const;   // the rule of wseq_windows_hot for any (sub-step, cap): ratings and rank pairs
+    void wseq_pair_check(const char *what) const;   // window_pair_sub > 0: what the lane does not cover, refused with its cause
     // ordered sub-steps of `sub` with at most `cap` updates per row and window: what the rows of two classes (means per_plain / per_child) ask for
     long wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const;
     double wseq_max_ratio() const { return (double)wseq_per_target_ / (double)wseq_per_target_max_; }

@@ -21,7 +21,9 @@ namespace svdf {
 // Records are in LAUNCH order: users sorted by count (descending), so the lane groups of a wave run the same number of iterations.
 
 // ------------------------------------------------------------------------------------------------- kernel A, any width <= 256
-template <int LPI, bool UNITVAL, int NI>
+// PHOT (rank pairs, NI = 2, WindowSchedule::hot_sub > 0): an entry whose item is hot in this window stores tmp_u, the user's bias
+// and -- a pair's label is always 1 -- the pair's POSITION in the user-grouped columns (k_window_apply_pairs finds both item ids and signs through it).
+template <int LPI, bool UNITVAL, int NI, bool PHOT = false>
 __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const WindowSchedule S) {
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
@@ -86,10 +88,10 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
             if (act) {   // what the reference would have changed on the item side
                 sub4(wi, q[e]);
                 const long slot = e == 0 ? S.slot[s] : S.slot1[s];
-                if (NI == 1 && S.hot_sub > 0 && S.iptr[item[0] + 1] - S.iptr[item[0]] > S.hot_sub) {
+                if ((NI == 1 || PHOT) && S.hot_sub > 0 && S.iptr[item[e] + 1] - S.iptr[item[e]] > S.hot_sub) {
                     // a hot item of this window: what the change is computed FROM goes to the slot; k_window_apply forms it against the row of its sub-step
                     store_contrib<LPI>(S.contrib, 0, (size_t)slot, pitch, L, k, tu);
-                    if (L == 0) { S.cbias[slot] = use_ubias ? bu : 0.0f; S.clabel[slot] = label; }
+                    if (L == 0) { S.cbias[slot] = use_ubias ? bu : 0.0f; S.clabel[slot] = PHOT ? __int_as_float((int)s) : label; }
                 } else {
                     store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)slot, pitch, L, k, wi);
                     if (L == 0) S.cbias[slot] = nbi - bi[e];
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
 // instance's item row, bias and record in flight while this one is computed (the item side is read-only inside a window, so the
 // prefetch cannot go stale).
 // NI = 2: rank pairs (two signed item entries, labels 1); LINK = 0 linear / 3 sigmoid rank loss; UB = user bias on.
-template <int LANES, int V, int G, int NI, int LINK, bool UB>
+template <int LANES, int V, int G, int NI, int LINK, bool UB, bool PHOT = false>   // PHOT: as in k_window_users
 __global__ __launch_bounds__(256) void k_window_users_slots(const DevParams P, const WindowSchedule S) {
     constexpr int T = 16 / LANES;
     constexpr int IPS = 64 / LANES;    // users per user set
@@ -151,11 +153,15 @@ __global__ __launch_bounds__(256) void k_window_users_slots(const DevParams P, c
     // software pipeline: record / item rows / item biases of iteration j + 1 are requested before iteration j is computed
     unsigned nir[G][NI];
     float nlabel[G], nbi_[G][NI], nia[G][NI];
-    int nslot[G][NI];
-    bool nhot[G];
+    int nslot[G][NI], npos[G];
+    bool nhot[G][NI];
     float4 nq[G][NI][V];
 #pragma unroll
-    for (int g = 0; g < G; g++) nhot[g] = false;
+    for (int g = 0; g < G; g++) {
+        npos[g] = 0;
+#pragma unroll
+        for (int e = 0; e < NI; e++) nhot[g][e] = false;
+    }
     auto fetch = [&](int j) {
 #pragma unroll
         for (int g = 0; g < G; g++) {
@@ -165,7 +171,12 @@ __global__ __launch_bounds__(256) void k_window_users_slots(const DevParams P, c
             nia[g][0] = NI == 2 ? S.ival[s] : 1.0f;
             if (NI == 2) { nir[g][NI - 1] = P.item_off + S.item1[s]; nslot[g][NI - 1] = S.slot1[s]; nia[g][NI - 1] = S.ival1[s]; }
             nlabel[g] = NI == 2 ? 1.0f : S.label[s];
-            if (NI == 1) nhot[g] = S.hot_sub > 0 && S.iptr[S.item[s] + 1] - S.iptr[S.item[s]] > S.hot_sub;
+            if (NI == 1) nhot[g][0] = S.hot_sub > 0 && S.iptr[S.item[s] + 1] - S.iptr[S.item[s]] > S.hot_sub;
+            if (PHOT) {
+                npos[g] = (int)s;
+                nhot[g][0] = S.iptr[S.item[s] + 1] - S.iptr[S.item[s]] > S.hot_sub;
+                nhot[g][NI - 1] = S.iptr[S.item1[s] + 1] - S.iptr[S.item1[s]] > S.hot_sub;
+            }
         }
 #pragma unroll
         for (int g = 0; g < G; g++) {
@@ -180,14 +191,15 @@ __global__ __launch_bounds__(256) void k_window_users_slots(const DevParams P, c
     fetch(0);
     for (int j = 0; j < maxc; j++) {
         float label[G], bi[G][NI], ia[G][NI];
-        int slot[G][NI];
-        bool hot[G];
+        int slot[G][NI], pos[G];
+        bool hot[G][NI];
         float4 q[G][NI][V];
 #pragma unroll
         for (int g = 0; g < G; g++) {
-            label[g] = nlabel[g]; hot[g] = nhot[g];
+            label[g] = nlabel[g]; pos[g] = npos[g];
 #pragma unroll
             for (int e = 0; e < NI; e++) {
+                hot[g][e] = nhot[g][e];
                 bi[g][e] = nbi_[g][e]; slot[g][e] = nslot[g][e]; ia[g][e] = nia[g][e];
 #pragma unroll
                 for (int v = 0; v < V; v++) q[g][e][v] = nq[g][e][v];
@@ -241,11 +253,11 @@ __global__ __launch_bounds__(256) void k_window_users_slots(const DevParams P, c
                     sub4(wi, q[g][e][v]);
                     c[v] = wi;
                 }
-                if (act && NI == 1 && hot[g]) {   // a hot item of this window (WindowSchedule::hot_sub): the slot takes what the change is computed FROM
+                if (act && (NI == 1 || PHOT) && hot[g][e]) {   // a hot item of this window (WindowSchedule::hot_sub): the slot takes what the change is computed FROM
 #pragma unroll
                     for (int v = 0; v < V; v++) store_contrib<K / 4>(S.contrib, 0, (size_t)slot[g][e], pitch, m + v * LANES, K, tu[v]);
                     S.cbias[slot[g][e]] = UB ? bu_before : 0.0f;
-                    S.clabel[slot[g][e]] = label[g];
+                    S.clabel[slot[g][e]] = PHOT ? __int_as_float(pos[g]) : label[g];
                 } else if (act) {
 #pragma unroll
                     for (int v = 0; v < V; v++) store_contrib<K / 4>(S.contrib, S.contrib_bf16, (size_t)slot[g][e], pitch, m + v * LANES, K, c[v]);
@@ -280,6 +292,7 @@ void launch_window_users(const DevParams &P, const WindowSchedule &S, int slots,
             const long per_wave = (long)G * (64 / LANES);
             const long waves = (S.nusers + per_wave - 1) / per_wave;
             if (NI == 1) hipLaunchKernelGGL((k_window_users_slots<LANES, 2, G, 1, 0, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S);
+            else if (S.hot_sub > 0) hipLaunchKernelGGL((k_window_users_slots<LANES, 2, G, 2, 3, false, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S);
             else hipLaunchKernelGGL((k_window_users_slots<LANES, 2, G, 2, 3, false>), dim3((unsigned)waves), dim3(64), 0, st, P, S);
         };
         const int g = groups_per_wave > 0 ? groups_per_wave : 1;
@@ -300,7 +313,9 @@ void launch_window_users(const DevParams &P, const WindowSchedule &S, int slots,
     const int lpi = lanes_per_instance(P.k);
     const long ipw = 64 / lpi;
     const long waves = (S.nusers + ipw - 1) / ipw;
-    if (S.item1 != nullptr) {
+    if (S.item1 != nullptr && S.hot_sub > 0) {   // rank pairs, a window with hot items (window data sets carry unit user values)
+        SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 2, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S));
+    } else if (S.item1 != nullptr) {
         if (S.uval == nullptr) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 2>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
         else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, false, 2>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     } else if (S.uval == nullptr) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 1>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
@@ -790,6 +805,233 @@ void launch_window_apply(const DevParams &P, const WindowSchedule &S, long num_i
     const unsigned grid = (unsigned)(hot_blocks + cold);
     if (P.active_type == ACT_LINEAR && P.reg_method == 0) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, true>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, false>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+}
+// ------------------------------------------------------------------------------------------------- rank pairs with hot items (round 12): apply + sums
+// ORDERED SUB-STEPS FOR RANK PAIRS (knob window_pair_sub).  An item with more than hot_sub slots in the window -- both signs counted --
+// is applied by one workgroup in file order, hot_sub slots at a time, built like k_window_apply's hot part: row and bias in LDS, the next round's slots
+// requested before this round's barrier, the changes parked in LDS and added in slot order, one row element per lane.  A slot holds what the walk alone
+// knows (tmp_u, the user's bias) and the pair's position in the user-grouped columns, which gives both item ids and signs.  New against the ratings lane:
+//   * a pair's change on h needs the OTHER item's row and bias, as of the window start even when that item is hot too: one more row gather per slot, which
+//     does not depend on the chain and is requested with the slot's record;
+//   * whether h is the lower or the higher id of the pair decides which of q_lo / q_hi is the LDS row (the order of the bias sum and of tmp_i is the walk's);
+//   * because other workgroups read h's window-start row meanwhile, NOTHING here writes the model: the finished row and bias go to h's first slot, and
+//     k_window_pair_sums -- the next launch -- moves them in while it adds the other items' slots in place (section 6m's order: walk, hot apply, sums).
+// Equals tests/item_hot_sim.py on pair-shaped rows bit for bit (tests/test_gpu_pair_hot_window.py).
+template <int LPI, int NT>
+__global__ __launch_bounds__(NT) void k_window_apply_pairs(const DevParams P, const WindowSchedule S, long num_item) {
+    constexpr int G = NT / LPI;
+    constexpr int K4 = 4 * LPI;
+    constexpr int CHUNK0 = 2048 / LPI > 128 ? 128 : 2048 / LPI;
+    constexpr int CHUNK = CHUNK0 < G ? G : CHUNK0;
+    constexpr int PER = CHUNK / G;
+    constexpr int EPL = (K4 + 63) / 64;
+    __shared__ float4 stage[CHUNK * LPI];
+    __shared__ float stage_b[CHUNK];
+    __shared__ float4 rowq[LPI];
+    __shared__ float rowb;
+    __shared__ int hl_item[NT], hl_b[NT], hl_e[NT];
+    __shared__ int hl_n;
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int L = lane & (LPI - 1);
+    const int grp = threadIdx.x / LPI;
+    const int pitch = P.pitch, k = P.k;
+    const bool use_ubias = P.no_user_bias == 0;
+    const float *stage_f = reinterpret_cast<const float *>(stage);
+    float *rowf = reinterpret_cast<float *>(rowq);
+    for (long base = blockIdx.x; base < num_item; base += (long)gridDim.x * NT) {
+    if (threadIdx.x == 0) hl_n = 0;
+    __syncthreads();
+    {
+        const long i = base + (long)threadIdx.x * gridDim.x;
+        if (i < num_item) {
+            const int b = S.iptr[i], e = S.iptr[i + 1];
+            if (e - b > S.hot_sub) { const int pos = atomicAdd(&hl_n, 1); hl_item[pos] = (int)i; hl_b[pos] = b; hl_e[pos] = e; }
+        }
+    }
+    __syncthreads();
+    const int nhot = hl_n;
+    for (int h = 0; h < nhot; h++) {
+        const unsigned item = (unsigned)hl_item[h];
+        const int b = hl_b[h], e = hl_e[h];
+        const unsigned ir = P.item_off + item;
+        const float wd_i = get_wd(P.i_rng, item, P.wd_item);
+        float4 q = load_row<LPI>(P.W, ir, pitch, L, k);
+        float bi = P.bias[ir];
+        if (grp == 0) { rowq[L] = q; if (L == 0) rowb = bi; }
+        {   // the item's slots were written by other CUs a kernel ago: bring them into this XCD's L2 with every request in flight at once (k_window_apply)
+            float warm = 0.0f;
+            const size_t w0 = (size_t)b * (size_t)pitch, w1 = (size_t)e * (size_t)pitch;
+            for (size_t off = w0 + (size_t)threadIdx.x * 32; off < w1; off += (size_t)NT * 32) warm += S.contrib[off];
+            for (int sl = b + (int)threadIdx.x * 32; sl < e; sl += NT * 32) warm += S.cbias[sl];
+            if (warm == 1.2345e-38f) rowb = warm;   // (never true for data that matters: keeps the loads alive)
+        }
+        // a round's slots, and the other items' window-start rows behind them, do not depend on the chain: the NEXT round's are requested before this
+        // round's changes are formed
+        float4 ntu[PER], nqo[PER];
+        float nbu[PER], nbo[PER], nalo[PER], nahi[PER];
+        bool nislo[PER];
+        auto fetch = [&](int first, int cn) {
+#pragma unroll
+            for (int r = 0; r < PER; r++) {
+                const int sl = grp + r * G;
+                const size_t slot = (size_t)(first + (sl < cn ? sl : 0));
+                ntu[r] = load_contrib<LPI>(S.contrib, 0, slot, pitch, L, k);
+                nbu[r] = S.cbias[slot];
+                const int pos = __float_as_int(S.clabel[slot]);
+                const unsigned ilo = S.item[pos], ihi = S.item1[pos];
+                nalo[r] = S.ival[pos]; nahi[r] = S.ival1[pos];
+                nislo[r] = ilo == item;
+                const unsigned other = P.item_off + (nislo[r] ? ihi : ilo);
+                nqo[r] = load_row<LPI>(P.W, other, pitch, L, k);
+                nbo[r] = P.bias[other];
+            }
+        };
+        fetch(b, min(min(CHUNK, S.hot_sub), e - b));
+        for (int s0 = b; s0 < e; s0 += S.hot_sub) {
+            const int sn = min(S.hot_sub, e - s0);
+            float acc[EPL];
+#pragma unroll
+            for (int x = 0; x < EPL; x++) acc[x] = 0.0f;
+            float accb = 0.0f;
+            for (int c0 = 0; c0 < sn; c0 += CHUNK) {
+                const int cn = min(CHUNK, sn - c0);
+                float4 tu[PER], qo[PER];
+                float bu[PER], bo[PER], alo[PER], ahi[PER];
+                bool islo[PER];
+#pragma unroll
+                for (int r = 0; r < PER; r++) { tu[r] = ntu[r]; qo[r] = nqo[r]; bu[r] = nbu[r]; bo[r] = nbo[r]; alo[r] = nalo[r]; ahi[r] = nahi[r]; islo[r] = nislo[r]; }
+                {   // the round after this one: the rest of the sub-step, else the head of the next sub-step
+                    int nf = s0 + c0 + CHUNK, nn = sn - c0 - CHUNK;
+                    if (nn <= 0) { nf = s0 + S.hot_sub; nn = min(S.hot_sub, e - nf); }
+                    if (nn > 0) fetch(nf, min(CHUNK, nn));
+                }
+#pragma unroll
+                for (int r = 0; r < PER; r++) {
+                    const int sl = grp + r * G;
+                    const float4 qlo = islo[r] ? q : qo[r], qhi = islo[r] ? qo[r] : q;
+                    const float blo = islo[r] ? bi : bo[r], bhi = islo[r] ? bo[r] : bi;
+                    // the statements of k_window_users<LPI, true, 2>, in its order
+                    double bs = 0.0;
+                    if (use_ubias) { bs += (double)(1.0f * bu[r]); bs += 0.0; }
+                    bs += 0.0;
+                    bs += (double)(alo[r] * blo);
+                    bs += (double)(ahi[r] * bhi);
+                    double sum = (double)P.base_score + bs;
+                    float4 ti = f4zero();
+                    axpy4(ti, qlo, alo[r]);
+                    axpy4(ti, qhi, ahi[r]);
+                    sum += (double)group_dot<LPI>(tu[r], ti, L, k);
+                    const float pred = map_active((float)sum, P.active_type);
+                    const float err = cal_grad(1.0f, pred, P.active_type) * 1.0f;
+                    const float si = P.lr * err * (islo[r] ? alo[r] : ahi[r]);
+                    float4 wi = q;
+                    axpy4(wi, tu[r], si);
+                    float nbi = bi + si;
+                    reg_row<LPI>(P, wi, wd_i, true, L);
+                    nbi = nbi * (1.0f - P.lr * P.wd_item_bias);
+                    sub4(wi, q);
+                    if (sl < cn) { stage[sl * LPI + L] = wi; if (L == 0) stage_b[sl] = nbi - bi; }
+                }
+                __syncthreads();
+                // slot order (acc = ((0 + c_1) + c_2) + ...), one ROW ELEMENT per lane of the first wave; the bias word by the second wave (k_window_apply)
+                if (wv == 0) {
+                    constexpr int AH = EPL == 1 ? 32 : (EPL == 2 ? 16 : 8);
+                    bool on[EPL];
+#pragma unroll
+                    for (int z = 0; z < EPL; z++) on[z] = lane + 64 * z < K4;
+                    int sl = 0;
+                    for (; sl + AH <= cn; sl += AH) {
+                        const float *src = stage_f + (size_t)sl * K4 + lane;
+                        float t[AH][EPL];
+#pragma unroll
+                        for (int x = 0; x < AH; x++) {
+#pragma unroll
+                            for (int z = 0; z < EPL; z++) t[x][z] = on[z] ? src[x * K4 + 64 * z] : 0.0f;
+                        }
+#pragma unroll
+                        for (int x = 0; x < AH; x++) {
+#pragma unroll
+                            for (int z = 0; z < EPL; z++) acc[z] = acc[z] + t[x][z];
+                        }
+                    }
+                    for (; sl < cn; sl++) {
+#pragma unroll
+                        for (int z = 0; z < EPL; z++) acc[z] = acc[z] + (on[z] ? stage_f[(size_t)sl * K4 + lane + 64 * z] : 0.0f);
+                    }
+                } else if (wv == 1) {
+                    int sl = 0;
+                    for (; sl + 32 <= cn; sl += 32) {
+                        float t[32];
+#pragma unroll
+                        for (int x = 0; x < 32; x++) t[x] = stage_b[sl + x];
+#pragma unroll
+                        for (int x = 0; x < 32; x++) accb = accb + t[x];
+                    }
+                    for (; sl < cn; sl++) accb = accb + stage_b[sl];
+                }
+                if (c0 + CHUNK < sn) __syncthreads();   // (more rounds of this sub-step: the staging area is written again)
+            }
+            // the row moves by the sub-step's sum; every lane group takes the new row
+            if (wv == 0) {
+#pragma unroll
+                for (int z = 0; z < EPL; z++) { const int el = lane + 64 * z; if (el < K4) rowf[el] = rowf[el] + acc[z]; }
+            } else if (wv == 1 && lane == 0) {
+                rowb = rowb + accb;
+            }
+            __syncthreads();
+            q = rowq[L];
+            bi = rowb;
+        }
+        __syncthreads();   // (the next item of this workgroup writes rowq / rowb)
+        if (grp == 0) {   // the finished row and bias: to the item's FIRST slot (every slot has been read); k_window_pair_sums moves them into the model
+            store_contrib<LPI>(S.contrib, 0, (size_t)b, pitch, L, k, q);
+            if (L == 0) S.cbias[b] = bi;
+        }
+    }
+    __syncthreads();   // (the next scan resets the queue)
+    }
+}
+void launch_window_apply_pairs(const DevParams &P, const WindowSchedule &S, long num_item, hipStream_t st) {
+    if (S.hot_sub <= 0 || num_item <= 0) return;
+    const int lpi = lanes_per_instance(P.k);
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply_pairs<LPI, 1024>), dim3(256), dim3(1024), 0, st, P, S, num_item));
+}
+// the sums of a window with hot items: an item with more than hot_sub slots takes the row and bias k_window_apply_pairs left in its first slot, every other
+// item its slots added in place in slot order (the additions of k_window_items<LPI, false, true, .>)
+template <int LPI>
+__global__ __launch_bounds__(256) void k_window_pair_sums(const WindowSchedule S, int pitch, int k, long num_item, float *w_item, float *i_bias) {
+    constexpr int G = 256 / LPI;
+    const int L = threadIdx.x & (LPI - 1);
+    const int grp = threadIdx.x / LPI;
+    const bool owns = !(LPI * 4 > k && L * 4 >= k);
+    const long stride = (long)gridDim.x * G;
+    for (long i = (long)blockIdx.x * G + grp; i < num_item; i += stride) {
+        const int b = S.iptr[i], e = S.iptr[i + 1];
+        if (b == e) continue;
+        float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
+        if (e - b > S.hot_sub) {
+            if (owns) *w = load_contrib<LPI>(S.contrib, 0, (size_t)b, pitch, L, k);
+            if (L == 0) i_bias[i] = S.cbias[b];
+            continue;
+        }
+        float4 acc = f4zero();
+        float accb = 0.0f;
+        sum_contrib_slots<LPI, false>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
+        if (owns) {
+            float4 c = *w;
+            c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
+            *w = c;
+        }
+        if (L == 0) i_bias[i] = i_bias[i] + accb;
+    }
+}
+void launch_window_pair_sums(const WindowSchedule &S, int pitch, int k, long num_item, float *w_item, float *i_bias, hipStream_t st) {
+    if (num_item <= 0) return;
+    const int lpi = lanes_per_instance(k);
+    const long groups = 256 / lpi;
+    const unsigned grid = (unsigned)std::min<long>((num_item + groups - 1) / groups, 4096);
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_pair_sums<LPI>), dim3(grid), dim3(256), 0, st, S, pitch, k, num_item, w_item, i_bias));
 }
 // the replicated ranges of the active partition as one packed fp32 buffer and back (the item block a rank hands to the next one)
 template <bool SET>

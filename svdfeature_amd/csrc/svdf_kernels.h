@@ -52,6 +52,8 @@ void launch_delta_unpack(const DeltaRanges &R, float *snap, const void *src, int
 // buffer (item range [lo, hi) + nglobal zeros), and replicated ranges += all-reduced wire buffer
 bool window_slots_applies(const DevParams &P, const WindowSchedule &S);
 void launch_window_apply(const DevParams &P, const WindowSchedule &S, long num_item, float *w_item, float *i_bias, hipStream_t st);   // a window WITH hot items: ordered sub-steps of the hot ones beside the in-place sums of the others, one launch
+void launch_window_apply_pairs(const DevParams &P, const WindowSchedule &S, long num_item, hipStream_t st);   // rank pairs, a window WITH hot items: their ordered sub-steps (the model is not written; a hot row's final value goes to its first slot)
+void launch_window_pair_sums(const WindowSchedule &S, int pitch, int k, long num_item, float *w_item, float *i_bias, hipStream_t st);   // ... then hot rows moved in, the others' slots summed in place
 void launch_window_users(const DevParams &P, const WindowSchedule &S, int slots, int groups_per_wave, hipStream_t st);
 void launch_window_items(const WindowSchedule &S, int pitch, int k, long lo, long hi, long nglobal, void *dst, int half, hipStream_t st, long nslots = -1);
 void launch_delta_addto(const DeltaRanges &R, const void *src, int half, hipStream_t st);

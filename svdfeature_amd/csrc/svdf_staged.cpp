@@ -69,6 +69,10 @@ const char *Engine::staged_config_rule(bool blocks) const {
         if (blocks) return "window_item_sub > 0 is not supported with user-group (SVD++) trainers";
         if (wunit_inplace_ == 0) return "window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)";
     }
+    if (wseq_pair_sub_ > 0) {
+        if (contrib_bf16_) return "window_pair_sub > 0 needs amd:contrib = fp32";
+        if (blocks) return "window_pair_sub > 0 is not supported with user-group (SVD++) trainers";
+    }
     if (blocks && mp_.common_feedback_space != 0) return "user-group trainers need a feedback space of their own (common_feedback_space = 0) in the window step";
     if (shared_user() && !(shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user)) return "amd:shared_user_from must be in 1 .. num_user";
     return nullptr;

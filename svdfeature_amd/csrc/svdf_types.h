@@ -217,7 +217,8 @@ struct WindowSchedule {
     // against the row as the previous sub-step left it (oracle/svdf_oracle.c: svdo_update_window_substeps).  Needs unit values, one item entry,
     // fp32 contribution rows.
     int hot_sub;
-    float *clabel;              // [slots] scratch: the label of a hot entry
+    float *clabel;              // [slots] scratch: the label of a hot entry; rank pairs (label always 1; knob window_pair_sub): the bits of the pair's
+                                // position in the user-grouped columns, through which k_window_apply_pairs finds both item ids and signs
 };
 
 // Window-minibatch data set of USER UNITS (svdf_k_wunit.hip): user-group (SVD++) blocks and rows with global

@@ -41,6 +41,7 @@ Dataset *Engine::dataset_window_from_pairs(long n, const unsigned *user, const u
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
     check(!multi_ || in_multi_scope(), "window data sets are per rank; shard rank pairs through svdfeature_amd.multi_gpu");
+    if (wseq_pair_sub_ > 0) wseq_pair_check("dataset_window_from_pairs");
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get());
     window_build(ds.get(), n, user, pos, nullptr, neg);

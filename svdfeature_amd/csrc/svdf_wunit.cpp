@@ -959,17 +959,19 @@ bool Engine::wseq_hot_ok() const {
 //   * how stale the USERS' view of a hot row gets (they read it as of the window start): at most window_hot_max updates (2 048; CPU simulation on a
 //     10 M-rating Zipf(0.7) stream, tools/substep_sim.py: 500 per window +1.5e-5, 1 000 +2.8e-5, 2 000 +6.0e-5, 4 000 +9.1e-5 against the 1e-4 contract;
 //     on the MI355X at the configs[1] size, 3 data seeds: 1 024 -> max 4.2e-5, 2 048 -> 6.6e-5, 3 072 -> 7.2e-5, profiles/r06_hot_lane_calibration.txt).
-long Engine::wseq_windows_hot(long n, const std::vector<long> &item_count) const {
+long Engine::wseq_windows_hot(long n, const std::vector<long> &item_count) const { return wseq_windows_sub(n, item_count, wseq_hot_sub_, wseq_hot_max_); }
+// the same rule for any sub-step size and cap; the mean is over ENTRIES (sum_i c_i: n for ratings, 2 n for rank pairs, whose items count both signs)
+long Engine::wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const {
     if (n <= 0) return 1;
     if (window_set_) return std::max<long>(1, (n + stage_window_ - 1) / stage_window_);
-    long mx = 0;
-    for (long c : item_count) mx = std::max(mx, c);
+    long mx = 0, total = 0;
+    for (long c : item_count) { mx = std::max(mx, c); total += c; }
     auto met = [&](long W) {
         double s = 0.0;
-        for (long c : item_count) s += std::min((double)c / (double)W, (double)wseq_hot_sub_) * (double)c;
-        return s / (double)n;
+        for (long c : item_count) s += std::min((double)c / (double)W, (double)sub) * (double)c;
+        return s / (double)total;
     };
-    long lo = std::max<long>(1, (mx + wseq_hot_max_ - 1) / wseq_hot_max_);
+    long lo = std::max<long>(1, (mx + cap - 1) / cap);
     if (met(lo) <= (double)wseq_per_target_) return lo;
     long hi = lo;
     while (met(hi) > (double)wseq_per_target_ && hi < n) hi *= 2;
@@ -1021,15 +1023,43 @@ Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned 
 // rank pairs (BASELINE configs[4]): two signed item entries per instance, two contribution slots per pair.  The window rule counts both
 // entries; amd:window (pairs per window) overrides -- the demo-rate calibration allows ~320 updates per item per window
 // (profiles/r04_pairs_windows_demo_rate.txt), an order of magnitude more than the rating default kept here.
+// window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs): fp32 slots, random-order trainers, the one-GPU sequence
+void Engine::wseq_pair_check(const char *what) const {
+    check(!contrib_bf16_, "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) needs amd:contrib = fp32");
+    check(!user_group(), "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is not supported with user-group (SVD++) trainers");
+    check(strcmp(what, "dataset_window_from_pairs") != 0,
+          "svdf_dataset_window_from_pairs: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence "
+          "(amd:step = minibatch); the N-rank exchange sums every slot on the wire");
+    check(gpus_ == 1 && !multi_ && !is_peer_,
+          "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence; amd:gpus > 1 sums every slot on the wire");
+}
 Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg) {
     std::vector<long> ci((size_t)mp_.num_item, 0);
     for (long r = 0; r < n; r++) {
         if (pos[r] >= (unsigned)mp_.num_item || neg[r] >= (unsigned)mp_.num_item) fail("item feature index exceed bound");
         ci[pos[r]]++; ci[neg[r]]++;
     }
-    const long W = wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    const int psub = wseq_pair_sub_;
+    if (psub > 0) wseq_pair_check("dataset_from_pairs");
+    // ordered sub-steps for hot items: the window count of wseq_windows_hot with the pair knobs, and which windows hold an
+    // item with more than window_pair_sub slots (both entries of a pair count)
+    const long W = psub > 0 ? wseq_windows_sub(n, ci, psub, wseq_pair_max_) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    std::vector<char> whot((size_t)W, 0);
+    if (psub > 0) {
+        std::vector<int> stamp((size_t)mp_.num_item, -1), cnt((size_t)mp_.num_item, 0);
+        for (long w = 0; w < W; w++) {
+            const long b0 = n * w / W, b1 = n * (w + 1) / W;
+            for (long r = b0; r < b1 && !whot[(size_t)w]; r++) {
+                for (const unsigned it : {pos[r], neg[r]}) {
+                    if (stamp[it] != (int)w) { stamp[it] = (int)w; cnt[it] = 0; }
+                    if (++cnt[it] > psub) whot[(size_t)w] = 1;
+                }
+            }
+        }
+    }
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
+    ds->wseq_pair_sub = psub;
     DevBuf<unsigned> d_user, d_pos, d_neg;
     const bool resident = device_window_ready() && n > 0;
     if (resident) { need_device("dataset"); d_user.upload(user, (size_t)n, stream_); d_pos.upload(pos, (size_t)n, stream_); d_neg.upload(neg, (size_t)n, stream_); }
@@ -1039,6 +1069,7 @@ Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *p
         adopt(c.get());
         if (resident && b1 > b0) { window_build_header(c.get(), b1 - b0, true); window_build_resident(c.get(), b1 - b0, d_user.p + b0, d_pos.p + b0, nullptr, d_neg.p + b0); }
         else window_build(c.get(), b1 - b0, user + b0, pos + b0, nullptr, neg + b0);
+        c->win_hot = whot[(size_t)w] != 0;
         ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
         ds->wchild.push_back(c.release());
     }
@@ -1053,7 +1084,13 @@ void Engine::wseq_train(Dataset *ds) {
     bool any_hot = false;
     long max_slots = 1;
     for (Dataset *c : ds->wchild) if (c->kind == 5 && c->win_hot) { any_hot = true; max_slots = std::max(max_slots, c->win_slots); }
-    const bool hot_lane = any_hot && wseq_hot_ok();
+    const bool pair_seq = ds->wseq_pair_sub >= 0;   // built by wseq_from_pairs: its hot windows belong to the pair lane (window_pair_sub), not to window_hot_sub
+    if (pair_seq) {
+        check(ds->wseq_pair_sub == wseq_pair_sub_,
+              "train_dataset: the window sequence was built with another window_pair_sub (ordered sub-steps for hot items of rank pairs); build the data set again after changing the knob");
+        if (wseq_pair_sub_ > 0) wseq_pair_check("train_dataset");
+    }
+    const bool hot_lane = any_hot && (pair_seq || wseq_hot_ok());
     if (any_hot) check(hot_lane, "train_dataset: the window sequence was built with ordered sub-steps for hot items (window_hot_sub); the configuration changed since");
     if (hot_lane) d_clabel_.reserve((size_t)max_slots);
     if (ds->wseq_shared_sub >= 0)
@@ -1067,9 +1104,13 @@ void Engine::wseq_train(Dataset *ds) {
             d_contrib_.reserve((size_t)std::max<long>(c->win_slots, 1) * (size_t)pitch_);
             d_cbias_.reserve((size_t)std::max<long>(c->win_slots, 1));
             WindowSchedule S = window_view(c);
-            if (hot_lane && c->win_hot) { S.hot_sub = wseq_hot_sub_; S.clabel = d_clabel_.p; }
+            if (hot_lane && c->win_hot) { S.hot_sub = pair_seq ? wseq_pair_sub_ : wseq_hot_sub_; S.clabel = d_clabel_.p; }
             launch_window_users(P, S, window_slots_, window_groups_, stream_);
-            if (S.hot_sub > 0) launch_window_apply(P, S, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_);
+            if (S.hot_sub > 0 && pair_seq) {   // walk, hot apply (does not write the model: a pair reads its OTHER item's row), then hot rows moved in + the cold sums
+                launch_window_apply_pairs(P, S, mp_.num_item, stream_);
+                launch_window_pair_sums(S, pitch_, mp_.num_factor, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_);
+                n_launches_++;
+            } else if (S.hot_sub > 0) launch_window_apply(P, S, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_);
             else launch_window_items_local(S, pitch_, mp_.num_factor, 0, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_, c->win_slots);
         } else {
             wunit_train(c);
