@@ -155,12 +155,16 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 bu[j] = P.bias[ur[j]];
             }
         }
-        int nmax = n;   // the wave walks as many steps as its longest run (dot_slots is a wave-wide operation)
+        // Every row is here before step 0 (an empty statement that reads a register of each: the compiler places its counted waits in front of
+        // it).  Without it the stores below, each under `act`, leave the compiler unsure of what is in flight where the paths meet, and steps
+        // 1 ... begin with vmcnt(1) / vmcnt(0): every step waited for the previous step's stores to be acknowledged.  With it the step loop
+        // holds no memory wait at all.  (Issuing all R rows at once, without the `if (j < n)` above, was measured too: 20.2 against 17.1 ms per
+        // pass, profiles/r13_runs_gather.md -- the row-by-row gather stays.)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o));
+        for (int j = 0; j < R; j++) asm volatile("" :: "v"(p[j][0].x), "v"(p[j][V - 1].x), "v"(bu[j]));
 #pragma unroll
         for (int j = 0; j < R; j++) {
-            if (j >= nmax) break;
+            if (!__any(j < n)) break;   // the wave walks as many steps as its longest run (dot_slots is a wave-wide operation)
             // the arithmetic of k_basicmf_slots (= basicmf_wave<K / 4, ., true, true, true>) on (user row j, the item row as the run has left it)
             double bs = 0.0;
             bs += (double)(1.0f * bu[j]); bs += 0.0;
