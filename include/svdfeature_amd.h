@@ -167,7 +167,14 @@ int svdf_rank_prefetch_buffer_file(svdf_trainer *t, const char *path);
 int64_t svdf_rank_sample_buffer_file(svdf_trainer *t, const char *in_path, const char *out_path);
 void svdf_dataset_destroy(svdf_dataset *ds);                     /* also valid after svdf_destroy of its trainer */
 int svdf_train_dataset(svdf_trainer *t, svdf_dataset *ds);       /* one pass, asynchronous on the trainer's stream */
-int svdf_predict_dataset(svdf_trainer *t, svdf_dataset *ds, float *out); /* out[num_row], file order */
+/* out[num_row], in FILE order: the order of the rows as they were handed to svdf_dataset_from_* / svdf_dataset_window_from_*.  Read-only scoring
+ * against the model as it stands at the call (pending staged rows are flushed first).  Window data sets score too -- the window sequences of
+ * "amd:step" = minibatch / auto and the stand-alone windows of svdf_dataset_window_from_* (every window keeps its rows' source positions,
+ * 4 bytes per row): each value is bit-identical to svdf_predict_csr_batch (user-group data sets: svdf_predict_block) for the same row on the same
+ * model; a rank pair is one row -- user value 1, the two items in index order with the negative's sign flipped.  A stand-alone window that
+ * svdf_train_dataset has walked but whose sums are not applied yet (svdf_window_delta_*) is scored against the model WITHOUT those sums.  Only
+ * the data sets of an "amd:gpus" handle are refused: their rows are regrouped rank by rank and keep no file order. */
+int svdf_predict_dataset(svdf_trainer *t, svdf_dataset *ds, float *out);
 /* dataset facts: 0 num_row, 1 number of conflict-free batches, 2 largest batch, 3 kernel kind
  * (0 = basicMF fused kernel, 1 = general sparse kernel, 2 = few-row fused kernel, 3 = SVD++ user units),
  * 4 algorithmic bytes per pass, 5 number of user units, 6 units on the register-resident
@@ -402,8 +409,10 @@ int svdf_set_knob(svdf_trainer *t, const char *name, long value);
  * stay in HBM; *sum_sq_err = sum over instances of ((pred - label) * scale_score)^2 (difference and scaling in fp32, square and
  * sum in fp64 like add_eval), *count = instances; RMSE = sqrt(sum / count) (print_stat).  The sum is a fixed fp64 tree on the
  * device + long double over the partial sums, the reference's is a sequential long double sum: equal to ~1e-13 relative.
- * Works on the data sets of an "amd:gpus" handle and on window data sets too (every piece is scored on the rank that holds it);
- * svdf_predict_dataset does not: their rows are regrouped, there is no file order to report predictions in. */
+ * Works on the data sets of an "amd:gpus" handle (every piece is scored on the rank that holds it; svdf_predict_dataset refuses those:
+ * their rows are regrouped, there is no file order to report predictions in) and on window data sets: a window sequence is scored window by
+ * window, the partial sums of all windows added on the host; rank-pair windows carry label 1 for every pair (apex_svd_data.cpp:905-911); a
+ * stand-alone window trained but not yet applied is scored against the model without its pending sums (see svdf_predict_dataset). */
 int svdf_eval_dataset(svdf_trainer *t, svdf_dataset *ds, float scale_score, double *sum_sq_err, int64_t *count);
 
 /* ---- ranking: class apex_svd::ISVDRanker (apex_svd.h:160-197) as implemented by SVDFeatureRanker

@@ -704,10 +704,57 @@ void Engine::disown(Dataset *ds) {
 // One exchange window of a rank's shard, grouped by user (svdf_k_window.hip).  svdf_train_dataset on it is
 // the first half of the window step (user side exact, item side read-only); window_delta_pack sums the item-side contributions
 // into the wire buffer; after the all-reduce window_delta_apply adds the sum on every rank.  Replaces what one instance
+
+// =============================================================================== scoring of window data sets
+// the scratch of window_score for the largest of the windows, taken once before the first launch (growing a buffer frees the old one)
+void Engine::window_score_reserve(Dataset *const *child, size_t nchild) {
+    long nmax = 1, segmax = 0, pairmax = 0;
+    for (size_t w = 0; w < nchild; w++) {
+        const Dataset *c = child[w];
+        nmax = std::max(nmax, c->num_row);
+        if (c->kind == 7 && c->wu_feedback) segmax = std::max<long>(segmax, std::max<long>(c->wu_nseg, 1));
+        if (c->kind == 5 && c->fused.max_ni == 2) pairmax = std::max(pairmax, c->num_row);
+    }
+    w_ucol_.reserve((size_t)nmax); w_segcol_.reserve((size_t)nmax); w_pred_.reserve((size_t)nmax);
+    if (segmax > 0) { w_sfb_.reserve((size_t)segmax * (size_t)pitch_); w_sfbb_.reserve((size_t)segmax); }
+    if (pairmax > 0 && (w_ones_.cap < (size_t)pairmax || !w_ones_.p)) {
+        w_ones_.reserve((size_t)pairmax);
+        launch_runs_fill_u32(reinterpret_cast<unsigned *>(w_ones_.p), (long)w_ones_.cap, 0x3f800000u, stream_);
+    }
+}
+// One window (kind 5 or 7) scored against the model as it stands: out[r] in regrouped order (pos == nullptr) or out[pos[r]].  Returns the labels
+// in regrouped order (rank pairs: every label is 1, apex_svd_data.cpp:905-911).  Read-only: neither the model nor the window nor the trainer's
+// contribution scratch is written, so a trained window whose sums are still pending (window_trained_) stays as it is.
+const float *Engine::window_score(Dataset *c, float *out, const int *pos) {
+    const DevParams &P = params();
+    const long n = c->num_row;
+    if (c->kind == 5) {
+        launch_window_user_column(c->win_urec.p, (int)c->num_units, w_ucol_.p, stream_);
+        if (c->fused.max_ni == 2) {   // rank pairs
+            launch_window_predict_pairs(P, window_view(c), w_ucol_.p, n, pos, out, stream_);
+            n_launches_ += 2;
+            return w_ones_.p;
+        }
+        BasicSchedule S{w_ucol_.p, c->item.p, c->label.p, nullptr, nullptr};
+        if (!pos) launch_predict_basic(P, S, n, out, stream_);
+        else {   // the contract's scoring kernel writes regrouped order: scattered by position afterwards
+            launch_predict_basic(P, S, n, w_pred_.p, stream_);
+            device_scatter_f32(w_pred_.p, pos, out, n, stream_);
+        }
+        n_launches_ += 2;
+        return c->label.p;
+    }
+    const WUnitSchedule S = wunit_view(c);
+    launch_wunit_score_columns(S, w_ucol_.p, w_segcol_.p, stream_);
+    if (c->wu_feedback) launch_wunit_score_prepare(P, S, c->wu_nseg, w_sfb_.p, w_sfbb_.p, stream_);
+    launch_wunit_score(P, S, c->wu_feedback, w_ucol_.p, w_segcol_.p, w_sfb_.p, w_sfbb_.p, n, pos, out, stream_);
+    n_launches_ += c->wu_feedback ? 3 : 2;
+    return c->label.p;
+}
+
 void Engine::predict_dataset(Dataset *ds, float *out) {
     check(ds && ds->owner == this, "predict_dataset: dataset belongs to another trainer");
-    check(ds->kind != 7 && ds->kind != 8, "predict_dataset: window data sets are training sets (their rows are regrouped by user); score rows with svdf_predict_csr_batch / svdf_predict_block or a level-scheduled data set of the same rows");
-    check(ds->kind != 5 && ds->kind != 6, "predict_dataset: window / multi-GPU data sets are training sets (their rows are regrouped: there is no file order to report predictions in); svdf_eval_dataset gives their squared error, svdf_predict_csr_batch scores rows (routed to the owner of each user)");
+    check(ds->kind != 6, "predict_dataset: multi-GPU data sets are training sets (their rows are regrouped rank by rank: there is no file order to report predictions in); svdf_eval_dataset gives their squared error, svdf_predict_csr_batch scores rows (routed to the owner of each user)");
     check(ds->sched_signature == schedule_signature(),
           "predict_dataset: the dataset was scheduled under another configuration; build it again");
     flush();
@@ -715,6 +762,24 @@ void Engine::predict_dataset(Dataset *ds, float *out) {
     const long n = ds->num_row;
     if (n == 0) return;
     w_out_.reserve((size_t)n);
+    if (ds->kind == 5 || ds->kind == 7 || ds->kind == 8) {   // window data sets: every window scored into its file range, one copy out
+        Dataset *self[1] = {ds};
+        Dataset *const *child = ds->kind == 8 ? ds->wchild.data() : self;
+        const size_t nchild = ds->kind == 8 ? ds->wchild.size() : 1;
+        check(ds->kind != 8 || ds->wfirst.size() == nchild, "predict_dataset: the window sequence keeps no file positions");
+        window_score_reserve(child, nchild);
+        for (size_t w = 0; w < nchild; w++) {
+            Dataset *c = child[w];
+            if (c->num_row == 0) continue;
+            const long first = ds->kind == 8 ? ds->wfirst[w] : 0;
+            check(c->win_has_pos && c->win_pos.p && first >= 0 && first + c->num_row <= n, "predict_dataset: the window data set keeps no file positions (windows of staged chunks and of amd:gpus shards are built without them)");
+            window_score(c, w_out_.p + first, c->win_pos.p);
+        }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(out, w_out_.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipStreamSynchronize(stream_));
+        return;
+    }
     if (ds->kind == 4) {
         const UnitDev &d = ds->unitdev;
         launch_imfb(P, d.csr(), d.units.p, d.blks.p, d.fbidx.p, d.fbval.p, nullptr, 0, ds->num_units, sample_counter_, w_out_.p, stream_);
@@ -783,8 +848,6 @@ void Engine::eval_dataset(Dataset *ds, float scale, double *sum_sq, int64_t *cou
         return;
     }
     check(ds->kind != 6, "eval_dataset: not a data set of this handle");
-    check(ds->kind != 7 && ds->kind != 8, "eval_dataset: user-unit window data sets are training sets; evaluate a level-scheduled data set of the same rows");
-    check(ds->kind != 5 || ds->fused.max_ni == 1, "eval_dataset: rank-pair window data sets have no label to compare a score with");
     check(ds->sched_signature == schedule_signature(), "eval_dataset: the dataset was scheduled under another configuration; build it again");
     flush();
     const DevParams &P = params();
@@ -793,6 +856,35 @@ void Engine::eval_dataset(Dataset *ds, float scale, double *sum_sq, int64_t *cou
     if (n == 0) return;
     w_out_.reserve((size_t)n);
     const float *labels = nullptr;
+    if (ds->kind == 5 || ds->kind == 7 || ds->kind == 8) {
+        // window data sets: every window scored in regrouped order next to its own labels (no file positions needed); the windows' per-workgroup
+        // fp64 partial sums side by side, added in long double on the host like every other kind's
+        Dataset *self[1] = {ds};
+        Dataset *const *child = ds->kind == 8 ? ds->wchild.data() : self;
+        const size_t nchild = ds->kind == 8 ? ds->wchild.size() : 1;
+        long gtotal = 0, cnt = 0;
+        for (size_t w = 0; w < nchild; w++) if (child[w]->num_row > 0) { gtotal += sqerr_partials_grid(child[w]->num_row); cnt += child[w]->num_row; }
+        check(cnt == n, "eval_dataset: the windows of the sequence do not add up to its rows");
+        if (d_partials_.cap < (size_t)gtotal) { if (d_partials_.p) (void)hipFree(d_partials_.p); d_partials_.p = nullptr; d_partials_.cap = 0; HIPCHECK(hipMalloc((void **)&d_partials_.p, (size_t)gtotal * sizeof(double))); d_partials_.cap = (size_t)gtotal; }
+        window_score_reserve(child, nchild);
+        long g0 = 0;
+        for (size_t w = 0; w < nchild; w++) {
+            Dataset *c = child[w];
+            if (c->num_row == 0) continue;
+            const float *lab = window_score(c, w_out_.p, nullptr);
+            launch_sqerr_partials(w_out_.p, lab, c->num_row, scale, d_partials_.p + g0, stream_);
+            g0 += sqerr_partials_grid(c->num_row);
+            n_launches_++;
+        }
+        HIPCHECK(hipGetLastError());
+        std::vector<double> part((size_t)gtotal);
+        HIPCHECK(hipMemcpyAsync(part.data(), d_partials_.p, (size_t)gtotal * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipStreamSynchronize(stream_));
+        long double acc = 0.0L;
+        for (double x : part) acc += (long double)x;
+        *sum_sq = (double)acc;
+        return;
+    }
     if (ds->kind == 4) {
         const UnitDev &d = ds->unitdev;
         launch_imfb(P, d.csr(), d.units.p, d.blks.p, d.fbidx.p, d.fbval.p, nullptr, 0, ds->num_units, sample_counter_, w_out_.p, stream_);
@@ -801,13 +893,6 @@ void Engine::eval_dataset(Dataset *ds, float scale, double *sum_sq, int64_t *cou
         const UnitDev &d = ds->unitdev;
         launch_svdpp_predict(P, d.csr(), d.units.p, d.fbidx.p, d.fbval.p, ds->num_units, w_out_.p, stream_);
         labels = d.label.p;
-    } else if (ds->kind == 5) {   // a window data set: instances grouped by user; the user column is written out for the scoring kernel
-        w_pred_.reserve((size_t)n);
-        unsigned *ucol = reinterpret_cast<unsigned *>(w_pred_.p);
-        launch_window_user_column(ds->win_urec.p, (int)ds->num_units, ucol, stream_);
-        BasicSchedule S{ucol, ds->item.p, ds->label.p, nullptr, nullptr};
-        launch_predict_basic(P, S, n, w_out_.p, stream_);
-        labels = ds->label.p;
     } else if (ds->kind == 0 || ds->kind == 9 || ds->kind == 10) {   // (kind 9: the columns hold the cold ratings, then the units' rows: svdf_pivot.cpp; kind 10: file order)
         BasicSchedule S{ds->user.p, ds->item.p, ds->label.p, ds->unit_values ? nullptr : ds->uval.p, ds->unit_values ? nullptr : ds->ival.p};
         launch_predict_basic(P, S, n, w_out_.p, stream_);

@@ -297,6 +297,12 @@ struct Dataset {
     int64_t chained_levels = 0;   // levels the current launch sequence of this data set walks inside chained launches
     bool win_hot = false;         // kind 5 inside a one-GPU sequence: some item has more than window_hot_sub (rank pairs: window_pair_sub) slots in this window (ordered sub-steps: k_window_apply / k_window_apply_pairs)
     long win_slots = 0;           // contribution slots of the window = item entries (kind 7: + feedback entries)
+    // kinds 5 and 7 of a resident data set (a one-GPU sequence's child, a stand-alone svdf_dataset_window_from_*): row r of the regrouped columns
+    // was row win_pos[r] of the window's source range -- what svdf_predict_dataset reports file order through.  Windows of
+    // staged chunks and of amd:gpus shards are built without it.
+    DevBuf<int> win_pos;
+    bool win_has_pos = false;
+    std::vector<long> wfirst;     // kind 8: the first file row of every child (children cover consecutive file ranges)
     // kind 7: window-minibatch data set of user units (svdf_k_wunit.hip): user-group blocks / rows with global features
     DevBuf<WinUnit> wu_units;
     DevBuf<WinSeg> wu_segs;
@@ -648,6 +654,15 @@ class Engine {
     bool window_build_device(Dataset *ds, long n, const unsigned *user, const unsigned *item, const float *label, const unsigned *neg);
     void window_build_resident(Dataset *ds, long n, const unsigned *d_user, const unsigned *d_item, const float *d_label, const unsigned *d_neg);
     void window_build_header(Dataset *ds, long n, bool pairs);
+    // scoring of window data sets (svdf_dataset.cpp): one window's predictions in regrouped order (pos == nullptr) or
+    // scattered to out[pos[r]]; returns the window's labels in regrouped order (rank pairs: ones)
+    const float *window_score(Dataset *c, float *out, const int *pos);
+    void window_score_reserve(Dataset *const *child, size_t nchild);
+    bool staged_building_ = false;        // set while a staged chunk's transient window sequence is built (svdf_staged.cpp): no file positions
+    bool window_keeps_positions() const { return !staged_building_ && !in_multi_scope(); }
+    DevBuf<unsigned> w_ucol_;             // scoring scratch: the user (kind 7: + segment) of every regrouped row of the window being scored
+    DevBuf<int> w_segcol_;
+    DevBuf<float> w_sfb_, w_sfbb_, w_ones_;   // ... the segments' prepared feedback sums / biases (kept apart from d_dvec_: a trained window's pending sums read that), labels of rank pairs
     bool device_window_ready() const { return !host_only_ && device_window_; }
     DevBuf<float> d_dvec_, d_dbias_;      // deferred feedback scatter: one scaled delta row + bias delta per segment of the largest window
     DevBuf<float> d_contrib_, d_cbias_;   // window-minibatch scratch: one contribution row + bias word per instance of the largest window

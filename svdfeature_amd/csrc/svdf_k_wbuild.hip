@@ -123,12 +123,13 @@ __global__ __launch_bounds__(256) void k_wb_urec(const unsigned *keys_sorted, co
 // the regrouped columns: sorted position p (user-major, file order inside a user) -> its place in launch order
 __global__ __launch_bounds__(256) void k_wb_place(long n, int pairs, const unsigned *inst, const int *mark, const int *run_start, const int *run_begin,
                                                   const unsigned *item, const unsigned *neg, const float *label, const int *slot_e, unsigned *w_item,
-                                                  unsigned *w_item1, float *w_label, float *w_v0, float *w_v1, int *w_slot, int *w_slot1, const int *iptr) {
+                                                  unsigned *w_item1, float *w_label, float *w_v0, float *w_v1, int *w_slot, int *w_slot1, const int *iptr, int *w_pos) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
         const int j = mark[p] - 1;
         const long at = (long)run_begin[j] + (p - (long)run_start[j]);
         const long r = (long)inst[p];
+        if (w_pos) w_pos[at] = (int)r;   // the instance's position in the window's source columns (scoring in file order)
         if (!pairs) {
             w_item[at] = item[r];
             w_label[at] = label[r];
@@ -187,7 +188,7 @@ void device_window_build(const WBuildIn &in, const WBuildBuffers &B, const WBuil
     WCHK(rocprim::exclusive_scan(B.tmp, tb, B.k0, B.v0, 0u, (size_t)n, rocprim::plus<unsigned>(), st));
     hipLaunchKernelGGL(k_wb_urec, dim3(wb_grid(n)), dim3(256), 0, st, B.k1, B.v1, B.v0, B.run_user, n, B.state, out.urec, B.run_begin);
     hipLaunchKernelGGL(k_wb_place, dim3(wb_grid(n)), dim3(256), 0, st, n, in.pairs, B.inst, B.mark, B.run_start, B.run_begin, in.item, in.neg, in.label, B.slot_e,
-                       out.item, out.item1, out.label, out.v0, out.v1, out.slot, out.slot1, out.iptr);
+                       out.item, out.item1, out.label, out.v0, out.v1, out.slot, out.slot1, out.iptr, out.pos);
     unsigned hs[WB_WORDS];
     WCHK(hipMemcpyAsync(hs, B.state, sizeof(hs), hipMemcpyDeviceToHost, st));
     WCHK(hipStreamSynchronize(st));

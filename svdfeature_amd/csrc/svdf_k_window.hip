@@ -1056,6 +1056,41 @@ void launch_window_user_column(const WinUser *urec, int nusers, unsigned *user_o
     const long blocks = ((long)nusers * 64 + 255) / 256;
     hipLaunchKernelGGL(k_window_user_column, dim3((unsigned)blocks), dim3(256), 0, st, urec, nusers, user_out);
 }
+// read-only scoring of a rank-pair window: the instance is one row -- user:1, the lower item id with ival, the higher with
+// ival1 -- and the statements are k_predict_fused's for that shape (calc_bias in double in entry order, apex_svd_base.h:445-454), so a score
+// equals svdf_predict_csr_batch's for the same row bit for bit.  The user comes from the column k_window_user_column wrote.  Nothing of the
+// model or of the window is written; slots and hot marks are not read.
+template <int LPI>
+__global__ __launch_bounds__(256) void k_window_predict_pairs(const DevParams P, const WindowSchedule S, const unsigned *user_col, long n, const int *pos,
+                                                              float *out) {
+    constexpr int IPW = 64 / LPI;
+    const int lane = threadIdx.x & 63;
+    const int L = lane & (LPI - 1);
+    const long gidx = ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * IPW + lane / LPI;
+    const long stride = (long)gridDim.x * (blockDim.x >> 6) * IPW;
+    for (long s = gidx; s < n; s += stride) {
+        const unsigned ur = P.user_off + user_col[s];
+        const unsigned i0 = P.item_off + S.item[s], i1 = P.item_off + S.item1[s];
+        const float v0 = S.ival[s], v1 = S.ival1[s];
+        double bs = 0.0;
+        if (P.no_user_bias == 0) bs += (double)(1.0f * P.bias[ur]);
+        bs += (double)(v0 * P.bias[i0]);
+        bs += (double)(v1 * P.bias[i1]);
+        float4 tu = f4zero(), ti = f4zero();
+        axpy4(tu, load_row<LPI>(P.W, ur, P.pitch, L, P.k), 1.0f);
+        axpy4(ti, load_row<LPI>(P.W, i0, P.pitch, L, P.k), v0);
+        axpy4(ti, load_row<LPI>(P.W, i1, P.pitch, L, P.k), v1);
+        double sum = (double)P.base_score + bs;
+        sum += (double)group_dot<LPI>(tu, ti, L, P.k);
+        if (L == 0) out[pos ? (long)pos[s] : s] = map_active((float)sum, P.active_type);
+    }
+}
+void launch_window_predict_pairs(const DevParams &P, const WindowSchedule &S, const unsigned *user_col, long n, const int *pos, float *out, hipStream_t st) {
+    if (n <= 0) return;
+    const int lpi = lanes_per_instance(P.k);
+    const int grid = grid_for(n, lpi, 256 * 8);
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_predict_pairs<LPI>), dim3(grid), dim3(256), 0, st, P, S, user_col, n, pos, out));
+}
 void launch_ranges_copy(const DeltaRanges &R, float *buf, int set, hipStream_t st) {
     const long total = R.off[R.n];
     if (total <= 0) return;

@@ -763,6 +763,136 @@ void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipSt
 // nitem_hot: the hot item rows of the window, S.hot[S.nhot .. S.nhot + nitem_hot)
 void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st) { launch_wunit_apply_hot<true>(P, S, nitem_hot, S.item_sub, st); }
 
+// ------------------------------------------------------------------------------------------------- scoring (read-only)
+// svdf_predict_dataset / svdf_eval_dataset on a window of user units.  Nothing is updated, so the rows are independent: they are scored
+// LPI lanes per row, not walked unit by unit.  Three launches per window:
+//   k_wunit_score_columns  the user and the segment of every regrouped row (one wave per unit spreads its segments' row ranges);
+//   k_wunit_score_prepare  user-group trainers: prepare_ufeedback (apex_svd_base.h:523-538) once per segment, k_wunit_walk's prepare block in
+//                          list order -- the sum of the feedback rows and of their biases, into a scratch row per segment;
+//   k_wunit_score          the walk's pred block statement for statement (:445-454; SVDPPFeature::predict :583-591 for user-group rows), the user's
+//                          row and bias from the model as it stands.
+// Every layout variant of a window is read -- estride / rptr rows, uval absent, the shared user section, the feature_item child section -- and of
+// an entry only idx, val and (children) pad = the parent's position: slots and the hot lanes' marks (ent.pad, uent.pad, child slots <= -2) are
+// not looked at.  A score equals svdf_predict_csr_batch's / svdf_predict_block's for the same row bit for bit.
+__global__ __launch_bounds__(256) void k_wunit_score_columns(const WUnitSchedule S, unsigned *user_col, int *seg_col) {
+    const int lane = threadIdx.x & 63;
+    const long uidx = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (uidx >= S.nunits) return;
+    const WinUnit un = S.units[uidx];
+    for (int sg = 0; sg < un.seg_count; sg++) {
+        const WinSeg seg = sg == 0 ? un.first : S.segs[un.seg_begin + sg];
+        for (int j = lane; j < seg.row_count; j += 64) {
+            user_col[seg.row_begin + j] = un.user;
+            seg_col[seg.row_begin + j] = un.seg_begin + sg;
+        }
+    }
+}
+template <int LPI>
+__global__ __launch_bounds__(256) void k_wunit_score_prepare(const DevParams P, const WUnitSchedule S, long nseg, float *fbvec, float *fbbias) {
+    constexpr int IPW = 64 / LPI;
+    const int lane = threadIdx.x & 63;
+    const int L = lane & (LPI - 1);
+    const long q = ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * IPW + lane / LPI;
+    if (q >= nseg) return;
+    const WinSeg seg = S.segs[q];
+    const int pitch = P.pitch, k = P.k;
+    const bool ub = P.no_user_bias == 0;
+    float4 tmp_fb = f4zero();
+    float tmp_bias = 0.0f;
+    for (int j = seg.fb_begin; j < seg.fb_begin + seg.fb_count; j++) {
+        const WinEnt f = S.fbent[j];
+        const unsigned row = P.fb_off + f.idx;
+        axpy4(tmp_fb, load_row<LPI>(P.W, row, pitch, L, k), f.val);
+        if (ub) tmp_bias = tmp_bias + P.bias[row] * f.val;
+    }
+    if (!(LPI * 4 > k && L * 4 >= k)) *reinterpret_cast<float4 *>(fbvec + (size_t)q * pitch + (size_t)L * 4) = tmp_fb;
+    if (L == 0) fbbias[q] = tmp_bias;
+}
+template <int LPI, bool FB>
+__global__ __launch_bounds__(256) void k_wunit_score(const DevParams P, const WUnitSchedule S, const unsigned *user_col, const int *seg_col,
+                                                     const float *fbvec, const float *fbbias, long nrow, const int *pos, float *out) {
+    constexpr int IPW = 64 / LPI;
+    const int lane = threadIdx.x & 63;
+    const int L = lane & (LPI - 1);
+    const long gidx = ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * IPW + lane / LPI;
+    const long stride = (long)gridDim.x * (blockDim.x >> 6) * IPW;
+    const int pitch = P.pitch, k = P.k;
+    const bool ub = P.no_user_bias == 0;
+    const bool owns = !(LPI * 4 > k && L * 4 >= k);
+    const size_t srow0 = (size_t)P.user_off + S.shared_from;
+    for (long r = gidx; r < nrow; r += stride) {
+        const unsigned ur = P.user_off + user_col[r];
+        const float4 p = load_row<LPI>(P.W, ur, pitch, L, k);
+        const float bu = ub ? P.bias[ur] : 0.0f;
+        float4 tmp_fb = f4zero();
+        float tmp_bias = 0.0f;
+        if (FB) {
+            const int q = seg_col[r];
+            if (owns) tmp_fb = *reinterpret_cast<const float4 *>(fbvec + (size_t)q * pitch + (size_t)L * 4);
+            tmp_bias = fbbias[q];
+        }
+        int e0, e1, e2;
+        if (S.rptr) { e0 = S.rptr[2 * r]; e1 = S.rptr[2 * r + 1]; e2 = S.rptr[2 * r + 2]; }
+        else { e0 = (int)r * S.estride; e1 = e0 + S.estride - 1; e2 = e1 + 1; }
+        const float ua = S.uval ? S.uval[r] : 1.0f;
+        int u0 = 0, um = 0, u1 = 0;
+        if (S.uptr) { u0 = S.uptr[r]; um = u0 + S.upos[r]; u1 = S.uptr[r + 1]; }
+        int c0 = 0, c1 = 0;
+        if (S.iptr) { c0 = S.iptr[r]; c1 = S.iptr[r + 1]; }
+        // ---- pred: k_wunit_walk's statements
+        double bs = 0.0;
+        for (int j = e0; j < e1; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.g_bias[e.idx]); }
+        if (ub) {
+            for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * P.bias[srow0 + e.idx]); }
+            bs += (double)(ua * bu);
+            for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * P.bias[srow0 + e.idx]); }
+            bs += (double)(FB ? tmp_bias : 0.0f);
+        }
+        bs += 0.0;
+        for (int j = e1, c = c0; j < e2; j++) {
+            const WinEnt e = S.ent[j];
+            bs += (double)(e.val * P.bias[P.item_off + e.idx]);
+            for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
+        }
+        double sum = (double)P.base_score + bs;
+        float4 tu = FB ? tmp_fb : f4zero();
+        for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+        axpy4(tu, p, ua);
+        for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+        float4 ti = f4zero();
+        for (int j = e1, c = c0; j < e2; j++) {
+            const WinEnt e = S.ent[j];
+            axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+            for (; c < c1 && S.ient[c].pad == j; c++) {
+                const WinEnt ch = S.ient[c];
+                axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+            }
+        }
+        sum += (double)group_dot<LPI>(tu, ti, L, k);
+        if (L == 0) out[pos ? (long)pos[r] : r] = map_active((float)sum, P.active_type);
+    }
+}
+void launch_wunit_score_columns(const WUnitSchedule &S, unsigned *user_col, int *seg_col, hipStream_t st) {
+    if (S.nunits <= 0) return;
+    const long blocks = (S.nunits * 64 + 255) / 256;
+    hipLaunchKernelGGL(k_wunit_score_columns, dim3((unsigned)blocks), dim3(256), 0, st, S, user_col, seg_col);
+}
+void launch_wunit_score_prepare(const DevParams &P, const WUnitSchedule &S, long nseg, float *fbvec, float *fbbias, hipStream_t st) {
+    if (nseg <= 0) return;
+    const int lpi = lanes_per_instance(P.k);
+    const long per_block = 4L * (64 / lpi);
+    const long grid = (nseg + per_block - 1) / per_block;
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score_prepare<LPI>), dim3((unsigned)grid), dim3(256), 0, st, P, S, nseg, fbvec, fbbias));
+}
+void launch_wunit_score(const DevParams &P, const WUnitSchedule &S, bool feedback, const unsigned *user_col, const int *seg_col, const float *fbvec,
+                        const float *fbbias, long nrow, const int *pos, float *out, hipStream_t st) {
+    if (nrow <= 0) return;
+    const int lpi = lanes_per_instance(P.k);
+    const int grid = grid_for(nrow, lpi, 256 * 8);
+    if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score<LPI, true>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
+    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score<LPI, false>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
+}
+
 bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedback) {
     if (!(P.k == 64 || P.k == 128) || S.rptr != nullptr || S.uval != nullptr || P.reg_method == 2) return false;
     const int ng = S.estride - 1;

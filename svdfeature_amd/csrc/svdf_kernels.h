@@ -71,6 +71,12 @@ void launch_ipc_signal(unsigned *const *pages, int n, int phase, int me, unsigne
 void launch_ipc_wait(unsigned *page, int phase, int n, unsigned seq, unsigned *err, unsigned long long spin_limit, hipStream_t st);
 void launch_ipc_copy(float *dst, const float *src, long n, const unsigned *err, hipStream_t st);
 void launch_window_user_column(const WinUser *urec, int nusers, unsigned *user_out, hipStream_t st);
+// read-only scoring of window data sets.  pos == nullptr: out[r] in regrouped order, else out[pos[r]] (file order)
+void launch_window_predict_pairs(const DevParams &P, const WindowSchedule &S, const unsigned *user_col, long n, const int *pos, float *out, hipStream_t st);
+void launch_wunit_score_columns(const WUnitSchedule &S, unsigned *user_col, int *seg_col, hipStream_t st);   // the user and segment of every regrouped row
+void launch_wunit_score_prepare(const DevParams &P, const WUnitSchedule &S, long nseg, float *fbvec, float *fbbias, hipStream_t st);   // prepare_ufeedback per segment
+void launch_wunit_score(const DevParams &P, const WUnitSchedule &S, bool feedback, const unsigned *user_col, const int *seg_col, const float *fbvec,
+                        const float *fbbias, long nrow, const int *pos, float *out, hipStream_t st);
 void launch_pairs_prepare(long n, const unsigned *pos, const unsigned *neg, unsigned *lo, unsigned *hi, float *vlo, float *vhi, float *ones,
                           unsigned *flag, hipStream_t st);
 void launch_delta_sum(const void *const *srcs, int n, void *dst, long total, int half, hipStream_t st);   // up to 16 buffers
@@ -181,7 +187,8 @@ struct WBuildBuffers {
     void *tmp; size_t tmp_bytes;   // wbuild_tmp_bytes(E)
     unsigned *state;               // [8]
 };
-struct WBuildOut { WinUser *urec; unsigned *item, *item1; float *label, *v0, *v1; int *slot, *slot1, *iptr; };
+struct WBuildOut { WinUser *urec; unsigned *item, *item1; float *label, *v0, *v1; int *slot, *slot1, *iptr;
+                   int *pos; };   // pos: nullptr, or [n] the source position of every regrouped instance (resident data sets: scoring in file order)
 size_t wbuild_tmp_bytes(long m);
 void device_window_build(const WBuildIn &in, const WBuildBuffers &B, const WBuildOut &out, long *nact, long *item_lo, long *item_hi, hipStream_t st);
 // ---- SVDModel::rand_init on the device (svdf_k_init.hip): the j-th matrix element is the j-th accepted attempt of the polar loop

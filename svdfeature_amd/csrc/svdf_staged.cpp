@@ -182,6 +182,8 @@ bool Engine::staged_window_csr(HostCSR &src) {
     // the builders read the chunk through columns / 64-bit pointers; they copy everything they keep
     std::vector<unsigned> cu, c0, c1;
     auto build = [&]() -> Dataset * {
+        staged_building_ = true;   // a transient sequence, dropped after its one pass: its windows keep no file positions
+        struct Done { bool &f; ~Done() { f = false; } } done{staged_building_};
         if (triples || pairs) {
             cu.resize((size_t)n); c0.resize((size_t)n);
             if (pairs) c1.resize((size_t)n);
@@ -288,6 +290,8 @@ bool Engine::staged_window_units() {
             rule = "a block's rows or feedback list are outside the window step (one user entry per row, one user per START .. END span, no id twice)";
     }
     auto build = [&]() -> Dataset * {
+        staged_building_ = true;   // a transient sequence, dropped after its one pass: its windows keep no file positions
+        struct Done { bool &f; ~Done() { f = false; } } done{staged_building_};
         return wseq_from_blocks((long)tag.size(), tag.data(), fbp.data(), fbi.data(), fbv.data(), brp.data(), staged_.row_label.data(), ptr64.data(),
                                 staged_.feat_index.data(), staged_.feat_value.data());
     };

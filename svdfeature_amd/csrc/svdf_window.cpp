@@ -97,8 +97,11 @@ void Engine::window_build(Dataset *ds, long n, const unsigned *user, const unsig
     std::vector<unsigned> w_item((size_t)n), w_item1(pairs ? (size_t)n : 0);
     std::vector<float> w_label(pairs ? 0 : (size_t)n), w_v0(pairs ? (size_t)n : 0), w_v1(pairs ? (size_t)n : 0);
     std::vector<int> w_slot((size_t)n), w_slot1(pairs ? (size_t)n : 0), icur(iptr.begin(), iptr.end() - 1);
+    const bool keep_pos = window_keeps_positions();
+    std::vector<int> w_pos(keep_pos ? (size_t)n : 0);
     for (long r = 0; r < n; r++) {   // file order: a user's instances and an item's slots both keep it
         const int at = ubegin[user[r]]++;
+        if (keep_pos) w_pos[(size_t)at] = (int)r;
         if (!pairs) {
             w_item[(size_t)at] = item[r];
             w_label[(size_t)at] = label[r];
@@ -115,6 +118,8 @@ void Engine::window_build(Dataset *ds, long n, const unsigned *user, const unsig
     ds->item.upload(w_item.data(), (size_t)n, stream_);
     ds->win_slot.upload(w_slot.data(), (size_t)n, stream_);
     ds->win_iptr.upload(iptr.data(), (size_t)NI + 1, stream_);
+    ds->win_has_pos = keep_pos;
+    if (keep_pos) ds->win_pos.upload(w_pos.data(), (size_t)n, stream_); else ds->win_pos.release();
     if (!pairs) {
         ds->label.upload(w_label.data(), (size_t)n, stream_);
         ds->win_item1.release();
@@ -163,11 +168,14 @@ void Engine::window_build_resident(Dataset *ds, long n, const unsigned *d_user, 
     ds->item.reserve((size_t)n); ds->win_slot.reserve((size_t)n); ds->win_iptr.reserve((size_t)NI + 1);
     if (!pairs) { ds->label.reserve((size_t)n); ds->win_item1.release(); }
     else { ds->win_item1.reserve((size_t)n); ds->win_slot1.reserve((size_t)n); ds->ival.reserve((size_t)n); ds->win_ival1.reserve((size_t)n); }
+    ds->win_has_pos = window_keeps_positions();
+    if (ds->win_has_pos) ds->win_pos.reserve((size_t)n); else ds->win_pos.release();
     WBuildIn in{n, pairs ? 1 : 0, d_user, d_item, d_neg, d_label, NU, NI};
     WBuildBuffers B{wb_k0_.p, wb_k1_.p, wb_v0_.p, wb_v1_.p, wb_inst_.p, wb_slot_e_.p, wb_head_.p, wb_mark_.p, wb_run_user_.p, wb_run_start_.p, wb_run_begin_.p,
                     wb_tmp_.p, tb, wb_state_.p};
     WBuildOut out{ds->win_urec.p, ds->item.p, pairs ? ds->win_item1.p : nullptr, pairs ? nullptr : ds->label.p, pairs ? ds->ival.p : nullptr,
-                  pairs ? ds->win_ival1.p : nullptr, ds->win_slot.p, pairs ? ds->win_slot1.p : nullptr, ds->win_iptr.p};
+                  pairs ? ds->win_ival1.p : nullptr, ds->win_slot.p, pairs ? ds->win_slot1.p : nullptr, ds->win_iptr.p,
+                  ds->win_has_pos ? ds->win_pos.p : nullptr};
     long nact = 0, lo = 0, hi = -1;
     try {
         device_window_build(in, B, out, &nact, &lo, &hi, stream_);

@@ -45,6 +45,7 @@ struct WUnitHost {
     std::vector<WinEnt> ient;
     std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), then hot item rows (window_item_sub): WUnitSchedule::hot / hrec; empty: none in the window
     std::vector<WinHotRec> hrec;
+    std::vector<int> pos;              // the source row of every regrouped row (Dataset::win_pos; uploaded for resident data sets only)
     long nhot_user = 0;                // how many of `hot` are shared user rows
     bool has_touched = false;
     long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
@@ -224,6 +225,7 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     int fixed_ng = -2;   // -2 unknown, -1 not fixed
     std::vector<long> src_of_new((size_t)nrow, -1);
     for (long r = 0; r < num_src_row; r++) if (newrow_of_src[(size_t)r] >= 0) src_of_new[(size_t)newrow_of_src[(size_t)r]] = r;
+    H.pos.assign(src_of_new.begin(), src_of_new.end());
     for (long nr = 0; nr < nrow; nr++) {
         const long r = src_of_new[(size_t)nr];
         const int64_t p0 = row_ptr[3 * r], p1 = row_ptr[3 * r + 1], p2 = row_ptr[3 * r + 2], p3 = row_ptr[3 * r + 3];
@@ -443,6 +445,8 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
     if (ds->wu_estride == 0) ds->wu_rptr.upload(rptr.data(), (size_t)2 * nrow + 1, stream_);
     ds->wu_ent.upload(ent.data(), (size_t)nent, stream_);
     ds->wu_fbent.upload(fbent.data(), (size_t)nfbe, stream_);
+    ds->win_has_pos = window_keeps_positions();
+    if (ds->win_has_pos) ds->win_pos.upload(H.pos.data(), (size_t)nrow, stream_); else ds->win_pos.release();
     ds->wu_fbrec.upload(H.fbrec.data(), H.fbrec.size(), stream_);
     ds->wu_ntouched = H.has_touched ? (long)H.touched.size() : -1;
     if (H.has_touched) ds->wu_touched.upload(H.touched.data(), H.touched.size(), stream_);
@@ -875,12 +879,13 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
             wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub, item_sub);
         },
-        [&](long, const WUnitHost &H) {
+        [&](long w, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
             adopt(c.get());
             wunit_adopt(c.get(), H);
             ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
             ds->wchild.push_back(c.release());
+            ds->wfirst.push_back(n * w / W);
         }, ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
@@ -936,12 +941,13 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
             wunit_host_from_blocks(H, inplace, cut[(size_t)w], cut[(size_t)w + 1], extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr,
                                    feat_index, feat_value);
         },
-        [&](long, const WUnitHost &H) {
+        [&](long w, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
             adopt(c.get());
             wunit_adopt(c.get(), H);
             ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
             ds->wchild.push_back(c.release());
+            ds->wfirst.push_back((long)(block_row_ptr[cut[(size_t)w]] - block_row_ptr[0]));
         }, ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = n;
@@ -1014,6 +1020,7 @@ Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned 
         c->win_hot = whot[(size_t)w] != 0;
         ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
         ds->wchild.push_back(c.release());
+        ds->wfirst.push_back(b0);
     }
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
@@ -1072,6 +1079,7 @@ Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *p
         c->win_hot = whot[(size_t)w] != 0;
         ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
         ds->wchild.push_back(c.release());
+        ds->wfirst.push_back(b0);
     }
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
