@@ -333,7 +333,9 @@ int svdf_synchronize(svdf_trainer *t);
  * 29 passes over rank pairs walked as user-run units,
  * 30 staged chunks trained by the window step (amd:step = minibatch / auto on the staged route of a one-GPU handle), 31 staged chunks kept
  * exact under those keys because their rows or the configuration are outside the window step, 32 depth warnings of the DEFAULT step about
- * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only) */
+ * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only),
+ * 33 / 34 user-group (SVD++) windows with shared user entries (amd:shared_user_from) walked by the one-wave-per-unit form that
+ * keeps a segment's shared rows in registers / by the general lane-group kernel */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -364,7 +366,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     device_schedule 1 (device_schedule_min 2^16: smaller staged windows stay on the host), device_rank 1, device_init 1
  *     (device_init_margin_log2 46), device_window 1, device_load 1
  *   the opt-in window step (amd:step = minibatch / auto; N-rank handles)
- *     wunit_fast 2, wunit_inplace 1, wunit_defer_fb 1, window_slots 1, window_groups 0      kernel forms, same bits
+ *     wunit_fast 2 (3: in addition the one-wave-per-unit form for user-group windows with shared user entries), wunit_inplace 1, wunit_defer_fb 1, window_slots 1, window_groups 0      kernel forms, same bits
  *     window_per_target (*) 24, window_per_target_fb (*) 16     updates a shared row / feedback row meets per window on average
  *     window_per_target_shared (*) 12                           ... a shared user row (amd:shared_user_from; profiles/r07_sidefeat_window.md)
  *     window_per_target_child (*) 3                             ... a feature_user / feature_item child row (profiles/r08_sidetable_window.md)
@@ -402,7 +404,19 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
  * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
  * per row, walked exactly), ids >= B are shared attribute rows (any number per row, read as of the window start and moved once per window
- * like item rows).  1 <= B <= num_user; refused with amd:gpus > 1, amd:contrib = bf16 and in svdf_dataset_window_from_csr. */
+ * like item rows).  1 <= B <= num_user; refused with amd:gpus > 1, amd:contrib = bf16 and in svdf_dataset_window_from_csr.
+ * On a user-group (format_type 1, SVD++) trainer every row of a DEFAULT block or START..END span carries the same private id
+ * -- the unit's user -- and any number of shared ids, which may differ from row to row (user-side attributes: region, device class, social
+ * group).  They join tmp_ufactor and calc_bias in entry order on top of the feedback state, and move once per window like item and feedback
+ * rows.  Reached under amd:step = minibatch from svdf_dataset_from_blocks and svdf_dataset_from_buffer_file(.., 1); scored by
+ * svdf_predict_dataset / svdf_eval_dataset.  The window step's accuracy contract has not been measured on such blocks
+ * (profiles/r15_block_shared.md); until it has, `auto` (decision 3) and the staged svdf_update_block route (counter 31, the one stderr line)
+ * keep blocks with shared ids on the exact pass.  Refused there as well: a span whose rows name two private ids; in
+ * svdf_dataset_window_from_blocks a row with several user entries of which one is >= B (a row whose ONLY user entry is >= B is an ordinary
+ * user to that entry point, as without the key); side tables and the ordered sub-step lanes (window_shared_sub, window_item_sub,
+ * window_pair_sub) stay refused with user-group trainers.
+ * Blocks whose rows have one user entry < B train bit for bit as without the key (in the window sequence a row whose only user entry is >= B
+ * has no private id and is refused). */
 int svdf_set_knob(svdf_trainer *t, const char *name, long value);
 
 /* ---- evaluation: RMSEEvaluator of svd_feature_infer.cpp:38-56,243-277 over a resident data set.  Predictions

@@ -283,7 +283,8 @@ Dataset *Engine::dataset_from_rank_buffer_file(const char *path) {
     UserGroupArrays g;
     if (!(device_rank_ && !rank_prefetch_ && !host_only_ && rank_pass_device_general(path, g))) rank_pass(path, g);
     if (auto_known && auto_rank_decision_ == 2 && wunit_config_ok() &&
-        wunit_blocks_ok((long)g.tag.size(), g.tag.data(), g.fb_ptr.data(), g.fb_index.data(), g.block_row_ptr.data(), g.rows.row_ptr.data(), g.rows.index.data())) {
+        wunit_blocks_ok((long)g.tag.size(), g.tag.data(), g.fb_ptr.data(), g.fb_index.data(), g.block_row_ptr.data(), g.rows.row_ptr.data(), g.rows.index.data(), shared_user_for_auto()) &&
+        (!shared_user() || wunit_blocks_one_user_entry((long)g.tag.size(), g.block_row_ptr.data(), g.rows.row_ptr.data()))) {
         flush();
         return wseq_from_blocks((long)g.tag.size(), g.tag.data(), g.fb_ptr.data(), g.fb_index.data(), g.fb_value.data(), g.block_row_ptr.data(),
                                 g.rows.label.data(), g.rows.row_ptr.data(), g.rows.index.data(), g.rows.value.data());

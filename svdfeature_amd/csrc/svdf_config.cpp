@@ -212,6 +212,9 @@ int64_t Engine::counter(int what) const {
     case 30: return n_staged_window_;  // staged chunks trained by the window step
     case 31: return n_staged_exact_;   // staged chunks kept exact because their rows or the configuration are outside the window step
     case 32: return n_staged_guard_;   // guard lines of the DEFAULT step about staged chunks (at most one per handle)
+    // user-group windows with shared user entries (amd:shared_user_from on SVD++ blocks)
+    case 33: return n_wave_shared_;    // windows walked by the one-wave-per-unit form that keeps the segment's shared rows in registers
+    case 34: return n_walk_shared_;    // windows walked by the general lane-group kernel
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -262,7 +265,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "staged_pool")) { check(value == 0 || value == 1, "staged_pool must be 0 or 1"); flush(); staged_pool_mode_ = (int)value; return 0; }
     if (!strcmp(name, "wunit_inplace")) { wunit_inplace_ = value != 0; return 0; }
     if (!strcmp(name, "wunit_defer_fb")) { wunit_defer_fb_ = value != 0; return 0; }
-    if (!strcmp(name, "wunit_fast")) { check(value >= 0 && value <= 2, "wunit_fast must be 0, 1 or 2"); wunit_fast_ = (int)value; return 0; }
+    if (!strcmp(name, "wunit_fast")) { check(value >= 0 && value <= 3, "wunit_fast must be 0, 1, 2 or 3"); wunit_fast_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_child")) { check(value >= 1, "window_per_target_child must be positive"); wseq_per_target_child_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_shared")) { check(value >= 1, "window_per_target_shared must be positive"); wseq_per_target_shared_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_fb")) { check(value >= 1, "window_per_target_fb must be positive"); wseq_per_target_fb_ = (int)value; return 0; }

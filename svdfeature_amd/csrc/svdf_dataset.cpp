@@ -33,7 +33,8 @@ Dataset *Engine::dataset_from_blocks(long num_block, const int *extend_tag, cons
     if (auto_step_active()) {
         auto_building_ = true;
         struct Done { bool &f; ~Done() { f = false; } } done{auto_building_};
-        const bool ok = wunit_config_ok() && wunit_blocks_ok(num_block, extend_tag, fb_ptr, fb_index, block_row_ptr, row_ptr, feat_index);
+        const bool ok = wunit_config_ok() && wunit_blocks_ok(num_block, extend_tag, fb_ptr, fb_index, block_row_ptr, row_ptr, feat_index, shared_user_for_auto()) &&
+                        (!shared_user() || wunit_blocks_one_user_entry(num_block, block_row_ptr, row_ptr));
         auto windows = [&]() { return wseq_from_blocks(num_block, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value); };
         // a large pass is judged on a prefix of whole users (like the rating / pair streams above): SVD++ blocks keep ~6 users per level whatever
         // their number, so the first 2 M rows tell -- and 100 M rows are not staged and level-scheduled (2.5 s) only to be dropped for the windows

@@ -319,6 +319,7 @@ struct Dataset {
     DevBuf<int> wu_uptr, wu_upos;  // shared user entries (amd:shared_user_from): per-row ranges into wu_uent and the private entry's position
     DevBuf<WinEnt> wu_uent;
     long wu_nshared = 0;           // > 0: the window has shared user entries; targets [.., + wu_nshared) are user rows B .. num_user - 1
+    bool wu_shared_uniform = false;   // user-group windows: every segment's rows carry one user section of at most 4 shared entries (the wave walk's form)
     DevBuf<int> wu_iptr;           // feature_item children of the window's item entries: per-row ranges into wu_ient
     DevBuf<WinEnt> wu_ient;
     bool wu_ichild = false;        // the window has feature_item children
@@ -690,7 +691,8 @@ class Engine {
     void wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                              bool shared = false, int shared_sub = 0, int item_sub = 0) const;
     void wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                                const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) const;
+                                const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
+                                bool shared = false) const;
     int wseq_build_threads_ = 32;         // knob "wseq_build_threads": host threads building the windows of a one-GPU window sequence (user units)
     void wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
     void wunit_fill_from_blocks(Dataset *ds, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
@@ -704,7 +706,7 @@ class Engine {
     int wunit_defer_fb_ = 1;              // knob "wunit_defer_fb": feedback-row contributions are formed by k_wunit_sum from the segments' deltas (1) or written as rows by the walk (0: A/B; same bits)
     int wunit_inplace_ = 1;               // knob "wunit_inplace": one-GPU window sequences apply a row's only contribution of a window in place (no slot); 0 = every contribution through a slot (A/B)
     bool wunit_inplace_build_ = false;    // set while wseq_from_csr / _from_blocks build their windows
-    int wunit_fast_ = 2;                  // knob "wunit_fast": 0 = the general lane-group kernel for every shape, 1 = + the slot kernel, 2 = + one wave per unit (A/B and tests)
+    int wunit_fast_ = 2;                  // knob "wunit_fast": 0 = the general lane-group kernel for every shape, 1 = + the slot kernel, 2 = + one wave per unit, 3 = + its form for user-group windows with shared user entries (A/B and tests)
     int wseq_per_target_fb_ = 16;         // knob "window_per_target_fb": the same for feedback rows (instance-sized updates pushed by whole blocks)
     int wseq_per_target_child_ = 3;       // knob "window_per_target_child": the same for side-table children (calibrated on the
                                           // variant of profiles/r08_sidetable_window.md, 3 seeds at 2 M rows: 12 -> |dRMSE| 2.2e-4, 6 -> 1.1e-4, 4 -> 8.8e-5, 3 -> 5.7e-5)
@@ -805,6 +807,7 @@ class Engine {
     std::vector<StagedBlk> staged_blks_w_;               // user-group trainers: the staged blocks as handed over (wseq_from_blocks cuts windows in blocks)
     int staged_auto_decision_ = 0;                       // amd:step = auto: 0 not taken yet, else auto_last_.decided of the chunk it was taken on
     int64_t n_staged_window_ = 0, n_staged_exact_ = 0, n_staged_guard_ = 0;
+    int64_t n_wave_shared_ = 0, n_walk_shared_ = 0;      // user-group windows with shared user entries: walked by the wave form / by the general kernel (counters 33 / 34)
     int64_t ns_staged_build_ = 0;                        // host time of the per-chunk pre-check + window build (part of ns_flush_; SVDF_PROFILE prints it)
     int64_t ns_wseq_host_ = 0, ns_wseq_adopt_ = 0;       // user-unit window sequences (wseq_build_windows): wall time of the host regrouping / of the windows' allocations + uploads + synchronisations
     std::string staged_auto_rule_;                       // amd:step = auto, decision 3: the rule that keeps the chunks exact

@@ -47,7 +47,11 @@ void validate_block_pointers(long num_block, const int64_t *fb_ptr, const int64_
 // block / START..END span, no id twice in a row's global or item entries, no feedback id twice in a block.  Pointers must be valid.
 bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index, unsigned shared_from = 0xFFFFFFFFu);
 bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const int64_t *block_row_ptr,
-                     const int64_t *row_ptr, const unsigned *feat_index);
+                     const int64_t *row_ptr, const unsigned *feat_index, unsigned shared_from = 0xFFFFFFFFu);
+// every row of the blocks has exactly one user entry (no shared user ids).  `auto` and the staged route take the window step on user-group blocks
+// only then: rows with shared ids are trained by it from resident data sets under amd:step = minibatch alone, until its
+// accuracy contract has been measured on such data
+bool wunit_blocks_one_user_entry(long num_block, const int64_t *block_row_ptr, const int64_t *row_ptr);
 
 // Instances of one batch commute: sorting a batch by a key changes no bit of the result (svdf_sched.cpp)
 void sort_batches(Schedule &sched, const unsigned *key);

@@ -755,7 +755,22 @@ __device__ __forceinline__ WaveRowBlock wave_row_block(const DevParams &P, const
 // compiled without the per-row switches.  Vector-memory instructions are the scarce resource of a wave here (at most 64 in flight, and all
 // ~1 500 waves of a window run their phases at the same time): bias words come with the 64-entry blocks (one load per block instead of
 // one per row), bias contributions leave as one store per group, and what is fetched ahead are row requests only.
-template <int NR, int PFW, bool BF16, bool FAST>
+// SH (amd:shared_user_from on user-group blocks): every row of a segment carries the same user section -- the private entry at
+// position `upos` among ns <= 4 shared entries (ids >= B: attributes of the user) -- which the builder has verified for the whole window
+// (WUnitHost::shared_uniform).  The section's rows, bias words and values are loaded once per segment (nothing writes them inside a
+// window; NR registers per row and lane; the scalars one entry per lane), per data row only the entries' contribution slots are fetched, with the row's record block.  The statements
+// are k_wunit_walk's: bias sum and tmp_u in entry order around the private row, one contribution per shared entry.  SH = false compiles to the code
+// as it was.
+constexpr int WAVE_SH = 4;
+struct WaveShBlock { int s0, s1, s2, s3; };   // a 64-record block's contribution slots of the shared entries, one row per lane
+__device__ __forceinline__ WaveShBlock wave_sh_block(const WUnitSchedule &S, int ubase, int ns, int first, int row_last, int lane) {
+    const WinEnt *u = S.uent + ubase + min(first + lane, row_last) * ns;
+    WaveShBlock x;
+    x.s0 = 0 < ns ? u[0].slot : 0; x.s1 = 1 < ns ? u[1].slot : 0; x.s2 = 2 < ns ? u[2].slot : 0; x.s3 = 3 < ns ? u[3].slot : 0;
+    return x;
+}
+static_assert(WAVE_SH == 4, "the shared entries of k_wunit_wave are named one by one (arrays of rows would be indexed in loops the compiler unrolls late: scratch)");
+template <int NR, int PFW, bool BF16, bool FAST, bool SH = false>
 __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two waves per SIMD (<= 256 registers) at k <= 128: a window has ~1.5 units per SIMD
     const DevParams P, const WUnitSchedule S) {
     constexpr int FBW = 16;
@@ -782,6 +797,35 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
         const int fb_begin = __builtin_amdgcn_readfirstlane(sv.x), nfb = __builtin_amdgcn_readfirstlane(sv.y);
         const int row_begin = __builtin_amdgcn_readfirstlane(sv.z), nrow = __builtin_amdgcn_readfirstlane(sv.w);
         const int fb_last = max(nfb - 1, 0), row_last = max(nrow - 1, 0);
+        // ---- SH: the segment's user section, once
+        int ns = 0, upos = 0, ubase = 0;
+        ChainRow<NR> sh0 = chain_zero<NR>(), sh1 = sh0, sh2 = sh0, sh3 = sh0;
+        // lane e < ns: entry e's value, model row, bias word, value * bias (calc_bias' term) -- read with pick(., e) where they are used
+        float sh_v = 0.0f, sh_b = 0.0f, sh_vb = 0.0f;
+        unsigned sh_row = 0u;
+        if constexpr (SH) {
+            ubase = __builtin_amdgcn_readfirstlane(S.uptr[row_begin]);
+            ns = __builtin_amdgcn_readfirstlane(S.uptr[row_begin + 1]) - ubase;
+            upos = __builtin_amdgcn_readfirstlane(S.upos[row_begin]);
+            if (ns > 0) {
+                const WinEnt ue = S.uent[ubase + min(lane, ns - 1)];
+                sh_v = ue.val;
+                sh_row = P.user_off + S.shared_from + ue.idx;
+                sh_b = ub ? P.bias[sh_row] : 0.0f;
+                sh_vb = sh_v * sh_b;
+            }
+            if (0 < ns) sh0 = chain_load<NR>(P.W, pick(sh_row, 0), pitch, lane, kio);
+            if (1 < ns) sh1 = chain_load<NR>(P.W, pick(sh_row, 1), pitch, lane, kio);
+            if (2 < ns) sh2 = chain_load<NR>(P.W, pick(sh_row, 2), pitch, lane, kio);
+            if (3 < ns) sh3 = chain_load<NR>(P.W, pick(sh_row, 3), pitch, lane, kio);
+        }
+        // the entries' rows and bias words as wave-uniform scalars, read here with every lane active: the groups' bias stores run lane-masked
+        unsigned shr0 = 0u, shr1 = 0u, shr2 = 0u, shr3 = 0u;
+        float shw0 = 0.0f, shw1 = 0.0f, shw2 = 0.0f, shw3 = 0.0f;
+        if constexpr (SH) {
+            shr0 = pick(sh_row, 0); shr1 = pick(sh_row, 1); shr2 = pick(sh_row, 2); shr3 = pick(sh_row, 3);
+            shw0 = pick(sh_b, 0); shw1 = pick(sh_b, 1); shw2 = pick(sh_b, 2); shw3 = pick(sh_b, 3);
+        }
         // ---- prepare_ufeedback (:523-538) in LINEAR layout: batches of 16 rows, accumulated in list order, the next batch requested
         ChainRow<NR> tl = chain_zero<NR>();
         float norm = 0.0f, tmp_bias = 0.0f;
@@ -815,6 +859,8 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
         const float old_bias = tmp_bias;
         // ---- the rows: records 64 at a time (one per lane, the next block requested a block ahead), item rows PFW ahead
         WaveRowBlock rb = wave_row_block(P, S, row_begin, 0, row_last, lane), rb_next = wave_row_block(P, S, row_begin, 64, row_last, lane);
+        WaveShBlock shb = {}, shb_next = {};
+        if constexpr (SH) { shb = wave_sh_block(S, ubase, ns, 0, row_last, lane); shb_next = wave_sh_block(S, ubase, ns, 64, row_last, lane); }
         ChainRow<NR> cur[PFW], nxt[PFW];
 #pragma unroll
         for (int c = 0; c < PFW; c++) cur[c] = chain_load<NR>(P.W, P.item_off + pick(rb.e.idx, c), pitch, lane, kio);
@@ -822,11 +868,14 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
             const int off_cur = j0 & 63, off_pre = (j0 + PFW) & 63;
             WaveRowBlock rb_pre = rb;
             if (off_pre == 0) { rb_pre = rb_next; rb_next = wave_row_block(P, S, row_begin, j0 + PFW + 64, row_last, lane); }   // the next group starts a new block
+            WaveShBlock shb_pre = shb;
+            if constexpr (SH) { if (off_pre == 0) { shb_pre = shb_next; shb_next = wave_sh_block(S, ubase, ns, j0 + PFW + 64, row_last, lane); } }
             if (j0 + PFW < nrow) {
 #pragma unroll
                 for (int c = 0; c < PFW; c++) nxt[c] = chain_load<NR>(P.W, P.item_off + pick(rb_pre.e.idx, off_pre + c), pitch, lane, kio);
             }
             float cbv = 0.0f;   // lane off_cur + c: the bias contribution of row j0 + c
+            float cbs0 = 0.0f, cbs1 = 0.0f, cbs2 = 0.0f, cbs3 = 0.0f;   // SH: ... and of its shared entries
 #pragma unroll
             for (int c = 0; c < PFW; c++) {
                 if (j0 + c < nrow) {
@@ -834,12 +883,35 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
                     const float label = pick(rb.label, off_cur + c), iv = pick(rb.e.val, off_cur + c), bi = pick(rb.bi, off_cur + c);
                     const int slot = pick(rb.e.slot, off_cur + c);
                     double bs = 0.0;
+                    if constexpr (SH) {   // calc_bias (:313-353): the user entries in entry order, the private one in its own position
+                        if (ub) {
+#pragma unroll
+                            for (int e = 0; e < WAVE_SH; e++) if (e < upos) bs += (double)pick(sh_vb, e);
+                            bs += (double)(1.0f * bu);
+#pragma unroll
+                            for (int e = 0; e < WAVE_SH; e++) if (e >= upos && e < ns) bs += (double)pick(sh_vb, e);
+                            bs += (double)tmp_bias;
+                        }
+                    } else {
                     if (ub) { bs += (double)(1.0f * bu); bs += (double)tmp_bias; }
+                    }
                     bs += 0.0;
                     bs += (double)(iv * bi);
                     double sum = (double)P.base_score + bs;
                     ChainRow<NR> tu = tmp_fb, ti = chain_zero<NR>();
+                    if constexpr (SH) {   // prepare_tmp (:354-381): tmp_ufactor in entry order on top of tmp_ufeedback
+                        if (0 < upos) chain_axpy(tu, sh0, pick(sh_v, 0));
+                        if (1 < upos) chain_axpy(tu, sh1, pick(sh_v, 1));
+                        if (2 < upos) chain_axpy(tu, sh2, pick(sh_v, 2));
+                        if (3 < upos) chain_axpy(tu, sh3, pick(sh_v, 3));
+                    }
                     chain_axpy(tu, p, 1.0f);
+                    if constexpr (SH) {
+                        if (0 >= upos && 0 < ns) chain_axpy(tu, sh0, pick(sh_v, 0));
+                        if (1 >= upos && 1 < ns) chain_axpy(tu, sh1, pick(sh_v, 1));
+                        if (2 >= upos && 2 < ns) chain_axpy(tu, sh2, pick(sh_v, 2));
+                        if (3 >= upos && 3 < ns) chain_axpy(tu, sh3, pick(sh_v, 3));
+                    }
                     chain_axpy(ti, xq, iv);
                     sum += (double)chain_dot(tu, ti, lane, k);
                     const float pred = FAST ? (float)sum : map_active((float)sum, P.active_type);
@@ -865,6 +937,47 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
                         contrib_chain_store<NR, BF16>(S.contrib, (size_t)slot, pitch, lane, w);
                     }
                     cbv = (lane == off_cur + c) ? nbi - bi : cbv;
+                    if constexpr (SH) {   // shared user rows: update_no_decay + reg_user (:211-249) against the window-start row, k_wunit_walk's statements
+                        auto shared_entry = [&](int e, const ChainRow<NR> &she, float &cbse, int slots) {
+                            const float ss = lr * err * pick(sh_v, e), sb = pick(sh_b, e);
+                            ChainRow<NR> ws = she;
+                            chain_axpy(ws, ti, ss);
+                            if (FAST) chain_scale(ws, dec_u);
+                            else chain_reg(P, ws, get_wd(P.u_rng, pick(sh_row, e) - P.user_off, P.wd_user), false, lane, k);
+#pragma unroll
+                            for (int q = 0; q < NR; q++) ws.r[q] = ws.r[q] - she.r[q];
+                            float cb = 0.0f;
+                            if (ub) { float nb = sb + ss; nb = nb * dec_ub; cb = nb - sb; }
+                            cbse = (lane == off_cur + c) ? cb : cbse;
+                            const int uslot = pick(slots, off_cur + c);
+                            if (uslot < 0) {   // the row's only contribution of this window (a one-row segment): applied here
+                                ChainRow<NR> a;
+#pragma unroll
+                                for (int q = 0; q < NR; q++) a.r[q] = apply_single(she.r[q], ws.r[q], false);
+                                chain_store<NR>(P.W, pick(sh_row, e), pitch, lane, kio, a);
+                            } else {
+                                chain_store<NR>(S.contrib, (size_t)uslot, pitch, lane, -1, ws);
+                            }
+                        };
+                        if constexpr (FAST) {
+                            if (0 < ns) shared_entry(0, sh0, cbs0, shb.s0);
+                            if (1 < ns) shared_entry(1, sh1, cbs1, shb.s1);
+                            if (2 < ns) shared_entry(2, sh2, cbs2, shb.s2);
+                            if (3 < ns) shared_entry(3, sh3, cbs3, shb.s3);
+                        } else {
+                            // the general regulariser (chain_reg: every method, projection included) once per entry would make the group's body too
+                            // large to unroll, and cur[] / nxt[] would then live in scratch: ONE instance, the entry chosen by wave-uniform selects
+#pragma nounroll
+                            for (int e = 0; e < ns; e++) {
+                                ChainRow<NR> she;
+#pragma unroll
+                                for (int q = 0; q < NR; q++) she.r[q] = e == 0 ? sh0.r[q] : e == 1 ? sh1.r[q] : e == 2 ? sh2.r[q] : sh3.r[q];
+                                float cbse = e == 0 ? cbs0 : e == 1 ? cbs1 : e == 2 ? cbs2 : cbs3;
+                                shared_entry(e, she, cbse, e == 0 ? shb.s0 : e == 1 ? shb.s1 : e == 2 ? shb.s2 : shb.s3);
+                                cbs0 = e == 0 ? cbse : cbs0; cbs1 = e == 1 ? cbse : cbs1; cbs2 = e == 2 ? cbse : cbs2; cbs3 = e == 3 ? cbse : cbs3;
+                            }
+                        }
+                    }
                     chain_axpy(tmp_fb, ti, lr2 * err * norm);          // update_svdpp (:512-520)
                     chain_scale(tmp_fb, 1.0f - lr2 * P.wd_ufeedback);
                     if (ub) {
@@ -881,10 +994,21 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
             if (lane >= off_cur && lane < off_cur + PFW && j0 + (lane - off_cur) < nrow) {   // one store for the group
                 if (rb.e.slot < 0) P.bias[P.item_off + rb.e.idx] = apply_single(rb.bi, cbv, false);
                 else S.cbias[rb.e.slot] = cbv;
+                if constexpr (SH) {
+                    auto shared_bias = [&](unsigned row, float b, float cbse, int slot) {
+                        if (slot < 0) { if (ub) P.bias[row] = apply_single(b, cbse, false); }
+                        else S.cbias[slot] = cbse;
+                    };
+                    if (0 < ns) shared_bias(shr0, shw0, cbs0, shb.s0);
+                    if (1 < ns) shared_bias(shr1, shw1, cbs1, shb.s1);
+                    if (2 < ns) shared_bias(shr2, shw2, cbs2, shb.s2);
+                    if (3 < ns) shared_bias(shr3, shw3, cbs3, shb.s3);
+                }
             }
 #pragma unroll
             for (int c = 0; c < PFW; c++) cur[c] = nxt[c];
             rb = rb_pre;
+            if constexpr (SH) shb = shb_pre;
         }
         // ---- update_ufeedback (:539-554) against the window-start rows: contributions (w + d val) - w, linear layout, same pipeline
         if (nfb > 0) {
@@ -954,9 +1078,14 @@ __global__ __launch_bounds__(64, (NR <= 2 ? 2 : 1)) void k_wunit_wave(   // two 
 bool wunit_wave_applies(const DevParams &P, const WUnitSchedule &S, bool feedback) {
     return feedback && S.rptr == nullptr && S.estride == 1 && S.uval == nullptr && P.k % 64 == 0 && P.k <= 256;
 }
-template <int NR, int PFW> static void launch_wunit_wave_nr(const DevParams &P, const WUnitSchedule &S, hipStream_t st) {
+template <int NR, int PFW> static void launch_wunit_wave_nr(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool shared) {
     const bool fast = P.active_type == ACT_LINEAR && P.reg_method == 0 && P.no_user_bias == 0 && P.user_nonnegative == 0 && P.u_rng.n == 0 && P.i_rng.n == 0;
     const dim3 grid((unsigned)S.nunits), block(64);
+    if (shared) {   // segments with one user section each (fp32 contribution rows: shared entries are refused with bfloat16 ones)
+        if (fast) hipLaunchKernelGGL((k_wunit_wave<NR, PFW, false, true, true>), grid, block, 0, st, P, S);
+        else hipLaunchKernelGGL((k_wunit_wave<NR, PFW, false, false, true>), grid, block, 0, st, P, S);
+        return;
+    }
     if (S.contrib_bf16) {
         if (fast) hipLaunchKernelGGL((k_wunit_wave<NR, PFW, true, true>), grid, block, 0, st, P, S);
         else hipLaunchKernelGGL((k_wunit_wave<NR, PFW, true, false>), grid, block, 0, st, P, S);
@@ -965,13 +1094,13 @@ template <int NR, int PFW> static void launch_wunit_wave_nr(const DevParams &P, 
         else hipLaunchKernelGGL((k_wunit_wave<NR, PFW, false, false>), grid, block, 0, st, P, S);
     }
 }
-void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st) {
+void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool shared) {
     if (S.nunits <= 0) return;
     switch (P.k / 64) {
-    case 1: launch_wunit_wave_nr<1, 8>(P, S, st); break;
-    case 2: launch_wunit_wave_nr<2, 8>(P, S, st); break;
-    case 3: launch_wunit_wave_nr<3, 8>(P, S, st); break;
-    default: launch_wunit_wave_nr<4, 8>(P, S, st); break;
+    case 1: launch_wunit_wave_nr<1, 8>(P, S, st, shared); break;
+    case 2: launch_wunit_wave_nr<2, 8>(P, S, st, shared); break;
+    case 3: launch_wunit_wave_nr<3, 8>(P, S, st, shared); break;
+    default: launch_wunit_wave_nr<4, 8>(P, S, st, shared); break;
     }
 }
 

@@ -898,12 +898,19 @@ bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedbac
     const int ng = S.estride - 1;
     return ng == 0 || (ng == 4 && !feedback);
 }
-void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st) {
-    if (S.nunits <= 0) return;
+int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st, bool shared_uniform) {
+    if (S.nunits <= 0) return 0;
+    // user-group windows whose segments carry one user section each (shared_uniform, the builder's flag): the wave form that holds
+    // the section's rows in registers, under the plain wave form's conditions.  Opt-in (fast = 3) until it has been measured against the general walk on
+    // an MI355X (profiles/r15_block_shared.md); fast = 3 is fast = 2 otherwise
+    if (fast >= 3 && S.uptr && shared_uniform && !S.iptr && !S.hot && !S.contrib_bf16 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) {
+        launch_wunit_wave(P, S, st, true);
+        return 1;
+    }
     if (S.uptr || S.iptr || S.hot) fast = 0;   // rows with shared user entries or feature_item children, windows with hot rows (the records of the ordered sub-steps): the general walk
     // fast: 0 = the general lane-group kernel, 1 = the slot kernel where it applies, 2 (default) = in addition one WAVE per unit for user-group
     // windows whose launch does not fill the chip anyway (its time is the longest unit's latency: svdf_k_wave.hip, k_wunit_wave)
-    if (fast >= 2 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) { launch_wunit_wave(P, S, st); return; }
+    if (fast >= 2 && wunit_wave_applies(P, S, feedback) && S.nunits <= 16384) { launch_wunit_wave(P, S, st); return 2; }
     if (fast && wunit_fast_applies(P, S, feedback)) {
         auto go = [&](auto lanes) {
             constexpr int LANES = decltype(lanes)::value;
@@ -918,7 +925,7 @@ void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback
         };
         if (P.k == 64) go(std::integral_constant<int, 8>());
         else go(std::integral_constant<int, 16>());
-        return;
+        return 0;
     }
     const int lpi = lanes_per_instance(P.k);
     const long ipw = 64 / lpi;
@@ -926,6 +933,7 @@ void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback
     if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else if (S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    return 0;
 }
 // dst == nullptr: add the sums to the model in place; else the wire buffer (half: fp16)
 void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int half, hipStream_t st) {

@@ -60,9 +60,10 @@ void launch_delta_addto(const DeltaRanges &R, const void *src, int half, hipStre
 void launch_window_items_local(const WindowSchedule &S, int pitch, int k, long lo, long hi, float *w_item, float *i_bias, hipStream_t st, long nslots = -1);   // nslots: contributions in the window (sparse windows take k_window_items_sparse)
 void launch_ranges_copy(const DeltaRanges &R, float *buf, int set, hipStream_t st);
 // the same step for user units: user-group (SVD++) blocks, rows with global features (svdf_k_wunit.hip)
-void launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st);
+// returns the form that ran: 0 the general or slot kernel, 1 the wave form with the segments' shared user rows in registers, 2 the plain wave form
+int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st, bool shared_uniform = false);
 bool wunit_wave_applies(const DevParams &P, const WUnitSchedule &S, bool feedback);   // svdf_k_wave.hip: one wave per user unit (SVD++ shape)
-void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st);
+void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool shared = false);
 void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st);   // hot shared user rows in ordered sub-steps, between the walk and the in-place sums
 void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st);   // hot item rows (S.hot[S.nhot .. + nitem_hot)) likewise; writes no model row either, so its order against the launch above is free
 void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int half, hipStream_t st);   // dst == nullptr: add to the model in place

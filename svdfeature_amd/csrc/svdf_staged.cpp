@@ -286,8 +286,12 @@ bool Engine::staged_window_units() {
             fbp.push_back((int64_t)fbi.size());
         }
         ptr64.assign(staged_.row_ptr.begin(), staged_.row_ptr.end());
-        if (tag.empty() || !wunit_blocks_ok((long)tag.size(), tag.data(), fbp.data(), fbi.data(), brp.data(), ptr64.data(), staged_.feat_index.data()))
-            rule = "a block's rows or feedback list are outside the window step (one user entry per row, one user per START .. END span, no id twice)";
+        if (tag.empty() || !wunit_blocks_ok((long)tag.size(), tag.data(), fbp.data(), fbi.data(), brp.data(), ptr64.data(), staged_.feat_index.data(), shared_user_for_auto()))
+            rule = shared_user() ? "a block's rows or feedback list are outside the window step (one private user id per row and START .. END span, no id twice)"
+                                 : "a block's rows or feedback list are outside the window step (one user entry per row, one user per START .. END span, no id twice)";
+        else if (shared_user() && !wunit_blocks_one_user_entry((long)tag.size(), brp.data(), ptr64.data()))
+            rule = "rows with shared user ids (amd:shared_user_from) on a user-group trainer keep the exact pass on the staged route; the window step trains "
+                   "them from resident data sets (svdf_dataset_from_blocks) under amd:step = minibatch";
     }
     auto build = [&]() -> Dataset * {
         staged_building_ = true;   // a transient sequence, dropped after its one pass: its windows keep no file positions

@@ -51,6 +51,7 @@ struct WUnitHost {
     long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
     int fixed_ng = -2;
     bool unit_uval = true, feedback = false;
+    bool shared_uniform = false;       // user-group windows with shared user entries: every segment's rows carry ONE user section (ids, values, private position), at most 4 shared entries
 };
 
 WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
@@ -413,6 +414,19 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     for (size_t j = 0; j < nunit; j++) units[j].first = wsegs[(size_t)units[j].seg_begin];   // the first segment travels with the unit record
     H.nrow = nrow; H.nent = nent; H.nfbe = nfbe; H.fixed_ng = fixed_ng; H.unit_uval = unit_uval;
     H.nshared = NS; H.shared_entries = (long)H.uent.size(); H.item_children = (long)H.ient.size();
+    if (has_shared && feedback) {   // attributes of the USER: the same section on every row of a segment -- the wave walk keeps it in registers (svdf_k_wave.hip)
+        bool same = true;
+        for (size_t q = 0; q < nseg_used && same; q++) {
+            const int r0 = wsegs[q].row_begin, a0 = H.uptr[(size_t)r0], n0 = H.uptr[(size_t)r0 + 1] - a0;
+            same = n0 <= 4;
+            for (int r = r0 + 1; r < r0 + wsegs[q].row_count && same; r++) {
+                const int a = H.uptr[(size_t)r];
+                same = H.uptr[(size_t)r + 1] - a == n0 && H.upos[(size_t)r] == H.upos[(size_t)r0];
+                for (int j = 0; j < n0 && same; j++) same = H.uent[(size_t)(a + j)].idx == H.uent[(size_t)(a0 + j)].idx && H.uent[(size_t)(a + j)].val == H.uent[(size_t)(a0 + j)].val;
+            }
+        }
+        H.shared_uniform = same;
+    }
     for (long nr = 0; nr < nrow; nr++) { const int g = rptr[(size_t)2 * nr + 1] - rptr[(size_t)2 * nr]; H.global_entries += g; H.item_entries += rptr[(size_t)2 * nr + 2] - rptr[(size_t)2 * nr] - g; }
     (void)NU;
 }
@@ -455,6 +469,7 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
     ds->wu_tptr.upload(tptr.data(), tptr.size(), stream_);
     ds->wu_gptr.upload(gptr.data(), gptr.size(), stream_);
     ds->wu_nshared = H.nshared;
+    ds->wu_shared_uniform = H.shared_uniform;
     if (H.nshared > 0) {
         ds->wu_uptr.upload(H.uptr.data(), H.uptr.size(), stream_);
         ds->wu_upos.upload(H.upos.data(), H.upos.size(), stream_);
@@ -582,10 +597,17 @@ void Engine::wunit_fill_from_blocks(Dataset *ds, long b0, long b1, const int *ex
     wunit_host_from_blocks(H, wunit_inplace_build_, b0, b1, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value);
     wunit_adopt(ds, H);
 }
+// shared: the one-GPU window sequence under amd:shared_user_from = B -- a row's user entries are ONE private id < B, the
+// same on every row of a block (or START..END span): the unit's user; and any number of shared ids >= B, which may differ from row to row.
 void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index,
                                     const float *fb_value, const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr,
-                                    const unsigned *feat_index, const float *feat_value) const {
+                                    const unsigned *feat_index, const float *feat_value, bool shared) const {
     const long NU = mp_.num_user;
+    const unsigned B = shared_user_from_;
+    const long r_lo = block_row_ptr[b0], r_hi = block_row_ptr[b1];
+    std::vector<int64_t> priv;   // shared mode: the private entry of every row of the window
+    if (shared) priv.resize((size_t)(r_hi - r_lo));
+    std::vector<unsigned> seen;
     std::vector<HostSeg> segs;
     std::vector<int64_t> seg_rows;
     bool open = false;
@@ -603,11 +625,29 @@ void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1
         }
         HostSeg &h = segs.back();
         for (int64_t r = block_row_ptr[b]; r < block_row_ptr[b + 1]; r++) {
-            check(row_ptr[3 * r + 2] - row_ptr[3 * r + 1] == 1, "window data sets: every row needs exactly one user entry");
-            const unsigned u = feat_index[row_ptr[3 * r + 1]];
+            const int64_t p1 = row_ptr[3 * r + 1], p2 = row_ptr[3 * r + 2];
+            int64_t pv = p1;
+            if (priv.empty()) {
+                check(p2 - p1 == 1, "window data sets: every row needs exactly one user entry");
+            } else {
+                pv = -1;
+                seen.clear();
+                for (int64_t j = p1; j < p2; j++) {
+                    const unsigned x = feat_index[j];
+                    if (x >= (unsigned)NU) fail("user feature index exceed bound");
+                    if (x < B) { check(pv < 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has two"); pv = j; continue; }
+                    for (unsigned y : seen) if (y == x) fail("window data sets: a shared user id listed twice in one row");
+                    seen.push_back(x);
+                    check(!contrib_bf16_, "window data sets: shared user entries (amd:shared_user_from) need amd:contrib = fp32");
+                }
+                check(pv >= 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has none");
+                priv[(size_t)(r - r_lo)] = pv;
+            }
+            const unsigned u = feat_index[pv];
             if (u >= (unsigned)NU) fail("user feature index exceed bound");
             if (!h.has_user) { h.user = u; h.has_user = true; }
-            check(h.user == u, "window data sets: the rows of one block (or START..END span) must belong to one user");
+            check(h.user == u, priv.empty() ? "window data sets: the rows of one block (or START..END span) must belong to one user"
+                                            : "window data sets: the rows of one block (or START..END span) must belong to one user (one private id < amd:shared_user_from)");
             seg_rows.push_back(r);
             h.row_count++;
         }
@@ -620,12 +660,12 @@ void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1
         if (tag == TAG_DEFAULT || tag == TAG_END) open = false;
     }
     check(!open, "window data sets: a window must not end inside a START..END span");
-    const long r_lo = block_row_ptr[b0], r_hi = block_row_ptr[b1];
     // source row ids relative to the window's first row
     for (auto &r : seg_rows) r -= r_lo;
     std::vector<int64_t> ptr((size_t)3 * (r_hi - r_lo) + 1);
     for (size_t j = 0; j < ptr.size(); j++) ptr[j] = row_ptr[3 * r_lo + (long)j];
-    wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, false, r_hi - r_lo, row_label + r_lo, ptr.data(), feat_index, feat_value, fb_index, fb_value);
+    wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, false, r_hi - r_lo, row_label + r_lo, ptr.data(), feat_index, feat_value, fb_index, fb_value,
+                     priv.empty() ? nullptr : priv.data());
 }
 
 Dataset *Engine::dataset_window_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
@@ -648,6 +688,12 @@ Dataset *Engine::dataset_window_from_blocks(long num_block, const int *extend_ta
     check(!multi_ || in_multi_scope(), "window data sets are per rank; an amd:gpus handle builds them itself from svdf_dataset_from_blocks");
     validate_block_pointers(num_block, fb_ptr, block_row_ptr);
     validate_csr_pointers((long)(block_row_ptr[num_block] - block_row_ptr[0]), row_ptr + 3 * block_row_ptr[0]);
+    if (shared_user())   // a row with several user entries, one of them shared: the cause is named before the builder's "exactly one user entry"
+        for (int64_t r = block_row_ptr[0]; r < block_row_ptr[num_block]; r++)
+            if (row_ptr[3 * r + 2] - row_ptr[3 * r + 1] != 1)
+                for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++)
+                    check(feat_index[j] < shared_user_from_, "svdf_dataset_window_from_blocks: shared user entries (amd:shared_user_from) are for the one-GPU window "
+                                                             "sequence; the N-rank exchange has no place for user rows");
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get());
     wunit_fill_from_blocks(ds.get(), 0, num_block, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value);
@@ -660,7 +706,9 @@ void Engine::wunit_train(Dataset *ds) {
     d_cbias_.reserve((size_t)std::max<long>(ds->win_slots, 1));
     d_gcontrib_.reserve((size_t)std::max<long>(ds->wu_gslots, 1));
     if (ds->wu_defer_fb) { d_dvec_.reserve((size_t)std::max<long>(ds->wu_nseg, 1) * (size_t)pitch_); d_dbias_.reserve((size_t)std::max<long>(ds->wu_nseg, 1)); }
-    launch_wunit_walk(params(), wunit_view(ds), ds->wu_feedback, wunit_fast_, stream_);
+    const int form = launch_wunit_walk(params(), wunit_view(ds), ds->wu_feedback, wunit_fast_, stream_, ds->wu_shared_uniform);
+    if (form == 1) n_wave_shared_++;                                            // counter 33
+    else if (ds->wu_feedback && ds->wu_nshared > 0) n_walk_shared_++;           // counter 34
     window_trained_ = ds;
 }
 // second half: dst == nullptr adds the per-target sums to the model in place, else they go to the wire buffer
@@ -767,8 +815,13 @@ bool wunit_rows_ok(long r0, long r1, const int64_t *row_ptr, const unsigned *fea
     }
     return true;
 }
+bool wunit_blocks_one_user_entry(long num_block, const int64_t *block_row_ptr, const int64_t *row_ptr) {
+    for (int64_t r = block_row_ptr[0]; r < block_row_ptr[num_block]; r++)
+        if (row_ptr[(size_t)3 * r + 2] - row_ptr[(size_t)3 * r + 1] != 1) return false;
+    return true;
+}
 bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const int64_t *block_row_ptr,
-                     const int64_t *row_ptr, const unsigned *feat_index) {
+                     const int64_t *row_ptr, const unsigned *feat_index, unsigned shared_from) {
     std::vector<unsigned> tmp;
     bool open = false, have_user = false;
     unsigned user = 0;
@@ -778,9 +831,11 @@ bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_pt
         else if (tag == TAG_MIDDLE || tag == TAG_END) { if (!open) return false; }
         else return false;
         if (!no_id_twice(fb_index + fb_ptr[b], fb_ptr[b + 1] - fb_ptr[b], tmp)) return false;
-        if (!wunit_rows_ok((long)block_row_ptr[b], (long)block_row_ptr[b + 1], row_ptr, feat_index)) return false;
+        if (!wunit_rows_ok((long)block_row_ptr[b], (long)block_row_ptr[b + 1], row_ptr, feat_index, shared_from)) return false;
         for (int64_t r = block_row_ptr[b]; r < block_row_ptr[b + 1]; r++) {
-            const unsigned u = feat_index[(size_t)row_ptr[(size_t)3 * r + 1]];
+            int64_t pv = row_ptr[(size_t)3 * r + 1];   // the private entry (wunit_rows_ok: exactly one below shared_from)
+            if (shared_from != 0xFFFFFFFFu) while (feat_index[(size_t)pv] >= shared_from) pv++;
+            const unsigned u = feat_index[(size_t)pv];
             if (have_user && u != user) return false;
             user = u; have_user = true;
         }
@@ -900,10 +955,18 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     validate_csr_pointers((long)(block_row_ptr[num_block] - block_row_ptr[0]), row_ptr + 3 * block_row_ptr[0]);
     const long n = (long)(block_row_ptr[num_block] - block_row_ptr[0]);
     std::vector<long> ci((size_t)mp_.num_item, 0), cg((size_t)mp_.num_global, 0);
+    std::vector<long> cs(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);   // shared user rows
     for (long r = block_row_ptr[0]; r < block_row_ptr[num_block]; r++) {
         for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
         for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) { if (feat_index[j] >= (unsigned)mp_.num_item) fail("item feature index exceed bound"); ci[feat_index[j]]++; }
+        if (!cs.empty())
+            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++)
+                if (feat_index[j] >= shared_user_from_ && feat_index[j] < (unsigned)mp_.num_user) cs[feat_index[j] - shared_user_from_]++;
     }
+    // the shared user rows' term, exactly wseq_from_csr's: mean and most updates met per window at window_per_target_shared under
+    // window_per_target_max, on the item term's scale
+    const double shared_met = cs.empty() ? 0.0 : mean_updates_met(cs, (double)wseq_per_target_shared_ / (double)wseq_per_target_max_) *
+                                                  (double)wseq_per_target_ / (double)wseq_per_target_shared_;
     // a feedback row moves by whole-block steps: a block of n rows pushes about n |value| instance-sized updates into every row of its
     // list at once (update_ufeedback, apex_svd_base.h:539-554) -- the same measure as svdf_multi.cpp's window heuristic
     std::vector<double> mass((size_t)std::max(num_fb_rows(), 1), 0.0);
@@ -922,7 +985,7 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     }
     double m1 = 0.0, m2 = 0.0;
     for (double m : mass) { m1 += m; m2 += m * m; }
-    const long W0 = std::min<long>(std::max<long>(num_block, 1), wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio()), m1 > 0.0 ? m2 / m1 : 0.0}));
+    const long W0 = std::min<long>(std::max<long>(num_block, 1), wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio()), m1 > 0.0 ? m2 / m1 : 0.0, shared_met}));
     // cuts in blocks (the rule of multi_gpu.block_window_bounds and svdf_multi.cpp): even block positions moved forward to the next
     // position where no START..END span is open
     std::vector<long> cut{0};
@@ -939,7 +1002,7 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     wseq_build_windows((long)cut.size() - 1, wseq_build_threads_,
         [&](long w, WUnitHost &H) {
             wunit_host_from_blocks(H, inplace, cut[(size_t)w], cut[(size_t)w + 1], extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr,
-                                   feat_index, feat_value);
+                                   feat_index, feat_value, shared_user());
         },
         [&](long w, const WUnitHost &H) {
             std::unique_ptr<Dataset> c(new Dataset());
