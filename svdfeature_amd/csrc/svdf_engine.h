@@ -198,6 +198,7 @@ struct RankRow {
 
 // libc rand() as a random-access stream (svdf_randstream.cpp): the generator's last 31 values, oldest first
 struct WUnitHost;   // one window's host-built arrays of the user-unit step (svdf_wunit.cpp)
+struct WseqCounts;  // updates per shared target of a pass, for the window rules (svdf_wunit.cpp)
 struct LibcRand { uint32_t x[31]; char *handle = nullptr; };
 bool libc_rand_capture(LibcRand &s);
 void libc_rand_restore(const LibcRand &s);
@@ -681,9 +682,6 @@ class Engine {
     void side_children_ok(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // svdf_wunit.cpp
     const char *side_children_rule(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;
     bool wunit_config_ok() const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
-    void wunit_build(Dataset *ds, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
-                     const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                     const unsigned *fb_index, const float *fb_value);
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                           const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr, bool children = false, int shared_sub = 0, int item_sub = 0) const;
@@ -694,9 +692,7 @@ class Engine {
                                 const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                                 bool shared = false) const;
     int wseq_build_threads_ = 32;         // knob "wseq_build_threads": host threads building the windows of a one-GPU window sequence (user units)
-    void wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
-    void wunit_fill_from_blocks(Dataset *ds, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                                const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
+    int64_t private_user_entry(int64_t p1, int64_t p2, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // amd:shared_user_from: the one id < B of a row's user entries
     void wunit_train(Dataset *ds);
     void wunit_sum(Dataset *ds, void *dst, int half);
     // one GPU, `amd:step = minibatch` (opt-in; not the reference's semantics): resident data sets become window sequences (kind 8)
@@ -705,7 +701,6 @@ class Engine {
     int fewrow_gslots_ = 1;               // knob "fewrow_gslots": 0 = k_fused for few-row data sets with inline global slots (A/B)
     int wunit_defer_fb_ = 1;              // knob "wunit_defer_fb": feedback-row contributions are formed by k_wunit_sum from the segments' deltas (1) or written as rows by the walk (0: A/B; same bits)
     int wunit_inplace_ = 1;               // knob "wunit_inplace": one-GPU window sequences apply a row's only contribution of a window in place (no slot); 0 = every contribution through a slot (A/B)
-    bool wunit_inplace_build_ = false;    // set while wseq_from_csr / _from_blocks build their windows
     int wunit_fast_ = 2;                  // knob "wunit_fast": 0 = the general lane-group kernel for every shape, 1 = + the slot kernel, 2 = + one wave per unit, 3 = + its form for user-group windows with shared user entries (A/B and tests)
     int wseq_per_target_fb_ = 16;         // knob "window_per_target_fb": the same for feedback rows (instance-sized updates pushed by whole blocks)
     int wseq_per_target_child_ = 3;       // knob "window_per_target_child": the same for side-table children (calibrated on the
@@ -727,6 +722,13 @@ class Engine {
     long wseq_windows_hot(long n, const std::vector<long> &item_count) const;
     long wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const;   // the rule of wseq_windows_hot for any (sub-step, cap): ratings and rank pairs
     void wseq_pair_check(const char *what) const;   // window_pair_sub > 0: what the lane does not cover, refused with its cause
+    // the refusals common to the sub-step knobs (window_shared_sub, window_item_sub, window_pair_sub) when `knob` is on
+    void wseq_sub_check(const char *what, const char *knob, const char *desc, const char *entry, const char *nrank, bool entry_only = false) const;
+    std::vector<long> wseq_item_counts(long n, const unsigned *item, const unsigned *item1) const;
+    Dataset *wseq_from_columns(long n, const unsigned *user, const unsigned *item, const unsigned *item1, const float *label, int sub, long W);   // the body of wseq_from_triples / _pairs
+    double wseq_class_term(const std::vector<long> &cnt, int per) const;
+    void wseq_count_targets(WseqCounts &C, long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index) const;
+    void wseq_adopt_window(Dataset *ds, const WUnitHost &H, long first);
     // ordered sub-steps of `sub` with at most `cap` updates per row and window: what the rows of two classes (means per_plain / per_child) ask for
     long wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const;
     double wseq_max_ratio() const { return (double)wseq_per_target_ / (double)wseq_per_target_max_; }

@@ -96,37 +96,35 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
               "window data sets: a feature_user side table needs amd:shared_user_from (its children are shared user rows, ids >= B)");
         check(!contrib_bf16_, "window data sets: feature_user / feature_item side tables need amd:contrib = fp32");
     }
-    if (wseq_shared_sub_ > 0) {   // ordered sub-steps for hot shared user rows: the one-GPU sequence of random-order rows, fp32 slots
-        check(!contrib_bf16_, "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) needs amd:contrib = fp32");
-        check(!user_group(), "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) is not supported with user-group (SVD++) trainers");
-        check(strcmp(what, "dataset_window_from_csr") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
-              "svdf_dataset_window_from_csr: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) is for the one-GPU window sequence "
-              "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) has no place for user rows");
-    }
-    if (wseq_item_sub_ > 0) {   // ordered sub-steps for hot item rows: the same ground as the user-side lane above
-        check(!contrib_bf16_, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs amd:contrib = fp32");
-        check(!user_group(), "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) is not supported with user-group (SVD++) trainers");
-        check(strcmp(what, "dataset_window_from_csr") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
-              "svdf_dataset_window_from_csr: window_item_sub > 0 (ordered sub-steps for hot item rows) is for the one-GPU window sequence "
-              "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) sums every slot on the wire");
+    // ordered sub-steps for hot shared user rows and for hot item rows (6m): the one-GPU sequence of random-order rows, fp32 slots
+    if (wseq_shared_sub_ > 0)
+        wseq_sub_check(what, "window_shared_sub", "ordered sub-steps for hot shared user rows", "dataset_window_from_csr",
+                       "the N-rank exchange (amd:gpus > 1) has no place for user rows");
+    if (wseq_item_sub_ > 0) {
+        wseq_sub_check(what, "window_item_sub", "ordered sub-steps for hot item rows", "dataset_window_from_csr",
+                       "the N-rank exchange (amd:gpus > 1) sums every slot on the wire");
         check(wunit_inplace_ != 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)");
     }
     check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
-    (void)what;
+}
+// What a sub-step knob that is on refuses, with its cause: bf16 slots, user-group trainers, and the N-rank exchange -- `entry` is the call that step
+// builds its windows through, `nrank` says why it cannot serve the lane.  entry_only: the third refusal is about `entry` alone (the caller refuses
+// amd:gpus > 1 in words of its own); otherwise it covers amd:gpus > 1 as well.
+void Engine::wseq_sub_check(const char *what, const char *knob, const char *desc, const char *entry, const char *nrank, bool entry_only) const {
+    auto refuse = [&](bool ok, const std::string &before, const char *after) {
+        if (!ok) fail(before + knob + " > 0 (" + desc + ")" + after);
+    };
+    refuse(!contrib_bf16_, "window data sets: ", " needs amd:contrib = fp32");
+    refuse(!user_group(), "window data sets: ", " is not supported with user-group (SVD++) trainers");
+    if (strcmp(what, entry) == 0 || !(entry_only || (gpus_ == 1 && !multi_ && !is_peer_)))
+        refuse(false, std::string("svdf_") + entry + ": ", (std::string(" is for the one-GPU window sequence (amd:step = minibatch); ") + nrank).c_str());
 }
 
 // Common builder.  segs: in FILE order; seg_rows: source row ids (rows of a segment in file order).  by_row_order: random-order
 // windows, where the file order of the contributions is the order of the source rows (segments of different users interleave);
 // otherwise (user-group passes) a segment's rows are consecutive in the file and its feedback scatter follows them.
-void Engine::wunit_build(Dataset *ds, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
-                         const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                         const unsigned *fb_index, const float *fb_value) {
-    WUnitHost H;
-    wunit_build_host(H, wunit_inplace_build_, segs_v, nseg, seg_rows, by_row_order, num_src_row, row_label, row_ptr, feat_index, feat_value, fb_index, fb_value);
-    wunit_adopt(ds, H);
-}
 void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order,
                               long num_src_row, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                               const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos, bool children, int shared_sub, int item_sub) const {
@@ -428,7 +426,6 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
         H.shared_uniform = same;
     }
     for (long nr = 0; nr < nrow; nr++) { const int g = rptr[(size_t)2 * nr + 1] - rptr[(size_t)2 * nr]; H.global_entries += g; H.item_entries += rptr[(size_t)2 * nr + 2] - rptr[(size_t)2 * nr] - g; }
-    (void)NU;
 }
 // the uploads and the data set's fields: the calling thread, in window order
 void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
@@ -497,12 +494,23 @@ void Engine::wunit_adopt(Dataset *ds, const WUnitHost &H) {
                             H.item_children * (8 * k + 8 + 8);          // a feature_item child: like an item entry
 }
 
-// ---- one exchange window of rows of a random-order trainer: any number of global and item entries, exactly one user entry
-void Engine::wunit_fill_from_csr(Dataset *ds, long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
-    WUnitHost H;
-    wunit_host_from_csr(H, wunit_inplace_build_, n, row_label, row_ptr, feat_index, feat_value);
-    wunit_adopt(ds, H);
+// A row's private user entry under amd:shared_user_from = B: its user entries [p1, p2) are exactly ONE id < B (returned: its position) and any number
+// of shared ids >= B, none of them twice (seen: scratch); shared entries need fp32 slots.
+int64_t Engine::private_user_entry(int64_t p1, int64_t p2, const unsigned *feat_index, std::vector<unsigned> &seen) const {
+    int64_t pv = -1;
+    seen.clear();
+    for (int64_t j = p1; j < p2; j++) {
+        const unsigned u = feat_index[j];
+        if (u >= (unsigned)mp_.num_user) fail("user feature index exceed bound");
+        if (u < shared_user_from_) { check(pv < 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has two"); pv = j; continue; }
+        for (unsigned x : seen) if (x == u) fail("window data sets: a shared user id listed twice in one row");
+        seen.push_back(u);
+        check(!contrib_bf16_, "window data sets: shared user entries (amd:shared_user_from) need amd:contrib = fp32");
+    }
+    check(pv >= 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has none");
+    return pv;
 }
+// ---- one exchange window of rows of a random-order trainer: any number of global and item entries, exactly one user entry
 // shared: the one-GPU window sequence under amd:shared_user_from = B -- a row's user entries are ONE private id < B (the unit's user) and any
 // number of shared ids >= B (targets like item rows).  Otherwise every row has exactly one user entry.  The sequence also takes loaded
 // feature_user / feature_item tables: every child is a shared target, and no row may reach one target twice.
@@ -525,18 +533,7 @@ void Engine::wunit_host_from_csr(WUnitHost &H, bool inplace, long n, const float
                                              "the N-rank exchange has no place for user rows");
             check(p2 - p1 == 1, "window data sets: every row needs exactly one user entry");
         } else {
-            int64_t pv = -1;
-            seen.clear();
-            for (int64_t j = p1; j < p2; j++) {
-                const unsigned u = feat_index[j];
-                if (u >= (unsigned)NU) fail("user feature index exceed bound");
-                if (u < B) { check(pv < 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has two"); pv = j; continue; }
-                for (unsigned x : seen) if (x == u) fail("window data sets: a shared user id listed twice in one row");
-                seen.push_back(u);
-                check(!contrib_bf16_, "window data sets: shared user entries (amd:shared_user_from) need amd:contrib = fp32");
-            }
-            check(pv >= 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has none");
-            priv[(size_t)r] = pv;
+            priv[(size_t)r] = private_user_entry(p1, p2, feat_index, seen);
         }
         const unsigned u = feat_index[priv.empty() ? p1 : priv[(size_t)r]];
         if (u >= (unsigned)NU) fail("user feature index exceed bound");
@@ -590,20 +587,12 @@ const char *Engine::side_children_rule(const int64_t *p, const unsigned *feat_in
 }
 
 // ---- one exchange window of a user-group pass: blocks [b0, b1), every START closed by its END inside the window
-void Engine::wunit_fill_from_blocks(Dataset *ds, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                                    const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
-                                    const float *feat_value) {
-    WUnitHost H;
-    wunit_host_from_blocks(H, wunit_inplace_build_, b0, b1, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value);
-    wunit_adopt(ds, H);
-}
 // shared: the one-GPU window sequence under amd:shared_user_from = B -- a row's user entries are ONE private id < B, the
 // same on every row of a block (or START..END span): the unit's user; and any number of shared ids >= B, which may differ from row to row.
 void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index,
                                     const float *fb_value, const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr,
                                     const unsigned *feat_index, const float *feat_value, bool shared) const {
     const long NU = mp_.num_user;
-    const unsigned B = shared_user_from_;
     const long r_lo = block_row_ptr[b0], r_hi = block_row_ptr[b1];
     std::vector<int64_t> priv;   // shared mode: the private entry of every row of the window
     if (shared) priv.resize((size_t)(r_hi - r_lo));
@@ -627,22 +616,8 @@ void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1
         for (int64_t r = block_row_ptr[b]; r < block_row_ptr[b + 1]; r++) {
             const int64_t p1 = row_ptr[3 * r + 1], p2 = row_ptr[3 * r + 2];
             int64_t pv = p1;
-            if (priv.empty()) {
-                check(p2 - p1 == 1, "window data sets: every row needs exactly one user entry");
-            } else {
-                pv = -1;
-                seen.clear();
-                for (int64_t j = p1; j < p2; j++) {
-                    const unsigned x = feat_index[j];
-                    if (x >= (unsigned)NU) fail("user feature index exceed bound");
-                    if (x < B) { check(pv < 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has two"); pv = j; continue; }
-                    for (unsigned y : seen) if (y == x) fail("window data sets: a shared user id listed twice in one row");
-                    seen.push_back(x);
-                    check(!contrib_bf16_, "window data sets: shared user entries (amd:shared_user_from) need amd:contrib = fp32");
-                }
-                check(pv >= 0, "window data sets: a row needs exactly one private user entry (id < amd:shared_user_from), this one has none");
-                priv[(size_t)(r - r_lo)] = pv;
-            }
+            if (priv.empty()) check(p2 - p1 == 1, "window data sets: every row needs exactly one user entry");
+            else pv = priv[(size_t)(r - r_lo)] = private_user_entry(p1, p2, feat_index, seen);
             const unsigned u = feat_index[pv];
             if (u >= (unsigned)NU) fail("user feature index exceed bound");
             if (!h.has_user) { h.user = u; h.has_user = true; }
@@ -676,7 +651,9 @@ Dataset *Engine::dataset_window_from_csr(long n, const float *row_label, const i
     validate_csr_pointers(n, row_ptr);
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get());
-    wunit_fill_from_csr(ds.get(), n, row_label, row_ptr, feat_index, feat_value);
+    WUnitHost H;
+    wunit_host_from_csr(H, false, n, row_label, row_ptr, feat_index, feat_value);
+    wunit_adopt(ds.get(), H);
     return ds.release();
 }
 Dataset *Engine::dataset_window_from_blocks(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
@@ -696,7 +673,9 @@ Dataset *Engine::dataset_window_from_blocks(long num_block, const int *extend_ta
                                                              "sequence; the N-rank exchange has no place for user rows");
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get());
-    wunit_fill_from_blocks(ds.get(), 0, num_block, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value);
+    WUnitHost H;
+    wunit_host_from_blocks(H, false, 0, num_block, extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr, feat_index, feat_value);
+    wunit_adopt(ds.get(), H);
     return ds.release();
 }
 
@@ -742,6 +721,11 @@ static double mean_updates_met(const std::vector<long> &cnt, double per_mean_ove
     long mx = 0;
     for (long c : cnt) { s1 += (double)c; s2 += (double)c * (double)c; mx = std::max(mx, c); }
     return std::max(s1 > 0.0 ? s2 / s1 : 0.0, (double)mx * per_mean_over_per_max);
+}
+// the term of a class of rows with a per-target mean of its own (`per`: window_per_target_shared, window_per_target_child) under the common cap
+// (window_per_target_max), expressed on the item term's scale
+double Engine::wseq_class_term(const std::vector<long> &cnt, int per) const {
+    return cnt.empty() ? 0.0 : mean_updates_met(cnt, (double)per / (double)wseq_per_target_max_) * (double)wseq_per_target_ / (double)per;
 }
 
 // The windows of a sequence share nothing but the caller's read-only columns: their host builds run on several threads (a quarter of the
@@ -868,21 +852,27 @@ long Engine::wseq_windows_shared(long n, const std::vector<long> &plain, const s
     return hi;
 }
 
-Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
-    wunit_check_config("dataset_from_csr", true);
-    validate_csr_pointers(n, row_ptr);
-    std::vector<long> ci((size_t)mp_.num_item, 0), cg((size_t)mp_.num_global, 0);
-    std::vector<long> cs(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);   // shared user rows
-    std::vector<unsigned char> ichild(feat_item_.num_row() ? (size_t)mp_.num_item : 0, 0);   // item rows that are a feature_item child somewhere
-    std::vector<unsigned char> uchild(feat_user_.num_row() ? cs.size() : 0, 0);               // shared user rows that are a feature_user child
+// How often a pass updates every shared target, for the window rules of the csr and block sequences: rows [r0, r1) counted into item rows (ci; a
+// feature_item child's row too, marked in ichild), global biases (cg) and shared user rows (cs, by id - amd:shared_user_from; a feature_user child
+// marked in uchild).  The marks are empty without the table.
+struct WseqCounts {
+    std::vector<long> ci, cg, cs;
+    std::vector<unsigned char> ichild, uchild;
+};
+void Engine::wseq_count_targets(WseqCounts &C, long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index) const {
+    std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
+    ci.assign((size_t)mp_.num_item, 0); cg.assign((size_t)mp_.num_global, 0);
+    cs.assign(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);
+    C.ichild.assign(feat_item_.num_row() ? (size_t)mp_.num_item : 0, 0);
+    C.uchild.assign(feat_user_.num_row() ? cs.size() : 0, 0);
     const SideTable &FU = feat_user_, &FI = feat_item_;
-    for (long r = 0; r < n; r++) {
+    for (long r = r0; r < r1; r++) {
         for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
         for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) {
             const unsigned i = feat_index[j];
             if (i >= (unsigned)mp_.num_item) fail("item feature index exceed bound");
             ci[i]++;
-            if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) { ci[FI.index[c]]++; ichild[FI.index[c]] = 1; }
+            if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) { ci[FI.index[c]]++; C.ichild[FI.index[c]] = 1; }
         }
         if (!cs.empty())
             for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++) {
@@ -890,9 +880,27 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
                 if (u >= shared_user_from_ && u < (unsigned)mp_.num_user) cs[u - shared_user_from_]++;
                 if (u < FU.num_row())
                     for (unsigned c = FU.row_ptr[u]; c < FU.row_ptr[u + 1]; c++)
-                        if (FU.index[c] >= shared_user_from_) { cs[FU.index[c] - shared_user_from_]++; uchild[FU.index[c] - shared_user_from_] = 1; }
+                        if (FU.index[c] >= shared_user_from_) { cs[FU.index[c] - shared_user_from_]++; C.uchild[FU.index[c] - shared_user_from_] = 1; }
             }
     }
+}
+// one built window joins its sequence: uploaded, its first source row recorded
+void Engine::wseq_adopt_window(Dataset *ds, const WUnitHost &H, long first) {
+    std::unique_ptr<Dataset> c(new Dataset());
+    adopt(c.get());
+    wunit_adopt(c.get(), H);
+    ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
+    ds->wchild.push_back(c.release());
+    ds->wfirst.push_back(first);
+}
+
+Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
+    wunit_check_config("dataset_from_csr", true);
+    validate_csr_pointers(n, row_ptr);
+    WseqCounts C;
+    wseq_count_targets(C, 0, n, row_ptr, feat_index);
+    std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
+    const std::vector<unsigned char> &ichild = C.ichild, &uchild = C.uchild;   // item rows / shared user rows that are a side-table child somewhere
     // side-table children: a row that is a child anywhere -- a feature_user child among the shared user rows, a feature_item
     // child among the item rows -- is a target of its own kind, with all its updates (as a plain entry too), at window_per_target_child
     std::vector<long> cc, ccu;   // (ccu: the feature_user children alone, for the rule with ordered sub-steps below)
@@ -901,10 +909,7 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
     // shared user rows are shared targets like item rows: the same rule (mean and most updates met per window), with a per-target mean of their
     // own (window_per_target_shared, 12: a bucket row met by 1/64 of all rows is far hotter than the items the 24 was calibrated on, and 24 left
     // |dRMSE| at 1.3e-4 on the SURVEY 8(d2) variant) and the common cap (window_per_target_max).  Expressed on the item term's scale.
-    const double shared_met = cs.empty() ? 0.0 : mean_updates_met(cs, (double)wseq_per_target_shared_ / (double)wseq_per_target_max_) *
-                                                  (double)wseq_per_target_ / (double)wseq_per_target_shared_;
-    const double child_met = cc.empty() ? 0.0 : mean_updates_met(cc, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) *
-                                                 (double)wseq_per_target_ / (double)wseq_per_target_child_;
+    const double shared_met = wseq_class_term(cs, wseq_per_target_shared_), child_met = wseq_class_term(cc, wseq_per_target_child_);
     long W;
     const int shared_sub = shared_user() ? wseq_shared_sub_ : 0;
     const int item_sub = wseq_item_sub_;
@@ -913,10 +918,7 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
         // wseq_windows_shared -- and the other side keeps its own: item rows at window_per_target, shared user rows at window_per_target_shared,
         // either side's children at window_per_target_child.  The global biases keep their term.
         cc.resize(cc.size() - ccu.size());   // (cc: the feature_item children alone from here on)
-        auto child_term = [&](const std::vector<long> &c) {
-            return c.empty() ? 0.0 : mean_updates_met(c, (double)wseq_per_target_child_ / (double)wseq_per_target_max_) * (double)wseq_per_target_ / (double)wseq_per_target_child_;
-        };
-        const double item_term = item_sub > 0 ? 0.0 : std::max(mean_updates_met(ci, wseq_max_ratio()), child_term(cc));
+        const double item_term = item_sub > 0 ? 0.0 : std::max(mean_updates_met(ci, wseq_max_ratio()), wseq_class_term(cc, wseq_per_target_child_));
         // (a user side that stays in the common term keeps the children's term as it was: the mean over the children of BOTH sides)
         const double user_term = shared_sub > 0 ? 0.0 : std::max(shared_met, ccu.empty() ? 0.0 : child_met);
         W = wseq_windows(n, {std::max(item_term, user_term), mean_updates_met(cg, wseq_max_ratio())});
@@ -934,14 +936,7 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
             wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub, item_sub);
         },
-        [&](long w, const WUnitHost &H) {
-            std::unique_ptr<Dataset> c(new Dataset());
-            adopt(c.get());
-            wunit_adopt(c.get(), H);
-            ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-            ds->wchild.push_back(c.release());
-            ds->wfirst.push_back(n * w / W);
-        }, ns_wseq_host_, ns_wseq_adopt_);
+        [&](long w, const WUnitHost &H) { wseq_adopt_window(ds.get(), H, n * w / W); }, ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
     return ds.release();
@@ -954,19 +949,10 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     validate_block_pointers(num_block, fb_ptr, block_row_ptr);
     validate_csr_pointers((long)(block_row_ptr[num_block] - block_row_ptr[0]), row_ptr + 3 * block_row_ptr[0]);
     const long n = (long)(block_row_ptr[num_block] - block_row_ptr[0]);
-    std::vector<long> ci((size_t)mp_.num_item, 0), cg((size_t)mp_.num_global, 0);
-    std::vector<long> cs(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);   // shared user rows
-    for (long r = block_row_ptr[0]; r < block_row_ptr[num_block]; r++) {
-        for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
-        for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) { if (feat_index[j] >= (unsigned)mp_.num_item) fail("item feature index exceed bound"); ci[feat_index[j]]++; }
-        if (!cs.empty())
-            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++)
-                if (feat_index[j] >= shared_user_from_ && feat_index[j] < (unsigned)mp_.num_user) cs[feat_index[j] - shared_user_from_]++;
-    }
-    // the shared user rows' term, exactly wseq_from_csr's: mean and most updates met per window at window_per_target_shared under
-    // window_per_target_max, on the item term's scale
-    const double shared_met = cs.empty() ? 0.0 : mean_updates_met(cs, (double)wseq_per_target_shared_ / (double)wseq_per_target_max_) *
-                                                  (double)wseq_per_target_ / (double)wseq_per_target_shared_;
+    WseqCounts C;   // (user-group trainers load no side tables: no children; cs: the shared user rows of DESIGN.md section 6p)
+    wseq_count_targets(C, (long)block_row_ptr[0], (long)block_row_ptr[num_block], row_ptr, feat_index);
+    const std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
+    const double shared_met = wseq_class_term(cs, wseq_per_target_shared_);   // the shared user rows' term, exactly wseq_from_csr's
     // a feedback row moves by whole-block steps: a block of n rows pushes about n |value| instance-sized updates into every row of its
     // list at once (update_ufeedback, apex_svd_base.h:539-554) -- the same measure as svdf_multi.cpp's window heuristic
     std::vector<double> mass((size_t)std::max(num_fb_rows(), 1), 0.0);
@@ -1004,14 +990,8 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
             wunit_host_from_blocks(H, inplace, cut[(size_t)w], cut[(size_t)w + 1], extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr,
                                    feat_index, feat_value, shared_user());
         },
-        [&](long w, const WUnitHost &H) {
-            std::unique_ptr<Dataset> c(new Dataset());
-            adopt(c.get());
-            wunit_adopt(c.get(), H);
-            ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-            ds->wchild.push_back(c.release());
-            ds->wfirst.push_back((long)(block_row_ptr[cut[(size_t)w]] - block_row_ptr[0]));
-        }, ns_wseq_host_, ns_wseq_adopt_);
+        [&](long w, const WUnitHost &H) { wseq_adopt_window(ds.get(), H, (long)(block_row_ptr[cut[(size_t)w]] - block_row_ptr[0])); },
+        ns_wseq_host_, ns_wseq_adopt_);
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = n;
     return ds.release();
@@ -1029,57 +1009,63 @@ bool Engine::wseq_hot_ok() const {
 //     10 M-rating Zipf(0.7) stream, tools/substep_sim.py: 500 per window +1.5e-5, 1 000 +2.8e-5, 2 000 +6.0e-5, 4 000 +9.1e-5 against the 1e-4 contract;
 //     on the MI355X at the configs[1] size, 3 data seeds: 1 024 -> max 4.2e-5, 2 048 -> 6.6e-5, 3 072 -> 7.2e-5, profiles/r06_hot_lane_calibration.txt).
 long Engine::wseq_windows_hot(long n, const std::vector<long> &item_count) const { return wseq_windows_sub(n, item_count, wseq_hot_sub_, wseq_hot_max_); }
-// the same rule for any sub-step size and cap; the mean is over ENTRIES (sum_i c_i: n for ratings, 2 n for rank pairs, whose items count both signs)
+// the same rule for any sub-step size and cap; the mean is over ENTRIES (sum_i c_i: n for ratings, 2 n for rank pairs, whose items count both signs):
+// wseq_windows_shared's search over one class of rows at window_per_target
 long Engine::wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const {
     if (n <= 0) return 1;
     if (window_set_) return std::max<long>(1, (n + stage_window_ - 1) / stage_window_);
-    long mx = 0, total = 0;
-    for (long c : item_count) { mx = std::max(mx, c); total += c; }
-    auto met = [&](long W) {
-        double s = 0.0;
-        for (long c : item_count) s += std::min((double)c / (double)W, (double)sub) * (double)c;
-        return s / (double)total;
-    };
-    long lo = std::max<long>(1, (mx + cap - 1) / cap);
-    if (met(lo) <= (double)wseq_per_target_) return lo;
-    long hi = lo;
-    while (met(hi) > (double)wseq_per_target_ && hi < n) hi *= 2;
-    while (lo + 1 < hi) { const long mid = (lo + hi) / 2; if (met(mid) <= (double)wseq_per_target_) hi = mid; else lo = mid; }
-    return hi;
+    return wseq_windows_shared(n, item_count, {}, sub, cap, wseq_per_target_, 0);
 }
 
-Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned *item, const float *label) {
+// how often a pass updates every item: the instances' one (item1 == nullptr) or two item columns
+std::vector<long> Engine::wseq_item_counts(long n, const unsigned *item, const unsigned *item1) const {
     std::vector<long> ci((size_t)mp_.num_item, 0);
-    for (long r = 0; r < n; r++) { if (item[r] >= (unsigned)mp_.num_item) fail("item feature index exceed bound"); ci[item[r]]++; }
-    const bool hot_lane = wseq_hot_ok();
-    const long W = hot_lane ? wseq_windows_hot(n, ci) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    // which windows hold a hot item (more than window_hot_sub slots of one item): one scan with per-item stamps
+    for (long r = 0; r < n; r++) {
+        if (item[r] >= (unsigned)mp_.num_item || (item1 && item1[r] >= (unsigned)mp_.num_item)) fail("item feature index exceed bound");
+        ci[item[r]]++;
+        if (item1) ci[item1[r]]++;
+    }
+    return ci;
+}
+// The window sequence of instances given as columns, cut into W windows of equal length: ratings (item, label) or rank pairs (item = the +1 item,
+// item1 = the -1 item, no label).  sub > 0: the windows that hold an item with more than `sub` slots (both entries of a pair count) are marked for
+// the lane of ordered sub-steps (k_window_apply / k_window_apply_pairs).
+Dataset *Engine::wseq_from_columns(long n, const unsigned *user, const unsigned *item, const unsigned *item1, const float *label, int sub, long W) {
     std::vector<char> whot((size_t)W, 0);
-    if (hot_lane) {
+    if (sub > 0) {   // one scan with per-item stamps
         std::vector<int> stamp((size_t)mp_.num_item, -1), cnt((size_t)mp_.num_item, 0);
         for (long w = 0; w < W; w++) {
             const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            for (long r = b0; r < b1; r++) {
-                const unsigned it = item[r];
-                if (stamp[it] != (int)w) { stamp[it] = (int)w; cnt[it] = 0; }
-                if (++cnt[it] > wseq_hot_sub_) { whot[(size_t)w] = 1; break; }
-            }
+            for (long r = b0; r < b1 && !whot[(size_t)w]; r++)
+                for (int e = 0; e < (item1 ? 2 : 1); e++) {
+                    const unsigned it = e == 0 ? item[r] : item1[r];
+                    if (stamp[it] != (int)w) { stamp[it] = (int)w; cnt[it] = 0; }
+                    if (++cnt[it] > sub) whot[(size_t)w] = 1;
+                }
         }
     }
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
+    if (item1) ds->wseq_pair_sub = sub;   // (a sequence of pairs records its window_pair_sub, 0 included: wseq_train)
     // the columns go to HBM in ONE copy each (large pageable copies run at the PCIe rate, 56 GB/s; window-sized ones at a fifth of it), the
     // windows are regrouped from slices of them (svdf_k_wbuild.hip)
-    DevBuf<unsigned> d_user, d_item;
+    DevBuf<unsigned> d_user, d_item, d_item1;
     DevBuf<float> d_label;
     const bool resident = device_window_ready() && n > 0;
-    if (resident) { need_device("dataset"); d_user.upload(user, (size_t)n, stream_); d_item.upload(item, (size_t)n, stream_); d_label.upload(label, (size_t)n, stream_); }
+    if (resident) {
+        need_device("dataset");
+        d_user.upload(user, (size_t)n, stream_); d_item.upload(item, (size_t)n, stream_);
+        if (label) d_label.upload(label, (size_t)n, stream_);
+        if (item1) d_item1.upload(item1, (size_t)n, stream_);
+    }
     for (long w = 0; w < W; w++) {
         const long b0 = n * w / W, b1 = n * (w + 1) / W;
         std::unique_ptr<Dataset> c(new Dataset());
         adopt(c.get());
-        if (resident && b1 > b0) { window_build_header(c.get(), b1 - b0, false); window_build_resident(c.get(), b1 - b0, d_user.p + b0, d_item.p + b0, d_label.p + b0, nullptr); }
-        else window_build(c.get(), b1 - b0, user + b0, item + b0, label + b0);
+        if (resident && b1 > b0) {
+            window_build_header(c.get(), b1 - b0, item1 != nullptr);
+            window_build_resident(c.get(), b1 - b0, d_user.p + b0, d_item.p + b0, label ? d_label.p + b0 : nullptr, item1 ? d_item1.p + b0 : nullptr);
+        } else window_build(c.get(), b1 - b0, user + b0, item + b0, label ? label + b0 : nullptr, item1 ? item1 + b0 : nullptr);
         c->win_hot = whot[(size_t)w] != 0;
         ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
         ds->wchild.push_back(c.release());
@@ -1088,6 +1074,13 @@ Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned 
     ds->sched.level_ptr = {0, n};
     ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
     return ds.release();
+}
+
+Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned *item, const float *label) {
+    const std::vector<long> ci = wseq_item_counts(n, item, nullptr);
+    const bool hot_lane = wseq_hot_ok();
+    const long W = hot_lane ? wseq_windows_hot(n, ci) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    return wseq_from_columns(n, user, item, nullptr, label, hot_lane ? wseq_hot_sub_ : 0, W);
 }
 
 // rank pairs (BASELINE configs[4]): two signed item entries per instance, two contribution slots per pair.  The window rule counts both
@@ -1095,58 +1088,18 @@ Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned 
 // (profiles/r04_pairs_windows_demo_rate.txt), an order of magnitude more than the rating default kept here.
 // window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs): fp32 slots, random-order trainers, the one-GPU sequence
 void Engine::wseq_pair_check(const char *what) const {
-    check(!contrib_bf16_, "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) needs amd:contrib = fp32");
-    check(!user_group(), "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is not supported with user-group (SVD++) trainers");
-    check(strcmp(what, "dataset_window_from_pairs") != 0,
-          "svdf_dataset_window_from_pairs: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence "
-          "(amd:step = minibatch); the N-rank exchange sums every slot on the wire");
+    wseq_sub_check(what, "window_pair_sub", "ordered sub-steps for hot items of rank pairs", "dataset_window_from_pairs",
+                   "the N-rank exchange sums every slot on the wire", true);
     check(gpus_ == 1 && !multi_ && !is_peer_,
           "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence; amd:gpus > 1 sums every slot on the wire");
 }
 Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg) {
-    std::vector<long> ci((size_t)mp_.num_item, 0);
-    for (long r = 0; r < n; r++) {
-        if (pos[r] >= (unsigned)mp_.num_item || neg[r] >= (unsigned)mp_.num_item) fail("item feature index exceed bound");
-        ci[pos[r]]++; ci[neg[r]]++;
-    }
+    const std::vector<long> ci = wseq_item_counts(n, pos, neg);
     const int psub = wseq_pair_sub_;
     if (psub > 0) wseq_pair_check("dataset_from_pairs");
-    // ordered sub-steps for hot items: the window count of wseq_windows_hot with the pair knobs, and which windows hold an
-    // item with more than window_pair_sub slots (both entries of a pair count)
+    // ordered sub-steps for hot items: the window count of wseq_windows_hot with the pair knobs
     const long W = psub > 0 ? wseq_windows_sub(n, ci, psub, wseq_pair_max_) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    std::vector<char> whot((size_t)W, 0);
-    if (psub > 0) {
-        std::vector<int> stamp((size_t)mp_.num_item, -1), cnt((size_t)mp_.num_item, 0);
-        for (long w = 0; w < W; w++) {
-            const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            for (long r = b0; r < b1 && !whot[(size_t)w]; r++) {
-                for (const unsigned it : {pos[r], neg[r]}) {
-                    if (stamp[it] != (int)w) { stamp[it] = (int)w; cnt[it] = 0; }
-                    if (++cnt[it] > psub) whot[(size_t)w] = 1;
-                }
-            }
-        }
-    }
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
-    ds->wseq_pair_sub = psub;
-    DevBuf<unsigned> d_user, d_pos, d_neg;
-    const bool resident = device_window_ready() && n > 0;
-    if (resident) { need_device("dataset"); d_user.upload(user, (size_t)n, stream_); d_pos.upload(pos, (size_t)n, stream_); d_neg.upload(neg, (size_t)n, stream_); }
-    for (long w = 0; w < W; w++) {
-        const long b0 = n * w / W, b1 = n * (w + 1) / W;
-        std::unique_ptr<Dataset> c(new Dataset());
-        adopt(c.get());
-        if (resident && b1 > b0) { window_build_header(c.get(), b1 - b0, true); window_build_resident(c.get(), b1 - b0, d_user.p + b0, d_pos.p + b0, nullptr, d_neg.p + b0); }
-        else window_build(c.get(), b1 - b0, user + b0, pos + b0, nullptr, neg + b0);
-        c->win_hot = whot[(size_t)w] != 0;
-        ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-        ds->wchild.push_back(c.release());
-        ds->wfirst.push_back(b0);
-    }
-    ds->sched.level_ptr = {0, n};
-    ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
-    return ds.release();
+    return wseq_from_columns(n, user, pos, neg, nullptr, psub, W);
 }
 
 // one pass over a window sequence: per window the users' walks, then the per-target sums added in place (two launches per window)

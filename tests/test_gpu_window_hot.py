@@ -44,7 +44,8 @@ def _oracle(conf, active, u, i, r, windows, sub, passes):
 
 
 @pytest.mark.parametrize("k,active,extra,sub", [(64, 0, (), 16), (128, 0, (), 16), (64, 0, (), 128), (24, 0, (), 16), (40, 0, (("no_user_bias", "1"),), 8),
-                                              (32, 2, (("base_score", "0.5"),), 16), (256, 0, (), 24), (8, 0, (("reg_method", "1"),), 16), (64, 0, (("wd_item", "0.02"), ("wd_user", "0.01")), 40)])
+                                              (32, 2, (("base_score", "0.5"),), 16), (256, 0, (), 24), (8, 0, (("reg_method", "1"),), 16), (64, 0, (("wd_item", "0.02"), ("wd_user", "0.01")), 40),
+                                              (128, 0, (), 200), (256, 0, (), 100)])   # (a sub-step of several rounds of the workgroup: three full ones and one of 8 / of 4)
 def test_hot_items_move_in_ordered_sub_steps_and_equal_the_checker(k, active, extra, sub):
     nu, ni, n, passes = 3000, 150, 60000, 2
     u, i, r = cases.planted_triples(n, nu, ni, seed=k + sub, zipf=True)
