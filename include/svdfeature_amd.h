@@ -335,7 +335,8 @@ int svdf_synchronize(svdf_trainer *t);
  * exact under those keys because their rows or the configuration are outside the window step, 32 depth warnings of the DEFAULT step about
  * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only),
  * 33 / 34 user-group (SVD++) windows with shared user entries (amd:shared_user_from) walked by the one-wave-per-unit form that
- * keeps a segment's shared rows in registers / by the general lane-group kernel */
+ * keeps a segment's shared rows in registers / by the general lane-group kernel,
+ * 35 hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub; the windows count under 34) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -391,6 +392,17 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               data set is built: train_dataset refuses a sequence built with another window_item_sub.  Refused with
  *                                                               amd:contrib = bf16, user-group trainers, amd:gpus > 1 / svdf_dataset_window_from_csr, wunit_inplace = 0.
  *                                                               Calibration: profiles/r11_item_hot.md
+ *     window_block_sub (*) 0, window_block_max (*) 512          the same lane for the shared user rows of USER-GROUP (SVD++) blocks (amd:shared_user_from on a format_type 1 trainer,
+ *                                                               svdf_dataset_from_blocks / svdf_dataset_from_buffer_file(.., 1) under amd:step = minibatch): a shared
+ *                                                               user row with more than window_block_sub (0 .. 4096) slots in a window moves in ordered sub-steps of that many
+ *                                                               (k_wunit_apply_hot, each slot from the span state its walk held: private row and bias, tmp_ufeedback and its
+ *                                                               bias; 0 = off, the default: the rule and bits of 6p) and meets at most window_block_max updates per window;
+ *                                                               window_per_target_shared then bounds the mean of min(updates per window, window_block_sub).  Without effect on
+ *                                                               random-order trainers, without amd:shared_user_from and on blocks without shared ids.  Set before the data
+ *                                                               set is built: train_dataset refuses a sequence built with another window_block_sub.  Refused with
+ *                                                               amd:contrib = bf16, amd:gpus > 1 / svdf_dataset_window_from_blocks, wunit_inplace = 0 once a row is hot.
+ *                                                               Measured on 64 dense buckets (profiles/r16_block_hot.md): 14x the 6p rule at the default cap, and the |dRMSE| <= 1e-4
+ *                                                               contract missed with the knob on (3.5e-3) and off (1.3e-3): the cap is not a calibrated value
  *     window_pair_sub (*) 0, window_pair_max (*) 4096           the same lane for RANK PAIRS (svdf_dataset_from_pairs and pair-shaped staged chunks under amd:step = minibatch /
  *                                                               auto): an item with more than window_pair_sub (0 .. 128) slots in a window -- both signs counted --
  *                                                               moves in ordered sub-steps of that many (k_window_apply_pairs; 0 = off, the default: the rule and bits as
@@ -413,8 +425,9 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  * (profiles/r15_block_shared.md); until it has, `auto` (decision 3) and the staged svdf_update_block route (counter 31, the one stderr line)
  * keep blocks with shared ids on the exact pass.  Refused there as well: a span whose rows name two private ids; in
  * svdf_dataset_window_from_blocks a row with several user entries of which one is >= B (a row whose ONLY user entry is >= B is an ordinary
- * user to that entry point, as without the key); side tables and the ordered sub-step lanes (window_shared_sub, window_item_sub,
- * window_pair_sub) stay refused with user-group trainers.
+ * user to that entry point, as without the key); side tables and the ordered sub-step lanes of the other routes (window_shared_sub,
+ * window_item_sub, window_pair_sub) stay refused with user-group trainers -- hot shared rows of such blocks have a lane of their own, knob
+ * window_block_sub.
  * Blocks whose rows have one user entry < B train bit for bit as without the key (in the window sequence a row whose only user entry is >= B
  * has no private id and is refused). */
 int svdf_set_knob(svdf_trainer *t, const char *name, long value);

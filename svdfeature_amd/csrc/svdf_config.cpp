@@ -215,6 +215,7 @@ int64_t Engine::counter(int what) const {
     // user-group windows with shared user entries (amd:shared_user_from on SVD++ blocks)
     case 33: return n_wave_shared_;    // windows walked by the one-wave-per-unit form that keeps the segment's shared rows in registers
     case 34: return n_walk_shared_;    // windows walked by the general lane-group kernel
+    case 35: return n_block_hot_;      // hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub, section 6q; the windows count under 34)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -273,6 +274,14 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_shared_max")) { check(value >= 1, "window_shared_max must be positive"); wseq_shared_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_item_sub")) { check(value >= 0 && value <= 128, "window_item_sub must be in 0 .. 128"); wseq_item_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_item_max")) { check(value >= 1, "window_item_max must be positive"); wseq_item_max_ = (int)value; return 0; }
+    if (!strcmp(name, "window_block_sub")) {
+        check(value >= 0 && value <= 4096, "window_block_sub must be in 0 .. 4096");
+        check(value == 0 || (gpus_ == 1 && !multi_ && !is_peer_),
+              "window_block_sub > 0 (ordered sub-steps for hot shared user rows of SVD++ blocks) is for the one-GPU window sequence; the N-rank exchange (amd:gpus > 1) has no place for user rows");
+        wseq_block_sub_ = (int)value;
+        return 0;
+    }
+    if (!strcmp(name, "window_block_max")) { check(value >= 1, "window_block_max must be positive"); wseq_block_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_pair_sub")) {
         check(value >= 0 && value <= 128, "window_pair_sub must be in 0 .. 128");
         check(value == 0 || (gpus_ == 1 && !multi_ && !is_peer_),

@@ -31,7 +31,7 @@ namespace svdf {
 // (S.iptr) follow their parent entry in every loop, with the reference's item-side forms for parent value ival and child value v: bias term
 // (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
 // HOT: the window has hot shared user rows or hot item rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the
-// code as it was.
+// code as it was.  FB and HOT together: user-group windows with hot shared user rows (knob window_block_sub).
 template <int LPI, bool FB, bool HOT = false>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     constexpr int IPW = 64 / LPI;
@@ -175,6 +175,10 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                                // the private user's row and bias as they are before this data row's update
                     store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
                     if (L == 0) S.cbias[e.slot] = bu;
+                    if (FB) {   // ... and the span's tmp_ufeedback / tmp_ufeedback_bias likewise, in the record's row of the second plane (pad = 1 + record)
+                        store_contrib<LPI>(S.hfb, 0, (size_t)(e.pad - 1), pitch, L, k, pp.tmp_fb);
+                        if (L == 0) S.hfbb[e.pad - 1] = pp.tmp_bias;
+                    }
                     continue;
                 }
                 const float ss = lr * err * e.val;
@@ -609,7 +613,7 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
 
 // ------------------------------------------------------------------------------------------------- kernel C: hot rows in ordered sub-steps
 // One workgroup per hot row of the window, between the walk and the sums: the hot shared user rows (ITEM = false: S.hot[0 .. nhot); knob
-// window_shared_sub) in one launch, the hot item rows (ITEM = true: S.hot[nhot ..); knob window_item_sub, section 6m) in another.
+// window_shared_sub; on user-group windows knob window_block_sub, section 6q: the FB build) in one launch, the hot item rows (ITEM = true: S.hot[nhot ..); knob window_item_sub, section 6m) in another.
 // The row and its bias live in LDS; its slots are taken in file order, `sub` at a time.  One lane group per slot of a sub-step redoes the data row's
 // update_inner the way k_wunit_walk does, statement for statement, with
 //   * the hot row and its bias as the previous sub-step left them (LDS) -- at the hot entry's own position: in uent for a user row, in ent for a
@@ -622,7 +626,9 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
 // and parks new - current of the hot row (and bias) in LDS.  The parked changes of a sub-step are added in slot order (acc = +0 + c_1 + c_2 ...; every
 // column by one thread) and the row moves by the sum.  The workgroup is sized to the sub-step: min(sub, 256 / LPI) lane groups; a larger sub-step
 // takes several rounds of them (k = 64, sub = 128: 8 rounds of 16), the parked changes joining the sum round by round, in slot order all the same.
-template <int LPI, bool ITEM>
+// FB (ITEM = false only; knob window_block_sub, section 6q): the data rows belong to user-group spans -- tmp_ufactor starts from the span's tmp_ufeedback and
+// calc_bias ends with tmp_ufeedback_bias, both as the walk held them when it reached the data row (the record's row of S.hfb / word of S.hfbb).
+template <int LPI, bool ITEM, bool FB = false>
 __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, const WUnitSchedule S) {
     extern __shared__ __align__(16) float hot_lds[];
     const int pitch = P.pitch, k = P.k, k4 = (k + 3) & ~3;
@@ -652,7 +658,8 @@ __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, cons
         for (int q0 = s0; q0 < s1; q0 += G) {
             const int slot = q0 + g;
             if (slot < s1) {
-                const WinHotRec rc = S.hrec[h.rec + (slot - h.b)];
+                const int rix = h.rec + (slot - h.b);
+                const WinHotRec rc = S.hrec[rix];
                 const int r = rc.row;
                 // where the hot entry sits: hu in uent (user side), he in ent or hc in ient (item side); -1: not there
                 const int hu = ITEM ? -1 : rc.pos, he = (ITEM && rc.pos >= 0) ? rc.pos : -1, hc = (ITEM && rc.pos < 0) ? ~rc.pos : -1;
@@ -669,14 +676,14 @@ __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, cons
                 const float bu = ub ? S.cbias[slot] : 0.0f;
                 const float4 hw = owns ? *reinterpret_cast<const float4 *>(cur + L * 4) : f4zero();
                 const float hb = sc[0];
-                // ---- pred: k_wunit_walk's statements (FB = false), the hot entry's row and bias from LDS
+                // ---- pred: k_wunit_walk's statements, the hot entry's row and bias from LDS
                 double bs = 0.0;
                 for (int j = e0; j < e1; j++) { const WinEnt e = S.ent[j]; bs += (double)(e.val * P.g_bias[e.idx]); }
                 if (ub) {
                     for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == hu ? hb : P.bias[srow0 + e.idx])); }
                     bs += (double)(ua * bu);
                     for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; bs += (double)(e.val * (j == hu ? hb : P.bias[srow0 + e.idx])); }
-                    bs += (double)0.0f;
+                    bs += (double)(FB ? S.hfbb[rix] : 0.0f);
                 }
                 bs += 0.0;
                 for (int j = e1, c = c0; j < e2; j++) {
@@ -685,7 +692,7 @@ __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, cons
                     for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)((c == hc ? hb : P.bias[P.item_off + ch.idx]) * ch.val * e.val); }
                 }
                 double sum = (double)P.base_score + bs;
-                float4 tu = f4zero();
+                float4 tu = FB ? load_row<LPI>(S.hfb, (size_t)rix, pitch, L, k) : f4zero();
                 for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == hu ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
                 axpy4(tu, p, ua);
                 for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, j == hu ? hw : load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
@@ -749,7 +756,7 @@ __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, cons
 }
 
 // the workgroup of a sub-step of `sub` slots: whole waves, min(sub, 256 / lpi) lane groups rounded up; LDS = current row, sum, G parked changes
-template <bool ITEM>
+template <bool ITEM, bool FB = false>
 static void launch_wunit_apply_hot(const DevParams &P, const WUnitSchedule &S, long nrows, int sub, hipStream_t st) {
     if (nrows <= 0 || sub <= 0) return;
     const int lpi = lanes_per_instance(P.k);
@@ -757,9 +764,13 @@ static void launch_wunit_apply_hot(const DevParams &P, const WUnitSchedule &S, l
     const int block = (int)std::min<long>(256, (want + 63) / 64 * 64);
     const int G = block / lpi;
     const size_t lds = ((size_t)(2 + G) * (size_t)P.pitch + (size_t)G + 2) * sizeof(float);
-    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_apply_hot<LPI, ITEM>), dim3((unsigned)nrows), dim3((unsigned)block), lds, st, P, S));
+    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_apply_hot<LPI, ITEM, FB>), dim3((unsigned)nrows), dim3((unsigned)block), lds, st, P, S));
 }
-void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st) { launch_wunit_apply_hot<false>(P, S, S.nhot, S.hot_sub, st); }
+// feedback: the window's rows belong to user-group spans (window_block_sub; the walk left their feedback state in S.hfb / S.hfbb)
+void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool feedback) {
+    if (feedback) launch_wunit_apply_hot<false, true>(P, S, S.nhot, S.hot_sub, st);
+    else launch_wunit_apply_hot<false>(P, S, S.nhot, S.hot_sub, st);
+}
 // nitem_hot: the hot item rows of the window, S.hot[S.nhot .. S.nhot + nitem_hot)
 void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st) { launch_wunit_apply_hot<true>(P, S, nitem_hot, S.item_sub, st); }
 
@@ -930,7 +941,8 @@ int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback,
     const int lpi = lanes_per_instance(P.k);
     const long ipw = 64 / lpi;
     const long waves = (S.nunits + ipw - 1) / ipw;
-    if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    if (feedback && S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    else if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else if (S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     return 0;

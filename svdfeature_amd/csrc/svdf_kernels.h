@@ -64,7 +64,7 @@ void launch_ranges_copy(const DeltaRanges &R, float *buf, int set, hipStream_t s
 int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback, int fast, hipStream_t st, bool shared_uniform = false);
 bool wunit_wave_applies(const DevParams &P, const WUnitSchedule &S, bool feedback);   // svdf_k_wave.hip: one wave per user unit (SVD++ shape)
 void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool shared = false);
-void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st);   // hot shared user rows in ordered sub-steps, between the walk and the in-place sums
+void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool feedback = false);   // hot shared user rows in ordered sub-steps, between the walk and the in-place sums
 void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st);   // hot item rows (S.hot[S.nhot .. + nitem_hot)) likewise; writes no model row either, so its order against the launch above is free
 void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int half, hipStream_t st);   // dst == nullptr: add to the model in place
 // cross-process direct exchange (svdf_ipc.cpp): sequence flags in IPC-mapped device memory

@@ -283,7 +283,8 @@ struct WUnitSchedule {
     // hot shared user rows (window_shared_sub > 0, one-GPU window sequences only): nullptr hot = none in this window.  A hot entry is marked
     // uent.pad = 1: the walk stores in its slot what the change is computed FROM that only the walk knows -- the private user's row and bias as
     // it held them when it reached the data row -- and k_wunit_apply_shared walks the hot rows' slots in sub-steps of hot_sub.  Such a window has
-    // no in-place single applies, so everything else the apply kernel re-reads is still as of the window start.
+    // no in-place single applies, so everything else the apply kernel re-reads is still as of the window start.  (User-group windows, knob
+    // window_block_sub: the mark is 1 + the record's index -- see hfb below.)
     // Hot item rows (window_item_sub > 0; section 6m) follow the user rows in `hot` and take the same record from the walk, in sub-steps of
     // item_sub.  A hot plain item entry is marked ent.pad = 1.  A hot feature_item child cannot be (ient.pad is its parent's position): it
     // carries its slot as -2 - slot instead -- such a window has no slot -1 (no in-place singles), so slot <= -2 says "hot" and names the slot.
@@ -292,6 +293,10 @@ struct WUnitSchedule {
     long nhot;                  // hot shared user rows (hot item rows: hot + nhot, counted by the host)
     int hot_sub;
     int item_sub;               // (in what was the struct's tail padding: the kernel argument keeps its size)
+    // hot shared user rows of USER-GROUP windows (window_block_sub > 0): a hot entry's uent.pad is 1 + the index of its record in
+    // hrec, and the walk stores there, next to the slot's record, the span state the data row's update starts from -- tmp_ufeedback (hfb[index][pitch])
+    // and tmp_ufeedback_bias (hfbb[index]); k_wunit_apply_hot<LPI, false, true> reads them back.  Trainer scratch, sized for the largest window's records.
+    float *hfb, *hfbb;
 };
 
 }  // namespace svdf

@@ -8,8 +8,9 @@ items, k = 128) at a prefix of --blocks users, every row carrying the user plus 
   --attr 0       no attribute: today's SVD++ window step, the ceiling
 Paths (--paths, in the order given, alternating over --reps rounds): exact (the default step), general (window step, knob wunit_fast = 0),
 wave (wunit_fast = 3), step (window step, default knobs: the one a library without the wave form's knob value accepts), auto (amd:step = auto:
-only the decision is recorded).  Per path: windows, ms per pass as the median of the rounds with
-min / max, inst/s, the model checksum, counters 33 / 34, and the RMSE on the users' held-out rows after --contract-passes passes from a
+only the decision is recorded), hot (the ordered sub-steps for hot shared user rows, DESIGN.md section 6q: one path `hot<S>x<M>` per pair of --block-sub S and
+--block-max M, knobs window_block_sub / window_block_max on the default knobs otherwise; a single pair can be named directly, e.g. hot8x512).  Per path: windows, ms per pass as the median of the rounds with
+min / max, inst/s, the model checksum, counters 33 / 34 / 35, and the RMSE on the users' held-out rows after --contract-passes passes from a
 fresh model (the contract |dRMSE| <= 1e-4 is against `exact`).  --lib PATH loads another build of the library (the parent commit's: the only
 route it has for this data is the exact pass).  --per-target-shared sets the knob window_per_target_shared.  One JSON line, appended to --out.
 
@@ -38,6 +39,8 @@ ap.add_argument("--paths", default="exact,general,wave")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--contract-passes", type=int, default=3)
 ap.add_argument("--per-target-shared", type=int, default=0)
+ap.add_argument("--block-sub", default="12", help="window_block_sub values of the `hot` path, comma-separated")
+ap.add_argument("--block-max", default="512", help="window_block_max values of the `hot` path, comma-separated")
 ap.add_argument("--lib", default="")
 ap.add_argument("--label", default="this commit")
 ap.add_argument("--out", default="")
@@ -72,6 +75,11 @@ PATHS = {"exact": ([], []), "general": ([("amd:step", "minibatch")] + key, [("wu
          "step": ([("amd:step", "minibatch")] + key, []), "auto": ([("amd:step", "auto")] + key, [])}
 
 
+def hot_path(name):
+    s, m = name[3:].split("x")
+    return [("amd:step", "minibatch")] + key, [("window_block_sub", int(s)), ("window_block_max", int(m))]
+
+
 def trainer(path):
     extra, knobs = PATHS[path]
     t = sa.Trainer(1, 0)
@@ -87,7 +95,12 @@ def trainer(path):
     return t
 
 
-paths = a.paths.split(",")
+paths = []
+for p in a.paths.split(","):
+    paths += ["hot%sx%s" % (s, m) for s in a.block_sub.split(",") for m in a.block_max.split(",")] if p == "hot" else [p]
+for p in paths:
+    if p.startswith("hot"):
+        PATHS[p] = hot_path(p)
 res = {"library": a.label, "blocks": a.blocks, "rows": n, "k": a.k, "attr": a.attr, "seed": a.seed, "per_target_shared": a.per_target_shared or 12, "paths": {}}
 state = {}
 for p in paths:
@@ -109,6 +122,8 @@ for p in paths:
             out["rmse_refused"] = str(e)[:80]
         out["model_checksum"] = float(np.float64(t.view("W_item")).sum() + np.float64(t.view("W_user")).sum())
         out["counter_33_34"] = [t.counter(33), t.counter(34)]
+        if p.startswith("hot"):
+            out["counter_35"] = t.counter(35)
     state[p] = (t, ds, [])
     res["paths"][p] = out
 for _ in range(a.reps):   # alternating rounds
