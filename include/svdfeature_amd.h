@@ -372,9 +372,21 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     window_per_target_shared (*) 12                           ... a shared user row (amd:shared_user_from; profiles/r07_sidefeat_window.md)
  *     window_per_target_child (*) 3                             ... a feature_user / feature_item child row (profiles/r08_sidetable_window.md)
  *     window_per_target_max (*) 128                             ... and at most (N-rank steps, rank pairs, user units; plain ratings on one GPU with window_hot_sub = 0)
+ *     window_count_actual (*) 1                                 one-GPU sequences of svdf_dataset_from_triples / _from_pairs / _from_csr (amd:step = minibatch / auto, the staged
+ *                                                               chunks of svdf_update_* included): the means and the "at most" values of this table are counted on the
+ *                                                               windows AS CUT (equal file positions), each times the slack 1.5, and the window count is raised until they hold --
+ *                                                               a file sorted by item, one that arrives in bursts, one sorted by a shared user id gets many small windows instead
+ *                                                               of NaN.  Enforced per window: mean over a class's entries of min(updates of the entry's row, sub-step of its lane)
+ *                                                               <= 1.5 x its window_per_target*; no row of the class more than 1.5 x its cap (window_per_target_max, or the lane's
+ *                                                               window_*_max).  The slack: a file in random order sits above the per-pass figures by the Poisson term (mean + 1; the
+ *                                                               maximum by about 3 sigma), and must keep the windows of the calibrations (profiles/r17_window_orders.md).  amd:gpus > 1
+ *                                                               enforces window_per_target_max alone, without slack.  NOT covered: user-group blocks (svdf_dataset_from_blocks):
+ *                                                               window_per_target_fb, window_per_target_shared and window_block_max hold there ON AVERAGE over a pass's windows only.
+ *                                                               amd:window overrides everything.  0 = the per-pass rule alone (A/B); part of the data set's schedule signature
  *     window_hot_sub (*) 128, window_hot_max (*) 2048           one-GPU sequences of plain ratings (round 6): an item with more than window_hot_sub slots in a window
  *                                                               moves in ordered sub-steps of that many (k_window_apply; 0 = off) and meets at most window_hot_max
- *                                                               updates per window -- the hottest item no longer sets the number of windows
+ *                                                               updates per window -- the hottest item no longer sets the number of windows.  Set before the data set is
+ *                                                               built: train_dataset refuses a sequence built with another window_hot_sub
  *     window_shared_sub (*) 0, window_shared_max (*) 512        one-GPU sequences of rows with shared user entries / feature_user children (amd:shared_user_from):
  *                                                               a shared user row (id >= B) with more than window_shared_sub slots in a window moves in ordered sub-steps
  *                                                               of that many (k_wunit_apply_shared; 0 = off, the default: the rule and bits of 6i / 6j) and meets at most
@@ -396,7 +408,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               svdf_dataset_from_blocks / svdf_dataset_from_buffer_file(.., 1) under amd:step = minibatch): a shared
  *                                                               user row with more than window_block_sub (0 .. 4096) slots in a window moves in ordered sub-steps of that many
  *                                                               (k_wunit_apply_hot, each slot from the span state its walk held: private row and bias, tmp_ufeedback and its
- *                                                               bias; 0 = off, the default: the rule and bits of 6p) and meets at most window_block_max updates per window;
+ *                                                               bias; 0 = off, the default: the rule and bits of 6p) and meets window_block_max updates per window on average (see window_count_actual);
  *                                                               window_per_target_shared then bounds the mean of min(updates per window, window_block_sub).  Without effect on
  *                                                               random-order trainers, without amd:shared_user_from and on blocks without shared ids.  Set before the data
  *                                                               set is built: train_dataset refuses a sequence built with another window_block_sub.  Refused with

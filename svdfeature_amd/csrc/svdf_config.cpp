@@ -290,6 +290,7 @@ int Engine::set_knob(const char *name, long value) {
         return 0;
     }
     if (!strcmp(name, "window_pair_max")) { check(value >= 1, "window_pair_max must be positive"); wseq_pair_max_ = (int)value; return 0; }
+    if (!strcmp(name, "window_count_actual")) { check(value == 0 || value == 1, "window_count_actual must be 0 or 1"); wseq_count_actual_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_sub")) { check(value >= 0 && value <= 4096, "window_hot_sub must be in 0 .. 4096"); wseq_hot_sub_ = (int)value; return 0; }
     if (!strcmp(name, "window_hot_max")) { check(value >= 1, "window_hot_max must be positive"); wseq_hot_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }

@@ -693,6 +693,7 @@ uint64_t Engine::schedule_signature() const {
     mix(user_group()); mix(lazy_decay()); mix((uint64_t)mp_.num_factor); mix(use_fused_); mix(use_simple_units_);
     mix((uint64_t)mtype_.extend_type);
     if (shared_user()) mix(0x5u + ((uint64_t)shared_user_from_ << 8));   // amd:shared_user_from: the window layout of user entries
+    if (!wseq_count_actual_) mix(0x77u);   // knob window_count_actual = 0: window sequences cut by the per-pass rule alone
     return h;
 }
 void Engine::disown(Dataset *ds) {

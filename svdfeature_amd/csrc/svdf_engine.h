@@ -332,6 +332,7 @@ struct Dataset {
     int wseq_item_sub = -1;        // the same for window_item_sub
     int wseq_block_sub = -1;       // kind 8 from wseq_from_blocks (else -1): window_block_sub as it took effect when the sequence was built (0 without amd:shared_user_from; train_dataset refuses another value)
     long wu_nhrec = 0;             // records in wu_hrec (user-group windows: the rows of the trainer's second record plane, d_hfb_ / d_hfbb_)
+    int wseq_hot_sub = -1;         // kind 8 from wseq_from_triples (else -1): window_hot_sub as it took effect when the sequence was built (0 without the lane; train_dataset refuses another value)
     int wseq_pair_sub = -1;        // kind 8 from wseq_from_pairs (else -1): window_pair_sub when the sequence was built (train_dataset refuses another value)
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
     std::vector<Dataset *> wchild;
@@ -725,6 +726,10 @@ class Engine {
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)
     int wseq_hot_max_ = 2048;             // knob "window_hot_max": the most updates a hot row may meet per window (how stale the USERS' view of it gets); 3 seeds of Zipf(0.7) at the configs[1] size: 1 024 max |dRMSE| 4.2e-5 / 66 ms per pass, 2 048 6.6e-5 / 55 ms, 3 072 7.2e-5 / 52 ms (profiles/r06_hot_lane_calibration.txt)
     DevBuf<float> d_clabel_;
+    int wseq_count_actual_ = 1;           // knob "window_count_actual": 1 = the window rule is evaluated on the windows as they are cut and W raised until it holds (svdf_wunit.cpp: wseq_actual_columns / _csr); 0 = the per-pass rule alone
+    bool wseq_actual_on() const;
+    long wseq_actual_columns(long W, long n, const unsigned *item, const unsigned *item1, int sub, int cap) const;
+    long wseq_actual_csr(long W, long n, const int64_t *row_ptr, const unsigned *feat_index, const WseqCounts &C0, int shared_sub, int item_sub) const;
     bool wseq_hot_ok() const;             // the configuration has the hot lane (unit ratings, fp32 contribution rows, one GPU)
     long wseq_windows_hot(long n, const std::vector<long> &item_count) const;
     long wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const;   // the rule of wseq_windows_hot for any (sub-step, cap): ratings and rank pairs

@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -38,6 +39,65 @@ struct ScopedNs {   // host-side time accounting (SVDF_PROFILE=1)
 // config keys of SVDTrainParam / SVDModelParam (svdf_config.cpp: one table row per key)
 void config_set_train_param(TrainParam &p, const char *name, const char *val);
 void config_set_model_param(ModelParam &p, const char *name, const char *val);
+
+// The window rule evaluated on the windows AS CUT (svdf_wunit.cpp: wseq_windows_actual).  The per-pass rules bound what a
+// row meets per window on average (c / W); the windows are cut at equal positions n w / W, so on a file sorted by item, or one that arrives in
+// bursts, one window can hold all of a row's updates.  A class of shared rows keeps two quantities on the actual windows: the mean over its
+// entries of min(count of the entry's row in its window, sub) (sub 0: the count) at `target`, and the most updates of one row in one window at
+// `cap`.  target <= 0 / cap <= 0: not checked.
+struct WseqClass {
+    long num_id;     // ids of the class are 0 .. num_id - 1
+    double target;
+    long cap;
+    int sub;
+};
+class WseqCounter {   // one scan: the caller walks the windows in order and adds every entry of the window's rows
+ public:
+    explicit WseqCounter(const std::vector<WseqClass> &classes) {
+        for (const WseqClass &k : classes) { cls_.push_back(Class{k, {}, {}, 0.0, 0, 0}); cls_.back().stamp.assign((size_t)k.num_id, -1); cls_.back().count.assign((size_t)k.num_id, 0); }
+    }
+    void begin_scan() { for (Class &c : cls_) { std::fill(c.stamp.begin(), c.stamp.end(), -1); c.sum = 0.0; c.entries = 0; c.worst = 0; } }
+    void begin_window(long w) { w_ = (int)w; }
+    void add(int k, unsigned id) {
+        Class &c = cls_[(size_t)k];
+        if (c.stamp[id] != w_) { c.stamp[id] = w_; c.count[id] = 0; }
+        const int v = ++c.count[id];
+        c.worst = std::max<long>(c.worst, v);
+        // sum over a row's v entries of min(v, sub) = v min(v, sub): what the v-th entry adds to it
+        c.sum += (c.k.sub == 0 || v <= c.k.sub) ? 2.0 * (double)v - 1.0 : (double)c.k.sub;
+        c.entries++;
+    }
+    // how far the worst class is over its bounds, slack included, as a fraction num / den (<= 1: every bound holds)
+    void excess(double slack, double &num, double &den) const {
+        num = 0.0; den = 1.0;
+        auto take = [&](double a, double b) { if (a / b > num / den) { num = a; den = b; } };
+        for (const Class &c : cls_) {
+            if (c.k.target > 0.0 && c.entries > 0) take(c.sum / (double)c.entries, c.k.target * slack);
+            if (c.k.cap > 0) take((double)c.worst, (double)c.k.cap * slack);
+        }
+    }
+ private:
+    struct Class { WseqClass k; std::vector<int> stamp, count; double sum; long entries, worst; };
+    std::vector<Class> cls_;
+    int w_ = 0;
+};
+// More windows at equal positions until every class holds on the windows [n w / W, n (w + 1) / W): scan(b0, b1, counter) adds the entries of the
+// file rows [b0, b1).  At most `rounds` scans; then W = n (one row per window meets every bound) when last_resort, else the count reached.
+template <typename Scan>
+long wseq_windows_actual(long W, long n, const std::vector<WseqClass> &classes, double slack, int rounds, bool last_resort, Scan scan) {
+    if (n <= 0) return W;
+    WseqCounter C(classes);
+    for (int round = 0; round < rounds; round++) {
+        C.begin_scan();
+        for (long w = 0; w < W; w++) { C.begin_window(w); scan(n * w / W, n * (w + 1) / W, C); }
+        double num, den;
+        C.excess(slack, num, den);
+        if (num <= den) return W;
+        W = std::max<long>(W + 1, (long)std::ceil((double)W * num / den));
+        if (W >= n) return n;
+    }
+    return last_resort ? n : W;
+}
 
 // Pointer arrays handed over by a caller are checked before anything indexes through them (the messages of dataset_from_csr /
 // dataset_from_blocks): counts not negative, pointers starting at >= 0 and non-decreasing, fewer than 2^31 entries.

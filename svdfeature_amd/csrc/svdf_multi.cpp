@@ -422,27 +422,14 @@ long Engine::multi_windows_for(long n, const std::vector<long> &item_count, bool
 // multi_windows_for bounds a row's updates per window on AVERAGE (mx / cap windows), but the windows are cut at equal row positions n w / W:
 // a hot item whose rows are clustered in the file (sorted or bursty input) would still meet far more than the cap inside one window -- the
 // condition under which stale sums diverge (the staged path's next_cut enforces the bound exactly).  Count per window after cutting and
-// take more windows until the bound holds.  cols: the item columns of the rows (one for ratings, two for rank pairs).
+// take more windows until the bound holds: the cap alone, without slack (wseq_windows_actual, svdf_internal.h -- the one-GPU sequences keep
+// their means there as well).  cols: the item columns of the rows (one for ratings, two for rank pairs).
 static long multi_windows_capped(long W, long n, long num_item, long cap, bool fixed, std::initializer_list<const unsigned *> cols) {
     if (fixed || n <= 0 || cap <= 0) return W;
-    std::vector<int> stamp((size_t)num_item), count((size_t)num_item);
-    for (int round = 0; round < 12; round++) {
-        std::fill(stamp.begin(), stamp.end(), -1);
-        long worst = 0;
-        for (long w = 0; w < W; w++) {
-            const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            for (const unsigned *c : cols)
-                for (long r = b0; r < b1; r++) {
-                    const unsigned it = c[r];
-                    if (stamp[it] != (int)w) { stamp[it] = (int)w; count[it] = 0; }
-                    worst = std::max<long>(worst, ++count[it]);
-                }
-        }
-        if (worst <= cap) return W;
-        W = std::max<long>(W + 1, (long)std::ceil((double)W * (double)worst / (double)cap));
-        if (W >= n) return n;
-    }
-    return W;
+    return wseq_windows_actual(W, n, {WseqClass{num_item, 0.0, cap, 0}}, 1.0, 12, false, [&](long b0, long b1, WseqCounter &C) {
+        for (const unsigned *c : cols)
+            for (long r = b0; r < b1; r++) C.add(0, c[r]);
+    });
 }
 
 // ---- resident data sets on the handle: sharded by user, cut into windows at global positions, one child per (rank, window)

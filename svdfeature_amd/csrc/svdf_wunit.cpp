@@ -942,6 +942,7 @@ Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *ro
         if (!window_set_ && item_sub > 0) W = std::max(W, wseq_windows_shared(n, ci, cc, item_sub, wseq_item_max_, wseq_per_target_, wseq_per_target_child_));
     } else
         W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
+    W = wseq_actual_csr(W, n, row_ptr, feat_index, C, shared_sub, item_sub);   // (C: ci / cs of the children are zeroed above, the marks are what it reads)
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     ds->wseq_shared_sub = shared_sub;
@@ -1039,6 +1040,64 @@ long Engine::wseq_windows_sub(long n, const std::vector<long> &item_count, int s
     return wseq_windows_shared(n, item_count, {}, sub, cap, wseq_per_target_, 0);
 }
 
+// The per-pass rules above take a row's c updates as spread evenly over the W windows.  On a file sorted by item, or one that arrives in bursts, they
+// are not: one window can hold all of an item's ratings (window_per_target_max 128 against 450 met, NaN at the sizes of profiles/r17_window_orders.md).
+// Knob window_count_actual (default 1): after the per-pass search the rule's two quantities -- the mean over entries of min(count, sub) at the class's
+// per-target value, the most updates of one row at the class's cap -- are counted on the windows as they are cut, and W is raised until both hold
+// (wseq_windows_actual, svdf_internal.h).  Both are taken times kWseqSlack: on a file in random order the actual mean sits above
+// the per-pass figure by about 1 (the Poisson term of E[c^2] / E[c]) and the actual maximum above mx / W by sampling noise, and the window counts of
+// the calibrations (every one of them on shuffled files) must stay what they are.  amd:window overrides everything, as before.
+static constexpr double kWseqSlack = 1.5;
+static constexpr int kWseqRounds = 40;
+bool Engine::wseq_actual_on() const { return wseq_count_actual_ != 0 && !window_set_; }
+long Engine::wseq_actual_columns(long W, long n, const unsigned *item, const unsigned *item1, int sub, int cap) const {
+    if (!wseq_actual_on()) return W;
+    return wseq_windows_actual(W, n, {WseqClass{(long)mp_.num_item, (double)wseq_per_target_, cap, sub}}, kWseqSlack, kWseqRounds, true,
+                               [&](long b0, long b1, WseqCounter &C) {
+                                   for (long r = b0; r < b1; r++) { C.add(0, item[r]); if (item1) C.add(0, item1[r]); }
+                               });
+}
+// the same for rows (wseq_from_csr): item rows, global biases, shared user rows and the side-table children, each class with the target and the cap
+// the per-pass rule gives it.  Without a lane the children of both sides are one class (wseq_from_csr: cc), with one they follow their side.
+long Engine::wseq_actual_csr(long W, long n, const int64_t *row_ptr, const unsigned *feat_index, const WseqCounts &C0, int shared_sub, int item_sub) const {
+    if (!wseq_actual_on()) return W;
+    const long NI = mp_.num_item, NS = (long)C0.cs.size();
+    const bool lanes = shared_sub > 0 || item_sub > 0;
+    const int icap = item_sub > 0 ? wseq_item_max_ : wseq_per_target_max_, ucap = shared_sub > 0 ? wseq_shared_max_ : wseq_per_target_max_;
+    enum { ITEM = 0, GLOBAL = 1, SHARED = 2, ICHILD = 3, UCHILD = 4 };
+    // (without a lane: UCHILD is unused, the feature_user children count into ICHILD at ids NI + j)
+    const std::vector<WseqClass> K{
+        {NI, (double)wseq_per_target_, icap, item_sub},
+        {(long)mp_.num_global, (double)wseq_per_target_, wseq_per_target_max_, 0},
+        {NS, (double)wseq_per_target_shared_, ucap, shared_sub},
+        {NI + (lanes ? 0 : NS), (double)wseq_per_target_child_, icap, item_sub},
+        {lanes ? NS : 0, (double)wseq_per_target_child_, ucap, shared_sub}};
+    const SideTable &FU = feat_user_, &FI = feat_item_;
+    const unsigned B = shared_user_from_;
+    auto item_entry = [&](WseqCounter &C, unsigned i) { C.add(!C0.ichild.empty() && C0.ichild[i] ? ICHILD : ITEM, i); };
+    auto user_entry = [&](WseqCounter &C, unsigned j) {
+        if (!C0.uchild.empty() && C0.uchild[j]) { if (lanes) C.add(UCHILD, j); else C.add(ICHILD, (unsigned)NI + j); }
+        else C.add(SHARED, j);
+    };
+    return wseq_windows_actual(W, n, K, kWseqSlack, kWseqRounds, true, [&](long b0, long b1, WseqCounter &C) {
+        for (long r = b0; r < b1; r++) {
+            for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) C.add(GLOBAL, feat_index[j]);
+            for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) {
+                const unsigned i = feat_index[j];
+                item_entry(C, i);
+                if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) item_entry(C, FI.index[c]);
+            }
+            if (NS > 0)
+                for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++) {
+                    const unsigned u = feat_index[j];
+                    if (u >= B && u < (unsigned)mp_.num_user) user_entry(C, u - B);
+                    if (u < FU.num_row())
+                        for (unsigned c = FU.row_ptr[u]; c < FU.row_ptr[u + 1]; c++) if (FU.index[c] >= B) user_entry(C, FU.index[c] - B);
+                }
+        }
+    });
+}
+
 // how often a pass updates every item: the instances' one (item1 == nullptr) or two item columns
 std::vector<long> Engine::wseq_item_counts(long n, const unsigned *item, const unsigned *item1) const {
     std::vector<long> ci((size_t)mp_.num_item, 0);
@@ -1101,8 +1160,11 @@ Dataset *Engine::wseq_from_columns(long n, const unsigned *user, const unsigned 
 Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned *item, const float *label) {
     const std::vector<long> ci = wseq_item_counts(n, item, nullptr);
     const bool hot_lane = wseq_hot_ok();
-    const long W = hot_lane ? wseq_windows_hot(n, ci) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    return wseq_from_columns(n, user, item, nullptr, label, hot_lane ? wseq_hot_sub_ : 0, W);
+    long W = hot_lane ? wseq_windows_hot(n, ci) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    W = wseq_actual_columns(W, n, item, nullptr, hot_lane ? wseq_hot_sub_ : 0, hot_lane ? wseq_hot_max_ : wseq_per_target_max_);
+    Dataset *ds = wseq_from_columns(n, user, item, nullptr, label, hot_lane ? wseq_hot_sub_ : 0, W);
+    ds->wseq_hot_sub = hot_lane ? wseq_hot_sub_ : 0;   // (the lane's sub-step as it took effect, 0 without the lane: wseq_train)
+    return ds;
 }
 
 // rank pairs (BASELINE configs[4]): two signed item entries per instance, two contribution slots per pair.  The window rule counts both
@@ -1120,7 +1182,8 @@ Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *p
     const int psub = wseq_pair_sub_;
     if (psub > 0) wseq_pair_check("dataset_from_pairs");
     // ordered sub-steps for hot items: the window count of wseq_windows_hot with the pair knobs
-    const long W = psub > 0 ? wseq_windows_sub(n, ci, psub, wseq_pair_max_) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    long W = psub > 0 ? wseq_windows_sub(n, ci, psub, wseq_pair_max_) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    W = wseq_actual_columns(W, n, pos, neg, psub, psub > 0 ? wseq_pair_max_ : wseq_per_target_max_);
     return wseq_from_columns(n, user, pos, neg, nullptr, psub, W);
 }
 
@@ -1136,6 +1199,9 @@ void Engine::wseq_train(Dataset *ds) {
               "train_dataset: the window sequence was built with another window_pair_sub (ordered sub-steps for hot items of rank pairs); build the data set again after changing the knob");
         if (wseq_pair_sub_ > 0) wseq_pair_check("train_dataset");
     }
+    if (ds->wseq_hot_sub >= 0)   // built by wseq_from_triples: the threshold between cold and hot rows was fixed then (the windows' marks, the window count)
+        check(ds->wseq_hot_sub == (wseq_hot_ok() ? wseq_hot_sub_ : 0),
+              "train_dataset: the window sequence was built with another window_hot_sub (ordered sub-steps for hot items); build the data set again after changing the knob");
     const bool hot_lane = any_hot && (pair_seq || wseq_hot_ok());
     if (any_hot) check(hot_lane, "train_dataset: the window sequence was built with ordered sub-steps for hot items (window_hot_sub); the configuration changed since");
     if (hot_lane) d_clabel_.reserve((size_t)max_slots);

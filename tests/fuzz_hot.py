@@ -51,7 +51,8 @@ def one(rng, case):
             t.set_param("amd:step", "minibatch")
         x.init_model()
         x.init_trainer()
-    for kk, v in (("window_hot_sub", sub), ("window_hot_max", cap), ("window_per_target", int(rng.choice([24, 100000])))):
+    for kk, v in (("window_hot_sub", sub), ("window_hot_max", cap), ("window_per_target", int(rng.choice([24, 100000]))),
+                  ("window_count_actual", 0)):   # (caps down to one update per window, to make every item hot: as a per-pass figure only)
         t.set_knob(kk, v)
     ds = t.dataset_from_triples(u, i, r)
     W = ds.num_batches

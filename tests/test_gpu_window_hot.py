@@ -130,7 +130,10 @@ def test_random_shapes_against_the_checker():
         u, i, r = cases.planted_triples(n, nu, ni, seed=1000 + case, zipf=bool(rng.integers(0, 4)))
         extra = [("no_user_bias", "1")] if rng.integers(0, 5) == 0 else []
         conf = cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k, learning_rate=0.002) + extra
-        t = _trainer(conf, 0, [("amd:step", "minibatch")], [("window_hot_sub", sub), ("window_hot_max", cap), ("window_per_target", 100000)])
+        # (window_count_actual 0: the draws pick caps down to ONE update per window so that every item of a window is hot; held on the windows as
+        # cut, such a cap means one rating per window -- up to 38 000 windows here and no hot item left to check.  tests/test_gpu_window_orders.py
+        # runs the lane under the rule as it is enforced)
+        t = _trainer(conf, 0, [("amd:step", "minibatch")], [("window_hot_sub", sub), ("window_hot_max", cap), ("window_per_target", 100000), ("window_count_actual", 0)])
         ds = t.dataset_from_triples(u, i, r)
         W = ds.num_batches
         for _ in range(passes):
