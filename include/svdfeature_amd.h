@@ -65,7 +65,15 @@ void svdf_destroy(svdf_trainer *t);
  * flush waits for the open user's END -- for at most 4 x stage_window staged rows, then it flushes like the default route; at any flush with
  * a user still open, that user and its continuation keep the exact unit path, which is normal and not counted).  A chunk whose rows or configuration the
  * window step does not cover keeps the exact flush -- never an error; the first one prints one stderr line naming the rule.  `auto` decides
- * on the first chunk of at least device_schedule_min rows and keeps the decision until the next svdf_set_param. */
+ * on the first chunk of at least device_schedule_min rows and keeps the decision until the next svdf_set_param.
+ * WIDTHS of the window step.  num_factor <= 1024: plain ratings and rank pairs -- svdf_dataset_from_triples / _from_pairs under
+ * minibatch / auto, staged chunks of those two shapes, the stand-alone windows svdf_dataset_window_from_triples / _from_pairs with
+ * svdf_window_delta_pack / _apply / _apply_local, svdf_stratum_step and the item-range pieces, amd:gpus handles on such rows, window_hot_sub, and
+ * svdf_predict_dataset / svdf_eval_dataset on all of these (beyond 256 factors a whole wave owns a row, two to four float4 per lane).
+ * num_factor <= 256: everything that takes the user-unit kernels, one lane group per row -- rows with global features or several user / item
+ * entries (svdf_dataset_from_csr, svdf_dataset_window_from_csr), SVD++ blocks, amd:shared_user_from, side tables, window_shared_sub /
+ * window_item_sub / window_block_sub -- and window_pair_sub > 0.  Beyond their width the resident calls refuse with a message; a staged chunk
+ * keeps the exact flush (counter 31) and `auto` keeps the exact levels (decision 3). */
 int svdf_set_param(svdf_trainer *t, const char *name, const char *val);
 /* apex_random::seed (apex-tensor/apex_random.h:42-44) -> srand; process-global like the reference. */
 void svdf_seed(unsigned seed);
@@ -386,7 +394,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     window_hot_sub (*) 128, window_hot_max (*) 2048           one-GPU sequences of plain ratings (round 6): an item with more than window_hot_sub slots in a window
  *                                                               moves in ordered sub-steps of that many (k_window_apply; 0 = off) and meets at most window_hot_max
  *                                                               updates per window -- the hottest item no longer sets the number of windows.  Set before the data set is
- *                                                               built: train_dataset refuses a sequence built with another window_hot_sub
+ *                                                               built: train_dataset refuses a sequence built with another window_hot_sub.  Every width (num_factor <= 1024)
  *     window_shared_sub (*) 0, window_shared_max (*) 512        one-GPU sequences of rows with shared user entries / feature_user children (amd:shared_user_from):
  *                                                               a shared user row (id >= B) with more than window_shared_sub slots in a window moves in ordered sub-steps
  *                                                               of that many (k_wunit_apply_shared; 0 = off, the default: the rule and bits of 6i / 6j) and meets at most
@@ -422,7 +430,8 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               window_pair_max updates per window; window_per_target then bounds the mean of min(updates per window,
  *                                                               window_pair_sub).  window_hot_sub keeps governing ratings only.  Set before the data set is built:
  *                                                               train_dataset refuses a sequence built with another window_pair_sub.  Refused with amd:contrib = bf16,
- *                                                               user-group trainers, amd:gpus > 1, svdf_dataset_window_from_pairs.  Calibration: profiles/r12_pair_hot.md
+ *                                                               user-group trainers, amd:gpus > 1, svdf_dataset_window_from_pairs, num_factor > 256 ("window_pair_sub > 0 needs
+ *                                                               num_factor <= 256": the pair lane has no wide rows).  Calibration: profiles/r12_pair_hot.md
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is

@@ -149,11 +149,11 @@ Dataset *Engine::dataset_from_triples(long n, const unsigned *user, const unsign
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
     if (multi_ && !in_multi_scope()) return multi_dataset_from_triples(n, user, item, label);
-    if (single_minibatch() && !user_group() && basic_fast_path_allowed()) return wseq_from_triples(n, user, item, label);
+    if (single_minibatch() && !user_group() && window_rows_allowed()) return wseq_from_triples(n, user, item, label);
     if (auto_step_active()) {
         auto_building_ = true;
         struct Done { bool &f; ~Done() { f = false; } } done{auto_building_};
-        const bool wok = wunit_config_ok() && !user_group() && basic_fast_path_allowed();
+        const bool wok = wunit_config_ok(false) && !user_group() && window_rows_allowed();
         if (wok && n > AUTO_PROBE_MIN && auto_probe_deep(dataset_from_triples(AUTO_PROBE_ROWS, user, item, label), n))
             return auto_step(nullptr, true, [&]() { return wseq_from_triples(n, user, item, label); });
         Dataset *exact = dataset_from_triples(n, user, item, label);
@@ -169,7 +169,9 @@ Dataset *Engine::dataset_from_triples(long n, const unsigned *user, const unsign
             idx[(size_t)2 * r] = user[r]; idx[(size_t)2 * r + 1] = item[r];
         }
         ptr[(size_t)3 * n] = 2 * n;
-        return dataset_from_csr(n, label, ptr.data(), idx.data(), val.data());
+        Dataset *g = dataset_from_csr(n, label, ptr.data(), idx.data(), val.data());
+        g->plain_rows = true;
+        return g;
     }
     if (Dataset *pv = pivot_dataset_from_triples(n, user, item, label)) return pv;
     if (Dataset *rn = runs_dataset_from_triples(n, user, item, label)) return rn;   // the contract configuration: runs of an item's consecutive ratings (svdf_runs.cpp)   // hot rows: runs of their ratings as walker units (svdf_pivot.cpp)
@@ -229,11 +231,11 @@ Dataset *Engine::dataset_from_pairs(long n, const unsigned *user, const unsigned
     need_device("dataset");
     if (wseq_pair_sub_ > 0 && ((multi_ && !in_multi_scope()) || (single_minibatch() && user_group()))) wseq_pair_check("dataset_from_pairs");   // (what never reaches wseq_from_pairs)
     if (multi_ && !in_multi_scope()) return multi_dataset_from_pairs(n, user, pos, neg);
-    if (single_minibatch() && !user_group() && basic_fast_path_allowed()) return wseq_from_pairs(n, user, pos, neg);
+    if (single_minibatch() && !user_group() && window_rows_allowed()) return wseq_from_pairs(n, user, pos, neg);
     if (auto_step_active()) {
         auto_building_ = true;
         struct Done { bool &f; ~Done() { f = false; } } done{auto_building_};
-        const bool wok = wunit_config_ok() && !user_group() && basic_fast_path_allowed();
+        const bool wok = wunit_config_ok(false) && !user_group() && window_rows_allowed() && (wseq_pair_sub_ == 0 || wunit_width_ok());
         if (wok && n > AUTO_PROBE_MIN && auto_probe_deep(dataset_from_pairs(AUTO_PROBE_ROWS, user, pos, neg), n))
             return auto_step(nullptr, true, [&]() { return wseq_from_pairs(n, user, pos, neg); });
         Dataset *exact = dataset_from_pairs(n, user, pos, neg);
@@ -287,7 +289,9 @@ Dataset *Engine::dataset_from_pairs(long n, const unsigned *user, const unsigned
             idx[(size_t)3 * r + 2] = pf ? neg[r] : pos[r]; val[(size_t)3 * r + 2] = pf ? -1.0f : 1.0f;
         }
         ptr[(size_t)3 * n] = 3 * n;
-        return dataset_from_csr(n, lab.data(), ptr.data(), idx.data(), val.data());
+        Dataset *g = dataset_from_csr(n, lab.data(), ptr.data(), idx.data(), val.data());
+        g->plain_rows = true;
+        return g;
     }
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->num_row = n; ds->kind = 2;
@@ -665,7 +669,9 @@ void Engine::note_dataset(Dataset *ds) {
     if (D.dag_ms <= 10.0 * D.stream_ms || D.dag_ms < 50.0) return;   // (passes below 50 ms are not worth a line)
     n_guard_warnings_++;
     if (quiet) return;
-    const bool window_ok = wunit_config_ok() && (ds->kind == 3 || ds->kind == 4 || basic_fast_path_allowed());
+    // (plain ratings / rank pairs beyond 256 factors arrive in the general representation: the window kernels take them, the user-unit kernels would not)
+    const bool window_ok = ds->plain_rows ? wunit_config_ok(false) && window_rows_allowed() && (wseq_pair_sub_ == 0 || wunit_width_ok())
+                                          : wunit_config_ok() && (ds->kind == 3 || ds->kind == 4 || basic_fast_path_allowed());
     fprintf(stderr, "[svdfeature_amd] default (exact) step: %ld rows in %ld conflict-free levels -- the data's dependency depth binds: about %.0f ms per pass "
                     "(%.2f M rows/s; levels x %.1f us) against %.1f ms if the rows streamed.  The exact pass keeps the reference's sequential result bit for bit; "
                     "%s\n",

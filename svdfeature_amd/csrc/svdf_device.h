@@ -141,7 +141,8 @@ __device__ __forceinline__ float group_dot(const float4 a, const float4 b, int L
 
 // ------------------------------------------------------------------ wide rows (256 < num_factor <= 1024)
 // A whole wave owns the row, VPL float4 per lane: chunk c (elements 4c..4c+3) sits in lane c % 64, slot c / 64, so a
-// row gather is VPL fully coalesced 1 KiB loads.  Only the general kernels are instantiated for wide rows; the
+// row gather is VPL fully coalesced 1 KiB loads.  The general kernels and the window kernels of plain ratings / rank
+// pairs (svdf_k_window.hip) are instantiated for wide rows; the
 // helpers below are overloads of the float4 ones, so the per-instance code is written once for both (typename R).
 template <int VPL>
 struct WideRow { float4 v[VPL]; };
@@ -540,6 +541,75 @@ template <int LPI, int V> struct row_io<LPI, WideRow<V>> {
     }
 };
 
+// ---- wide rows in the window step (256 < num_factor <= 1024): contribution slots and LDS rows by row type.  The float4 forms are
+// the functions above under another name, so a kernel written over `typename R` is the narrow kernel at R = float4.
+template <int LPI, typename R> struct contrib_io;
+template <int LPI> struct contrib_io<LPI, float4> {
+    static __device__ __forceinline__ void store(float *base, int bf16, size_t slot, int pitch, int L, int k, const float4 &v) { store_contrib<LPI>(base, bf16, slot, pitch, L, k, v); }
+    static __device__ __forceinline__ float4 load(const float *base, int bf16, size_t slot, int pitch, int L, int k) { return load_contrib<LPI>(base, bf16, slot, pitch, L, k); }
+};
+// chunk c of a slot sits where chunk c of a model row sits (lane c % 64, slot c / 64): the same rounding (bf16_rne) per element, V coalesced stores
+template <int LPI, int V> struct contrib_io<LPI, WideRow<V>> {
+    static_assert(LPI == 64, "wide rows are owned by a whole wave");
+    static __device__ __forceinline__ void store(float *base, int bf16, size_t slot, int pitch, int L, int k, const WideRow<V> &r) {
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+            const int e = 4 * (L + 64 * v);
+            if (e >= k) continue;
+            if (bf16) {
+                uint2 pk;
+                pk.x = bf16_rne(r.v[v].x) | (bf16_rne(r.v[v].y) << 16);
+                pk.y = bf16_rne(r.v[v].z) | (bf16_rne(r.v[v].w) << 16);
+                *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(base) + slot * (size_t)pitch + (size_t)e) = pk;
+            } else {
+                *reinterpret_cast<float4 *>(base + slot * (size_t)pitch + (size_t)e) = r.v[v];
+            }
+        }
+    }
+    static __device__ __forceinline__ WideRow<V> load(const float *base, int bf16, size_t slot, int pitch, int L, int k) {
+        WideRow<V> r;
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+            const int e = 4 * (L + 64 * v);
+            if (e >= k) { r.v[v] = f4zero(); continue; }
+            if (bf16) {
+                const uint2 pk = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(base) + slot * (size_t)pitch + (size_t)e);
+                r.v[v] = make_float4(__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xFFFF0000u), __uint_as_float(pk.y << 16), __uint_as_float(pk.y & 0xFFFF0000u));
+            } else {
+                r.v[v] = *reinterpret_cast<const float4 *>(base + slot * (size_t)pitch + (size_t)e);
+            }
+        }
+        return r;
+    }
+};
+// sum_contrib_slots for wide rows: acc = +0 + c_1 + c_2 ... in slot order, NB rows (NB * V float4 per lane) requested at a time
+template <int LPI, bool BF16, int NB = 4, int V>
+__device__ __forceinline__ void sum_contrib_slots(const float *contrib, const float *cbias, int b, int e, int pitch, int L, int k, WideRow<V> &acc, float &accb) {
+    for (int t = b; t < e; t += NB) {
+        WideRow<V> c[NB];
+        float cb[NB];
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+            const bool in = t + q < e;
+            c[q] = in ? contrib_io<LPI, WideRow<V>>::load(contrib, BF16 ? 1 : 0, (size_t)(t + q), pitch, L, k) : row_traits<WideRow<V>>::zero();
+            cb[q] = in ? cbias[t + q] : 0.0f;
+        }
+#pragma unroll
+        for (int q = 0; q < NB; q++) { add_rows(acc, c[q]); accb = accb + cb[q]; }
+    }
+}
+// a row parked in LDS as consecutive chunks (chunk c at base[c]): k_window_apply's staging area and its copy of the hot row
+__device__ __forceinline__ void lds_put_row(float4 *base, int L, const float4 &r) { base[L] = r; }
+template <int V> __device__ __forceinline__ void lds_put_row(float4 *base, int L, const WideRow<V> &r) {
+#pragma unroll
+    for (int v = 0; v < V; v++) base[L + 64 * v] = r.v[v];
+}
+__device__ __forceinline__ void lds_get_row(const float4 *base, int L, float4 &r) { r = base[L]; }
+template <int V> __device__ __forceinline__ void lds_get_row(const float4 *base, int L, WideRow<V> &r) {
+#pragma unroll
+    for (int v = 0; v < V; v++) r.v[v] = base[L + 64 * v];
+}
+
 
 // ---- launch helpers (host side)
 static inline int grid_for(long groups, int lpi, int cap) {
@@ -577,6 +647,11 @@ static inline void launch_shape(long groups, int lpi, int cap, bool small_blocks
         using R = float4;                                                                  \
         SVDF_DISPATCH_LPI(lanes_per_instance(k), __VA_ARGS__)                              \
     } else if ((k) <= 512) { constexpr int LPI = 64; using R = WideRow<2>; __VA_ARGS__; }  \
+    else if ((k) <= 768) { constexpr int LPI = 64; using R = WideRow<3>; __VA_ARGS__; }    \
+    else { constexpr int LPI = 64; using R = WideRow<4>; __VA_ARGS__; }
+// the wide branches alone (k > 256), for launchers whose narrow rows take another kernel or another launch shape
+#define SVDF_DISPATCH_WIDE(k, ...)                                                         \
+    if ((k) <= 512) { constexpr int LPI = 64; using R = WideRow<2>; __VA_ARGS__; }         \
     else if ((k) <= 768) { constexpr int LPI = 64; using R = WideRow<3>; __VA_ARGS__; }    \
     else { constexpr int LPI = 64; using R = WideRow<4>; __VA_ARGS__; }
 

@@ -309,8 +309,11 @@ void Engine::stage_rows_into(HostCSR &staged_, int num_row, const float *row_lab
         staged_.feat_value.insert(staged_.feat_value.end(), feat_value + p0, feat_value + p3);
     }
 }
-bool Engine::basic_fast_path_allowed() const {
-    return !relaxed() && !lazy_decay() && mp_.num_factor <= max_fast_path_factor() && (!user_group() || rows_as_instances_) && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 && feat_item_.num_row() == 0;
+bool Engine::basic_fast_path_allowed() const { return window_rows_allowed() && mp_.num_factor <= max_fast_path_factor(); }
+// rows the window kernels of plain ratings and rank pairs take (svdf_k_window.hip): the conditions of the exact fast forms at every width the model
+// supports -- beyond max_fast_path_factor() a whole wave owns a row (WideRow<2..4>)
+bool Engine::window_rows_allowed() const {
+    return !relaxed() && !lazy_decay() && mp_.num_factor <= max_supported_factor() && (!user_group() || rows_as_instances_) && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 && feat_item_.num_row() == 0;
 }
 
 void Engine::update_csr(float label, int ng, int nu, int ni, const unsigned *index, const float *value) {

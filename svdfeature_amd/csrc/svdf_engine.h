@@ -332,6 +332,7 @@ struct Dataset {
     int wseq_item_sub = -1;        // the same for window_item_sub
     int wseq_block_sub = -1;       // kind 8 from wseq_from_blocks (else -1): window_block_sub as it took effect when the sequence was built (0 without amd:shared_user_from; train_dataset refuses another value)
     long wu_nhrec = 0;             // records in wu_hrec (user-group windows: the rows of the trainer's second record plane, d_hfb_ / d_hfbb_)
+    bool plain_rows = false;       // built by dataset_from_triples / _from_pairs through the general representation (side tables, wide rows ...): the default-step guard names the window step by the columns' shape
     int wseq_hot_sub = -1;         // kind 8 from wseq_from_triples (else -1): window_hot_sub as it took effect when the sequence was built (0 without the lane; train_dataset refuses another value)
     int wseq_pair_sub = -1;        // kind 8 from wseq_from_pairs (else -1): window_pair_sub when the sequence was built (train_dataset refuses another value)
     // kind 8: one GPU, `amd:step = minibatch`: the pass as a sequence of windows (kind 5 or kind 7 children), each trained and applied in place
@@ -610,6 +611,7 @@ class Engine {
     void stage_rows_into(HostCSR &dst, int num_row, const float *row_label, const int *row_ptr, const unsigned *feat_index, const float *feat_value);
     void check_row(int ng, int nu, int ni, const unsigned *index);
     bool basic_fast_path_allowed() const;
+    bool window_rows_allowed() const;     // the same with the width bound at 1024: what the window kernels of ratings / rank pairs take
     bool fused_allowed() const;
     bool fused_allowed_for_rows() const;   // the same for the rows of a feedback-free user-group pass
     template <typename PtrT> bool fused_shape_ok(long n, const PtrT *row_ptr, const unsigned *idx, FusedHost &out);
@@ -685,7 +687,8 @@ class Engine {
     bool side_tables() const { return feat_user_.num_row() != 0 || feat_item_.num_row() != 0; }
     void side_children_ok(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // svdf_wunit.cpp
     const char *side_children_rule(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;
-    bool wunit_config_ok() const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
+    bool wunit_width_ok() const;        // the user-unit kernels' width (one lane group per row)
+    bool wunit_config_ok(bool user_units = true) const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
                           const unsigned *fb_index, const float *fb_value, const int64_t *priv_pos = nullptr, bool children = false, int shared_sub = 0, int item_sub = 0) const;
@@ -808,7 +811,7 @@ class Engine {
     // ---- `amd:step = minibatch | auto` on the staged route of a one-GPU handle (svdf_staged.cpp): a chunk of staged
     // rows is trained as the window sequence svdf_dataset_from_* would build from it; chunks the window step does not cover keep the exact flush
     bool staged_step_wanted() const { return (step_minibatch_set_ || step_auto_set_) && gpus_ == 1 && !multi_ && !is_peer_ && !host_only_; }
-    const char *staged_config_rule(bool blocks) const;   // nullptr: the configuration is inside the window step, else the rule that keeps it out
+    const char *staged_config_rule(bool blocks, bool user_units) const;   // nullptr: the configuration is inside the window step, else the rule that keeps it out
     bool staged_window_csr(HostCSR &src);                // true: the chunk was trained by the window step (src is cleared)
     bool staged_window_units();                          // the same for the closed units of a user-group trainer (flush_units)
     bool staged_window_live() const { return staged_step_wanted() && !auto_building_ && (!step_auto_set_ || staged_auto_decision_ == 0 || staged_auto_decision_ == 2); }

@@ -258,7 +258,8 @@ bool launch_basicmf_chain(const DevParams &P, const BasicSchedule &S, const long
     return true;
 }
 
-template <int LPI, bool UNITVAL>
+// R: float4, or WideRow<2..4> for the rating windows of wide rows (a wave per instance)
+template <int LPI, bool UNITVAL, typename R = float4>
 __global__ __launch_bounds__(256) void k_predict_basic(const DevParams P, const BasicSchedule S, long n, float *out) {
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
@@ -272,9 +273,9 @@ __global__ __launch_bounds__(256) void k_predict_basic(const DevParams P, const 
         if (P.no_user_bias == 0) bs += (double)(ua * P.bias[ur]);
         bs += (double)(ia * P.bias[ir]);
         double sum = (double)P.base_score + bs;
-        float4 tu = f4zero(), ti = f4zero();
-        axpy4(tu, load_row<LPI>(P.W, ur, P.pitch, L, P.k), ua);
-        axpy4(ti, load_row<LPI>(P.W, ir, P.pitch, L, P.k), ia);
+        R tu = row_traits<R>::zero(), ti = row_traits<R>::zero();
+        axpy4(tu, row_io<LPI, R>::load(P.W, ur, P.pitch, L, P.k), ua);
+        axpy4(ti, row_io<LPI, R>::load(P.W, ir, P.pitch, L, P.k), ia);
         sum += (double)group_dot<LPI>(tu, ti, L, P.k);
         if (L == 0) out[s] = map_active((float)sum, P.active_type);
     }
@@ -343,8 +344,8 @@ void launch_predict_basic(const DevParams &P, const BasicSchedule &S, long n, fl
     if (n <= 0) return;
     const int lpi = lanes_per_instance(P.k);
     const int grid = grid_for(n, lpi, 256 * 8);
-    if (S.uval == nullptr) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_predict_basic<LPI, true>), dim3(grid), dim3(256), 0, st, P, S, n, out)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_predict_basic<LPI, false>), dim3(grid), dim3(256), 0, st, P, S, n, out)); }
+    if (S.uval == nullptr) { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_predict_basic<LPI, true, R>), dim3(grid), dim3(256), 0, st, P, S, n, out)); }
+    else { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_predict_basic<LPI, false, R>), dim3(grid), dim3(256), 0, st, P, S, n, out)); }
 }
 
 }  // namespace svdf

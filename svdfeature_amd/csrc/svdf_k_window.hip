@@ -20,10 +20,11 @@ namespace svdf {
 // One user's instances of a window: entries [begin, begin + count) of the user-grouped columns.
 // Records are in LAUNCH order: users sorted by count (descending), so the lane groups of a wave run the same number of iterations.
 
-// ------------------------------------------------------------------------------------------------- kernel A, any width <= 256
+// ------------------------------------------------------------------------------------------------- kernel A, any width
+// R: the row type -- float4 (one lane group per user, num_factor <= 256) or WideRow<2..4> (LPI = 64: one wave per user).
 // PHOT (rank pairs, NI = 2, WindowSchedule::hot_sub > 0): an entry whose item is hot in this window stores tmp_u, the user's bias
 // and -- a pair's label is always 1 -- the pair's POSITION in the user-grouped columns (k_window_apply_pairs finds both item ids and signs through it).
-template <int LPI, bool UNITVAL, int NI, bool PHOT = false>
+template <int LPI, bool UNITVAL, int NI, bool PHOT = false, typename R = float4>
 __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const WindowSchedule S) {
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
     const int pitch = P.pitch, k = P.k;
     const bool use_ubias = P.no_user_bias == 0;
     const unsigned ur = P.user_off + rec.user;
-    float4 p = load_row<LPI>(P.W, ur, pitch, L, k);
+    R p = row_io<LPI, R>::load(P.W, ur, pitch, L, k);
     float bu = use_ubias ? P.bias[ur] : 0.0f;
     const float wd_u = get_wd(P.u_rng, rec.user, P.wd_user);
     for (int j = 0; j < maxc; j++) {
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
         const long s = (long)rec.begin + (act ? j : 0);
         unsigned item[NI];
         float ia[NI], bi[NI];
-        float4 q[NI];
+        R q[NI];
         item[0] = S.item[s];
         ia[0] = (UNITVAL && NI == 1) ? 1.0f : S.ival[s];
         if (NI == 2) { item[1] = S.item1[s]; ia[1] = S.ival1[s]; }
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
         const float ua = UNITVAL ? 1.0f : S.uval[s];
 #pragma unroll
         for (int e = 0; e < NI; e++) {
-            q[e] = load_row<LPI>(P.W, P.item_off + item[e], pitch, L, k);
+            q[e] = row_io<LPI, R>::load(P.W, P.item_off + item[e], pitch, L, k);
             bi[e] = P.bias[P.item_off + item[e]];
         }
         // calc_bias (:313-353) in double; "+ 0.0" terms are the svdpp / plugin hooks returning 0.0f
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
 #pragma unroll
         for (int e = 0; e < NI; e++) bs += (double)(ia[e] * bi[e]);
         double sum = (double)P.base_score + bs;
-        float4 tu = f4zero(), ti = f4zero();
+        R tu = row_traits<R>::zero(), ti = row_traits<R>::zero();
         axpy4(tu, p, ua);
 #pragma unroll
         for (int e = 0; e < NI; e++) axpy4(ti, q[e], ia[e]);
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
         const float pred = map_active((float)sum, P.active_type);
         const float err = cal_grad(label, pred, P.active_type) * 1.0f;
         const float su = P.lr * err * ua;
-        float4 wu = p;
+        R wu = p;
         axpy4(wu, ti, su);
         float nbu = bu + su;
         reg_row<LPI>(P, wu, wd_u, false, L);
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
 #pragma unroll
         for (int e = 0; e < NI; e++) {
             const float si = P.lr * err * ia[e];
-            float4 wi = q[e];
+            R wi = q[e];
             axpy4(wi, tu, si);
             float nbi = bi[e] + si;
             reg_row<LPI>(P, wi, get_wd(P.i_rng, item[e], P.wd_item), true, L);
@@ -90,10 +91,10 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
                 const long slot = e == 0 ? S.slot[s] : S.slot1[s];
                 if ((NI == 1 || PHOT) && S.hot_sub > 0 && S.iptr[item[e] + 1] - S.iptr[item[e]] > S.hot_sub) {
                     // a hot item of this window: what the change is computed FROM goes to the slot; k_window_apply forms it against the row of its sub-step
-                    store_contrib<LPI>(S.contrib, 0, (size_t)slot, pitch, L, k, tu);
+                    contrib_io<LPI, R>::store(S.contrib, 0, (size_t)slot, pitch, L, k, tu);
                     if (L == 0) { S.cbias[slot] = use_ubias ? bu : 0.0f; S.clabel[slot] = PHOT ? __int_as_float((int)s) : label; }
                 } else {
-                    store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)slot, pitch, L, k, wi);
+                    contrib_io<LPI, R>::store(S.contrib, S.contrib_bf16, (size_t)slot, pitch, L, k, wi);
                     if (L == 0) S.cbias[slot] = nbi - bi[e];
                 }
             }
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void k_window_users(const DevParams P, const W
         }
     }
     if (valid) {
-        store_row<LPI>(P.W, ur, pitch, L, k, p);
+        row_io<LPI, R>::store(P.W, ur, pitch, L, k, p);
         if (use_ubias && L == 0) P.bias[ur] = bu;
     }
 }
@@ -315,11 +316,11 @@ void launch_window_users(const DevParams &P, const WindowSchedule &S, int slots,
     const long waves = (S.nusers + ipw - 1) / ipw;
     if (S.item1 != nullptr && S.hot_sub > 0) {   // rank pairs, a window with hot items (window data sets carry unit user values)
         SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 2, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S));
-    } else if (S.item1 != nullptr) {
-        if (S.uval == nullptr) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 2>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
-        else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, false, 2>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
-    } else if (S.uval == nullptr) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, true, 1>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_users<LPI, false, 1>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    } else if (S.item1 != nullptr) {   // (from here on wide rows too: SVDF_DISPATCH_ROW is SVDF_DISPATCH_LPI with R = float4 up to 256 factors, a wave per user beyond)
+        if (S.uval == nullptr) { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_window_users<LPI, true, 2, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+        else { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_window_users<LPI, false, 2, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    } else if (S.uval == nullptr) { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_window_users<LPI, true, 1, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+    else { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_window_users<LPI, false, 1, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
 }
 
 // position j of the packed layout -> the float it stands for
@@ -552,6 +553,81 @@ __global__ __launch_bounds__(256) void k_window_items_sparse(const WindowSchedul
         __syncthreads();
     }
 }
+// WIDE ROWS (256 < num_factor <= 1024): one sum order, one form.  A WAVE owns an item and adds its slots in slot order with
+// sum_contrib_slots (acc = +0 + c_1 + c_2 ..., four slots of V float4 per lane requested ahead) -- the additions of k_window_items, hence its bits, without the
+// LDS queue for long lists.  `span` items are looked at per wave and step: 1 for dense windows (every wave has a list to add), 64 for sparse ones (a lane reads
+// one item's list bounds, the wave walks the items that have slots: k_window_items_sparse's idea without the workgroup queue).  The wire form writes every item of
+// [lo, hi) -- zeros for an item without slots -- and the nglobal zeros behind them; LOCAL adds in place and skips items without slots.
+template <int V, bool HALF, bool LOCAL, bool BF16>
+__global__ __launch_bounds__(256) void k_window_items_wide(const WindowSchedule S, int pitch, int k, long lo, long hi, long nglobal, void *dst, float *dbias, int span) {
+    using R = WideRow<V>;
+    const int lane = threadIdx.x & 63;
+    const long nitem = hi - lo;
+    const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (long)gridDim.x * (blockDim.x >> 6);
+    for (long base = wave * span; base < nitem; base += nwaves * span) {
+        const long mine = base + lane;
+        int b = 0, e = 0;
+        const bool have = lane < span && mine < nitem;
+        if (have) { b = S.iptr[lo + mine]; e = S.iptr[lo + mine + 1]; }
+        unsigned long long todo = __ballot(LOCAL ? (have && e > b) : have);
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int jb = __shfl(b, j), je = __shfl(e, j);
+            const long it = base + j;
+            R acc = row_traits<R>::zero();
+            float accb = 0.0f;
+            sum_contrib_slots<64, BF16>(S.contrib, S.cbias, jb, je, pitch, lane, k, acc, accb);
+            if (LOCAL) {   // dst = W_item's first row, dbias = i_bias
+                float *w = reinterpret_cast<float *>(dst);
+                R c = row_io<64, R>::load(w, (size_t)(lo + it), pitch, lane, k);
+                add_rows(c, acc);
+                row_io<64, R>::store(w, (size_t)(lo + it), pitch, lane, k, c);
+                if (lane == 0) dbias[lo + it] = dbias[lo + it] + accb;
+                continue;
+            }
+#pragma unroll
+            for (int v = 0; v < V; v++) {
+                const int el = 4 * (lane + 64 * v);
+                if (el >= k) continue;
+                const size_t pos = (size_t)it * pitch + (size_t)el;
+                if (HALF) {
+                    __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
+                    h[0] = __halves2half2(__float2half_rn(acc.v[v].x), __float2half_rn(acc.v[v].y));
+                    h[1] = __halves2half2(__float2half_rn(acc.v[v].z), __float2half_rn(acc.v[v].w));
+                } else {
+                    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc.v[v];
+                }
+            }
+            if (lane == 0) {
+                const size_t pos = (size_t)nitem * pitch + (size_t)it;
+                if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
+                else reinterpret_cast<float *>(dst)[pos] = accb;
+            }
+        }
+    }
+    if (LOCAL) return;
+    const long g0 = nitem * (long)(pitch + 1);
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < nglobal; j += (long)gridDim.x * blockDim.x) {
+        if (HALF) reinterpret_cast<__half *>(dst)[g0 + j] = __float2half_rn(0.0f);
+        else reinterpret_cast<float *>(dst)[g0 + j] = 0.0f;
+    }
+}
+template <bool HALF, bool LOCAL>
+static void launch_window_items_wide(const WindowSchedule &S, int pitch, int k, long lo, long hi, long nglobal, void *dst, float *dbias, hipStream_t st, long nslots) {
+    const long nitem = std::max<long>(hi - lo, 0);
+    const int span = (nslots >= 0 && nslots * 2 < nitem) ? 64 : 1;
+    const long waves = std::max<long>((nitem + span - 1) / span, 1);
+    const unsigned grid = (unsigned)std::min<long>((waves + 3) / 4, 16384);
+    const int v = k <= 512 ? 2 : (k <= 768 ? 3 : 4);
+    auto go = [&](auto vv, auto bf) {
+        hipLaunchKernelGGL((k_window_items_wide<decltype(vv)::value, HALF, LOCAL, decltype(bf)::value>), dim3(grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, dbias, span);
+    };
+    auto fmt = [&](auto vv) { if (S.contrib_bf16) go(vv, std::true_type()); else go(vv, std::false_type()); };
+    if (v == 2) fmt(std::integral_constant<int, 2>());
+    else if (v == 3) fmt(std::integral_constant<int, 3>());
+    else fmt(std::integral_constant<int, 4>());
+}
 // A list is LONG relative to its window: the cooperative form serialises a workgroup's long lists, which pays when they are the exception (the hot rows of a
 // skewed window) and costs when every list is long (a dense window of uniform data: 24 slots per item at configs[1], 300 at configs[4] -- there the lane
 // groups' own loops, all busy at once, are the parallel form).  Long = more than 16 slots AND more than four times the window's mean list.
@@ -564,6 +640,11 @@ static int window_hot_min(long nslots, long nitems) {
 static bool window_may_hold_long_lists(long nslots, long nitems) { return nslots >= 0 && nitems > 0 && nslots < 8 * nitems; }
 void launch_window_items(const WindowSchedule &S, int pitch, int k, long lo, long hi, long nglobal, void *dst, int half, hipStream_t st, long nslots) {
     if (hi <= lo && nglobal <= 0) return;
+    if (k > 256) {
+        if (half) launch_window_items_wide<true, false>(S, pitch, k, lo, hi, nglobal, dst, nullptr, st, nslots);
+        else launch_window_items_wide<false, false>(S, pitch, k, lo, hi, nglobal, dst, nullptr, st, nslots);
+        return;
+    }
     const int lpi = lanes_per_instance(k);
     const long ipw = 64 / lpi;
     long waves = (std::max<long>(hi - lo, 1) + ipw - 1) / ipw;
@@ -579,6 +660,7 @@ void launch_window_items(const WindowSchedule &S, int pitch, int k, long lo, lon
 // the same sums added in place to the rows / biases of items [lo, hi): W_item + i * pitch, i_bias + i
 void launch_window_items_local(const WindowSchedule &S, int pitch, int k, long lo, long hi, float *w_item, float *i_bias, hipStream_t st, long nslots) {
     if (hi <= lo) return;
+    if (k > 256) { launch_window_items_wide<false, true>(S, pitch, k, lo, hi, 0L, (void *)w_item, i_bias, st, nslots); return; }
     const int lpi = lanes_per_instance(k);
     if (nslots >= 0 && nslots * 2 < hi - lo) {   // far fewer contributions than items: most items have none (k_window_items_sparse)
         const long grid = std::min<long>((hi - lo + 255) / 256, 16384);
@@ -609,17 +691,23 @@ void launch_window_items_local(const WindowSchedule &S, int pitch, int k, long l
 // ... (neighbouring ids, which real catalogues often sort by popularity, go to different workgroups), queues the hot ones in LDS and walks them --, the
 // other workgroups add the cold items' slots in place, a lane group per item in slot order (sum_contrib_slots: the additions of k_window_items).  Hot and
 // cold items share no row, so the hot items' dependent chains run beside the streaming sums instead of after them.
-template <int LPI, int NT, bool PLAIN>
+// WIDE ROWS (R = WideRow<V>, LPI = 64): the same structure with a wave per slot and V float4 per lane.  NT = 512 there: eight waves, two
+// per SIMD, so that a wave may hold its six rows of up to 16 VGPRs without scratch; a round is two slots per wave at V = 2 and one at V = 3 / 4 (at most 32 KiB of
+// staging), and the summing wave adds 4 V row elements per lane.
+template <int LPI, int NT, bool PLAIN, typename R = float4>
 __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const WindowSchedule S, long num_item, float *w_item, float *i_bias, int hot_blocks) {
+    constexpr int VPL = row_traits<R>::VPL;
+    constexpr int CPR = LPI * VPL;                                    // float4 chunks of a (padded) row
     constexpr int G = NT / LPI;
-    constexpr int K4 = 4 * LPI;                                       // floats of a (padded) row
-    constexpr int CHUNK0 = 2048 / LPI > 128 ? 128 : 2048 / LPI;       // slots per round: at most 32 KB of LDS whatever the width ...
-    constexpr int CHUNK = CHUNK0 < G ? G : CHUNK0;                    // ... and at least one per lane group
+    constexpr int K4 = 4 * CPR;                                       // floats of a (padded) row
+    constexpr int CHUNK0 = 2048 / CPR > 128 ? 128 : 2048 / CPR;       // slots per round: at most 32 KB of LDS whatever the width ...
+    constexpr int CHUNK = CHUNK0 < G ? G : CHUNK0 / G * G;            // ... at least one per lane group, and a whole number per lane group (V = 3: 2048 / 192 = 10 -> 8)
     constexpr int PER = CHUNK / G;
+    static_assert(PER * G == CHUNK, "every lane group forms the same number of changes per round");
     constexpr int EPL = (K4 + 63) / 64;                               // row elements per lane of the summing wave
-    __shared__ float4 stage[CHUNK * LPI];
+    __shared__ float4 stage[CHUNK * CPR];
     __shared__ float stage_b[CHUNK];
-    __shared__ float4 rowq[LPI];
+    __shared__ float4 rowq[CPR];
     __shared__ float rowb;
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
@@ -633,14 +721,20 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
         for (long i = (long)(blockIdx.x - hot_blocks) * G + grp; i < num_item; i += stride) {
             const int b = S.iptr[i], e = S.iptr[i + 1];
             if (b == e || e - b > S.hot_sub) continue;
-            float4 acc = f4zero();
+            R acc = row_traits<R>::zero();
             float accb = 0.0f;
             sum_contrib_slots<LPI, false>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
-            if (owns) {
-                float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
-                float4 c = *w;
-                c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-                *w = c;
+            if constexpr (VPL == 1) {
+                if (owns) {
+                    float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
+                    float4 c = *w;
+                    c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
+                    *w = c;
+                }
+            } else {
+                R c = row_io<LPI, R>::load(w_item, (size_t)i, pitch, L, k);
+                add_rows(c, acc);
+                row_io<LPI, R>::store(w_item, (size_t)i, pitch, L, k, c);
             }
             if (L == 0) i_bias[i] = i_bias[i] + accb;
         }
@@ -667,9 +761,9 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
         const int b = hl_b[h], e = hl_e[h];
         const unsigned ir = P.item_off + item;
         const float wd_i = get_wd(P.i_rng, item, P.wd_item);
-        float4 q = load_row<LPI>(P.W, ir, pitch, L, k);
+        R q = row_io<LPI, R>::load(P.W, ir, pitch, L, k);
         float bi = P.bias[ir];
-        if (grp == 0) { rowq[L] = q; if (L == 0) rowb = bi; }
+        if (grp == 0) { lds_put_row(rowq, L, q); if (L == 0) rowb = bi; }
         {   // the item's slots were written by other CUs a kernel ago (they sit in HBM / the Infinity Cache): one request per 128-byte line, all in flight at
             // once, brings them into this XCD's L2 -- the sub-steps below are a dependent chain and would otherwise pay that latency once per sub-step
             float warm = 0.0f;
@@ -679,14 +773,14 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
             if (warm == 1.2345e-38f) rowb = warm;   // (never true for data that matters: keeps the loads alive)
         }
         // the slots of a round do not depend on the row: the NEXT round's are requested before this round's changes are formed
-        float4 ntu[PER];
+        R ntu[PER];
         float nbu[PER], nlabel[PER];
         auto fetch = [&](int first, int cn) {
 #pragma unroll
             for (int r = 0; r < PER; r++) {
                 const int sl = grp + r * G;
                 const size_t slot = (size_t)(first + (sl < cn ? sl : 0));
-                ntu[r] = load_contrib<LPI>(S.contrib, 0, slot, pitch, L, k);
+                ntu[r] = contrib_io<LPI, R>::load(S.contrib, 0, slot, pitch, L, k);
                 nbu[r] = S.cbias[slot];
                 nlabel[r] = S.clabel[slot];
             }
@@ -700,7 +794,7 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
             float accb = 0.0f;
             for (int c0 = 0; c0 < sn; c0 += CHUNK) {
                 const int cn = min(CHUNK, sn - c0);
-                float4 tu[PER];
+                R tu[PER];
                 float bu[PER], label[PER];
 #pragma unroll
                 for (int r = 0; r < PER; r++) { tu[r] = ntu[r]; bu[r] = nbu[r]; label[r] = nlabel[r]; }
@@ -718,20 +812,20 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
                     bs += 0.0;
                     bs += (double)(1.0f * bi);
                     double sum = (double)P.base_score + bs;
-                    float4 ti = f4zero();
+                    R ti = row_traits<R>::zero();
                     axpy4(ti, q, 1.0f);
                     sum += (double)group_dot<LPI>(tu[r], ti, L, k);
                     const float pred = PLAIN ? (float)sum : map_active((float)sum, P.active_type);
                     const float err = (PLAIN ? label[r] - pred : cal_grad(label[r], pred, P.active_type)) * 1.0f;
                     const float si = P.lr * err * 1.0f;
-                    float4 wi = q;
+                    R wi = q;
                     axpy4(wi, tu[r], si);
                     float nbi = bi + si;
                     if (PLAIN) scale4(wi, 1.0f - P.lr * wd_i);   // (reg_row's method 0)
                     else reg_row<LPI>(P, wi, wd_i, true, L);
                     nbi = nbi * (1.0f - P.lr * P.wd_item_bias);
                     sub4(wi, q);
-                    if (sl < cn) { stage[sl * LPI + L] = wi; if (L == 0) stage_b[sl] = nbi - bi; }
+                    if (sl < cn) { lds_put_row(stage + sl * CPR, L, wi); if (L == 0) stage_b[sl] = nbi - bi; }
                 }
                 __syncthreads();
                 // slot order (acc = ((0 + c_1) + c_2) + ..., the sums of k_window_items), one ROW ELEMENT per lane of the first wave: 128 dependent
@@ -739,7 +833,7 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
                 if (wv == 0) {
                     // whole batches first: AH reads at constant offsets, AH additions, no per-slot bounds test (the clamped form costs ~45 cycles of scalar
                     // bookkeeping per slot: 2.5 us per sub-step of 128), then the tail one slot at a time
-                    constexpr int AH = EPL == 1 ? 32 : (EPL == 2 ? 16 : 8);
+                    constexpr int AH = EPL == 1 ? 32 : (EPL == 2 ? 16 : (EPL <= 4 ? 8 : 4));   // (wide rows: 8 .. 16 elements per lane, four slots ahead)
                     bool on[EPL];
 #pragma unroll
                     for (int z = 0; z < EPL; z++) on[z] = lane + 64 * z < K4;
@@ -784,12 +878,12 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
                 rowb = rowb + accb;
             }
             __syncthreads();
-            q = rowq[L];
+            lds_get_row(rowq, L, q);
             bi = rowb;
         }
         __syncthreads();   // (the next item of this workgroup writes rowq / rowb)
         if (grp == 0) {
-            store_row<LPI>(P.W, ir, pitch, L, k, q);
+            row_io<LPI, R>::store(P.W, ir, pitch, L, k, q);
             if (L == 0) P.bias[ir] = bi;
         }
     }
@@ -800,10 +894,19 @@ void launch_window_apply(const DevParams &P, const WindowSchedule &S, long num_i
     if (S.hot_sub <= 0 || num_item <= 0) return;
     const int lpi = lanes_per_instance(P.k);
     const int hot_blocks = 256;
+    const bool plain = P.active_type == ACT_LINEAR && P.reg_method == 0;
+    if (P.k > 256) {   // wide rows: a wave per slot, 512 threads (the kernel's head comment)
+        const long groups = 512 / 64;
+        const long cold = std::min<long>(std::max<long>((num_item + groups - 1) / groups, 1), 4096);
+        const unsigned grid = (unsigned)(hot_blocks + cold);
+        if (plain) { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_window_apply<LPI, 512, true, R>), dim3(grid), dim3(512), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+        else { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_window_apply<LPI, 512, false, R>), dim3(grid), dim3(512), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+        return;
+    }
     const long groups = 1024 / lpi;
     const long cold = std::min<long>(std::max<long>((num_item + groups - 1) / groups, 1), 4096);
     const unsigned grid = (unsigned)(hot_blocks + cold);
-    if (P.active_type == ACT_LINEAR && P.reg_method == 0) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, true>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+    if (plain) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, true>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
     else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, false>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
 }
 // ------------------------------------------------------------------------------------------------- rank pairs with hot items (round 12): apply + sums
@@ -1060,7 +1163,7 @@ void launch_window_user_column(const WinUser *urec, int nusers, unsigned *user_o
 // ival1 -- and the statements are k_predict_fused's for that shape (calc_bias in double in entry order, apex_svd_base.h:445-454), so a score
 // equals svdf_predict_csr_batch's for the same row bit for bit.  The user comes from the column k_window_user_column wrote.  Nothing of the
 // model or of the window is written; slots and hot marks are not read.
-template <int LPI>
+template <int LPI, typename R = float4>
 __global__ __launch_bounds__(256) void k_window_predict_pairs(const DevParams P, const WindowSchedule S, const unsigned *user_col, long n, const int *pos,
                                                               float *out) {
     constexpr int IPW = 64 / LPI;
@@ -1076,10 +1179,10 @@ __global__ __launch_bounds__(256) void k_window_predict_pairs(const DevParams P,
         if (P.no_user_bias == 0) bs += (double)(1.0f * P.bias[ur]);
         bs += (double)(v0 * P.bias[i0]);
         bs += (double)(v1 * P.bias[i1]);
-        float4 tu = f4zero(), ti = f4zero();
-        axpy4(tu, load_row<LPI>(P.W, ur, P.pitch, L, P.k), 1.0f);
-        axpy4(ti, load_row<LPI>(P.W, i0, P.pitch, L, P.k), v0);
-        axpy4(ti, load_row<LPI>(P.W, i1, P.pitch, L, P.k), v1);
+        R tu = row_traits<R>::zero(), ti = row_traits<R>::zero();
+        axpy4(tu, row_io<LPI, R>::load(P.W, ur, P.pitch, L, P.k), 1.0f);
+        axpy4(ti, row_io<LPI, R>::load(P.W, i0, P.pitch, L, P.k), v0);
+        axpy4(ti, row_io<LPI, R>::load(P.W, i1, P.pitch, L, P.k), v1);
         double sum = (double)P.base_score + bs;
         sum += (double)group_dot<LPI>(tu, ti, L, P.k);
         if (L == 0) out[pos ? (long)pos[s] : s] = map_active((float)sum, P.active_type);
@@ -1089,7 +1192,7 @@ void launch_window_predict_pairs(const DevParams &P, const WindowSchedule &S, co
     if (n <= 0) return;
     const int lpi = lanes_per_instance(P.k);
     const int grid = grid_for(n, lpi, 256 * 8);
-    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_predict_pairs<LPI>), dim3(grid), dim3(256), 0, st, P, S, user_col, n, pos, out));
+    SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_window_predict_pairs<LPI, R>), dim3(grid), dim3(256), 0, st, P, S, user_col, n, pos, out));
 }
 void launch_ranges_copy(const DeltaRanges &R, float *buf, int set, hipStream_t st) {
     const long total = R.off[R.n];

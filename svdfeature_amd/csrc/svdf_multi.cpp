@@ -315,7 +315,7 @@ static bool rows_are_triples(const HostCSR &src, long r0, long r1) {
     return true;
 }
 bool Engine::multi_minibatch_allowed() const {
-    return !multi_step_levels_ && !user_group() && mtype_.extend_type == 0 && basic_fast_path_allowed() && g_stride_ == 1;
+    return !multi_step_levels_ && !user_group() && mtype_.extend_type == 0 && window_rows_allowed() && g_stride_ == 1;
 }
 
 // the staged rows as exchange windows over all ranks (called instead of flush_csr on the handle): at most stage_window_ rows

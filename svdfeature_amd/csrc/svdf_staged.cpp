@@ -47,13 +47,15 @@ void DevPool::end_chunk() {
 }
 
 // ---- what keeps a configuration out of the window step: wunit_check_config / window_build_header as a predicate
-const char *Engine::staged_config_rule(bool blocks) const {
+// user_units: the chunk takes the user-unit kernels (rows with globals or several entries, SVD++ blocks: num_factor <= 256); chunks of plain ratings / rank
+// pairs take the window kernels, which have wide rows
+const char *Engine::staged_config_rule(bool blocks, bool user_units) const {
     if (mtype_.extend_type != 0) return "the window step covers the base solvers only (extend_type 0)";
     if (relaxed()) return "relaxed ids (amd:relax_*) are outside the window step";
     if (lazy_decay()) return "lazy decay (reg_method / reg_global >= 4) is outside the window step";
     if (mp_.common_latent_space != 0) return "a shared latent space (common_latent_space) is outside the window step";
     if (g_stride_ != 1) return "the relaxed layout of the global biases is outside the window step";
-    if (mp_.num_factor > 256) return "the window step needs num_factor <= 256";
+    if (user_units && !wunit_width_ok()) return "the window step of rows with global features, several user / item entries or implicit feedback needs num_factor <= 256";
     if (side_tables()) {
         if (blocks) return "feature_user / feature_item side tables are not supported with user-group (SVD++) trainers in the window step";
         if (feat_user_.num_row() != 0 && !shared_user()) return "a feature_user side table needs amd:shared_user_from in the window step (its children are shared user rows)";
@@ -73,6 +75,7 @@ const char *Engine::staged_config_rule(bool blocks) const {
     if (wseq_pair_sub_ > 0) {
         if (contrib_bf16_) return "window_pair_sub > 0 needs amd:contrib = fp32";
         if (blocks) return "window_pair_sub > 0 is not supported with user-group (SVD++) trainers";
+        if (!wunit_width_ok()) return "window_pair_sub > 0 needs num_factor <= 256";
     }
     if (blocks && mp_.common_feedback_space != 0) return "user-group trainers need a feedback space of their own (common_feedback_space = 0) in the window step";
     if (shared_user() && !(shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user)) return "amd:shared_user_from must be in 1 .. num_user";
@@ -148,7 +151,7 @@ bool Engine::staged_window_csr(HostCSR &src) {
     const unsigned *idx = src.feat_index.data();
     const float *val = src.feat_value.data();
     // the chunk's shape picks the builder svdf_dataset_from_* would be called with
-    bool triples = basic_fast_path_allowed(), pairs = triples;
+    bool triples = window_rows_allowed(), pairs = triples;
     for (long r = 0; r < n && (triples || pairs); r++) {
         const int *p = rp + 3 * r;
         if (p[1] != p[0] || p[2] != p[1] + 1) { triples = pairs = false; break; }
@@ -159,7 +162,7 @@ bool Engine::staged_window_csr(HostCSR &src) {
         }
     }
     if (n == 0) triples = pairs = false;
-    const char *rule = staged_config_rule(false);
+    const char *rule = staged_config_rule(false, !triples && !pairs);
     std::vector<int64_t> ptr64;
     if (!triples && !pairs) {
         ptr64.assign(src.row_ptr.begin(), src.row_ptr.end());
@@ -258,7 +261,7 @@ bool Engine::staged_window_units() {
     long u0 = 0, u1 = nu;
     if (!closed(0)) u0 = 1;
     if (nu > u0 && !closed(nu - 1)) u1 = nu - 1;
-    const char *rule = staged_config_rule(true);
+    const char *rule = staged_config_rule(true, true);
     for (long t = 0; t < nu && !rule; t++) {   // rows staged without a block carry neither tag (update_csr_batch marks them UNIT_LOAD | UNIT_SAVE)
         const int f = staged_units_[(size_t)t].flags;
         if (!(f & UNIT_START) && !(f & UNIT_END) && (f & UNIT_SAVE)) rule = "rows without a block (svdf_update_csr on a user-group trainer) are outside the window step";

@@ -51,7 +51,7 @@ Dataset *Engine::dataset_window_from_pairs(long n, const unsigned *user, const u
 // neg != nullptr: rank pairs, `item` holds the positive items and the labels are 1.
 void Engine::window_build_header(Dataset *ds, long n, bool pairs) {
     check(!user_group() && mtype_.extend_type == 0, "window data sets: random-order trainers only");
-    check(basic_fast_path_allowed(), "window data sets: no side tables, relaxed ids, lazy decay or shared latent space; num_factor <= 256");
+    check(window_rows_allowed(), "window data sets: no side tables, relaxed ids, lazy decay or shared latent space");
     check(n >= 0 && n < (1L << 30), "window data sets: at most 2^30-1 instances per window");
     if (window_trained_ == ds) window_trained_ = nullptr;
     ds->num_row = n; ds->kind = 5;
@@ -60,7 +60,7 @@ void Engine::window_build_header(Dataset *ds, long n, bool pairs) {
 }
 void Engine::window_build(Dataset *ds, long n, const unsigned *user, const unsigned *item, const float *label, const unsigned *neg) {
     check(!user_group() && mtype_.extend_type == 0, "window data sets: random-order trainers only");
-    check(basic_fast_path_allowed(), "window data sets: no side tables, relaxed ids, lazy decay or shared latent space; num_factor <= 256");
+    check(window_rows_allowed(), "window data sets: no side tables, relaxed ids, lazy decay or shared latent space");
     check(n >= 0 && n < (1L << 30), "window data sets: at most 2^30-1 instances per window");
     const long NU = mp_.num_user, NI = mp_.num_item;
     const bool pairs = neg != nullptr;

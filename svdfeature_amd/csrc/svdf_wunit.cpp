@@ -78,10 +78,13 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     return S;
 }
 
-bool Engine::wunit_config_ok() const {
+// user_units: the data set would take the user-unit kernels (svdf_k_wunit.hip, svdf_k_wave.hip: one lane group per row, num_factor <= 256); the windows of
+// plain ratings / rank pairs (svdf_k_window.hip) have wide rows and ask with false
+bool Engine::wunit_config_ok(bool user_units) const {
     return trainer_ready_ && mtype_.extend_type == 0 && !relaxed() && !lazy_decay() && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 &&
-           feat_item_.num_row() == 0 && g_stride_ == 1 && mp_.num_factor <= 256 && (!user_group() || mp_.common_feedback_space == 0);
+           feat_item_.num_row() == 0 && g_stride_ == 1 && (!user_units || wunit_width_ok()) && (!user_group() || mp_.common_feedback_space == 0);
 }
+bool Engine::wunit_width_ok() const { return mp_.num_factor <= 256; }
 void Engine::wunit_check_config(const char *what, bool tables_ok) const {
     check(trainer_ready_, "dataset: init_trainer has not been called");
     check(mtype_.extend_type == 0, "window data sets: the base solvers only (extend_type 0)");
@@ -108,7 +111,7 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
         check(wunit_inplace_ != 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)");
     }
     if (block_sub() > 0) wseq_block_check(what);
-    check(mp_.num_factor <= 256, "window data sets: num_factor <= 256");
+    check(wunit_width_ok(), "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
 }
@@ -1023,7 +1026,7 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
 // Ordered sub-steps (svdf_k_window.hip: k_window_apply): plain ratings of the configurations the window kernels walk with unit values and fp32
 // contribution rows, on the one-GPU sequence (in-place sums).
 bool Engine::wseq_hot_ok() const {
-    return wseq_hot_sub_ > 0 && !contrib_bf16_ && !user_group() && basic_fast_path_allowed() && gpus_ == 1 && !multi_ && !is_peer_;
+    return wseq_hot_sub_ > 0 && !contrib_bf16_ && !user_group() && window_rows_allowed() && gpus_ == 1 && !multi_ && !is_peer_;
 }
 // The window count with the hot lane.  What the round-5 rule bounded through ONE number per row -- updates met per window -- are two different things:
 //   * how many changes of a row are computed against one value of it (overshoot: diverges on Zipf items): with sub-steps at most hot_sub for every row,
@@ -1176,6 +1179,7 @@ void Engine::wseq_pair_check(const char *what) const {
                    "the N-rank exchange sums every slot on the wire", true);
     check(gpus_ == 1 && !multi_ && !is_peer_,
           "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence; amd:gpus > 1 sums every slot on the wire");
+    check(wunit_width_ok(), "window data sets: window_pair_sub > 0 needs num_factor <= 256 (the lane of rank pairs has no wide rows)");
 }
 Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg) {
     const std::vector<long> ci = wseq_item_counts(n, pos, neg);
