@@ -66,14 +66,17 @@ void svdf_destroy(svdf_trainer *t);
  * a user still open, that user and its continuation keep the exact unit path, which is normal and not counted).  A chunk whose rows or configuration the
  * window step does not cover keeps the exact flush -- never an error; the first one prints one stderr line naming the rule.  `auto` decides
  * on the first chunk of at least device_schedule_min rows and keeps the decision until the next svdf_set_param.
- * WIDTHS of the window step (DESIGN.md 6s).  num_factor <= 1024: plain ratings and rank pairs -- svdf_dataset_from_triples / _from_pairs under
+ * WIDTHS of the window step (DESIGN.md 6s, 6t).  num_factor <= 1024: plain ratings and rank pairs -- svdf_dataset_from_triples / _from_pairs under
  * minibatch / auto, staged chunks of those two shapes, the stand-alone windows svdf_dataset_window_from_triples / _from_pairs with
- * svdf_window_delta_pack / _apply / _apply_local, svdf_stratum_step and the item-range pieces, amd:gpus handles on such rows, window_hot_sub, and
- * svdf_predict_dataset / svdf_eval_dataset on all of these (beyond 256 factors a whole wave owns a row, two to four float4 per lane).
- * num_factor <= 256: everything that takes the user-unit kernels, one lane group per row -- rows with global features or several user / item
- * entries (svdf_dataset_from_csr, svdf_dataset_window_from_csr), SVD++ blocks, amd:shared_user_from, side tables, window_shared_sub /
- * window_item_sub / window_block_sub -- and window_pair_sub > 0.  Beyond their width the resident calls refuse with a message; a staged chunk
- * keeps the exact flush (counter 31) and `auto` keeps the exact levels (decision 3). */
+ * svdf_window_delta_pack / _apply / _apply_local, svdf_stratum_step and the item-range pieces, amd:gpus handles on such rows, window_hot_sub --
+ * and, on the one-GPU window sequence of amd:step = minibatch alone, everything that takes the user-unit kernels: svdf_dataset_from_csr (rows with
+ * global features or several user / item entries, amd:shared_user_from, side tables) and svdf_dataset_from_blocks (SVD++ blocks, with shared user
+ * ids too), the buffer-file routes that end in them, fp32 and bf16 slots as at the narrow widths; svdf_predict_dataset / svdf_eval_dataset on all of
+ * these (beyond 256 factors a whole wave owns a row, two to four float4 per lane).
+ * num_factor <= 256: the other routes of user units, one lane group per row -- svdf_dataset_window_from_csr / _from_blocks (the N-rank builders,
+ * amd:gpus > 1), the staged route, amd:step = auto -- and the lanes of ordered sub-steps: window_shared_sub / window_item_sub / window_block_sub /
+ * window_pair_sub > 0.  Beyond their width the resident calls refuse with a message that names the knob or the call; a staged chunk keeps the
+ * exact flush (counter 31) and `auto` keeps the exact levels (decision 3). */
 int svdf_set_param(svdf_trainer *t, const char *name, const char *val);
 /* apex_random::seed (apex-tensor/apex_random.h:42-44) -> srand; process-global like the reference. */
 void svdf_seed(unsigned seed);

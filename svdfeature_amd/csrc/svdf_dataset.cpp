@@ -645,8 +645,9 @@ std::string Engine::path_for(const Dataset *ds) const {
     case 5: return "window data set (one window of the window-minibatch step, user side exact): k_window_users / k_window_items";
     case 6: return "amd:gpus handle: per-rank windows (svdf_multi.cpp)";
     case 7: return "window data set of user units: k_wunit_* (svdf_k_wunit.hip)";
-    case 8: snprintf(buf, sizeof(buf), "window sequence (amd:step = minibatch / auto): %zu windows, each trained and applied in place%s; NOT the reference's sequential semantics (|dRMSE| <= 1e-4 contract)",
-                     ds->wchild.size(), side_tables() ? ", feature_user / feature_item children as shared rows (general walk k_wunit_walk)" : ""); return buf;
+    case 8: snprintf(buf, sizeof(buf), "window sequence (amd:step = minibatch / auto): %zu windows, each trained and applied in place%s%s; NOT the reference's sequential semantics (|dRMSE| <= 1e-4 contract)",
+                     ds->wchild.size(), side_tables() ? ", feature_user / feature_item children as shared rows (general walk k_wunit_walk)" : "",
+                     !ds->wchild.empty() && ds->wchild[0]->kind == 7 && !wunit_width_ok() ? ", user units of wide rows: the wide general walk k_wunit_walk<64, ., ., WideRow>, one wave per unit" : ""); return buf;
     case 9: snprintf(buf, sizeof(buf), "exact, %ld levels: hot rows walked as units (k_svdpp_wave on %s parameters, %ld units) + cold ratings through the contract kernel",
                      L, ds->pv_item_pivot ? "transposed" : "plain", ds->num_units); return buf;
     case 10: snprintf(buf, sizeof(buf), "exact, %ld levels of runs: k_basicmf_runs_soa (up to %d consecutive ratings of one item per lane group, the item's row in registers)", L, ds->rn_len); return buf;

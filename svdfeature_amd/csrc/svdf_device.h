@@ -142,8 +142,8 @@ __device__ __forceinline__ float group_dot(const float4 a, const float4 b, int L
 // ------------------------------------------------------------------ wide rows (256 < num_factor <= 1024)
 // A whole wave owns the row, VPL float4 per lane: chunk c (elements 4c..4c+3) sits in lane c % 64, slot c / 64, so a
 // row gather is VPL fully coalesced 1 KiB loads.  The general kernels and the window kernels of plain ratings / rank
-// pairs (svdf_k_window.hip) are instantiated for wide rows; the
-// helpers below are overloads of the float4 ones, so the per-instance code is written once for both (typename R).
+// pairs (svdf_k_window.hip) are instantiated for wide rows, and so are the general walk, the in-place sums and the
+// scoring kernels of user units (svdf_k_wunit.hip); the helpers below are overloads of the float4 ones, so the per-instance code is written once for both (typename R).
 template <int VPL>
 struct WideRow { float4 v[VPL]; };
 template <typename R> struct row_traits;
@@ -494,6 +494,22 @@ __device__ __forceinline__ float apply_single(float w, float c, bool bf16) {
 }
 __device__ __forceinline__ float4 apply_single(const float4 w, const float4 c, bool bf16) {
     return make_float4(apply_single(w.x, c.x, bf16), apply_single(w.y, c.y, bf16), apply_single(w.z, c.z, bf16), apply_single(w.w, c.w, bf16));
+}
+template <int V> __device__ __forceinline__ WideRow<V> apply_single(const WideRow<V> &w, const WideRow<V> &c, bool bf16) {
+    WideRow<V> r;
+#pragma unroll
+    for (int v = 0; v < V; v++) r.v[v] = apply_single(w.v[v], c.v[v], bf16);
+    return r;
+}
+// a whole contribution row as its slot would have stored it (k_wunit_sum's deferred feedback sums form the row themselves)
+__device__ __forceinline__ float4 contrib_as_stored(const float4 c, bool bf16) {
+    return make_float4(contrib_as_stored(c.x, bf16), contrib_as_stored(c.y, bf16), contrib_as_stored(c.z, bf16), contrib_as_stored(c.w, bf16));
+}
+template <int V> __device__ __forceinline__ WideRow<V> contrib_as_stored(const WideRow<V> &c, bool bf16) {
+    WideRow<V> r;
+#pragma unroll
+    for (int v = 0; v < V; v++) r.v[v] = contrib_as_stored(c.v[v], bf16);
+    return r;
 }
 // sum of contribution slots [b, e) in slot order: eight rows requested at a time; slots past the segment's end feed +0.0f, which leaves the running
 // sum unchanged bit for bit (the sum starts at +0.0f and x + y is -0 only when both are, so acc is never -0).  The storage format is a TEMPLATE

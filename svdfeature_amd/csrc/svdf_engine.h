@@ -687,7 +687,8 @@ class Engine {
     bool side_tables() const { return feat_user_.num_row() != 0 || feat_item_.num_row() != 0; }
     void side_children_ok(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // svdf_wunit.cpp
     const char *side_children_rule(const int64_t *row_ptr3, const unsigned *feat_index, std::vector<unsigned> &seen) const;
-    bool wunit_width_ok() const;        // the user-unit kernels' width (one lane group per row)
+    bool wunit_width_ok() const;        // the user-unit kernels' width (one lane group per row): the sub-step lanes, the N-rank builders, the staged route, `auto`
+    bool wunit_wide_ok() const;         // the one-GPU window sequence of user units (wseq_from_csr / wseq_from_blocks): wide rows too, a wave per unit
     bool wunit_config_ok(bool user_units = true) const;       // the same conditions as a predicate (svdf_multi.cpp picks the step per data set)
     void wunit_build_host(WUnitHost &H, bool inplace, const void *segs, size_t nseg, const std::vector<int64_t> &seg_rows, bool by_row_order, long num_src_row,
                           const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,

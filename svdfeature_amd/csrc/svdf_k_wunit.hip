@@ -14,6 +14,7 @@
 //     the sum to the model in place (one GPU, `amd:step = minibatch`) or writes the wire buffer of the N-rank exchange.
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 
 #include "svdf_instance.h"
 
@@ -24,7 +25,8 @@ namespace svdf {
 // ------------------------------------------------------------------------------------------------- kernel A: the users' exact walks
 // FB: the trainer is SVDPPFeature (user-group format): a segment prepares tmp_ufeedback from its feedback list (:523-538), every row
 // goes through the update_svdpp hook (:512-520), the segment's end is update_ufeedback (:539-554) against the window-start rows.
-// General form: any width <= 256, any row shape (one user entry per row), every link and regulariser of the base solver.
+// General form: any width, any row shape (one user entry per row), every link and regulariser of the base solver.  R: the row type -- float4 (one lane
+// group per unit, num_factor <= 256) or WideRow<2..4> (LPI = 64: one wave per unit, HOT = false only).
 // Shared user rows (S.uptr, amd:shared_user_from): the row's other user entries are read as of the window start, in entry order around the
 // private one (calc_bias :313-353, prepare_tmp :354-381), and their change goes to a contribution slot like an item row's.
 // Side-table children: feature_user children are shared user entries (the builder expands them); feature_item children
@@ -32,8 +34,10 @@ namespace svdf {
 // (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
 // HOT: the window has hot shared user rows or hot item rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the
 // code as it was.  FB and HOT together: user-group windows with hot shared user rows (knob window_block_sub).
-template <int LPI, bool FB, bool HOT = false>
+template <int LPI, bool FB, bool HOT = false, typename R = float4>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
+    using io = row_io<LPI, R>;
+    using cio = contrib_io<LPI, R>;
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
     const int L = lane & (LPI - 1);
@@ -44,18 +48,18 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
     const bool ub = P.no_user_bias == 0;
     const float lr = P.lr;
     const unsigned ur = P.user_off + un.user;
-    float4 p = load_row<LPI>(P.W, ur, pitch, L, k);
+    R p = io::load(P.W, ur, pitch, L, k);
     float bu = ub ? P.bias[ur] : 0.0f;
     const float wd_u = get_wd(P.u_rng, un.user, P.wd_user);
     for (int sg = 0; sg < un.seg_count; sg++) {
         const WinSeg seg = sg == 0 ? un.first : S.segs[un.seg_begin + sg];
-        SvdppRegs pp;
-        pp.tmp_fb = f4zero(); pp.old_fb = f4zero(); pp.norm = 0.0f; pp.tmp_bias = 0.0f; pp.old_bias = 0.0f;
+        SvdppRegsT<R> pp;
+        pp.tmp_fb = row_traits<R>::zero(); pp.old_fb = row_traits<R>::zero(); pp.norm = 0.0f; pp.tmp_bias = 0.0f; pp.old_bias = 0.0f;
         if (FB) {   // prepare_ufeedback + the backup of update(block) (:568-574)
             for (int j = seg.fb_begin; j < seg.fb_begin + seg.fb_count; j++) {
                 const WinEnt f = S.fbent[j];
                 const unsigned row = P.fb_off + f.idx;
-                axpy4(pp.tmp_fb, load_row<LPI>(P.W, row, pitch, L, k), f.val);
+                axpy4(pp.tmp_fb, io::load(P.W, row, pitch, L, k), f.val);
                 pp.norm = pp.norm + f.val * f.val;
                 if (ub) pp.tmp_bias = pp.tmp_bias + P.bias[row] * f.val;
             }
@@ -89,17 +93,17 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
             }
             double sum = (double)P.base_score + bs;
-            float4 tu = FB ? pp.tmp_fb : f4zero();
-            for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+            R tu = FB ? pp.tmp_fb : row_traits<R>::zero();
+            for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, io::load(P.W, srow0 + e.idx, pitch, L, k), e.val); }
             axpy4(tu, p, ua);
-            for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
-            float4 ti = f4zero();
+            for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, io::load(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+            R ti = row_traits<R>::zero();
             for (int j = e1, c = c0; j < e2; j++) {
                 const WinEnt e = S.ent[j];
-                axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+                axpy4(ti, io::load(P.W, P.item_off + e.idx, pitch, L, k), e.val);
                 for (; c < c1 && S.ient[c].pad == j; c++) {   // scalar formed in double
                     const WinEnt ch = S.ient[c];
-                    axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+                    axpy4(ti, io::load(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
                 }
             }
             sum += (double)group_dot<LPI>(tu, ti, L, k);
@@ -114,30 +118,30 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 if (L == 0) S.gcontrib[e.slot] = g2 - g;
             }
             const float su = lr * err * ua;
-            float4 wu = p;
+            R wu = p;
             axpy4(wu, ti, su);
             float nbu = bu + su;
             for (int j = e1; j < e2; j++) {
                 const WinEnt e = S.ent[j];
                 if (HOT && e.pad) {   // a hot item row of this window (k_wunit_apply_hot<ITEM>): the same record as for a hot shared user row below
-                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
+                    cio::store(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
                     if (L == 0) S.cbias[e.slot] = bu;
                     continue;
                 }
                 const float si = lr * err * e.val;
-                const float4 q = load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k);
+                const R q = io::load(P.W, P.item_off + e.idx, pitch, L, k);
                 const float bi = P.bias[P.item_off + e.idx];
-                float4 wi = q;
+                R wi = q;
                 axpy4(wi, tu, si);
                 float nbi = bi + si;
                 reg_row<LPI>(P, wi, get_wd(P.i_rng, e.idx, P.wd_item), true, L);
                 nbi = nbi * (1.0f - lr * P.wd_item_bias);
                 sub4(wi, q);
                 if (e.slot < 0) {   // the row's only contribution of this window: applied here (apply_single, svdf_device.h)
-                    store_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k, apply_single(q, wi, S.contrib_bf16 != 0));
+                    io::store(P.W, P.item_off + e.idx, pitch, L, k, apply_single(q, wi, S.contrib_bf16 != 0));
                     if (L == 0) P.bias[P.item_off + e.idx] = apply_single(bi, nbi - bi, false);
                 } else {
-                    store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)e.slot, pitch, L, k, wi);
+                    cio::store(S.contrib, S.contrib_bf16, (size_t)e.slot, pitch, L, k, wi);
                     if (L == 0) S.cbias[e.slot] = nbi - bi;
                 }
             }
@@ -146,25 +150,25 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 for (; c < c1 && S.ient[c].pad == j; c++) {
                     const WinEnt ch = S.ient[c];
                     if (HOT && ch.slot < -1) {   // a hot child (its slot travels as -2 - slot: ient.pad is taken by the parent's position)
-                        store_contrib<LPI>(S.contrib, 0, (size_t)(-2 - ch.slot), pitch, L, k, p);
+                        cio::store(S.contrib, 0, (size_t)(-2 - ch.slot), pitch, L, k, p);
                         if (L == 0) S.cbias[-2 - ch.slot] = bu;
                         continue;
                     }
                     const float si = lr * err * ch.val * ival;
                     const size_t row = (size_t)P.item_off + ch.idx;
-                    const float4 q = load_row<LPI>(P.W, row, pitch, L, k);
+                    const R q = io::load(P.W, row, pitch, L, k);
                     const float bi = P.bias[row];
-                    float4 wi = q;
+                    R wi = q;
                     axpy4(wi, tu, si);
                     float nbi = bi + si;
                     reg_row<LPI>(P, wi, get_wd(P.i_rng, ch.idx, P.wd_item), true, L);
                     nbi = nbi * (1.0f - lr * P.wd_item_bias);
                     sub4(wi, q);
                     if (ch.slot < 0) {   // the row's only contribution of this window
-                        store_row<LPI>(P.W, row, pitch, L, k, apply_single(q, wi, false));
+                        io::store(P.W, row, pitch, L, k, apply_single(q, wi, false));
                         if (L == 0) P.bias[row] = apply_single(bi, nbi - bi, false);
                     } else {
-                        store_contrib<LPI>(S.contrib, 0, (size_t)ch.slot, pitch, L, k, wi);
+                        cio::store(S.contrib, 0, (size_t)ch.slot, pitch, L, k, wi);
                         if (L == 0) S.cbias[ch.slot] = nbi - bi;
                     }
                 }
@@ -173,28 +177,28 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 const WinEnt e = S.uent[j];
                 if (HOT && e.pad) {   // a hot row of this window (ordered sub-steps, k_wunit_apply_shared): the slot takes what only this walk knows --
                                // the private user's row and bias as they are before this data row's update
-                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
+                    cio::store(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
                     if (L == 0) S.cbias[e.slot] = bu;
                     if (FB) {   // ... and the span's tmp_ufeedback / tmp_ufeedback_bias likewise, in the record's row of the second plane (pad = 1 + record)
-                        store_contrib<LPI>(S.hfb, 0, (size_t)(e.pad - 1), pitch, L, k, pp.tmp_fb);
+                        cio::store(S.hfb, 0, (size_t)(e.pad - 1), pitch, L, k, pp.tmp_fb);
                         if (L == 0) S.hfbb[e.pad - 1] = pp.tmp_bias;
                     }
                     continue;
                 }
                 const float ss = lr * err * e.val;
                 const size_t row = srow0 + e.idx;
-                const float4 w = load_row<LPI>(P.W, row, pitch, L, k);
-                float4 ws = w;
+                const R w = io::load(P.W, row, pitch, L, k);
+                R ws = w;
                 axpy4(ws, ti, ss);
                 reg_row<LPI>(P, ws, get_wd(P.u_rng, S.shared_from + e.idx, P.wd_user), false, L);
                 sub4(ws, w);
                 float cb = 0.0f, b = 0.0f;
                 if (ub) { b = P.bias[row]; float nb = b + ss; nb = nb * (1.0f - lr * P.wd_user_bias); cb = nb - b; }
                 if (e.slot < 0) {   // the row's only contribution of this window
-                    store_row<LPI>(P.W, row, pitch, L, k, apply_single(w, ws, false));
+                    io::store(P.W, row, pitch, L, k, apply_single(w, ws, false));
                     if (ub && L == 0) P.bias[row] = apply_single(b, cb, false);
                 } else {
-                    store_contrib<LPI>(S.contrib, 0, (size_t)e.slot, pitch, L, k, ws);
+                    cio::store(S.contrib, 0, (size_t)e.slot, pitch, L, k, ws);
                     if (L == 0) S.cbias[e.slot] = cb;
                 }
             }
@@ -205,25 +209,25 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             if (ub) bu = nbu;
         }
         if (FB && seg.fb_count > 0) {   // update_ufeedback (:539-554) against the window-start feedback rows
-            float4 d = pp.tmp_fb;
+            R d = pp.tmp_fb;
             sub4(d, pp.old_fb);
             float db = pp.tmp_bias - pp.old_bias;
             const float inv = 1.0f / pp.norm;
             scale4(d, inv);
             db = db * inv;
             if (S.fbrec) {   // deferred scatter: the segment's delta; k_wunit_sum forms (w + d val) - w against the rows it updates
-                if (!(LPI * 4 > k && L * 4 >= k)) *reinterpret_cast<float4 *>(S.dvec + (size_t)(un.seg_begin + sg) * pitch + (size_t)L * 4) = d;
+                io::store(S.dvec, (size_t)(un.seg_begin + sg), pitch, L, k, d);   // (raw float4 chunks at L * 4, like a model row)
                 if (L == 0) S.dbias[un.seg_begin + sg] = db;
             } else
             for (int j = seg.fb_begin; j < seg.fb_begin + seg.fb_count; j++) {
                 const WinEnt f = S.fbent[j];
                 const unsigned row = P.fb_off + f.idx;
-                const float4 w = load_row<LPI>(P.W, row, pitch, L, k);
-                float4 w2 = w;
+                const R w = io::load(P.W, row, pitch, L, k);
+                R w2 = w;
                 axpy4(w2, d, f.val);
                 sub4(w2, w);
-                if (f.slot < 0) store_row<LPI>(P.W, row, pitch, L, k, apply_single(w, w2, S.contrib_bf16 != 0));
-                else store_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)f.slot, pitch, L, k, w2);
+                if (f.slot < 0) io::store(P.W, row, pitch, L, k, apply_single(w, w2, S.contrib_bf16 != 0));
+                else cio::store(S.contrib, S.contrib_bf16, (size_t)f.slot, pitch, L, k, w2);
                 if (L == 0) {
                     const float b = (ub || f.slot < 0) ? P.bias[row] : 0.0f;
                     float cb = 0.0f;
@@ -234,7 +238,7 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
             }
         }
     }
-    store_row<LPI>(P.W, ur, pitch, L, k, p);
+    io::store(P.W, ur, pitch, L, k, p);
     if (ub && L == 0) P.bias[ur] = bu;
 }
 
@@ -500,9 +504,12 @@ __global__ __launch_bounds__(256) void k_wunit_fast(const DevParams P, const WUn
 //   else:  the wire buffer of the exchange, dst = [T rows of `pitch` | T biases | nglobal global biases] (the packed layout of
 //          Engine::delta_ranges for the whole item range), fp32 or fp16.
 // The global biases' sums (gptr over gcontrib) are taken by the same launch, one thread per global id.
-template <int LPI, bool HALF, bool LOCAL, bool HOT = false>   // HOT: the touched list may hold hot shared user rows / hot item rows (in-place sums only)
+// R: the row type -- float4, or WideRow<2..4> at LPI = 64 for the in-place sums of wide rows (LOCAL, no hot rows): a wave per target
+template <int LPI, bool HALF, bool LOCAL, bool HOT = false, typename R = float4>   // HOT: the touched list may hold hot shared user rows / hot item rows (in-place sums only)
 __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float *W, float *bias, float *g_bias, unsigned fb_off, unsigned item_off,
                                                    unsigned user_off, int pitch, int k, void *dst) {
+    static_assert(LOCAL || row_traits<R>::VPL == 1, "the wire buffer builds are for float4 rows");
+    using io = row_io<LPI, R>;
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
     const int L = lane & (LPI - 1);
@@ -527,42 +534,41 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
         const int b = pb, e = pe;
         if (i + stride < N) request(i + stride);
         if (LOCAL && b == e) continue;
-        const bool owns = !(LPI * 4 > k && L * 4 >= k);
         if (HOT && LOCAL && e < 0) {   // a hot shared user row or item row (WinTouched): k_wunit_apply_hot left the row and bias it ends the window with in slot b
             const long ts = t - S.nfb_rows - S.nitem_rows;
             const size_t row = ts < 0 ? (size_t)item_off + (size_t)(t - S.nfb_rows) : (size_t)user_off + S.shared_from + (size_t)ts;
-            if (owns) *reinterpret_cast<float4 *>(W + row * pitch + (size_t)L * 4) = *reinterpret_cast<const float4 *>(S.contrib + (size_t)b * pitch + (size_t)L * 4);
+            io::store(W, row, pitch, L, k, io::load(S.contrib, (size_t)b, pitch, L, k));
             if (L == 0 && (ts < 0 || S.user_bias)) bias[row] = S.cbias[b];
             continue;
         }
-        float4 acc = f4zero();
+        R acc = row_traits<R>::zero();
         float accb = 0.0f;
         if (S.fbrec && t < S.nfb_rows) {
             // deferred feedback scatter: slot s names a segment and the entry's value; the contribution is what the unit's walk would have stored --
             // (w + d val) - w against the window-start row, rounded like a stored contribution row -- and the sum runs in slot (= file) order
             const size_t row = (size_t)fb_off + (size_t)t;
-            const float4 w = owns ? *reinterpret_cast<const float4 *>(W + row * pitch + (size_t)L * 4) : f4zero();
+            const R w = io::load(W, row, pitch, L, k);
             const float bw = S.user_bias ? bias[row] : 0.0f;
             const bool bf = S.contrib_bf16 != 0;
             constexpr int DB = 4;   // records / deltas requested together (a feedback row of the configs[3] windows meets 1.5 contributions on average)
             for (int s0 = b; s0 < e; s0 += DB) {
                 WinFbRec r[DB];
-                float4 d[DB];
+                R d[DB];
                 float dbv[DB];
 #pragma unroll
                 for (int q = 0; q < DB; q++) r[q] = S.fbrec[min(s0 + q, e - 1)];
 #pragma unroll
                 for (int q = 0; q < DB; q++) {
-                    d[q] = owns ? *reinterpret_cast<const float4 *>(S.dvec + (size_t)r[q].seg * pitch + (size_t)L * 4) : f4zero();
+                    d[q] = io::load(S.dvec, (size_t)r[q].seg, pitch, L, k);
                     dbv[q] = S.dbias[r[q].seg];
                 }
 #pragma unroll
                 for (int q = 0; q < DB; q++) {
                     if (s0 + q < e) {
-                        float4 w2 = w;
+                        R w2 = w;
                         axpy4(w2, d[q], r[q].val);
                         sub4(w2, w);
-                        add_rows(acc, make_float4(contrib_as_stored(w2.x, bf), contrib_as_stored(w2.y, bf), contrib_as_stored(w2.z, bf), contrib_as_stored(w2.w, bf)));
+                        add_rows(acc, contrib_as_stored(w2, bf));
                         float cb = 0.0f;
                         if (S.user_bias) { const float b2 = bw + dbv[q] * r[q].val; cb = b2 - bw; }
                         accb = accb + cb;
@@ -571,33 +577,30 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
             }
         } else if (S.contrib_bf16) sum_contrib_slots<LPI, true, (LOCAL ? 4 : 8)>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
         else sum_contrib_slots<LPI, false, (LOCAL ? 4 : 8)>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
-        if (LOCAL) {
+        if constexpr (LOCAL) {
             const long ti = t - S.nfb_rows, ts = ti - S.nitem_rows;
             const size_t row = t < S.nfb_rows ? (size_t)fb_off + (size_t)t
                              : ts < 0 ? (size_t)item_off + (size_t)ti : (size_t)user_off + S.shared_from + (size_t)ts;
-            if (owns) {
-                float4 *w = reinterpret_cast<float4 *>(W + row * pitch + (size_t)L * 4);
-                float4 c = *w;
-                c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-                *w = c;
-            }
+            R c = io::load(W, row, pitch, L, k);
+            add_rows(c, acc);
+            io::store(W, row, pitch, L, k, c);
             if (L == 0 && (ts < 0 || S.user_bias)) bias[row] = bias[row] + accb;
-            continue;
-        }
-        if (owns) {
-            const size_t pos = (size_t)t * pitch + (size_t)L * 4;
-            if (HALF) {
-                __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
-                h[0] = __halves2half2(__float2half_rn(acc.x), __float2half_rn(acc.y));
-                h[1] = __halves2half2(__float2half_rn(acc.z), __float2half_rn(acc.w));
-            } else {
-                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc;
+        } else {
+            if (!(LPI * 4 > k && L * 4 >= k)) {
+                const size_t pos = (size_t)t * pitch + (size_t)L * 4;
+                if (HALF) {
+                    __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
+                    h[0] = __halves2half2(__float2half_rn(acc.x), __float2half_rn(acc.y));
+                    h[1] = __halves2half2(__float2half_rn(acc.z), __float2half_rn(acc.w));
+                } else {
+                    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc;
+                }
             }
-        }
-        if (L == 0) {
-            const size_t pos = (size_t)T * pitch + (size_t)t;
-            if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
-            else reinterpret_cast<float *>(dst)[pos] = accb;
+            if (L == 0) {
+                const size_t pos = (size_t)T * pitch + (size_t)t;
+                if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
+                else reinterpret_cast<float *>(dst)[pos] = accb;
+            }
         }
     }
     const long g0 = T * (long)(pitch + 1);
@@ -798,8 +801,9 @@ __global__ __launch_bounds__(256) void k_wunit_score_columns(const WUnitSchedule
         }
     }
 }
-template <int LPI>
+template <int LPI, typename R = float4>
 __global__ __launch_bounds__(256) void k_wunit_score_prepare(const DevParams P, const WUnitSchedule S, long nseg, float *fbvec, float *fbbias) {
+    using io = row_io<LPI, R>;
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
     const int L = lane & (LPI - 1);
@@ -808,20 +812,21 @@ __global__ __launch_bounds__(256) void k_wunit_score_prepare(const DevParams P, 
     const WinSeg seg = S.segs[q];
     const int pitch = P.pitch, k = P.k;
     const bool ub = P.no_user_bias == 0;
-    float4 tmp_fb = f4zero();
+    R tmp_fb = row_traits<R>::zero();
     float tmp_bias = 0.0f;
     for (int j = seg.fb_begin; j < seg.fb_begin + seg.fb_count; j++) {
         const WinEnt f = S.fbent[j];
         const unsigned row = P.fb_off + f.idx;
-        axpy4(tmp_fb, load_row<LPI>(P.W, row, pitch, L, k), f.val);
+        axpy4(tmp_fb, io::load(P.W, row, pitch, L, k), f.val);
         if (ub) tmp_bias = tmp_bias + P.bias[row] * f.val;
     }
-    if (!(LPI * 4 > k && L * 4 >= k)) *reinterpret_cast<float4 *>(fbvec + (size_t)q * pitch + (size_t)L * 4) = tmp_fb;
+    io::store(fbvec, (size_t)q, pitch, L, k, tmp_fb);   // (slot by slot for a wide row)
     if (L == 0) fbbias[q] = tmp_bias;
 }
-template <int LPI, bool FB>
+template <int LPI, bool FB, typename R = float4>
 __global__ __launch_bounds__(256) void k_wunit_score(const DevParams P, const WUnitSchedule S, const unsigned *user_col, const int *seg_col,
                                                      const float *fbvec, const float *fbbias, long nrow, const int *pos, float *out) {
+    using io = row_io<LPI, R>;
     constexpr int IPW = 64 / LPI;
     const int lane = threadIdx.x & 63;
     const int L = lane & (LPI - 1);
@@ -829,17 +834,16 @@ __global__ __launch_bounds__(256) void k_wunit_score(const DevParams P, const WU
     const long stride = (long)gridDim.x * (blockDim.x >> 6) * IPW;
     const int pitch = P.pitch, k = P.k;
     const bool ub = P.no_user_bias == 0;
-    const bool owns = !(LPI * 4 > k && L * 4 >= k);
     const size_t srow0 = (size_t)P.user_off + S.shared_from;
     for (long r = gidx; r < nrow; r += stride) {
         const unsigned ur = P.user_off + user_col[r];
-        const float4 p = load_row<LPI>(P.W, ur, pitch, L, k);
+        const R p = io::load(P.W, ur, pitch, L, k);
         const float bu = ub ? P.bias[ur] : 0.0f;
-        float4 tmp_fb = f4zero();
+        R tmp_fb = row_traits<R>::zero();
         float tmp_bias = 0.0f;
         if (FB) {
             const int q = seg_col[r];
-            if (owns) tmp_fb = *reinterpret_cast<const float4 *>(fbvec + (size_t)q * pitch + (size_t)L * 4);
+            tmp_fb = io::load(fbvec, (size_t)q, pitch, L, k);
             tmp_bias = fbbias[q];
         }
         int e0, e1, e2;
@@ -866,17 +870,17 @@ __global__ __launch_bounds__(256) void k_wunit_score(const DevParams P, const WU
             for (; c < c1 && S.ient[c].pad == j; c++) { const WinEnt ch = S.ient[c]; bs += (double)(P.bias[P.item_off + ch.idx] * ch.val * e.val); }
         }
         double sum = (double)P.base_score + bs;
-        float4 tu = FB ? tmp_fb : f4zero();
-        for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+        R tu = FB ? tmp_fb : row_traits<R>::zero();
+        for (int j = u0; j < um; j++) { const WinEnt e = S.uent[j]; axpy4(tu, io::load(P.W, srow0 + e.idx, pitch, L, k), e.val); }
         axpy4(tu, p, ua);
-        for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, load_row<LPI>(P.W, srow0 + e.idx, pitch, L, k), e.val); }
-        float4 ti = f4zero();
+        for (int j = um; j < u1; j++) { const WinEnt e = S.uent[j]; axpy4(tu, io::load(P.W, srow0 + e.idx, pitch, L, k), e.val); }
+        R ti = row_traits<R>::zero();
         for (int j = e1, c = c0; j < e2; j++) {
             const WinEnt e = S.ent[j];
-            axpy4(ti, load_row<LPI>(P.W, P.item_off + e.idx, pitch, L, k), e.val);
+            axpy4(ti, io::load(P.W, P.item_off + e.idx, pitch, L, k), e.val);
             for (; c < c1 && S.ient[c].pad == j; c++) {
                 const WinEnt ch = S.ient[c];
-                axpy4(ti, load_row<LPI>(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
+                axpy4(ti, io::load(P.W, P.item_off + ch.idx, pitch, L, k), (float)((double)ch.val * (double)e.val));
             }
         }
         sum += (double)group_dot<LPI>(tu, ti, L, k);
@@ -893,15 +897,15 @@ void launch_wunit_score_prepare(const DevParams &P, const WUnitSchedule &S, long
     const int lpi = lanes_per_instance(P.k);
     const long per_block = 4L * (64 / lpi);
     const long grid = (nseg + per_block - 1) / per_block;
-    SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score_prepare<LPI>), dim3((unsigned)grid), dim3(256), 0, st, P, S, nseg, fbvec, fbbias));
+    SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_wunit_score_prepare<LPI, R>), dim3((unsigned)grid), dim3(256), 0, st, P, S, nseg, fbvec, fbbias));   // (wide rows: a wave per segment)
 }
 void launch_wunit_score(const DevParams &P, const WUnitSchedule &S, bool feedback, const unsigned *user_col, const int *seg_col, const float *fbvec,
                         const float *fbbias, long nrow, const int *pos, float *out, hipStream_t st) {
     if (nrow <= 0) return;
     const int lpi = lanes_per_instance(P.k);
     const int grid = grid_for(nrow, lpi, 256 * 8);
-    if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score<LPI, true>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_score<LPI, false>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
+    if (feedback) { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_wunit_score<LPI, true, R>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
+    else { SVDF_DISPATCH_ROW(P.k, hipLaunchKernelGGL((k_wunit_score<LPI, false, R>), dim3(grid), dim3(256), 0, st, P, S, user_col, seg_col, fbvec, fbbias, nrow, pos, out)); }
 }
 
 bool wunit_fast_applies(const DevParams &P, const WUnitSchedule &S, bool feedback) {
@@ -941,6 +945,13 @@ int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback,
     const int lpi = lanes_per_instance(P.k);
     const long ipw = 64 / lpi;
     const long waves = (S.nunits + ipw - 1) / ipw;
+    if (P.k > 256) {   // wide rows: the general walk, one wave per unit; no fast, slot or wave form (the predicates above say no), no hot rows
+                       // (the sub-step lanes keep one lane group per slot: the host refuses their knobs at these widths)
+        if (S.hot) throw std::runtime_error("k_wunit_walk: ordered sub-steps need num_factor <= 256");
+        if (feedback) { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_wunit_walk<LPI, true, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+        else { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_wunit_walk<LPI, false, false, R>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
+        return 0;
+    }
     if (feedback && S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else if (feedback) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
     else if (S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_walk<LPI, false, true>), dim3((unsigned)waves), dim3(64), 0, st, P, S)); }
@@ -959,6 +970,11 @@ void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int
     // (many short-lived waves beat one resident set walking several targets each: grid cap 2 048 -> 53.5 us, 4 096 -> 45.8, 16 384 -> 43.8 per SVD++ window)
     if (grid > 16384) grid = 16384;
     if (grid < 1) grid = 1;
+    if (P.k > 256) {   // wide rows: the in-place sums of the one-GPU sequence, a wave per target (the N-rank builders stay at 256 factors: no wire buffer of wide rows)
+        if (dst || S.hot) throw std::runtime_error("k_wunit_sum: the wire buffer and ordered sub-steps need num_factor <= 256");
+        SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true, false, R>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr));
+        return;
+    }
     if (!dst && S.hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
     else if (!dst) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, (void *)nullptr)); }
     else if (half) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_wunit_sum<LPI, true, false>), dim3((unsigned)grid), dim3(256), 0, st, S, P.W, P.bias, P.g_bias, P.fb_off, P.item_off, P.user_off, P.pitch, P.k, dst)); }

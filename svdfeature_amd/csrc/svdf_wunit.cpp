@@ -78,13 +78,17 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     return S;
 }
 
-// user_units: the data set would take the user-unit kernels (svdf_k_wunit.hip, svdf_k_wave.hip: one lane group per row, num_factor <= 256); the windows of
-// plain ratings / rank pairs (svdf_k_window.hip) have wide rows and ask with false
+// user_units: the data set would take the user-unit kernels (svdf_k_wunit.hip, svdf_k_wave.hip) on a route that keeps one lane group per row (num_factor
+// <= 256: `auto`, the staged route, the N-rank paths, the rank-buffer route); the windows of plain ratings / rank pairs (svdf_k_window.hip) have wide rows
+// and ask with false.  (The one-GPU sequence under amd:step = minibatch has wide user units too: wunit_wide_ok.)
 bool Engine::wunit_config_ok(bool user_units) const {
     return trainer_ready_ && mtype_.extend_type == 0 && !relaxed() && !lazy_decay() && mp_.common_latent_space == 0 && feat_user_.num_row() == 0 &&
            feat_item_.num_row() == 0 && g_stride_ == 1 && (!user_units || wunit_width_ok()) && (!user_group() || mp_.common_feedback_space == 0);
 }
 bool Engine::wunit_width_ok() const { return mp_.num_factor <= 256; }
+// the one-GPU sequence of user units (wseq_from_csr / wseq_from_blocks): its general walk, in-place sums and scoring kernels have wide rows, a wave
+// per unit / target / row.  Everything else that trains user units asks wunit_width_ok.
+bool Engine::wunit_wide_ok() const { return mp_.num_factor <= max_supported_factor(); }
 void Engine::wunit_check_config(const char *what, bool tables_ok) const {
     check(trainer_ready_, "dataset: init_trainer has not been called");
     check(mtype_.extend_type == 0, "window data sets: the base solvers only (extend_type 0)");
@@ -111,7 +115,16 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
         check(wunit_inplace_ != 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)");
     }
     if (block_sub() > 0) wseq_block_check(what);
-    check(wunit_width_ok(), "window data sets: num_factor <= 256");
+    // width: the one-GPU sequences (amd:step = minibatch) take wide rows through the general walk; the N-rank builders and the sub-step lanes (one lane
+    // group per slot) stay at 256 factors
+    const bool sequence = strcmp(what, "dataset_from_csr") == 0 || strcmp(what, "dataset_from_blocks") == 0;
+    if (sequence && !wunit_width_ok()) {
+        check(wunit_wide_ok(), "window data sets: num_factor <= 1024");
+        check(wseq_shared_sub_ == 0, "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) needs num_factor <= 256 (the lane has no wide rows)");
+        check(wseq_item_sub_ == 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs num_factor <= 256 (the lane has no wide rows)");
+        check(block_sub() == 0, "window data sets: window_block_sub > 0 (ordered sub-steps for hot shared user rows of SVD++ blocks) needs num_factor <= 256 (the lane has no wide rows)");
+    } else
+        check(wunit_width_ok(), "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
     check(!shared_user() || (shared_user_from_ >= 1 && (long)shared_user_from_ <= (long)mp_.num_user), "amd:shared_user_from must be in 1 .. num_user");
 }
