@@ -47,6 +47,11 @@ def _same(t, o, names, what=None):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (name, what)
 
 
+def _binary(labels):
+    labels[:] = (labels > 3).astype(np.float32)
+    assert set(np.unique(labels)) == {0.0, 1.0}
+
+
 def _sequence(conf, data, windows, passes, fmt=0, active=0, extra=(), knobs=()):
     """the one-GPU window sequence of `windows` windows (amd:window in rows), trained `passes` times"""
     t = _trainer(conf, fmt, active, MB + [("amd:window", -(-data.num_row // windows))] + list(extra), knobs)
@@ -73,6 +78,154 @@ def test_rows_with_globals_at_every_wide_width_equal_the_stale_sum_simulation(k,
     conf = _row_conf(k)
     t, _ = _sequence(conf, d, 3, 2)
     _same(t, simulate(conf, d, None, None, 1, 3, 2, minibatch=True)[0].t, ROW_NAMES, k)
+
+
+def _ragged_rows(k, seed, binary=False):
+    """2 000 ragged rows: 0 .. 3 global entries, sometimes a second item entry, user values 1 / 0.5 (tests/test_gpu_wunit._rows_with_globals)"""
+    d = _rows_with_globals(2000, 150, 40, 12, 3, seed, fixed=False)
+    if binary:
+        _binary(d.row_label)
+    return d
+
+
+SIGMOID = (("base_score", "0.5"),)
+RANGES = (("up:wd", "0.1"), ("up:bound", "60"), ("up:wd", "0.002"), ("up:bound", "100000"), ("ip:wd", "0.05"), ("ip:bound", "15"), ("ip:wd", "0.004"),
+          ("ip:bound", "100000"), ("num_regfree_global", "2"), ("gp:wd", "0.1"), ("gp:bound", "5"), ("gp:wd", "0.002"), ("gp:bound", "100"))
+
+
+@pytest.mark.parametrize("k,active,extra", [(515, 1, SIGMOID), (515, 2, SIGMOID), (515, 5, SIGMOID), (515, 7, SIGMOID),
+                                            (515, 0, (("reg_method", "1"),)), (1000, 0, (("reg_method", "2"), ("wd_user", "0.5"), ("wd_item", "0.5"))),
+                                            (515, 0, (("reg_method", "3"),)), (515, 0, (("reg_global", "1"), ("num_regfree_global", "2"))),
+                                            (515, 0, (("user_nonnegative", "1"),)), (515, 0, (("no_user_bias", "1"),)), (515, 0, RANGES),
+                                            (1000, 0, (("reg_method", "2"), ("wd_user", "0.1"), ("wd_item", "0.1")))])
+def test_links_and_regularisers_on_rows_with_globals_at_wide_widths(k, active, extra):
+    """k_wunit_walk<64, false, false, WideRow<3 / 4>> beyond the linear link and L2: the sigmoid links (1, 2, 7) and the smooth hinge (5) on binary
+    labels, L1 on every row (1) and on the user rows alone (3), the projection (2: group_dot over a wide row, at k = 1000), L1 on the global
+    biases with two of them free, the nonnegative clamp, no user bias, split up: / ip: / gp: ranges.  Ragged rows, a second item entry, non-unit
+    user values; 515 = 2 * 256 + 3.  Under the bound 0.5 no row is ever scaled (the squared norms stay near 0.1 at k = 1000: the dot is formed and
+    must stay below the bound); the last case puts the bound at 0.1, inside the rows' norms: in the simulation 46 of the 150 user rows end on it."""
+    d = _ragged_rows(k, 40 + active + len(extra), binary=active != 0)
+    conf = _row_conf(k, extra=extra)
+    t, _ = _sequence(conf, d, 3, 2, active=active)
+    _same(t, simulate(conf, d, None, None, 1, 3, 2, active=active, minibatch=True)[0].t, ROW_NAMES, (k, active, extra))
+
+
+def _simulate_rounds(conf, d, windows, passes):
+    """multi_rank_utils.simulate for one rank with the reference's round protocol around every pass: set_round(p), the pass, finish_round"""
+    from svdfeature_amd.multi_gpu import shard_csr_windows
+    a = multi_rank_utils.OracleShard(multi_rank_utils.make_oracle(conf), minibatch=True)
+    wins = a.make_windows(shard_csr_windows(d, 0, 1, windows))
+    for p in range(passes):
+        a.t.set_round(p)
+        for w in wins:
+            a.delta_begin()
+            a.train(w)
+            a.delta_set(a.delta_get().copy())
+        a.t.finish_round()
+    return a.t
+
+
+def test_the_decayed_learning_rate_reaches_the_wide_walk_between_two_passes():
+    """decay_learning_rate = 1, decay_rate = 0.5: set_round(1) after the first pass halves the rate on both sides (the window sequence honours it:
+    Engine::set_round marks the kernel parameters dirty and the next pass reads them); without the set_round calls the model is another one"""
+    k = 515
+    d = _ragged_rows(k, 77)
+    conf = _row_conf(k, extra=(("decay_learning_rate", "1"), ("decay_rate", "0.5")))
+    t = _trainer(conf, 0, 0, MB + [("amd:window", -(-d.num_row // 3))])
+    ds = t.dataset_from_csr(d)
+    assert ds.kind == 8 and ds.num_batches == 3
+    for p in range(2):
+        t.set_round(p)
+        t.train_dataset(ds)
+        t.finish_round()
+    t.synchronize()
+    _same(t, _simulate_rounds(conf, d, 3, 2), ROW_NAMES)
+    flat = simulate(conf, d, None, None, 1, 3, 2, minibatch=True)[0].t   # no set_round: the rate never decays
+    assert not np.array_equal(flat.view("W_item"), t.view("W_item"))
+
+
+# ------------------------------------------------------------------------------------------------- 1b. contribution counts at the sums' group edges
+EDGE_K = 770
+ROW_COUNTS = (1, 2, 3, 4, 5, 7, 8, 9, 17)   # rows of the window that meet one item / one global id: around the in-place sums' groups of 4 slots
+FB_COUNTS = (1, 3, 4, 5, 8, 9)              # segments of the window whose list names one feedback id: around the deferred sum's groups of 4 records
+
+
+def _edge_rows():
+    """56 rows in one window: item j is met by ROW_COUNTS[j] rows and global id j by ROW_COUNTS[j] rows (items 9 .. 11 and ids 9, 10 by none)"""
+    rng = np.random.default_rng(3)
+    items = rng.permutation(np.repeat(np.arange(len(ROW_COUNTS)), ROW_COUNTS))
+    gids = rng.permutation(np.repeat(np.arange(len(ROW_COUNTS)), ROW_COUNTS))
+    rows = [(float(rng.integers(1, 6)), [(int(g), float(rng.uniform(0.1, 1.0)))], [(int(rng.integers(0, 30)), float(rng.choice([1.0, 0.5])))], [(int(i), 1.0)])
+            for i, g in zip(items, gids)]
+    return CSRData.from_rows(rows)
+
+
+@pytest.mark.parametrize("inplace", [1, 0])
+@pytest.mark.parametrize("contrib", ["fp32", "bf16"])
+def test_item_and_global_rows_met_by_1_to_17_rows_of_one_window(contrib, inplace):
+    """k_wunit_sum in place over WideRow<4> (770 = 3 * 256 + 2): rows with 1 (applied in place under wunit_inplace = 1), 2, 3, 4, 5, 7, 8, 9 and 17
+    contributions, which the sum requests 4 slots at a time -- a short group, a full group, one over, two groups, four groups and one"""
+    d = _edge_rows()
+    ni, ng = 12, 11
+    assert d.num_row == sum(ROW_COUNTS) and np.array_equal(d.row_ptr, np.arange(3 * d.num_row + 1))   # one global, one user, one item entry per row
+    glob_col, item_col = d.feat_index.reshape(-1, 3)[:, 0], d.feat_index.reshape(-1, 3)[:, 2]
+    assert tuple(np.bincount(item_col, minlength=ni)) == ROW_COUNTS + (0, 0, 0) and tuple(np.bincount(glob_col, minlength=ng)) == ROW_COUNTS + (0, 0)
+    conf = _row_conf(EDGE_K, 30, ni, ng)
+    t = _trainer(conf, 0, 0, MB + [("amd:window", d.num_row), ("amd:contrib", contrib)], [("wunit_inplace", inplace)])
+    ds = t.dataset_from_csr(d)
+    assert ds.kind == 8 and ds.num_batches == 1
+    for _ in range(2):
+        t.train_dataset(ds)
+    t.synchronize()
+    multi_rank_utils.CONTRIB_BF16 = contrib == "bf16"
+    try:
+        sim = simulate(conf, d, None, None, 1, 1, 2, minibatch=True)
+    finally:
+        multi_rank_utils.CONTRIB_BF16 = False
+    _same(t, sim[0].t, ROW_NAMES, (contrib, inplace))
+
+
+def _edge_blocks():
+    """10 users in one window, the third as a START / MIDDLE / END span: feedback id j is in the lists of FB_COUNTS[j] segments (ids 6, 7 in none)"""
+    from svdfeature_amd.data import PlusBlock, TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
+    rng = np.random.default_rng(4)
+    blocks = []
+    for b in range(10):
+        fb = np.array([j for j, c in enumerate(FB_COUNTS) if (b - j) % 10 < c], np.uint32)
+        val = np.full(len(fb), 1.0 / np.sqrt(max(len(fb), 1)), np.float32)
+        rows = CSRData.from_rows([(float(rng.integers(1, 6)), [], [(b, 1.0)], [(int(rng.integers(0, 30)), 1.0)]) for _ in range(3 + b % 3)])
+        if b == 2:
+            e = np.zeros(0, np.uint32), np.zeros(0, np.float32)
+            blocks += [PlusBlock(fb, val, rows.slice_rows(0, 1), TAG_START), PlusBlock(e[0], e[1], rows.slice_rows(1, rows.num_row - 1), TAG_MIDDLE),
+                       PlusBlock(fb, val, rows.slice_rows(rows.num_row - 1, rows.num_row), TAG_END)]
+        else:
+            blocks.append(PlusBlock(fb, val, rows, TAG_DEFAULT))
+    segments = [b for b in blocks if b.extend_tag in (TAG_DEFAULT, TAG_START)]
+    return blocks, np.bincount(np.concatenate([b.index_ufeedback for b in segments]).astype(np.int64), minlength=8)
+
+
+@pytest.mark.parametrize("defer", [1, 0])
+@pytest.mark.parametrize("inplace", [1, 0])
+@pytest.mark.parametrize("contrib", ["fp32", "bf16"])
+def test_feedback_rows_named_by_1_to_9_segments_of_one_window(contrib, inplace, defer):
+    """the deferred feedback sum (wunit_defer_fb = 1: k_wunit_sum forms the rows' contributions from the segments' deltas, DB = 4 records at a time)
+    and the same rows through slots (0) over WideRow<4>: feedback ids named by 1, 3, 4, 5, 8 and 9 segments"""
+    blocks, counts = _edge_blocks()
+    assert tuple(counts) == FB_COUNTS + (0, 0) and len(blocks) == 12
+    ba = BlockArrays.from_blocks(blocks)
+    conf = cases.conf_with(cases.BASICMF_CONF, num_user=10, num_item=30, num_factor=EDGE_K, num_ufeedback=8) + SVDPP_EXTRA
+    t = _trainer(conf, 1, 0, MB + [("amd:window", ba.num_row), ("amd:contrib", contrib)], [("wunit_inplace", inplace), ("wunit_defer_fb", defer)])
+    ds = t.dataset_from_blocks(ba)
+    assert ds.kind == 8 and ds.num_batches == 1
+    for _ in range(2):
+        t.train_dataset(ds)
+    t.synchronize()
+    multi_rank_utils.CONTRIB_BF16 = contrib == "bf16"
+    try:
+        sim = simulate(conf, ba, None, None, 1, 1, 2, fmt=1, minibatch=True)
+    finally:
+        multi_rank_utils.CONTRIB_BF16 = False
+    _same(t, sim[0].t, SVDPP_NAMES, (contrib, inplace, defer))
 
 
 # ------------------------------------------------------------------------------------------------- 2. SVD++ blocks
@@ -170,8 +323,9 @@ def test_blocks_with_shared_ids_at_wide_widths_equal_the_checker(k, long_unit, f
 
 
 # ------------------------------------------------------------------------------------------------- 6. bf16 slots
-@pytest.mark.parametrize("shape,k", [("blocks", 320), ("rows", 512)])
+@pytest.mark.parametrize("shape,k", [("blocks", 320), ("rows", 512), ("blocks", 770), ("rows", 1023), ("blocks", 1024), ("rows", 515)])
 def test_bf16_contribution_rows_at_wide_widths_equal_the_simulation_with_the_same_rounding(shape, k):
+    """contrib_io<64, WideRow<2 / 3 / 4>> and the bf16 branch of the deferred feedback sum; 770, 1023 and 515 end in a ragged float4 (k % 4 = 2, 3, 3)"""
     if shape == "blocks":
         data = BlockArrays.from_blocks(cases.user_blocks(130, 200, 80, 80, seed=k, max_rows=12, max_fb=8, split_every=5))
         conf, fmt, names = _block_conf(k, 200, 80), 1, SVDPP_NAMES
@@ -190,14 +344,12 @@ def test_bf16_contribution_rows_at_wide_widths_equal_the_simulation_with_the_sam
 
 
 # ------------------------------------------------------------------------------------------------- 7. in-place single applies
-@pytest.mark.parametrize("contrib", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", ["blocks", "rows"])
-def test_single_contributions_are_applied_in_place_with_the_same_bits_at_a_wide_width(shape, contrib):
-    """many more items than rows per window, so most contributions are single (no slot: apply_single on a wide row): the default == every
-    contribution through a slot (wunit_inplace = 0) == feedback contributions written as rows by the walk (wunit_defer_fb = 0) == the simulation"""
-    k, windows = 320, 4
+def _single_applies(shape, contrib, k):
+    """the four knob combinations and the simulation; above 320 the blocks' catalogue is 1 400 items, which keeps the two item-side matrices near
+    11 MB at about 350 rows per window"""
+    windows = 4
     if shape == "blocks":
-        nu, ni = 150, 2000
+        nu, ni = 150, 2000 if k == 320 else 1400
         data = BlockArrays.from_blocks(cases.user_blocks(140, nu, ni, ni, seed=k, max_rows=20, max_fb=16, split_every=6))
         conf, fmt, names = _block_conf(k, nu, ni), 1, SVDPP_NAMES
     else:
@@ -217,6 +369,22 @@ def test_single_contributions_are_applied_in_place_with_the_same_bits_at_a_wide_
         for other in got[1:]:
             assert np.array_equal(got[0][name].view(np.uint32), other[name].view(np.uint32)), name
         assert np.array_equal(got[0][name].view(np.uint32), sim[0].t.view(name).view(np.uint32)), name
+
+
+@pytest.mark.parametrize("contrib", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", ["blocks", "rows"])
+def test_single_contributions_are_applied_in_place_with_the_same_bits_at_a_wide_width(shape, contrib):
+    """many more items than rows per window, so most contributions are single (no slot: apply_single on a wide row): the default == every
+    contribution through a slot (wunit_inplace = 0) == feedback contributions written as rows by the walk (wunit_defer_fb = 0) == the simulation"""
+    _single_applies(shape, contrib, 320)
+
+
+@pytest.mark.parametrize("contrib", ["fp32", "bf16"])
+@pytest.mark.parametrize("shape", ["blocks", "rows"])
+@pytest.mark.parametrize("k", [700, 1022])
+def test_single_contributions_are_applied_in_place_with_three_and_four_float4_per_lane(k, shape, contrib):
+    """the same equalities over WideRow<3> (700) and WideRow<4> with a ragged last float4 (1022, k % 4 = 2)"""
+    _single_applies(shape, contrib, k)
 
 
 # ------------------------------------------------------------------------------------------------- 8. scoring
@@ -264,6 +432,54 @@ def test_scoring_a_wide_block_sequence(defer):
     conf = cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k, num_ufeedback=ni, wd_ufeedback="0.004", ufeedback_init_sigma="0.01")
     ba = BlockArrays.from_blocks(blocks)
     t = _trainer(conf, 1, 0, MB + [("amd:window", 150)], [("wunit_defer_fb", defer)])
+    ds = t.dataset_from_blocks(ba)
+    assert ds.kind == 8 and ds.num_batches >= 3
+    score = lambda: np.concatenate([t.predict_block(b) for b in blocks])
+    before = _check_scores(t, ds, score(), ba.row_label, SVDPP_NAMES)
+    for _ in range(2):
+        t.train_dataset(ds)
+    after = _check_scores(t, ds, score(), ba.row_label, SVDPP_NAMES)
+    assert not np.array_equal(before, after)
+
+
+@pytest.mark.parametrize("variant,k,active,extra", [("a", 768, 0, ()), ("b", 515, 0, ()), ("c", 1023, 0, ()), ("d", 1024, 0, ()),
+                                                    ("b", 900, 2, (("base_score", "0.5"), ("no_user_bias", "1")))])
+def test_scoring_wide_csr_sequences_of_every_layout_with_three_and_four_float4_per_lane(tmp_path, variant, k, active, extra):
+    """k_wunit_score<false, WideRow<3 / 4>> on the four csr layouts of tests/test_gpu_window_scoring.py: the fixed layout (estride) at 768, ragged rows
+    with two item entries and non-unit values (rptr) at 515 (k % 4 = 3), shared user entries at 1023 (k % 4 = 3), both side tables at 1024; the
+    sigmoid link on binary labels without a user bias at 900.  Scored before and after two passes against predict_batch of the same trainer."""
+    import test_gpu_window_scoring as ws
+    keys, more, d = ws._csr_case(variant, tmp_path, seed=k)
+    if active:
+        _binary(d.row_label)
+    conf = cases.conf_with(cases.BASICMF_CONF, num_user=ws.NP_ + ws.NS_, num_item=ws.NT_ + ws.NA_, num_global=ws.NG_, num_factor=k, wd_global="0.002",
+                           learning_rate="0.01") + keys + list(extra)
+    t = _trainer(conf, 0, active, MB + [("amd:window", 170)] + more)
+    ds = t.dataset_from_csr(d)
+    assert ds.kind == 8 and 3 <= ds.num_batches <= 4
+    before = _check_scores(t, ds, t.predict_batch(d), d.row_label, ROW_NAMES)
+    for _ in range(2):
+        t.train_dataset(ds)
+    after = _check_scores(t, ds, t.predict_batch(d), d.row_label, ROW_NAMES)
+    assert not np.array_equal(before, after)
+
+
+@pytest.mark.parametrize("k,defer,active,extra", [(700, 0, 0, ()), (700, 1, 0, ()), (1000, 0, 0, ()), (1000, 1, 0, ()),
+                                                  (770, 1, 2, (("base_score", "0.5"), ("no_user_bias", "1")))])
+def test_scoring_wide_block_sequences_with_three_and_four_float4_per_lane(k, defer, active, extra):
+    """k_wunit_score_prepare and k_wunit_score<true, WideRow<3 / 4>>: START / MIDDLE / END spans, users without feedback and the feedback list of 70
+    entries (more than one 64-record block), against predict_block of the same trainer; the sigmoid link without a user bias at 770 (k % 4 = 2)"""
+    import test_gpu_window_scoring as ws
+    nu, ni, blocks = ws._svdpp_blocks(seed=k + defer)
+    assert any(b.num_ufeedback > 64 for b in blocks) and any(b.num_ufeedback == 0 for b in blocks)
+    if active:
+        for b in blocks:
+            b.data.row_label[:] = (b.data.row_label > 3).astype(np.float32)
+    conf = cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k, num_ufeedback=ni, wd_ufeedback="0.004",
+                           ufeedback_init_sigma="0.01") + list(extra)
+    ba = BlockArrays.from_blocks(blocks)
+    assert not active or set(np.unique(ba.row_label)) == {0.0, 1.0}
+    t = _trainer(conf, 1, active, MB + [("amd:window", 150)], [("wunit_defer_fb", defer)])
     ds = t.dataset_from_blocks(ba)
     assert ds.kind == 8 and ds.num_batches >= 3
     score = lambda: np.concatenate([t.predict_block(b) for b in blocks])
@@ -340,6 +556,52 @@ def test_the_window_step_keeps_the_accuracy_contract_on_rows_with_globals_at_a_w
         for _ in range(3):
             t.train_dataset(ds)
         p = t.predict_batch(test)
+        assert np.isfinite(p).all()
+        out.append((float(np.sqrt(np.mean((p.astype(np.float64) - tl) ** 2))), ds.num_batches, ds.kind))
+    print("held-out RMSE: exact %.6f window %.6f difference %.3g (%d windows)" % (out[0][0], out[1][0], out[1][0] - out[0][0], out[1][1]))
+    assert out[0][2] != 8 and out[1][2] == 8 and out[1][1] == 40
+    assert abs(out[1][0] - out[0][0]) <= 1e-4, out
+
+
+def svdpp_contract_input(nu=4000, ni=800, n=60000, held=6000, k=320):
+    """planted ratings grouped into one SVD++ block per user, the users in a random order; a user's feedback list is the set of items of its training
+    rows at value n^-1/2; the held-out rows are grouped the same way and carry the training lists.  (conf, training blocks, test blocks, test labels)"""
+    from svdfeature_amd.data import PlusBlock, TAG_DEFAULT
+    u, i, r = cases.planted_triples(n + held, nu, ni, seed=23)
+    order = np.argsort(u[:n], kind="stable")
+    lo = np.searchsorted(u[:n][order], np.arange(nu + 1))
+    horder = n + np.argsort(u[n:], kind="stable")
+    hlo = np.searchsorted(u[horder], np.arange(nu + 1))
+    train, test, labels = [], [], []
+    for uid in np.random.default_rng(9).permutation(nu):
+        m, h = order[lo[uid]:lo[uid + 1]], horder[hlo[uid]:hlo[uid + 1]]
+        fb = np.unique(i[m]).astype(np.uint32)
+        val = np.full(len(fb), 1.0 / np.sqrt(max(len(fb), 1)), np.float32)
+        if len(m):
+            train.append(PlusBlock(fb, val, CSRData.from_triples(u[m], i[m], r[m]), TAG_DEFAULT))
+        if len(h):
+            test.append(PlusBlock(fb, val, CSRData.from_triples(u[h], i[h], r[h]), TAG_DEFAULT))
+            labels.append(r[h])
+    conf = cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k, num_ufeedback=ni) + SVDPP_EXTRA
+    return conf, train, test, np.concatenate(labels).astype(np.float64)
+
+
+def test_the_window_step_keeps_the_accuracy_contract_on_svdpp_blocks_at_a_wide_width():
+    """60 000 planted ratings of 4 000 users on 800 items as one SVD++ block per user (feedback list: the user's training items at n^-1/2), k = 320,
+    windows of 1 500 rows (40 windows, cut at block positions), three passes: held-out RMSE on 6 000 further rows, scored with predict_block under
+    the training lists, within 1e-4 of the exact pass of the same build.  The checkers alone on the CPU (oracle update_block against
+    simulate(fmt = 1, minibatch)) give exact 0.723293 and window 0.723345 on this input, a difference of 5.2e-5 (8.3e-5 at 20 windows, 1.6e-5 at
+    60); both engine paths equal their checkers bit for bit, so the figures printed here are those."""
+    conf, train, test, tl = svdpp_contract_input()
+    ba = BlockArrays.from_blocks(train)
+    assert ba.num_row == 60000 and len(tl) == 6000
+    out = []
+    for extra in ([], MB + [("amd:window", 1500)]):
+        t = _trainer(conf, 1, 0, extra)
+        ds = t.dataset_from_blocks(ba)
+        for _ in range(3):
+            t.train_dataset(ds)
+        p = np.concatenate([t.predict_block(b) for b in test])
         assert np.isfinite(p).all()
         out.append((float(np.sqrt(np.mean((p.astype(np.float64) - tl) ** 2))), ds.num_batches, ds.kind))
     print("held-out RMSE: exact %.6f window %.6f difference %.3g (%d windows)" % (out[0][0], out[1][0], out[1][0] - out[0][0], out[1][1]))
