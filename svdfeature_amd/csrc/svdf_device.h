@@ -626,6 +626,42 @@ template <int V> __device__ __forceinline__ void lds_get_row(const float4 *base,
     for (int v = 0; v < V; v++) r.v[v] = base[L + 64 * v];
 }
 
+// ---- the wire buffer of a window's exchange: [ nrows rows of `pitch` | nrows biases | global words ], fp32 or fp16 (round to nearest even, once per
+// window).  wire_put writes the finished sum of row `it` (k_window_items, k_window_items_wide, k_wunit_sum); wire_zero_tail the n global words behind
+// the rows of a data set that carries no global entry, the whole grid striding over them.
+__device__ __forceinline__ const float4 &row_chunk(const float4 &r, int) { return r; }
+template <int V> __device__ __forceinline__ const float4 &row_chunk(const WideRow<V> &r, int v) { return r.v[v]; }
+template <int LPI, bool HALF, typename R>
+__device__ __forceinline__ void wire_put(void *dst, long it, long nrows, int pitch, int L, int k, const R &acc, float accb) {
+    constexpr int VPL = row_traits<R>::VPL;
+#pragma unroll
+    for (int v = 0; v < VPL; v++) {
+        const int c = L + 64 * v;   // the lane's v-th chunk of the row
+        if ((VPL > 1 || LPI * 4 > k) && c * 4 >= k) continue;
+        const size_t pos = (size_t)it * pitch + (size_t)c * 4;
+        const float4 &a = row_chunk(acc, v);
+        if (HALF) {
+            __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
+            h[0] = __halves2half2(__float2half_rn(a.x), __float2half_rn(a.y));
+            h[1] = __halves2half2(__float2half_rn(a.z), __float2half_rn(a.w));
+        } else {
+            *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = a;
+        }
+    }
+    if (L == 0) {
+        const size_t pos = (size_t)nrows * pitch + (size_t)it;
+        if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
+        else reinterpret_cast<float *>(dst)[pos] = accb;
+    }
+}
+template <bool HALF>
+__device__ __forceinline__ void wire_zero_tail(void *dst, long g0, long n) {
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (long)gridDim.x * blockDim.x) {
+        if (HALF) reinterpret_cast<__half *>(dst)[g0 + j] = __float2half_rn(0.0f);
+        else reinterpret_cast<float *>(dst)[g0 + j] = 0.0f;
+    }
+}
+
 
 // ---- launch helpers (host side)
 static inline int grid_for(long groups, int lpi, int cap) {

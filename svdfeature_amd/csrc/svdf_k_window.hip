@@ -17,6 +17,63 @@
 
 namespace svdf {
 
+// ------------------------------------------------------------------------------------------------- item side: what kernels B and B' share
+// A finished sum added to item i's row and bias in place (row i at w_item + i * pitch, bias at i_bias + i): c = c + acc.  A lane that owns no
+// chunk of the row (row_io's guard) holds acc = 0, forms 0 + 0 and stores nothing.
+template <int LPI, typename R>
+__device__ __forceinline__ void add_sum_in_place(float *w_item, float *i_bias, size_t i, int pitch, int L, int k, const R &acc, float accb) {
+    R c = row_io<LPI, R>::load(w_item, i, pitch, L, k);
+    add_rows(c, acc);
+    row_io<LPI, R>::store(w_item, i, pitch, L, k, c);
+    if (L == 0) i_bias[i] = i_bias[i] + accb;
+}
+// LONG lists (round 5).  The window rule lets a row meet up to 128 updates per window, and on skewed data (Zipf-popular items) the hottest rows do: one
+// lane group adding 128 slots eight at a time is sixteen dependent round trips -- 42 us per window of 13 K ratings, when the users' walk takes 6.  A lane
+// group that meets a list longer than its kernel's hot_min therefore queues it (LDS), and after the scan the WHOLE workgroup (256 threads, every one of
+// them calls this) loads such a list's slots [b, e) side by side into LDS, a chunk at a time (one round trip per 16 - 64 slots), and its first lane
+// group adds them in slot order: acc = ((0 + c_1) + c_2) + ... as sum_contrib_slots does, the same additions in the same order, hence the same bits.
+// acc / accb mean something in lane group 0 only.
+template <int LPI> constexpr int WIN_LIST_CHUNK = LPI >= 64 ? 16 : (LPI >= 32 ? 32 : 64);   // slots staged at a time: at most 16 KB of LDS whatever the width
+template <int LPI>
+__device__ __forceinline__ void sum_list_by_workgroup(const WindowSchedule &S, int b, int e, int pitch, int k, float4 *stage, float *stage_b, float4 &acc, float &accb) {
+    constexpr int G = 256 / LPI, CHUNK = WIN_LIST_CHUNK<LPI>;
+    const int L = threadIdx.x & (LPI - 1);
+    const int grp = threadIdx.x / LPI;
+    acc = f4zero();
+    accb = 0.0f;
+    for (int c0 = b; c0 < e; c0 += CHUNK) {
+        const int cn = min(CHUNK, e - c0);
+        // every lane group requests its share of the chunk's slots at once (CHUNK / G per group), then parks them in LDS
+        constexpr int PER = (CHUNK + G - 1) / G;
+        float4 v[PER];
+        float vb[PER];
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int sl = grp + r * G;
+            const bool in = sl < cn;
+            v[r] = in ? load_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)(c0 + sl), pitch, L, k) : f4zero();
+            vb[r] = (in && L == 0) ? S.cbias[c0 + sl] : 0.0f;
+        }
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int sl = grp + r * G;
+            if (sl < cn) { stage[sl * LPI + L] = v[r]; if (L == 0) stage_b[sl] = vb[r]; }
+        }
+        __syncthreads();
+        if (grp == 0) {   // eight LDS reads requested ahead of their (ordered) additions
+            for (int sl = 0; sl < cn; sl += 8) {
+                float4 t[8];
+                float tb[8];
+#pragma unroll
+                for (int q = 0; q < 8; q++) { const int x = min(sl + q, cn - 1); t[q] = stage[x * LPI + L]; tb[q] = stage_b[x]; }
+#pragma unroll
+                for (int q = 0; q < 8; q++) if (sl + q < cn) { add_rows(acc, t[q]); accb = accb + tb[q]; }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // One user's instances of a window: entries [begin, begin + count) of the user-grouped columns.
 // Records are in LAUNCH order: users sorted by count (descending), so the lane groups of a wave run the same number of iterations.
 
@@ -335,19 +392,16 @@ __device__ __forceinline__ float *addto_slot(const DeltaRanges &R, long j) {
 // Item i's contributions sit in slots [iptr[i], iptr[i + 1]), in file order.  One lane group per item sums them in that order
 // (acc = 0 + c_1 + c_2 ..., four rows requested ahead) and writes the item's row and bias of the wire buffer:
 // dst = [ (hi - lo) rows of `pitch` | (hi - lo) item biases | nglobal zeros ] for the item range [lo, hi) of the active
-// exchange partition (svdf_item_delta_select) -- the packed layout of k_delta_pack.
+// exchange partition (svdf_item_delta_select) -- the packed layout of k_delta_pack (wire_put, wire_zero_tail).
 // LOCAL (stratified schedule): the rank owns the item block exclusively, so there is no sum over ranks and the
-// per-item sum is added to the model in place: dst = W_item's first row (row i at dst + i * pitch), dbias = i_bias; fp32, no wire buffer.
-// LONG lists (round 5).  The window rule lets a row meet up to 128 updates per window, and on skewed data (Zipf-popular items) the hottest rows do: one
-// lane group adding 128 slots eight at a time is sixteen dependent round trips -- 42 us per window of 13 K ratings, when the users' walk takes 6.  A lane
-// group that meets a list longer than HOT_MIN therefore queues it (LDS), and after the scan the WHOLE workgroup loads such a list's slots side by side into
-// LDS (one round trip per 16 - 64 slots) and its first lane group adds them in slot order: the same additions in the same order, hence the same bits.
+// per-item sum is added to the model in place (add_sum_in_place): dst = W_item's first row, dbias = i_bias; fp32, no wire buffer.
+// HOT: a list longer than hot_min is queued and summed by the whole workgroup after the scan (sum_list_by_workgroup).
 #define SVDF_WIN_HOT_MIN 16
 #define SVDF_WIN_HOT_QUEUE 32
 template <int LPI, bool HALF, bool LOCAL, bool HOT>   // HOT: the window may hold lists that are long relative to its mean (the launcher decides: dense windows keep the plain form)
 __global__ __launch_bounds__(256) void k_window_items(const WindowSchedule S, int pitch, int k, long lo, long hi, long nglobal, void *dst, float *dbias, int hot_min) {
-    constexpr int IPW = 64 / LPI, G = 256 / LPI;
-    constexpr int CHUNK = LPI >= 64 ? 16 : (LPI >= 32 ? 32 : 64);   // slots staged at a time: at most 16 KB of LDS whatever the width
+    constexpr int IPW = 64 / LPI;
+    constexpr int CHUNK = WIN_LIST_CHUNK<LPI>;
     __shared__ int hq_it[HOT ? SVDF_WIN_HOT_QUEUE : 1], hq_b[HOT ? SVDF_WIN_HOT_QUEUE : 1], hq_e[HOT ? SVDF_WIN_HOT_QUEUE : 1];
     __shared__ int hq_n;
     __shared__ float4 stage[HOT ? CHUNK * LPI : 1];
@@ -358,40 +412,16 @@ __global__ __launch_bounds__(256) void k_window_items(const WindowSchedule S, in
     const long stride = (long)gridDim.x * (blockDim.x >> 6) * IPW;
     const long first = ((long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * IPW + lane / LPI;
     const long nitem = hi - lo;
-    const bool owns = !(LPI * 4 > k && L * 4 >= k);
     if constexpr (HOT) {
         if (threadIdx.x == 0) hq_n = 0;
         __syncthreads();
     }
-    // what becomes of a finished sum: added to the model in place (LOCAL) or written to the wire buffer
+    // what becomes of a finished sum: added to the model in place (LOCAL; not where nobody rated the item in this window) or written to the wire buffer
+    const bool owns = !(LPI * 4 > k && L * 4 >= k);   // (a lane without a chunk of the row writes nothing -- lane 0 always has one; decided once, ahead of both loops)
     auto finish = [&](long it, int b, int e, const float4 &acc, float accb) {
-        const long i = lo + it;
-        if (LOCAL) {
-            if (b == e) return;   // nobody rated the item in this window
-            if (owns) {
-                float4 *w = reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + (size_t)i * pitch + (size_t)L * 4);
-                float4 c = *w;
-                c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-                *w = c;
-            }
-            if (L == 0) dbias[i] = dbias[i] + accb;
-            return;
-        }
-        if (owns) {
-            const size_t pos = (size_t)it * pitch + (size_t)L * 4;
-            if (HALF) {
-                __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
-                h[0] = __halves2half2(__float2half_rn(acc.x), __float2half_rn(acc.y));
-                h[1] = __halves2half2(__float2half_rn(acc.z), __float2half_rn(acc.w));
-            } else {
-                *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc;
-            }
-        }
-        if (L == 0) {
-            const size_t pos = (size_t)nitem * pitch + (size_t)it;
-            if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
-            else reinterpret_cast<float *>(dst)[pos] = accb;
-        }
+        if (!owns) return;
+        if (!LOCAL) wire_put<LPI, HALF>(dst, it, nitem, pitch, L, k, acc, accb);
+        else if (b != e) add_sum_in_place<LPI>(reinterpret_cast<float *>(dst), dbias, (size_t)(lo + it), pitch, L, k, acc, accb);
     };
     for (long it = first; it < nitem; it += stride) {
         const long i = lo + it;
@@ -412,61 +442,26 @@ __global__ __launch_bounds__(256) void k_window_items(const WindowSchedule S, in
         finish(it, b, e, acc, accb);
     }
     if constexpr (HOT) {
-    __syncthreads();
-    const int nq = min(hq_n, SVDF_WIN_HOT_QUEUE);
-    for (int qi = 0; qi < nq; qi++) {
-        const int b = hq_b[qi], e = hq_e[qi];
-        float4 acc = f4zero();
-        float accb = 0.0f;
-        for (int c0 = b; c0 < e; c0 += CHUNK) {
-            const int cn = min(CHUNK, e - c0);
-            // every lane group requests its share of the chunk's slots at once (CHUNK / G per group), then parks them in LDS
-            constexpr int PER = (CHUNK + G - 1) / G;
-            float4 v[PER];
-            float vb[PER];
-#pragma unroll
-            for (int r = 0; r < PER; r++) {
-                const int sl = grp + r * G;
-                const bool in = sl < cn;
-                v[r] = in ? load_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)(c0 + sl), pitch, L, k) : f4zero();
-                vb[r] = (in && L == 0) ? S.cbias[c0 + sl] : 0.0f;
-            }
-#pragma unroll
-            for (int r = 0; r < PER; r++) {
-                const int sl = grp + r * G;
-                if (sl < cn) { stage[sl * LPI + L] = v[r]; if (L == 0) stage_b[sl] = vb[r]; }
-            }
-            __syncthreads();
-            if (grp == 0) {   // slot order, acc = ((0 + c_1) + c_2) + ... as sum_contrib_slots does; eight LDS reads requested ahead of their (ordered) additions
-                for (int sl = 0; sl < cn; sl += 8) {
-                    float4 t[8];
-                    float tb[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) { const int x = min(sl + q, cn - 1); t[q] = stage[x * LPI + L]; tb[q] = stage_b[x]; }
-#pragma unroll
-                    for (int q = 0; q < 8; q++) if (sl + q < cn) { add_rows(acc, t[q]); accb = accb + tb[q]; }
-                }
-            }
-            __syncthreads();
+        __syncthreads();
+        const int nq = min(hq_n, SVDF_WIN_HOT_QUEUE);
+        for (int qi = 0; qi < nq; qi++) {
+            const int b = hq_b[qi], e = hq_e[qi];
+            float4 acc;
+            float accb;
+            sum_list_by_workgroup<LPI>(S, b, e, pitch, k, stage, stage_b, acc, accb);
+            if (grp == 0) finish((long)hq_it[qi], b, e, acc, accb);
         }
-        if (grp == 0) finish((long)hq_it[qi], b, e, acc, accb);
     }
-    }
-    if (LOCAL) return;
     // the global biases' part of the wire buffer: a window data set carries no global entry
-    const long g0 = nitem * (long)(pitch + 1);
-    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < nglobal; j += (long)gridDim.x * blockDim.x) {
-        if (HALF) reinterpret_cast<__half *>(dst)[g0 + j] = __float2half_rn(0.0f);
-        else reinterpret_cast<float *>(dst)[g0 + j] = 0.0f;
-    }
+    if (!LOCAL) wire_zero_tail<HALF>(dst, nitem * (long)(pitch + 1), nglobal);
 }
 // SPARSE windows (round 5): the windows the max-updates rule cuts on skewed data hold far fewer instances than there are items (13 K ratings over
 // 100 K items), and a lane group per ITEM is then 25 K waves that find nothing.  Here a THREAD looks at one item, the workgroup's items that have slots
-// go to an LDS queue, the lane groups share the queue (long lists: the cooperative form above).  In place only; same additions in the same order.
+// go to an LDS queue, the lane groups share the queue (long lists: sum_list_by_workgroup).  In place only; same additions in the same order.
 template <int LPI>
 __global__ __launch_bounds__(256) void k_window_items_sparse(const WindowSchedule S, int pitch, int k, long lo, long hi, float *w_item, float *dbias, int hot_min) {
     constexpr int G = 256 / LPI;
-    constexpr int CHUNK = LPI >= 64 ? 16 : (LPI >= 32 ? 32 : 64);
+    constexpr int CHUNK = WIN_LIST_CHUNK<LPI>;
     __shared__ int q_it[256], q_b[256], q_e[256];
     __shared__ int hq_idx[SVDF_WIN_HOT_QUEUE];
     __shared__ int q_n, hq_n;
@@ -476,17 +471,7 @@ __global__ __launch_bounds__(256) void k_window_items_sparse(const WindowSchedul
     const int L = lane & (LPI - 1);
     const int grp = threadIdx.x / LPI;
     const long nitem = hi - lo;
-    const bool owns = !(LPI * 4 > k && L * 4 >= k);
-    auto finish = [&](long it, const float4 &acc, float accb) {
-        const long i = lo + it;
-        if (owns) {
-            float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
-            float4 c = *w;
-            c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-            *w = c;
-        }
-        if (L == 0) dbias[i] = dbias[i] + accb;
-    };
+    const bool owns = !(LPI * 4 > k && L * 4 >= k);   // (as in k_window_items)
     for (long base = (long)blockIdx.x * 256; base < nitem; base += (long)gridDim.x * 256) {
         if (threadIdx.x == 0) { q_n = 0; hq_n = 0; }
         __syncthreads();
@@ -509,46 +494,16 @@ __global__ __launch_bounds__(256) void k_window_items_sparse(const WindowSchedul
             float accb = 0.0f;
             if (S.contrib_bf16) sum_contrib_slots<LPI, true, 4>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
             else sum_contrib_slots<LPI, false, 4>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
-            finish((long)q_it[idx], acc, accb);
+            if (owns) add_sum_in_place<LPI>(w_item, dbias, (size_t)(lo + q_it[idx]), pitch, L, k, acc, accb);
         }
         __syncthreads();
         const int nq = min(hq_n, SVDF_WIN_HOT_QUEUE);
         for (int qi = 0; qi < nq; qi++) {
             const int idx = hq_idx[qi];
-            const int b = q_b[idx], e = q_e[idx];
-            float4 acc = f4zero();
-            float accb = 0.0f;
-            for (int c0 = b; c0 < e; c0 += CHUNK) {
-                const int cn = min(CHUNK, e - c0);
-                constexpr int PER = (CHUNK + G - 1) / G;
-                float4 v[PER];
-                float vb[PER];
-#pragma unroll
-                for (int r = 0; r < PER; r++) {
-                    const int sl = grp + r * G;
-                    const bool in = sl < cn;
-                    v[r] = in ? load_contrib<LPI>(S.contrib, S.contrib_bf16, (size_t)(c0 + sl), pitch, L, k) : f4zero();
-                    vb[r] = (in && L == 0) ? S.cbias[c0 + sl] : 0.0f;
-                }
-#pragma unroll
-                for (int r = 0; r < PER; r++) {
-                    const int sl = grp + r * G;
-                    if (sl < cn) { stage[sl * LPI + L] = v[r]; if (L == 0) stage_b[sl] = vb[r]; }
-                }
-                __syncthreads();
-                if (grp == 0) {
-                    for (int sl = 0; sl < cn; sl += 8) {
-                        float4 t[8];
-                        float tb[8];
-#pragma unroll
-                        for (int q = 0; q < 8; q++) { const int x = min(sl + q, cn - 1); t[q] = stage[x * LPI + L]; tb[q] = stage_b[x]; }
-#pragma unroll
-                        for (int q = 0; q < 8; q++) if (sl + q < cn) { add_rows(acc, t[q]); accb = accb + tb[q]; }
-                    }
-                }
-                __syncthreads();
-            }
-            if (grp == 0) finish((long)q_it[idx], acc, accb);
+            float4 acc;
+            float accb;
+            sum_list_by_workgroup<LPI>(S, q_b[idx], q_e[idx], pitch, k, stage, stage_b, acc, accb);
+            if (grp == 0 && owns) add_sum_in_place<LPI>(w_item, dbias, (size_t)(lo + q_it[idx]), pitch, L, k, acc, accb);
         }
         __syncthreads();
     }
@@ -578,41 +533,14 @@ __global__ __launch_bounds__(256) void k_window_items_wide(const WindowSchedule 
             R acc = row_traits<R>::zero();
             float accb = 0.0f;
             sum_contrib_slots<64, BF16>(S.contrib, S.cbias, jb, je, pitch, lane, k, acc, accb);
-            if (LOCAL) {   // dst = W_item's first row, dbias = i_bias
-                float *w = reinterpret_cast<float *>(dst);
-                R c = row_io<64, R>::load(w, (size_t)(lo + it), pitch, lane, k);
-                add_rows(c, acc);
-                row_io<64, R>::store(w, (size_t)(lo + it), pitch, lane, k, c);
-                if (lane == 0) dbias[lo + it] = dbias[lo + it] + accb;
-                continue;
-            }
-#pragma unroll
-            for (int v = 0; v < V; v++) {
-                const int el = 4 * (lane + 64 * v);
-                if (el >= k) continue;
-                const size_t pos = (size_t)it * pitch + (size_t)el;
-                if (HALF) {
-                    __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
-                    h[0] = __halves2half2(__float2half_rn(acc.v[v].x), __float2half_rn(acc.v[v].y));
-                    h[1] = __halves2half2(__float2half_rn(acc.v[v].z), __float2half_rn(acc.v[v].w));
-                } else {
-                    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc.v[v];
-                }
-            }
-            if (lane == 0) {
-                const size_t pos = (size_t)nitem * pitch + (size_t)it;
-                if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
-                else reinterpret_cast<float *>(dst)[pos] = accb;
-            }
+            if (LOCAL) add_sum_in_place<64>(reinterpret_cast<float *>(dst), dbias, (size_t)(lo + it), pitch, lane, k, acc, accb);   // dst = W_item's first row, dbias = i_bias
+            else wire_put<64, HALF>(dst, it, nitem, pitch, lane, k, acc, accb);
         }
     }
-    if (LOCAL) return;
-    const long g0 = nitem * (long)(pitch + 1);
-    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < nglobal; j += (long)gridDim.x * blockDim.x) {
-        if (HALF) reinterpret_cast<__half *>(dst)[g0 + j] = __float2half_rn(0.0f);
-        else reinterpret_cast<float *>(dst)[g0 + j] = 0.0f;
-    }
+    if (!LOCAL) wire_zero_tail<HALF>(dst, nitem * (long)(pitch + 1), nglobal);
 }
+// a runtime flag as a compile-time one: f(std::true_type()) or f(std::false_type())
+template <typename F> static void with_flag(bool on, F &&f) { if (on) f(std::true_type()); else f(std::false_type()); }
 template <bool HALF, bool LOCAL>
 static void launch_window_items_wide(const WindowSchedule &S, int pitch, int k, long lo, long hi, long nglobal, void *dst, float *dbias, hipStream_t st, long nslots) {
     const long nitem = std::max<long>(hi - lo, 0);
@@ -620,10 +548,11 @@ static void launch_window_items_wide(const WindowSchedule &S, int pitch, int k, 
     const long waves = std::max<long>((nitem + span - 1) / span, 1);
     const unsigned grid = (unsigned)std::min<long>((waves + 3) / 4, 16384);
     const int v = k <= 512 ? 2 : (k <= 768 ? 3 : 4);
-    auto go = [&](auto vv, auto bf) {
-        hipLaunchKernelGGL((k_window_items_wide<decltype(vv)::value, HALF, LOCAL, decltype(bf)::value>), dim3(grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, dbias, span);
+    auto fmt = [&](auto vv) {
+        with_flag(S.contrib_bf16 != 0, [&](auto bf) {
+            hipLaunchKernelGGL((k_window_items_wide<decltype(vv)::value, HALF, LOCAL, decltype(bf)::value>), dim3(grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, dbias, span);
+        });
     };
-    auto fmt = [&](auto vv) { if (S.contrib_bf16) go(vv, std::true_type()); else go(vv, std::false_type()); };
     if (v == 2) fmt(std::integral_constant<int, 2>());
     else if (v == 3) fmt(std::integral_constant<int, 3>());
     else fmt(std::integral_constant<int, 4>());
@@ -641,8 +570,7 @@ static bool window_may_hold_long_lists(long nslots, long nitems) { return nslots
 void launch_window_items(const WindowSchedule &S, int pitch, int k, long lo, long hi, long nglobal, void *dst, int half, hipStream_t st, long nslots) {
     if (hi <= lo && nglobal <= 0) return;
     if (k > 256) {
-        if (half) launch_window_items_wide<true, false>(S, pitch, k, lo, hi, nglobal, dst, nullptr, st, nslots);
-        else launch_window_items_wide<false, false>(S, pitch, k, lo, hi, nglobal, dst, nullptr, st, nslots);
+        with_flag(half != 0, [&](auto hf) { launch_window_items_wide<decltype(hf)::value, false>(S, pitch, k, lo, hi, nglobal, dst, nullptr, st, nslots); });
         return;
     }
     const int lpi = lanes_per_instance(k);
@@ -651,11 +579,11 @@ void launch_window_items(const WindowSchedule &S, int pitch, int k, long lo, lon
     long grid = (waves + 3) / 4;
     if (grid > 16384) grid = 16384;
     const int hot_min = window_hot_min(nslots, hi - lo);
-    const bool hot = window_may_hold_long_lists(nslots, hi - lo);
-    if (half && hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, true, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, (float *)nullptr, hot_min)); }
-    else if (half) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, true, false, false>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, (float *)nullptr, hot_min)); }
-    else if (hot) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, false, false, true>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, (float *)nullptr, hot_min)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, false, false, false>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, (float *)nullptr, hot_min)); }
+    with_flag(half != 0, [&](auto hf) {
+        with_flag(window_may_hold_long_lists(nslots, hi - lo), [&](auto hot) {
+            SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, decltype(hf)::value, false, decltype(hot)::value>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, nglobal, dst, (float *)nullptr, hot_min));
+        });
+    });
 }
 // the same sums added in place to the rows / biases of items [lo, hi): W_item + i * pitch, i_bias + i
 void launch_window_items_local(const WindowSchedule &S, int pitch, int k, long lo, long hi, float *w_item, float *i_bias, hipStream_t st, long nslots) {
@@ -671,8 +599,11 @@ void launch_window_items_local(const WindowSchedule &S, int pitch, int k, long l
     long waves = (hi - lo + ipw - 1) / ipw;
     long grid = (waves + 3) / 4;
     if (grid > 16384) grid = 16384;
-    if (window_may_hold_long_lists(nslots, hi - lo)) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, false, true, true>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, 0L, (void *)w_item, i_bias, window_hot_min(nslots, hi - lo))); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, false, true, false>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, 0L, (void *)w_item, i_bias, 0x7FFFFFFF)); }
+    const bool may_hot = window_may_hold_long_lists(nslots, hi - lo);
+    const int hot_min = may_hot ? window_hot_min(nslots, hi - lo) : 0x7FFFFFFF;
+    with_flag(may_hot, [&](auto hot) {
+        SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_items<LPI, false, true, decltype(hot)::value>), dim3((unsigned)grid), dim3(256), 0, st, S, pitch, k, lo, hi, 0L, (void *)w_item, i_bias, hot_min));
+    });
 }
 // ------------------------------------------------------------------------------------------------- kernel B', windows with hot items (round 6)
 // ORDERED SUB-STEPS.  The window rule of round 5 let no row meet more than 128 updates per window, because thousands of changes computed against
@@ -715,8 +646,7 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
     const int grp = threadIdx.x / LPI;
     const int pitch = P.pitch, k = P.k;
     const bool use_ubias = P.no_user_bias == 0;
-    if ((int)blockIdx.x >= hot_blocks) {   // ---- cold items: the in-place sums of k_window_items<LPI, false, true, .> for every list of at most hot_sub slots
-        const bool owns = !(LPI * 4 > k && L * 4 >= k);
+    if ((int)blockIdx.x >= hot_blocks) {   // ---- cold items: the in-place sums of k_window_items<LPI, false, true, .> (add_sum_in_place) for every list of at most hot_sub slots
         const long stride = (long)(gridDim.x - hot_blocks) * G;
         for (long i = (long)(blockIdx.x - hot_blocks) * G + grp; i < num_item; i += stride) {
             const int b = S.iptr[i], e = S.iptr[i + 1];
@@ -724,19 +654,7 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
             R acc = row_traits<R>::zero();
             float accb = 0.0f;
             sum_contrib_slots<LPI, false>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
-            if constexpr (VPL == 1) {
-                if (owns) {
-                    float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
-                    float4 c = *w;
-                    c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-                    *w = c;
-                }
-            } else {
-                R c = row_io<LPI, R>::load(w_item, (size_t)i, pitch, L, k);
-                add_rows(c, acc);
-                row_io<LPI, R>::store(w_item, (size_t)i, pitch, L, k, c);
-            }
-            if (L == 0) i_bias[i] = i_bias[i] + accb;
+            add_sum_in_place<LPI>(w_item, i_bias, (size_t)i, pitch, L, k, acc, accb);
         }
         return;
     }
@@ -892,22 +810,17 @@ __global__ __launch_bounds__(NT) void k_window_apply(const DevParams P, const Wi
 }
 void launch_window_apply(const DevParams &P, const WindowSchedule &S, long num_item, float *w_item, float *i_bias, hipStream_t st) {
     if (S.hot_sub <= 0 || num_item <= 0) return;
-    const int lpi = lanes_per_instance(P.k);
     const int hot_blocks = 256;
-    const bool plain = P.active_type == ACT_LINEAR && P.reg_method == 0;
-    if (P.k > 256) {   // wide rows: a wave per slot, 512 threads (the kernel's head comment)
-        const long groups = 512 / 64;
-        const long cold = std::min<long>(std::max<long>((num_item + groups - 1) / groups, 1), 4096);
-        const unsigned grid = (unsigned)(hot_blocks + cold);
-        if (plain) { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_window_apply<LPI, 512, true, R>), dim3(grid), dim3(512), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
-        else { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_window_apply<LPI, 512, false, R>), dim3(grid), dim3(512), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
-        return;
-    }
-    const long groups = 1024 / lpi;
+    const bool wide = P.k > 256;   // wide rows: a wave per slot, 512 threads (the kernel's head comment)
+    const int lpi = wide ? 64 : lanes_per_instance(P.k);
+    const long groups = (wide ? 512 : 1024) / lpi;
     const long cold = std::min<long>(std::max<long>((num_item + groups - 1) / groups, 1), 4096);
     const unsigned grid = (unsigned)(hot_blocks + cold);
-    if (plain) { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, true>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
-    else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, false>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+    with_flag(P.active_type == ACT_LINEAR && P.reg_method == 0, [&](auto plain) {
+        constexpr bool PLAIN = decltype(plain)::value;
+        if (wide) { SVDF_DISPATCH_WIDE(P.k, hipLaunchKernelGGL((k_window_apply<LPI, 512, PLAIN, R>), dim3(grid), dim3(512), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+        else { SVDF_DISPATCH_LPI(lpi, hipLaunchKernelGGL((k_window_apply<LPI, 1024, PLAIN>), dim3(grid), dim3(1024), 0, st, P, S, num_item, w_item, i_bias, hot_blocks)); }
+    });
 }
 // ------------------------------------------------------------------------------------------------- rank pairs with hot items (round 12): apply + sums
 // ORDERED SUB-STEPS FOR RANK PAIRS (knob window_pair_sub).  An item with more than hot_sub slots in the window -- both signs counted --
@@ -1107,26 +1020,19 @@ __global__ __launch_bounds__(256) void k_window_pair_sums(const WindowSchedule S
     constexpr int G = 256 / LPI;
     const int L = threadIdx.x & (LPI - 1);
     const int grp = threadIdx.x / LPI;
-    const bool owns = !(LPI * 4 > k && L * 4 >= k);
     const long stride = (long)gridDim.x * G;
     for (long i = (long)blockIdx.x * G + grp; i < num_item; i += stride) {
         const int b = S.iptr[i], e = S.iptr[i + 1];
         if (b == e) continue;
-        float4 *w = reinterpret_cast<float4 *>(w_item + (size_t)i * pitch + (size_t)L * 4);
         if (e - b > S.hot_sub) {
-            if (owns) *w = load_contrib<LPI>(S.contrib, 0, (size_t)b, pitch, L, k);
+            store_row<LPI>(w_item, (size_t)i, pitch, L, k, load_contrib<LPI>(S.contrib, 0, (size_t)b, pitch, L, k));
             if (L == 0) i_bias[i] = S.cbias[b];
             continue;
         }
         float4 acc = f4zero();
         float accb = 0.0f;
         sum_contrib_slots<LPI, false>(S.contrib, S.cbias, b, e, pitch, L, k, acc, accb);
-        if (owns) {
-            float4 c = *w;
-            c.x = c.x + acc.x; c.y = c.y + acc.y; c.z = c.z + acc.z; c.w = c.w + acc.w;
-            *w = c;
-        }
-        if (L == 0) i_bias[i] = i_bias[i] + accb;
+        add_sum_in_place<LPI>(w_item, i_bias, (size_t)i, pitch, L, k, acc, accb);
     }
 }
 void launch_window_pair_sums(const WindowSchedule &S, int pitch, int k, long num_item, float *w_item, float *i_bias, hipStream_t st) {

@@ -586,21 +586,7 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
             io::store(W, row, pitch, L, k, c);
             if (L == 0 && (ts < 0 || S.user_bias)) bias[row] = bias[row] + accb;
         } else {
-            if (!(LPI * 4 > k && L * 4 >= k)) {
-                const size_t pos = (size_t)t * pitch + (size_t)L * 4;
-                if (HALF) {
-                    __half2 *h = reinterpret_cast<__half2 *>(reinterpret_cast<__half *>(dst) + pos);
-                    h[0] = __halves2half2(__float2half_rn(acc.x), __float2half_rn(acc.y));
-                    h[1] = __halves2half2(__float2half_rn(acc.z), __float2half_rn(acc.w));
-                } else {
-                    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(dst) + pos) = acc;
-                }
-            }
-            if (L == 0) {
-                const size_t pos = (size_t)T * pitch + (size_t)t;
-                if (HALF) reinterpret_cast<__half *>(dst)[pos] = __float2half_rn(accb);
-                else reinterpret_cast<float *>(dst)[pos] = accb;
-            }
+            wire_put<LPI, HALF>(dst, t, T, pitch, L, k, acc, accb);
         }
     }
     const long g0 = T * (long)(pitch + 1);

@@ -137,6 +137,17 @@ def test_fp16_wire_stays_close_and_item_range_pieces_are_exact_at_wide_widths():
     _check_ranks(pieces, simulate_parts(conf, u, i, r, 2, 4, 2, 2, ni, minibatch=True))
 
 
+@pytest.mark.parametrize("k", [320, 1024])
+@pytest.mark.parametrize("ni", [9, 30000])
+def test_fp16_wire_buffer_is_the_fp32_one_rounded_to_nearest_even_at_wide_widths(k, ni):
+    """k_window_items_wide's fp16 writer: ni = 9, a wave per item (span = 1); ni = 30 000, 6 000 ratings: the sparse form (span = 64), items without
+    slots written as zeros"""
+    from test_gpu_window import _fp16_wire_is_the_rounded_fp32_wire
+    nu, n = 2000, 6000
+    u, i, r = cases.planted_triples(n, nu, ni, seed=k + ni)
+    _fp16_wire_is_the_rounded_fp32_wire(cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k), u, i, r)
+
+
 def test_stratified_schedule_with_in_place_sums_into_item_blocks_at_a_wide_width():
     """svdf_window_delta_apply_local on an item block [lo, hi) with lo > 0, svdf_item_block_get / _set and the trainer class over them: the
     schedule test of tests/test_gpu_window.py at k = 320, two ranks"""

@@ -126,6 +126,36 @@ def test_fp16_wire_stays_close_and_item_range_pieces_are_exact():
     _check(pieces, simulate_parts(conf, u, i, r, 2, 4, 2, 2, ni, minibatch=True))
 
 
+def _fp16_wire_is_the_rounded_fp32_wire(conf, u, i, r):
+    """one window on two identically seeded adaptors, fp32 wire and fp16 wire: the fp16 buffer is the fp32 buffer rounded to nearest even, word for word"""
+    import torch
+    bufs = []
+    for half in (False, True):
+        ad = HipShard(_trainer(conf), torch, torch.device("cuda", 0), minibatch=True)
+        ad.set_wire_half(half)
+        ad.train(ad.make_windows([(u, i, r)])[0])
+        d = ad.delta_get()
+        ad.stream.synchronize()
+        bufs.append(d.cpu().numpy())
+    full, half = bufs
+    assert full.dtype == np.float32 and half.dtype == np.float16 and full.shape == half.shape
+    assert np.isfinite(full).all() and np.isfinite(half).all() and full.any()   # (not an empty window)
+    assert np.array_equal(half.view(np.uint16), full.astype(np.float16).view(np.uint16))
+
+
+@pytest.mark.parametrize("k", [16, 64, 200])
+@pytest.mark.parametrize("ni", [400, 2000])
+def test_fp16_wire_buffer_is_the_fp32_one_rounded_to_nearest_even(k, ni):
+    """the fp16 writer of k_window_items behind both of its forms: ni = 400, 15 slots per item: the plain form; ni = 2 000, 3 slots per item on average
+    and two lists of ~2 000 / ~850 slots: the cooperative form through the LDS queue, several chunks per list"""
+    nu, n = 2000, 6000
+    u, i, r = cases.planted_triples(n, nu, ni, seed=k + ni)
+    if ni == 2000:
+        i[::3] = 7
+        i[1::7] = 11
+    _fp16_wire_is_the_rounded_fp32_wire(cases.conf_with(cases.BASICMF_CONF, num_user=nu, num_item=ni, num_factor=k), u, i, r)
+
+
 def test_refused_configurations():
     conf = cases.conf_with(cases.BASICMF_CONF, num_user=50, num_item=20, num_factor=8)
     t = _trainer(conf + [("reg_method", "4")])
