@@ -347,7 +347,9 @@ int svdf_synchronize(svdf_trainer *t);
  * staged chunks (the stderr line of 26 for svdf_update_*: at most one per handle; 26 .. 28 count resident data sets only),
  * 33 / 34 user-group (SVD++) windows with shared user entries (amd:shared_user_from) walked by the one-wave-per-unit form that
  * keeps a segment's shared rows in registers / by the general lane-group kernel,
- * 35 hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub; the windows count under 34) */
+ * 35 hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub; the windows count under 34),
+ * 36 hot item rows applied in ordered sub-steps on user-group (SVD++) windows, with or without shared user entries (knob window_block_item_sub;
+ * DESIGN.md 6u; the windows keep counting where they do without the knob) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -426,6 +428,19 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               amd:contrib = bf16, amd:gpus > 1 / svdf_dataset_window_from_blocks, wunit_inplace = 0 once a row is hot.
  *                                                               Measured on 64 dense buckets (profiles/r16_block_hot.md): 14x the 6p rule at the default cap, and the |dRMSE| <= 1e-4
  *                                                               contract missed with the knob on (3.5e-3) and off (1.3e-3): the cap is not a calibrated value
+ *     window_block_item_sub (*) 0, window_block_item_max (*) 2048   OPT-IN.  The same lane for the ITEM rows of USER-GROUP (SVD++) blocks (format_type 1 trainers, with or without amd:shared_user_from;
+ *                                                               svdf_dataset_from_blocks / svdf_dataset_from_buffer_file(.., 1) / staged svdf_update_block chunks under amd:step =
+ *                                                               minibatch): an item row with more than window_block_item_sub (0 .. 128) slots in a window moves in
+ *                                                               ordered sub-steps of that many (k_wunit_apply_hot<LPI, true, true>, each slot from the span state its walk held:
+ *                                                               private row and bias, tmp_ufeedback and its bias; 0 = off, the default: today's rule and bits) and meets at most
+ *                                                               window_block_item_max updates per window; window_per_target then bounds the mean of min(updates per window,
+ *                                                               window_block_item_sub).  The range and meaning of window_item_sub, which stays refused with user-group trainers.
+ *                                                               Without effect on random-order trainers and on windows in which no item is hot.  Set before the data set is
+ *                                                               built: train_dataset refuses a sequence built with another window_block_item_sub.  Refused with amd:contrib =
+ *                                                               bf16, amd:gpus > 1 / svdf_dataset_window_from_blocks, num_factor > 256, wunit_inplace = 0 once a row is hot.
+ *                                                               Measured on Zipf(0.7) items (profiles/r22_block_item_hot.md): caps 512 .. 4 096 hold |dRMSE| <= 1e-4; 2 048 and 4 096 cut the
+ *                                                               same windows there, so the default stays 2 048.  The lane is SLOWER than the knob at 0 on that input (0.86x at best:
+ *                                                               windows with a hot row leave the one-wave-per-unit walk), and the feedback rows' term of the rule is not lowered by it
  *     window_pair_sub (*) 0, window_pair_max (*) 4096           the same lane for RANK PAIRS (svdf_dataset_from_pairs and pair-shaped staged chunks under amd:step = minibatch /
  *                                                               auto): an item with more than window_pair_sub (0 .. 128) slots in a window -- both signs counted --
  *                                                               moves in ordered sub-steps of that many (k_window_apply_pairs; 0 = off, the default: the rule and bits as
@@ -451,7 +466,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  * svdf_dataset_window_from_blocks a row with several user entries of which one is >= B (a row whose ONLY user entry is >= B is an ordinary
  * user to that entry point, as without the key); side tables and the ordered sub-step lanes of the other routes (window_shared_sub,
  * window_item_sub, window_pair_sub) stay refused with user-group trainers -- hot shared rows of such blocks have a lane of their own, knob
- * window_block_sub.
+ * window_block_sub, and so have their hot item rows, knob window_block_item_sub (it does not need this key).
  * Blocks whose rows have one user entry < B train bit for bit as without the key (in the window sequence a row whose only user entry is >= B
  * has no private id and is refused). */
 int svdf_set_knob(svdf_trainer *t, const char *name, long value);

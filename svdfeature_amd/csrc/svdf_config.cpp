@@ -216,6 +216,7 @@ int64_t Engine::counter(int what) const {
     case 33: return n_wave_shared_;    // windows walked by the one-wave-per-unit form that keeps the segment's shared rows in registers
     case 34: return n_walk_shared_;    // windows walked by the general lane-group kernel
     case 35: return n_block_hot_;      // hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub, section 6q; the windows count under 34)
+    case 36: return n_block_item_hot_; // hot item rows applied in ordered sub-steps on user-group (SVD++) windows (knob window_block_item_sub, section 6u)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -282,6 +283,14 @@ int Engine::set_knob(const char *name, long value) {
         return 0;
     }
     if (!strcmp(name, "window_block_max")) { check(value >= 1, "window_block_max must be positive"); wseq_block_max_ = (int)value; return 0; }
+    if (!strcmp(name, "window_block_item_sub")) {
+        check(value >= 0 && value <= 128, "window_block_item_sub must be in 0 .. 128");
+        check(value == 0 || (gpus_ == 1 && !multi_ && !is_peer_),
+              "window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) is for the one-GPU window sequence; the N-rank exchange (amd:gpus > 1) sums every slot on the wire");
+        wseq_block_item_sub_ = (int)value;
+        return 0;
+    }
+    if (!strcmp(name, "window_block_item_max")) { check(value >= 1, "window_block_item_max must be positive"); wseq_block_item_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_pair_sub")) {
         check(value >= 0 && value <= 128, "window_pair_sub must be in 0 .. 128");
         check(value == 0 || (gpus_ == 1 && !multi_ && !is_peer_),

@@ -331,6 +331,7 @@ struct Dataset {
     int wseq_shared_sub = -1;      // kind 8 from wseq_from_csr (else -1): window_shared_sub when the sequence was built (train_dataset refuses another value)
     int wseq_item_sub = -1;        // the same for window_item_sub
     int wseq_block_sub = -1;       // kind 8 from wseq_from_blocks (else -1): window_block_sub as it took effect when the sequence was built (0 without amd:shared_user_from; train_dataset refuses another value)
+    int wseq_block_item_sub = -1;  // the same for window_block_item_sub (hot item rows of SVD++ blocks; 0 on trainers that are not user-group)
     long wu_nhrec = 0;             // records in wu_hrec (user-group windows: the rows of the trainer's second record plane, d_hfb_ / d_hfbb_)
     bool plain_rows = false;       // built by dataset_from_triples / _from_pairs through the general representation (side tables, wide rows ...): the default-step guard names the window step by the columns' shape
     int wseq_hot_sub = -1;         // kind 8 from wseq_from_triples (else -1): window_hot_sub as it took effect when the sequence was built (0 without the lane; train_dataset refuses another value)
@@ -672,7 +673,7 @@ class Engine {
     DevBuf<float> w_sfb_, w_sfbb_, w_ones_;   // ... the segments' prepared feedback sums / biases (kept apart from d_dvec_: a trained window's pending sums read that), labels of rank pairs
     bool device_window_ready() const { return !host_only_ && device_window_; }
     DevBuf<float> d_dvec_, d_dbias_;      // deferred feedback scatter: one scaled delta row + bias delta per segment of the largest window
-    DevBuf<float> d_hfb_, d_hfbb_;        // user-group windows with hot shared user rows (window_block_sub): tmp_ufeedback + its bias per hot record of the largest window
+    DevBuf<float> d_hfb_, d_hfbb_;        // user-group windows with hot shared user rows (window_block_sub) or hot item rows (window_block_item_sub): tmp_ufeedback + its bias per hot record of the largest window
     DevBuf<float> d_contrib_, d_cbias_;   // window-minibatch scratch: one contribution row + bias word per instance of the largest window
     std::unique_ptr<IpcState, IpcDeleter> ipc_;
     std::unique_ptr<RcclState, RcclDeleter> rccl_;
@@ -698,7 +699,7 @@ class Engine {
                              bool shared = false, int shared_sub = 0, int item_sub = 0) const;
     void wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                                 const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value,
-                                bool shared = false, int shared_sub = 0) const;
+                                bool shared = false, int shared_sub = 0, int item_sub = 0) const;
     int wseq_build_threads_ = 32;         // knob "wseq_build_threads": host threads building the windows of a one-GPU window sequence (user units)
     int64_t private_user_entry(int64_t p1, int64_t p2, const unsigned *feat_index, std::vector<unsigned> &seen) const;   // amd:shared_user_from: the one id < B of a row's user entries
     void wunit_train(Dataset *ds);
@@ -725,6 +726,10 @@ class Engine {
     int wseq_block_max_ = 512;            // knob "window_block_max": the most updates a hot shared user row of such blocks may meet per window; taken over from window_shared_max and NOT confirmed: on 64 dense buckets (2 M rows, 3 seeds) no cap of 128 .. 1 024 holds |dRMSE| <= 1e-4, nor does the rule with the knob off (profiles/r16_block_hot.md)
     int block_sub() const { return user_group() && shared_user() ? wseq_block_sub_ : 0; }   // the knob as it takes effect: user-group trainers with amd:shared_user_from
     void wseq_block_check(const char *what) const;   // window_block_sub in effect: what the lane does not cover, refused with its cause
+    int wseq_block_item_sub_ = 0;         // knob "window_block_item_sub" (0 .. 128): an item row with more slots than this in a window of user-group blocks (wseq_from_blocks) is applied in ordered sub-steps of this many (k_wunit_apply_hot<LPI, true, true>); 0 = off
+    int wseq_block_item_max_ = 2048;      // knob "window_block_item_max": the most updates a hot item row of such blocks may meet per window; taken over from window_item_max; holds |dRMSE| <= 1e-4 on Zipf(0.7) items over 2 M rows of SVD++ blocks (3 seeds, sub 64 / 128: at most 5.9e-5; profiles/r22_block_item_hot.md).  4 096 holds it too but cut the same 14 windows there (the feedback term binds; the hottest item meets about 1 400 updates per window), so it was not taken: the largest cap exercised as a bound is 1 024
+    int block_item_sub() const { return user_group() ? wseq_block_item_sub_ : 0; }   // the knob as it takes effect: user-group trainers (their passes are in file order), with or without amd:shared_user_from
+    void wseq_block_item_check(const char *what) const;   // window_block_item_sub in effect: what the lane does not cover, refused with its cause
     int wseq_pair_sub_ = 0;               // knob "window_pair_sub" (0 .. 128): an item with more slots than this (both signs counted) in a window of rank pairs (wseq_from_pairs) is applied in ordered sub-steps of this many (k_window_apply_pairs); 0 = off
     int wseq_pair_max_ = 4096;            // knob "window_pair_max": the most updates a hot item of rank pairs may meet per window (how stale everybody else's view of it gets); the largest swept value: Zipf(0.7) pairs at the configs[4] shape, 20 M-pair prefix, 3 seeds, sub 8 / 24 / 128: worst seed at 3 % of the pair contract (accuracy within 3e-3, margin within 2 %; profiles/r12_pair_hot.md)
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)
@@ -826,6 +831,7 @@ class Engine {
     int staged_auto_decision_ = 0;                       // amd:step = auto: 0 not taken yet, else auto_last_.decided of the chunk it was taken on
     int64_t n_staged_window_ = 0, n_staged_exact_ = 0, n_staged_guard_ = 0;
     int64_t n_block_hot_ = 0;                            // hot shared user rows applied in ordered sub-steps on user-group windows (counter 35)
+    int64_t n_block_item_hot_ = 0;                       // hot item rows applied in ordered sub-steps on user-group windows (counter 36)
     int64_t n_wave_shared_ = 0, n_walk_shared_ = 0;      // user-group windows with shared user entries: walked by the wave form / by the general kernel (counters 33 / 34)
     int64_t ns_staged_build_ = 0;                        // host time of the per-chunk pre-check + window build (part of ns_flush_; SVDF_PROFILE prints it)
     int64_t ns_wseq_host_ = 0, ns_wseq_adopt_ = 0;       // user-unit window sequences (wseq_build_windows): wall time of the host regrouping / of the windows' allocations + uploads + synchronisations

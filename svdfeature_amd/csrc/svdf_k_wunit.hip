@@ -33,7 +33,8 @@ namespace svdf {
 // (S.iptr) follow their parent entry in every loop, with the reference's item-side forms for parent value ival and child value v: bias term
 // (b v) ival, tmp_i scale (float)((double)v ival), update scale ((lr err) v) ival -- svdf_instance.h restates the same forms for the exact pass.
 // HOT: the window has hot shared user rows or hot item rows (ordered sub-steps, kernel C below); windows without them run the HOT = false build, the
-// code as it was.  FB and HOT together: user-group windows with hot shared user rows (knob window_block_sub).
+// code as it was.  FB and HOT together: user-group windows with hot shared user rows (knob window_block_sub) or hot item rows
+// (knob window_block_item_sub, section 6u).
 template <int LPI, bool FB, bool HOT = false, typename R = float4>
 __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUnitSchedule S) {
     using io = row_io<LPI, R>;
@@ -126,6 +127,10 @@ __global__ __launch_bounds__(256) void k_wunit_walk(const DevParams P, const WUn
                 if (HOT && e.pad) {   // a hot item row of this window (k_wunit_apply_hot<ITEM>): the same record as for a hot shared user row below
                     cio::store(S.contrib, 0, (size_t)e.slot, pitch, L, k, p);
                     if (L == 0) S.cbias[e.slot] = bu;
+                    if (FB) {   // user-group windows (knob window_block_item_sub, section 6u): the span's feedback state too, as for a hot uent below (pad = 1 + record)
+                        cio::store(S.hfb, 0, (size_t)(e.pad - 1), pitch, L, k, pp.tmp_fb);
+                        if (L == 0) S.hfbb[e.pad - 1] = pp.tmp_bias;
+                    }
                     continue;
                 }
                 const float si = lr * err * e.val;
@@ -615,7 +620,7 @@ __global__ __launch_bounds__(256) void k_wunit_sum(const WUnitSchedule S, float 
 // and parks new - current of the hot row (and bias) in LDS.  The parked changes of a sub-step are added in slot order (acc = +0 + c_1 + c_2 ...; every
 // column by one thread) and the row moves by the sum.  The workgroup is sized to the sub-step: min(sub, 256 / LPI) lane groups; a larger sub-step
 // takes several rounds of them (k = 64, sub = 128: 8 rounds of 16), the parked changes joining the sum round by round, in slot order all the same.
-// FB (ITEM = false only; knob window_block_sub, section 6q): the data rows belong to user-group spans -- tmp_ufactor starts from the span's tmp_ufeedback and
+// FB (knob window_block_sub, section 6q; ITEM: knob window_block_item_sub, section 6u): the data rows belong to user-group spans -- tmp_ufactor starts from the span's tmp_ufeedback and
 // calc_bias ends with tmp_ufeedback_bias, both as the walk held them when it reached the data row (the record's row of S.hfb / word of S.hfbb).
 template <int LPI, bool ITEM, bool FB = false>
 __global__ __launch_bounds__(256) void k_wunit_apply_hot(const DevParams P, const WUnitSchedule S) {
@@ -761,7 +766,10 @@ void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipSt
     else launch_wunit_apply_hot<false>(P, S, S.nhot, S.hot_sub, st);
 }
 // nitem_hot: the hot item rows of the window, S.hot[S.nhot .. S.nhot + nitem_hot)
-void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st) { launch_wunit_apply_hot<true>(P, S, nitem_hot, S.item_sub, st); }
+void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st, bool feedback) {
+    if (feedback) launch_wunit_apply_hot<true, true>(P, S, nitem_hot, S.item_sub, st);   // user-group windows: knob window_block_item_sub
+    else launch_wunit_apply_hot<true>(P, S, nitem_hot, S.item_sub, st);
+}
 
 // ------------------------------------------------------------------------------------------------- scoring (read-only)
 // svdf_predict_dataset / svdf_eval_dataset on a window of user units.  Nothing is updated, so the rows are independent: they are scored

@@ -65,7 +65,7 @@ int launch_wunit_walk(const DevParams &P, const WUnitSchedule &S, bool feedback,
 bool wunit_wave_applies(const DevParams &P, const WUnitSchedule &S, bool feedback);   // svdf_k_wave.hip: one wave per user unit (SVD++ shape)
 void launch_wunit_wave(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool shared = false);
 void launch_wunit_apply_shared(const DevParams &P, const WUnitSchedule &S, hipStream_t st, bool feedback = false);   // hot shared user rows in ordered sub-steps, between the walk and the in-place sums
-void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st);   // hot item rows (S.hot[S.nhot .. + nitem_hot)) likewise; writes no model row either, so its order against the launch above is free
+void launch_wunit_apply_item(const DevParams &P, const WUnitSchedule &S, long nitem_hot, hipStream_t st, bool feedback = false);   // hot item rows (S.hot[S.nhot .. + nitem_hot)) likewise; writes no model row either, so its order against the launch above is free
 void launch_wunit_sum(const DevParams &P, const WUnitSchedule &S, void *dst, int half, hipStream_t st);   // dst == nullptr: add to the model in place
 // cross-process direct exchange (svdf_ipc.cpp): sequence flags in IPC-mapped device memory
 void launch_ipc_signal(unsigned *const *pages, int n, int phase, int me, unsigned seq, const unsigned *err, hipStream_t st);

@@ -72,6 +72,10 @@ const char *Engine::staged_config_rule(bool blocks, bool user_units) const {
         if (wunit_inplace_ == 0) return "window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)";
     }
     if (blocks && block_sub() > 0 && contrib_bf16_) return "window_block_sub > 0 needs amd:contrib = fp32";
+    if (blocks && block_item_sub() > 0) {
+        if (contrib_bf16_) return "window_block_item_sub > 0 needs amd:contrib = fp32";
+        if (wunit_inplace_ == 0) return "window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) needs the in-place sums (knob wunit_inplace = 1)";
+    }
     if (wseq_pair_sub_ > 0) {
         if (contrib_bf16_) return "window_pair_sub > 0 needs amd:contrib = fp32";
         if (blocks) return "window_pair_sub > 0 is not supported with user-group (SVD++) trainers";

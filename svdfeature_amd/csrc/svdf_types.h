@@ -296,6 +296,8 @@ struct WUnitSchedule {
     // hot shared user rows of USER-GROUP windows (window_block_sub > 0): a hot entry's uent.pad is 1 + the index of its record in
     // hrec, and the walk stores there, next to the slot's record, the span state the data row's update starts from -- tmp_ufeedback (hfb[index][pitch])
     // and tmp_ufeedback_bias (hfbb[index]); k_wunit_apply_hot<LPI, false, true> reads them back.  Trainer scratch, sized for the largest window's records.
+    // Hot item rows of such windows (window_block_item_sub > 0; section 6u) take the same record: ent.pad = 1 + the record's index, read back by
+    // k_wunit_apply_hot<LPI, true, true>.
     float *hfb, *hfbb;
 };
 

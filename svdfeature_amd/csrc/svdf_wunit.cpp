@@ -72,7 +72,8 @@ WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     S.nshared_rows = ds->wu_nshared; S.shared_from = sh ? shared_user_from_ : 0u;
     S.iptr = ds->wu_ichild ? ds->wu_iptr.p : nullptr; S.ient = ds->wu_ichild ? ds->wu_ient.p : nullptr;
     const bool hot = ds->wu_nhot + ds->wu_nihot > 0;
-    S.hot = hot ? ds->wu_hot.p : nullptr; S.hrec = hot ? ds->wu_hrec.p : nullptr; S.nhot = ds->wu_nhot; S.item_sub = wseq_item_sub_;
+    S.hot = hot ? ds->wu_hot.p : nullptr; S.hrec = hot ? ds->wu_hrec.p : nullptr; S.nhot = ds->wu_nhot;
+    S.item_sub = ds->wu_feedback ? block_item_sub() : wseq_item_sub_;   // user-group windows: knob window_block_item_sub
     S.hot_sub = ds->wu_feedback ? block_sub() : wseq_shared_sub_;   // user-group windows: knob window_block_sub
     S.hfb = d_hfb_.p; S.hfbb = d_hfbb_.p;
     return S;
@@ -115,6 +116,7 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
         check(wunit_inplace_ != 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs the in-place sums (knob wunit_inplace = 1)");
     }
     if (block_sub() > 0) wseq_block_check(what);
+    if (block_item_sub() > 0) wseq_block_item_check(what);
     // width: the one-GPU sequences (amd:step = minibatch) take wide rows through the general walk; the N-rank builders and the sub-step lanes (one lane
     // group per slot) stay at 256 factors
     const bool sequence = strcmp(what, "dataset_from_csr") == 0 || strcmp(what, "dataset_from_blocks") == 0;
@@ -123,6 +125,7 @@ void Engine::wunit_check_config(const char *what, bool tables_ok) const {
         check(wseq_shared_sub_ == 0, "window data sets: window_shared_sub > 0 (ordered sub-steps for hot shared user rows) needs num_factor <= 256 (the lane has no wide rows)");
         check(wseq_item_sub_ == 0, "window data sets: window_item_sub > 0 (ordered sub-steps for hot item rows) needs num_factor <= 256 (the lane has no wide rows)");
         check(block_sub() == 0, "window data sets: window_block_sub > 0 (ordered sub-steps for hot shared user rows of SVD++ blocks) needs num_factor <= 256 (the lane has no wide rows)");
+        check(block_item_sub() == 0, "window data sets: window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) needs num_factor <= 256 (the lane has no wide rows)");
     } else
         check(wunit_width_ok(), "window data sets: num_factor <= 256");
     check(!user_group() || mp_.common_feedback_space == 0, "window data sets: user-group trainers need a feedback space of their own (common_feedback_space = 0)");
@@ -148,6 +151,15 @@ void Engine::wseq_block_check(const char *what) const {
     check(strcmp(what, "dataset_window_from_blocks") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
           "svdf_dataset_window_from_blocks: window_block_sub > 0 (ordered sub-steps for hot shared user rows of SVD++ blocks) is for the one-GPU window sequence "
           "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) has no place for user rows");
+}
+
+// window_block_item_sub in effect (user-group trainer): fp32 slots, the one-GPU window sequence.  (The in-place sums are asked
+// for by the builder, once a row is hot.)
+void Engine::wseq_block_item_check(const char *what) const {
+    check(!contrib_bf16_, "window data sets: window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) needs amd:contrib = fp32");
+    check(strcmp(what, "dataset_window_from_blocks") != 0 && gpus_ == 1 && !multi_ && !is_peer_,
+          "svdf_dataset_window_from_blocks: window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) is for the one-GPU window sequence "
+          "(amd:step = minibatch); the N-rank exchange (amd:gpus > 1) sums every slot on the wire");
 }
 
 // Common builder.  segs: in FILE order; seg_rows: source row ids (rows of a segment in file order).  by_row_order: random-order
@@ -386,7 +398,8 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
     if (!H.hot.empty()) {   // the hot rows' slot ranges and records (slots are in file order: the record of a slot is found through its entry)
         check(inplace, H.nhot_user > 0 ? (feedback ? "window data sets: window_block_sub > 0 (ordered sub-steps for hot shared user rows of SVD++ blocks) needs the in-place sums (knob wunit_inplace = 1)"
                                                    : "window data sets: ordered sub-steps for shared user rows need the in-place sums (knob wunit_inplace = 1)")
-                                       : "window data sets: ordered sub-steps for item rows need the in-place sums (knob wunit_inplace = 1)");
+                                       : feedback ? "window data sets: window_block_item_sub > 0 (ordered sub-steps for hot item rows of SVD++ blocks) needs the in-place sums (knob wunit_inplace = 1)"
+                                                  : "window data sets: ordered sub-steps for item rows need the in-place sums (knob wunit_inplace = 1)");
         std::vector<int> hot_of((size_t)(NI + NS), -1);   // by target - NF: item rows, then shared user rows
         int rec = 0;
         for (size_t q = 0; q < H.hot.size(); q++) {
@@ -409,12 +422,13 @@ void Engine::wunit_build_host(WUnitHost &H, bool inplace, const void *segs_v, si
                     record(q, u.slot, nr, e);
                 }
             if ((long)H.hot.size() == H.nhot_user) continue;
-            // hot item rows (svdf_types.h, WinHotRec): a plain entry is marked pad = 1, position e; a child carries its slot as -2 - slot, position ~c
+            // hot item rows (svdf_types.h, WinHotRec): a plain entry is marked pad = 1 (user-group windows, section 6u: 1 + the record's index, as a hot
+            // uent above), position e; a child carries its slot as -2 - slot, position ~c
             for (int e = rptr[(size_t)2 * nr + 1]; e < rptr[(size_t)2 * nr + 2]; e++) {
                 WinEnt &it = ent[(size_t)e];
                 const int q = hot_of[it.idx];
                 if (q < 0) continue;
-                it.pad = 1;
+                it.pad = feedback ? 1 + H.hot[(size_t)q].rec + it.slot - H.hot[(size_t)q].b : 1;
                 record(q, it.slot, nr, e);
             }
             if (has_ichild)
@@ -622,7 +636,7 @@ const char *Engine::side_children_rule(const int64_t *p, const unsigned *feat_in
 // same on every row of a block (or START..END span): the unit's user; and any number of shared ids >= B, which may differ from row to row.
 void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index,
                                     const float *fb_value, const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr,
-                                    const unsigned *feat_index, const float *feat_value, bool shared, int shared_sub) const {
+                                    const unsigned *feat_index, const float *feat_value, bool shared, int shared_sub, int item_sub) const {
     const long NU = mp_.num_user;
     const long r_lo = block_row_ptr[b0], r_hi = block_row_ptr[b1];
     std::vector<int64_t> priv;   // shared mode: the private entry of every row of the window
@@ -671,7 +685,7 @@ void Engine::wunit_host_from_blocks(WUnitHost &H, bool inplace, long b0, long b1
     std::vector<int64_t> ptr((size_t)3 * (r_hi - r_lo) + 1);
     for (size_t j = 0; j < ptr.size(); j++) ptr[j] = row_ptr[3 * r_lo + (long)j];
     wunit_build_host(H, inplace, segs.data(), segs.size(), seg_rows, false, r_hi - r_lo, row_label + r_lo, ptr.data(), feat_index, feat_value, fb_index, fb_value,
-                     priv.empty() ? nullptr : priv.data(), false, shared_sub, 0);
+                     priv.empty() ? nullptr : priv.data(), false, shared_sub, item_sub);
 }
 
 Dataset *Engine::dataset_window_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
@@ -715,7 +729,7 @@ void Engine::wunit_train(Dataset *ds) {
     d_contrib_.reserve((size_t)std::max<long>(ds->win_slots, 1) * (size_t)pitch_);
     d_cbias_.reserve((size_t)std::max<long>(ds->win_slots, 1));
     d_gcontrib_.reserve((size_t)std::max<long>(ds->wu_gslots, 1));
-    if (ds->wu_feedback && ds->wu_nhot > 0) { d_hfb_.reserve((size_t)std::max<long>(ds->wu_nhrec, 1) * (size_t)pitch_); d_hfbb_.reserve((size_t)std::max<long>(ds->wu_nhrec, 1)); }
+    if (ds->wu_feedback && ds->wu_nhot + ds->wu_nihot > 0) { d_hfb_.reserve((size_t)std::max<long>(ds->wu_nhrec, 1) * (size_t)pitch_); d_hfbb_.reserve((size_t)std::max<long>(ds->wu_nhrec, 1)); }
     if (ds->wu_defer_fb) { d_dvec_.reserve((size_t)std::max<long>(ds->wu_nseg, 1) * (size_t)pitch_); d_dbias_.reserve((size_t)std::max<long>(ds->wu_nseg, 1)); }
     const int form = launch_wunit_walk(params(), wunit_view(ds), ds->wu_feedback, wunit_fast_, stream_, ds->wu_shared_uniform);
     if (form == 1) n_wave_shared_++;                                            // counter 33
@@ -1006,9 +1020,12 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     for (double m : mass) { m1 += m; m2 += m * m; }
     // ordered sub-steps for hot shared user rows (knob window_block_sub): the rule of section 6k -- the shared rows' term leaves the
     // common call, their rows follow wseq_windows_shared with the block knobs; amd:window overrides, and the count stays capped by the number of blocks
-    const int bsub = block_sub();
-    long Wn = wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio()), m1 > 0.0 ? m2 / m1 : 0.0, bsub > 0 ? 0.0 : shared_met});
+    // ordered sub-steps for hot item rows (knob window_block_item_sub, section 6u): the rule of section 6m likewise -- the item term leaves the common call, the
+    // item rows follow wseq_windows_shared with window_block_item_max as the cap and window_per_target as the mean
+    const int bsub = block_sub(), isub = block_item_sub();
+    long Wn = wseq_windows(n, {isub > 0 ? 0.0 : mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio()), m1 > 0.0 ? m2 / m1 : 0.0, bsub > 0 ? 0.0 : shared_met});
     if (bsub > 0 && !window_set_) Wn = std::max(Wn, wseq_windows_shared(n, cs, {}, bsub, wseq_block_max_, wseq_per_target_shared_, 0));
+    if (isub > 0 && !window_set_) Wn = std::max(Wn, wseq_windows_shared(n, ci, {}, isub, wseq_block_item_max_, wseq_per_target_, 0));
     const long W0 = std::min<long>(std::max<long>(num_block, 1), Wn);
     // cuts in blocks (the rule of multi_gpu.block_window_bounds and svdf_multi.cpp): even block positions moved forward to the next
     // position where no START..END span is open
@@ -1023,11 +1040,12 @@ Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const i
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     ds->wseq_block_sub = bsub;
+    ds->wseq_block_item_sub = isub;
     const bool inplace = wunit_inplace_ != 0;
     wseq_build_windows((long)cut.size() - 1, wseq_build_threads_,
         [&](long w, WUnitHost &H) {
             wunit_host_from_blocks(H, inplace, cut[(size_t)w], cut[(size_t)w + 1], extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr,
-                                   feat_index, feat_value, shared_user(), bsub);
+                                   feat_index, feat_value, shared_user(), bsub, isub);
         },
         [&](long w, const WUnitHost &H) { wseq_adopt_window(ds.get(), H, (long)(block_row_ptr[cut[(size_t)w]] - block_row_ptr[0])); },
         ns_wseq_host_, ns_wseq_adopt_);
@@ -1228,8 +1246,10 @@ void Engine::wseq_train(Dataset *ds) {
     if (ds->wseq_block_sub >= 0) {
         check(ds->wseq_block_sub == block_sub(),
               "train_dataset: the window sequence was built with another window_block_sub (ordered sub-steps for hot shared user rows of SVD++ blocks); build the data set again after changing the knob");
-        long most = 0;   // the second record plane: sized once, for the largest window's hot records
-        for (Dataset *c : ds->wchild) if (c->wu_feedback && c->wu_nhot > 0) most = std::max(most, c->wu_nhrec);
+        check(ds->wseq_block_item_sub == block_item_sub(),
+              "train_dataset: the window sequence was built with another window_block_item_sub (ordered sub-steps for hot item rows of SVD++ blocks); build the data set again after changing the knob");
+        long most = 0;   // the second record plane: sized once, for the largest window's hot records (of both sides)
+        for (Dataset *c : ds->wchild) if (c->wu_feedback && c->wu_nhot + c->wu_nihot > 0) most = std::max(most, c->wu_nhrec);
         if (most > 0) { d_hfb_.reserve((size_t)most * (size_t)pitch_); d_hfbb_.reserve((size_t)most); }
     }
     if (ds->wseq_item_sub >= 0)
@@ -1257,7 +1277,11 @@ void Engine::wseq_train(Dataset *ds) {
                 n_launches_++;
                 if (c->wu_feedback) n_block_hot_ += c->wu_nhot;   // counter 35
             }
-            if (c->wu_nihot > 0) { launch_wunit_apply_item(P, wunit_view(c), c->wu_nihot, stream_); n_launches_++; }   // hot item rows likewise (neither launch writes the model)
+            if (c->wu_nihot > 0) {   // hot item rows likewise (neither launch writes the model; user-group windows: the FB build, knob window_block_item_sub -- section 6u)
+                launch_wunit_apply_item(P, wunit_view(c), c->wu_nihot, stream_, c->wu_feedback);
+                n_launches_++;
+                if (c->wu_feedback) n_block_item_hot_ += c->wu_nihot;   // counter 36
+            }
             wunit_sum(c, nullptr, 0);
         }
         n_launches_ += 2;
