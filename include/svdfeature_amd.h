@@ -166,7 +166,13 @@ svdf_dataset *svdf_dataset_from_buffer_file(svdf_trainer *t, const char *path, i
  * on the same pairs.  One call = one pass of the iterator: the reference re-draws the pairs every round, so build a
  * new dataset per round.  Sampler keys are taken from svdf_set_param like the reference's iterator takes them from the
  * config: pos_sample_lowerb, neg_sample_upperb, rank_sample_num, rank_sample_max, rank_sample_method (0, 1),
- * rank_sample_gap, rank_sample_pointwise, seed_sampler_bytime.  Needs format_type = 1. */
+ * rank_sample_gap, rank_sample_pointwise, seed_sampler_bytime.  Needs format_type = 1.
+ * "amd:step" on a one-GPU handle: `minibatch` (and `auto` for the passes after the one that chose the window step for this file) gives a window
+ * sequence (kind 8).  A file of plain rows -- no globals, one user and one item entry per row, every value exactly 1, no feedback ids -- drawn
+ * with rank_sample_method 0 and no pointwise output is drawn AND cut into rank-pair windows (kind-5 children) in HBM: nothing of the pass but
+ * the per-item counts and a few scalars crosses PCIe (counters 7 and 37).  Every other file, a prefetched pass, knob
+ * device_window = 0 or window_pair_sub > 0 keep the route they had: user-unit windows (kind-7 children) built from the drawn blocks on the
+ * host, or the exact pass where the window step does not take the configuration.  Same draws and the same rand() position on every route. */
 svdf_dataset *svdf_dataset_from_rank_buffer_file(svdf_trainer *t, const char *path);
 /* Draws the NEXT pass on a background host thread (the sampler is host work on the mapped file and libc rand(); the
  * device can train the current pass meanwhile).  The next svdf_dataset_from_rank_buffer_file / svdf_rank_sample_buffer_file
@@ -189,7 +195,8 @@ int svdf_predict_dataset(svdf_trainer *t, svdf_dataset *ds, float *out);
 /* dataset facts: 0 num_row, 1 number of conflict-free batches, 2 largest batch, 3 kernel kind
  * (0 = basicMF fused kernel, 1 = general sparse kernel, 2 = few-row fused kernel, 3 = SVD++ user units),
  * 4 algorithmic bytes per pass, 5 number of user units, 6 units on the register-resident
- * fast path, 7 a digest of the host-resident schedule (level boundaries, fast-path split, unit order) */
+ * fast path, 7 a digest of the host-resident schedule (level boundaries, fast-path split, unit order),
+ * 8 a window sequence's (kind 8) kind of windows: 5 plain ratings / rank pairs, 7 user units; -1 for any other data set */
 int64_t svdf_dataset_info(const svdf_dataset *ds, int what);
 
 /* ---- multi-GPU support: item-side parameters are replicated, each rank trains its
@@ -349,7 +356,8 @@ int svdf_synchronize(svdf_trainer *t);
  * keeps a segment's shared rows in registers / by the general lane-group kernel,
  * 35 hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub; the windows count under 34),
  * 36 hot item rows applied in ordered sub-steps on user-group (SVD++) windows, with or without shared user entries (knob window_block_item_sub;
- * DESIGN.md 6u; the windows keep counting where they do without the knob) */
+ * DESIGN.md 6u; the windows keep counting where they do without the knob),
+ * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).

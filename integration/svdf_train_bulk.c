@@ -8,7 +8,8 @@
  *   svdf_train_bulk <config> [name=value ...]
  *
  * input_type 0 / 1: one resident data set for all rounds (svdf_dataset_from_buffer_file);  input_type 2: a new rank-pair pass
- * per round (svdf_dataset_from_rank_buffer_file, pairs drawn on the device when the file's rows are plain). */
+ * per round (svdf_dataset_from_rank_buffer_file, pairs drawn on the device when the file's rows are plain; with amd:step = minibatch / auto
+ * in the configuration such a pass is also cut into windows on the device). */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -276,6 +276,12 @@ Dataset *Engine::dataset_from_rank_buffer_file(const char *path) {
     // exact: the all-in-HBM form below; window: the drawn blocks straight into the window builder.
     const bool auto_on = auto_step_active();
     const bool auto_known = auto_on && auto_rank_path_ == path && auto_rank_decision_ != 0;
+    // the window step on such a file (amd:step = minibatch; auto once the file's first pass chose it): drawn in HBM like the exact form below and
+    // cut into pair windows there.  Declined (nullptr, libc's generator untouched): everything goes on as before
+    if (device_rank_ && !rank_prefetch_ && !host_only_ && (single_minibatch() || (auto_known && auto_rank_decision_ == 2))) {
+        Dataset *ds = rank_pass_device(path, true);
+        if (ds) return ds;
+    }
     if (device_rank_ && device_sched_ && !rank_prefetch_ && !host_only_ && (!multi_ || in_multi_scope()) && (!auto_on || (auto_known && auto_rank_decision_ != 2))) {
         Dataset *ds = rank_pass_device(path);
         if (ds) return ds;
@@ -330,6 +336,8 @@ bool Engine::rank_source_load(const char *path) {
         ok = uv[(size_t)r] > 1e-6f || uv[(size_t)r] < -1e-6f;
     }
     src->eligible = ok && nr < 0x7FFFFFFFL;
+    src->unit_values = src->eligible;   // what the pair windows of the window step carry (rank_pass_device, as_windows)
+    for (long r = 0; r < nr && src->unit_values; r++) src->unit_values = uv[(size_t)r] == 1.0f && iv[(size_t)r] == 1.0f;
     src->general = nr < 0x7FFFFFFFL && nv < 0x7FFFFFFFL;
     if (src->eligible || src->general) {
         need_device("rank input");
@@ -450,16 +458,24 @@ bool Engine::rank_pass_device_general(const char *path, UserGroupArrays &g) {
     return true;
 }
 
-Dataset *Engine::rank_pass_device(const char *path) {
+// what the window form of the pass (as_windows) asks of the configuration: the pair windows' own conditions (window_build_header, with the
+// feedback-free user-group trainer admitted), the device builder, and no lane of ordered sub-steps -- the lane stays refused with user-group
+// trainers (wseq_pair_check), and a run that trains today must not become an error
+bool Engine::rank_window_route_ok() const {
+    return mtype_.extend_type == 0 && !relaxed() && !lazy_decay() && mp_.num_factor <= max_supported_factor() && mp_.common_latent_space == 0 &&
+           feat_user_.num_row() == 0 && feat_item_.num_row() == 0 && device_window_ready() && wseq_pair_sub_ == 0;
+}
+Dataset *Engine::rank_pass_device(const char *path, bool as_windows) {
     if (pair_sampler_.method() != 0 || pair_sampler_.pointwise() != 0) return nullptr;
-    if (!rows_without_feedback_ || !fused_allowed_for_rows()) return nullptr;
+    if (!rows_without_feedback_ || !(as_windows ? rank_window_route_ok() : fused_allowed_for_rows())) return nullptr;
     if (!rank_source_load(path)) return nullptr;
     RankSource &S = *rank_source_;
-    if (!S.eligible) return nullptr;
+    if (!S.eligible || (as_windows && !S.unit_values)) return nullptr;
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
     flush();
     check(!unit_open_, "dataset_from_blocks: a START block is pending in the trainer");
+    const auto draw_t0 = std::chrono::steady_clock::now();
     LibcRand rs;
     if (!libc_rand_capture(rs)) return nullptr;   // a caller-installed generator of another size: the host path just calls rand()
     pair_sampler_.init();
@@ -488,10 +504,6 @@ Dataset *Engine::rank_pass_device(const char *path) {
     S.raw.reserve((size_t)std::max<long>(D_total, 1));
     launch_rand_expand(S.tables.p, nchunks, C, D_total, S.raw.p, stream_);
     // the generated instances, file order
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 2; ds->num_row = P_total;
-    FusedDev &f = ds->fused;
-    f.max_nu = 1; f.max_ni = 2; f.has_g = false; f.inline_g = false;
     DevBuf<float> rl, ruv, rv0, rv1;
     DevBuf<unsigned> rui, ri0, ri1;
     const size_t np = (size_t)std::max<long>(P_total, 1);
@@ -514,6 +526,23 @@ Dataset *Engine::rank_pass_device(const char *path) {
         libc_rand_restore(after);
     }
     HIPCHECK(hipGetLastError());
+    if (as_windows) {
+        HIPCHECK(hipStreamSynchronize(stream_));
+        ns_rank_draw_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - draw_t0).count();
+    }
+    if (as_windows) {   // the columns stay in HBM: item counts, window rule and windows are built there (svdf_wunit.cpp: wseq_from_device_pairs)
+        rows_as_instances_ = true;
+        struct Reset { bool &f; ~Reset() { f = false; } } reset{rows_as_instances_};
+        Dataset *seq = wseq_from_device_pairs(P_total, rui.p, ri0.p, rv0.p, ri1.p);
+        if (!seq) { libc_rand_restore(rs); return nullptr; }   // a pair the windows do not take: the caller draws the pass again on today's route
+        n_device_rank_passes_++;
+        n_rank_window_passes_++;
+        return seq;
+    }
+    std::unique_ptr<Dataset> ds(new Dataset());
+    adopt(ds.get()); ds->kind = 2; ds->num_row = P_total;
+    FusedDev &f = ds->fused;
+    f.max_nu = 1; f.max_ni = 2; f.has_g = false; f.inline_g = false;
     if (P_total > 0) {
         const unsigned *res[3] = {rui.p, ri0.p, ri1.p};
         const unsigned off[3] = {0u, (unsigned)mp_.num_user, (unsigned)mp_.num_user};

@@ -265,6 +265,7 @@ int64_t svdf_dataset_info(const svdf_dataset *ds, int what) {
         for (int v : ds->d->sched.order) mix((uint64_t)(unsigned)v);
         return (int64_t)(h >> 1);
     }
+    case 8: return ds->d->kind == 8 && !ds->d->wchild.empty() ? (int64_t)ds->d->wchild[0]->kind : -1;
     default: return -1;
     }
 }

@@ -217,6 +217,7 @@ int64_t Engine::counter(int what) const {
     case 34: return n_walk_shared_;    // windows walked by the general lane-group kernel
     case 35: return n_block_hot_;      // hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub, section 6q; the windows count under 34)
     case 36: return n_block_item_hot_; // hot item rows applied in ordered sub-steps on user-group (SVD++) windows (knob window_block_item_sub, section 6u)
+    case 37: return n_rank_window_passes_;   // rank passes of a candidate file built as device window sequences (amd:step = minibatch / auto, section 6v); they count under 7 too
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

@@ -136,6 +136,9 @@ Engine::~Engine() {
             fprintf(stderr, "[svdfeature_amd] staged route: %ld chunks trained by the window step, %ld kept exact (rows or configuration outside it); window build %.3fs of the flush time (user-unit windows: host regrouping %.3fs, allocations + uploads + synchronisations %.3fs); "
                             "device blocks from the handle's pool %ld, from hipMalloc %ld\n",
                     (long)n_staged_window_, (long)n_staged_exact_, ns_staged_build_ * 1e-9, ns_wseq_host_ * 1e-9, ns_wseq_adopt_ * 1e-9, (long)staged_pool_.n_taken, (long)staged_pool_.n_missed);
+        if (getenv("SVDF_PROFILE") && n_rank_window_passes_ > 0)
+            fprintf(stderr, "[svdfeature_amd] rank-buffer route: %ld passes built as device window sequences; draw %.3fs, item counts + window rule %.3fs, window build %.3fs\n",
+                    (long)n_rank_window_passes_, ns_rank_draw_ * 1e-9, ns_rank_rule_ * 1e-9, ns_rank_wbuild_ * 1e-9);
         if (pred_pin_) (void)hipHostFree(pred_pin_);
         save_pipe_free(save_pipe_);
         save_pipe_free(save_async_.pipe);

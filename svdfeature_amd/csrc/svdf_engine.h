@@ -246,6 +246,7 @@ struct RankSource {
     std::string path;
     long file_size = -1, file_mtime = -1, file_ino = -1;   // cache key: size, mtime in ns, inode
     bool eligible = false;
+    bool unit_values = false;   // eligible and every row's user and item value is exactly 1 (pair windows carry unit values)
     long num_block = 0, num_row = 0;
     DevBuf<long> block_row_ptr, draws, pairs, draw_off, pair_off;
     DevBuf<float> label, uval, ival;
@@ -580,7 +581,10 @@ class Engine {
     uint64_t schedule_signature() const;
     void disown(Dataset *ds);
     void rank_pass(const char *path, UserGroupArrays &g);
-    Dataset *rank_pass_device(const char *path);   // nullptr when the file or the sampler settings need the host path
+    // nullptr when the file or the sampler settings need the host path.  as_windows: the drawn columns become a window sequence (kind 8 of kind-5
+    // pair windows, wseq_from_device_pairs) instead of an exact level-scheduled pass (kind 2); nullptr also when the windows do not take the pass
+    Dataset *rank_pass_device(const char *path, bool as_windows = false);
+    bool rank_window_route_ok() const;             // what the configuration must satisfy for as_windows (the file's part: RankSource::unit_values)
     bool rank_source_load(const char *path);       // (re)loads rank_source_ for this file; false when it cannot be opened / stat'ed
     bool rank_pass_device_general(const char *path, UserGroupArrays &g);   // any row shape / method: the pass drawn in HBM, blocks back in g
     std::unique_ptr<RankSource> rank_source_;
@@ -661,7 +665,7 @@ class Engine {
     DevBuf<char> wb_tmp_;
     bool window_build_device(Dataset *ds, long n, const unsigned *user, const unsigned *item, const float *label, const unsigned *neg);
     void window_build_resident(Dataset *ds, long n, const unsigned *d_user, const unsigned *d_item, const float *d_label, const unsigned *d_neg);
-    void window_build_header(Dataset *ds, long n, bool pairs);
+    void window_build_header(Dataset *ds, long n, bool pairs, bool rows_as_instances = false);
     // scoring of window data sets (svdf_dataset.cpp): one window's predictions in regrouped order (pos == nullptr) or
     // scattered to out[pos[r]]; returns the window's labels in regrouped order (rank pairs: ones)
     const float *window_score(Dataset *c, float *out, const int *pos);
@@ -806,6 +810,10 @@ class Engine {
                               const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
     Dataset *wseq_from_triples(long n, const unsigned *user, const unsigned *item, const float *label);
     Dataset *wseq_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg);
+    // the same sequence from a pass of rank pairs the device sampler left in HBM (merged item entries i0 / v0 / i1 of unit-value rows, file order):
+    // counts, window rule and windows without the columns visiting the host (svdf_k_rankwin.hip).  nullptr: a pair the windows do not take
+    // (positive and negative row of one item, an id out of range) -- the caller falls back to the route that reports it
+    Dataset *wseq_from_device_pairs(long n, const unsigned *d_user, const unsigned *d_i0, const float *d_v0, const unsigned *d_i1);
     void wseq_train(Dataset *ds);
     WindowSchedule window_view(const Dataset *ds) const;
     Dataset *window_trained_ = nullptr;   // the window data set whose contributions the scratch holds
@@ -834,6 +842,7 @@ class Engine {
     int64_t n_block_item_hot_ = 0;                       // hot item rows applied in ordered sub-steps on user-group windows (counter 36)
     int64_t n_wave_shared_ = 0, n_walk_shared_ = 0;      // user-group windows with shared user entries: walked by the wave form / by the general kernel (counters 33 / 34)
     int64_t ns_staged_build_ = 0;                        // host time of the per-chunk pre-check + window build (part of ns_flush_; SVDF_PROFILE prints it)
+    int64_t ns_rank_draw_ = 0, ns_rank_rule_ = 0, ns_rank_wbuild_ = 0;   // rank passes built as device window sequences: wall time of the draw / of the item counts + window rule / of the windows' regrouping (SVDF_PROFILE prints it)
     int64_t ns_wseq_host_ = 0, ns_wseq_adopt_ = 0;       // user-unit window sequences (wseq_build_windows): wall time of the host regrouping / of the windows' allocations + uploads + synchronisations
     std::string staged_auto_rule_;                       // amd:step = auto, decision 3: the rule that keeps the chunks exact
     long staged_defer_factor_ = 4;                       // a user still open after this many stage_window rows no longer holds back the automatic flush
@@ -888,6 +897,7 @@ class Engine {
     void write_model_from_device(FILE *fo);
     int64_t ns_flush_ = 0, ns_model_ = 0;   // host-side time accounting (SVDF_PROFILE=1 prints it)
     int64_t n_device_rank_passes_ = 0;
+    int64_t n_rank_window_passes_ = 0;   // counter 37: rank passes built as device window sequences
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

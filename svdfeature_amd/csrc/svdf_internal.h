@@ -98,6 +98,25 @@ long wseq_windows_actual(long W, long n, const std::vector<WseqClass> &classes, 
     }
     return last_resort ? n : W;
 }
+// The same search for ONE class without sub-steps (sub 0) whose entries are counted elsewhere (device columns: svdf_k_rankwin.hip): count(W, sum,
+// worst) gives the sum over (row, window) of c^2 -- what WseqCounter::add's 2 v - 1 terms add up to -- and the largest c on the W windows.  The
+// counter's sums are doubles of integers, so the integers give the same excess and the same W.
+template <typename Count>
+long wseq_windows_actual_counted(long W, long n, const WseqClass &k, long entries, double slack, int rounds, bool last_resort, Count count) {
+    if (n <= 0) return W;
+    for (int round = 0; round < rounds; round++) {
+        unsigned long long sum = 0ull, worst = 0ull;
+        count(W, sum, worst);
+        double num = 0.0, den = 1.0;
+        auto take = [&](double a, double b) { if (a / b > num / den) { num = a; den = b; } };
+        if (k.target > 0.0 && entries > 0) take((double)sum / (double)entries, k.target * slack);
+        if (k.cap > 0) take((double)(long)worst, (double)k.cap * slack);
+        if (num <= den) return W;
+        W = std::max<long>(W + 1, (long)std::ceil((double)W * num / den));
+        if (W >= n) return n;
+    }
+    return last_resort ? n : W;
+}
 
 // Pointer arrays handed over by a caller are checked before anything indexes through them (the messages of dataset_from_csr /
 // dataset_from_blocks): counts not negative, pointers starting at >= 0 and non-decreasing, fewer than 2^31 entries.

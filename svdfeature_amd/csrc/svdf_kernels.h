@@ -192,6 +192,18 @@ struct WBuildOut { WinUser *urec; unsigned *item, *item1; float *label, *v0, *v1
                    int *pos; };   // pos: nullptr, or [n] the source position of every regrouped instance (resident data sets: scoring in file order)
 size_t wbuild_tmp_bytes(long m);
 void device_window_build(const WBuildIn &in, const WBuildBuffers &B, const WBuildOut &out, long *nact, long *item_lo, long *item_hi, hipStream_t st);
+// ---- the window rule of a sequence of rank-pair windows on a pass the device sampler left in HBM (svdf_k_rankwin.hip).
+// columns: the sampler's merged item entries (i0, v0, i1) of unit-value rows -> pos / neg item per pair, count[item] += entries (integer atomics),
+// keys / vals (nullptr: not wanted) = the 2 n entries' item and index for the sort; state[0] collects RW_ERR_* bits (such pairs are counted nowhere)
+enum { RW_ERR_USER = 1, RW_ERR_ITEM = 2, RW_ERR_SAME = 4 };
+void launch_rank_window_columns(long n, const unsigned *user, const unsigned *i0, const float *v0, const unsigned *i1, long num_user, long num_item,
+                                unsigned *pos, unsigned *neg, unsigned *keys, unsigned *vals, unsigned *count, unsigned *state, hipStream_t st);
+size_t rank_window_sort_bytes(long E);
+void rank_window_sort(void *tmp, size_t tmp_bytes, const unsigned *keys, unsigned *keys_sorted, const unsigned *vals, unsigned *vals_sorted, long E, long num_item,
+                      hipStream_t st);
+// for W windows cut at n w / W: the sum over (item, window) of c^2 and the largest c, c = the item's entries in the window.  Synchronizes st.
+void rank_window_sums(const unsigned *keys_sorted, const unsigned *vals_sorted, long E, long n, long W, unsigned long long *d_out, unsigned long long *sum,
+                      unsigned long long *worst, hipStream_t st);
 // ---- SVDModel::rand_init on the device (svdf_k_init.hip): the j-th matrix element is the j-th accepted attempt of the polar loop
 struct InitSeg { long begin, count; long row0; int k; float sigma; int absf; };   // elements [begin, begin + count) -> rows row0.. of W, k per row
 struct InitPlan { InitSeg seg[3]; int nseg; long total; int pitch; double margin; };

@@ -49,8 +49,10 @@ Dataset *Engine::dataset_window_from_pairs(long n, const unsigned *user, const u
 }
 // (re)fills ds in place: the staged path of an amd:gpus handle rebuilds one window data set per rank every window.
 // neg != nullptr: rank pairs, `item` holds the positive items and the labels are 1.
-void Engine::window_build_header(Dataset *ds, long n, bool pairs) {
-    check(!user_group() && mtype_.extend_type == 0, "window data sets: random-order trainers only");
+// rows_as_instances: the caller is the rank-buffer route (Engine::wseq_from_device_pairs), whose user-group trainer trains a feedback-free pass --
+// update(block) == update_inner(row), the case dataset_from_blocks schedules row by row; every public entry point keeps the refusal
+void Engine::window_build_header(Dataset *ds, long n, bool pairs, bool rows_as_instances) {
+    check((!user_group() || rows_as_instances) && mtype_.extend_type == 0, "window data sets: random-order trainers only");
     check(window_rows_allowed(), "window data sets: no side tables, relaxed ids, lazy decay or shared latent space");
     check(n >= 0 && n < (1L << 30), "window data sets: at most 2^30-1 instances per window");
     if (window_trained_ == ds) window_trained_ = nullptr;

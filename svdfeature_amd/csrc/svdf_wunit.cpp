@@ -1221,6 +1221,84 @@ Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *p
     W = wseq_actual_columns(W, n, pos, neg, psub, psub > 0 ? wseq_pair_max_ : wseq_per_target_max_);
     return wseq_from_columns(n, user, pos, neg, nullptr, psub, W);
 }
+// The same sequence for a pass of rank pairs that is in HBM already (the device sampler's columns, file order: Engine::rank_pass_device; DESIGN.md
+// section 6v).  What wseq_from_pairs reads from host arrays -- the item counts, the per-pass W, its raise on the windows as cut -- comes from
+// svdf_k_rankwin.hip: only the num_item counts and two integers per search round cross PCIe.  Without the lane of ordered sub-steps (the caller
+// keeps window_pair_sub > 0 off this route).  The windows are regrouped from slices of the columns like wseq_from_columns' resident form.
+Dataset *Engine::wseq_from_device_pairs(long n, const unsigned *d_user, const unsigned *d_i0, const float *d_v0, const unsigned *d_i1) {
+    const long NI = mp_.num_item, E = 2 * n;
+    std::vector<long> ci((size_t)NI, 0);
+    std::unique_ptr<ScopedNs> timer(new ScopedNs(ns_rank_rule_));
+    DevBuf<unsigned> d_pos, d_neg, d_cnt, d_state, k0, k1, v0, v1;
+    const bool actual = wseq_actual_on() && n > 0;
+    if (n > 0) {
+        need_device("dataset");
+        d_pos.reserve((size_t)n); d_neg.reserve((size_t)n); d_cnt.reserve((size_t)std::max<long>(NI, 1)); d_state.reserve(4);
+        if (actual) { k0.reserve((size_t)E); k1.reserve((size_t)E); v0.reserve((size_t)E); v1.reserve((size_t)E); }
+        HIPCHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)std::max<long>(NI, 1) * sizeof(unsigned), stream_));
+        HIPCHECK(hipMemsetAsync(d_state.p, 0, 4 * sizeof(unsigned), stream_));
+        launch_rank_window_columns(n, d_user, d_i0, d_v0, d_i1, mp_.num_user, NI, d_pos.p, d_neg.p, actual ? k0.p : nullptr, actual ? v0.p : nullptr, d_cnt.p, d_state.p,
+                                   stream_);
+        std::vector<unsigned> hc((size_t)NI);
+        unsigned hs[4] = {0u, 0u, 0u, 0u};
+        if (NI > 0) HIPCHECK(hipMemcpyAsync(hc.data(), d_cnt.p, (size_t)NI * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipMemcpyAsync(hs, d_state.p, sizeof(hs), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipStreamSynchronize(stream_));
+        HIPCHECK(hipGetLastError());
+        if (hs[0] != 0u) return nullptr;
+        for (long i = 0; i < NI; i++) ci[(size_t)i] = (long)hc[(size_t)i];
+    }
+    long W = wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
+    if (actual) {
+        try {
+            DevBuf<char> tmp;
+            const size_t tb = rank_window_sort_bytes(E);
+            tmp.reserve(std::max<size_t>(tb, 1));
+            rank_window_sort(tmp.p, tb, k0.p, k1.p, v0.p, v1.p, E, NI, stream_);
+            DevBuf<unsigned long long> d_out;
+            d_out.reserve(2);
+            W = wseq_windows_actual_counted(W, n, WseqClass{NI, (double)wseq_per_target_, (long)wseq_per_target_max_, 0}, E, kWseqSlack, kWseqRounds, true,
+                                            [&](long w, unsigned long long &sum, unsigned long long &worst) {
+                                                rank_window_sums(k1.p, v1.p, E, n, w, d_out.p, &sum, &worst, stream_);
+                                            });
+        } catch (const std::runtime_error &e) {
+            fail(e.what());
+        }
+        k0.release(); k1.release(); v0.release(); v1.release();
+    }
+    timer.reset(new ScopedNs(ns_rank_wbuild_));
+    std::unique_ptr<Dataset> ds(new Dataset());
+    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
+    ds->wseq_pair_sub = 0;
+    for (long w = 0; w < W; w++) {
+        const long b0 = n * w / W, b1 = n * (w + 1) / W;
+        std::unique_ptr<Dataset> c(new Dataset());
+        adopt(c.get());
+        window_build_header(c.get(), b1 - b0, true, true);
+        if (b1 > b0) window_build_resident(c.get(), b1 - b0, d_user + b0, d_pos.p + b0, nullptr, d_neg.p + b0);   // (returns after the window's read-back: the columns outlive every read)
+        else {   // a pass that drew no pair: one window without instances, the arrays of window_build at n = 0
+            need_device("dataset");
+            c->win_urec.reserve(1); c->item.reserve(1); c->win_slot.reserve(1); c->win_item1.reserve(1); c->win_slot1.reserve(1); c->ival.reserve(1); c->win_ival1.reserve(1);
+            c->win_iptr.reserve((size_t)NI + 1);
+            HIPCHECK(hipMemsetAsync(c->win_iptr.p, 0, ((size_t)NI + 1) * sizeof(int), stream_));
+            HIPCHECK(hipStreamSynchronize(stream_));
+            c->win_has_pos = window_keeps_positions();
+            if (c->win_has_pos) c->win_pos.reserve(1);
+            c->sched_signature = schedule_signature();
+            c->win_item_lo = NI; c->win_item_hi = -1;
+            c->unit_values = true;
+            c->num_units = 0;
+            c->sched.level_ptr = {0, 0};
+            c->sched.max_level_size = 0;
+        }
+        ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
+        ds->wchild.push_back(c.release());
+        ds->wfirst.push_back(b0);
+    }
+    ds->sched.level_ptr = {0, n};
+    ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
+    return ds.release();
+}
 
 // one pass over a window sequence: per window the users' walks, then the per-target sums added in place (two launches per window)
 void Engine::wseq_train(Dataset *ds) {
