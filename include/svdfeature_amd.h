@@ -459,6 +459,7 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               user-group trainers, amd:gpus > 1, svdf_dataset_window_from_pairs, num_factor > 256 ("window_pair_sub > 0 needs
  *                                                               num_factor <= 256": the pair lane has no wide rows).  Calibration: profiles/r12_pair_hot.md
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
+ *     rank_eval_budget 4194304   svdf_rank_eval_positions: positives + distinct banned ids + sections processed per piece of whole sections (>= 1)
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
  * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
@@ -518,6 +519,53 @@ int64_t svdf_ranker_process_block(svdf_ranker *r, int num_ufeedback, int extend_
 /* counters: 0 user sections ranked, 1 sections finished by the host sort because scores tied at a requested position,
  * 2 positive samples of the open user section (what a PROCESS line would report now when top_k = 0: sizes the output) */
 int64_t svdf_ranker_counter(svdf_ranker *r, int what);
+
+/* ---- batch ranking evaluation on the LIVE model: where the positives a user held out rank among ALL items, for many
+ * users in one call, and the reference's ranking metrics (apex-utils/apex_evaluator.h:33-215) of those positions.  No model file, no
+ * second handle, no candidate matrix: the sweep reads W_item where the trainer keeps it.
+ *
+ * A format_type = 0, extend_type = 0 trainer with its model in HBM.  Section s of S: the user user[s], its held-out positives
+ * pos_item[pos_ptr[s] .. pos_ptr[s + 1]) and its banned items ban_item[ban_ptr[s] .. ban_ptr[s + 1]) -- the user's training items;
+ * ban_ptr == NULL: none.  The candidates of every section are the item ids 0 .. num_item - 1; a candidate is RANKED unless it is banned,
+ * positives are ranked candidates like any other.  The score of candidate i is proc_rank's (apex_svd_base.h:754-765) for a USER line
+ * user[s]:1 and ITEM lines i:1: i_bias[i] + <W_user[user[s]], W_item[i]> in the ranker's fp32 order, bit for bit what svdf_ranker_*
+ * computes from the saved model (no user bias, no base score, no link).  For positive p (entry j of pos_item):
+ *   position_out[j] = ranked candidates scoring strictly higher than p + ranked candidates c != p with score_c == score_p and c < p
+ *   tied_out[j]     = ranked candidates c != p with score_c == score_p
+ * +0 and -0 compare equal.  The reference shuffles before it sorts (apex_evaluator.h:178), so its order inside a tie is random; here a
+ * tie is broken by item id, and tied_out says where that happened (tied == 0: the position is the ranker's, index for index).
+ *   ranked_out[s]   = num_item - distinct banned ids of the section
+ *   nan_out[s]      = 1 when a ranked candidate (a positive included) scores NaN: the section's positions are -1, the metrics skip it
+ * Duplicate ban ids count once.  Refused, with the ranker's messages: a positive that is also banned ("each pos sample item can not occur
+ * in baned sample list"), ids out of range ("user feature index exceed bound", "sample item index exceed bound"); a positive repeated
+ * inside a section.  A section without positives returns nothing.  A user may appear in several sections.  Everything is validated on
+ * the host before any device work.  The call runs on the trainer's stream behind the passes already queued and returns when the results
+ * are on the host; a stand-alone window trained but not yet applied is ranked against the model without its pending sums (see
+ * svdf_predict_dataset).  Lists of more than `rank_eval_budget` entries (knob, default 4194304 positives + distinct bans + sections) are
+ * processed in pieces of whole sections.  Counter 38 counts the sections ranked.
+ * Refused, each with its cause: user-group trainers and extend_type != 0, feature_user / feature_item side tables (they change the
+ * score), common_latent_space != 0, amd:gpus > 1 and the per-rank handles of the exchange schemes, host-only handles ("needs a GPU").
+ * svdf_ranker_* remains the route for those.
+ *
+ * svdf_rank_eval_metrics is a host function (no GPU, no handle): sections [sec_ptr[s], sec_ptr[s + 1]) of position[], each sorted ascending
+ * first (add_eval(pos_idx, false)), then added in section order in double precision exactly as EvaluatorMAP::add_eval / print_result do
+ * -- MAP sum_i (i + 1) / (pos_i + 1) / npos; MAP@k, Pre@k, Rec@k with the counter j of :146-166 and the FLOAT running sum sum_ar of
+ * :138-142 -- for up to 8 cut-offs, handled in ascending order (out->at).  The figures the reference prints are sum / ninst.  Empty
+ * sections and sections with nan[s] != 0 (nan may be NULL) are no instances: they count under skipped / nan_sections.  With ranked != NULL
+ * a per-section AUC, which is NOT in the reference, is added too: positives sorted, 0-based,
+ * AUC_s = 1 - sum_i (pos_i - i) / ((double)npos * (double)(ranked[s] - npos)), left out when ranked[s] == npos (nauc counts the rest).
+ * Positions from svdf_ranker_process_* can be fed as well.  svdf_rank_eval does both steps. */
+typedef struct svdf_rank_metrics {
+    int64_t ninst, skipped, nan_sections, nauc;
+    int num_at, at[8];                 /* the cut-offs, ascending */
+    double sum_map, sum_map_at[8], sum_pre_at[8], sum_rec_at[8], sum_auc;
+} svdf_rank_metrics;
+int svdf_rank_eval_positions(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item,
+                             const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out);
+int svdf_rank_eval_metrics(long num_section, const int64_t *sec_ptr, const int *position, const int *ranked, const int *nan, int num_at,
+                           const int *at, svdf_rank_metrics *out);
+int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item,
+                   const int64_t *ban_ptr, const unsigned *ban_item, int num_at, const int *at, svdf_rank_metrics *out);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

@@ -35,6 +35,44 @@ class SvdfError(RuntimeError):
     pass
 
 
+class RankMetrics(C.Structure):
+    """struct svdf_rank_metrics (include/svdfeature_amd.h)"""
+    _fields_ = [("ninst", C.c_int64), ("skipped", C.c_int64), ("nan_sections", C.c_int64), ("nauc", C.c_int64), ("num_at", C.c_int), ("at", C.c_int * 8),
+                ("sum_map", C.c_double), ("sum_map_at", C.c_double * 8), ("sum_pre_at", C.c_double * 8), ("sum_rec_at", C.c_double * 8), ("sum_auc", C.c_double)]
+
+    def as_dict(self):
+        """the raw sums and counts, and the figures EvaluatorMAP::print_result divides out of them (sum / ninst)"""
+        n, at = self.ninst, list(self.at[:self.num_at])
+        d = {"ninst": n, "skipped": self.skipped, "nan_sections": self.nan_sections, "nauc": self.nauc, "at": at, "sum_map": self.sum_map,
+             "sum_map_at": list(self.sum_map_at[:self.num_at]), "sum_pre_at": list(self.sum_pre_at[:self.num_at]),
+             "sum_rec_at": list(self.sum_rec_at[:self.num_at]), "sum_auc": self.sum_auc}
+        if n:
+            d["MAP"] = self.sum_map / n
+            for j, k in enumerate(at):
+                d["MAP@%d" % k], d["Pre@%d" % k], d["Rec@%d" % k] = self.sum_map_at[j] / n, self.sum_pre_at[j] / n, self.sum_rec_at[j] / n
+        if self.nauc:
+            d["AUC"] = self.sum_auc / self.nauc   # not in the reference
+        return d
+
+
+def _opt_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def rank_metrics(sec_ptr, position, ranked=None, nan=None, at=(1, 5, 10, 100)):
+    """svdf_rank_eval_metrics: the reference's MAP / MAP@k / Pre@k / Rec@k sums (EvaluatorMAP) over sections of rank positions, plus a
+    per-section AUC when `ranked` is given.  A host function: no GPU, no handle.  Returns RankMetrics.as_dict()."""
+    lib = load_library()
+    sec_ptr = _pad(sec_ptr, np.int64)
+    ranked = None if ranked is None else _pad(ranked, np.int32)
+    nan = None if nan is None else _pad(nan, np.int32)
+    m = RankMetrics()
+    if lib.svdf_rank_eval_metrics(len(sec_ptr) - 1, sec_ptr, _pad(position, np.int32), _opt_ptr(ranked), _opt_ptr(nan), len(at), _pad(list(at), np.int32),
+                                  C.byref(m)) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return m.as_dict()
+
+
 def load_library():
     """dlopen libsvdfeature_amd.so and declare every prototype of include/svdfeature_amd.h."""
     global _lib
@@ -151,6 +189,9 @@ def load_library():
     lib.svdf_set_knob.argtypes = [P, C.c_char_p, C.c_long]
     lib.svdf_schedule_resources.argtypes = [C.c_long, _i64p, _u32p, C.c_long, _i32p, _i64p, C.c_long]
     lib.svdf_eval_dataset.argtypes = [P, P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.svdf_rank_eval_positions.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
+    lib.svdf_rank_eval_metrics.argtypes = [C.c_long, _i64p, _i32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_rank_eval.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -604,6 +645,36 @@ class Trainer:
         out = np.zeros(max(ds.num_row, 1), dtype=np.float32)
         self._ok(self.lib.svdf_predict_dataset(self.h, ds.h, out))
         return out[:ds.num_row]
+
+    # -- batch ranking evaluation on the live model (svdf_rank_eval_*)
+    @staticmethod
+    def _rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item):
+        users, pos_ptr = np.ascontiguousarray(users, np.uint32), _pad(pos_ptr, np.int64)
+        if len(pos_ptr) != len(users) + 1:
+            raise SvdfError("rank_eval: pos_ptr must have one entry more than users")
+        if ban_ptr is not None:
+            ban_ptr, ban_item = _pad(ban_ptr, np.int64), _pad(ban_item if ban_item is not None else [], np.uint32)
+            if len(ban_ptr) != len(users) + 1:
+                raise SvdfError("rank_eval: ban_ptr must have one entry more than users")
+        return users, pos_ptr, _pad(pos_item, np.uint32), ban_ptr, (ban_item if ban_ptr is not None else None)
+
+    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None):
+        """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section."""
+        users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
+        S, n = len(users), int(pos_ptr[-1]) if len(users) else 0
+        position, tied = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        ranked, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+        self._ok(self.lib.svdf_rank_eval_positions(self.h, S, _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
+                                                   position, tied, ranked, nan))
+        return position[:n], tied[:n], ranked[:S], nan[:S]
+
+    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100)):
+        """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict)."""
+        users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
+        m = RankMetrics()
+        self._ok(self.lib.svdf_rank_eval(self.h, len(users), _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
+                                         len(at), _pad(list(at), np.int32), C.byref(m)))
+        return m.as_dict()
 
     # -- multi-GPU item-side delta
     def item_delta_begin(self):

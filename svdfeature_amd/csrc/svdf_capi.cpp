@@ -11,6 +11,8 @@
 #include "svdf_kernels.h"
 
 namespace svdf {
+void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, const int *ranked, const int *nan, int num_at, const int *at,
+                       svdf_rank_metrics *out);
 void set_error_mode(int m);
 const char *last_error();
 void note_error(const std::string &m);
@@ -295,6 +297,26 @@ int svdf_set_knob(svdf_trainer *t, const char *name, long value) { SVDF_GUARD(-1
 
 int svdf_eval_dataset(svdf_trainer *t, svdf_dataset *ds, float scale_score, double *sum_sq_err, int64_t *count) {
     SVDF_GUARD(-1, { t->e->eval_dataset(ds->d, scale_score, sum_sq_err, count); return 0; })
+}
+
+/* ---- batch ranking evaluation on the live model ---- */
+int svdf_rank_eval_positions(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item,
+                             const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
+    SVDF_GUARD(-1, { t->e->rank_eval_positions(num_section, user, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out); return 0; })
+}
+int svdf_rank_eval_metrics(long num_section, const int64_t *sec_ptr, const int *position, const int *ranked, const int *nan, int num_at,
+                           const int *at, svdf_rank_metrics *out) {
+    SVDF_GUARD(-1, { svdf::rank_eval_metrics(num_section, sec_ptr, position, ranked, nan, num_at, at, out); return 0; })
+}
+int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item,
+                   const int64_t *ban_ptr, const unsigned *ban_item, int num_at, const int *at, svdf_rank_metrics *out) {
+    SVDF_GUARD(-1, {
+        const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
+        std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
+        t->e->rank_eval_positions(num_section, user, pos_ptr, pos_item, ban_ptr, ban_item, position.data(), tied.data(), ranked.data(), nan.data());
+        svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
+        return 0;
+    })
 }
 
 /* ---- ISVDRanker ---- */

@@ -444,6 +444,9 @@ class Engine {
     void train_dataset(Dataset *ds);
     void predict_dataset(Dataset *ds, float *out);
     void eval_dataset(Dataset *ds, float scale, double *sum_sq, int64_t *count);
+    // batch ranking evaluation on the live model (svdf_rankeval.cpp, svdf_k_rankeval.hip)
+    void rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
+                             const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out);
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -898,6 +901,10 @@ class Engine {
     int64_t ns_flush_ = 0, ns_model_ = 0;   // host-side time accounting (SVDF_PROFILE=1 prints it)
     int64_t n_device_rank_passes_ = 0;
     int64_t n_rank_window_passes_ = 0;   // counter 37: rank passes built as device window sequences
+    int64_t n_rank_eval_sections_ = 0;   // counter 38: sections ranked by the batch evaluation's sweep
+    long rank_eval_budget_ = 1L << 22;   // knob rank_eval_budget: positives + distinct bans + sections of one piece
+    DevBuf<int> re_in_, re_cnt_;
+    DevBuf<float> re_ps_;
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -259,5 +259,28 @@ void device_scatter_f32(const float *src, const int *order, float *dst, long n, 
 // test probe: out[j] = device expf of in[j], or (in == nullptr) of the float with bit pattern first + j*step
 int device_expf(const float *in, unsigned first, unsigned step, float *out, long n);
 
+// ---- batch ranking evaluation on the live model (svdf_k_rankeval.hip): one piece of whole sections.  Every index is
+// local to the piece and has been validated on the host.  A ROW of the sweep is a section or, for a section with more positives than a
+// tile keeps thresholds, a slice of its positives; consecutive rows hold consecutive positives.
+constexpr int RANK_EVAL_TILE_POS = 512;   // thresholds (positives) one sweep tile keeps in LDS; also the most positives of one row
+struct RankEvalDev {
+    int nsec;                   // sections of the piece
+    const unsigned *sec_user;   // [nsec]
+    const int *sec_p0;          // [nsec + 1] positives of section s: [sec_p0[s], sec_p0[s + 1])
+    long npos;
+    const int *pos_item, *pos_sec;   // [npos]
+    float *pos_score;                // [npos] written by k_rank_eval_pos
+    int *greater, *tied, *before;    // [npos] zeroed by the caller
+    int *nan_cnt;                    // [nsec] ranked candidates with a NaN score, zeroed by the caller
+    int nrow, ntile;
+    const int *row_sec, *row_first;  // [nrow] the row's section; 1 on the first row of a section (it counts the NaNs)
+    const int *row_p0;               // [nrow + 1]
+    const int *tile_r0;              // [ntile + 1] rows of tile t: at most rank_eval_tile_rows() of them, at most RANK_EVAL_TILE_POS positives
+    long nban;
+    const int *ban_sec, *ban_item;   // [nban] distinct (section, banned id) pairs
+};
+int rank_eval_tile_rows(const DevParams &P);
+void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st);   // positives' scores, the counting sweep, the ban correction
+
 }  // namespace svdf
 #endif

@@ -1,0 +1,218 @@
+// svdf_rankeval.cpp -- batch ranking evaluation on the live model: the host side of svdf_rank_eval_positions
+// (validation, pieces, rows and tiles of the sweep in svdf_k_rankeval.hip) and the reference's ranking metrics over positions
+// (apex-utils/apex_evaluator.h:33-215), which need no GPU.
+#include <svdfeature_amd.h>
+
+#include <climits>
+#include <cstring>
+
+#include "svdf_internal.h"
+#include "svdf_kernels.h"
+
+namespace svdf {
+
+// EvaluatorMAP::add_eval(pos_idx, false) per section and the sums print_result divides by ninst.  `sum_ar` is the reference's
+// std::vector<float>: the running sum MAP@k reads has been rounded to float, and `sum_ar[j - 1] / pos_idx.size()` is a FLOAT division
+// (the size converts to float) whose quotient is then added in double.
+void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, const int *ranked, const int *nan, int num_at, const int *at,
+                       svdf_rank_metrics *out) {
+    check(S >= 0 && (S == 0 || sec_ptr) && out, "rank_eval_metrics: bad arguments");
+    check(num_at >= 0 && num_at <= 8 && (num_at == 0 || at), "rank_eval_metrics: up to 8 cut-offs");
+    memset(out, 0, sizeof(*out));
+    out->num_at = num_at;
+    for (int i = 0; i < num_at; i++) { check(at[i] >= 1, "rank_eval_metrics: a cut-off must be at least 1"); out->at[i] = at[i]; }
+    std::sort(out->at, out->at + num_at);   // init(): the at lists are sorted
+    if (S > 0) check(sec_ptr[0] >= 0, "rank_eval_metrics: section pointers must start at >= 0");
+    std::vector<int> pos;
+    std::vector<float> sum_ar;
+    for (long s = 0; s < S; s++) {
+        check(sec_ptr[s + 1] >= sec_ptr[s], "rank_eval_metrics: section pointers must not decrease");
+        const size_t n = (size_t)(sec_ptr[s + 1] - sec_ptr[s]);
+        if (n == 0) { out->skipped++; continue; }   // add_eval would assert: "no positive record presented"
+        if (nan && nan[s]) { out->nan_sections++; continue; }
+        pos.assign(position + sec_ptr[s], position + sec_ptr[s + 1]);
+        std::sort(pos.begin(), pos.end());
+        check(pos[0] >= 0, "rank_eval_metrics: negative position in a section that is not flagged");
+        double sumap = 0.0;
+        sum_ar.clear();
+        for (size_t i = 0; i < n; i++) {
+            const double pp = ((double)(i + 1)) / (pos[i] + 1);
+            sumap += pp;
+            sum_ar.push_back((float)sumap);
+        }
+        out->sum_map += sumap / n;
+        size_t j = 0;
+        for (int i = 0; i < num_at; i++) {
+            while (j < n && pos[j] < out->at[i]) j++;
+            if (j != 0) out->sum_map_at[i] += sum_ar[j - 1] / n;
+        }
+        j = 0;
+        for (int i = 0; i < num_at; i++) {
+            while (j < n && pos[j] < out->at[i]) j++;
+            out->sum_pre_at[i] += ((double)j) / out->at[i];
+        }
+        j = 0;
+        for (int i = 0; i < num_at; i++) {
+            while (j < n && pos[j] < out->at[i]) j++;
+            out->sum_rec_at[i] += ((double)j) / n;
+        }
+        out->ninst++;
+        if (ranked && (int64_t)ranked[s] > (int64_t)n) {   // AUC (not in the reference): the share of (positive, other ranked candidate) pairs in the right order
+            int64_t above = 0;
+            for (size_t i = 0; i < n; i++) above += (int64_t)pos[i] - (int64_t)i;
+            out->sum_auc += 1.0 - (double)above / ((double)n * (double)((int64_t)ranked[s] - (int64_t)n));
+            out->nauc++;
+        }
+    }
+}
+
+void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
+                                 const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
+    // ---- what the batch call does not cover (svdf_ranker_* does)
+    check(!user_group() && mtype_.extend_type == 0,
+          "rank_eval: user-group trainers (format_type = 1) and extend_type != 0 are not covered: the score has a feedback part; rank the saved model with svdf_ranker_*");
+    check(name_feat_user_ == "NULL" && name_feat_item_ == "NULL",
+          "rank_eval: feature_user / feature_item side tables change the score and are not covered; rank the saved model with svdf_ranker_*");
+    check(mp_.common_latent_space == 0, "rank_eval: common_latent_space != 0 is not covered; rank the saved model with svdf_ranker_*");
+    check(gpus_ == 1 && !multi_, "rank_eval: amd:gpus > 1 is not covered (the model is spread over the ranks); rank the saved model with svdf_ranker_*");
+    check(!is_peer_ && !ipc_ && !rccl_, "rank_eval: a rank handle of the one-process-per-GPU exchange holds a partition in flight; rank the saved model with svdf_ranker_*");
+    check(space_allocated_ && trainer_ready_, "rank_eval: call init_model / load_model and init_trainer first");
+    // ---- the lists, before any device work
+    check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
+    const long num_item = mp_.num_item;
+    std::vector<int64_t> ban_first((size_t)S + 1, 0);   // distinct (section, banned id) pairs of sections WITH positives: [ban_first[s], ban_first[s + 1])
+    std::vector<int> ban_ids;
+    if (S > 0) {
+        check(pos_ptr[0] >= 0, "rank_eval: pos_ptr must start at >= 0");
+        check(!ban_ptr || ban_ptr[0] >= 0, "rank_eval: ban_ptr must start at >= 0");
+        for (long s = 0; s < S; s++) {
+            check(pos_ptr[s + 1] >= pos_ptr[s], "rank_eval: pos_ptr must not decrease");
+            check(!ban_ptr || ban_ptr[s + 1] >= ban_ptr[s], "rank_eval: ban_ptr must not decrease");
+        }
+        check(pos_ptr[S] == 0 || pos_item, "rank_eval: pos_item is missing");
+        check(!ban_ptr || ban_ptr[S] == 0 || ban_item, "rank_eval: ban_item is missing");
+        std::vector<long> stamp((size_t)num_item, 0);   // 2 s + 1: banned in section s, 2 s + 2: positive of section s
+        for (long s = 0; s < S; s++) {
+            check(user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
+            long nban = 0;
+            const bool keep = pos_ptr[s + 1] > pos_ptr[s];
+            if (ban_ptr)
+                for (int64_t j = ban_ptr[s]; j < ban_ptr[s + 1]; j++) {
+                    const unsigned b = ban_item[j];
+                    check((long)b < num_item, "sample item index exceed bound");
+                    if (stamp[b] == 2 * s + 1) continue;   // the ranker's tag write is idempotent
+                    stamp[b] = 2 * s + 1;
+                    nban++;
+                    if (keep) ban_ids.push_back((int)b);
+                }
+            for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
+                const unsigned p = pos_item[j];
+                check((long)p < num_item, "sample item index exceed bound");
+                check(stamp[p] != 2 * s + 1, "each pos sample item can not occur in baned sample list");
+                check(stamp[p] != 2 * s + 2, "rank_eval: a positive item is repeated inside a section");
+                stamp[p] = 2 * s + 2;
+            }
+            ban_first[(size_t)s + 1] = (int64_t)ban_ids.size();
+            ranked_out[s] = (int)(num_item - nban);
+            nan_out[s] = 0;
+        }
+    }
+    need_device("rank_eval");
+    if (S == 0 || pos_ptr[S] == pos_ptr[0]) return;
+    flush();   // behind whatever has been staged
+    const DevParams &P = params();
+    const int tile_rows = rank_eval_tile_rows(P);
+    std::vector<int> in, back;
+    for (long s0 = 0; s0 < S;) {
+        // ---- a piece of whole sections within the device budget
+        long s1 = s0;
+        int64_t load = 0;
+        while (s1 < S) {
+            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1;
+            if (s1 > s0 && load + add > rank_eval_budget_) break;
+            load += add;
+            s1++;
+        }
+        const long nsec = s1 - s0;
+        const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
+        check(npos < INT_MAX / 4 && nban < INT_MAX / 4, "rank_eval: one section with more than 2^29 entries");
+        if (npos == 0) { s0 = s1; continue; }
+        // ---- rows (a section, or a slice of its positives) and tiles of rows
+        std::vector<int> row_sec, row_first, row_p0, tile_r0;
+        for (long s = s0; s < s1; s++) {
+            const int p0 = (int)(pos_ptr[s] - pos_ptr[s0]), p1 = (int)(pos_ptr[s + 1] - pos_ptr[s0]);
+            for (int a = p0; a < p1; a += RANK_EVAL_TILE_POS) { row_sec.push_back((int)(s - s0)); row_first.push_back(a == p0 ? 1 : 0); row_p0.push_back(a); }
+        }
+        row_p0.push_back((int)npos);
+        const int nrow = (int)row_sec.size();
+        for (int r = 0; r < nrow;) {
+            tile_r0.push_back(r);
+            int e = r + 1;
+            while (e < nrow && e - r < tile_rows && row_p0[(size_t)e + 1] - row_p0[(size_t)r] <= RANK_EVAL_TILE_POS) e++;
+            r = e;
+        }
+        tile_r0.push_back(nrow);
+        const int ntile = (int)tile_r0.size() - 1;
+        // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item
+        in.clear();
+        auto put = [&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
+        const size_t o_user = put((size_t)nsec), o_sp0 = put((size_t)nsec + 1), o_pitem = put((size_t)npos), o_psec = put((size_t)npos);
+        for (long s = s0; s < s1; s++) {
+            in[o_user + (size_t)(s - s0)] = (int)user[s];
+            in[o_sp0 + (size_t)(s - s0)] = (int)(pos_ptr[s] - pos_ptr[s0]);
+            for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
+                in[o_pitem + (size_t)(j - pos_ptr[s0])] = (int)pos_item[j];
+                in[o_psec + (size_t)(j - pos_ptr[s0])] = (int)(s - s0);
+            }
+        }
+        in[o_sp0 + (size_t)nsec] = (int)npos;
+        const size_t o_rsec = put((size_t)nrow), o_rfirst = put((size_t)nrow), o_rp0 = put((size_t)nrow + 1), o_tile = put((size_t)ntile + 1);
+        std::copy(row_sec.begin(), row_sec.end(), in.begin() + (long)o_rsec);
+        std::copy(row_first.begin(), row_first.end(), in.begin() + (long)o_rfirst);
+        std::copy(row_p0.begin(), row_p0.end(), in.begin() + (long)o_rp0);
+        std::copy(tile_r0.begin(), tile_r0.end(), in.begin() + (long)o_tile);
+        const size_t o_bsec = put((size_t)nban), o_bitem = put((size_t)nban);
+        for (long s = s0; s < s1; s++)
+            for (int64_t j = ban_first[(size_t)s]; j < ban_first[(size_t)s + 1]; j++) {
+                in[o_bsec + (size_t)(j - ban_first[(size_t)s0])] = (int)(s - s0);
+                in[o_bitem + (size_t)(j - ban_first[(size_t)s0])] = ban_ids[(size_t)j];
+            }
+        re_in_.upload(in.data(), in.size(), stream_);
+        const size_t ncnt = 3 * (size_t)npos + (size_t)nsec;
+        re_cnt_.reserve(ncnt);
+        re_ps_.reserve((size_t)npos);
+        HIPCHECK(hipMemsetAsync(re_cnt_.p, 0, ncnt * sizeof(int), stream_));
+        RankEvalDev D;
+        D.nsec = (int)nsec;
+        D.sec_user = reinterpret_cast<const unsigned *>(re_in_.p + o_user);
+        D.sec_p0 = re_in_.p + o_sp0;
+        D.npos = (long)npos;
+        D.pos_item = re_in_.p + o_pitem; D.pos_sec = re_in_.p + o_psec;
+        D.pos_score = re_ps_.p;
+        D.greater = re_cnt_.p; D.tied = re_cnt_.p + npos; D.before = re_cnt_.p + 2 * npos; D.nan_cnt = re_cnt_.p + 3 * npos;
+        D.nrow = nrow; D.ntile = ntile;
+        D.row_sec = re_in_.p + o_rsec; D.row_first = re_in_.p + o_rfirst; D.row_p0 = re_in_.p + o_rp0; D.tile_r0 = re_in_.p + o_tile;
+        D.nban = (long)nban;
+        D.ban_sec = re_in_.p + o_bsec; D.ban_item = re_in_.p + o_bitem;
+        launch_rank_eval(P, D, stream_);
+        HIPCHECK(hipGetLastError());
+        n_launches_ += 2 + (nban > 0 ? 1 : 0);
+        back.resize(ncnt);
+        HIPCHECK(hipMemcpyAsync(back.data(), re_cnt_.p, ncnt * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipStreamSynchronize(stream_));
+        for (long s = s0; s < s1; s++) {
+            if (pos_ptr[s + 1] == pos_ptr[s]) continue;
+            const bool bad = back[3 * (size_t)npos + (size_t)(s - s0)] != 0;
+            nan_out[s] = bad ? 1 : 0;
+            for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
+                const size_t q = (size_t)(j - pos_ptr[s0]);
+                position_out[j] = bad ? -1 : back[q] + back[2 * (size_t)npos + q];
+                tied_out[j] = bad ? -1 : back[(size_t)npos + q];
+            }
+            n_rank_eval_sections_++;
+        }
+        s0 = s1;
+    }
+}
+
+}  // namespace svdf
