@@ -832,7 +832,7 @@ void launch_window_apply(const DevParams &P, const WindowSchedule &S, long num_i
 //   * whether h is the lower or the higher id of the pair decides which of q_lo / q_hi is the LDS row (the order of the bias sum and of tmp_i is the walk's);
 //   * because other workgroups read h's window-start row meanwhile, NOTHING here writes the model: the finished row and bias go to h's first slot, and
 //     k_window_pair_sums -- the next launch -- moves them in while it adds the other items' slots in place (section 6m's order: walk, hot apply, sums).
-// Equals tests/item_hot_sim.py on pair-shaped rows bit for bit (tests/test_gpu_pair_hot_window.py).
+// Equals tests/window_sim.py on pair-shaped rows bit for bit (tests/test_gpu_pair_hot_window.py).
 template <int LPI, int NT>
 __global__ __launch_bounds__(NT) void k_window_apply_pairs(const DevParams P, const WindowSchedule S, long num_item) {
     constexpr int G = NT / LPI;

@@ -5,15 +5,15 @@ k_wunit_apply_hot<LPI, true, true>): random widths, links,
 user bias, scale_lr_ufeedback), block shapes (1 ... 12 rows, START / MIDDLE / END spans, feedback lists of 0 ... 90 ids, one or two item entries
 per row, non-unit item values, 2 ... 14 items), with and without shared user ids (`amd:shared_user_from`, then `window_block_sub` on at random as
 well), sub-steps of 1 ... 40, window counts, passes and the knobs wunit_fast / wunit_defer_fb -- `amd:step = minibatch` on one GPU against the
-checker of tests/block_item_hot_sim.py, bit for bit, and counters 35 / 36 against the checker's counts of hot rows.
+checker of tests/window_sim.py, bit for bit, and counters 35 / 36 against the checker's counts of hot rows.
 usage: python tests/fuzz_block_item_hot.py --iters 150 --seed 1"""
 import argparse, json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import block_item_hot_sim as sim
 import cases
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 
 
@@ -55,7 +55,7 @@ def one(rng):
     shared = bool(rng.random() < 0.4)
     max_shared = min(ns, int(rng.integers(1, 5))) if shared else 0
     nblocks = int(rng.integers(1, 40))
-    blocks = sim.shared_blocks(rng, nblocks, npv, ns, ni, nf, max_rows=int(rng.integers(1, 13)), max_fb=min(nf, int(rng.choice([0, 3, 20, 90]))),
+    blocks = ws.shared_blocks(rng, nblocks, npv, ns, ni, nf, max_rows=int(rng.integers(1, 13)), max_fb=min(nf, int(rng.choice([0, 3, 20, 90]))),
                                max_shared=max_shared, min_shared=0, per_row=bool(rng.random() < 0.4), uvals=bool(rng.random() < 0.5) if shared else False,
                                split_every=int(rng.choice([0, 2, 4])), binary=active != 0)
     two, vals = bool(rng.random() < 0.4), bool(rng.random() < 0.5)
@@ -82,10 +82,10 @@ def one(rng):
     for _ in range(passes):
         t.train_dataset(ds)
     t.synchronize()
-    o = sim.make_oracle(conf, active=active)
-    nuh, nih = sim.simulate(o, ba, npv if shared else npv + ns, ds.num_batches, passes, isub, sub, user_bias=extra.get("no_user_bias") != "1")
+    o = ws.make_oracle(conf, active=active, user_group=True)
+    nuh, nih = ws.simulate_blocks(o, ba, npv if shared else npv + ns, ds.num_batches, passes, isub=isub, sub=sub, user_bias=extra.get("no_user_bias") != "1")
     bad = []
-    for name in sim.VIEWS:
+    for name in ws.VIEWS:
         a, b = t.view(name), o.view(name)
         if a is None or b is None or b.size == 0:
             continue

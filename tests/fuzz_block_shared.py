@@ -4,15 +4,15 @@
 links, regularisers (per-id user decay ranges over the shared ids, nonnegative users, no user bias, scale_lr_ufeedback), block shapes (1 ... 12
 rows, START / MIDDLE / END spans, feedback lists of 0 ... 90 ids, 0 ... 5 shared ids with the private entry anywhere, one section per block or per
 row, non-unit values), window counts, passes and the knobs wunit_fast / wunit_defer_fb -- `amd:step = minibatch` on one GPU against the checker
-of tests/block_shared_sim.py, bit for bit.
+of tests/window_sim.py, bit for bit.
 usage: python tests/fuzz_block_shared.py --iters 150 --seed 1"""
 import argparse, json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import block_shared_sim as sim
 import cases
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays
 
 
@@ -38,7 +38,7 @@ def one(rng):
     uvals = rng.choice(["", "shared", "all"], p=[0.3, 0.5, 0.2])
     max_shared = min(ns, int(rng.integers(0, 6)))
     nblocks = int(rng.integers(1, 40))
-    blocks = sim.shared_blocks(rng, nblocks, npv, ns, ni, nf, max_rows=int(rng.integers(1, 13)), max_fb=min(nf, int(rng.choice([0, 3, 20, 90]))),
+    blocks = ws.shared_blocks(rng, nblocks, npv, ns, ni, nf, max_rows=int(rng.integers(1, 13)), max_fb=min(nf, int(rng.choice([0, 3, 20, 90]))),
                                max_shared=max_shared, min_shared=int(rng.integers(0, max_shared + 1)), per_row=per_row,
                                uvals={"": False, "shared": True, "all": "all"}[str(uvals)], split_every=int(rng.choice([0, 2, 4])), binary=active != 0)
     ba = BlockArrays.from_blocks(blocks)
@@ -57,9 +57,10 @@ def one(rng):
     for _ in range(passes):
         t.train_dataset(ds)
     t.synchronize()
-    o = sim.simulate(sim.make_oracle(conf, active=active), ba, npv, ds.num_batches, passes, user_bias=extra.get("no_user_bias") != "1")
+    o = ws.make_oracle(conf, active=active, user_group=True)
+    ws.simulate_blocks(o, ba, npv, ds.num_batches, passes, user_bias=extra.get("no_user_bias") != "1")
     bad = []
-    for name in sim.VIEWS:
+    for name in ws.VIEWS:
         a, b = t.view(name), o.view(name)
         if a is None or b is None or b.size == 0:
             continue

@@ -3,7 +3,7 @@
 `window_pair_sub`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs).  Random widths (the two
 slots-walk widths drawn often), links, regularisers (per-id decay ranges on both sides, nonnegative users, user bias on and off, bias decays),
 catalogue sizes, skew (0 ... 4 hot items, drawn as positive and as negative with random probabilities), window sizes, passes and a random
-sub-step 1 ... 16 (1 ... 128 in one draw of eight): `amd:step = minibatch` on one GPU against the checker of tests/item_hot_sim.py on the
+sub-step 1 ... 16 (1 ... 128 in one draw of eight): `amd:step = minibatch` on one GPU against the checker of tests/window_sim.py on the
 pair-shaped rows, bit for bit.
 usage: python tests/fuzz_pair_hot.py --iters 150 --seed 1"""
 import argparse, json, os, sys

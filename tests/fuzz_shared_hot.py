@@ -5,7 +5,7 @@ tests/fuzz_side_table.py -- random widths, links, regularisers (per-id decay ran
 (none, user only, both; hot and rare children), row shapes (0 ... 3 global entries, 0 ... 3 shared user ids with the private entry anywhere,
 1 ... 3 items, values other than 1), window sizes and passes -- with amd:shared_user_from always set, few shared ids in half of the draws (so
 that a data row holds several hot entries) and a random sub-step size 1 ... 16: `amd:step = minibatch` on one GPU against the checker of
-tests/shared_hot_sim.py, bit for bit.
+tests/window_sim.py, bit for bit.
 usage: python tests/fuzz_shared_hot.py --iters 150 --seed 1"""
 import argparse, json, os, sys, tempfile
 import numpy as np
@@ -13,10 +13,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cases
 import fuzz_side_table
-import shared_hot_sim as shs
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 
 VIEWS = fuzz_side_table.VIEWS
 same = fuzz_side_table.same
@@ -47,18 +45,18 @@ def one(rng, tmp):
     tu, ti = [], []
     if which != "none":
         hot = tuple(npv + int(x) for x in rng.choice(ns, size=min(ns, int(rng.integers(0, 3))), replace=False))
-        tu = sts.random_table(rng, int(rng.integers(1, npv + ns + 1)), npv, npv + ns, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
+        tu = ws.random_table(rng, int(rng.integers(1, npv + ns + 1)), npv, npv + ns, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
                               hot=hot, hot_p=float(rng.uniform(0, 1)))
-        conf += [("feature_user", sts.write_table(os.path.join(tmp, "fu.txt"), tu))]
+        conf += [("feature_user", ws.write_table(os.path.join(tmp, "fu.txt"), tu))]
     if which == "both":
         hot = tuple(nt + int(x) for x in rng.choice(na, size=min(na, int(rng.integers(0, 3))), replace=False))
-        ti = sts.random_table(rng, int(rng.integers(1, nt + 1)), nt, ni, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
+        ti = ws.random_table(rng, int(rng.integers(1, nt + 1)), nt, ni, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
                               hot=hot, hot_p=float(rng.uniform(0, 1)))
-        conf += [("feature_item", sts.write_table(os.path.join(tmp, "fi.txt"), ti))]
-    tu, ti = [sts.read_table(dict(conf)[x]) if x in dict(conf) else [] for x in ("feature_user", "feature_item")]
-    d = sts.table_rows(rng, n, npv, ns, nt, num_global=ng, max_g=int(rng.integers(0, 4)) if ng else 0, max_shared=int(rng.integers(1, 4)),
+        conf += [("feature_item", ws.write_table(os.path.join(tmp, "fi.txt"), ti))]
+    tu, ti = [ws.read_table(dict(conf)[x]) if x in dict(conf) else [] for x in ("feature_user", "feature_item")]
+    d = ws.table_rows(rng, n, npv, ns, nt, num_global=ng, max_g=int(rng.integers(0, 4)) if ng else 0, max_shared=int(rng.integers(1, 4)),
                        max_items=int(rng.integers(1, 4)), uvals=rng.random() < 0.6, ivals=rng.random() < 0.7)
-    d = sts.drop_rows_reaching_twice(d, npv, tu, ti)
+    d = ws.drop_rows_reaching_twice(d, npv, tu, ti)
     if active != 0:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
     window = int(rng.integers(1, max(d.num_row, 1) + 1))
@@ -80,15 +78,15 @@ def check(c):
         t.train_dataset(ds)
     t.synchronize()
     W = ds.num_batches
-    o = shs.simulate(shared_user_sim.make_oracle(c["conf"], active=c["active"]), d, c["npv"], W, c["passes"], c["sub"], c["tu"], c["ti"],
+    o = ws.simulate_rows(ws.make_oracle(c["conf"], active=c["active"]), d, c["npv"], W, c["passes"], sub=c["sub"], fu=c["tu"], fi=c["ti"],
                      user_bias=c["extra"].get("no_user_bias") != "1")
     bad = [name for name in VIEWS if not same(t.view(name), o.view(name))]
     hot = 0   # hot rows over the windows of one pass: how much of the draw rode the lane
-    for b0, b1 in shs.window_cuts(d.num_row, W):
+    for b0, b1 in ws.row_cuts(d.num_row, W):
         cnt = {}
         for r in range(b0, b1):
             _, ng, nu, _, idx, _ = d.row(r)
-            for u in sts.row_targets(idx, ng, nu, c["npv"], c["tu"], c["ti"])[0]:
+            for u in ws.row_targets(idx, ng, nu, c["npv"], c["tu"], c["ti"])[0]:
                 cnt[u] = cnt.get(u, 0) + 1
         hot += sum(v > c["sub"] for v in cnt.values())
     desc = dict(k=c["k"], np=c["npv"], ns=c["ns"], ng=c["ng"], n=d.num_row, active=c["active"], reg=c["reg"], tables=c["which"], extra=c["extra"],

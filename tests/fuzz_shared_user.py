@@ -2,15 +2,15 @@
 """(not collected by pytest) Randomised differential run of the window step with shared user rows (`amd:shared_user_from`, svdf_wunit.cpp,
 svdf_k_wunit.hip): random widths, links, regularisers (per-id user decay ranges over the shared ids, nonnegative users, no user bias), row
 shapes (0 ... 4 global entries, 0 ... 4 shared ids with the private entry anywhere, non-unit values, one or two item entries), hot and rare
-shared ids, window sizes and passes -- `amd:step = minibatch` on one GPU against the checker of tests/shared_user_sim.py, bit for bit.
+shared ids, window sizes and passes -- `amd:step = minibatch` on one GPU against the checker of tests/window_sim.py, bit for bit.
 usage: python tests/fuzz_shared_user.py --iters 300 --seed 1"""
 import argparse, json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cases
-import shared_user_sim
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import CSRData
 
 VIEWS = ("W_user", "u_bias", "W_item", "i_bias", "g_bias")
@@ -34,7 +34,7 @@ def one(rng):
         cut = int(rng.integers(1, npv + ns))
         conf += [("up:wd", "0.01"), ("up:bound", str(cut)), ("up:wd", "0.002"), ("up:bound", str(npv + ns))]
     hot = tuple(npv + int(x) for x in rng.choice(ns, size=min(ns, int(rng.integers(0, 3))), replace=False))
-    d = shared_user_sim.shared_rows(rng, n, npv, ns, ni, num_global=ng, max_g=int(rng.integers(0, 5)) if ng else 0,
+    d = ws.shared_rows(rng, n, npv, ns, ni, num_global=ng, max_g=int(rng.integers(0, 5)) if ng else 0,
                                     max_shared=min(ns, int(rng.integers(0, 5))), uvals=rng.random() < 0.6, hot=hot, hot_p=float(rng.uniform(0, 1)))
     if rng.random() < 0.3:   # a second item entry in some rows
         rows = []
@@ -62,7 +62,7 @@ def one(rng):
     for _ in range(passes):
         t.train_dataset(ds)
     t.synchronize()
-    o = shared_user_sim.simulate(shared_user_sim.make_oracle(conf, active=active), d, npv, ds.num_batches, passes,
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, npv, ds.num_batches, passes,
                                  user_bias=extra.get("no_user_bias") != "1")
     bad = [name for name in VIEWS if not np.array_equal(t.view(name).view(np.uint32), o.view(name).view(np.uint32))]
     desc = dict(k=k, np=npv, ns=ns, ni=ni, ng=ng, n=n, active=active, reg=reg, extra=extra, hot=hot, windows=ds.num_batches, passes=passes)

@@ -3,7 +3,7 @@
 svdf_k_wunit.hip): random widths, links, regularisers (per-id decay ranges on both sides, nonnegative users, no user
 bias, bias decays), tables (user only, item only, both; 0 ... 3 children per id, hot and rare children, ids without a table row), row shapes
 (0 ... 3 global entries, 0 ... 3 shared user ids with the private entry anywhere, 1 ... 3 items, values other than 1), window sizes and
-passes -- `amd:step = minibatch` on one GPU against the checker of tests/side_table_sim.py, bit for bit.  Rows that reach one target twice
+passes -- `amd:step = minibatch` on one GPU against the checker of tests/window_sim.py, bit for bit.  Rows that reach one target twice
 (which the step refuses) are dropped from the draw.
 usage: python tests/fuzz_side_table.py --iters 150 --seed 1"""
 import argparse, json, os, sys, tempfile
@@ -11,9 +11,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cases
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 
 VIEWS = ("W_user", "u_bias", "W_item", "i_bias", "g_bias")
 
@@ -52,20 +51,20 @@ def one(rng, tmp):
     tu, ti = [], []
     if which != "item":
         hot = tuple(npv + int(x) for x in rng.choice(ns, size=min(ns, int(rng.integers(0, 3))), replace=False))
-        tu = sts.random_table(rng, int(rng.integers(1, npv + ns + 1)), npv, npv + ns, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
+        tu = ws.random_table(rng, int(rng.integers(1, npv + ns + 1)), npv, npv + ns, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
                               hot=hot, hot_p=float(rng.uniform(0, 1)))
-        conf += [("feature_user", sts.write_table(os.path.join(tmp, "fu.txt"), tu))]
+        conf += [("feature_user", ws.write_table(os.path.join(tmp, "fu.txt"), tu))]
     if which != "user":
         lo = 0 if rng.random() < 0.3 else nt   # children among the tracks themselves, or among the attribute ids after them
         hot = tuple(lo + int(x) for x in rng.choice(ni - lo, size=min(ni - lo, int(rng.integers(0, 3))), replace=False))
-        ti = sts.random_table(rng, int(rng.integers(1, nt + 1)), lo, ni, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
+        ti = ws.random_table(rng, int(rng.integers(1, nt + 1)), lo, ni, int(rng.integers(1, 4)), p_none=float(rng.uniform(0, 0.6)),
                               hot=hot, hot_p=float(rng.uniform(0, 1)))
-        conf += [("feature_item", sts.write_table(os.path.join(tmp, "fi.txt"), ti))]
-    tu, ti = [sts.read_table(dict(conf)[x]) if x in dict(conf) else [] for x in ("feature_user", "feature_item")]
+        conf += [("feature_item", ws.write_table(os.path.join(tmp, "fi.txt"), ti))]
+    tu, ti = [ws.read_table(dict(conf)[x]) if x in dict(conf) else [] for x in ("feature_user", "feature_item")]
     B = npv if key else npv + ns
-    d = sts.table_rows(rng, n, npv, ns, nt, num_global=ng, max_g=int(rng.integers(0, 4)) if ng else 0, max_shared=int(rng.integers(0, 4)) if key else 0,
+    d = ws.table_rows(rng, n, npv, ns, nt, num_global=ng, max_g=int(rng.integers(0, 4)) if ng else 0, max_shared=int(rng.integers(0, 4)) if key else 0,
                        max_items=int(rng.integers(1, 4)), uvals=rng.random() < 0.6, ivals=rng.random() < 0.7)
-    d = sts.drop_rows_reaching_twice(d, B, tu, ti)
+    d = ws.drop_rows_reaching_twice(d, B, tu, ti)
     if active != 0:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
     window = int(rng.integers(1, max(d.num_row, 1) + 1))
@@ -89,7 +88,7 @@ def check(c, knobs=()):
     for _ in range(passes):
         t.train_dataset(ds)
     t.synchronize()
-    o = sts.simulate(shared_user_sim.make_oracle(conf, active=active), d, B, ds.num_batches, passes, tu, ti,
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, B, ds.num_batches, passes, fu=tu, fi=ti,
                      user_bias=extra.get("no_user_bias") != "1")
     bad = [name for name in VIEWS if not same(t.view(name), o.view(name))]
     desc = dict(k=k, np=npv, ns=ns, nt=nt, na=na, ng=ng, n=d.num_row, active=active, reg=reg, tables=which, key=key, extra=extra,

@@ -2,15 +2,13 @@
 `window_pair_sub`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs): the pair draws, what a
 draw holds window by window, the checker call and a Python restatement of the window rule.
 
-The checker is tests/item_hot_sim.py on the pair-shaped rows of svdfeature_amd.pairs_as_csr -- no global entry, user:1, the two item entries
+The checker is tests/window_sim.py on the pair-shaped rows of svdfeature_amd.pairs_as_csr -- no global entry, user:1, the two item entries
 in ascending id with the negative's sign flipped, label 1 -- with B = num_user (no shared user row), no tables and isub = window_pair_sub."""
 import numpy as np
 
 import cases
-import item_hot_sim as ihs
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 
 NU, NI = 60, 40
 HOT = (0, 1, 2)
@@ -50,7 +48,7 @@ def facts(pos, neg, W, s):
     item met as the lower / higher id and as positive / negative"""
     f = dict(nhot=0, ragged=False, two_hot=0, as_lo=False, as_hi=False, as_pos=False, as_neg=False, most=0)
     n = len(pos)
-    for b0, b1 in shared_user_sim.window_cuts(n, W):
+    for b0, b1 in ws.row_cuts(n, W):
         cnt = np.bincount(np.concatenate([pos[b0:b1], neg[b0:b1]]).astype(np.int64))
         hot = {int(i) for i in np.nonzero(cnt > s)[0]}
         f["nhot"] += len(hot)
@@ -73,10 +71,10 @@ def check(c, u, pos, neg, W, passes, s, **kw):
     active = int(dict(c).get("active_type", 0))
     ub = dict(c).get("no_user_bias", "0") != "1"
     nu = int(dict(c)["num_user"])
-    o = shared_user_sim.make_oracle(c, active=active)
+    o = ws.make_oracle(c, active=active)
     if s == 0:
-        return sts.simulate(o, d, nu, W, passes, (), (), ub)
-    return ihs.simulate(o, d, nu, W, passes, isub=s, user_bias=ub, **kw)
+        return ws.simulate_rows(o, d, nu, W, passes, fu=(), fi=(), user_bias=ub)
+    return ws.simulate_rows(o, d, nu, W, passes, isub=s, user_bias=ub, **kw)
 
 
 def rule(counts, s, cap, per=24):

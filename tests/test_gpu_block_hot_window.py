@@ -2,22 +2,21 @@
 under `amd:shared_user_from = B` on a format_type 1 trainer; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_walk<LPI, true, true> and
 k_wunit_apply_hot<LPI, false, true>).  A shared user row with more than `window_block_sub` slots in a window is applied in
 file order, that many slots at a time, every slot computed from the span state the walk held when it reached the data row (private row and bias,
-tmp_ufeedback and its bias).  All seven views must equal the checker of tests/block_hot_sim.py -- the pinned C port of SVDPPFeature::update with
+tmp_ufeedback and its bias).  All seven views must equal the checker of tests/window_sim.py -- the pinned C port of SVDPPFeature::update with
 every hot slot's span replayed from its start -- bit for bit, and counter 35 the checker's count of hot rows."""
 import numpy as np
 import pytest
 
-import block_hot_sim as sim
-import block_shared_sim
 import cases
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
 
 pytestmark = pytest.mark.gpu
 
 NP, NS, NI, NF = 60, 8, 40, 40      # private users, shared user ids (B = NP), items, feedback ids: the shape of tests/test_gpu_block_shared_window.py
-VIEWS = sim.VIEWS
+VIEWS = ws.VIEWS
 SVDPP = [("wd_ufeedback", "0.004"), ("ufeedback_init_sigma", "0.01")]
 MB = [("amd:step", "minibatch"), ("amd:shared_user_from", NP)]
 SPLIT = (("up:wd", "0.01"), ("up:bound", str(NP + 3)), ("up:wd", "0.003"), ("up:bound", str(NP + NS)))   # wd_user ranges that split the shared ids
@@ -48,7 +47,7 @@ def _conf(k, active=0, reg=0, extra=(), nf=NF, ng=0):
 
 
 def _blocks(seed, n=75, **kw):
-    return sim.shared_blocks(np.random.default_rng(seed), n, NP, NS, NI, kw.pop("num_fb", NF), **kw)
+    return ws.shared_blocks(np.random.default_rng(seed), n, NP, NS, NI, kw.pop("num_fb", NF), **kw)
 
 
 def _window_key(ba, windows=3):
@@ -78,10 +77,10 @@ def _run(conf, ba, active=0, knobs=(), passes=2, extra=MB, sub=0):
 
 
 def _against_checker(conf, ba, sub, active=0, knobs=(), user_bias=True, hot=True, passes=2):
-    """2 passes of 3 windows against block_hot_sim; counter 35 = the checker's hot rows (hot: some / none), the windows under counter 34"""
+    """2 passes of 3 windows against window_sim.step_blocks; counter 35 = the checker's hot rows (hot: some / none), the windows under counter 34"""
     t, ds = _run(conf, ba, active, knobs, passes=passes, sub=sub)
-    o = sim.make_oracle(conf, active=active)
-    nhot = sim.simulate(o, ba, NP, 3, passes, sub, user_bias=user_bias)
+    o = ws.make_oracle(conf, active=active, user_group=True)
+    nhot = ws.simulate_blocks(o, ba, NP, 3, passes, sub=sub, user_bias=user_bias)[0]
     _same(_views(t), {name: o.view(name) for name in VIEWS})
     assert (nhot > 0) == hot and t.counter(35) == nhot, (nhot, t.counter(35))
     assert t.counter(33) + t.counter(34) == 3 * passes and (not hot or t.counter(34) > 0)
@@ -92,8 +91,8 @@ def _slot_range(ba, s=None):
     """the fewest and the most slots a shared id meets in one of the 3 windows"""
     blocks = ba.to_blocks()
     lo, hi = 1 << 30, 0
-    for b0, b1 in sim.window_cuts(ba, 3):
-        c = sim.slot_counts(blocks[b0:b1], NP)
+    for b0, b1 in ws.block_cuts(ba, 3):
+        c = ws.slot_counts(blocks[b0:b1], NP)
         vals = [c.get(NP + j, 0) for j in range(NS)] if s is None else [c.get(s, 0)]
         lo, hi = min(lo, min(vals)), max(hi, max(vals))
     return lo, hi
@@ -152,7 +151,7 @@ def test_long_feedback_lists_and_users_in_two_spans(k, defer, sub):
     conf = _conf(k, nf=nf)
     blocks = _blocks(64, num_fb=nf, min_shared=1, max_shared=4, uvals=True, fb_sizes=(0, 1, 70, 3))
     ba = BlockArrays.from_blocks(blocks)
-    for b0, b1 in sim.window_cuts(ba, 3):
+    for b0, b1 in ws.block_cuts(ba, 3):
         owners = [min(int(x) for x in b.data.row(0)[4][:b.data.row(0)[2]]) for b in blocks[b0:b1] if b.extend_tag in (TAG_DEFAULT, TAG_START)]
         assert len(set(owners)) < len(owners)   # some user has two spans in this window
     _against_checker(conf, ba, sub, knobs=[("wunit_defer_fb", defer)])
@@ -160,7 +159,7 @@ def test_long_feedback_lists_and_users_in_two_spans(k, defer, sub):
 
 @pytest.mark.parametrize("k", [16, 64])
 def test_where_no_row_is_hot_the_knob_changes_no_bit(k):
-    """blocks without shared ids, and a sub-step above every slot count: the bits of the knob off, which are block_shared_sim's; counter 35 stays 0"""
+    """blocks without shared ids, and a sub-step above every slot count: the bits of the knob off, which are the plain window step's; counter 35 stays 0"""
     conf = _conf(k)
     plain = BlockArrays.from_blocks(_blocks(5, max_shared=0))
     a, _ = _run(conf, plain, sub=None)
@@ -172,7 +171,8 @@ def test_where_no_row_is_hot_the_knob_changes_no_bit(k):
     off, _ = _run(conf, ba, sub=0)
     on, _ = _against_checker(conf, ba, hi, hot=False)
     _same(_views(off), _views(on))
-    o = block_shared_sim.simulate(block_shared_sim.make_oracle(conf), ba, NP, 3, 2)
+    o = ws.make_oracle(conf, user_group=True)
+    ws.simulate_blocks(o, ba, NP, 3, 2)
     _same(_views(off), {name: o.view(name) for name in VIEWS})
     nokey, _ = _run(conf, plain, extra=[("amd:step", "minibatch")], sub=3)   # a trainer without amd:shared_user_from
     _same(_views(a), _views(nokey))

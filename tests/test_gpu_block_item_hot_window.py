@@ -2,16 +2,15 @@
 `window_block_item_max` on a format_type 1 trainer, with or without `amd:shared_user_from`; svdf_wunit.cpp, svdf_k_wunit.hip:
 k_wunit_walk<LPI, true, true> and k_wunit_apply_hot<LPI, true, true>).  An item row with more than `window_block_item_sub`
 slots in a window is applied in file order, that many slots at a time, every slot computed from the span state the walk held when it reached the
-data row (private row and bias, tmp_ufeedback and its bias).  All seven views must equal the checker of tests/block_item_hot_sim.py -- the pinned
+data row (private row and bias, tmp_ufeedback and its bias).  All seven views must equal the checker of tests/window_sim.py -- the pinned
 C port of SVDPPFeature::update with every hot slot's span replayed from its start -- bit for bit, and counters 35 / 36 the checker's counts of
 hot user rows / hot item rows."""
 import numpy as np
 import pytest
 
-import block_item_hot_sim as sim
-import block_shared_sim
 import cases
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
 
@@ -19,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 NP, NS, NI, NF = 60, 8, 8, 40      # private users, shared user ids, items (few: they are hot), feedback ids: otherwise the shape of tests/test_gpu_block_hot_window.py
 NU = NP + NS
-VIEWS = sim.VIEWS
+VIEWS = ws.VIEWS
 SVDPP = [("wd_ufeedback", "0.004"), ("ufeedback_init_sigma", "0.01")]
 MB = [("amd:step", "minibatch")]
 SHARED = MB + [("amd:shared_user_from", NP)]
@@ -72,7 +71,7 @@ def _items(blocks, seed, ni=NI, two=False, vals=False, to_zero=0.0):
 
 def _blocks(seed, n=75, ni=NI, items=None, **kw):
     kw.setdefault("max_shared", 0)   # plain SVD++ blocks: one user entry per row
-    blocks = sim.shared_blocks(np.random.default_rng(seed), n, NP, NS, ni, kw.pop("num_fb", NF), **kw)
+    blocks = ws.shared_blocks(np.random.default_rng(seed), n, NP, NS, ni, kw.pop("num_fb", NF), **kw)
     return _items(blocks, seed, ni, **items) if items else blocks
 
 
@@ -104,11 +103,11 @@ def _run(conf, ba, active=0, knobs=(), passes=2, extra=MB, isub=0, sub=0):
 
 
 def _against_checker(conf, ba, isub, active=0, knobs=(), user_bias=True, hot=True, passes=2, extra=MB, sub=0):
-    """2 passes of 3 windows against block_item_hot_sim; counters 35 / 36 = the checker's hot user rows / hot item rows"""
+    """2 passes of 3 windows against window_sim.step_blocks; counters 35 / 36 = the checker's hot user rows / hot item rows"""
     t, ds = _run(conf, ba, active, knobs, passes=passes, extra=extra, isub=isub, sub=sub)
-    o = sim.make_oracle(conf, active=active)
+    o = ws.make_oracle(conf, active=active, user_group=True)
     B = NP if any(k == "amd:shared_user_from" for k, _ in extra) else NU
-    nuh, nih = sim.simulate(o, ba, B, 3, passes, isub, sub, user_bias=user_bias)
+    nuh, nih = ws.simulate_blocks(o, ba, B, 3, passes, isub=isub, sub=sub, user_bias=user_bias)
     assert all(np.isfinite(v).all() for v in _views(t).values() if v is not None)
     _same(_views(t), {name: o.view(name) for name in VIEWS})
     assert (nih > 0) == hot and t.counter(36) == nih and t.counter(35) == nuh, (nuh, nih, t.counter(35), t.counter(36))
@@ -119,8 +118,8 @@ def _slot_range(ba, item=None):
     """the fewest and the most slots an item meets in one of the 3 windows"""
     blocks = ba.to_blocks()
     lo, hi = 1 << 30, 0
-    for b0, b1 in sim.window_cuts(ba, 3):
-        c = sim.item_slot_counts(blocks[b0:b1])
+    for b0, b1 in ws.block_cuts(ba, 3):
+        c = ws.block_item_slot_counts(blocks[b0:b1])
         vals = [c.get(j, 0) for j in range(NI)] if item is None else [c.get(item, 0)]
         lo, hi = min(lo, min(vals)), max(hi, max(vals))
     return lo, hi
@@ -179,7 +178,7 @@ def test_long_feedback_lists_and_users_in_two_spans(k, defer, isub):
     conf = _conf(k, nf=nf)
     blocks = _blocks(64, num_fb=nf, fb_sizes=(0, 1, 70, 3), items=dict(vals=True))
     ba = BlockArrays.from_blocks(blocks)
-    for b0, b1 in sim.window_cuts(ba, 3):
+    for b0, b1 in ws.block_cuts(ba, 3):
         owners = [int(b.data.row(0)[4][b.data.row(0)[1]]) for b in blocks[b0:b1] if b.extend_tag in (TAG_DEFAULT, TAG_START)]
         assert len(set(owners)) < len(owners)   # some user has two spans in this window
     _against_checker(conf, ba, isub, knobs=[("wunit_defer_fb", defer)])
@@ -201,7 +200,7 @@ def test_blocks_with_shared_user_ids_and_both_lanes(k, isub, sub, opts):
 
 @pytest.mark.parametrize("k", [16, 64])
 def test_where_no_item_is_hot_the_knob_changes_no_bit(k):
-    """a sub-step above every slot count: the bits of the knob off and of the knob unset, which are block_shared_sim's; counter 36 stays 0"""
+    """a sub-step above every slot count: the bits of the knob off and of the knob unset, which are the plain window step's; counter 36 stays 0"""
     conf = _conf(k)
     ba = BlockArrays.from_blocks(_blocks(k))
     hi = _slot_range(ba)[1]
@@ -211,7 +210,8 @@ def test_where_no_item_is_hot_the_knob_changes_no_bit(k):
     on, _ = _against_checker(conf, ba, hi, hot=False)
     _same(_views(unset), _views(off))
     _same(_views(off), _views(on))
-    o = block_shared_sim.simulate(block_shared_sim.make_oracle(conf), ba, NU, 3, 2)
+    o = ws.make_oracle(conf, user_group=True)
+    ws.simulate_blocks(o, ba, NU, 3, 2)
     _same(_views(off), {name: o.view(name) for name in VIEWS})
     hot, _ = _run(conf, ba, isub=3)
     assert hot.counter(36) > 0
@@ -387,7 +387,7 @@ def test_the_staged_route_equals_the_resident_sequence_chunk_by_chunk():
     window = 150
     cuts = _block_cuts(blocks, window)
     assert len(cuts) >= 3
-    assert all(max(sim.item_slot_counts(blocks[a:b]).values()) > 5 for a, b in cuts)
+    assert all(max(ws.block_item_slot_counts(blocks[a:b]).values()) > 5 for a, b in cuts)
     make = lambda isub: _trainer(conf, 0, MB, [("stage_window", window), ("window_block_item_sub", isub)])   # noqa: E731
 
     def feed(t):

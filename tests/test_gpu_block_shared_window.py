@@ -1,23 +1,23 @@
 """Shared user ids on user-group (SVD++) blocks in the one-GPU window step (`amd:shared_user_from = B` on a format_type 1 trainer; svdf_wunit.cpp,
 svdf_k_wunit.hip, svdf_k_wave.hip): every row of a DEFAULT block or START..END span carries the unit's private id (< B) and any
 number of shared ids (>= B: region, device class ...), which are read as of the window start and move once per window, like item and feedback rows.
-Every view must equal the checker of tests/block_shared_sim.py -- the pinned C port of SVDPPFeature::update fed row by row on (the private state the
+Every view must equal the checker of tests/window_sim.py -- the pinned C port of SVDPPFeature::update fed row by row on (the private state the
 walk holds, the window-start shared rows), shared changes summed per target in file order -- bit for bit.  Windows whose segments carry ONE user
 section each (attributes of the user) run one wave per unit with the section's rows in registers under knob wunit_fast = 3 (counter 33); everything else
 with shared entries, and every such window by default, runs the general lane-group kernel (counter 34)."""
 import numpy as np
 import pytest
 
-import block_shared_sim as sim
 import cases
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
 
 pytestmark = pytest.mark.gpu
 
 NP, NS, NI, NF = 60, 8, 40, 40      # private users, shared user ids (B = NP), items, feedback ids
-VIEWS = sim.VIEWS
+VIEWS = ws.VIEWS
 SVDPP = [("wd_ufeedback", "0.004"), ("ufeedback_init_sigma", "0.01")]
 MB = [("amd:step", "minibatch"), ("amd:shared_user_from", NP)]
 SPLIT = (("up:wd", "0.01"), ("up:bound", str(NP + 3)), ("up:wd", "0.003"), ("up:bound", str(NP + NS)))   # wd_user ranges that split the shared ids
@@ -48,7 +48,7 @@ def _conf(k, active=0, reg=0, extra=(), nf=NF, ng=0):
 
 
 def _blocks(seed, n=75, **kw):
-    return sim.shared_blocks(np.random.default_rng(seed), n, NP, NS, NI, kw.pop("num_fb", NF), **kw)
+    return ws.shared_blocks(np.random.default_rng(seed), n, NP, NS, NI, kw.pop("num_fb", NF), **kw)
 
 
 def _seq(t, ba, windows=3):
@@ -86,7 +86,8 @@ def _run(conf, ba, active=0, knobs=(), passes=2, extra=MB):
 def _against_checker(conf, ba, active=0, knobs=(), wave=None, user_bias=True):
     """2 passes of 3 windows; wave: True = every window in the wave form, False = every window in the general kernel, None = not asserted"""
     t, ds = _run(conf, ba, active, list(knobs) + ([("wunit_fast", 3)] if wave else []))   # (the wave form is opt-in: knob wunit_fast = 3)
-    o = sim.simulate(sim.make_oracle(conf, active=active), ba, NP, 3, 2, user_bias=user_bias)
+    o = ws.make_oracle(conf, active=active, user_group=True)
+    ws.simulate_blocks(o, ba, NP, 3, 2, user_bias=user_bias)
     _same(_views(t), {name: o.view(name) for name in VIEWS})
     c33, c34 = t.counter(33), t.counter(34)
     if wave is True:

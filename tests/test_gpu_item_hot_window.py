@@ -2,16 +2,14 @@
 `window_item_max`; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_hot<ITEM>).  An item-range row -- a plain item entry's
 row, a feature_item child's row, or a row that is both -- with more than window_item_sub slots in a window is applied in file order, that many
 slots at a time, every sub-step's changes formed against the row as the previous sub-step left it; everything else moves as in the plain window
-step, hot shared user rows (section 6k) in their own lane.  Every view must equal the checker of tests/item_hot_sim.py -- the pinned C port
+step, hot shared user rows (section 6k) in their own lane.  Every view must equal the checker of tests/window_sim.py -- the pinned C port
 driven one slot at a time -- bit for bit.  With the knob at 0 (the default) nothing changes."""
 import numpy as np
 import pytest
 
 import cases
-import item_hot_sim as ihs
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import CSRData
 
 pytestmark = pytest.mark.gpu
@@ -104,11 +102,11 @@ def _facts(d, B, window, isub, sub, fu, fi):
              user_and_item=False, most=0)
     for b0 in range(0, d.num_row, window):
         win = d.slice_rows(b0, min(b0 + window, d.num_row))
-        ic = ihs.item_slot_counts(win, B, fu, fi)
+        ic = ws.item_slot_counts(win, B, fu, fi)
         uc = {}
         for r in range(win.num_row):
             _, ng, nu, _, idx, _ = win.row(r)
-            for u in sts.row_targets(idx, ng, nu, B, fu, fi)[0]:
+            for u in ws.row_targets(idx, ng, nu, B, fu, fi)[0]:
                 uc[u] = uc.get(u, 0) + 1
         ihot = {i for i, c in ic.items() if c > isub}
         uhot = {u for u, c in uc.items() if c > sub} if sub > 0 else set()
@@ -120,10 +118,10 @@ def _facts(d, B, window, isub, sub, fu, fi):
         for r in range(win.num_row):
             _, ng, nu, _, idx, _ = win.row(r)
             entries = [int(x) for x in idx[ng + nu:]]
-            users, items = sts.row_targets(idx, ng, nu, B, fu, fi)
+            users, items = ws.row_targets(idx, ng, nu, B, fu, fi)
             as_entry |= set(entries) & ihot
             for p in entries:
-                for c in sts.children(fi, [p]):
+                for c in ws.children(fi, [p]):
                     if c in ihot:
                         as_child.add(c)
                         f["child_hot_parent" if p in ihot else "child_cold_parent"] = True
@@ -144,15 +142,15 @@ def _run(tmp_path, k, active, reg, extra, isub, ns=0, sub=0, table="item", windo
     rng = np.random.default_rng(1000 + k + reg + isub if seed is None else seed)
     keys, tu, ti = [], [], []
     if table in ("item", "both"):
-        ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), _table(rng)))
+        ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), _table(rng)))
         keys.append(("feature_item", str(tmp_path / "fi.txt")))
     if table == "both":
-        tu = sts.read_table(sts.write_table(str(tmp_path / "fu.txt"), sts.random_table(rng, NP + ns, NP, NP + ns, 2, hot=(NP, NP + 1), hot_p=0.7)))
+        tu = ws.read_table(ws.write_table(str(tmp_path / "fu.txt"), ws.random_table(rng, NP + ns, NP, NP + ns, 2, hot=(NP, NP + 1), hot_p=0.7)))
         keys.append(("feature_user", str(tmp_path / "fu.txt")))
     conf = _conf(k, ns, reg, extra, active) + keys
     B = NP   # with ns = 0 there is no id >= B: no shared user row, and the trainer never hears of amd:shared_user_from
     d = _rows(rng, n, ns, hot_users=(NP, NP + 1, NP + 2) if ns else (), logistic=active != 0)
-    d = sts.drop_rows_reaching_twice(d, B, tu, ti)
+    d = ws.drop_rows_reaching_twice(d, B, tu, ti)
     f = _facts(d, B, window, isub, sub, tu, ti)
     params = [("amd:step", "minibatch"), ("amd:window", window)] + ([("amd:shared_user_from", NP)] if ns else [])
     knobs = [("window_item_sub", isub)] + ([("window_shared_sub", sub)] if sub else [])
@@ -164,10 +162,10 @@ def _run(tmp_path, k, active, reg, extra, isub, ns=0, sub=0, table="item", windo
         t.train_dataset(ds)
     t.synchronize()
     ub = dict(extra).get("no_user_bias") != "1"
-    o = ihs.simulate(shared_user_sim.make_oracle(conf, active=active), d, B, W, passes, isub, sub, tu, ti, user_bias=ub)
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, B, W, passes, isub=isub, sub=sub, fu=tu, fi=ti, user_bias=ub)
     _assert_same(t, o)
     # the lane did something: the plain window step ends elsewhere
-    p = sts.simulate(shared_user_sim.make_oracle(conf, active=active), d, B, W, passes, tu, ti, ub)
+    p = ws.simulate_rows(ws.make_oracle(conf, active=active), d, B, W, passes, fu=tu, fi=ti, user_bias=ub)
     assert not np.array_equal(p.view(plain_differs)[0], o.view(plain_differs)[0])
     return f, d, t
 
@@ -234,9 +232,9 @@ def test_hot_item_rows_next_to_shared_user_rows(tmp_path, k, active, reg, extra,
 
 def _zero_case(tmp_path):
     rng = np.random.default_rng(5)
-    ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), _table(rng)))
+    ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), _table(rng)))
     conf = _conf(32, 0) + [("feature_item", str(tmp_path / "fi.txt"))]
-    return conf, sts.drop_rows_reaching_twice(_rows(rng, 2000), NP, [], ti)
+    return conf, ws.drop_rows_reaching_twice(_rows(rng, 2000), NP, [], ti)
 
 
 def test_knob_at_zero_is_the_knob_unset(tmp_path):
@@ -279,8 +277,8 @@ def _rule(plain, child, globs, sub, cap, per=24, per_child=3, per_max=128):
 
 def test_window_rule_with_sub_steps(tmp_path):
     conf, d = _zero_case(tmp_path)
-    ti = sts.read_table(str(tmp_path / "fi.txt"))
-    counts = ihs.item_slot_counts(d, NP, (), ti)
+    ti = ws.read_table(str(tmp_path / "fi.txt"))
+    counts = ws.item_slot_counts(d, NP, (), ti)
     is_child = {c for row in ti for c, _ in row}
     plain = [n for i, n in counts.items() if i not in is_child]
     child = [n for i, n in counts.items() if i in is_child]
@@ -356,14 +354,14 @@ def test_the_staged_route_honours_the_knob(tmp_path, isub, sub, batch):
     from test_gpu_staged_window import _cuts, _feed, _resident, _same, _views, _differ
     rng = np.random.default_rng(11)
     ns, S = 40, 1024
-    ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), _table(rng)))
+    ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), _table(rng)))
     conf = _conf(32, ns) + [("feature_item", str(tmp_path / "fi.txt"))]
-    d = sts.drop_rows_reaching_twice(_rows(rng, 2600, ns, hot_users=(NP, NP + 1, NP + 2)), NP, [], ti)
+    d = ws.drop_rows_reaching_twice(_rows(rng, 2600, ns, hot_users=(NP, NP + 1, NP + 2)), NP, [], ti)
     params = [("amd:step", "minibatch"), ("amd:window", 256), ("amd:shared_user_from", NP)]
     make = lambda i, s: _trainer(conf, extra=params, knobs=[("stage_window", S), ("window_item_sub", i), ("window_shared_sub", s)])   # noqa: E731
     cuts = _cuts(d.num_row, batch, S)
     assert len(cuts) >= 2
-    assert max(ihs.item_slot_counts(d.slice_rows(0, 256), NP, (), ti).values()) > isub
+    assert max(ws.item_slot_counts(d.slice_rows(0, 256), NP, (), ti).values()) > isub
     t = make(isub, sub)
     _feed(t, d, batch)
     r = _resident(make(isub, sub), d, cuts, lambda t_, a, b: t_.dataset_from_csr(d.slice_rows(a, b)))

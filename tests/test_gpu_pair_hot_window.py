@@ -2,7 +2,7 @@
 `window_pair_max`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs / k_window_pair_sums).  An
 item with more than window_pair_sub slots in a window -- both signs counted -- is applied in file order, that many slots at a time, every
 sub-step's changes formed against the row as the previous sub-step left it and against the OTHER item's window-start row; everything else
-moves as in the plain window step.  Every view must equal the checker of tests/item_hot_sim.py on the pair-shaped rows (tests/pair_hot_cases.py)
+moves as in the plain window step.  Every view must equal the checker of tests/window_sim.py on the pair-shaped rows (tests/pair_hot_cases.py)
 bit for bit.  With the knob at 0 (the default) nothing changes."""
 import numpy as np
 import pytest

@@ -2,16 +2,14 @@
 `window_shared_max`; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_shared).  A shared user row (id >=
 amd:shared_user_from: a plain shared entry or a feature_user child) with more than window_shared_sub slots in a window is applied in file
 order, that many slots at a time, every sub-step's changes formed against the row as the previous sub-step left it; everything else moves as
-in the plain window step.  Every view must equal the checker of tests/shared_hot_sim.py -- the pinned C port driven one slot at a time --
+in the plain window step.  Every view must equal the checker of tests/window_sim.py -- the pinned C port driven one slot at a time --
 bit for bit.  With the knob at 0 (the default) nothing changes."""
 import numpy as np
 import pytest
 
 import cases
-import shared_hot_sim as shs
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import CSRData
 
 pytestmark = pytest.mark.gpu
@@ -49,7 +47,7 @@ def _slot_counts(d, b0, b1, B, fu=(), fi=()):
     c = {}
     for r in range(b0, b1):
         _, ng, nu, _, idx, _ = d.row(r)
-        for u in sts.row_targets(idx, ng, nu, B, fu, fi)[0]:
+        for u in ws.row_targets(idx, ng, nu, B, fu, fi)[0]:
             c[u] = c.get(u, 0) + 1
     return c
 
@@ -66,7 +64,7 @@ def _hot_per_row(d, B, window, sub, fu=(), fi=()):
         ragged = ragged or any(c[u] % sub for u in hot)
         for r in range(b0, b1):
             _, ng, nu, _, idx, _ = d.row(r)
-            most = max(most, sum(u in hot for u in sts.row_targets(idx, ng, nu, B, fu, fi)[0]))
+            most = max(most, sum(u in hot for u in ws.row_targets(idx, ng, nu, B, fu, fi)[0]))
     return nhot, most, ragged
 
 
@@ -100,7 +98,7 @@ def test_hot_shared_rows_in_sub_steps_equal_the_checker(k, active, reg, extra, p
         conf = cases.conf_with(conf, base_score="0.5")
     rng = np.random.default_rng(1000 + k + reg)
     hot = (NP, NP + 1, NP + 2)
-    d = shared_user_sim.shared_rows(rng, 330, NP, ns, NT, num_global=NG, max_g=2, max_shared=3, uvals=True, hot=hot, hot_p=0.8,
+    d = ws.shared_rows(rng, 330, NP, ns, NT, num_global=NG, max_g=2, max_shared=3, uvals=True, hot=hot, hot_p=0.8,
                                     positions=positions)
     if active != 0:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
@@ -115,20 +113,20 @@ def test_hot_shared_rows_in_sub_steps_equal_the_checker(k, active, reg, extra, p
         t.train_dataset(ds)
     t.synchronize()
     ub = dict(extra).get("no_user_bias") != "1"
-    o = shs.simulate(shared_user_sim.make_oracle(conf, active=active), d, NP, W, 2, sub, user_bias=ub)
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, NP, W, 2, sub=sub, user_bias=ub)
     _assert_same(t, o)
     # the lane did something: the plain window step ends elsewhere
-    p = shared_user_sim.simulate(shared_user_sim.make_oracle(conf, active=active), d, NP, W, 2, ub)
+    p = ws.simulate_rows(ws.make_oracle(conf, active=active), d, NP, W, 2, user_bias=ub)
     assert not np.array_equal(p.view("W_user")[NP], o.view("W_user")[NP])
 
 
 def _tables(tmp_path, seed, which, ns):
     rng = np.random.default_rng(seed)
     hot = (NP, NP + 1)
-    tu = sts.read_table(sts.write_table(str(tmp_path / "fu.txt"), sts.random_table(rng, NP + ns, NP, NP + ns, 2, hot=hot, hot_p=0.7)))
+    tu = ws.read_table(ws.write_table(str(tmp_path / "fu.txt"), ws.random_table(rng, NP + ns, NP, NP + ns, 2, hot=hot, hot_p=0.7)))
     keys, ti = [("feature_user", str(tmp_path / "fu.txt"))], []
     if which == "both":
-        ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), sts.random_table(rng, NT, NT, NI, 3, hot=(NT, NT + 1), hot_p=0.7)))
+        ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), ws.random_table(rng, NT, NT, NI, 3, hot=(NT, NT + 1), hot_p=0.7)))
         keys.append(("feature_item", str(tmp_path / "fi.txt")))
     return keys, tu, ti
 
@@ -154,8 +152,8 @@ def test_hot_feature_user_children_in_sub_steps_equal_the_checker(tmp_path, k, a
     if active != 0:
         conf = cases.conf_with(conf, base_score="0.5")
     rng = np.random.default_rng(k + reg)
-    d = sts.table_rows(rng, 360, NP, ns, NT, num_global=NG, max_g=2, max_shared=2, max_items=2, uvals=True, ivals=True, positions=positions)
-    d = sts.drop_rows_reaching_twice(d, NP, tu, ti)
+    d = ws.table_rows(rng, 360, NP, ns, NT, num_global=NG, max_g=2, max_shared=2, max_items=2, uvals=True, ivals=True, positions=positions)
+    d = ws.drop_rows_reaching_twice(d, NP, tu, ti)
     if active != 0:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
     nhot, most, _ = _hot_per_row(d, NP, 90, sub, tu, ti)
@@ -168,9 +166,9 @@ def test_hot_feature_user_children_in_sub_steps_equal_the_checker(tmp_path, k, a
         t.train_dataset(ds)
     t.synchronize()
     ub = dict(extra).get("no_user_bias") != "1"
-    o = shs.simulate(shared_user_sim.make_oracle(conf, active=active), d, NP, W, 2, sub, tu, ti, user_bias=ub)
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, NP, W, 2, sub=sub, fu=tu, fi=ti, user_bias=ub)
     _assert_same(t, o)
-    p = sts.simulate(shared_user_sim.make_oracle(conf, active=active), d, NP, W, 2, tu, ti, ub)
+    p = ws.simulate_rows(ws.make_oracle(conf, active=active), d, NP, W, 2, fu=tu, fi=ti, user_bias=ub)
     assert not np.array_equal(p.view("W_user")[NP], o.view("W_user")[NP])
 
 

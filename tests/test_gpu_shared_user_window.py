@@ -1,14 +1,14 @@
 """Shared user rows in the one-GPU window step (`amd:shared_user_from = B`; svdf_wunit.cpp, svdf_k_wunit.hip): user ids
 < B are private (one per row, walked exactly by its unit), ids >= B are shared attribute rows (an age bucket, a region ...) read as of the
-window start and moved once per window, like item rows.  Every view must equal the checker of tests/shared_user_sim.py -- the pinned C port
+window start and moved once per window, like item rows.  Every view must equal the checker of tests/window_sim.py -- the pinned C port
 of the reference's update_inner (apex_svd_base.h:456-462) row by row on (the private user's current row, the window-start shared rows),
 shared changes summed per target in file order -- bit for bit."""
 import numpy as np
 import pytest
 
 import cases
-import shared_user_sim
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import CSRData
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +35,7 @@ def _conf(k, reg=0, extra=()):
 
 def _data(seed, n=360, positions=("first", "middle", "last"), binary=False):
     rng = np.random.default_rng(seed)
-    d = shared_user_sim.shared_rows(rng, n, NP, NS, NI, num_global=NG, max_g=2, max_shared=3, uvals=True, hot=HOT, hot_p=0.7,
+    d = ws.shared_rows(rng, n, NP, NS, NI, num_global=NG, max_g=2, max_shared=3, uvals=True, hot=HOT, hot_p=0.7,
                                     positions=positions)
     if binary:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
@@ -75,7 +75,7 @@ def test_minibatch_with_shared_user_rows_equals_the_checker(k, active, reg, extr
     for _ in range(3):
         t.train_dataset(ds)
     t.synchronize()
-    o = shared_user_sim.simulate(shared_user_sim.make_oracle(conf, active=active), d, NP, W, 3, user_bias=dict(extra).get("no_user_bias") != "1")
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, NP, W, 3, user_bias=dict(extra).get("no_user_bias") != "1")
     _assert_same(t, o)
 
 

@@ -2,14 +2,13 @@
 section 6j).  Every child is a shared target: read as of the window start, its change summed per row in file order at the window's end (or
 applied in place when it is the row's only contribution).  feature_user children are shared user rows (ids >= amd:shared_user_from);
 feature_item children keep the reference's item-side forms (apex_svd_base.h:313-427).  Every view must equal the checker of
-tests/side_table_sim.py -- the pinned C port loading the same table files, row by row on the window-start shared rows -- bit for bit."""
+tests/window_sim.py -- the pinned C port loading the same table files, row by row on the window-start shared rows -- bit for bit."""
 import numpy as np
 import pytest
 
 import cases
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import CSRData
 
 pytestmark = pytest.mark.gpu
@@ -43,19 +42,19 @@ def _tables(tmp_path, seed, which):
     rng = np.random.default_rng(seed)
     keys, tu, ti = [], [], []
     if which in ("user", "both"):
-        tu = sts.read_table(sts.write_table(str(tmp_path / "fu.txt"), sts.random_table(rng, NP + NS, NP, NP + NS, 2, hot=HOT_U, hot_p=0.7)))
+        tu = ws.read_table(ws.write_table(str(tmp_path / "fu.txt"), ws.random_table(rng, NP + NS, NP, NP + NS, 2, hot=HOT_U, hot_p=0.7)))
         keys.append(("feature_user", str(tmp_path / "fu.txt")))
     if which in ("item", "both"):
-        ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), sts.random_table(rng, NT, NT, NI, 3, hot=HOT_I, hot_p=0.7)))
+        ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), ws.random_table(rng, NT, NT, NI, 3, hot=HOT_I, hot_p=0.7)))
         keys.append(("feature_item", str(tmp_path / "fi.txt")))
     return keys, tu, ti
 
 
 def _data(seed, tu, ti, n=360, positions=("first", "middle", "last"), max_shared=2, binary=False):
     rng = np.random.default_rng(seed)
-    d = sts.table_rows(rng, n, NP, NS, NT, num_global=NG, max_g=2, max_shared=max_shared, max_items=2, uvals=True, ivals=True,
+    d = ws.table_rows(rng, n, NP, NS, NT, num_global=NG, max_g=2, max_shared=max_shared, max_items=2, uvals=True, ivals=True,
                        positions=positions)
-    d = sts.drop_rows_reaching_twice(d, NP, tu, ti)
+    d = ws.drop_rows_reaching_twice(d, NP, tu, ti)
     if binary:
         d.row_label[:] = (rng.random(d.num_row) < 0.5).astype(np.float32)
     return d
@@ -90,8 +89,8 @@ def test_minibatch_with_side_tables_equals_the_checker(tmp_path, k, active, reg,
         conf = cases.conf_with(conf, base_score="0.5")
     d = _data(k + reg, tu, ti, positions=positions, max_shared=2 if key else 0, binary=active != 0)
     B = NP if key else NP + NS
-    nkids = sum(len(sts.children(tu, [int(x) for x in d.row(r)[4][d.row(r)[1]:d.row(r)[1] + d.row(r)[2]]])) +
-                len(sts.children(ti, [int(x) for x in d.row(r)[4][d.row(r)[1] + d.row(r)[2]:]])) for r in range(d.num_row))
+    nkids = sum(len(ws.children(tu, [int(x) for x in d.row(r)[4][d.row(r)[1]:d.row(r)[1] + d.row(r)[2]]])) +
+                len(ws.children(ti, [int(x) for x in d.row(r)[4][d.row(r)[1] + d.row(r)[2]:]])) for r in range(d.num_row))
     assert d.num_row > 200 and nkids > 150
     t = _trainer(conf, active, [("amd:step", "minibatch"), ("amd:window", 90)] + ([("amd:shared_user_from", NP)] if key else []))
     ds = t.dataset_from_csr(d)
@@ -101,18 +100,18 @@ def test_minibatch_with_side_tables_equals_the_checker(tmp_path, k, active, reg,
     for _ in range(2):
         t.train_dataset(ds)
     t.synchronize()
-    o = sts.simulate(shared_user_sim.make_oracle(conf, active=active), d, B, W, 2, tu, ti, user_bias=dict(extra).get("no_user_bias") != "1")
+    o = ws.simulate_rows(ws.make_oracle(conf, active=active), d, B, W, 2, fu=tu, fi=ti, user_bias=dict(extra).get("no_user_bias") != "1")
     _assert_same(t, o)
 
 
 def test_a_table_that_covers_none_of_the_data_changes_nothing(tmp_path):
     """children only for ids the data never uses: the same windows and bits as without the tables"""
     rng = np.random.default_rng(4)
-    tu = [[] for _ in range(NP)] + sts.random_table(rng, NS, NP, NP + NS, 2)          # only shared ids >= NP have children: rows use none
-    ti = [[] for _ in range(NT // 2)] + sts.random_table(rng, NT // 2, NT, NI, 3)    # only tracks >= NT / 2 have children
-    fu, fi = sts.write_table(str(tmp_path / "fu.txt"), tu), sts.write_table(str(tmp_path / "fi.txt"), ti)
+    tu = [[] for _ in range(NP)] + ws.random_table(rng, NS, NP, NP + NS, 2)          # only shared ids >= NP have children: rows use none
+    ti = [[] for _ in range(NT // 2)] + ws.random_table(rng, NT // 2, NT, NI, 3)    # only tracks >= NT / 2 have children
+    fu, fi = ws.write_table(str(tmp_path / "fu.txt"), tu), ws.write_table(str(tmp_path / "fi.txt"), ti)
     r2 = np.random.default_rng(5)
-    d = sts.table_rows(r2, 300, NP, NS, NT // 2, num_global=NG, max_g=2, max_shared=0, max_items=2, uvals=True, ivals=True)
+    d = ws.table_rows(r2, 300, NP, NS, NT // 2, num_global=NG, max_g=2, max_shared=0, max_items=2, uvals=True, ivals=True)
     got = []
     for keys in ([], [("feature_user", fu), ("feature_item", fi)]):
         t = _trainer(_conf(64) + keys, 0, [("amd:step", "minibatch"), ("amd:window", 70), ("amd:shared_user_from", NP)])
@@ -129,8 +128,8 @@ def test_a_table_that_covers_none_of_the_data_changes_nothing(tmp_path):
 def _deep(tmp_path, n=20000, seed=3):
     """300 users, 200 tracks; every user a child among 4 buckets (ids 300 ..), every track a child among 4 genres (ids 200 ..): the exact
     levels are n / 4 deep"""
-    fu = sts.write_table(str(tmp_path / "fu.txt"), [[(300 + u % 4, 1.0)] for u in range(300)])
-    fi = sts.write_table(str(tmp_path / "fi.txt"), [[(200 + i % 4, 0.5)] for i in range(200)])
+    fu = ws.write_table(str(tmp_path / "fu.txt"), [[(300 + u % 4, 1.0)] for u in range(300)])
+    fi = ws.write_table(str(tmp_path / "fi.txt"), [[(200 + i % 4, 0.5)] for i in range(200)])
     rng = np.random.default_rng(seed)
     rows = [(float(rng.integers(1, 6)), [(int(rng.integers(0, 8)), float(rng.uniform(0.1, 1.0)))], [(int(rng.integers(0, 300)), 1.0)],
              [(int(rng.integers(0, 200)), 1.0)]) for _ in range(n)]
@@ -171,9 +170,9 @@ def test_default_window_rule_counts_children_at_3_updates_per_window(tmp_path):
 
 
 def test_refusals_name_their_cause(tmp_path):
-    fu = sts.write_table(str(tmp_path / "fu.txt"), [[(NP + 5, 1.0)], [(NP + 6, 0.5), (NP + 7, 1.0)]])
-    low = sts.write_table(str(tmp_path / "low.txt"), [[(NP + 5, 1.0)], [(3, 1.0)]])
-    fi = sts.write_table(str(tmp_path / "fi.txt"), [[(NT + 1, 1.0)], [(NT + 1, 0.5)], [(NT + 2, 1.0)]])
+    fu = ws.write_table(str(tmp_path / "fu.txt"), [[(NP + 5, 1.0)], [(NP + 6, 0.5), (NP + 7, 1.0)]])
+    low = ws.write_table(str(tmp_path / "low.txt"), [[(NP + 5, 1.0)], [(3, 1.0)]])
+    fi = ws.write_table(str(tmp_path / "fi.txt"), [[(NT + 1, 1.0)], [(NT + 1, 0.5)], [(NT + 2, 1.0)]])
     mb = [("amd:step", "minibatch"), ("amd:shared_user_from", NP)]
     one = CSRData.from_rows([(3.0, [], [(0, 1.0)], [(2, 1.0)])])
     # a feature_user table without amd:shared_user_from

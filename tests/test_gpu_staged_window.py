@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 
 import cases
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_START
 
@@ -173,7 +172,7 @@ def _shared_conf(k=32):
 def test_shared_user_entries_and_ordered_sub_steps(sub, batch):
     """rows with shared user entries under amd:shared_user_from (12 shared ids: every one is hot); window_shared_sub = 12 applies them in
     ordered sub-steps (k_wunit_apply_shared)"""
-    d = shared_user_sim.shared_rows(np.random.default_rng(4), 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=2, uvals=True)
+    d = ws.shared_rows(np.random.default_rng(4), 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=2, uvals=True)
     knobs = [("stage_window", S), ("window_shared_sub", sub)]
     make = lambda extra: _trainer(_shared_conf(), extra=list(extra) + [("amd:shared_user_from", NP)], knobs=knobs)
     _check(make, d, _from_csr(d), batch)
@@ -182,10 +181,10 @@ def test_shared_user_entries_and_ordered_sub_steps(sub, batch):
 @pytest.mark.parametrize("batch,async_flush,window_key", [(1000, 0, None), (0, 1, None), (350, 1, 100)])
 def test_feature_user_and_feature_item_tables(tmp_path, batch, async_flush, window_key):
     rng = np.random.default_rng(6)
-    tu = sts.read_table(sts.write_table(str(tmp_path / "fu.txt"), sts.random_table(rng, NP + NS, NP, NP + NS, 2)))
-    ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), sts.random_table(rng, NT, NT, NT + NA, 2)))
-    d = sts.table_rows(rng, 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=1, max_items=2, uvals=True, ivals=True)
-    d = sts.drop_rows_reaching_twice(d, NP, tu, ti)
+    tu = ws.read_table(ws.write_table(str(tmp_path / "fu.txt"), ws.random_table(rng, NP + NS, NP, NP + NS, 2)))
+    ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), ws.random_table(rng, NT, NT, NT + NA, 2)))
+    d = ws.table_rows(rng, 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=1, max_items=2, uvals=True, ivals=True)
+    d = ws.drop_rows_reaching_twice(d, NP, tu, ti)
     conf = _shared_conf() + [("feature_user", str(tmp_path / "fu.txt")), ("feature_item", str(tmp_path / "fi.txt"))]
     knobs = [("async_flush", async_flush)] + ([] if window_key else [("stage_window", S)])
     make = lambda extra: _trainer(conf, extra=list(extra) + [("amd:shared_user_from", NP)] + ([("amd:window", window_key)] if window_key else []), knobs=knobs)
@@ -388,7 +387,7 @@ def test_the_default_step_names_amd_step_auto_once_for_a_deep_staged_chunk(capfd
 def test_ordered_sub_steps_without_the_in_place_sums_keep_the_exact_step(capfd):
     """window_shared_sub > 0 with knob wunit_inplace = 0 is a configuration the builder refuses once a shared row is hot: decided before the
     build -- the chunks train exactly, nothing raises (neither here nor from the background flush)"""
-    d = shared_user_sim.shared_rows(np.random.default_rng(4), 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=2, uvals=True)
+    d = ws.shared_rows(np.random.default_rng(4), 9000, NP, NS, NT, num_global=NG, max_g=2, max_shared=2, uvals=True)
     knobs = [("stage_window", S), ("window_shared_sub", 12), ("wunit_inplace", 0), ("async_flush", 1)]
     t = _trainer(_shared_conf(), extra=[("amd:step", "minibatch"), ("amd:shared_user_from", NP)], knobs=knobs)
     e = _trainer(_shared_conf(), extra=[("amd:shared_user_from", NP)], knobs=knobs)

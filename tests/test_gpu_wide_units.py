@@ -2,16 +2,14 @@
 item entries, SVD++ blocks, `amd:shared_user_from` rows and feature_user / feature_item side tables on the one-GPU window sequence of
 `amd:step = minibatch`, through k_wunit_walk / k_wunit_sum / k_wunit_score with a whole wave per unit, target or row (WideRow<2..4>: two, three or four
 float4 per lane).  The semantics are those of the narrow widths, so the checkers are the ones of the narrow tests -- tests/multi_rank_utils.py,
-shared_user_sim.py, side_table_sim.py, block_shared_sim.py -- and every comparison is on uint32 views."""
+tests/window_sim.py -- and every comparison is on uint32 views."""
 import numpy as np
 import pytest
 
-import block_shared_sim
 import cases
 import multi_rank_utils
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from multi_rank_utils import simulate
 from svdfeature_amd import BlockArrays, CSRData
 from test_gpu_wunit import SVDPP_NAMES, _rows_with_globals
@@ -275,7 +273,7 @@ def test_shared_user_rows_at_wide_widths_equal_the_checker(k, reg, extra):
     for _ in range(3):
         t.train_dataset(ds)
     t.synchronize()
-    o = shared_user_sim.simulate(shared_user_sim.make_oracle(conf), d, su.NP, 4, 3, user_bias=dict(extra).get("no_user_bias") != "1")
+    o = ws.simulate_rows(ws.make_oracle(conf), d, su.NP, 4, 3, user_bias=dict(extra).get("no_user_bias") != "1")
     _same(t, o, su.VIEWS, k)
 
 
@@ -295,7 +293,7 @@ def test_side_tables_at_a_wide_width_equal_the_checker(tmp_path):
     for _ in range(2):
         t.train_dataset(ds)
     t.synchronize()
-    _same(t, sts.simulate(shared_user_sim.make_oracle(conf), d, st.NP, W, 2, tu, ti), st.VIEWS)
+    _same(t, ws.simulate_rows(ws.make_oracle(conf), d, st.NP, W, 2, fu=tu, fi=ti), st.VIEWS)
 
 
 # ------------------------------------------------------------------------------------------------- 5. blocks with shared ids
@@ -316,7 +314,8 @@ def test_blocks_with_shared_ids_at_wide_widths_equal_the_checker(k, long_unit, f
     ba = BlockArrays.from_blocks(blocks)
     t, _ = bs._run(conf, ba, knobs=[("wunit_fast", fast)] if fast is not None else [])
     assert (t.counter(33), t.counter(34)) == (0, 6)
-    o = block_shared_sim.simulate(block_shared_sim.make_oracle(conf), ba, bs.NP, 3, 2)
+    o = ws.make_oracle(conf, user_group=True)
+    ws.simulate_blocks(o, ba, bs.NP, 3, 2)
     bs._same(bs._views(t), {name: o.view(name) for name in bs.VIEWS})
     for name in ("W_user", "W_item", "W_ufeedback"):
         assert np.isfinite(t.view(name)).all(), name

@@ -17,11 +17,10 @@ import numpy as np
 import pytest
 
 import cases
-import item_hot_sim as ihs
 import pair_hot_cases as ph
-import shared_user_sim
 import window_order_cases as woc
 import svdfeature_amd as sa
+import window_sim as ws
 from test_window_orders import CONTRACT, HOT_MAX, HOT_SUB, K, N, NI, NU, PARENT_W, PER, PER_MAX, SEED, SLACK, actual_rule, per_pass_rule
 
 pytestmark = pytest.mark.gpu
@@ -219,9 +218,9 @@ def test_b_rows_with_shared_user_ids_equal_the_checker_on_clustered_windows(orde
     _bounds(s, ns, W, ssub, 64 if ssub else PER_MAX, PER_SHARED)
     for _ in range(2):
         t.train_dataset(ds)
-    got = _views(t, shared_user_sim.SHARED[:2] + shared_user_sim.SHARED[3:])
-    o = shared_user_sim.make_oracle(conf)
-    o = ihs.simulate(o, d, npriv, W, 2, isub=isub, sub=ssub) if ssub or isub else shared_user_sim.simulate(o, d, npriv, W, 2)
+    got = _views(t, ws.SHARED[:2] + ws.SHARED[3:])
+    o = ws.make_oracle(conf)
+    o = ws.simulate_rows(o, d, npriv, W, 2, isub=isub, sub=ssub)
     _same(got, {nm: o.view(nm) for nm in got}, (W,))
 
 

@@ -3,7 +3,7 @@
 svdf_dataset_from_* / svdf_dataset_window_from_* -- and equal, bit for bit, what the pinned C port of the reference (oracle.oracle: predict_batch,
 predict_block = the reference's pred, apex_svd_base.h:445-454, and SVDPPFeature::predict, :583-591) gives for the same rows on the same model:
 the engine's parameters are copied into the port through view / set_view after training.  With side tables the port loads the same table files
-(tests/side_table_sim.py does the same for the training checker).
+(tests/window_sim.py does the same for the training checker).
 
 Every case also checks the evaluator: count == n and |ss - sum_float64 (p - label)^2| <= 1e-9 ss with p the file-order predictions (the bound
 tests/test_gpu_native_multi.py uses for this evaluator: per-workgroup fp64 partial sums, long double on the host); rank pairs carry label 1
@@ -17,9 +17,8 @@ import numpy as np
 import pytest
 
 import cases
-import shared_user_sim
-import side_table_sim as sts
 import svdfeature_amd as sa
+import window_sim as ws
 from oracle import oracle
 from svdfeature_amd import BlockArrays, CSRData
 from svdfeature_amd.data import PlusBlock, TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
@@ -147,15 +146,15 @@ def _csr_case(variant, tmp_path, seed):
                  [(int(rng.integers(0, NP_ + NS_)), 1.0)], [(int(rng.integers(0, NT_ + NA_)), 1.0)]) for _ in range(600)]
         return [], [], CSRData.from_rows(rows)
     if variant == "b":     # 0-3 globals, 1-2 item entries with values != 1, user values != 1: the rptr layout
-        return [], [], sts.table_rows(rng, 600, NP_ + NS_, 0, NT_ + NA_, num_global=NG_, max_g=3, max_shared=0, max_items=2, uvals=True, ivals=True)
+        return [], [], ws.table_rows(rng, 600, NP_ + NS_, 0, NT_ + NA_, num_global=NG_, max_g=3, max_shared=0, max_items=2, uvals=True, ivals=True)
     if variant == "c":     # amd:shared_user_from: 0-3 shared ids, the private entry first / middle / last
-        d = shared_user_sim.shared_rows(rng, 600, NP_, NS_, NT_ + NA_, num_global=NG_, max_g=2, max_shared=3, uvals=True, hot=(NP_, NP_ + 1), hot_p=0.6)
+        d = ws.shared_rows(rng, 600, NP_, NS_, NT_ + NA_, num_global=NG_, max_g=2, max_shared=3, uvals=True, hot=(NP_, NP_ + 1), hot_p=0.6)
         return [], [("amd:shared_user_from", NP_)], d
     assert variant == "d"  # feature_user and feature_item tables, children behind item entries with values != 1
-    tu = sts.read_table(sts.write_table(str(tmp_path / "fu.txt"), sts.random_table(rng, NP_ + NS_, NP_, NP_ + NS_, 2, hot=(NP_, NP_ + 1), hot_p=0.7)))
-    ti = sts.read_table(sts.write_table(str(tmp_path / "fi.txt"), sts.random_table(rng, NT_, NT_, NT_ + NA_, 3, hot=(NT_, NT_ + 1), hot_p=0.7)))
-    d = sts.table_rows(rng, 660, NP_, NS_, NT_, num_global=NG_, max_g=2, max_shared=2, max_items=2, uvals=True, ivals=True)
-    d = sts.drop_rows_reaching_twice(d, NP_, tu, ti)
+    tu = ws.read_table(ws.write_table(str(tmp_path / "fu.txt"), ws.random_table(rng, NP_ + NS_, NP_, NP_ + NS_, 2, hot=(NP_, NP_ + 1), hot_p=0.7)))
+    ti = ws.read_table(ws.write_table(str(tmp_path / "fi.txt"), ws.random_table(rng, NT_, NT_, NT_ + NA_, 3, hot=(NT_, NT_ + 1), hot_p=0.7)))
+    d = ws.table_rows(rng, 660, NP_, NS_, NT_, num_global=NG_, max_g=2, max_shared=2, max_items=2, uvals=True, ivals=True)
+    d = ws.drop_rows_reaching_twice(d, NP_, tu, ti)
     return [("feature_user", str(tmp_path / "fu.txt")), ("feature_item", str(tmp_path / "fi.txt"))], [("amd:shared_user_from", NP_)], d
 
 

@@ -1,6 +1,6 @@
 """The checker of the ordered sub-steps for hot items of rank pairs (knob `window_pair_sub`), CPU only.  The checker is
-tests/item_hot_sim.py on pair-shaped rows (tests/pair_hot_cases.py: check); here it is pinned on that shape:
-  * ONE sub-step that holds every slot of every item (ihot_over = 0) is the plain window step -- side_table_sim.window_step -- bit for bit;
+tests/window_sim.py on pair-shaped rows (tests/pair_hot_cases.py: check); here it is pinned on that shape:
+  * ONE sub-step that holds every slot of every item (ihot_over = 0) is the plain window step -- window_sim.step_rows without sub-steps -- bit for bit;
   * sub-steps of s end elsewhere than the plain window step, and stay finite;
   * the Python restatement of the window rule that tests/test_gpu_pair_hot_window.py compares num_batches with, on hand-computed cases."""
 import numpy as np
