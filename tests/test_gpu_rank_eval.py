@@ -7,6 +7,7 @@ import pytest
 import cases
 import svdfeature_amd as sa
 from oracle import oracle
+from rank_rounding import score_fp32
 from test_rank_eval import auc_restated
 
 pytestmark = pytest.mark.gpu
@@ -74,19 +75,6 @@ def ranked_count(ni, ban_ptr, ban_item):
     return np.array([ni - len(np.unique(ban_item[a:b])) for a, b in zip(ban_ptr[:-1], ban_ptr[1:])], np.int32)
 
 
-def score_fp32(urow, W, bias):
-    """the ranker's score in numpy float32: four chains over the 4-float chunks, (a0 + a2) + (a1 + a3), the tail in index order, bias + sum"""
-    n, k = W.shape
-    nfull = k // 4
-    a = np.zeros((n, 4), F32)
-    for j in range(nfull):
-        a = a + urow[4 * j:4 * j + 4][None, :] * W[:, 4 * j:4 * j + 4]
-    s = (a[:, 0] + a[:, 2]) + (a[:, 1] + a[:, 3])
-    for t in range(4 * nfull, k):
-        s = s + urow[t] * W[:, t]
-    return F32(0.0) + (bias + s)
-
-
 def rule_positions(scores, pos, banned):
     """the documented rule on one section's scores"""
     on = np.ones(len(scores), bool)
@@ -129,14 +117,16 @@ def test_positions_match_the_port_ranker_on_random_models(k, tmp_path):
         assert sorted(position[a:b]) == list(range(b - a))
 
 
-@pytest.mark.parametrize("k", [64, 128])
-def test_rounding_is_pinned(k, tmp_path):
+@pytest.mark.parametrize("k, ni", [pytest.param(7, 500, id="7"), pytest.param(64, 500, id="64"), pytest.param(128, 500, id="128"), pytest.param(200, 500, id="200"),
+                                   pytest.param(320, 500, id="320"), pytest.param(64, 1200, id="64-1200items")])
+def test_rounding_is_pinned(k, ni, tmp_path):
     """Item rows are one base row plus small perturbations (up to 800 ulp of an element, which moves a score of magnitude ~8 by a few ulp
     of the SCORE), so the scores of a section cluster within a few ulp of each other: another summation order changes positions (a plain
     sequential sum moves ~2000 of 5000 ranks on these inputs in numpy).  Condition on the input (about one half for either width when the test
     was written: 0.47 / 0.55 over every fourth user; asserted here): at least 20 % of the adjacent ranked pairs differ by less than 4 ulp in a double-precision score;
-    ~3/4 of the fp32 scores are still untied, and only those positions are compared."""
-    nu, ni, S = 40, 500, 70
+    ~3/4 of the fp32 scores are still untied, and only those positions are compared.  The widths take every sweep: k = 7, 64 and 128 two item
+    tiles per pass (IB = 2), 200 one (IB = 1), 320 k_rank_eval_sweep_wide; with 1 200 items the IB = 2 sweep splits them over two workgroups in y."""
+    nu, S = 40, 70
     rng = np.random.default_rng(k)
     t = new_trainer(nu, ni, k)
     base = rng.standard_normal(k).astype(F32)
