@@ -357,7 +357,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 35 hot shared user rows applied in ordered sub-steps on such windows (knob window_block_sub; the windows count under 34),
  * 36 hot item rows applied in ordered sub-steps on user-group (SVD++) windows, with or without shared user entries (knob window_block_item_sub;
  * DESIGN.md 6u; the windows keep counting where they do without the knob),
- * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too) */
+ * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too),
+ * 38 sections ranked by svdf_rank_eval_positions, 39 sections listed by svdf_rank_topn */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -460,6 +461,8 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                                               num_factor <= 256": the pair lane has no wide rows).  Calibration: profiles/r12_pair_hot.md
  *     ipc_spin_limit             polls before a flag wait of the IPC exchange gives up
  *     rank_eval_budget 4194304   svdf_rank_eval_positions: positives + distinct banned ids + sections processed per piece of whole sections (>= 1)
+ *     rank_topn_budget 33554432  svdf_rank_topn: 64-bit keys (8 bytes each) of the selection's list workspace; a call that needs more takes fewer
+ *                                item ranges per section first, then pieces of whole sections (>= 1; results do not depend on it)
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
  * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
@@ -566,6 +569,34 @@ int svdf_rank_eval_metrics(long num_section, const int64_t *sec_ptr, const int *
                            const int *at, svdf_rank_metrics *out);
 int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item,
                    const int64_t *ban_ptr, const unsigned *ban_item, int num_at, const int *at, svdf_rank_metrics *out);
+
+/* ---- top-N item lists on the live model: the other half of ISVDRanker -- top_k -- for many users in one call, on
+ * the trainer's own model: which items do we recommend?  The preconditions are svdf_rank_eval_positions': a format_type = 0,
+ * extend_type = 0 trainer with its model in HBM; refused, each with its cause and in the same words behind the prefix "rank_topn:", are
+ * user-group trainers and extend_type != 0, feature_user / feature_item side tables, common_latent_space != 0, amd:gpus > 1 and the
+ * per-rank handles of the exchange schemes, and host-only handles ("needs a GPU", raised after the lists have been validated).
+ *
+ * Section s of num_section: the user user[s] with the banned items ban_item[ban_ptr[s] .. ban_ptr[s + 1]); ban_ptr == NULL: no section has
+ * bans.  Duplicate ban ids count once.  The candidates are all item ids 0 .. num_item - 1; a candidate is RANKED unless it is banned.  Its
+ * score is svdf_rank_eval_positions': 0 + (i_bias[i] + <W_user[user[s]], W_item[i]>) in the ranker's fp32 order (four chains over the
+ * 4-float chunks, (a0 + a2) + (a1 + a3), the scalar tail, bias + sum; no FMA), bit for bit what svdf_ranker_* computes from the saved model.
+ * ORDER: higher score first; equal scores by ASCENDING ITEM ID; +0 == -0.  The reference's std::sort (apex_svd_base.h:767) leaves the order
+ * inside a tie unspecified; here it is by id, the rule of svdf_rank_eval_positions, so position r of that call is entry r of this one.
+ *   count_out[s]              = min(top_n, num_item - distinct banned ids): the reference asserts "k can not exceed candidate size", the
+ *                               batch call returns the shorter list
+ *   item_out[s * top_n + r]   = the id at rank r for r < count_out[s], -1 beyond
+ *   score_out[s * top_n + r]  = that item's score, 0.0f beyond; score_out may be NULL
+ *   nan_out[s]                = 1 when a RANKED candidate scores NaN: the section's whole list is -1 / 0.0f and count_out[s] = 0 (a banned
+ *                               NaN row does not flag)
+ * 1 <= top_n <= 256; a larger top_n is refused ("top_n must be between 1 and 256"): rank the saved model with svdf_ranker_* and top_k.
+ * Ids out of range are refused with the ranker's messages ("user feature index exceed bound", "sample item index exceed bound"); all
+ * validation runs on the host before any device work.  num_section == 0 returns 0 and launches nothing.  A user may appear in several
+ * sections.  The call runs on the trainer's stream behind whatever is queued and returns when the results are on the host; a stand-alone
+ * window trained but not yet applied is ranked without its pending sums (see svdf_predict_dataset).  The per-(section, item range) lists of
+ * the selection live in a device workspace of at most `rank_topn_budget` 64-bit keys (knob, default 33554432 = 256 MiB): fewer item ranges
+ * first, then pieces of whole sections; the result does not depend on the knob.  Counter 39 counts the sections listed. */
+int svdf_rank_topn(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
+                   int *item_out, float *score_out, int *count_out, int *nan_out);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

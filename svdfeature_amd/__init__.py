@@ -192,6 +192,7 @@ def load_library():
     lib.svdf_rank_eval_positions.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_metrics.argtypes = [C.c_long, _i64p, _i32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_eval.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_rank_topn.argtypes = [P, C.c_long, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -675,6 +676,24 @@ class Trainer:
         self._ok(self.lib.svdf_rank_eval(self.h, len(users), _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
                                          len(at), _pad(list(at), np.int32), C.byref(m)))
         return m.as_dict()
+
+    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None):
+        """svdf_rank_topn: the top_n best items per section among all items that are not banned, higher score first and equal
+        scores by ascending id; (items [S, top_n] int32, -1 beyond count; scores [S, top_n] float32; count [S]; nan [S])."""
+        users, top_n = np.ascontiguousarray(users, np.uint32), int(top_n)
+        S = len(users)
+        if ban_ptr is not None:
+            ban_ptr, ban_item = _pad(ban_ptr, np.int64), _pad(ban_item if ban_item is not None else [], np.uint32)
+            if len(ban_ptr) != S + 1:
+                raise SvdfError("rank_topn: ban_ptr must have one entry more than users")
+        else:
+            ban_item = None
+        n = max(top_n, 1)
+        items, scores = np.full((max(S, 1), n), -1, np.int32), np.zeros((max(S, 1), n), np.float32)
+        count, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+        self._ok(self.lib.svdf_rank_topn(self.h, S, _pad(users, np.uint32), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, items.reshape(-1),
+                                         scores.ctypes.data_as(C.c_void_p), count, nan))
+        return items[:S], scores[:S], count[:S], nan[:S]
 
     # -- multi-GPU item-side delta
     def item_delta_begin(self):

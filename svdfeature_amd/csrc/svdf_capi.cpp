@@ -318,6 +318,10 @@ int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, cons
         return 0;
     })
 }
+int svdf_rank_topn(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
+                   int *item_out, float *score_out, int *count_out, int *nan_out) {
+    SVDF_GUARD(-1, { t->e->rank_topn(num_section, user, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out); return 0; })
+}
 
 /* ---- ISVDRanker ---- */
 svdf_ranker *svdf_ranker_create(uint8_t format_type, uint8_t active_type, uint8_t extend_type, uint8_t variant_type, int device) {

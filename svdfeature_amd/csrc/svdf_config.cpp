@@ -219,6 +219,7 @@ int64_t Engine::counter(int what) const {
     case 36: return n_block_item_hot_; // hot item rows applied in ordered sub-steps on user-group (SVD++) windows (knob window_block_item_sub, section 6u)
     case 37: return n_rank_window_passes_;   // rank passes of a candidate file built as device window sequences (amd:step = minibatch / auto, section 6v); they count under 7 too
     case 38: return n_rank_eval_sections_;   // sections (with positives) ranked by svdf_rank_eval_positions' sweep (section 6w)
+    case 39: return n_rank_topn_sections_;   // sections listed by svdf_rank_topn (section 6x)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -307,6 +308,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target")) { check(value >= 1, "window_per_target must be positive"); wseq_per_target_ = (int)value; return 0; }
     if (!strcmp(name, "rank_eval_budget")) { check(value >= 1, "rank_eval_budget must be positive"); rank_eval_budget_ = value; return 0; }
+    if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }
     if (!strcmp(name, "window_slots")) { window_slots_ = value != 0; return 0; }
     if (!strcmp(name, "window_groups")) { check(value >= 0 && value <= 2, "window_groups must be 0 (auto), 1 or 2"); window_groups_ = (int)value; return 0; }
     if (!strcmp(name, "block_threads")) {

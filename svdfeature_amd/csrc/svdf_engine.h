@@ -447,6 +447,10 @@ class Engine {
     // batch ranking evaluation on the live model (svdf_rankeval.cpp, svdf_k_rankeval.hip)
     void rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
                              const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out);
+    // top-N item lists on the live model (svdf_ranktopn.cpp, svdf_k_ranktopn.hip)
+    void rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
+                   int *count_out, int *nan_out);
+    void rank_live_refusals(const char *who);   // the configurations neither batch ranking call covers
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -905,6 +909,10 @@ class Engine {
     long rank_eval_budget_ = 1L << 22;   // knob rank_eval_budget: positives + distinct bans + sections of one piece
     DevBuf<int> re_in_, re_cnt_;
     DevBuf<float> re_ps_;
+    int64_t n_rank_topn_sections_ = 0;   // counter 39: sections listed by svdf_rank_topn
+    long rank_topn_budget_ = 1L << 25;   // knob rank_topn_budget: 64-bit keys of the list workspace of one piece (256 MiB)
+    DevBuf<int> tn_in_, tn_out_;
+    DevBuf<unsigned long long> tn_list_;
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -1,0 +1,35 @@
+// svdf_k_rankscore.h -- the score of one candidate for one user on the live model, shared by the batch ranking kernels
+// (svdf_k_rankeval.hip, svdf_k_ranktopn.hip; DESIGN.md sections 6w, 6x): i_bias[i] + <W_user[u], W_item[i]> in the ranker's fp32 order.
+#ifndef SVDF_K_RANKSCORE_H_
+#define SVDF_K_RANKSCORE_H_
+
+#include "svdf_kernels.h"
+
+namespace svdf {
+
+// one candidate against one user by ONE lane, both rows row-major in HBM
+__device__ __forceinline__ float re_row_score(int k, const float4 *__restrict__ p4, const float4 *__restrict__ q4, float bias) {
+    const int nfull = k >> 2, ntail = k & 3;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    for (int j = 0; j < nfull; j++) {
+        const float4 p = p4[j], v = q4[j];
+        a0 = a0 + p.x * v.x; a1 = a1 + p.y * v.y; a2 = a2 + p.z * v.z; a3 = a3 + p.w * v.w;
+    }
+    float sum = (a0 + a2) + (a1 + a3);
+    if (ntail) {
+        const float4 p = p4[nfull], v = q4[nfull];
+        sum = sum + p.x * v.x;
+        if (ntail > 1) sum = sum + p.y * v.y;
+        if (ntail > 2) sum = sum + p.z * v.z;
+    }
+    return 0.0f + (bias + sum);   // k_rank_score: item_score (0) + (bias + dot)
+}
+__device__ __forceinline__ const float4 *re_user_row(const DevParams &P, unsigned u) {
+    return reinterpret_cast<const float4 *>(P.W + (size_t)(P.user_off + u) * P.pitch);
+}
+__device__ __forceinline__ const float4 *re_item_row(const DevParams &P, long i) {
+    return reinterpret_cast<const float4 *>(P.W + (size_t)(P.item_off + i) * P.pitch);
+}
+
+}  // namespace svdf
+#endif

@@ -282,5 +282,28 @@ struct RankEvalDev {
 int rank_eval_tile_rows(const DevParams &P);
 void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st);   // positives' scores, the counting sweep, the ban correction
 
+// ---- top-N item lists on the live model (svdf_k_ranktopn.hip): one piece of whole sections.  The sweep keeps, per
+// (section, item range y), a list of up to `cap` 64-bit keys (order-preserving score word << 32 | ~item id) in `list`; the merge selects the
+// top_n largest keys of a section's gy lists.  Every index is local to the piece and has been validated on the host.
+constexpr int RANK_TOPN_MAX = 256;       // largest top_n
+constexpr int RANK_TOPN_MAX_CAP = 512;   // keys one wave sorts in LDS: the largest list capacity
+struct RankTopnDev {
+    int nsec;                        // sections of the piece
+    const unsigned *sec_user;        // [nsec]
+    const int *ban_p0;               // [nsec + 1] banned ids of section s: ban_item[ban_p0[s] .. ban_p0[s + 1]), distinct, ascending
+    const int *ban_item;
+    int top_n, cap, gy;              // list capacity (rank_topn_cap), item ranges (rank_topn_geometry)
+    long items_per_block;            // items of one range
+    unsigned long long *list;        // [nsec][gy][cap]
+    int *list_cnt;                   // [nsec][gy] keys in the list, written by the sweep
+    int *nan_cnt;                    // [nsec] ranked candidates with a NaN score, zeroed by the caller
+    int *item_out;                   // [nsec][top_n] ids in rank order, -1 beyond count_out
+    float *score_out;                // [nsec][top_n] their scores, 0 beyond count_out
+    int *count_out;                  // [nsec] entries listed; 0 for a section with a NaN among its ranked candidates
+};
+int rank_topn_cap(const DevParams &P, int top_n);   // capacity of one list, <= RANK_TOPN_MAX_CAP
+void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block);   // at most max_lists / nsec (>= 1) item ranges
+void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep, then the merge: two launches
+
 }  // namespace svdf
 #endif

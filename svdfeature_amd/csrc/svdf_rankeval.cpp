@@ -68,15 +68,7 @@ void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, cons
 
 void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
                                  const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
-    // ---- what the batch call does not cover (svdf_ranker_* does)
-    check(!user_group() && mtype_.extend_type == 0,
-          "rank_eval: user-group trainers (format_type = 1) and extend_type != 0 are not covered: the score has a feedback part; rank the saved model with svdf_ranker_*");
-    check(name_feat_user_ == "NULL" && name_feat_item_ == "NULL",
-          "rank_eval: feature_user / feature_item side tables change the score and are not covered; rank the saved model with svdf_ranker_*");
-    check(mp_.common_latent_space == 0, "rank_eval: common_latent_space != 0 is not covered; rank the saved model with svdf_ranker_*");
-    check(gpus_ == 1 && !multi_, "rank_eval: amd:gpus > 1 is not covered (the model is spread over the ranks); rank the saved model with svdf_ranker_*");
-    check(!is_peer_ && !ipc_ && !rccl_, "rank_eval: a rank handle of the one-process-per-GPU exchange holds a partition in flight; rank the saved model with svdf_ranker_*");
-    check(space_allocated_ && trainer_ready_, "rank_eval: call init_model / load_model and init_trainer first");
+    rank_live_refusals("rank_eval");   // what the batch call does not cover (svdf_ranker_* does): svdf_ranktopn.cpp
     // ---- the lists, before any device work
     check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
     const long num_item = mp_.num_item;
