@@ -196,7 +196,9 @@ int svdf_predict_dataset(svdf_trainer *t, svdf_dataset *ds, float *out);
  * (0 = basicMF fused kernel, 1 = general sparse kernel, 2 = few-row fused kernel, 3 = SVD++ user units),
  * 4 algorithmic bytes per pass, 5 number of user units, 6 units on the register-resident
  * fast path, 7 a digest of the host-resident schedule (level boundaries, fast-path split, unit order),
- * 8 a window sequence's (kind 8) kind of windows: 5 plain ratings / rank pairs, 7 user units; -1 for any other data set */
+ * 8 a window sequence's (kind 8) kind of windows: 5 plain ratings / rank pairs, 7 user units; -1 for any other data set,
+ * 9 operand staging of a runs data set (knob runs_stage): 0 not built yet, 1 built, 2 refused (size gate or no memory: rows stay in W),
+ * 10 bytes of its staging buffers */
 int64_t svdf_dataset_info(const svdf_dataset *ds, int what);
 
 /* ---- multi-GPU support: item-side parameters are replicated, each rank trains its
@@ -381,6 +383,9 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *   schedule forms of plain ratings
  *     runs_exec           1      runs of an item's consecutive ratings as units (svdf_k_runs.hip); runs_len 4 (2..7), runs_sets 1, runs_block 64,
  *                                runs_min_rows 2^20 (smaller data sets keep one instance per lane group)
+ *     runs_stage          1      a run writes every row into its next reader's schedule slot instead of W (W is written at the row's last touch of a
+ *                                pass and is the truth between passes; same bits).  Costs (1 + R) * runs * (4 k + 8) bytes of device memory, taken
+ *                                only when that is at most half of the free memory and at most runs_stage_max_mb (-1 = no cap); 0 = rows live in W
  *     pivot_exec          1      hot rows walked as units (svdf_pivot.cpp); pivot_min 2048 (ratings that make a row hot), pivot_run 256 (per unit)
  *   schedule forms of rank pairs
  *     pair_units          1      user-grouped pair streams (the generator's own order: a user's pairs back to back) walked as user-run units

@@ -268,6 +268,8 @@ int64_t svdf_dataset_info(const svdf_dataset *ds, int what) {
         return (int64_t)(h >> 1);
     }
     case 8: return ds->d->kind == 8 && !ds->d->wchild.empty() ? (int64_t)ds->d->wchild[0]->kind : -1;
+    case 9: return ds->d->rn_stage_state;   // runs data sets, operand staging: 0 not tried, 1 built, 2 refused (gate / no memory)
+    case 10: return ds->d->rn_stage_bytes;  // ... bytes of the staging buffers
     default: return -1;
     }
 }

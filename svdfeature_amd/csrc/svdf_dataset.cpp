@@ -650,7 +650,13 @@ std::string Engine::path_for(const Dataset *ds) const {
                      !ds->wchild.empty() && ds->wchild[0]->kind == 7 && !wunit_width_ok() ? ", user units of wide rows: the wide general walk k_wunit_walk<64, ., ., WideRow>, one wave per unit" : ""); return buf;
     case 9: snprintf(buf, sizeof(buf), "exact, %ld levels: hot rows walked as units (k_svdpp_wave on %s parameters, %ld units) + cold ratings through the contract kernel",
                      L, ds->pv_item_pivot ? "transposed" : "plain", ds->num_units); return buf;
-    case 10: snprintf(buf, sizeof(buf), "exact, %ld levels of runs: k_basicmf_runs_soa (up to %d consecutive ratings of one item per lane group, the item's row in registers)", L, ds->rn_len); return buf;
+    case 10: {
+        char st[96] = "rows in W";
+        if (runs_staged(ds)) snprintf(st, sizeof(st), "rows handed from run to run through staging slots (runs_stage, %.1f MB)", (double)ds->rn_stage_bytes / 1048576.0);
+        else if (ds->rn_stage_state == 2) snprintf(st, sizeof(st), "rows in W (operand staging refused)");
+        snprintf(buf, sizeof(buf), "exact, %ld levels of runs: k_basicmf_runs_soa (up to %d consecutive ratings of one item per lane group, the item's row in registers); %s", L, ds->rn_len, st);
+        return buf;
+    }
     case 11: snprintf(buf, sizeof(buf), "exact, %ld levels of user-run units: k_pair_units (%ld units of up to %d consecutive pairs of one user, the user's row in registers)",
                       L, ds->num_units, pair_unit_cap_); return buf;
     default: return "unknown";

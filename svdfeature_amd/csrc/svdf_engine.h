@@ -291,6 +291,12 @@ struct Dataset {
     DevBuf<unsigned> rn_item, rn_user[8];
     DevBuf<float> rn_label[8];
     int rn_len = 0;
+    // ... and their operand staging (knob "runs_stage"; svdf_runs.cpp: runs_stage_build): slot j * num_units + s; rn_first[r] = the slot of row r's first touch
+    DevBuf<float> rn_stage_row, rn_stage_bias;
+    DevBuf<unsigned> rn_dst, rn_first;
+    int rn_stage_state = 0;       // 0 not tried yet, 1 built, 2 refused (the gate, or no memory): the data set keeps reading and writing W
+    unsigned rn_stage_row0 = 0;   // the W row of user 0 the HOME words were built against
+    int64_t rn_stage_bytes = 0;
     // kind 9: hot rows walked as units (svdf_pivot.cpp): sched.level_ptr = the cold ratings' level boundaries (user / item / label above),
     // pv_unit_ptr = the units' (unitdev.xunits in launch order, their rows in unitdev)
     std::vector<long> pv_unit_ptr;
@@ -775,6 +781,10 @@ class Engine {
     bool runs_config_ok() const;
     Dataset *runs_dataset_from_triples(long n, const unsigned *user, const unsigned *item, const float *label);
     void runs_train(Dataset *ds);
+    int runs_stage_ = 1;                  // knob "runs_stage": 1 = a run's rows are written into their next reader's schedule slot (where the gate allows), 0 = rows live in W
+    long runs_stage_max_mb_ = -1;         // knob "runs_stage_max_mb": cap on a data set's staging buffers (-1: half of the free device memory is the only limit)
+    void runs_stage_build(Dataset *ds);
+    bool runs_staged(const Dataset *ds) const { return runs_stage_ != 0 && ds->rn_stage_state == 1 && ds->rn_stage_row0 == user_off_; }
     // exact passes over data with hot rows: runs of a hot row's ratings as walker units (svdf_pivot.cpp)
     int pivot_exec_ = 1;                  // knob "pivot_exec"
     int pivot_run_ = 256, pivot_run_long_ = 256;   // knobs "pivot_run" / "pivot_run_long": ratings per unit at most, among cold levels / beyond them (a longer tail cap measured slower)

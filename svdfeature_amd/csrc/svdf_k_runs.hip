@@ -106,9 +106,77 @@ void launch_runs_fill_u32(unsigned *v, long n, unsigned x, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_runs_fill_u32, dim3(runs_grid(n)), dim3(256), 0, st, v, n, x);
 }
 
+// ------------------------------------------------------------------------------------------------- operand staging (knob "runs_stage")
+// Every row is read and written at every touch anyway, so the write can go where the row's NEXT reader will look: slot j * nunit + s of the
+// staging buffers, s = the reader's position in level order, j = 0 its item row, 1 .. R its users' rows.  The links are a file-order fact too: runs
+// are numbered by head position and a row's touches ascend in that number, so a stable sort of (row, unit number) puts every touch next to its successor.
+// pos_of[order[s]] = s: unit number -> position in level order
+__global__ __launch_bounds__(256) void k_runs_inverse(const int *order, long nunit, unsigned *pos_of) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nunit; s += stride) pos_of[order[s]] = (unsigned)s;
+}
+// the operands in unit-number order: entry un * (1 + R) + j = (row id in the scheduler's numbering: users first, then items; slot).  Holes get the key
+// 0xFFFFFFFF and sort behind every row.
+__global__ __launch_bounds__(256) void k_runs_operands(const RunSchedule S, const unsigned *pos_of, long nunit, int R, unsigned num_user, unsigned *keys, unsigned *vals) {
+    const long stride = (long)gridDim.x * blockDim.x, m = nunit * (1 + R);
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride) {
+        const long un = t / (1 + R);
+        const int j = (int)(t - un * (1 + R));
+        const unsigned s = pos_of[un];
+        const unsigned id = j == 0 ? num_user + S.item[s] : S.user[j - 1][s];
+        keys[t] = (j > 0 && id == (unsigned)SLOT_ABSENT) ? 0xFFFFFFFFu : id;
+        vals[t] = (unsigned)((long)j * nunit + s);
+    }
+}
+// keys / vals sorted: dst of every slot, and the slot of every touched row's first touch
+__global__ __launch_bounds__(256) void k_runs_links(const unsigned *keys, const unsigned *vals, long m, unsigned row0, unsigned *dst, unsigned *first) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride) {
+        const unsigned key = keys[t], slot = vals[t];
+        if (key == 0xFFFFFFFFu) { dst[slot] = (unsigned)SLOT_ABSENT; continue; }
+        dst[slot] = (t + 1 < m && keys[t + 1] == key) ? vals[t + 1] : ((unsigned)RUNS_HOME | (row0 + key));
+        if (t == 0 || keys[t - 1] != key) first[key] = slot;
+    }
+}
+void launch_runs_stage_links(const RunSchedule &S, const int *order, long nunit, int R, unsigned num_user, unsigned row0, unsigned *pos_of, unsigned *ka, unsigned *kb,
+                             unsigned *va, unsigned *vb, void **tmp, size_t *tmp_bytes, unsigned *dst, unsigned *first, long nrow, hipStream_t st) {
+    if (nunit <= 0) return;
+    const long m = nunit * (1 + R);
+    hipLaunchKernelGGL(k_runs_inverse, dim3(runs_grid(nunit)), dim3(256), 0, st, order, nunit, pos_of);
+    hipLaunchKernelGGL(k_runs_operands, dim3(runs_grid(m)), dim3(256), 0, st, S, pos_of, nunit, R, num_user, ka, va);
+    device_sort_pairs_u32(ka, kb, va, vb, m, tmp, tmp_bytes, st);
+    launch_runs_fill_u32(first, nrow, (unsigned)SLOT_ABSENT, st);
+    hipLaunchKernelGGL(k_runs_links, dim3(runs_grid(m)), dim3(256), 0, st, kb, vb, m, row0, dst, first);
+}
+// Before level 0 of a staged pass: W is the truth between passes, so every touched row (and its bias) is copied into the slot of its first touch.
+// first[r], r in the scheduler's numbering = W row row0 + r; LPR lanes per row
+template <int LPR>
+__global__ __launch_bounds__(256) void k_runs_stage_in(const DevParams P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias) {
+    const int L = threadIdx.x % LPR;
+    const long per = 256 / LPR, stride = (long)gridDim.x * per;
+    for (long r = (long)blockIdx.x * per + threadIdx.x / LPR; r < nrow; r += stride) {
+        const unsigned slot = first[r];
+        if (slot == (unsigned)SLOT_ABSENT) continue;
+        store_row<LPR>(stage_row, slot, P.pitch, L, P.k, load_row_nt<LPR>(P.W, (size_t)row0 + (size_t)r, P.pitch, L, P.k));
+        if (L == 0) stage_bias[slot] = P.bias[(size_t)row0 + (size_t)r];
+    }
+}
+void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, hipStream_t st) {
+    if (nrow <= 0) return;
+    const long per = P.k == 128 ? 8 : 16;
+    long grid = (nrow + per - 1) / per;
+    if (grid > 16384) grid = 16384;
+    if (P.k == 128) hipLaunchKernelGGL(k_runs_stage_in<32>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias);
+    else hipLaunchKernelGGL(k_runs_stage_in<16>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias);
+}
+
 // ------------------------------------------------------------------------------------------------- the pass
 // One level of runs.  S.item[s], S.user[j][s], S.label[j][s] (j < R; S.user[j][s] == SLOT_ABSENT: the run has fewer than j + 1 ratings).
-template <int LANES, int V, int R, int G>
+// STAGED (knob "runs_stage"): the run's rows and biases are read from its own staging slots -- addresses that are arithmetic on s, no id has to arrive
+// first -- and written to the slots of their next readers (S.dst), home to W / P.bias at a row's last touch of the pass.  The steps are the same lines.
+__device__ __forceinline__ unsigned load_u32_nt(const unsigned *p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ float load_f32_nt(const float *p) { return __builtin_nontemporal_load(p); }
+template <int LANES, int V, int R, int G, bool STAGED>
 __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, const RunSchedule S, long begin, long end) {
     constexpr int T = 16 / LANES;
     constexpr int IPS = 64 / LANES;    // runs per wave and row set
@@ -128,31 +196,61 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
         const long s = w0 + gslot;
         const bool live = s < end;
         const long sc = live ? s : w0;
-        const unsigned ir = P.item_off + S.item[sc];
-        unsigned ur[R];
-        float label[R], bu[R];
+        unsigned ir, ur[R];   // the rows in W; STAGED: the dst words of the item operand and of the user operands (where each is written)
+        float label[R], bu[R], bi;
         float4 p[R][V], q[V];
         int n = 0;
+        if constexpr (!STAGED) {
+            ir = P.item_off + S.item[sc];
 #pragma unroll
-        for (int j = 0; j < R; j++) {
-            const unsigned u = S.user[j][sc];
-            label[j] = S.label[j][sc];
-            const bool on = live && u != (unsigned)SLOT_ABSENT;
-            ur[j] = P.user_off + (on ? u : 0u);
-            if (on) n = j + 1;
-        }
+            for (int j = 0; j < R; j++) {
+                const unsigned u = S.user[j][sc];
+                label[j] = S.label[j][sc];
+                const bool on = live && u != (unsigned)SLOT_ABSENT;
+                ur[j] = P.user_off + (on ? u : 0u);
+                if (on) n = j + 1;
+            }
 #pragma unroll
-        for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(P.W, ir, pitch, m + v * LANES, K) : f4zero();
-        float bi = live ? P.bias[ir] : 0.0f;
+            for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(P.W, ir, pitch, m + v * LANES, K) : f4zero();
+            bi = live ? P.bias[ir] : 0.0f;
 #pragma unroll
-        for (int j = 0; j < R; j++) {
+            for (int j = 0; j < R; j++) {
 #pragma unroll
-            for (int v = 0; v < V; v++) p[j][v] = f4zero();
-            bu[j] = 0.0f;
-            if (j < n) {
+                for (int v = 0; v < V; v++) p[j][v] = f4zero();
+                bu[j] = 0.0f;
+                if (j < n) {
 #pragma unroll
-                for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(P.W, ur[j], pitch, m + v * LANES, K);
-                bu[j] = P.bias[ur[j]];
+                    for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(P.W, ur[j], pitch, m + v * LANES, K);
+                    bu[j] = P.bias[ur[j]];
+                }
+            }
+        } else {
+            const size_t nun = (size_t)S.nunit, at0 = (size_t)sc;
+            ir = load_u32_nt(S.dst + at0);
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                ur[j] = load_u32_nt(S.dst + (size_t)(1 + j) * nun + at0);
+                label[j] = S.label[j][sc];
+            }
+            // Row by row, the shape of the loads from W above: one operand per round trip, every operand under `if (j < n)`.  The addresses need no id, so
+            // the whole read could leave with the dst words -- built and measured: 19.8 against 16.9 ms per pass (W) and 16.2 (this form), profiles/r26_runs_stage.md.
+#pragma unroll
+            for (int j = 0; j < R; j++)
+                if (live && ur[j] != (unsigned)SLOT_ABSENT) n = j + 1;
+#pragma unroll
+            for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(S.stage_row, at0, pitch, m + v * LANES, K) : f4zero();
+            bi = live ? load_f32_nt(S.stage_bias + at0) : 0.0f;
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+#pragma unroll
+                for (int v = 0; v < V; v++) p[j][v] = f4zero();
+                bu[j] = 0.0f;
+                if (j < n) {
+                    const size_t at = (size_t)(1 + j) * nun + at0;
+#pragma unroll
+                    for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(S.stage_row, at, pitch, m + v * LANES, K);
+                    bu[j] = load_f32_nt(S.stage_bias + at);
+                }
             }
         }
         // Every row is here before step 0 (an empty statement that reads a register of each: the compiler places its counted waits in front of
@@ -183,6 +281,13 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
             nbu = nbu * (1.0f - P.lr * P.wd_user_bias);
             nbi = nbi * (1.0f - P.lr * P.wd_item_bias);
             const bool act = j < n;
+            float *wb = P.W, *bb = P.bias;
+            size_t wr = ur[j];
+            if constexpr (STAGED) {   // the row's next reader's slot, or home at its last touch of the pass
+                const bool home = (ur[j] & (unsigned)RUNS_HOME) != 0u;
+                wb = home ? P.W : S.stage_row; bb = home ? P.bias : S.stage_bias;
+                wr = ur[j] & ~(unsigned)RUNS_HOME;
+            }
 #pragma unroll
             for (int v = 0; v < V; v++) {
                 float4 wu = p[j][v], wi = q[v];
@@ -191,19 +296,26 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 wu.x = wu.x * dec_u1; wu.y = wu.y * dec_u1; wu.z = wu.z * dec_u1; wu.w = wu.w * dec_u1;
                 wi.x = wi.x * dec_i1; wi.y = wi.y * dec_i1; wi.z = wi.z * dec_i1; wi.w = wi.w * dec_i1;
                 if (act) {
-                    store_row<K / 4>(P.W, ur[j], pitch, m + v * LANES, K, wu);
+                    store_row<K / 4>(wb, wr, pitch, m + v * LANES, K, wu);
                     q[v] = wi;
                 }
             }
             if (act) {
-                P.bias[ur[j]] = nbu;
+                bb[wr] = nbu;
                 bi = nbi;
             }
         }
         if (live) {
+            float *wb = P.W, *bb = P.bias;
+            size_t wr = ir;
+            if constexpr (STAGED) {
+                const bool home = (ir & (unsigned)RUNS_HOME) != 0u;
+                wb = home ? P.W : S.stage_row; bb = home ? P.bias : S.stage_bias;
+                wr = ir & ~(unsigned)RUNS_HOME;
+            }
 #pragma unroll
-            for (int v = 0; v < V; v++) store_row<K / 4>(P.W, ir, pitch, m + v * LANES, K, q[v]);
-            P.bias[ir] = bi;
+            for (int v = 0; v < V; v++) store_row<K / 4>(wb, wr, pitch, m + v * LANES, K, q[v]);
+            bb[wr] = bi;
         }
     }
 }
@@ -220,7 +332,11 @@ void launch_basicmf_runs_soa(const DevParams &P, const RunSchedule &S, long begi
     const long per_block = (long)(block_threads / 64) * G * per_wave;
     int grid = (int)((end - begin + per_block - 1) / per_block);
     if (P.xcd_remap) grid = (grid + 7) & ~7;
-#define RUNS_LAUNCH(L_, R_, G_) hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end)
+#define RUNS_LAUNCH(L_, R_, G_)                                                                                                                          \
+    do {                                                                                                                                                \
+        if (S.dst) hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);              \
+        else hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);                   \
+    } while (0)
 #define RUNS_BY_R(L_)                                                                                                          \
     if (R == 2) { if (G >= 2) RUNS_LAUNCH(L_, 2, 2); else RUNS_LAUNCH(L_, 2, 1); }      /* R = user / label columns of the schedule: 2, 4 or 7 */ \
     else if (R == 4) { if (G >= 2) RUNS_LAUNCH(L_, 4, 2); else RUNS_LAUNCH(L_, 4, 1); }                                       \

@@ -141,6 +141,11 @@ bool pair_units_applies(const DevParams &P);
 void launch_pair_units(const DevParams &P, const PairUnitSchedule &S, long begin, long end, float *out, hipStream_t st);
 void launch_runs_iota(unsigned *v, long n, hipStream_t st);
 void launch_runs_fill_u32(unsigned *v, long n, unsigned x, hipStream_t st);
+// operand staging of a runs data set (knob "runs_stage"): dst[] / first[] from the level-sorted columns S and the schedule's order (ka .. vb: (1 + R) * nunit
+// words each, pos_of: nunit; first: nrow = num_user + num_item words; row0 = the W row of user 0), and the copy of every touched row into its first slot
+void launch_runs_stage_links(const RunSchedule &S, const int *order, long nunit, int R, unsigned num_user, unsigned row0, unsigned *pos_of, unsigned *ka, unsigned *kb,
+                             unsigned *va, unsigned *vb, void **tmp, size_t *tmp_bytes, unsigned *dst, unsigned *first, long nrow, hipStream_t st);
+void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, hipStream_t st);
 bool basicmf_runs_soa_applies(const DevParams &P);
 void launch_basicmf_runs_soa(const DevParams &P, const RunSchedule &S, long begin, long end, int R, int G, int block_threads, hipStream_t st);
 void device_sort_pairs_u32(unsigned *keys_in, unsigned *keys_out, unsigned *vals_in, unsigned *vals_out, long n, void **tmp, size_t *tmp_bytes, hipStream_t st);

@@ -84,7 +84,68 @@ Dataset *Engine::runs_dataset_from_triples(long n, const unsigned *user, const u
     schedule_device_columns(ds.get(), nunit, 1 + R, res, off, limit, msg, sort_batches_ == 1 ? c_item.p : nullptr, NI, du, df);
     ds->num_units = nunit;
     ds->algorithmic_bytes = n * (8L * mp_.num_factor * 2 + 8 * 2 + 16 + 8 * 2);
+    if (runs_stage_) runs_stage_build(ds.get());
     return ds.release();
+}
+
+// Operand staging (knob "runs_stage"): (1 + R) * nunit slots of one row + one bias, the dst word of each, the first slot of every
+// row.  Built once per data set from the level-sorted columns and the schedule's order; refused -- the data set then keeps reading and writing W, the
+// same bits -- when the slots do not fit 31 bits, half of the free device memory or the knob "runs_stage_max_mb", or when the allocation fails.
+namespace {
+template <typename T>
+bool try_reserve(DevBuf<T> &b, size_t n) {   // DevBuf::reserve without the failure: false, the error cleared
+    b.release();
+    if (hipMalloc((void **)&b.p, (n ? n : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+    b.cap = n ? n : 1;
+    return true;
+}
+}  // namespace
+void Engine::runs_stage_build(Dataset *ds) {
+    ds->rn_stage_state = 2;
+    ds->rn_stage_bytes = 0;
+    const long nunit = ds->num_units, nrow = (long)mp_.num_user + (long)mp_.num_item;
+    const int R = ds->rn_len;
+    const long m = (long)(1 + R) * nunit;
+    if (nunit <= 0) return;
+    const int64_t bytes = (int64_t)m * ((int64_t)pitch_ * 4 + 8) + (int64_t)nrow * 4;
+    auto refuse = [&](const char *why) {
+        ds->rn_stage_row.release(); ds->rn_stage_bias.release(); ds->rn_dst.release(); ds->rn_first.release();
+        if (!getenv("SVDF_QUIET"))
+            fprintf(stderr, "[svdfeature_amd] data set of %ld rows: no operand staging (%.1f MB: %s); its runs keep reading and writing W\n", (long)ds->num_row, (double)bytes / 1048576.0, why);
+    };
+    if (item_off_ != user_off_ + (unsigned)mp_.num_user || n_uiset_ >= 0x7FFFFFFFL) { refuse("W_user and W_item are not adjacent in W"); return; }
+    if (m >= 0x7FFFFFFFL) { refuse("more than 2^31 slots"); return; }
+    if (runs_stage_max_mb_ >= 0 && bytes > (int64_t)runs_stage_max_mb_ * 1048576) { refuse("above runs_stage_max_mb"); return; }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); refuse("hipMemGetInfo failed"); return; }
+    if ((uint64_t)bytes > (uint64_t)free_b / 2) { refuse("more than half of the free device memory"); return; }
+    if (!try_reserve(ds->rn_stage_row, (size_t)m * (size_t)pitch_) || !try_reserve(ds->rn_stage_bias, (size_t)m) || !try_reserve(ds->rn_dst, (size_t)m) ||
+        !try_reserve(ds->rn_first, (size_t)nrow)) { refuse("hipMalloc failed"); return; }
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    struct FreeTmp { void *&p; ~FreeTmp() { if (p) (void)hipFree(p); } } free_tmp{tmp};
+    try {
+        DevBuf<unsigned> pos_of, ka, kb, va, vb;   // scratch of the build: 16 bytes per slot
+        if (!try_reserve(pos_of, (size_t)nunit) || !try_reserve(ka, (size_t)m) || !try_reserve(kb, (size_t)m) || !try_reserve(va, (size_t)m) || !try_reserve(vb, (size_t)m)) {
+            refuse("hipMalloc failed");
+            return;
+        }
+        RunSchedule S;
+        memset(&S, 0, sizeof(S));
+        S.item = ds->rn_item.p;
+        for (int j = 0; j < R; j++) S.user[j] = ds->rn_user[j].p;
+        launch_runs_stage_links(S, ds->order_dev.p, nunit, R, (unsigned)mp_.num_user, user_off_, pos_of.p, ka.p, kb.p, va.p, vb.p, &tmp, &tmp_bytes, ds->rn_dst.p,
+                                ds->rn_first.p, nrow, stream_);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(stream_));
+    } catch (const std::exception &ex) {
+        (void)hipGetLastError();
+        refuse(ex.what());
+        return;
+    }
+    ds->rn_stage_state = 1;
+    ds->rn_stage_row0 = user_off_;
+    ds->rn_stage_bytes = bytes;
 }
 
 void Engine::runs_train(Dataset *ds) {
@@ -94,6 +155,13 @@ void Engine::runs_train(Dataset *ds) {
     S.item = ds->rn_item.p;
     for (int j = 0; j < ds->rn_len; j++) { S.user[j] = ds->rn_user[j].p; S.label[j] = ds->rn_label[j].p; }
     const Schedule &sc = ds->sched;
+    if (runs_stage_ && ds->rn_stage_state == 0) runs_stage_build(ds);   // a data set built while the knob was off
+    if (runs_staged(ds)) {
+        // W is the truth between passes: every touched row goes to the slot of its first touch, the levels hand it on from slot to slot, its last touch writes it home
+        S.dst = ds->rn_dst.p; S.stage_row = ds->rn_stage_row.p; S.stage_bias = ds->rn_stage_bias.p; S.nunit = ds->num_units;
+        launch_runs_stage_in(P, ds->rn_first.p, (long)mp_.num_user + (long)mp_.num_item, user_off_, S.stage_row, S.stage_bias, stream_);
+        n_launches_++;
+    }
     for (size_t l = 0; l < sc.num_levels(); l++) launch_basicmf_runs_soa(P, S, sc.level_ptr[l], sc.level_ptr[l + 1], ds->rn_len, runs_sets_, runs_block_, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_ += (int64_t)sc.num_levels();

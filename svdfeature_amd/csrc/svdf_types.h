@@ -120,7 +120,15 @@ struct RunSchedule {
     const unsigned *item;
     const unsigned *user[8];
     const float *label[8];
+    // operand staging (knob "runs_stage"): operand (j, s) -- j = 0 the item row of run s, j = 1 .. R its users' rows -- lies in
+    // slot j * nunit + s of stage_row (pitch floats each) / stage_bias; dst[slot] = the slot of the row's NEXT touch, RUNS_HOME | W row at its
+    // last touch of the pass, SLOT_ABSENT for a hole (never read or written).  nullptr: rows are read from and written to W.
+    const unsigned *dst;
+    float *stage_row;
+    float *stage_bias;
+    long nunit;
 };
+enum : unsigned { RUNS_HOME = 0x80000000u };
 
 // USER-RUN UNITS of rank pairs (svdf_k_wave.hip: k_pair_units; svdf_punit.cpp; round 6): the reference's own pair order (apex_svd_data.cpp:946-965) emits a
 // user's pairs back to back.  A unit = up to `cap` CONSECUTIVE pairs of one user whose item ids are pairwise distinct; a wave keeps the user's row in
