@@ -615,6 +615,33 @@ int svdf_rand_skip(long n);
  * pattern is first_bits + j*step_bits.  Tests compare it with the host libm bit for bit.  Needs a GPU. */
 int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, float *out, long n);
 
+/* ---- probes of the window rule of `amd:step = minibatch` (svdf_wseq_rule.h): into how many windows a pass is cut, from knob values and
+ * counts alone.  Host functions, no handle and no GPU; the data-set builders reach the same functions.  Tests compare them with
+ * tests/window_rule.py.
+ * svdf_window_rule: the per-pass rule of one route -- 0 instances given as columns (ratings, rank pairs; item_count, the item lane),
+ * 1 rows (svdf_dataset_from_csr: all three counts, the child marks, both lanes), 2 user-group blocks (the counts, fb_mass, num_block, both
+ * lanes).  Returns the window count, -1 on an unknown route.  A lane with sub == 0 is off; a mark array may be NULL (no side table). */
+typedef struct svdf_window_rule_in {
+    int per_target, per_target_max, per_target_fb, per_target_shared, per_target_child; /* the knobs window_per_target ... */
+    long window;                              /* amd:window rows, 0 = unset */
+    int shared_sub, shared_cap, item_sub, item_cap; /* the lanes of ordered sub-steps: window_shared_sub / _max and their kin */
+    long n, num_block;                        /* instances of the pass; blocks (route 2) */
+    long num_item, num_global, num_shared;    /* lengths of the count (and mark) arrays */
+    const int64_t *item_count, *global_count, *shared_count; /* updates per pass of every item row, global bias, shared user row */
+    const unsigned char *item_child, *shared_child; /* rows that are a feature_item / feature_user child somewhere */
+    long num_fb;
+    const double *fb_mass;                    /* per feedback row: instance-sized updates per pass (route 2) */
+} svdf_window_rule_in;
+long svdf_window_rule(int route, const svdf_window_rule_in *in);
+/* the rule on the windows as cut, one class of rows over `ncol` id columns of n rows each (ids < num_id): from W, more windows at equal
+ * positions until the mean over entries of min(count of the entry's row in its window, sub) (sub 0: the count) is within target * slack
+ * and the most updates of one row in one window within cap * slack; after `rounds` scans, or past n windows, n.  -1 on bad arguments. */
+long svdf_window_rule_as_cut(long W, long n, int ncol, const unsigned *const *cols, long num_id, double target, long cap, int sub,
+                             double slack, int rounds);
+/* the cut of num_block user-group blocks into W windows: W + 1 block positions into cut_out, even positions moved forward to where no
+ * START .. END span is open.  -1 on bad arguments. */
+int svdf_window_block_cuts(long num_block, const int *extend_tag, long W, long *cut_out);
+
 /* ---- host-side conflict-free batch scheduler, exposed so it can be tested without a GPU.
  * Unit r touches resources res[res_ptr[r] .. res_ptr[r+1]) out of num_res.  Writes the batch-sorted
  * (stable) unit order and level_ptr[0..nlevels]; returns the number of batches, -2 if level_cap

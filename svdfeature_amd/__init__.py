@@ -59,6 +59,58 @@ def _opt_ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+class WindowRuleIn(C.Structure):
+    """struct svdf_window_rule_in (include/svdfeature_amd.h)"""
+    _fields_ = [("per_target", C.c_int), ("per_target_max", C.c_int), ("per_target_fb", C.c_int), ("per_target_shared", C.c_int),
+                ("per_target_child", C.c_int), ("window", C.c_long), ("shared_sub", C.c_int), ("shared_cap", C.c_int), ("item_sub", C.c_int),
+                ("item_cap", C.c_int), ("n", C.c_long), ("num_block", C.c_long), ("num_item", C.c_long), ("num_global", C.c_long),
+                ("num_shared", C.c_long), ("item_count", C.c_void_p), ("global_count", C.c_void_p), ("shared_count", C.c_void_p),
+                ("item_child", C.c_void_p), ("shared_child", C.c_void_p), ("num_fb", C.c_long), ("fb_mass", C.c_void_p)]
+
+
+WINDOW_ROUTES = {"columns": 0, "csr": 1, "blocks": 2}
+
+
+def window_rule(route, n, item_count, global_count=(), shared_count=(), item_child=None, shared_child=None, fb_mass=(), num_block=0,
+                shared_lane=(0, 0), item_lane=(0, 0), per_target=24, per_target_max=128, per_target_fb=16, per_target_shared=12,
+                per_target_child=3, window=0):
+    """svdf_window_rule: the window count of `amd:step = minibatch` for one route ("columns", "csr", "blocks") from per-pass counts, the
+    lanes (sub, cap) and the knob values.  A host function: no GPU, no handle; the data-set builders call the same code."""
+    lib = load_library()
+    keep = [np.ascontiguousarray(a, np.int64) for a in (item_count, global_count, shared_count)]
+    marks = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in (item_child, shared_child)]
+    mass = np.ascontiguousarray(fb_mass, np.float64)
+    a = WindowRuleIn(per_target, per_target_max, per_target_fb, per_target_shared, per_target_child, int(window), int(shared_lane[0]),
+                     int(shared_lane[1]), int(item_lane[0]), int(item_lane[1]), int(n), int(num_block), len(keep[0]), len(keep[1]), len(keep[2]),
+                     _opt_ptr(keep[0]), _opt_ptr(keep[1]), _opt_ptr(keep[2]), _opt_ptr(marks[0]), _opt_ptr(marks[1]), len(mass), _opt_ptr(mass))
+    W = lib.svdf_window_rule(WINDOW_ROUTES[route], C.byref(a))
+    if W < 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return W
+
+
+def window_rule_as_cut(W, cols, num_id, target, cap, sub=0, slack=1.5, rounds=40):
+    """svdf_window_rule_as_cut: W raised until one class of rows (ids < num_id, the id columns `cols` of the file's rows) keeps the rule on
+    the windows as cut.  A host function."""
+    lib = load_library()
+    cols = [np.ascontiguousarray(c, np.uint32) for c in cols]
+    ptrs = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+    out = lib.svdf_window_rule_as_cut(int(W), len(cols[0]), len(cols), ptrs, int(num_id), float(target), int(cap), int(sub), float(slack), int(rounds))
+    if out < 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return out
+
+
+def window_block_cuts(extend_tag, W):
+    """svdf_window_block_cuts: the W + 1 block positions at which a pass of user-group blocks is cut into W windows.  A host function."""
+    lib = load_library()
+    tag = np.ascontiguousarray(extend_tag, np.int32)
+    cut = np.zeros(int(W) + 1, np.int64)
+    if lib.svdf_window_block_cuts(len(tag), _pad(tag, np.int32), int(W), cut.ctypes.data_as(C.c_void_p)) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return cut
+
+
 def rank_metrics(sec_ptr, position, ranked=None, nan=None, at=(1, 5, 10, 100)):
     """svdf_rank_eval_metrics: the reference's MAP / MAP@k / Pre@k / Rec@k sums (EvaluatorMAP) over sections of rank positions, plus a
     per-section AUC when `ranked` is given.  A host function: no GPU, no handle.  Returns RankMetrics.as_dict()."""
@@ -210,6 +262,11 @@ def load_library():
     lib.svdf_rand_peek.argtypes = [C.c_long, _i32p]
     lib.svdf_rand_skip.argtypes = [C.c_long]
     lib.svdf_device_expf.argtypes = [C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_long]
+    lib.svdf_window_rule.restype = C.c_long
+    lib.svdf_window_rule.argtypes = [C.c_int, C.POINTER(WindowRuleIn)]
+    lib.svdf_window_rule_as_cut.restype = C.c_long
+    lib.svdf_window_rule_as_cut.argtypes = [C.c_long, C.c_long, C.c_int, C.POINTER(C.c_void_p), C.c_long, C.c_double, C.c_long, C.c_int, C.c_double, C.c_int]
+    lib.svdf_window_block_cuts.argtypes = [C.c_long, _i32p, C.c_long, C.c_void_p]
     lib.svdf_debug_sort_labels.argtypes = [C.c_long, _f32p, _i32p, _i32p]
     lib.svdf_debug_sort_scores.argtypes = [C.c_long, _f32p, C.c_int, _i32p, _i32p]
     lib.svdf_set_error_mode(1)   # python callers get exceptions instead of exit(-1)

@@ -530,7 +530,7 @@ Dataset *Engine::rank_pass_device(const char *path, bool as_windows) {
         HIPCHECK(hipStreamSynchronize(stream_));
         ns_rank_draw_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - draw_t0).count();
     }
-    if (as_windows) {   // the columns stay in HBM: item counts, window rule and windows are built there (svdf_wunit.cpp: wseq_from_device_pairs)
+    if (as_windows) {   // the columns stay in HBM: item counts, window rule and windows are built there (svdf_wseq.cpp: wseq_from_device_pairs)
         rows_as_instances_ = true;
         struct Reset { bool &f; ~Reset() { f = false; } } reset{rows_as_instances_};
         Dataset *seq = wseq_from_device_pairs(P_total, rui.p, ri0.p, rv0.p, ri1.p);

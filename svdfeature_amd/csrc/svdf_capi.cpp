@@ -9,6 +9,7 @@
 
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
+#include "svdf_wseq_rule.h"
 
 namespace svdf {
 void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, const int *ranked, const int *nan, int num_at, const int *at,
@@ -362,6 +363,43 @@ int svdf_rand_skip(long n) { SVDF_GUARD(-1, { svdf::libc_rand_skip(n); return 0;
 
 int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, float *out, long n) {
     SVDF_GUARD(-1, { return svdf::device_expf(in, first_bits, step_bits, out, n); })
+}
+
+// the window rule exposed for CPU tests (tests/test_window_rule.py): svdf_wseq_rule.h, the functions the data-set builders call
+long svdf_window_rule(int route, const svdf_window_rule_in *in) {
+    SVDF_GUARD(-1, {
+        if (!in || route < 0 || route > 2) svdf::fail("svdf_window_rule: bad arguments");
+        svdf::WseqKnobs K;
+        K.per_target = in->per_target; K.per_target_max = in->per_target_max; K.per_target_fb = in->per_target_fb;
+        K.per_target_shared = in->per_target_shared; K.per_target_child = in->per_target_child; K.window = in->window;
+        const svdf::WseqLane shared_lane{in->shared_sub, in->shared_cap}, item_lane{in->item_sub, in->item_cap};
+        svdf::WseqCounts C;
+        C.ci.assign(in->item_count, in->item_count + in->num_item);
+        if (route == 0) return svdf::wseq_rule_columns(K, in->n, C.ci, item_lane);
+        C.cg.assign(in->global_count, in->global_count + in->num_global);
+        C.cs.assign(in->shared_count, in->shared_count + in->num_shared);
+        if (in->item_child) C.ichild.assign(in->item_child, in->item_child + in->num_item);
+        if (in->shared_child) C.uchild.assign(in->shared_child, in->shared_child + in->num_shared);
+        if (route == 1) return svdf::wseq_rule_csr(K, in->n, C, shared_lane, item_lane);
+        return svdf::wseq_rule_blocks(K, in->n, in->num_block, C, std::vector<double>(in->fb_mass, in->fb_mass + in->num_fb), shared_lane, item_lane);
+    })
+}
+long svdf_window_rule_as_cut(long W, long n, int ncol, const unsigned *const *cols, long num_id, double target, long cap, int sub, double slack,
+                             int rounds) {
+    SVDF_GUARD(-1, {
+        if (W < 1 || n < 0 || ncol < 1 || !cols || num_id < 0) svdf::fail("svdf_window_rule_as_cut: bad arguments");
+        for (int c = 0; c < ncol; c++)
+            for (long r = 0; r < n; r++) if ((long)cols[c][r] >= num_id) svdf::fail("svdf_window_rule_as_cut: an id is out of range");
+        return svdf::wseq_windows_actual_columns(W, n, svdf::WseqClass{num_id, target, cap, sub}, std::vector<const unsigned *>(cols, cols + ncol), slack, rounds, true);
+    })
+}
+int svdf_window_block_cuts(long num_block, const int *extend_tag, long W, long *cut_out) {
+    SVDF_GUARD(-1, {
+        if (num_block < 0 || W < 1 || !cut_out) svdf::fail("svdf_window_block_cuts: bad arguments");
+        const std::vector<long> cut = svdf::wseq_block_cuts(num_block, extend_tag, W);
+        std::copy(cut.begin(), cut.end(), cut_out);
+        return 0;
+    })
 }
 
 // host-side scheduler exposed for CPU tests (tests/test_scheduler.py): levels for a CSR stream over

@@ -129,7 +129,7 @@ void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:
         check(!strcmp(val, "minibatch") || !strcmp(val, "levels") || !strcmp(val, "auto"), "amd:step must be minibatch, levels or auto");
         check(!multi_, "amd:step must be set before the model is created");
         multi_step_levels_ = !strcmp(val, "levels");
-        step_minibatch_set_ = !strcmp(val, "minibatch");   // one GPU: opt-in window-minibatch SGD (svdf_wunit.cpp: resident data sets become window sequences)
+        step_minibatch_set_ = !strcmp(val, "minibatch");   // one GPU: opt-in window-minibatch SGD (svdf_wseq.cpp: resident data sets become window sequences)
         step_auto_set_ = !strcmp(val, "auto");             // one GPU: opt-in, decided per resident data set from its level schedule (svdf_dataset.cpp: auto_step)
         // both keys also apply to the rows staged by svdf_update_csr / _csr_batch / _block on a one-GPU handle (svdf_staged.cpp)
     }
@@ -138,7 +138,7 @@ void Engine::set_param(const char *name, const char *val) {  // apex_svd_base.h:
         contrib_bf16_ = !strcmp(val, "bf16");
     }
     if (!strcmp(name, "amd:window")) { stage_window_ = std::max<long>(1, atol(val)); window_set_ = true; }
-    // the data-driven window rule of the window / N-rank steps (svdf_wunit.cpp, svdf_multi.cpp): updates a shared row may meet per window, mean and most
+    // the data-driven window rule of the window / N-rank steps (svdf_wseq_rule.h; svdf_wseq.cpp, svdf_multi.cpp): updates a shared row may meet per window, mean and most
     if (!strcmp(name, "amd:window_per_target")) { check(atoi(val) >= 1, "amd:window_per_target must be positive"); wseq_per_target_ = atoi(val); }
     if (!strcmp(name, "amd:window_per_target_max")) { check(atoi(val) >= 1, "amd:window_per_target_max must be positive"); wseq_per_target_max_ = atoi(val); }
     if (multi_) for (int d = 1; d < gpus_; d++) rank_engine(d)->set_param(name, val);

@@ -781,7 +781,7 @@ void Engine::train_dataset(Dataset *ds) {
     check(ds->sched_signature == schedule_signature(),
           "train_dataset: the dataset was scheduled under another configuration (relaxed-id keys, side tables, lazy decay or kernel-routing knobs changed since it was built); build it again");
     flush();
-    if (ds->kind == 8) {   // one GPU, amd:step = minibatch: the pass as a sequence of windows, each trained and applied in place (svdf_wunit.cpp)
+    if (ds->kind == 8) {   // one GPU, amd:step = minibatch: the pass as a sequence of windows, each trained and applied in place (svdf_wseq.cpp)
         wseq_train(ds);
         HIPCHECK(hipGetLastError());
         n_batches_ += (int64_t)ds->wchild.size();

@@ -197,8 +197,10 @@ struct RankRow {
 };
 
 // libc rand() as a random-access stream (svdf_randstream.cpp): the generator's last 31 values, oldest first
-struct WUnitHost;   // one window's host-built arrays of the user-unit step (svdf_wunit.cpp)
-struct WseqCounts;  // updates per shared target of a pass, for the window rules (svdf_wunit.cpp)
+struct WUnitHost;   // one window's host-built arrays of the user-unit step (svdf_internal.h)
+struct WseqCounts;  // updates per shared target of a pass, for the window rule (svdf_wseq_rule.h)
+struct WseqKnobs;   // the knob values the window rule reads (svdf_wseq_rule.h)
+struct WseqLane;    // a lane of ordered sub-steps: its sub-step and its cap (svdf_wseq_rule.h)
 struct LibcRand { uint32_t x[31]; char *handle = nullptr; };
 bool libc_rand_capture(LibcRand &s);
 void libc_rand_restore(const LibcRand &s);
@@ -752,24 +754,17 @@ class Engine {
     int wseq_hot_sub_ = 128;              // knob "window_hot_sub": an item with more slots than this in a window is applied in sub-steps of this many (0 = off: the round-5 rule, no row more than window_per_target_max per window)
     int wseq_hot_max_ = 2048;             // knob "window_hot_max": the most updates a hot row may meet per window (how stale the USERS' view of it gets); 3 seeds of Zipf(0.7) at the configs[1] size: 1 024 max |dRMSE| 4.2e-5 / 66 ms per pass, 2 048 6.6e-5 / 55 ms, 3 072 7.2e-5 / 52 ms (profiles/r06_hot_lane_calibration.txt)
     DevBuf<float> d_clabel_;
-    int wseq_count_actual_ = 1;           // knob "window_count_actual": 1 = the window rule is evaluated on the windows as they are cut and W raised until it holds (svdf_wunit.cpp: wseq_actual_columns / _csr); 0 = the per-pass rule alone
-    bool wseq_actual_on() const;
-    long wseq_actual_columns(long W, long n, const unsigned *item, const unsigned *item1, int sub, int cap) const;
-    long wseq_actual_csr(long W, long n, const int64_t *row_ptr, const unsigned *feat_index, const WseqCounts &C0, int shared_sub, int item_sub) const;
+    int wseq_count_actual_ = 1;           // knob "window_count_actual": 1 = the window rule is evaluated on the windows as they are cut and W raised until it holds (svdf_wseq_rule.h: wseq_actual_columns / _csr); 0 = the per-pass rule alone
+    WseqKnobs wseq_knobs() const;         // the knob values the window rule reads (svdf_wseq_rule.h), amd:window among them
     bool wseq_hot_ok() const;             // the configuration has the hot lane (unit ratings, fp32 contribution rows, one GPU)
-    long wseq_windows_hot(long n, const std::vector<long> &item_count) const;
-    long wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const;   // the rule of wseq_windows_hot for any (sub-step, cap): ratings and rank pairs
     void wseq_pair_check(const char *what) const;   // window_pair_sub > 0: what the lane does not cover, refused with its cause
     // the refusals common to the sub-step knobs (window_shared_sub, window_item_sub, window_pair_sub) when `knob` is on
     void wseq_sub_check(const char *what, const char *knob, const char *desc, const char *entry, const char *nrank, bool entry_only = false) const;
     std::vector<long> wseq_item_counts(long n, const unsigned *item, const unsigned *item1) const;
-    Dataset *wseq_from_columns(long n, const unsigned *user, const unsigned *item, const unsigned *item1, const float *label, int sub, long W);   // the body of wseq_from_triples / _pairs
-    double wseq_class_term(const std::vector<long> &cnt, int per) const;
+    Dataset *wseq_from_columns(long n, const unsigned *user, const unsigned *item, const unsigned *item1, const float *label,
+                               const std::vector<long> &item_count, WseqLane lane);   // the body of wseq_from_triples / _pairs
     void wseq_count_targets(WseqCounts &C, long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index) const;
     void wseq_adopt_window(Dataset *ds, const WUnitHost &H, long first);
-    // ordered sub-steps of `sub` with at most `cap` updates per row and window: what the rows of two classes (means per_plain / per_child) ask for
-    long wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const;
-    double wseq_max_ratio() const { return (double)wseq_per_target_ / (double)wseq_per_target_max_; }
     int wseq_per_target_ = 24;            // knob "window_per_target": updates a shared row meets per window when amd:window is not given
     bool single_minibatch() const { return step_minibatch_set_ && gpus_ == 1 && !multi_ && !is_peer_; }
     // runs of an item's consecutive ratings as the units of the contract workload's schedule (svdf_runs.cpp / svdf_k_runs.hip)
@@ -821,7 +816,6 @@ class Engine {
     // stderr line says so and names `amd:step = auto` (svdf_dataset.cpp; counters 26 .. 28).  Called once per data set by the C entry points.
     int64_t n_guard_warnings_ = 0;
     AutoDecision guard_last_;
-    long wseq_windows(long n, const std::vector<double> &updates_per_target) const;
     Dataset *wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
     Dataset *wseq_from_blocks(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                               const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value);
@@ -885,7 +879,6 @@ class Engine {
                                        const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
                                        const float *feat_value);
     void multi_train_dataset(Dataset *ds);
-    long multi_windows_for(long n, const std::vector<long> &item_count, bool minibatch) const;
     void multi_synchronize();
     int multi_predict_rank_ = 0;         // owner of the user-group block scored last (predict_block on an amd:gpus handle)
     int multi_exchange_mode_ = 0;        // "amd:exchange": 0 p2p (peer loads / stores between the ranks of this process), 1 rccl

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "svdf_engine.h"
+#include "svdf_wseq_rule.h"   // the window rule (how many windows a pass is cut into): host-only, no Engine
 
 namespace svdf {
 
@@ -40,83 +41,30 @@ struct ScopedNs {   // host-side time accounting (SVDF_PROFILE=1)
 void config_set_train_param(TrainParam &p, const char *name, const char *val);
 void config_set_model_param(ModelParam &p, const char *name, const char *val);
 
-// The window rule evaluated on the windows AS CUT (svdf_wunit.cpp: wseq_windows_actual).  The per-pass rules bound what a
-// row meets per window on average (c / W); the windows are cut at equal positions n w / W, so on a file sorted by item, or one that arrives in
-// bursts, one window can hold all of a row's updates.  A class of shared rows keeps two quantities on the actual windows: the mean over its
-// entries of min(count of the entry's row in its window, sub) (sub 0: the count) at `target`, and the most updates of one row in one window at
-// `cap`.  target <= 0 / cap <= 0: not checked.
-struct WseqClass {
-    long num_id;     // ids of the class are 0 .. num_id - 1
-    double target;
-    long cap;
-    int sub;
+// what one window's host build produces (svdf_wunit.cpp: wunit_build_host) and wunit_adopt uploads: plain arrays, so that the windows of a
+// sequence (svdf_wseq.cpp) can be built by several host threads at once (they share nothing but the caller's read-only columns)
+struct WUnitHost {
+    std::vector<WinUnit> units;
+    std::vector<WinSeg> wsegs;
+    std::vector<float> w_label, w_uval;
+    std::vector<int> rptr, tptr, gptr;
+    std::vector<WinEnt> ent, fbent;
+    std::vector<WinFbRec> fbrec;   // deferred feedback scatter (empty: contribution rows)
+    std::vector<WinTouched> touched;   // one-GPU windows (inplace builds): the targets that keep slots
+    std::vector<int> uptr, upos;       // shared user entries (amd:shared_user_from), WUnitSchedule::uptr / upos / uent; empty: none in the window
+    std::vector<WinEnt> uent;
+    std::vector<int> iptr;             // feature_item children, WUnitSchedule::iptr / ient; empty: none in the window
+    std::vector<WinEnt> ient;
+    std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), then hot item rows (window_item_sub): WUnitSchedule::hot / hrec; empty: none in the window
+    std::vector<WinHotRec> hrec;
+    std::vector<int> pos;              // the source row of every regrouped row (Dataset::win_pos; uploaded for resident data sets only)
+    long nhot_user = 0;                // how many of `hot` are shared user rows
+    bool has_touched = false;
+    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
+    int fixed_ng = -2;
+    bool unit_uval = true, feedback = false;
+    bool shared_uniform = false;       // user-group windows with shared user entries: every segment's rows carry ONE user section (ids, values, private position), at most 4 shared entries
 };
-class WseqCounter {   // one scan: the caller walks the windows in order and adds every entry of the window's rows
- public:
-    explicit WseqCounter(const std::vector<WseqClass> &classes) {
-        for (const WseqClass &k : classes) { cls_.push_back(Class{k, {}, {}, 0.0, 0, 0}); cls_.back().stamp.assign((size_t)k.num_id, -1); cls_.back().count.assign((size_t)k.num_id, 0); }
-    }
-    void begin_scan() { for (Class &c : cls_) { std::fill(c.stamp.begin(), c.stamp.end(), -1); c.sum = 0.0; c.entries = 0; c.worst = 0; } }
-    void begin_window(long w) { w_ = (int)w; }
-    void add(int k, unsigned id) {
-        Class &c = cls_[(size_t)k];
-        if (c.stamp[id] != w_) { c.stamp[id] = w_; c.count[id] = 0; }
-        const int v = ++c.count[id];
-        c.worst = std::max<long>(c.worst, v);
-        // sum over a row's v entries of min(v, sub) = v min(v, sub): what the v-th entry adds to it
-        c.sum += (c.k.sub == 0 || v <= c.k.sub) ? 2.0 * (double)v - 1.0 : (double)c.k.sub;
-        c.entries++;
-    }
-    // how far the worst class is over its bounds, slack included, as a fraction num / den (<= 1: every bound holds)
-    void excess(double slack, double &num, double &den) const {
-        num = 0.0; den = 1.0;
-        auto take = [&](double a, double b) { if (a / b > num / den) { num = a; den = b; } };
-        for (const Class &c : cls_) {
-            if (c.k.target > 0.0 && c.entries > 0) take(c.sum / (double)c.entries, c.k.target * slack);
-            if (c.k.cap > 0) take((double)c.worst, (double)c.k.cap * slack);
-        }
-    }
- private:
-    struct Class { WseqClass k; std::vector<int> stamp, count; double sum; long entries, worst; };
-    std::vector<Class> cls_;
-    int w_ = 0;
-};
-// More windows at equal positions until every class holds on the windows [n w / W, n (w + 1) / W): scan(b0, b1, counter) adds the entries of the
-// file rows [b0, b1).  At most `rounds` scans; then W = n (one row per window meets every bound) when last_resort, else the count reached.
-template <typename Scan>
-long wseq_windows_actual(long W, long n, const std::vector<WseqClass> &classes, double slack, int rounds, bool last_resort, Scan scan) {
-    if (n <= 0) return W;
-    WseqCounter C(classes);
-    for (int round = 0; round < rounds; round++) {
-        C.begin_scan();
-        for (long w = 0; w < W; w++) { C.begin_window(w); scan(n * w / W, n * (w + 1) / W, C); }
-        double num, den;
-        C.excess(slack, num, den);
-        if (num <= den) return W;
-        W = std::max<long>(W + 1, (long)std::ceil((double)W * num / den));
-        if (W >= n) return n;
-    }
-    return last_resort ? n : W;
-}
-// The same search for ONE class without sub-steps (sub 0) whose entries are counted elsewhere (device columns: svdf_k_rankwin.hip): count(W, sum,
-// worst) gives the sum over (row, window) of c^2 -- what WseqCounter::add's 2 v - 1 terms add up to -- and the largest c on the W windows.  The
-// counter's sums are doubles of integers, so the integers give the same excess and the same W.
-template <typename Count>
-long wseq_windows_actual_counted(long W, long n, const WseqClass &k, long entries, double slack, int rounds, bool last_resort, Count count) {
-    if (n <= 0) return W;
-    for (int round = 0; round < rounds; round++) {
-        unsigned long long sum = 0ull, worst = 0ull;
-        count(W, sum, worst);
-        double num = 0.0, den = 1.0;
-        auto take = [&](double a, double b) { if (a / b > num / den) { num = a; den = b; } };
-        if (k.target > 0.0 && entries > 0) take((double)sum / (double)entries, k.target * slack);
-        if (k.cap > 0) take((double)(long)worst, (double)k.cap * slack);
-        if (num <= den) return W;
-        W = std::max<long>(W + 1, (long)std::ceil((double)W * num / den));
-        if (W >= n) return n;
-    }
-    return last_resort ? n : W;
-}
 
 // Pointer arrays handed over by a caller are checked before anything indexes through them (the messages of dataset_from_csr /
 // dataset_from_blocks): counts not negative, pointers starting at >= 0 and non-decreasing, fewer than 2^31 entries.

@@ -404,32 +404,14 @@ void Engine::multi_flush(HostCSR &src) {
     MCHECK(hipSetDevice(device_));
 }
 
-// The automatic window assumes every item is updated equally often (per_item x num_item instances per window).  A resident data
-// set knows better: an instance meets  sum_i c_i^2 / n  updates of its own items per pass (c_i = rows that carry item i), which is
-// n / num_item for a uniform catalogue and larger for a skewed one -- THAT is kept at `per_item` per window.
-long Engine::multi_windows_for(long n, const std::vector<long> &item_count, bool minibatch) const {
-    long W = std::max<long>(1, (n + stage_window_ - 1) / stage_window_);
-    if (window_set_ || n <= 0) return W;
-    double s2 = 0.0;
-    long mx = 0;
-    for (long c : item_count) { s2 += (double)c * (double)c; mx = std::max(mx, c); }
-    const double per_item = !minibatch ? (gpus_ <= 2 ? 64.0 : (gpus_ <= 4 ? 42.0 : 32.0)) : 24.0;
-    // ... and no row more than window_per_target_max updates per window (skewed data: svdf_wunit.cpp, mean_updates_met)
-    const double need = std::max(s2 / (double)n / per_item, (double)mx / (double)wseq_per_target_max_);
-    return std::max<long>(W, (long)std::ceil(need));
-}
-
 // multi_windows_for bounds a row's updates per window on AVERAGE (mx / cap windows), but the windows are cut at equal row positions n w / W:
 // a hot item whose rows are clustered in the file (sorted or bursty input) would still meet far more than the cap inside one window -- the
 // condition under which stale sums diverge (the staged path's next_cut enforces the bound exactly).  Count per window after cutting and
-// take more windows until the bound holds: the cap alone, without slack (wseq_windows_actual, svdf_internal.h -- the one-GPU sequences keep
-// their means there as well).  cols: the item columns of the rows (one for ratings, two for rank pairs).
-static long multi_windows_capped(long W, long n, long num_item, long cap, bool fixed, std::initializer_list<const unsigned *> cols) {
+// take more windows until the bound holds: the cap alone, without slack (wseq_windows_actual_columns, svdf_wseq_rule.h -- the one-GPU sequences
+// keep their means there as well).  cols: the item columns of the rows (one for ratings, two for rank pairs).
+static long multi_windows_capped(long W, long n, long num_item, long cap, bool fixed, const std::vector<const unsigned *> &cols) {
     if (fixed || n <= 0 || cap <= 0) return W;
-    return wseq_windows_actual(W, n, {WseqClass{num_item, 0.0, cap, 0}}, 1.0, 12, false, [&](long b0, long b1, WseqCounter &C) {
-        for (const unsigned *c : cols)
-            for (long r = b0; r < b1; r++) C.add(0, c[r]);
-    });
+    return wseq_windows_actual_columns(W, n, WseqClass{num_item, 0.0, cap, 0}, cols, 1.0, 12, false);
 }
 
 // ---- resident data sets on the handle: sharded by user, cut into windows at global positions, one child per (rank, window)
@@ -449,7 +431,7 @@ Dataset *Engine::multi_dataset_from_triples(long n, const unsigned *user, const 
     ds->m_minibatch = mbatch;
     std::vector<long> cnt((size_t)mp_.num_item, 0);
     for (long r = 0; r < n; r++) cnt[item[r]]++;
-    const long W = multi_windows_capped(multi_windows_for(n, cnt, mbatch), n, mp_.num_item, mbatch ? wseq_per_target_max_ : 0, window_set_, {item});
+    const long W = multi_windows_capped(multi_windows_for(wseq_knobs(), gpus_, stage_window_, n, cnt, mbatch), n, mp_.num_item, mbatch ? wseq_per_target_max_ : 0, window_set_, {item});
     ds->mchild.assign((size_t)N, std::vector<Dataset *>((size_t)W, nullptr));
     for (long w = 0; w < W; w++) {
         const long b0 = n * w / W, b1 = n * (w + 1) / W;
@@ -492,7 +474,7 @@ Dataset *Engine::multi_dataset_from_pairs(long n, const unsigned *user, const un
     ds->m_minibatch = true;
     std::vector<long> cnt((size_t)mp_.num_item, 0);
     for (long r = 0; r < n; r++) { cnt[pos[r]]++; cnt[neg[r]]++; }
-    const long W = multi_windows_capped(multi_windows_for(n, cnt, true), n, mp_.num_item, wseq_per_target_max_, window_set_, {pos, neg});
+    const long W = multi_windows_capped(multi_windows_for(wseq_knobs(), gpus_, stage_window_, n, cnt, true), n, mp_.num_item, wseq_per_target_max_, window_set_, {pos, neg});
     ds->mchild.assign((size_t)N, std::vector<Dataset *>((size_t)W, nullptr));
     for (long w = 0; w < W; w++) {
         const long b0 = n * w / W, b1 = n * (w + 1) / W;
@@ -549,7 +531,7 @@ Dataset *Engine::multi_dataset_from_csr(long num_row, const float *row_label, co
         for (int64_t j = row_ptr[(size_t)3 * r + 2]; j < row_ptr[(size_t)3 * r + 3]; j++) if (feat_index[(size_t)j] < (unsigned)mp_.num_item) cnt[feat_index[(size_t)j]]++;
         for (int64_t j = row_ptr[(size_t)3 * r]; j < row_ptr[(size_t)3 * r + 1]; j++) if (feat_index[(size_t)j] < (unsigned)mp_.num_global) gcnt[feat_index[(size_t)j]]++;
     }
-    long W = multi_windows_for(num_row, cnt, units);
+    long W = multi_windows_for(wseq_knobs(), gpus_, stage_window_, num_row, cnt, units);
     if (units && !window_set_) {   // a global bias meets sum c_g^2 / sum c_g updates of its own per pass: kept at the same per-window count
         double s1 = 0.0, s2 = 0.0;
         for (long c : gcnt) { s1 += (double)c; s2 += (double)c * (double)c; }
@@ -628,7 +610,7 @@ Dataset *Engine::multi_dataset_from_blocks(long num_block, const int *extend_tag
     // a row without exactly one user entry): those keep exact conflict-free units per rank, as before the step existed
     const bool wstep = !multi_step_levels_ && wunit_config_ok() &&
                        wunit_blocks_ok(num_block, extend_tag, fb_ptr, fb_index, block_row_ptr, row_ptr, feat_index);
-    long W0 = multi_windows_for(std::max<long>(num_row, 1), cnt, wstep);
+    long W0 = multi_windows_for(wseq_knobs(), gpus_, stage_window_, std::max<long>(num_row, 1), cnt, wstep);
     if (!window_set_ && num_row > 0) {
         // the implicit-feedback rows move by whole-block steps: a block of n rows pushes about n |value| instance-sized updates into
         // every row of its feedback list at once (update_ufeedback, apex_svd_base.h:539-554), and stale sums of those overshoot much
@@ -642,15 +624,9 @@ Dataset *Engine::multi_dataset_from_blocks(long num_block, const int *extend_tag
         }
         double s1 = 0.0, s2 = 0.0;
         for (double m : mass) { s1 += m; s2 += m * m; }
-        if (s1 > 0.0) W0 = std::max<long>(W0, std::min<long>(num_block, (long)std::ceil(s2 / s1 / (wstep ? (double)wseq_per_target_fb_ : 24.0))));   // window-minibatch step: calibrated at 16 (svdf_wunit.cpp)
+        if (s1 > 0.0) W0 = std::max<long>(W0, std::min<long>(num_block, (long)std::ceil(s2 / s1 / (wstep ? (double)wseq_per_target_fb_ : 24.0))));   // window-minibatch step: calibrated at 16 (svdf_wseq_rule.h)
     }
-    std::vector<long> cut{0};
-    for (long w = 1; w < W0; w++) {
-        long pos = std::max<long>(num_block * w / W0, cut.back());
-        while (pos < num_block && pos > 0 && (extend_tag[pos - 1] == TAG_START || extend_tag[pos - 1] == TAG_MIDDLE)) pos++;
-        cut.push_back(pos);
-    }
-    cut.push_back(num_block);
+    const std::vector<long> cut = wseq_block_cuts(num_block, extend_tag, W0);
     const long W = (long)cut.size() - 1;
     flush();
     MultiScope local;

@@ -1,6 +1,7 @@
 // svdf_wunit.cpp -- host side of the window-minibatch step for user units (svdf_k_wunit.hip): builds the
 // window data sets of user-group (SVD++) blocks and of rows with global features -- units, segments, regrouped rows, contribution
-// slots in file order -- and the one-GPU window sequence behind `amd:step = minibatch`.
+// slots in file order --, the shape checks and the config refusals.  The one-GPU window sequence behind `amd:step = minibatch` that is built
+// from these windows: svdf_wseq.cpp.
 //
 // What the step replaces in the reference: the shared-state part of SVDPPFeature::update (apex_svd_base.h:568-582: prepare_ufeedback
 // :523-538, update_ufeedback :539-554) and of update_no_decay / regularize on item rows and global biases (:383-427, :188-210) is
@@ -28,31 +29,6 @@ struct HostSeg {
     bool has_user = false;
 };
 }  // namespace
-
-// what one window's host build produces (wunit_build_host) and wunit_adopt uploads: plain arrays, so that the windows of a sequence can be
-// built by several host threads at once (they share nothing but the caller's read-only columns)
-struct WUnitHost {
-    std::vector<WinUnit> units;
-    std::vector<WinSeg> wsegs;
-    std::vector<float> w_label, w_uval;
-    std::vector<int> rptr, tptr, gptr;
-    std::vector<WinEnt> ent, fbent;
-    std::vector<WinFbRec> fbrec;   // deferred feedback scatter (empty: contribution rows)
-    std::vector<WinTouched> touched;   // one-GPU windows (inplace builds): the targets that keep slots
-    std::vector<int> uptr, upos;       // shared user entries (amd:shared_user_from), WUnitSchedule::uptr / upos / uent; empty: none in the window
-    std::vector<WinEnt> uent;
-    std::vector<int> iptr;             // feature_item children, WUnitSchedule::iptr / ient; empty: none in the window
-    std::vector<WinEnt> ient;
-    std::vector<WinHot> hot;           // hot shared user rows (window_shared_sub), then hot item rows (window_item_sub): WUnitSchedule::hot / hrec; empty: none in the window
-    std::vector<WinHotRec> hrec;
-    std::vector<int> pos;              // the source row of every regrouped row (Dataset::win_pos; uploaded for resident data sets only)
-    long nhot_user = 0;                // how many of `hot` are shared user rows
-    bool has_touched = false;
-    long nrow = 0, nent = 0, nfbe = 0, item_entries = 0, global_entries = 0, nshared = 0, shared_entries = 0, item_children = 0;
-    int fixed_ng = -2;
-    bool unit_uval = true, feedback = false;
-    bool shared_uniform = false;       // user-group windows with shared user entries: every segment's rows carry ONE user section (ids, values, private position), at most 4 shared entries
-};
 
 WUnitSchedule Engine::wunit_view(const Dataset *ds) const {
     WUnitSchedule S;
@@ -741,70 +717,6 @@ void Engine::wunit_sum(Dataset *ds, void *dst, int half) {
     launch_wunit_sum(params(), wunit_view(ds), dst, half, stream_);
 }
 
-// =============================================================================== one GPU, `amd:step = minibatch`: a sequence of windows
-// OPT-IN and NOT the reference's semantics: the pass is cut into windows; inside a window the shared rows are read as of its start and
-// move once, at its end (the N-rank step run by one rank -- the result does not depend on the number of ranks).
-// Accuracy contract |dRMSE| <= 1e-4 against the sequential pass, like every N > 1 line; the exact level-scheduled pass stays the default.
-// updates_per_target: {item rows, global biases[, feedback rows (instance-sized mass)]}.  Calibrated at the full BASELINE configs[3] sizes
-// on three data seeds, 4 and 10 passes (profiles/r04_wstep_calibration.txt): item rows / global biases at 24 per window, feedback rows at 16
-// keep |dRMSE| <= 6.2e-5 (SVD++: 24 -> 9.2e-5, 48 -> 1.6e-4; neighbourhood: 64 -> 2.1e-5, 256 -> 1.8e-4 after 10 passes).
-long Engine::wseq_windows(long n, const std::vector<double> &updates_per_target) const {
-    if (n <= 0) return 1;
-    if (window_set_) return std::max<long>(1, (n + stage_window_ - 1) / stage_window_);
-    double worst = 0.0;
-    for (size_t j = 0; j < updates_per_target.size(); j++)
-        worst = std::max(worst, updates_per_target[j] / (double)(j == 2 ? wseq_per_target_fb_ : wseq_per_target_));
-    return std::max<long>(1, (long)std::ceil(worst));
-}
-
-
-// How many updates of its own target an entry meets per pass: sum c^2 / sum c (the MEAN over entries, what the calibrations at the uniform
-// BASELINE sizes bound at 24 per window) -- and, for skewed data, the MAX: a row that collects far more updates in one window than the
-// mean (a Zipf-popular item: 800 where the mean is 24) has all of them computed against its window-start value and overshoots; the pass
-// diverges (NaN on Zipf(0.7) items, round 5).  max c is therefore bounded at `per_max` per window, expressed here on the mean's scale.
-static double mean_updates_met(const std::vector<long> &cnt, double per_mean_over_per_max) {
-    double s1 = 0.0, s2 = 0.0;
-    long mx = 0;
-    for (long c : cnt) { s1 += (double)c; s2 += (double)c * (double)c; mx = std::max(mx, c); }
-    return std::max(s1 > 0.0 ? s2 / s1 : 0.0, (double)mx * per_mean_over_per_max);
-}
-// the term of a class of rows with a per-target mean of its own (`per`: window_per_target_shared, window_per_target_child) under the common cap
-// (window_per_target_max), expressed on the item term's scale
-double Engine::wseq_class_term(const std::vector<long> &cnt, int per) const {
-    return cnt.empty() ? 0.0 : mean_updates_met(cnt, (double)per / (double)wseq_per_target_max_) * (double)wseq_per_target_ / (double)per;
-}
-
-// The windows of a sequence share nothing but the caller's read-only columns: their host builds run on several threads (a quarter of the
-// host's hardware threads, at most 32 and at most `wseq_build_threads`), a batch of windows at a time; uploads stay with the calling thread,
-// in window order.  A failure inside a worker is reported by the calling thread (the error text is thread-local).
-template <typename BuildFn, typename AdoptFn>
-static void wseq_build_windows(long W, int max_threads, BuildFn build, AdoptFn adopt_window, int64_t &ns_host, int64_t &ns_adopt) {
-    const long hw = (long)std::thread::hardware_concurrency();
-    const long T = std::max<long>(1, std::min<long>(std::min<long>(W, max_threads), std::max<long>(1, std::min<long>(32, hw / 4))));
-    for (long w0 = 0; w0 < W; w0 += T) {
-        const long nb = std::min<long>(T, W - w0);
-        std::vector<WUnitHost> H((size_t)nb);
-        std::vector<std::string> err((size_t)nb);
-        std::vector<char> failed((size_t)nb, 0);
-        auto work = [&](long j) {
-            try { build(w0 + j, H[(size_t)j]); }
-            catch (const std::exception &e) { failed[(size_t)j] = 1; err[(size_t)j] = e.what(); }
-        };
-        std::unique_ptr<ScopedNs> timer(new ScopedNs(ns_host));   // wall time of the batch's host builds ...
-        if (nb == 1) work(0);
-        else {
-            std::vector<std::thread> th;
-            for (long j = 1; j < nb; j++) th.emplace_back(work, j);
-            work(0);
-            for (auto &t : th) t.join();
-        }
-        timer.reset();
-        for (long j = 0; j < nb; j++) if (failed[(size_t)j]) fail(err[(size_t)j]);
-        ScopedNs adopt_timer(ns_adopt);                            // ... and of its windows' allocations, uploads and synchronisations
-        for (long j = 0; j < nb; j++) { adopt_window(w0 + j, H[(size_t)j]); H[(size_t)j] = WUnitHost(); }
-    }
-}
-
 void validate_csr_pointers(long num_row, const int64_t *row_ptr) {
     check(num_row >= 0, "dataset: negative row count");
     if (num_row == 0) return;
@@ -872,499 +784,6 @@ bool wunit_blocks_ok(long num_block, const int *extend_tag, const int64_t *fb_pt
         open = (tag == TAG_START || tag == TAG_MIDDLE);
     }
     return !open;
-}
-
-// The window count one side's rows ask for when hot ones move in ordered sub-steps of `sub` (modelled on wseq_windows_hot below): the shared user
-// rows under window_shared_sub > 0 (cap window_shared_max), the item rows under window_item_sub > 0 (cap window_item_max; 6m).
-// Per class -- plain rows at per_plain (window_per_target_shared / window_per_target), side-table children at per_child (window_per_target_child) --
-// the mean over entries of the changes formed against ONE value of a row, sum_j min(c_j / W, sub) c_j / sum_j c_j, stays at the class value; and
-// no row of the side meets more than `cap` updates per window (how stale everybody else's view of it gets).
-long Engine::wseq_windows_shared(long n, const std::vector<long> &plain, const std::vector<long> &child, int sub, int cap, int per_plain, int per_child) const {
-    if (n <= 0) return 1;
-    long mx = 0;
-    for (long c : plain) mx = std::max(mx, c);
-    for (long c : child) mx = std::max(mx, c);
-    auto met = [&](const std::vector<long> &cnt, long W) {
-        double s = 0.0, s1 = 0.0;
-        for (long c : cnt) { s += std::min((double)c / (double)W, (double)sub) * (double)c; s1 += (double)c; }
-        return s1 > 0.0 ? s / s1 : 0.0;
-    };
-    auto ok = [&](long W) { return met(plain, W) <= (double)per_plain && met(child, W) <= (double)per_child; };
-    long lo = std::max<long>(1, (mx + cap - 1) / cap);
-    if (ok(lo)) return lo;
-    long hi = lo;
-    while (!ok(hi) && hi < n) hi *= 2;
-    while (lo + 1 < hi) { const long mid = (lo + hi) / 2; if (ok(mid)) hi = mid; else lo = mid; }
-    return hi;
-}
-
-// How often a pass updates every shared target, for the window rules of the csr and block sequences: rows [r0, r1) counted into item rows (ci; a
-// feature_item child's row too, marked in ichild), global biases (cg) and shared user rows (cs, by id - amd:shared_user_from; a feature_user child
-// marked in uchild).  The marks are empty without the table.
-struct WseqCounts {
-    std::vector<long> ci, cg, cs;
-    std::vector<unsigned char> ichild, uchild;
-};
-void Engine::wseq_count_targets(WseqCounts &C, long r0, long r1, const int64_t *row_ptr, const unsigned *feat_index) const {
-    std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
-    ci.assign((size_t)mp_.num_item, 0); cg.assign((size_t)mp_.num_global, 0);
-    cs.assign(shared_user() ? (size_t)std::max<long>(mp_.num_user - (long)shared_user_from_, 0) : 0, 0);
-    C.ichild.assign(feat_item_.num_row() ? (size_t)mp_.num_item : 0, 0);
-    C.uchild.assign(feat_user_.num_row() ? cs.size() : 0, 0);
-    const SideTable &FU = feat_user_, &FI = feat_item_;
-    for (long r = r0; r < r1; r++) {
-        for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) { if (feat_index[j] >= (unsigned)mp_.num_global) fail("global feature index exceed setting"); cg[feat_index[j]]++; }
-        for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) {
-            const unsigned i = feat_index[j];
-            if (i >= (unsigned)mp_.num_item) fail("item feature index exceed bound");
-            ci[i]++;
-            if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) { ci[FI.index[c]]++; C.ichild[FI.index[c]] = 1; }
-        }
-        if (!cs.empty())
-            for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++) {
-                const unsigned u = feat_index[j];
-                if (u >= shared_user_from_ && u < (unsigned)mp_.num_user) cs[u - shared_user_from_]++;
-                if (u < FU.num_row())
-                    for (unsigned c = FU.row_ptr[u]; c < FU.row_ptr[u + 1]; c++)
-                        if (FU.index[c] >= shared_user_from_) { cs[FU.index[c] - shared_user_from_]++; C.uchild[FU.index[c] - shared_user_from_] = 1; }
-            }
-    }
-}
-// one built window joins its sequence: uploaded, its first source row recorded
-void Engine::wseq_adopt_window(Dataset *ds, const WUnitHost &H, long first) {
-    std::unique_ptr<Dataset> c(new Dataset());
-    adopt(c.get());
-    wunit_adopt(c.get(), H);
-    ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-    ds->wchild.push_back(c.release());
-    ds->wfirst.push_back(first);
-}
-
-Dataset *Engine::wseq_from_csr(long n, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index, const float *feat_value) {
-    wunit_check_config("dataset_from_csr", true);
-    validate_csr_pointers(n, row_ptr);
-    WseqCounts C;
-    wseq_count_targets(C, 0, n, row_ptr, feat_index);
-    std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
-    const std::vector<unsigned char> &ichild = C.ichild, &uchild = C.uchild;   // item rows / shared user rows that are a side-table child somewhere
-    // side-table children: a row that is a child anywhere -- a feature_user child among the shared user rows, a feature_item
-    // child among the item rows -- is a target of its own kind, with all its updates (as a plain entry too), at window_per_target_child
-    std::vector<long> cc, ccu;   // (ccu: the feature_user children alone, for the rule with ordered sub-steps below)
-    for (size_t i = 0; i < ichild.size(); i++) if (ichild[i]) { cc.push_back(ci[i]); ci[i] = 0; }
-    for (size_t j = 0; j < uchild.size(); j++) if (uchild[j]) { cc.push_back(cs[j]); ccu.push_back(cs[j]); cs[j] = 0; }
-    // shared user rows are shared targets like item rows: the same rule (mean and most updates met per window), with a per-target mean of their
-    // own (window_per_target_shared, 12: a bucket row met by 1/64 of all rows is far hotter than the items the 24 was calibrated on, and 24 left
-    // |dRMSE| at 1.3e-4 on the SURVEY 8(d2) variant) and the common cap (window_per_target_max).  Expressed on the item term's scale.
-    const double shared_met = wseq_class_term(cs, wseq_per_target_shared_), child_met = wseq_class_term(cc, wseq_per_target_child_);
-    long W;
-    const int shared_sub = shared_user() ? wseq_shared_sub_ : 0;
-    const int item_sub = wseq_item_sub_;
-    if (shared_sub > 0 || item_sub > 0) {
-        // ordered sub-steps (DESIGN.md sections 6k / 6m): a side whose hot rows ride a lane leaves the common term -- its rows follow
-        // wseq_windows_shared -- and the other side keeps its own: item rows at window_per_target, shared user rows at window_per_target_shared,
-        // either side's children at window_per_target_child.  The global biases keep their term.
-        cc.resize(cc.size() - ccu.size());   // (cc: the feature_item children alone from here on)
-        const double item_term = item_sub > 0 ? 0.0 : std::max(mean_updates_met(ci, wseq_max_ratio()), wseq_class_term(cc, wseq_per_target_child_));
-        // (a user side that stays in the common term keeps the children's term as it was: the mean over the children of BOTH sides)
-        const double user_term = shared_sub > 0 ? 0.0 : std::max(shared_met, ccu.empty() ? 0.0 : child_met);
-        W = wseq_windows(n, {std::max(item_term, user_term), mean_updates_met(cg, wseq_max_ratio())});
-        if (!window_set_ && shared_sub > 0) W = std::max(W, wseq_windows_shared(n, cs, ccu, shared_sub, wseq_shared_max_, wseq_per_target_shared_, wseq_per_target_child_));
-        if (!window_set_ && item_sub > 0) W = std::max(W, wseq_windows_shared(n, ci, cc, item_sub, wseq_item_max_, wseq_per_target_, wseq_per_target_child_));
-    } else
-        W = wseq_windows(n, {std::max({mean_updates_met(ci, wseq_max_ratio()), shared_met, child_met}), mean_updates_met(cg, wseq_max_ratio())});
-    W = wseq_actual_csr(W, n, row_ptr, feat_index, C, shared_sub, item_sub);   // (C: ci / cs of the children are zeroed above, the marks are what it reads)
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
-    ds->wseq_shared_sub = shared_sub;
-    ds->wseq_item_sub = item_sub;
-    const bool inplace = wunit_inplace_ != 0;   // a window is summed in place right after its walk (wseq_train): single contributions need no slot
-    wseq_build_windows(W, wseq_build_threads_,
-        [&](long w, WUnitHost &H) {
-            const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            wunit_host_from_csr(H, inplace, b1 - b0, row_label + b0, row_ptr + 3 * b0, feat_index, feat_value, true, shared_sub, item_sub);
-        },
-        [&](long w, const WUnitHost &H) { wseq_adopt_window(ds.get(), H, n * w / W); }, ns_wseq_host_, ns_wseq_adopt_);
-    ds->sched.level_ptr = {0, n};
-    ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
-    return ds.release();
-}
-
-Dataset *Engine::wseq_from_blocks(long num_block, const int *extend_tag, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                                  const int64_t *block_row_ptr, const float *row_label, const int64_t *row_ptr, const unsigned *feat_index,
-                                  const float *feat_value) {
-    wunit_check_config("dataset_from_blocks");
-    validate_block_pointers(num_block, fb_ptr, block_row_ptr);
-    validate_csr_pointers((long)(block_row_ptr[num_block] - block_row_ptr[0]), row_ptr + 3 * block_row_ptr[0]);
-    const long n = (long)(block_row_ptr[num_block] - block_row_ptr[0]);
-    WseqCounts C;   // (user-group trainers load no side tables: no children; cs: the shared user rows of DESIGN.md section 6p)
-    wseq_count_targets(C, (long)block_row_ptr[0], (long)block_row_ptr[num_block], row_ptr, feat_index);
-    const std::vector<long> &ci = C.ci, &cg = C.cg, &cs = C.cs;
-    const double shared_met = wseq_class_term(cs, wseq_per_target_shared_);   // the shared user rows' term, exactly wseq_from_csr's
-    // a feedback row moves by whole-block steps: a block of n rows pushes about n |value| instance-sized updates into every row of its
-    // list at once (update_ufeedback, apex_svd_base.h:539-554) -- the same measure as svdf_multi.cpp's window heuristic
-    std::vector<double> mass((size_t)std::max(num_fb_rows(), 1), 0.0);
-    {
-        long open_rows = 0;
-        for (long b = 0; b < num_block; b++) {
-            const int tag = extend_tag[b];
-            if (tag == TAG_DEFAULT || tag == TAG_START) open_rows = 0;
-            open_rows += (long)(block_row_ptr[b + 1] - block_row_ptr[b]);
-            if (tag == TAG_DEFAULT || tag == TAG_END)
-                for (int64_t j = fb_ptr[b]; j < fb_ptr[b + 1]; j++) {
-                    if (fb_index[j] >= (unsigned)num_fb_rows()) fail("ufeedback id exceed bound");
-                    mass[fb_index[j]] += (double)open_rows * std::fabs((double)fb_value[j]);
-                }
-        }
-    }
-    double m1 = 0.0, m2 = 0.0;
-    for (double m : mass) { m1 += m; m2 += m * m; }
-    // ordered sub-steps for hot shared user rows (knob window_block_sub): the rule of section 6k -- the shared rows' term leaves the
-    // common call, their rows follow wseq_windows_shared with the block knobs; amd:window overrides, and the count stays capped by the number of blocks
-    // ordered sub-steps for hot item rows (knob window_block_item_sub, section 6u): the rule of section 6m likewise -- the item term leaves the common call, the
-    // item rows follow wseq_windows_shared with window_block_item_max as the cap and window_per_target as the mean
-    const int bsub = block_sub(), isub = block_item_sub();
-    long Wn = wseq_windows(n, {isub > 0 ? 0.0 : mean_updates_met(ci, wseq_max_ratio()), mean_updates_met(cg, wseq_max_ratio()), m1 > 0.0 ? m2 / m1 : 0.0, bsub > 0 ? 0.0 : shared_met});
-    if (bsub > 0 && !window_set_) Wn = std::max(Wn, wseq_windows_shared(n, cs, {}, bsub, wseq_block_max_, wseq_per_target_shared_, 0));
-    if (isub > 0 && !window_set_) Wn = std::max(Wn, wseq_windows_shared(n, ci, {}, isub, wseq_block_item_max_, wseq_per_target_, 0));
-    const long W0 = std::min<long>(std::max<long>(num_block, 1), Wn);
-    // cuts in blocks (the rule of multi_gpu.block_window_bounds and svdf_multi.cpp): even block positions moved forward to the next
-    // position where no START..END span is open
-    std::vector<long> cut{0};
-    for (long w = 1; w < W0; w++) {
-        long pos = std::max<long>(num_block * w / W0, cut.back());
-        while (pos < num_block && pos > 0 && (extend_tag[pos - 1] == TAG_START || extend_tag[pos - 1] == TAG_MIDDLE)) pos++;
-        cut.push_back(pos);
-    }
-    cut.push_back(num_block);
-    if (num_block > 0 && (extend_tag[num_block - 1] == TAG_START || extend_tag[num_block - 1] == TAG_MIDDLE)) fail("dataset_from_blocks: the last user's END block is missing");
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
-    ds->wseq_block_sub = bsub;
-    ds->wseq_block_item_sub = isub;
-    const bool inplace = wunit_inplace_ != 0;
-    wseq_build_windows((long)cut.size() - 1, wseq_build_threads_,
-        [&](long w, WUnitHost &H) {
-            wunit_host_from_blocks(H, inplace, cut[(size_t)w], cut[(size_t)w + 1], extend_tag, fb_ptr, fb_index, fb_value, block_row_ptr, row_label, row_ptr,
-                                   feat_index, feat_value, shared_user(), bsub, isub);
-        },
-        [&](long w, const WUnitHost &H) { wseq_adopt_window(ds.get(), H, (long)(block_row_ptr[cut[(size_t)w]] - block_row_ptr[0])); },
-        ns_wseq_host_, ns_wseq_adopt_);
-    ds->sched.level_ptr = {0, n};
-    ds->sched.max_level_size = n;
-    return ds.release();
-}
-
-// Ordered sub-steps (svdf_k_window.hip: k_window_apply): plain ratings of the configurations the window kernels walk with unit values and fp32
-// contribution rows, on the one-GPU sequence (in-place sums).
-bool Engine::wseq_hot_ok() const {
-    return wseq_hot_sub_ > 0 && !contrib_bf16_ && !user_group() && window_rows_allowed() && gpus_ == 1 && !multi_ && !is_peer_;
-}
-// The window count with the hot lane.  What the round-5 rule bounded through ONE number per row -- updates met per window -- are two different things:
-//   * how many changes of a row are computed against one value of it (overshoot: diverges on Zipf items): with sub-steps at most hot_sub for every row,
-//     so the MEAN over entries  sum_i min(c_i / W, hot_sub) c_i / n  is kept at window_per_target (24, the calibration of the uniform sizes);
-//   * how stale the USERS' view of a hot row gets (they read it as of the window start): at most window_hot_max updates (2 048; CPU simulation on a
-//     10 M-rating Zipf(0.7) stream, tools/substep_sim.py: 500 per window +1.5e-5, 1 000 +2.8e-5, 2 000 +6.0e-5, 4 000 +9.1e-5 against the 1e-4 contract;
-//     on the MI355X at the configs[1] size, 3 data seeds: 1 024 -> max 4.2e-5, 2 048 -> 6.6e-5, 3 072 -> 7.2e-5, profiles/r06_hot_lane_calibration.txt).
-long Engine::wseq_windows_hot(long n, const std::vector<long> &item_count) const { return wseq_windows_sub(n, item_count, wseq_hot_sub_, wseq_hot_max_); }
-// the same rule for any sub-step size and cap; the mean is over ENTRIES (sum_i c_i: n for ratings, 2 n for rank pairs, whose items count both signs):
-// wseq_windows_shared's search over one class of rows at window_per_target
-long Engine::wseq_windows_sub(long n, const std::vector<long> &item_count, int sub, int cap) const {
-    if (n <= 0) return 1;
-    if (window_set_) return std::max<long>(1, (n + stage_window_ - 1) / stage_window_);
-    return wseq_windows_shared(n, item_count, {}, sub, cap, wseq_per_target_, 0);
-}
-
-// The per-pass rules above take a row's c updates as spread evenly over the W windows.  On a file sorted by item, or one that arrives in bursts, they
-// are not: one window can hold all of an item's ratings (window_per_target_max 128 against 450 met, NaN at the sizes of profiles/r17_window_orders.md).
-// Knob window_count_actual (default 1): after the per-pass search the rule's two quantities -- the mean over entries of min(count, sub) at the class's
-// per-target value, the most updates of one row at the class's cap -- are counted on the windows as they are cut, and W is raised until both hold
-// (wseq_windows_actual, svdf_internal.h).  Both are taken times kWseqSlack: on a file in random order the actual mean sits above
-// the per-pass figure by about 1 (the Poisson term of E[c^2] / E[c]) and the actual maximum above mx / W by sampling noise, and the window counts of
-// the calibrations (every one of them on shuffled files) must stay what they are.  amd:window overrides everything, as before.
-static constexpr double kWseqSlack = 1.5;
-static constexpr int kWseqRounds = 40;
-bool Engine::wseq_actual_on() const { return wseq_count_actual_ != 0 && !window_set_; }
-long Engine::wseq_actual_columns(long W, long n, const unsigned *item, const unsigned *item1, int sub, int cap) const {
-    if (!wseq_actual_on()) return W;
-    return wseq_windows_actual(W, n, {WseqClass{(long)mp_.num_item, (double)wseq_per_target_, cap, sub}}, kWseqSlack, kWseqRounds, true,
-                               [&](long b0, long b1, WseqCounter &C) {
-                                   for (long r = b0; r < b1; r++) { C.add(0, item[r]); if (item1) C.add(0, item1[r]); }
-                               });
-}
-// the same for rows (wseq_from_csr): item rows, global biases, shared user rows and the side-table children, each class with the target and the cap
-// the per-pass rule gives it.  Without a lane the children of both sides are one class (wseq_from_csr: cc), with one they follow their side.
-long Engine::wseq_actual_csr(long W, long n, const int64_t *row_ptr, const unsigned *feat_index, const WseqCounts &C0, int shared_sub, int item_sub) const {
-    if (!wseq_actual_on()) return W;
-    const long NI = mp_.num_item, NS = (long)C0.cs.size();
-    const bool lanes = shared_sub > 0 || item_sub > 0;
-    const int icap = item_sub > 0 ? wseq_item_max_ : wseq_per_target_max_, ucap = shared_sub > 0 ? wseq_shared_max_ : wseq_per_target_max_;
-    enum { ITEM = 0, GLOBAL = 1, SHARED = 2, ICHILD = 3, UCHILD = 4 };
-    // (without a lane: UCHILD is unused, the feature_user children count into ICHILD at ids NI + j)
-    const std::vector<WseqClass> K{
-        {NI, (double)wseq_per_target_, icap, item_sub},
-        {(long)mp_.num_global, (double)wseq_per_target_, wseq_per_target_max_, 0},
-        {NS, (double)wseq_per_target_shared_, ucap, shared_sub},
-        {NI + (lanes ? 0 : NS), (double)wseq_per_target_child_, icap, item_sub},
-        {lanes ? NS : 0, (double)wseq_per_target_child_, ucap, shared_sub}};
-    const SideTable &FU = feat_user_, &FI = feat_item_;
-    const unsigned B = shared_user_from_;
-    auto item_entry = [&](WseqCounter &C, unsigned i) { C.add(!C0.ichild.empty() && C0.ichild[i] ? ICHILD : ITEM, i); };
-    auto user_entry = [&](WseqCounter &C, unsigned j) {
-        if (!C0.uchild.empty() && C0.uchild[j]) { if (lanes) C.add(UCHILD, j); else C.add(ICHILD, (unsigned)NI + j); }
-        else C.add(SHARED, j);
-    };
-    return wseq_windows_actual(W, n, K, kWseqSlack, kWseqRounds, true, [&](long b0, long b1, WseqCounter &C) {
-        for (long r = b0; r < b1; r++) {
-            for (int64_t j = row_ptr[3 * r]; j < row_ptr[3 * r + 1]; j++) C.add(GLOBAL, feat_index[j]);
-            for (int64_t j = row_ptr[3 * r + 2]; j < row_ptr[3 * r + 3]; j++) {
-                const unsigned i = feat_index[j];
-                item_entry(C, i);
-                if (i < FI.num_row()) for (unsigned c = FI.row_ptr[i]; c < FI.row_ptr[i + 1]; c++) item_entry(C, FI.index[c]);
-            }
-            if (NS > 0)
-                for (int64_t j = row_ptr[3 * r + 1]; j < row_ptr[3 * r + 2]; j++) {
-                    const unsigned u = feat_index[j];
-                    if (u >= B && u < (unsigned)mp_.num_user) user_entry(C, u - B);
-                    if (u < FU.num_row())
-                        for (unsigned c = FU.row_ptr[u]; c < FU.row_ptr[u + 1]; c++) if (FU.index[c] >= B) user_entry(C, FU.index[c] - B);
-                }
-        }
-    });
-}
-
-// how often a pass updates every item: the instances' one (item1 == nullptr) or two item columns
-std::vector<long> Engine::wseq_item_counts(long n, const unsigned *item, const unsigned *item1) const {
-    std::vector<long> ci((size_t)mp_.num_item, 0);
-    for (long r = 0; r < n; r++) {
-        if (item[r] >= (unsigned)mp_.num_item || (item1 && item1[r] >= (unsigned)mp_.num_item)) fail("item feature index exceed bound");
-        ci[item[r]]++;
-        if (item1) ci[item1[r]]++;
-    }
-    return ci;
-}
-// The window sequence of instances given as columns, cut into W windows of equal length: ratings (item, label) or rank pairs (item = the +1 item,
-// item1 = the -1 item, no label).  sub > 0: the windows that hold an item with more than `sub` slots (both entries of a pair count) are marked for
-// the lane of ordered sub-steps (k_window_apply / k_window_apply_pairs).
-Dataset *Engine::wseq_from_columns(long n, const unsigned *user, const unsigned *item, const unsigned *item1, const float *label, int sub, long W) {
-    std::vector<char> whot((size_t)W, 0);
-    if (sub > 0) {   // one scan with per-item stamps
-        std::vector<int> stamp((size_t)mp_.num_item, -1), cnt((size_t)mp_.num_item, 0);
-        for (long w = 0; w < W; w++) {
-            const long b0 = n * w / W, b1 = n * (w + 1) / W;
-            for (long r = b0; r < b1 && !whot[(size_t)w]; r++)
-                for (int e = 0; e < (item1 ? 2 : 1); e++) {
-                    const unsigned it = e == 0 ? item[r] : item1[r];
-                    if (stamp[it] != (int)w) { stamp[it] = (int)w; cnt[it] = 0; }
-                    if (++cnt[it] > sub) whot[(size_t)w] = 1;
-                }
-        }
-    }
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
-    if (item1) ds->wseq_pair_sub = sub;   // (a sequence of pairs records its window_pair_sub, 0 included: wseq_train)
-    // the columns go to HBM in ONE copy each (large pageable copies run at the PCIe rate, 56 GB/s; window-sized ones at a fifth of it), the
-    // windows are regrouped from slices of them (svdf_k_wbuild.hip)
-    DevBuf<unsigned> d_user, d_item, d_item1;
-    DevBuf<float> d_label;
-    const bool resident = device_window_ready() && n > 0;
-    if (resident) {
-        need_device("dataset");
-        d_user.upload(user, (size_t)n, stream_); d_item.upload(item, (size_t)n, stream_);
-        if (label) d_label.upload(label, (size_t)n, stream_);
-        if (item1) d_item1.upload(item1, (size_t)n, stream_);
-    }
-    for (long w = 0; w < W; w++) {
-        const long b0 = n * w / W, b1 = n * (w + 1) / W;
-        std::unique_ptr<Dataset> c(new Dataset());
-        adopt(c.get());
-        if (resident && b1 > b0) {
-            window_build_header(c.get(), b1 - b0, item1 != nullptr);
-            window_build_resident(c.get(), b1 - b0, d_user.p + b0, d_item.p + b0, label ? d_label.p + b0 : nullptr, item1 ? d_item1.p + b0 : nullptr);
-        } else window_build(c.get(), b1 - b0, user + b0, item + b0, label ? label + b0 : nullptr, item1 ? item1 + b0 : nullptr);
-        c->win_hot = whot[(size_t)w] != 0;
-        ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-        ds->wchild.push_back(c.release());
-        ds->wfirst.push_back(b0);
-    }
-    ds->sched.level_ptr = {0, n};
-    ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
-    return ds.release();
-}
-
-Dataset *Engine::wseq_from_triples(long n, const unsigned *user, const unsigned *item, const float *label) {
-    const std::vector<long> ci = wseq_item_counts(n, item, nullptr);
-    const bool hot_lane = wseq_hot_ok();
-    long W = hot_lane ? wseq_windows_hot(n, ci) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    W = wseq_actual_columns(W, n, item, nullptr, hot_lane ? wseq_hot_sub_ : 0, hot_lane ? wseq_hot_max_ : wseq_per_target_max_);
-    Dataset *ds = wseq_from_columns(n, user, item, nullptr, label, hot_lane ? wseq_hot_sub_ : 0, W);
-    ds->wseq_hot_sub = hot_lane ? wseq_hot_sub_ : 0;   // (the lane's sub-step as it took effect, 0 without the lane: wseq_train)
-    return ds;
-}
-
-// rank pairs (BASELINE configs[4]): two signed item entries per instance, two contribution slots per pair.  The window rule counts both
-// entries; amd:window (pairs per window) overrides -- the demo-rate calibration allows ~320 updates per item per window
-// (profiles/r04_pairs_windows_demo_rate.txt), an order of magnitude more than the rating default kept here.
-// window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs): fp32 slots, random-order trainers, the one-GPU sequence
-void Engine::wseq_pair_check(const char *what) const {
-    wseq_sub_check(what, "window_pair_sub", "ordered sub-steps for hot items of rank pairs", "dataset_window_from_pairs",
-                   "the N-rank exchange sums every slot on the wire", true);
-    check(gpus_ == 1 && !multi_ && !is_peer_,
-          "window data sets: window_pair_sub > 0 (ordered sub-steps for hot items of rank pairs) is for the one-GPU window sequence; amd:gpus > 1 sums every slot on the wire");
-    check(wunit_width_ok(), "window data sets: window_pair_sub > 0 needs num_factor <= 256 (the lane of rank pairs has no wide rows)");
-}
-Dataset *Engine::wseq_from_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg) {
-    const std::vector<long> ci = wseq_item_counts(n, pos, neg);
-    const int psub = wseq_pair_sub_;
-    if (psub > 0) wseq_pair_check("dataset_from_pairs");
-    // ordered sub-steps for hot items: the window count of wseq_windows_hot with the pair knobs
-    long W = psub > 0 ? wseq_windows_sub(n, ci, psub, wseq_pair_max_) : wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    W = wseq_actual_columns(W, n, pos, neg, psub, psub > 0 ? wseq_pair_max_ : wseq_per_target_max_);
-    return wseq_from_columns(n, user, pos, neg, nullptr, psub, W);
-}
-// The same sequence for a pass of rank pairs that is in HBM already (the device sampler's columns, file order: Engine::rank_pass_device; DESIGN.md
-// section 6v).  What wseq_from_pairs reads from host arrays -- the item counts, the per-pass W, its raise on the windows as cut -- comes from
-// svdf_k_rankwin.hip: only the num_item counts and two integers per search round cross PCIe.  Without the lane of ordered sub-steps (the caller
-// keeps window_pair_sub > 0 off this route).  The windows are regrouped from slices of the columns like wseq_from_columns' resident form.
-Dataset *Engine::wseq_from_device_pairs(long n, const unsigned *d_user, const unsigned *d_i0, const float *d_v0, const unsigned *d_i1) {
-    const long NI = mp_.num_item, E = 2 * n;
-    std::vector<long> ci((size_t)NI, 0);
-    std::unique_ptr<ScopedNs> timer(new ScopedNs(ns_rank_rule_));
-    DevBuf<unsigned> d_pos, d_neg, d_cnt, d_state, k0, k1, v0, v1;
-    const bool actual = wseq_actual_on() && n > 0;
-    if (n > 0) {
-        need_device("dataset");
-        d_pos.reserve((size_t)n); d_neg.reserve((size_t)n); d_cnt.reserve((size_t)std::max<long>(NI, 1)); d_state.reserve(4);
-        if (actual) { k0.reserve((size_t)E); k1.reserve((size_t)E); v0.reserve((size_t)E); v1.reserve((size_t)E); }
-        HIPCHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)std::max<long>(NI, 1) * sizeof(unsigned), stream_));
-        HIPCHECK(hipMemsetAsync(d_state.p, 0, 4 * sizeof(unsigned), stream_));
-        launch_rank_window_columns(n, d_user, d_i0, d_v0, d_i1, mp_.num_user, NI, d_pos.p, d_neg.p, actual ? k0.p : nullptr, actual ? v0.p : nullptr, d_cnt.p, d_state.p,
-                                   stream_);
-        std::vector<unsigned> hc((size_t)NI);
-        unsigned hs[4] = {0u, 0u, 0u, 0u};
-        if (NI > 0) HIPCHECK(hipMemcpyAsync(hc.data(), d_cnt.p, (size_t)NI * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
-        HIPCHECK(hipMemcpyAsync(hs, d_state.p, sizeof(hs), hipMemcpyDeviceToHost, stream_));
-        HIPCHECK(hipStreamSynchronize(stream_));
-        HIPCHECK(hipGetLastError());
-        if (hs[0] != 0u) return nullptr;
-        for (long i = 0; i < NI; i++) ci[(size_t)i] = (long)hc[(size_t)i];
-    }
-    long W = wseq_windows(n, {mean_updates_met(ci, wseq_max_ratio())});
-    if (actual) {
-        try {
-            DevBuf<char> tmp;
-            const size_t tb = rank_window_sort_bytes(E);
-            tmp.reserve(std::max<size_t>(tb, 1));
-            rank_window_sort(tmp.p, tb, k0.p, k1.p, v0.p, v1.p, E, NI, stream_);
-            DevBuf<unsigned long long> d_out;
-            d_out.reserve(2);
-            W = wseq_windows_actual_counted(W, n, WseqClass{NI, (double)wseq_per_target_, (long)wseq_per_target_max_, 0}, E, kWseqSlack, kWseqRounds, true,
-                                            [&](long w, unsigned long long &sum, unsigned long long &worst) {
-                                                rank_window_sums(k1.p, v1.p, E, n, w, d_out.p, &sum, &worst, stream_);
-                                            });
-        } catch (const std::runtime_error &e) {
-            fail(e.what());
-        }
-        k0.release(); k1.release(); v0.release(); v1.release();
-    }
-    timer.reset(new ScopedNs(ns_rank_wbuild_));
-    std::unique_ptr<Dataset> ds(new Dataset());
-    adopt(ds.get()); ds->kind = 8; ds->num_row = n;
-    ds->wseq_pair_sub = 0;
-    for (long w = 0; w < W; w++) {
-        const long b0 = n * w / W, b1 = n * (w + 1) / W;
-        std::unique_ptr<Dataset> c(new Dataset());
-        adopt(c.get());
-        window_build_header(c.get(), b1 - b0, true, true);
-        if (b1 > b0) window_build_resident(c.get(), b1 - b0, d_user + b0, d_pos.p + b0, nullptr, d_neg.p + b0);   // (returns after the window's read-back: the columns outlive every read)
-        else {   // a pass that drew no pair: one window without instances, the arrays of window_build at n = 0
-            need_device("dataset");
-            c->win_urec.reserve(1); c->item.reserve(1); c->win_slot.reserve(1); c->win_item1.reserve(1); c->win_slot1.reserve(1); c->ival.reserve(1); c->win_ival1.reserve(1);
-            c->win_iptr.reserve((size_t)NI + 1);
-            HIPCHECK(hipMemsetAsync(c->win_iptr.p, 0, ((size_t)NI + 1) * sizeof(int), stream_));
-            HIPCHECK(hipStreamSynchronize(stream_));
-            c->win_has_pos = window_keeps_positions();
-            if (c->win_has_pos) c->win_pos.reserve(1);
-            c->sched_signature = schedule_signature();
-            c->win_item_lo = NI; c->win_item_hi = -1;
-            c->unit_values = true;
-            c->num_units = 0;
-            c->sched.level_ptr = {0, 0};
-            c->sched.max_level_size = 0;
-        }
-        ds->algorithmic_bytes += c->algorithmic_bytes; ds->num_units += c->num_units;
-        ds->wchild.push_back(c.release());
-        ds->wfirst.push_back(b0);
-    }
-    ds->sched.level_ptr = {0, n};
-    ds->sched.max_level_size = W > 0 ? (n + W - 1) / W : n;
-    return ds.release();
-}
-
-// one pass over a window sequence: per window the users' walks, then the per-target sums added in place (two launches per window)
-void Engine::wseq_train(Dataset *ds) {
-    const DevParams &P = params();
-    bool any_hot = false;
-    long max_slots = 1;
-    for (Dataset *c : ds->wchild) if (c->kind == 5 && c->win_hot) { any_hot = true; max_slots = std::max(max_slots, c->win_slots); }
-    const bool pair_seq = ds->wseq_pair_sub >= 0;   // built by wseq_from_pairs: its hot windows belong to the pair lane (window_pair_sub), not to window_hot_sub
-    if (pair_seq) {
-        check(ds->wseq_pair_sub == wseq_pair_sub_,
-              "train_dataset: the window sequence was built with another window_pair_sub (ordered sub-steps for hot items of rank pairs); build the data set again after changing the knob");
-        if (wseq_pair_sub_ > 0) wseq_pair_check("train_dataset");
-    }
-    if (ds->wseq_hot_sub >= 0)   // built by wseq_from_triples: the threshold between cold and hot rows was fixed then (the windows' marks, the window count)
-        check(ds->wseq_hot_sub == (wseq_hot_ok() ? wseq_hot_sub_ : 0),
-              "train_dataset: the window sequence was built with another window_hot_sub (ordered sub-steps for hot items); build the data set again after changing the knob");
-    const bool hot_lane = any_hot && (pair_seq || wseq_hot_ok());
-    if (any_hot) check(hot_lane, "train_dataset: the window sequence was built with ordered sub-steps for hot items (window_hot_sub); the configuration changed since");
-    if (hot_lane) d_clabel_.reserve((size_t)max_slots);
-    if (ds->wseq_shared_sub >= 0)
-        check(ds->wseq_shared_sub == (shared_user() ? wseq_shared_sub_ : 0),
-              "train_dataset: the window sequence was built with another window_shared_sub (ordered sub-steps for hot shared user rows); build the data set again after changing the knob");
-    if (ds->wseq_block_sub >= 0) {
-        check(ds->wseq_block_sub == block_sub(),
-              "train_dataset: the window sequence was built with another window_block_sub (ordered sub-steps for hot shared user rows of SVD++ blocks); build the data set again after changing the knob");
-        check(ds->wseq_block_item_sub == block_item_sub(),
-              "train_dataset: the window sequence was built with another window_block_item_sub (ordered sub-steps for hot item rows of SVD++ blocks); build the data set again after changing the knob");
-        long most = 0;   // the second record plane: sized once, for the largest window's hot records (of both sides)
-        for (Dataset *c : ds->wchild) if (c->wu_feedback && c->wu_nhot + c->wu_nihot > 0) most = std::max(most, c->wu_nhrec);
-        if (most > 0) { d_hfb_.reserve((size_t)most * (size_t)pitch_); d_hfbb_.reserve((size_t)most); }
-    }
-    if (ds->wseq_item_sub >= 0)
-        check(ds->wseq_item_sub == wseq_item_sub_,
-              "train_dataset: the window sequence was built with another window_item_sub (ordered sub-steps for hot item rows); build the data set again after changing the knob");
-    for (Dataset *c : ds->wchild) {
-        if (c->kind == 5) {
-            d_contrib_.reserve((size_t)std::max<long>(c->win_slots, 1) * (size_t)pitch_);
-            d_cbias_.reserve((size_t)std::max<long>(c->win_slots, 1));
-            WindowSchedule S = window_view(c);
-            if (hot_lane && c->win_hot) { S.hot_sub = pair_seq ? wseq_pair_sub_ : wseq_hot_sub_; S.clabel = d_clabel_.p; }
-            launch_window_users(P, S, window_slots_, window_groups_, stream_);
-            if (S.hot_sub > 0 && pair_seq) {   // walk, hot apply (does not write the model: a pair reads its OTHER item's row), then hot rows moved in + the cold sums
-                launch_window_apply_pairs(P, S, mp_.num_item, stream_);
-                launch_window_pair_sums(S, pitch_, mp_.num_factor, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_);
-                n_launches_++;
-            } else if (S.hot_sub > 0) launch_window_apply(P, S, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_);
-            else launch_window_items_local(S, pitch_, mp_.num_factor, 0, mp_.num_item, dW_.p + (size_t)item_off_ * pitch_, dbias_.p + item_off_, stream_, c->win_slots);
-        } else {
-            wunit_train(c);
-            // hot shared user rows in ordered sub-steps: after the walk (its records) and before the sums (which move the finished rows in); the
-            // workgroups run one hot row each, so the launch lasts as long as the hottest row's chain of sub-steps
-            if (c->wu_nhot > 0) {
-                launch_wunit_apply_shared(P, wunit_view(c), stream_, c->wu_feedback);   // (user-group windows: the FB build, knob window_block_sub -- section 6q)
-                n_launches_++;
-                if (c->wu_feedback) n_block_hot_ += c->wu_nhot;   // counter 35
-            }
-            if (c->wu_nihot > 0) {   // hot item rows likewise (neither launch writes the model; user-group windows: the FB build, knob window_block_item_sub -- section 6u)
-                launch_wunit_apply_item(P, wunit_view(c), c->wu_nihot, stream_, c->wu_feedback);
-                n_launches_++;
-                if (c->wu_feedback) n_block_item_hot_ += c->wu_nihot;   // counter 36
-            }
-            wunit_sum(c, nullptr, 0);
-        }
-        n_launches_ += 2;
-        window_trained_ = nullptr;
-    }
 }
 
 }  // namespace svdf

@@ -120,7 +120,7 @@ def item_block_bounds(num_item, world):
     return [(int(num_item) * b) // world for b in range(world + 1)]
 
 
-PER_ITEM_MAX = 128.0   # the most updates ANY item row may meet per window (svdf_wunit.cpp: window_per_target_max; calibrated on Zipf(0.7) items: 512 diverges)
+PER_ITEM_MAX = 128.0   # the most updates ANY item row may meet per window (svdf_wseq_rule.h: window_per_target_max; calibrated on Zipf(0.7) items: 512 diverges)
 
 
 def stratum_num_windows(items, lo, nblk, per_item):

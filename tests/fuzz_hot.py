@@ -1,5 +1,5 @@
 """(not collected by pytest) Randomised differential run of the one-GPU window step with ordered sub-steps (svdf_k_window.hip: k_window_apply,
-k_window_users*; svdf_wunit.cpp: wseq_windows_hot) against oracle/svdf_oracle.c: svdo_update_window_substeps: random sizes, widths 1 .. 256, links, decays,
+k_window_users*; svdf_wseq_rule.h: wseq_rule_columns) against oracle/svdf_oracle.c: svdo_update_window_substeps: random sizes, widths 1 .. 256, links, decays,
 user bias on / off, sub-step sizes 1 .. 128, caps below and above the sub-step, uniform and Zipf items, 1 - 3 passes; every parameter compared bit for bit.
 usage: python tests/fuzz_hot.py [--iters N] [--seed S]"""
 import argparse

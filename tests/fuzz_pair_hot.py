@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """(not collected by pytest) Randomised differential run of the ordered sub-steps for hot items of rank pairs in the window step (knob
-`window_pair_sub`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs).  Random widths (the two
+`window_pair_sub`; svdf_wseq.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs).  Random widths (the two
 slots-walk widths drawn often), links, regularisers (per-id decay ranges on both sides, nonnegative users, user bias on and off, bias decays),
 catalogue sizes, skew (0 ... 4 hot items, drawn as positive and as negative with random probabilities), window sizes, passes and a random
 sub-step 1 ... 16 (1 ... 128 in one draw of eight): `amd:step = minibatch` on one GPU against the checker of tests/window_sim.py on the

@@ -1,6 +1,6 @@
 """(not collected by pytest) Shared by the tests of the ordered sub-steps for hot items of rank pairs in the window step (knob
-`window_pair_sub`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs): the pair draws, what a
-draw holds window by window, the checker call and a Python restatement of the window rule.
+`window_pair_sub`; svdf_wseq.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs): the pair draws, what a
+draw holds window by window and the checker call.  (The window rule: tests/window_rule.py, columns with both items of a pair counted.)
 
 The checker is tests/window_sim.py on the pair-shaped rows of svdfeature_amd.pairs_as_csr -- no global entry, user:1, the two item entries
 in ascending id with the negative's sign flipped, label 1 -- with B = num_user (no shared user row), no tables and isub = window_pair_sub."""
@@ -75,29 +75,3 @@ def check(c, u, pos, neg, W, passes, s, **kw):
     if s == 0:
         return ws.simulate_rows(o, d, nu, W, passes, fu=(), fi=(), user_bias=ub)
     return ws.simulate_rows(o, d, nu, W, passes, isub=s, user_bias=ub, **kw)
-
-
-def rule(counts, s, cap, per=24):
-    """the window count of wseq_from_pairs with window_pair_sub = s > 0 and amd:window unset (svdf_wunit.cpp: wseq_windows_sub): c_i = the
-    pass's slots of item i, both entries of a pair counted; the smallest W >= ceil(max c / window_pair_max) with
-    sum_i min(c_i / W, s) c_i / sum_i c_i <= window_per_target"""
-    counts = [int(c) for c in counts]
-    total = sum(counts)
-    if total == 0:
-        return 1
-
-    def met(W):
-        acc = 0.0
-        for c in counts:
-            acc += min(c / W, float(s)) * c
-        return acc / total
-    W = max(1, -(-max(counts) // cap))
-    while met(W) > per:
-        W += 1
-    return W
-
-
-def default_rule(counts, per=24, per_max=128):
-    """the rule without the lane (svdf_wunit.cpp: mean_updates_met): max(sum c^2 / sum c, max c * per / per_max) / per, rounded up"""
-    c = np.asarray(counts, np.float64)
-    return max(1, int(np.ceil(max(float((c ** 2).sum() / c.sum()), float(c.max()) * per / per_max) / per)))

@@ -1,5 +1,5 @@
 """Ordered sub-steps for hot shared user rows of user-group (SVD++) blocks in the one-GPU window step (knobs `window_block_sub`, `window_block_max`
-under `amd:shared_user_from = B` on a format_type 1 trainer; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_walk<LPI, true, true> and
+under `amd:shared_user_from = B` on a format_type 1 trainer; svdf_wseq.cpp, svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_walk<LPI, true, true> and
 k_wunit_apply_hot<LPI, false, true>).  A shared user row with more than `window_block_sub` slots in a window is applied in
 file order, that many slots at a time, every slot computed from the span state the walk held when it reached the data row (private row and bias,
 tmp_ufeedback and its bias).  All seven views must equal the checker of tests/window_sim.py -- the pinned C port of SVDPPFeature::update with
@@ -9,6 +9,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
@@ -209,41 +210,23 @@ def _dense_blocks(seed, nblocks=3000, nu=300, ns=4, ni=200):
     return BlockArrays.from_blocks(blocks)
 
 
-def _rule(ba, nu, ns, ni, sub, cap, per_shared=12, per=24, per_max=128, per_fb=16):
-    """svdf_wunit.cpp: wseq_from_blocks with window_block_sub > 0, restated: item and feedback terms as before, the shared rows by the search of
-    wseq_windows_shared -- the fewest windows W >= max c / cap at which the mean over entries of min(c / W, sub) stays at window_per_target_shared"""
-    n = ba.num_row
+def _pass_counts(ba, nu, ns, ni):
+    """what the rule of wseq_from_blocks reads: the pass's updates of every item row and shared user row, the feedback rows' mass"""
     rows = ba.rows()
-    ci = np.zeros(ni)
-    cs = np.zeros(ns)
-    for r in range(n):
+    ci = np.zeros(ni, np.int64)
+    cs = np.zeros(ns, np.int64)
+    for r in range(ba.num_row):
         _, ng, nuu, _, idx, _ = rows.row(r)
         for x in idx[ng:ng + nuu]:
             if x >= nu:
                 cs[int(x) - nu] += 1
         for x in idx[ng + nuu:]:
             ci[int(x)] += 1
-
-    def met(c):
-        return max((c ** 2).sum() / c.sum(), c.max() * per / per_max)
     mass = np.zeros(ni)
     for b in ba.to_blocks():
         for f, v in zip(b.index_ufeedback, b.value_ufeedback):
             mass[int(f)] += b.data.num_row * abs(float(v))
-    common = int(np.ceil(max(met(ci) / per, (mass ** 2).sum() / mass.sum() / per_fb)))
-
-    def ok(W):
-        return (np.minimum(cs / W, sub) * cs).sum() / cs.sum() <= per_shared
-    lo = max(1, int(-(-cs.max() // cap)))
-    if not ok(lo):
-        hi = lo
-        while not ok(hi) and hi < n:
-            hi *= 2
-        while lo + 1 < hi:
-            mid = (lo + hi) // 2
-            lo, hi = (lo, mid) if ok(mid) else (mid, hi)
-        lo = hi
-    return min(ba.num_block, max(1, common, lo))
+    return ci, cs, mass
 
 
 @pytest.mark.parametrize("sub,cap", [(12, 512), (8, 128), (12, 64)])
@@ -258,7 +241,8 @@ def test_the_default_window_rule_on_dense_buckets(sub, cap):
     d0 = off.dataset_from_blocks(ba)
     t = _trainer(conf, extra=key, knobs=[("window_block_sub", sub), ("window_block_max", cap)])
     ds = t.dataset_from_blocks(ba)
-    want = _rule(ba, nu, ns, ni, sub, cap)
+    ci, cs, mass = _pass_counts(ba, nu, ns, ni)
+    want = wr.blocks(ba.num_row, ba.num_block, ci, (), cs, mass, shared_lane=(sub, cap))
     assert ds.kind == 8 and ds.num_batches == want and want < d0.num_batches, (ds.num_batches, want, d0.num_batches)
     t.train_dataset(ds)
     t.synchronize()

@@ -10,6 +10,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
@@ -252,14 +253,11 @@ def _zipf_blocks(seed, nblocks=3000, nu=300, ni=200, nf=2000, s=0.7):
     return BlockArrays.from_blocks(blocks)
 
 
-def _rule(ba, ni, nf, sub, cap, per=24, per_max=128, per_fb=16):
-    """svdf_wunit.cpp: wseq_from_blocks, restated.  sub = 0: the common rule -- the mean and (on the mean's scale) the most updates an item meets, the
-    feedback rows' mass.  sub > 0: the item term leaves the common rule, and the items follow the search of wseq_windows_shared -- the fewest windows
-    W >= max c / cap at which the mean over entries of min(c / W, sub) stays at window_per_target"""
-    n = ba.num_row
+def _pass_counts(ba, ni, nf):
+    """what the rule of wseq_from_blocks reads: the pass's updates of every item row, the feedback rows' mass"""
     rows = ba.rows()
-    ci = np.zeros(ni)
-    for r in range(n):
+    ci = np.zeros(ni, np.int64)
+    for r in range(ba.num_row):
         _, ng, nuu, _, idx, _ = rows.row(r)
         for x in idx[ng + nuu:]:
             ci[int(x)] += 1
@@ -267,23 +265,7 @@ def _rule(ba, ni, nf, sub, cap, per=24, per_max=128, per_fb=16):
     for b in ba.to_blocks():
         for f, v in zip(b.index_ufeedback, b.value_ufeedback):
             mass[int(f)] += b.data.num_row * abs(float(v))
-    fb = (mass ** 2).sum() / mass.sum() / per_fb
-    if sub == 0:
-        met = max((ci ** 2).sum() / ci.sum(), ci.max() * per / per_max)
-        return min(ba.num_block, max(1, int(np.ceil(max(met / per, fb)))))
-
-    def ok(W):
-        return (np.minimum(ci / W, sub) * ci).sum() / ci.sum() <= per
-    lo = max(1, int(-(-ci.max() // cap)))
-    if not ok(lo):
-        hi = lo
-        while not ok(hi) and hi < n:
-            hi *= 2
-        while lo + 1 < hi:
-            mid = (lo + hi) // 2
-            lo, hi = (lo, mid) if ok(mid) else (mid, hi)
-        lo = hi
-    return min(ba.num_block, max(1, int(np.ceil(fb)), lo))
+    return ci, mass
 
 
 @pytest.mark.parametrize("sub,cap", [(12, 512), (64, 128), (24, 2048)])
@@ -295,10 +277,11 @@ def test_the_default_window_rule_on_zipf_items(sub, cap):
     ba = _zipf_blocks(3)
     off = _trainer(conf, extra=MB)
     d0 = off.dataset_from_blocks(ba)
-    assert d0.num_batches == _rule(ba, ni, nf, 0, 0)
+    ci, mass = _pass_counts(ba, ni, nf)
+    assert d0.num_batches == wr.blocks(ba.num_row, ba.num_block, ci, fb_mass=mass)
     t = _trainer(conf, extra=MB, knobs=[("window_block_item_sub", sub), ("window_block_item_max", cap)])
     ds = t.dataset_from_blocks(ba)
-    want = _rule(ba, ni, nf, sub, cap)
+    want = wr.blocks(ba.num_row, ba.num_block, ci, fb_mass=mass, item_lane=(sub, cap))
     assert ds.kind == 8 and ds.num_batches == want, (ds.num_batches, want, d0.num_batches)
     assert want < d0.num_batches or sub > 24   # (sub-steps above window_per_target: the mean over entries asks for the windows, not the cap)
     t.train_dataset(ds)

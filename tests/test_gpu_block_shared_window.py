@@ -10,6 +10,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import BlockArrays, CSRData, PlusBlock
 from svdfeature_amd.data import TAG_DEFAULT, TAG_END, TAG_MIDDLE, TAG_START
@@ -253,7 +254,7 @@ def test_auto_keeps_blocks_with_shared_ids_on_the_exact_levels():
     dm = m.dataset_from_blocks(ba)
     # the shared rows set the window count: 4 ids, at window_per_target_shared = 12 updates met per window
     counts = np.bincount(ba.feat_index[ba.feat_index >= 300] - 300, minlength=4).astype(np.float64)
-    assert dm.kind == 8 and dm.num_batches == int(np.ceil((counts ** 2).sum() / counts.sum() / 12))
+    assert dm.kind == 8 and dm.num_batches == int(np.ceil(wr.met(counts, 0.0) / 12))
     m.train_dataset(dm)
     m.synchronize()
     assert m.counter(34) == dm.num_batches and m.counter(33) == 0   # k = 32: the general kernel

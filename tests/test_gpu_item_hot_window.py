@@ -1,5 +1,5 @@
 """Ordered sub-steps for hot ITEM rows on the csr path of the one-GPU window step (`amd:step = minibatch`, knobs `window_item_sub` /
-`window_item_max`; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_hot<ITEM>).  An item-range row -- a plain item entry's
+`window_item_max`; svdf_wseq.cpp, svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_hot<ITEM>).  An item-range row -- a plain item entry's
 row, a feature_item child's row, or a row that is both -- with more than window_item_sub slots in a window is applied in file order, that many
 slots at a time, every sub-step's changes formed against the row as the previous sub-step left it; everything else moves as in the plain window
 step, hot shared user rows (section 6k) in their own lane.  Every view must equal the checker of tests/window_sim.py -- the pinned C port
@@ -9,6 +9,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import CSRData
 
@@ -256,41 +257,25 @@ def test_knob_at_zero_is_the_knob_unset(tmp_path):
     assert got[3][1] < got[0][1] and not np.array_equal(got[0][2]["W_item"][:3], got[3][2]["W_item"][:3])
 
 
-def _met(counts, per_max_ratio):
-    """svdf_wunit.cpp: mean_updates_met"""
-    c = np.asarray(counts, np.float64)
-    return max(float((c ** 2).sum() / c.sum()), float(c.max()) * per_max_ratio) if c.sum() else 0.0
-
-
-def _rule(plain, child, globs, sub, cap, per=24, per_child=3, per_max=128):
-    """the window count of wseq_from_csr with window_item_sub > 0: the global biases keep their term; the item side asks
-    for the fewest windows with, per class, mean_j min(c_j / W, sub) <= the class value (the mean over entries; plain items at
-    window_per_target, feature_item children at window_per_target_child) and max_j c_j / W <= window_item_max"""
-    w_other = max(1, int(np.ceil(_met(globs, per / per_max) / per)))
-    p, c = np.asarray(plain, np.float64), np.asarray(child, np.float64)
-    mean = lambda x, W: float((np.minimum(x / W, sub) * x).sum() / x.sum()) if x.sum() else 0.0   # noqa: E731
-    W = max(1, int(-(-int(max(p.max(initial=0), c.max(initial=0))) // cap)))
-    while not (mean(p, W) <= per and mean(c, W) <= per_child):
-        W += 1
-    return max(w_other, W)
-
-
 def test_window_rule_with_sub_steps(tmp_path):
     conf, d = _zero_case(tmp_path)
     ti = ws.read_table(str(tmp_path / "fi.txt"))
     counts = ws.item_slot_counts(d, NP, (), ti)
-    is_child = {c for row in ti for c, _ in row}
-    plain = [n for i, n in counts.items() if i not in is_child]
-    child = [n for i, n in counts.items() if i in is_child]
+    ci, child = np.zeros(NI, np.int64), np.zeros(NI, np.uint8)   # the pass's slots of every item-range row; the rows that are a feature_item child
+    for i, n in counts.items():
+        ci[i] = n
+    for row in ti:
+        for c, _ in row:
+            child[c] = 1
     globs = np.bincount(np.concatenate([d.row(r)[4][:d.row(r)[1]] for r in range(d.num_row)]).astype(np.int64), minlength=NG)
     t = _trainer(conf, extra=[("amd:step", "minibatch")])
     default = t.dataset_from_csr(d).num_batches
-    assert default == max(1, int(np.ceil(max(_met(plain, 24 / 128), _met(child, 3 / 128) * 24 / 3, _met(globs, 24 / 128)) / 24)))
+    assert default == wr.csr(d.num_row, ci, globs, item_child=child)
     for sub, cap in ((3, 2048), (3, 64), (2, 256), (8, 128), (24, 512)):
         t.set_knob("window_item_sub", sub)
         t.set_knob("window_item_max", cap)
         W = t.dataset_from_csr(d).num_batches
-        assert W == _rule(plain, child, globs, sub, cap), (sub, cap)
+        assert W == wr.csr(d.num_row, ci, globs, item_child=child, item_lane=(sub, cap)), (sub, cap)
         assert W <= default
     t.set_knob("window_item_sub", 3)
     t.set_knob("window_item_max", 2048)

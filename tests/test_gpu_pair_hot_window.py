@@ -1,5 +1,5 @@
 """Ordered sub-steps for hot items of rank pairs in the one-GPU window step (`amd:step = minibatch`, knobs `window_pair_sub` /
-`window_pair_max`; svdf_wunit.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs / k_window_pair_sums).  An
+`window_pair_max`; svdf_wseq.cpp: wseq_from_pairs, svdf_k_window.hip: k_window_apply_pairs / k_window_pair_sums).  An
 item with more than window_pair_sub slots in a window -- both signs counted -- is applied in file order, that many slots at a time, every
 sub-step's changes formed against the row as the previous sub-step left it and against the OTHER item's window-start row; everything else
 moves as in the plain window step.  Every view must equal the checker of tests/window_sim.py on the pair-shaped rows (tests/pair_hot_cases.py)
@@ -10,6 +10,7 @@ import pytest
 import cases
 import pair_hot_cases as ph
 import svdfeature_amd as sa
+import window_rule as wr
 
 pytestmark = pytest.mark.gpu
 
@@ -141,13 +142,13 @@ def test_window_rule_with_sub_steps():
     counts = np.bincount(np.concatenate([p, q]).astype(np.int64), minlength=NI)
     t = _trainer(ph.conf(16), MB)
     default = t.dataset_from_pairs(u, p, q).num_batches
-    assert default == ph.default_rule(counts) and default > 8
+    assert default == wr.columns(len(u), counts) and default > 8
     seen = set()
     for s, cap in ((5, 2048), (5, 64), (30, 2048), (128, 512), (12, 100), (24, 200)):
         t.set_knob("window_pair_sub", s)
         t.set_knob("window_pair_max", cap)
         W = t.dataset_from_pairs(u, p, q).num_batches
-        assert W == ph.rule(counts, s, cap), (s, cap)
+        assert W == wr.columns(len(u), counts, (s, cap)), (s, cap)
         seen.add(W)
     assert len(seen) >= 4 and 1 in seen
     # amd:window overrides the count, and rows over the threshold still ride the lane (the parity cases above run under amd:window)

@@ -1,5 +1,5 @@
 """Ordered sub-steps for hot shared user rows in the one-GPU window step (`amd:step = minibatch`, knobs `window_shared_sub` /
-`window_shared_max`; svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_shared).  A shared user row (id >=
+`window_shared_max`; svdf_wseq.cpp, svdf_wunit.cpp, svdf_k_wunit.hip: k_wunit_apply_shared).  A shared user row (id >=
 amd:shared_user_from: a plain shared entry or a feature_user child) with more than window_shared_sub slots in a window is applied in file
 order, that many slots at a time, every sub-step's changes formed against the row as the previous sub-step left it; everything else moves as
 in the plain window step.  Every view must equal the checker of tests/window_sim.py -- the pinned C port driven one slot at a time --
@@ -9,6 +9,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import CSRData
 
@@ -199,31 +200,12 @@ def test_knob_at_zero_is_the_knob_unset():
         t.synchronize()
         got.append((ds.kind, ds.num_batches, {name: t.view(name).copy() for name in VIEWS}))
     uid = d.feat_index[d.row_ptr[1:-1:3] + 1].astype(np.int64)
-    W0 = int(np.ceil(_met(np.bincount(uid - 300, minlength=4), 12 / 128) / 12))   # about 1 500 updates per shared row at 12 per window
+    W0 = int(np.ceil(wr.met(np.bincount(uid - 300, minlength=4), 12 / 128) / 12))   # about 1 500 updates per shared row at 12 per window
     assert got[0][:2] == got[1][:2] == got[2][:2] == (8, W0)
     for other in got[1:3]:
         for name in VIEWS:
             assert np.array_equal(got[0][2][name].view(np.uint32), other[2][name].view(np.uint32)), name
     assert got[3][1] < W0 and not np.array_equal(got[0][2]["W_user"][300:], got[3][2]["W_user"][300:])
-
-
-def _met(counts, per_max_ratio):
-    """svdf_wunit.cpp: mean_updates_met"""
-    c = np.asarray(counts, np.float64)
-    return max(float((c ** 2).sum() / c.sum()), float(c.max()) * per_max_ratio)
-
-
-def _rule(n, shared, items, globs, sub, cap, per_shared=12, per=24, per_max=128):
-    """the window count of wseq_from_csr with window_shared_sub > 0: the item rows and global biases keep their terms; the
-    shared user rows ask for the fewest windows with mean_j min(c_j / W, sub) <= window_per_target_shared (the mean over entries) and
-    max_j c_j / W <= window_shared_max"""
-    w_other = max(1, int(np.ceil(max(_met(items, per / per_max), _met(globs, per / per_max)) / per)))
-    c = np.asarray(shared, np.float64)
-    ok = lambda W: float((np.minimum(c / W, sub) * c).sum() / c.sum()) <= per_shared   # noqa: E731
-    W = max(1, int(-(-int(c.max()) // cap)))
-    while not ok(W):
-        W += 1
-    return max(w_other, W)
 
 
 def test_window_rule_with_sub_steps():
@@ -235,24 +217,24 @@ def test_window_rule_with_sub_steps():
     assert shared.sum() == items.sum() == globs.sum() == 20000
     t = _trainer(DEEP_CONF, extra=[("amd:step", "minibatch"), ("amd:shared_user_from", 300)])
     default = t.dataset_from_csr(d).num_batches
-    assert default == int(np.ceil(_met(shared, 12 / 128) / 12))
+    assert default == int(np.ceil(wr.met(shared, 12 / 128) / 12)) == wr.csr(20000, items, globs, shared)
     t.set_knob("window_per_target", 100000)   # (the global biases out of the way: 8 ids met by 2 500 rows each ask for 105 windows of their own)
     assert t.dataset_from_csr(d).num_batches == default
     for sub, cap in ((12, 256), (12, 64), (3, 1024), (8, 512)):
         t.set_knob("window_shared_sub", sub)
         t.set_knob("window_shared_max", cap)
         W = t.dataset_from_csr(d).num_batches
-        assert W == _rule(20000, shared, items, globs, sub, cap, per=100000), (sub, cap)
+        assert W == wr.csr(20000, items, globs, shared, shared_lane=(sub, cap), per_target=100000), (sub, cap)
         assert W < default
     # sub-steps larger than the class mean: the mean term binds (16 of 16 -> c / W <= 12 again)
     t.set_knob("window_shared_sub", 16)
     t.set_knob("window_shared_max", 512)
-    assert t.dataset_from_csr(d).num_batches == _rule(20000, shared, items, globs, 16, 512, per=100000) == default
+    assert t.dataset_from_csr(d).num_batches == wr.csr(20000, items, globs, shared, shared_lane=(16, 512), per_target=100000) == default
     t.set_knob("window_per_target", 24)
     t.set_knob("window_shared_sub", 12)
     t.set_knob("window_shared_max", 128)
     W = t.dataset_from_csr(d).num_batches
-    assert W == _rule(20000, shared, items, globs, 12, 128) and W < default
+    assert W == wr.csr(20000, items, globs, shared, shared_lane=(12, 128)) and W < default
 
 
 def test_train_dataset_refuses_a_knob_changed_since_the_build():

@@ -8,6 +8,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import CSRData
 
@@ -193,7 +194,7 @@ def test_default_window_rule_keeps_shared_rows_at_12_updates_per_window():
     conf = cases.conf_with(cases.BASICMF_CONF, num_user=304, num_item=200, num_global=8, num_factor=32, wd_global="0.001")
     d = _deep_rows(20000, 3)
     counts = np.bincount(d.feat_index[d.row_ptr[1:-1:3] + 1] - 300, minlength=4)
-    met = float((counts.astype(np.float64) ** 2).sum() / counts.sum())   # updates an entry's shared row meets per pass (svdf_wunit.cpp: mean_updates_met)
+    met = wr.met(counts, 0.0)   # updates an entry's shared row meets per pass: sum c^2 / sum c (the most updates of one row do not bind here)
     t = _trainer(conf, extra=[("amd:step", "minibatch"), ("amd:shared_user_from", 300)])
     assert t.dataset_from_csr(d).num_batches == int(np.ceil(met / 12))
     t.set_knob("window_per_target_shared", 24)

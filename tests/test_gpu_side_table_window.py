@@ -8,6 +8,7 @@ import pytest
 
 import cases
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
 from svdfeature_amd import CSRData
 
@@ -160,7 +161,7 @@ def test_default_window_rule_counts_children_at_3_updates_per_window(tmp_path):
     uid = d.feat_index[d.row_ptr[1:-1:3]].astype(np.int64)
     iid = d.feat_index[d.row_ptr[2:-1:3]].astype(np.int64)
     counts = np.concatenate([np.bincount(uid % 4, minlength=4), np.bincount(iid % 4, minlength=4)]).astype(np.float64)
-    met = float((counts ** 2).sum() / counts.sum())   # svdf_wunit.cpp: mean_updates_met over the child targets
+    met = wr.met(counts, 0.0)   # sum c^2 / sum c over the child targets (the most updates of one row do not bind here)
     t = _trainer(conf, extra=[("amd:step", "minibatch"), ("amd:shared_user_from", 300)])
     assert t.dataset_from_csr(d).num_batches == int(np.ceil(met / 3))
     t.set_knob("window_per_target_shared", 1)   # the shared user rows' knob does not move child rows

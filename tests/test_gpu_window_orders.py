@@ -1,4 +1,4 @@
-"""The one-GPU window sequence (`amd:step = minibatch / auto`) on clustered file orders (tests/window_order_cases.py; svdf_wunit.cpp:
+"""The one-GPU window sequence (`amd:step = minibatch / auto`) on clustered file orders (tests/window_order_cases.py; svdf_wseq_rule.h:
 wseq_actual_columns / wseq_actual_csr; knob `window_count_actual`).  The window rule is evaluated on the windows as they
 are cut, so that what include/svdfeature_amd.h states about a window -- the mean over entries of min(count, sub) at the class's per-target value,
 no row more than the class's cap, both times the slack 1.5 -- holds on a file sorted by item, one that arrives in bursts, one sorted by a shared
@@ -20,8 +20,9 @@ import cases
 import pair_hot_cases as ph
 import window_order_cases as woc
 import svdfeature_amd as sa
+import window_rule as wr
 import window_sim as ws
-from test_window_orders import CONTRACT, HOT_MAX, HOT_SUB, K, N, NI, NU, PARENT_W, PER, PER_MAX, SEED, SLACK, actual_rule, per_pass_rule
+from test_window_orders import CONTRACT, HOT_MAX, HOT_SUB, K, N, NI, NU, PARENT_W, PER, PER_MAX, SEED, SLACK
 
 pytestmark = pytest.mark.gpu
 
@@ -81,7 +82,7 @@ def test_a_triples_windows_keep_the_documented_bounds(order, sub):
     W = ds.num_batches
     assert ds.kind == 8
     _bounds(i, ANI, W, sub, HOT_MAX if sub else PER_MAX)
-    W0 = per_pass_rule(np.bincount(i.astype(np.int64), minlength=ANI), sub, HOT_MAX if sub else PER_MAX)
+    W0 = wr.columns(AN, np.bincount(i.astype(np.int64), minlength=ANI), (sub, HOT_MAX))   # (sub 0: no lane)
     assert W == W0 if order in ("shuffled", "user") else W > 5 * W0, (order, W, W0)
 
 
@@ -319,7 +320,7 @@ def test_f_knob_zero_is_the_per_pass_rule(order):
         t = _trainer(_conf(NU, NI, K), MB, [("window_hot_sub", sub), ("window_count_actual", 0)])
         assert t.dataset_from_triples(u, i, r).num_batches == PARENT_W     # build only: this configuration is never trained
         t.set_knob("window_count_actual", 1)
-        assert t.dataset_from_triples(u, i, r).num_batches == actual_rule(PARENT_W, [i], NI, sub, HOT_MAX if sub else PER_MAX)
+        assert t.dataset_from_triples(u, i, r).num_batches == wr.as_cut(PARENT_W, [i], NI, sub, HOT_MAX if sub else PER_MAX)
     with pytest.raises(sa.SvdfError, match="window_count_actual must be 0 or 1"):
         t.set_knob("window_count_actual", 2)
 

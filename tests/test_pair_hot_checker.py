@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pair_hot_cases as ph
+import window_rule as wr
 
 # (k, active_type, reg_method, extra keys, sub-step)
 CASES = [
@@ -58,21 +59,26 @@ def test_sub_steps_differ_from_the_plain_window_step(plain, k, active, reg, extr
     assert not np.array_equal(a.view("W_user"), b.view("W_user"))
 
 
+def _pair_windows(counts, s=0, cap=0):
+    """the window count of a pass of pairs whose items hold `counts` slots (both entries of a pair counted); s = 0: without the lane"""
+    return wr.columns(sum(counts) // 2, counts, (s, cap))
+
+
 def test_window_rule_on_hand_computed_cases():
     # every term below the bound at one window: min(c / 1, 5) = 5 for all three items, mean 5 <= 24
-    assert ph.rule([100, 10, 10], 5, 2048) == 1
+    assert _pair_windows([100, 10, 10], 5, 2048) == 1
     # the cap alone: ceil(5000 / 2048) = 3, and min(c / 3, 5) <= 5
-    assert ph.rule([5000, 10], 5, 2048) == 3
-    assert ph.rule([5000, 10], 5, 100) == 50
+    assert _pair_windows([5000, 10], 5, 2048) == 3
+    assert _pair_windows([5000, 10], 5, 100) == 50
     # the mean binds: with s = 30 the hot item alone needs 5000 / W * 5000 + 100 / W <= 24 * 5010 = 120 240:
     #   W = 207: (24.1546 * 5000 + 0.483) / 5010 = 24.106 > 24;  W = 208: (24.0385 * 5000 + 0.481) / 5010 = 23.991 <= 24
-    assert ph.rule([5000, 10], 30, 2048) == 208
+    assert _pair_windows([5000, 10], 30, 2048) == 208
     # two equal items, s = 128: min(1000 / W, 128) <= 24 from W = 42 on (1000 / 41 = 24.39, 1000 / 42 = 23.81)
-    assert ph.rule([1000, 1000], 128, 2048) == 42
+    assert _pair_windows([1000, 1000], 128, 2048) == 42
     # items without a slot change nothing; an empty pass is one window
-    assert ph.rule([0, 1000, 0, 1000], 128, 2048) == 42
-    assert ph.rule([0, 0], 8, 2048) == 1
+    assert _pair_windows([0, 1000, 0, 1000], 128, 2048) == 42
+    assert _pair_windows([0, 0], 8, 2048) == 1
     # the default rule, for comparison: max(sum c^2 / sum c, max c * 24 / 128) / 24, rounded up
-    assert ph.default_rule([5000, 10]) == 208     # 4990.04 / 24 = 207.9
-    assert ph.default_rule([1000, 1000]) == 42    # 1000 / 24 = 41.7
-    assert ph.default_rule([4000] + [100] * 60) == 70   # sum c^2 / sum c = 1660, / 24 = 69.2; the max term 4000 * 0.1875 / 24 = 31.25 does not bind
+    assert _pair_windows([5000, 10]) == 208     # 4990.04 / 24 = 207.9
+    assert _pair_windows([1000, 1000]) == 42    # 1000 / 24 = 41.7
+    assert _pair_windows([4000] + [100] * 60) == 70   # sum c^2 / sum c = 1660, / 24 = 69.2; the max term 4000 * 0.1875 / 24 = 31.25 does not bind

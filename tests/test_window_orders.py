@@ -1,8 +1,8 @@
-"""The window rule on clustered file orders, on the CPU checkers alone (tests/window_order_cases.py; svdf_wunit.cpp: wseq_actual_columns; DESIGN.md
+"""The window rule on clustered file orders, on the CPU checkers alone (tests/window_order_cases.py; svdf_wseq_rule.h: wseq_actual_columns; DESIGN.md
 section 6r).  The per-pass rule takes a row's c updates as spread evenly over the W windows and cuts the file at equal positions; on a file sorted
 by item, or one that arrives in bursts, one window holds all of an item's ratings.  This test keeps the inputs of tests/test_gpu_window_orders.py
 honest: at the parent's window count the item and burst orders break the accuracy contract by at least 5x (so they bite), and at the count of the
-rule evaluated on the windows as cut every order keeps it.  The Python version of that rule lives here and nowhere else.
+rule evaluated on the windows as cut every order keeps it.  The Python version of that rule is tests/window_rule.py.
 
 Checkers: OracleTrainer.update_batch_stale plus the window's add (the window step without a lane), update_window_substeps (ordered sub-steps of
 window_hot_sub = 128); dRMSE on the held-out tenth against update_batch (the exact sequential pass) on the same file order.
@@ -13,40 +13,14 @@ import pytest
 
 import cases
 import window_order_cases as woc
+import window_rule as wr
 from svdfeature_amd import CSRData
 
 NU, NI, N, K, PASSES, SEED = 20000, 500, 200000, 16, 3, 22
 PER, PER_MAX, HOT_SUB, HOT_MAX = 24, 128, 128, 2048   # window_per_target, window_per_target_max, window_hot_sub, window_hot_max (include/svdfeature_amd.h)
-SLACK = 1.5                                          # svdf_wunit.cpp: kWseqSlack
+SLACK = wr.SLACK                                     # svdf_wseq_rule.h: kWseqSlack
 PARENT_W = 17                                        # the per-pass rule on these inputs, either lane, any order (tests/test_gpu_window_orders.py pins it on the engine with window_count_actual = 0)
 CONTRACT = 1e-4
-
-
-def per_pass_rule(counts, sub=0, cap=PER_MAX, per=PER):
-    """the window count from per-pass counts (svdf_wunit.cpp: mean_updates_met / wseq_windows without a lane, wseq_windows_shared with one)"""
-    c = np.asarray(counts, np.float64)
-    if sub == 0:
-        return max(1, int(np.ceil(max(float((c ** 2).sum() / c.sum()), float(c.max()) * per / cap) / per)))
-    met = lambda W: float((np.minimum(c / W, sub) * c).sum() / c.sum())   # noqa: E731
-    W = max(1, -(-int(c.max()) // cap))
-    while met(W) > per:
-        W += 1
-    return W
-
-
-def actual_rule(W, cols, num_id, sub=0, cap=PER_MAX, per=PER, slack=SLACK, rounds=40):
-    """the rule on the windows as cut (svdf_internal.h: wseq_windows_actual): more windows at equal positions until the mean over entries of
-    min(count of the entry's row in its window, sub) is within per * slack and the worst count within cap * slack"""
-    n = len(cols[0])
-    for _ in range(rounds):
-        worst, per_entry = woc.window_counts(list(cols), num_id, W)
-        num, den = max([(woc.mean_met(per_entry, sub), per * slack), (float(worst), cap * slack)], key=lambda f: f[0] / f[1])
-        if num <= den:
-            return W
-        W = max(W + 1, int(np.ceil(W * num / den)))
-        if W >= n:
-            return n
-    return n
 
 
 def _oracle():
@@ -94,7 +68,7 @@ def inputs():
 def test_the_per_pass_rule_gives_the_parents_count_on_every_order(inputs):
     for order in woc.ORDERS:
         counts = np.bincount(inputs[order][0][1].astype(np.int64), minlength=NI)
-        assert per_pass_rule(counts) == PARENT_W and per_pass_rule(counts, HOT_SUB, HOT_MAX) == PARENT_W, order
+        assert wr.columns(N, counts) == PARENT_W and wr.columns(N, counts, (HOT_SUB, HOT_MAX)) == PARENT_W, order
 
 
 @pytest.mark.parametrize("order", ["item", "burst"])
@@ -114,7 +88,7 @@ def test_the_parents_cut_breaks_the_contract_on_clustered_orders(inputs, order):
 def test_the_rule_on_the_windows_as_cut_keeps_the_contract(inputs, order, sub):
     train, held, exact = inputs[order]
     cap = HOT_MAX if sub else PER_MAX
-    W = actual_rule(PARENT_W, [train[1]], NI, sub, cap)
+    W = wr.as_cut(PARENT_W, [train[1]], NI, sub, cap)
     worst, per_entry = woc.window_counts(train[1], NI, W)
     assert worst <= cap * SLACK and woc.mean_met(per_entry, sub) <= PER * SLACK
     if order in ("shuffled", "user"):

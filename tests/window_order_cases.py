@@ -1,4 +1,4 @@
-"""(not collected by pytest) Inputs in clustered file orders for the window step (`amd:step = minibatch`; svdf_wunit.cpp: wseq_actual_columns /
+"""(not collected by pytest) Inputs in clustered file orders for the window step (`amd:step = minibatch`; svdf_wseq_rule.h: wseq_actual_columns /
 wseq_actual_csr).  The window rule sizes its windows from per-pass counts and cuts them at equal positions n w / W; on a
 file sorted by item, or one that arrives in bursts, a row's updates do not spread over the windows.  Every generator here returns one seeded
 draw in one of these orders:
@@ -9,11 +9,12 @@ draw in one of these orders:
   user       stable sort by user id -- the control: users are walked exactly, their order changes neither the window count nor the accuracy class
   shared     (rows with shared user ids only) stable sort by the shared user id: the same failure on the user side of wseq_from_csr
 
-and the helpers count what the windows as cut hold (what the tests assert the documented bounds on)."""
+and tests/window_rule.py's helpers count what the windows as cut hold (what the tests assert the documented bounds on)."""
 import numpy as np
 
 import cases
 from svdfeature_amd import CSRData
+from window_rule import mean_met, window_counts, window_cuts  # noqa: F401  (what the windows as cut hold: counted where the rule is stated)
 
 ORDERS = ("shuffled", "item", "burst", "user")
 ROW_ORDERS = ORDERS + ("shared",)
@@ -63,28 +64,3 @@ def shared_rows(n, num_private, num_shared, ni, seed, order):
     base = 3 * np.arange(n, dtype=np.int64)
     ptr[0:3 * n:3], ptr[1:3 * n:3], ptr[2:3 * n:3], ptr[3 * n] = base, base, base + 2, 3 * n
     return CSRData(r, ptr, idx, np.ones(3 * n, np.float32)), u, s, i
-
-
-def window_cuts(n, W):
-    """the windows of a sequence: equal positions [n w / W, n (w + 1) / W)"""
-    return [(n * w // W, n * (w + 1) // W) for w in range(W)]
-
-
-def window_counts(ids, num_id, W):
-    """(worst count of one id in one window, for every entry the count of its id in its window) -- ids: one array, or several columns of one
-    class (rank pairs: both items) with one entry per row each"""
-    cols = [np.asarray(c, np.int64) for c in (ids if isinstance(ids, (list, tuple)) else [ids])]
-    n = len(cols[0])
-    worst, per_entry = 0, []
-    for b0, b1 in window_cuts(n, W):
-        c = np.bincount(np.concatenate([col[b0:b1] for col in cols]), minlength=num_id)
-        worst = max(worst, int(c.max()) if b1 > b0 else 0)
-        for col in cols:
-            per_entry.append(c[col[b0:b1]])
-    return worst, np.concatenate(per_entry) if per_entry else np.zeros(0, np.int64)
-
-
-def mean_met(per_entry, sub):
-    """the mean over entries of min(count of the entry's row in its window, sub); sub = 0: of the count"""
-    c = np.asarray(per_entry, np.float64)
-    return float((np.minimum(c, sub) if sub > 0 else c).mean()) if c.size else 0.0

@@ -279,12 +279,12 @@ def step_blocks(o, blocks, B, *, sub=0, isub=0, user_bias=True, hot_over=None, i
 
 
 def row_cuts(n, W):
-    """the window sequence's cuts (svdf_wunit.cpp: wseq_from_csr): window w = rows [n w / W, n (w + 1) / W)"""
+    """the window sequence's cuts (svdf_wseq.cpp: wseq_from_csr): window w = rows [n w / W, n (w + 1) / W)"""
     return [(n * w // W, n * (w + 1) // W) for w in range(W)]
 
 
 def block_cuts(ba, W):
-    """the block sequence's cuts (svdf_wunit.cpp: wseq_from_blocks): even block positions moved forward to where no span is open"""
+    """the block sequence's cuts (svdf_wseq_rule.h: wseq_block_cuts): even block positions moved forward to where no span is open"""
     nb, tag = ba.num_block, ba.extend_tag
     cut = [0]
     for w in range(1, W):

@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--checks", default="3,10", help="passes after which the held-out RMSE is taken")
     ap.add_argument("--skip-allreduce", action="store_true")
     ap.add_argument("--zipf", type=float, default=0.0, help="> 0: items Zipf-distributed with this exponent (benchlib/orders.py: the skew of demo/basicMF/ua.base is ~0.7) instead of uniform")
-    ap.add_argument("--per-item-max", type=float, default=128.0, help="all-reduce step: the most updates ANY item may meet per window (svdf_wunit.cpp: window_per_target_max)")
+    ap.add_argument("--per-item-max", type=float, default=128.0, help="all-reduce step: the most updates ANY item may meet per window (svdf_wseq_rule.h: window_per_target_max)")
     ap.add_argument("--contrib", choices=["fp32", "bf16"], default="fp32", help="amd:contrib of the window-minibatch trainers")
     a = ap.parse_args()
     import torch

@@ -1,4 +1,4 @@
-"""Calibration of `window_per_target_max` (svdf_wunit.cpp): BASELINE configs[1] with Zipf(0.7) items (benchlib/orders.py), ratings through the exact
+"""Calibration of `window_per_target_max` (svdf_wseq_rule.h): BASELINE configs[1] with Zipf(0.7) items (benchlib/orders.py), ratings through the exact
 pass and through the window step with the hot item bounded at 32 ... 512 updates per window; held-out RMSE after 3 passes against the exact run's.
 python tools/zipf_window_calibration.py [ratings] [exponent]"""
 import sys
