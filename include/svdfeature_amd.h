@@ -198,7 +198,10 @@ int svdf_predict_dataset(svdf_trainer *t, svdf_dataset *ds, float *out);
  * fast path, 7 a digest of the host-resident schedule (level boundaries, fast-path split, unit order),
  * 8 a window sequence's (kind 8) kind of windows: 5 plain ratings / rank pairs, 7 user units; -1 for any other data set,
  * 9 operand staging of a runs data set (knob runs_stage): 0 not built yet, 1 built, 2 refused (size gate or no memory: rows stay in W),
- * 10 bytes of its staging buffers */
+ * 10 bytes of its staging buffers,
+ * 11 runs data sets, runs_wave_steps: the sum, over the aligned row sets a wave of the pass kernel carries (8 runs at k = 64, 4 at k = 128, from each
+ * level's begin), of the set's longest run = the steps the waves walk per pass; 12 runs_mixed_sets: the row sets whose runs differ in length;
+ * 13 the order inside a level the data set was built with (knob runs_order); 11 - 13 are -1 for any other data set */
 int64_t svdf_dataset_info(const svdf_dataset *ds, int what);
 
 /* ---- multi-GPU support: item-side parameters are replicated, each rank trains its
@@ -386,6 +389,10 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     runs_stage          1      a run writes every row into its next reader's schedule slot instead of W (W is written at the row's last touch of a
  *                                pass and is the truth between passes; same bits).  Costs (1 + R) * runs * (4 k + 8) bytes of device memory, taken
  *                                only when that is at most half of the free memory and at most runs_stage_max_mb (-1 = no cap); 0 = rows live in W
+ *     runs_order          1      order of the runs inside a level, honoured with sort_batches 1: 1 = by length, longest first, then by item, the level's
+ *                                row sets dealt round robin into the eight contiguous shares the XCDs take (a wave walks as many steps as its
+ *                                longest run; same bits); 0 = by item.  Read when a data set is BUILT: changing it later does not touch an existing
+ *                                data set (svdf_dataset_info 11 - 13).  Falls back to 0 when R * num_item does not fit 32 bits
  *     pivot_exec          1      hot rows walked as units (svdf_pivot.cpp); pivot_min 2048 (ratings that make a row hot), pivot_run 256 (per unit)
  *   schedule forms of rank pairs
  *     pair_units          1      user-grouped pair streams (the generator's own order: a user's pairs back to back) walked as user-run units

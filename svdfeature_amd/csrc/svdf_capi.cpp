@@ -271,6 +271,9 @@ int64_t svdf_dataset_info(const svdf_dataset *ds, int what) {
     case 8: return ds->d->kind == 8 && !ds->d->wchild.empty() ? (int64_t)ds->d->wchild[0]->kind : -1;
     case 9: return ds->d->rn_stage_state;   // runs data sets, operand staging: 0 not tried, 1 built, 2 refused (gate / no memory)
     case 10: return ds->d->rn_stage_bytes;  // ... bytes of the staging buffers
+    case 11: return ds->d->kind == 10 ? ds->d->rn_wave_steps : -1;   // runs data sets, runs_wave_steps: sum over the pass kernel's aligned row sets of the longest run
+    case 12: return ds->d->kind == 10 ? ds->d->rn_mixed_sets : -1;   // ... runs_mixed_sets: row sets whose runs differ in length
+    case 13: return ds->d->kind == 10 ? ds->d->rn_order : -1;        // ... the in-level order the data set was built with (knob runs_order)
     default: return -1;
     }
 }

@@ -252,6 +252,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "device_load")) { device_load_ = value != 0; return 0; }
     if (!strcmp(name, "runs_exec")) { check(value == 0 || value == 1, "runs_exec must be 0 or 1"); runs_exec_ = (int)value; return 0; }
     if (!strcmp(name, "runs_len")) { check(value >= 2 && value <= 7, "runs_len must be in 2 .. 7"); runs_len_ = (int)value; return 0; }
+    if (!strcmp(name, "runs_order")) { check(value == 0 || value == 1, "runs_order must be 0 (by item) or 1 (by run length, then item)"); runs_order_ = (int)value; return 0; }
     if (!strcmp(name, "runs_sets")) { check(value >= 1 && value <= 2, "runs_sets must be 1 or 2"); runs_sets_ = (int)value; return 0; }
     if (!strcmp(name, "runs_block")) { check(value == 64 || value == 128 || value == 256, "runs_block must be 64, 128 or 256"); runs_block_ = (int)value; return 0; }
     if (!strcmp(name, "runs_min_rows")) { check(value >= 0, "runs_min_rows must not be negative"); runs_min_rows_ = value; return 0; }

@@ -626,8 +626,8 @@ Dataset *Engine::auto_step(Dataset *exact, bool window_ok, const std::function<D
 std::string Engine::path_for(const Dataset *ds) const {
     const DevParams &P = const_cast<Engine *>(this)->params();
     const long L = (long)ds->sched.num_levels();
-    char buf[512];
-    auto levels = [&](const char *what) { snprintf(buf, sizeof(buf), "exact, %ld conflict-free levels: %s", L, what); return std::string(buf); };
+    char buf[768];
+    auto levels =[&](const char *what) { snprintf(buf, sizeof(buf), "exact, %ld conflict-free levels: %s", L, what); return std::string(buf); };
     switch (ds->kind) {
     case 0: return levels(chain_width_ > 0 ? "contract kernel k_basicmf / k_basicmf_slots, one (user, item) instance per lane group; narrow levels chained (k_basicmf_slots_chain)"
                                            : "contract kernel k_basicmf / k_basicmf_slots, one (user, item) instance per lane group");
@@ -654,7 +654,11 @@ std::string Engine::path_for(const Dataset *ds) const {
         char st[96] = "rows in W";
         if (runs_staged(ds)) snprintf(st, sizeof(st), "rows handed from run to run through staging slots (runs_stage, %.1f MB)", (double)ds->rn_stage_bytes / 1048576.0);
         else if (ds->rn_stage_state == 2) snprintf(st, sizeof(st), "rows in W (operand staging refused)");
-        snprintf(buf, sizeof(buf), "exact, %ld levels of runs: k_basicmf_runs_soa (up to %d consecutive ratings of one item per lane group, the item's row in registers); %s", L, ds->rn_len, st);
+        char hist[160] = "";
+        for (int c = 1, at = 0; c <= ds->rn_len && at < (int)sizeof(hist) - 24; c++) at += snprintf(hist + at, sizeof(hist) - (size_t)at, "%s%ld", c > 1 ? " / " : "", (long)ds->rn_hist[c]);
+        snprintf(buf, sizeof(buf), "exact, %ld levels of runs: k_basicmf_runs_soa (up to %d consecutive ratings of one item per lane group, the item's row in registers); %s; "
+                 "a level's runs by %s (runs_order %d): runs_wave_steps %ld, runs_mixed_sets %ld, runs of 1 .. %d ratings: %s", L, ds->rn_len, st,
+                 ds->rn_order ? "length, then item" : "item", ds->rn_order, (long)ds->rn_wave_steps, (long)ds->rn_mixed_sets, ds->rn_len, hist);
         return buf;
     }
     case 11: snprintf(buf, sizeof(buf), "exact, %ld levels of user-run units: k_pair_units (%ld units of up to %d consecutive pairs of one user, the user's row in registers)",

@@ -293,6 +293,11 @@ struct Dataset {
     DevBuf<unsigned> rn_item, rn_user[8];
     DevBuf<float> rn_label[8];
     int rn_len = 0;
+    // ... their order inside a level (knob "runs_order" when the data set was built): 1 = longest runs first, item order inside a length, 0 = item order.
+    // Counted in HBM once per data set over the aligned row sets a wave of the pass kernel carries (svdf_dataset_info 11 / 12): the sum of every set's
+    // longest run = the steps the waves walk, the sets whose runs differ in length; rn_hist[length] = runs of that length
+    int rn_order = 0;
+    int64_t rn_wave_steps = 0, rn_mixed_sets = 0, rn_hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // ... and their operand staging (knob "runs_stage"; svdf_runs.cpp: runs_stage_build): slot j * num_units + s; rn_first[r] = the slot of row r's first touch
     DevBuf<float> rn_stage_row, rn_stage_bias;
     DevBuf<unsigned> rn_dst, rn_first;
@@ -772,7 +777,9 @@ class Engine {
     int runs_len_ = 4;                    // knob "runs_len": ratings per run at most (2 .. 7)
     int runs_sets_ = 1, runs_block_ = 64; // knobs "runs_sets" / "runs_block": row sets per wave, threads per workgroup of k_basicmf_runs_soa
     long runs_min_rows_ = 1 << 20;        // knob "runs_min_rows": smaller data sets keep the plain schedule (levels too narrow for runs to matter)
+    int runs_order_ = 1;                  // knob "runs_order": a level's runs sorted by 1 = (length, longest first; item), 0 = item; read when a data set is built, with sort_batches = 1
     int64_t n_runs_passes_ = 0;
+    void runs_order_stats(Dataset *ds);
     bool runs_config_ok() const;
     Dataset *runs_dataset_from_triples(long n, const unsigned *user, const unsigned *item, const float *label);
     void runs_train(Dataset *ds);

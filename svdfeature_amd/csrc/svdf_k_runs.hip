@@ -106,6 +106,98 @@ void launch_runs_fill_u32(unsigned *v, long n, unsigned x, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_runs_fill_u32, dim3(runs_grid(n)), dim3(256), 0, st, v, n, x);
 }
 
+// ------------------------------------------------------------------------------------------------- order inside a level (knob "runs_order")
+// A wave carries 64 / LANES runs and walks as many steps -- and gather rounds -- as its longest one, so a level's runs are sorted by length, longest first,
+// item order inside a length: the units of a level commute, and the in-level order is a free sort key of the scheduler (profiles/r28_runs_order.md).
+// A run's ratings fill its user slots from 0 without holes: its length is its last present slot + 1.
+__device__ __forceinline__ int runs_length(const RunSchedule &S, size_t at, int R) {
+    int len = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        if (j < R && S.user[j][at] != (unsigned)SLOT_ABSENT) len = j + 1;
+    return len;
+}
+__global__ __launch_bounds__(256) void k_runs_order_key(const unsigned *c_item, const unsigned *c_user, long nunit, int R, unsigned num_item, unsigned *key) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long un = (long)blockIdx.x * blockDim.x + threadIdx.x; un < nunit; un += stride) {
+        int len = 0;
+        for (int j = 0; j < R; j++)
+            if (c_user[(size_t)j * (size_t)nunit + (size_t)un] != (unsigned)SLOT_ABSENT) len = j + 1;
+        key[un] = (unsigned)(R - len) * num_item + c_item[un];
+    }
+}
+// With xcd_remap the pass kernel gives each of the 8 XCDs one contiguous eighth of a level, and a level sorted by length alone leaves the long runs to the
+// first XCDs (measured: +9 % per pass).  So the level's full row sets are dealt round robin into 8 contiguous shares: share x = the sets x, x + 8, ... of
+// the sorted order, each share sorted by length again.  Sets stay whole and aligned to the level's begin; the last, partial set stays last.
+__global__ __launch_bounds__(256) void k_runs_order_deal(const int *order, int *out, const long *level_ptr, int nlev, long nunit, int ips) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < nunit; s += stride) {
+        int lo = 0, hi = nlev - 1;   // the last level that begins at or before s
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (level_ptr[mid] <= s) lo = mid; else hi = mid - 1; }
+        const long begin = level_ptr[lo], nf = (level_ptr[lo + 1] - begin) / ips, p = s - begin;
+        long to = s;
+        if (p < nf * ips) {
+            const long q = p / ips;
+            const int x = (int)(q & 7);
+            long base = 0;
+            for (int y = 0; y < x; y++) base += (nf - y + 7) / 8;   // the sets q' < nf with q' % 8 == y
+            to = begin + (base + (q >> 3)) * ips + p % ips;
+        }
+        out[to] = order[s];
+    }
+}
+void launch_runs_order_deal(const int *order, int *out, const long *level_ptr, int nlev, long nunit, int ips, hipStream_t st) {
+    if (nunit > 0 && nlev > 0) hipLaunchKernelGGL(k_runs_order_deal, dim3(runs_grid(nunit)), dim3(256), 0, st, order, out, level_ptr, nlev, nunit, ips);
+}
+// Over the level-sorted columns, once per data set.  The aligned sets of `ips` runs from each level's begin are the rows one wave of k_basicmf_runs_soa
+// carries: tot[0] += the set's longest run (the steps that wave walks), tot[1] += 1 for a set whose runs differ in length; tot[1 + length] += the runs of
+// that length.
+__global__ __launch_bounds__(256) void k_runs_order_stats(const RunSchedule S, const long *level_ptr, int nlev, long nunit, int R, int ips, unsigned long long *tot) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    unsigned long long steps = 0ull, mixed = 0ull, cnt[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) cnt[c] = 0ull;
+    for (long base = (long)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < nunit; base += stride) {   // a wave-uniform bound: ballots below
+        const long s = base + lane;
+        const bool on = s < nunit;
+        int len = 0;
+        if (on) {
+            int lo = 0, hi = nlev - 1;   // the last level that begins at or before s
+            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (level_ptr[mid] <= s) lo = mid; else hi = mid - 1; }
+            len = runs_length(S, (size_t)s, R);
+            const long begin = level_ptr[lo], end = level_ptr[lo + 1];
+            if ((s - begin) % ips == 0) {
+                int mx = len;
+                bool mix = false;
+                for (int t = 1; t < ips && s + t < end; t++) {
+                    const int l2 = runs_length(S, (size_t)(s + t), R);
+                    mix = mix || l2 != len;
+                    mx = l2 > mx ? l2 : mx;
+                }
+                steps += (unsigned long long)mx;
+                mixed += mix ? 1ull : 0ull;
+            }
+        }
+#pragma unroll
+        for (int c = 1; c < 8; c++) cnt[c] += (unsigned long long)__popcll(__ballot(on && len == c));   // the same sums in every lane
+    }
+    for (int o = 32; o > 0; o >>= 1) { steps += __shfl_xor(steps, o); mixed += __shfl_xor(mixed, o); }
+    if (lane == 0) {
+        if (steps) atomicAdd(tot, steps);
+        if (mixed) atomicAdd(tot + 1, mixed);
+#pragma unroll
+        for (int c = 1; c < 8; c++)
+            if (cnt[c]) atomicAdd(tot + 1 + c, cnt[c]);
+    }
+}
+void launch_runs_order_key(const unsigned *c_item, const unsigned *c_user, long nunit, int R, unsigned num_item, unsigned *key, hipStream_t st) {
+    if (nunit > 0) hipLaunchKernelGGL(k_runs_order_key, dim3(runs_grid(nunit)), dim3(256), 0, st, c_item, c_user, nunit, R, num_item, key);
+}
+void launch_runs_order_stats(const RunSchedule &S, const long *level_ptr, int nlev, long nunit, int R, int ips, unsigned long long *tot, hipStream_t st) {
+    if (nunit > 0 && nlev > 0) hipLaunchKernelGGL(k_runs_order_stats, dim3(runs_grid(nunit)), dim3(256), 0, st, S, level_ptr, nlev, nunit, R, ips, tot);
+}
+
 // ------------------------------------------------------------------------------------------------- operand staging (knob "runs_stage")
 // Every row is read and written at every touch anyway, so the write can go where the row's NEXT reader will look: slot j * nunit + s of the
 // staging buffers, s = the reader's position in level order, j = 0 its item row, 1 .. R its users' rows.  The links are a file-order fact too: runs

@@ -146,6 +146,12 @@ void launch_runs_fill_u32(unsigned *v, long n, unsigned x, hipStream_t st);
 void launch_runs_stage_links(const RunSchedule &S, const int *order, long nunit, int R, unsigned num_user, unsigned row0, unsigned *pos_of, unsigned *ka, unsigned *kb,
                              unsigned *va, unsigned *vb, void **tmp, size_t *tmp_bytes, unsigned *dst, unsigned *first, long nrow, hipStream_t st);
 void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, hipStream_t st);
+// in-level order of the runs (knob "runs_order"): key[un] = (R - length) * num_item + item over the columns in unit-number order; over the level-sorted
+// columns S: tot[0] = sum over the aligned sets of `ips` runs (from each level's begin) of the set's longest run, tot[1] = sets whose runs differ in length,
+// tot[1 + length] = runs of that length
+void launch_runs_order_key(const unsigned *c_item, const unsigned *c_user, long nunit, int R, unsigned num_item, unsigned *key, hipStream_t st);
+void launch_runs_order_deal(const int *order, int *out, const long *level_ptr, int nlev, long nunit, int ips, hipStream_t st);
+void launch_runs_order_stats(const RunSchedule &S, const long *level_ptr, int nlev, long nunit, int R, int ips, unsigned long long *tot, hipStream_t st);
 bool basicmf_runs_soa_applies(const DevParams &P);
 void launch_basicmf_runs_soa(const DevParams &P, const RunSchedule &S, long begin, long end, int R, int G, int block_threads, hipStream_t st);
 void device_sort_pairs_u32(unsigned *keys_in, unsigned *keys_out, unsigned *vals_in, unsigned *vals_out, long n, void **tmp, size_t *tmp_bytes, hipStream_t st);

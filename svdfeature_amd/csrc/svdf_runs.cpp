@@ -18,6 +18,35 @@ bool Engine::runs_config_ok() const {
            basic_i8_ != 0 && store_mode_ == 0;
 }
 
+// The in-level sort key (R - length) * NI + item takes values up to R * NI - 1, and the scheduler's key column holds 32 bits
+static constexpr bool runs_order_key_fits(int R, unsigned NI) { return (uint64_t)R * (uint64_t)NI <= 0xFFFFFFFFull; }
+static_assert(runs_order_key_fits(7, 1u << 27) && runs_order_key_fits(7, 613566756u) && !runs_order_key_fits(7, 613566757u), "R = 7: 7 * NI up to 2^32 - 1");
+static_assert(runs_order_key_fits(4, (1u << 30) - 1u) && !runs_order_key_fits(4, 1u << 30), "R = 4: NI below 2^30");
+static_assert(runs_order_key_fits(2, (1u << 31) - 1u) && !runs_order_key_fits(2, 1u << 31), "R = 2: NI below 2^31");
+
+// What the order costs the pass, counted once over the level-sorted columns for either order (svdf_dataset_info 11 / 12; SVDF_VERBOSE)
+void Engine::runs_order_stats(Dataset *ds) {
+    const long nunit = ds->num_units;
+    const size_t nlev = ds->sched.num_levels();
+    if (nunit <= 0 || nlev == 0 || nlev >= 0x7FFFFFFFul) return;
+    DevBuf<long> lp;
+    DevBuf<unsigned long long> tot;
+    lp.upload(ds->sched.level_ptr.data(), nlev + 1, stream_);
+    tot.reserve(9);
+    HIPCHECK(hipMemsetAsync(tot.p, 0, 9 * sizeof(unsigned long long), stream_));
+    RunSchedule S;
+    memset(&S, 0, sizeof(S));
+    for (int j = 0; j < ds->rn_len; j++) S.user[j] = ds->rn_user[j].p;
+    launch_runs_order_stats(S, lp.p, (int)nlev, nunit, ds->rn_len, mp_.num_factor == 128 ? 4 : 8, tot.p, stream_);
+    HIPCHECK(hipGetLastError());
+    unsigned long long h[9];
+    HIPCHECK(hipMemcpyAsync(h, tot.p, sizeof(h), hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));
+    ds->rn_wave_steps = (int64_t)h[0];
+    ds->rn_mixed_sets = (int64_t)h[1];
+    for (int c = 1; c < 8; c++) ds->rn_hist[c] = (int64_t)h[1 + c];
+}
+
 // nullptr: the configuration has no runs kernel: the caller builds the plain level schedule
 Dataset *Engine::runs_dataset_from_triples(long n, const unsigned *user, const unsigned *item, const float *label) {
     if (!runs_config_ok() || n < runs_min_rows_ || n >= 0x7FFFFFF0L) return nullptr;
@@ -81,8 +110,41 @@ Dataset *Engine::runs_dataset_from_triples(long n, const unsigned *user, const u
         du.push_back(DUCol{c_user.p + (size_t)j * (size_t)nunit, &ds->rn_user[j]});
         df.push_back(DFCol{c_label.p + (size_t)j * (size_t)nunit, &ds->rn_label[j]});
     }
-    schedule_device_columns(ds.get(), nunit, 1 + R, res, off, limit, msg, sort_batches_ == 1 ? c_item.p : nullptr, NI, du, df);
+    // the order inside a level (knob "runs_order", with sort_batches = 1): by (R - length) * NI + item, or by item.  The key's largest value R * NI - 1 has
+    // to fit the scheduler's 32-bit key column (it widens the sort to 64 bits by itself when level bits + key bits need it); beyond that: item order
+    const unsigned *sort_key = sort_batches_ == 1 ? c_item.p : nullptr;
+    unsigned sort_max = NI;
+    DevBuf<unsigned> c_key;
+    if (sort_batches_ == 1 && runs_order_ == 1 && runs_order_key_fits(R, NI)) {
+        c_key.reserve((size_t)nunit);
+        launch_runs_order_key(c_item.p, c_user.p, nunit, R, NI, c_key.p, stream_);
+        HIPCHECK(hipGetLastError());
+        sort_key = c_key.p; sort_max = (unsigned)R * NI;
+        ds->rn_order = 1;
+    }
+    if (ds->rn_order == 1) {
+        // the sorted order without the columns, a level's row sets dealt into the XCDs' eight shares (k_runs_order_deal), then the columns in that order
+        schedule_device_columns(ds.get(), nunit, 1 + R, res, off, limit, msg, sort_key, sort_max, {}, {});
+        const size_t nlev = ds->sched.num_levels();
+        if (nlev > 0 && nlev < 0x7FFFFFFFul) {
+            DevBuf<long> lp;
+            DevBuf<int> dealt;
+            lp.upload(ds->sched.level_ptr.data(), nlev + 1, stream_);
+            dealt.reserve((size_t)nunit);
+            launch_runs_order_deal(ds->order_dev.p, dealt.p, lp.p, (int)nlev, nunit, mp_.num_factor == 128 ? 4 : 8, stream_);
+            HIPCHECK(hipMemcpyAsync(ds->order_dev.p, dealt.p, (size_t)nunit * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipStreamSynchronize(stream_));
+        }
+        for (const DUCol &c : du) { c.dst->reserve((size_t)nunit); device_gather_u32(c.src, ds->order_dev.p, c.dst->p, nunit, stream_); }
+        for (const DFCol &c : df) { c.dst->reserve((size_t)nunit); device_gather_f32(c.src, ds->order_dev.p, c.dst->p, nunit, stream_); }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(stream_));
+    } else {
+        schedule_device_columns(ds.get(), nunit, 1 + R, res, off, limit, msg, sort_key, sort_max, du, df);
+    }
     ds->num_units = nunit;
+    runs_order_stats(ds.get());
     ds->algorithmic_bytes = n * (8L * mp_.num_factor * 2 + 8 * 2 + 16 + 8 * 2);
     if (runs_stage_) runs_stage_build(ds.get());
     return ds.release();
