@@ -363,7 +363,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 36 hot item rows applied in ordered sub-steps on user-group (SVD++) windows, with or without shared user entries (knob window_block_item_sub;
  * DESIGN.md 6u; the windows keep counting where they do without the knob),
  * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too),
- * 38 sections ranked by svdf_rank_eval_positions, 39 sections listed by svdf_rank_topn */
+ * 38 sections ranked by svdf_rank_eval_positions, 39 sections listed by svdf_rank_topn,
+ * 40 of the sections under 38 / 39, those ranked with a user row built from a feedback list (the _fb calls on user-group trainers) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -609,6 +610,50 @@ int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, cons
  * first, then pieces of whole sections; the result does not depend on the knob.  Counter 39 counts the sections listed. */
 int svdf_rank_topn(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
                    int *item_out, float *score_out, int *count_out, int *nan_out);
+
+/* ---- the two calls above for USER-GROUP (format_type = 1, SVD++) trainers: sections with feedback lists.  Each _fb
+ * entry point is its twin plus three arguments behind `user`: section s carries the feedback list fb_index / fb_value[fb_ptr[s] ..
+ * fb_ptr[s + 1]) of (id, value) pairs, in the order in which the reference's ranker would add them.  The score of candidate i is the
+ * ranker's for one block holding that list, a USER line user[s]:1 and ITEM lines i:1 (apex_svd_base.h:719-735, 798-808):
+ *   tmp_ufeedback = 0;  for j in list order:  tmp_ufeedback += W_ufeedback[fb_index[j]] * fb_value[j]
+ *   tmp_ufactor   = tmp_ufeedback;            tmp_ufactor   += W_user[user[s]] * 1
+ *   score(i)      = 0 + (i_bias[i] + <tmp_ufactor, W_item[i]>)                     -- the dot product in the order given above
+ * every multiply and add rounded separately to fp32 (no FMA), a value within 1e-6 of 1 multiplying as exactly 1 (the reference's
+ * scalar_map): bit for bit what svdf_ranker_process_block computes from the saved model.  A list's sum is a serial chain per element in
+ * list order; it is never split or reassociated, so a long list costs its length.  Everything else is the twin's, unchanged:
+ * positives, bans, ties by id, +-0, count, top_n <= 256, pieces, outputs, and "validated on the host before any device work, and before
+ * `needs a GPU`".
+ * Accepted: format_type = 1 trainers with extend_type 0 or 1 (both are SVDPPFeature with one model).  LEGAL: an empty list (the row is
+ * 0 + W_user[u] * 1); an id repeated inside a list (added twice, in order); any float value; a user in several sections with different
+ * lists.  A NaN that reaches a row through a value (or through W_ufeedback) flags the section like any NaN score.  A NaN VALUE is the
+ * one input on which the call leaves the ranker: the reference's scalar_map takes a NaN scalar for 1 (its |s - 1| > 1e-6 test is false) and
+ * adds the row unscaled; here the NaN reaches every element of the section's row and flags the section.
+ * REFUSED on the host, behind the prefixes "rank_eval:" / "rank_topn:" (the ranker's message bare):
+ *   a feedback id >= num_ufeedback                     "ufeedback id exceed bound"
+ *   fb_ptr that starts below 0 / decreases             "fb_ptr must start at >= 0" / "fb_ptr must not decrease"
+ *   entries without fb_index or fb_value               "fb_index / fb_value is missing"
+ *   fb_ptr == NULL on a user-group trainer             "fb_ptr is NULL on a user-group trainer; a section without feedback must be given
+ *                                                      explicitly as an empty list ..." -- the reference's ranker scores such a section
+ *                                                      with a clone of W_user[0] left over from init_ranker (:680-682), an accident the
+ *                                                      batch call does not reproduce
+ *   fb_ptr != NULL on a format_type = 0 trainer        "feedback lists need a user-group trainer"
+ *   extend_type 2 / 15, feature_user / feature_item side tables, common_latent_space != 0, amd:gpus > 1, rank handles: as the twins do,
+ *   in the same words.
+ * On a format_type = 0 trainer a _fb call with fb_ptr == NULL IS the twin.  The twins themselves are unchanged: they refuse user-group
+ * trainers as before.
+ * Per piece the lists ride in the piece's one upload and one more kernel launch (k_rank_live_rows) builds the sections' rows into a
+ * workspace of sections x pitch floats, which the sweeps read instead of W_user rows.  Feedback entries count towards `rank_eval_budget`
+ * in the evaluation call; the top-N call also ends a piece whose feedback entries would exceed that knob.  No result depends on a knob.
+ * Counter 40 counts the sections ranked with a row built from a feedback list: of the sections counters 38 / 39 count (which count as
+ * before), those of _fb calls on user-group trainers. */
+int svdf_rank_eval_positions_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index,
+                                const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
+                                const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out);
+int svdf_rank_eval_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                      const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_at, const int *at,
+                      svdf_rank_metrics *out);
+int svdf_rank_topn_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                      const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

@@ -245,6 +245,10 @@ def load_library():
     lib.svdf_rank_eval_metrics.argtypes = [C.c_long, _i64p, _i32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_eval.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_topn.argtypes = [P, C.c_long, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    _fb = [C.c_void_p, C.c_void_p, C.c_void_p]   # fb_ptr, fb_index, fb_value behind `user`
+    lib.svdf_rank_eval_positions_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
+    lib.svdf_rank_eval_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_rank_topn_fb.argtypes = [P, C.c_long, _u32p] + _fb + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -716,27 +720,55 @@ class Trainer:
                 raise SvdfError("rank_eval: ban_ptr must have one entry more than users")
         return users, pos_ptr, _pad(pos_item, np.uint32), ban_ptr, (ban_item if ban_ptr is not None else None)
 
-    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None):
-        """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section."""
+    @staticmethod
+    def _feedback_lists(who, feedback, S):
+        """feedback = (fb_ptr, fb_index, fb_value), section s carrying the entries [fb_ptr[s], fb_ptr[s + 1]) -> the three pointer arguments of the
+        svdf_rank_*_fb calls (the arrays are kept alive by the returned tuple); fb_ptr = None passes NULL pointers"""
+        fb_ptr, fb_index, fb_value = feedback
+        if fb_ptr is None:
+            return (None, None, None), ()
+        keep = (_pad(fb_ptr, np.int64), _pad(fb_index if fb_index is not None else [], np.uint32), _pad(fb_value if fb_value is not None else [], np.float32))
+        if len(keep[0]) != S + 1:
+            raise SvdfError(who + ": fb_ptr must have one entry more than users")
+        n = int(keep[0][-1]) if S else 0
+        if n > 0 and (len(keep[1]) < n or len(keep[2]) < n):
+            raise SvdfError(who + ": fb_index / fb_value are shorter than fb_ptr says")
+        return tuple(_opt_ptr(a) for a in keep), keep
+
+    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None):
+        """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section.  feedback = (fb_ptr, fb_index, fb_value): the
+        sections' feedback lists, for user-group trainers (svdf_rank_eval_positions_fb)."""
         users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
         S, n = len(users), int(pos_ptr[-1]) if len(users) else 0
         position, tied = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         ranked, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
-        self._ok(self.lib.svdf_rank_eval_positions(self.h, S, _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
-                                                   position, tied, ranked, nan))
+        if feedback is None:
+            self._ok(self.lib.svdf_rank_eval_positions(self.h, S, _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
+                                                       position, tied, ranked, nan))
+        else:
+            fb, keep = self._feedback_lists("rank_eval", feedback, S)
+            self._ok(self.lib.svdf_rank_eval_positions_fb(self.h, S, _pad(users, np.uint32), fb[0], fb[1], fb[2], pos_ptr, pos_item, _opt_ptr(ban_ptr),
+                                                          _opt_ptr(ban_item), position, tied, ranked, nan))
         return position[:n], tied[:n], ranked[:S], nan[:S]
 
-    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100)):
-        """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict)."""
+    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None):
+        """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict).
+        feedback: as in rank_positions (svdf_rank_eval_fb)."""
         users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
         m = RankMetrics()
-        self._ok(self.lib.svdf_rank_eval(self.h, len(users), _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
-                                         len(at), _pad(list(at), np.int32), C.byref(m)))
+        if feedback is None:
+            self._ok(self.lib.svdf_rank_eval(self.h, len(users), _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
+                                             len(at), _pad(list(at), np.int32), C.byref(m)))
+        else:
+            fb, keep = self._feedback_lists("rank_eval", feedback, len(users))
+            self._ok(self.lib.svdf_rank_eval_fb(self.h, len(users), _pad(users, np.uint32), fb[0], fb[1], fb[2], pos_ptr, pos_item, _opt_ptr(ban_ptr),
+                                                _opt_ptr(ban_item), len(at), _pad(list(at), np.int32), C.byref(m)))
         return m.as_dict()
 
-    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None):
+    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None, feedback=None):
         """svdf_rank_topn: the top_n best items per section among all items that are not banned, higher score first and equal
-        scores by ascending id; (items [S, top_n] int32, -1 beyond count; scores [S, top_n] float32; count [S]; nan [S])."""
+        scores by ascending id; (items [S, top_n] int32, -1 beyond count; scores [S, top_n] float32; count [S]; nan [S]).  feedback = (fb_ptr,
+        fb_index, fb_value): the sections' feedback lists, for user-group trainers (svdf_rank_topn_fb)."""
         users, top_n = np.ascontiguousarray(users, np.uint32), int(top_n)
         S = len(users)
         if ban_ptr is not None:
@@ -748,8 +780,13 @@ class Trainer:
         n = max(top_n, 1)
         items, scores = np.full((max(S, 1), n), -1, np.int32), np.zeros((max(S, 1), n), np.float32)
         count, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
-        self._ok(self.lib.svdf_rank_topn(self.h, S, _pad(users, np.uint32), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, items.reshape(-1),
-                                         scores.ctypes.data_as(C.c_void_p), count, nan))
+        if feedback is None:
+            self._ok(self.lib.svdf_rank_topn(self.h, S, _pad(users, np.uint32), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, items.reshape(-1),
+                                             scores.ctypes.data_as(C.c_void_p), count, nan))
+        else:
+            fb, keep = self._feedback_lists("rank_topn", feedback, S)
+            self._ok(self.lib.svdf_rank_topn_fb(self.h, S, _pad(users, np.uint32), fb[0], fb[1], fb[2], _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n,
+                                                items.reshape(-1), scores.ctypes.data_as(C.c_void_p), count, nan))
         return items[:S], scores[:S], count[:S], nan[:S]
 
     # -- multi-GPU item-side delta

@@ -220,6 +220,7 @@ int64_t Engine::counter(int what) const {
     case 37: return n_rank_window_passes_;   // rank passes of a candidate file built as device window sequences (amd:step = minibatch / auto, section 6v); they count under 7 too
     case 38: return n_rank_eval_sections_;   // sections (with positives) ranked by svdf_rank_eval_positions' sweep (section 6w)
     case 39: return n_rank_topn_sections_;   // sections listed by svdf_rank_topn (section 6x)
+    case 40: return n_rank_fb_sections_;     // of those two, the sections ranked with a row built from a feedback list (section 6y)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

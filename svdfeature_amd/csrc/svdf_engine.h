@@ -463,7 +463,19 @@ class Engine {
     // top-N item lists on the live model (svdf_ranktopn.cpp, svdf_k_ranktopn.hip)
     void rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                    int *count_out, int *nan_out);
-    void rank_live_refusals(const char *who);   // the configurations neither batch ranking call covers
+    void rank_live_refusals(const char *who, bool svdpp_ok = false);   // the configurations neither batch ranking call covers
+    // the same calls for sections with feedback lists: user-group (SVD++) trainers (svdf_k_rankrows.hip)
+    void rank_eval_positions_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
+                                int *nan_out);
+    void rank_topn_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+                      const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+    bool rank_live_fb_refusals(const char *who, bool has_lists);
+    void rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                       const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
+                       int *nan_out);
+    void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+                       const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -923,6 +935,8 @@ class Engine {
     long rank_topn_budget_ = 1L << 25;   // knob rank_topn_budget: 64-bit keys of the list workspace of one piece (256 MiB)
     DevBuf<int> tn_in_, tn_out_;
     DevBuf<unsigned long long> tn_list_;
+    int64_t n_rank_fb_sections_ = 0;   // counter 40: sections the _fb calls ranked with a row built from a feedback list
+    DevBuf<float> rk_rows_;            // a piece's effective user rows, [nsec][pitch]
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -18,14 +18,14 @@ constexpr int RE_TS = 64;     // sections (rows) of a tile
 constexpr int RE_SB = 4;      // sections a lane scores at once (register block)
 constexpr int RE_PCH = RANK_EVAL_TILE_POS;   // thresholds (positives) a tile keeps in LDS
 
-// re_row_score (one candidate against one user by ONE lane), re_user_row, re_item_row: svdf_k_rankscore.h
+// re_row_score (one candidate against one user by ONE lane), re_section_row, re_item_row: svdf_k_rankscore.h
 
 // the positives' own scores: the thresholds of the sweep.  One lane per (section, positive) pair.
 __global__ __launch_bounds__(256) void k_rank_eval_pos(const DevParams P, const RankEvalDev D) {
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= D.npos) return;
     const int item = D.pos_item[q];
-    D.pos_score[q] = re_row_score(P.k, re_user_row(P, D.sec_user[D.pos_sec[q]]), re_item_row(P, item), P.bias[P.item_off + item]);
+    D.pos_score[q] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, D.pos_sec[q]), re_item_row(P, item), P.bias[P.item_off + item]);
 }
 
 // what lane `lane` adds for one score against the thresholds [q0, q1) of its section; cnt[] = greater | tied | tied with a smaller id
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep(const DevParams P, cons
     for (int q = tid; q < RE_TS * nch; q += 256) {
         const int sec = q / nch, ch = q - sec * nch;
         float4 v = zero4;
-        if (sec < nrows) v = re_user_row(P, D.sec_user[D.row_sec[r0 + sec]])[ch];
+        if (sec < nrows) v = re_section_row(P, D.user_rows, D.sec_user, D.row_sec[r0 + sec])[ch];
         l_user[q] = v;
     }
     for (int q = tid; q < NP; q += 256) { l_ps[q] = D.pos_score[P0 + q]; l_pid[q] = D.pos_item[P0 + q]; }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep_wide(const DevParams P,
     const bool on[1] = {c < (long)P.num_item};
     const int cid[1] = {(int)c};
     float s[1] = {0.0f};
-    if (on[0]) s[0] = re_row_score(P.k, re_user_row(P, D.sec_user[sec]), re_item_row(P, c), P.bias[P.item_off + c]);
+    if (on[0]) s[0] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(P, c), P.bias[P.item_off + c]);
     re_count<1>(s, on, cid, D.row_p0[r], D.row_p0[r + 1], D.pos_score, D.pos_item, lane, [&](int q, int ngt, int neq, int nbf) {
         if (ngt) atomicAdd(&D.greater[q], ngt);
         if (neq) atomicAdd(&D.tied[q], neq);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_ban(const DevParams P, const 
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= D.nban) return;
     const int sec = D.ban_sec[b], c = D.ban_item[b];
-    const float s = re_row_score(P.k, re_user_row(P, D.sec_user[sec]), re_item_row(P, c), P.bias[P.item_off + c]);
+    const float s = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(P, c), P.bias[P.item_off + c]);
     if (s != s) { atomicSub(&D.nan_cnt[sec], 1); return; }
     for (int q = D.sec_p0[sec]; q < D.sec_p0[sec + 1]; q++) {
         const float t = D.pos_score[q];

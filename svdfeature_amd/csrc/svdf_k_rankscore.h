@@ -27,6 +27,11 @@ __device__ __forceinline__ float re_row_score(int k, const float4 *__restrict__ 
 __device__ __forceinline__ const float4 *re_user_row(const DevParams &P, unsigned u) {
     return reinterpret_cast<const float4 *>(P.W + (size_t)(P.user_off + u) * P.pitch);
 }
+// the user row section `sec` of a piece scores with: row `sec` of the workspace k_rank_live_rows wrote (a user-group trainer: feedback sum + user
+// row), or the W_user row of the section's user
+__device__ __forceinline__ const float4 *re_section_row(const DevParams &P, const float *user_rows, const unsigned *sec_user, int sec) {
+    return user_rows ? reinterpret_cast<const float4 *>(user_rows + (size_t)sec * P.pitch) : re_user_row(P, sec_user[sec]);
+}
 __device__ __forceinline__ const float4 *re_item_row(const DevParams &P, long i) {
     return reinterpret_cast<const float4 *>(P.W + (size_t)(P.item_off + i) * P.pitch);
 }

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
     for (int q = tid; q < TN_TS * nch; q += 256) {
         const int sec = q / nch, ch = q - sec * nch;
         float4 v = zero4;
-        if (sec < nrows) v = re_user_row(P, D.sec_user[sec_base + sec])[ch];
+        if (sec < nrows) v = re_section_row(P, D.user_rows, D.sec_user, sec_base + sec)[ch];
         l_user[q] = v;
     }
     for (int q = tid; q < TN_TS; q += 256) { l_thr[q] = 0ull; l_cnt[q] = 0; l_nan[q] = 0; }
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(64) void k_rank_topn_sweep_wide(const DevParams P, 
     const long i_begin = (long)blockIdx.y * D.items_per_block;
     const long i_end = i_begin + D.items_per_block < (long)P.num_item ? i_begin + D.items_per_block : (long)P.num_item;
     const int b0 = D.ban_p0[sec], b1 = D.ban_p0[sec + 1];
-    const float4 *urow = re_user_row(P, D.sec_user[sec]);
+    const float4 *urow = re_section_row(P, D.user_rows, D.sec_user, sec);
     tn_key_t *list = D.list + ((size_t)sec * D.gy + blockIdx.y) * D.cap;
     int nn = 0;
     for (long c0 = i_begin; c0 < i_end; c0 += 64) {

@@ -277,6 +277,7 @@ constexpr int RANK_EVAL_TILE_POS = 512;   // thresholds (positives) one sweep ti
 struct RankEvalDev {
     int nsec;                   // sections of the piece
     const unsigned *sec_user;   // [nsec]
+    const float *user_rows;     // nullptr: section s scores with the W_user row of sec_user[s]; else with row s of this [nsec][pitch] workspace (RankLiveRowsDev)
     const int *sec_p0;          // [nsec + 1] positives of section s: [sec_p0[s], sec_p0[s + 1])
     long npos;
     const int *pos_item, *pos_sec;   // [npos]
@@ -301,6 +302,7 @@ constexpr int RANK_TOPN_MAX_CAP = 512;   // keys one wave sorts in LDS: the larg
 struct RankTopnDev {
     int nsec;                        // sections of the piece
     const unsigned *sec_user;        // [nsec]
+    const float *user_rows;          // nullptr: W_user rows; else the [nsec][pitch] workspace of effective user rows (RankLiveRowsDev)
     const int *ban_p0;               // [nsec + 1] banned ids of section s: ban_item[ban_p0[s] .. ban_p0[s + 1]), distinct, ascending
     const int *ban_item;
     int top_n, cap, gy;              // list capacity (rank_topn_cap), item ranges (rank_topn_geometry)
@@ -315,6 +317,19 @@ struct RankTopnDev {
 int rank_topn_cap(const DevParams &P, int top_n);   // capacity of one list, <= RANK_TOPN_MAX_CAP
 void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block);   // at most max_lists / nsec (>= 1) item ranges
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep, then the merge: two launches
+
+// ---- the effective user rows of a piece's sections on a user-group trainer (svdf_k_rankrows.hip):
+// rows[s] = (0 + sum_j W_ufeedback[fb_index[j]] * fb_value[j], j in [fb_p0[s], fb_p0[s + 1]) in list order) + W_user[sec_user[s]] * 1, in the
+// ranker's unfused fp32 arithmetic.  Every index is local to the piece and has been validated on the host.
+struct RankLiveRowsDev {
+    int nsec;
+    const unsigned *sec_user;   // [nsec]
+    const int *fb_p0;           // [nsec + 1]
+    const unsigned *fb_index;   // feedback ids, < num_ufeedback
+    const float *fb_value;
+    float *rows;                // [nsec][pitch]
+};
+void launch_rank_live_rows(const DevParams &P, const RankLiveRowsDev &D, hipStream_t st);   // one launch
 
 }  // namespace svdf
 #endif

@@ -8,6 +8,7 @@
 
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
+#include "svdf_rankfb_lists.h"
 
 namespace svdf {
 
@@ -69,6 +70,21 @@ void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, cons
 void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
                                  const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
     rank_live_refusals("rank_eval");   // what the batch call does not cover (svdf_ranker_* does): svdf_ranktopn.cpp
+    rank_eval_run(S, user, nullptr, nullptr, nullptr, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
+}
+
+// the same on a user-group trainer, whose sections bring feedback lists; without lists on a format_type = 0 trainer: the call above
+void Engine::rank_eval_positions_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                                    const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out,
+                                    int *tied_out, int *ranked_out, int *nan_out) {
+    if (!rank_live_fb_refusals("rank_eval", fb_ptr != nullptr)) fb_ptr = nullptr;
+    rank_eval_run(S, user, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
+}
+
+// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted)
+void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                           const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
+                           int *nan_out) {
     // ---- the lists, before any device work
     check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
     const long num_item = mp_.num_item;
@@ -109,6 +125,7 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
             nan_out[s] = 0;
         }
     }
+    if (fb_ptr) rank_fb_validate("rank_eval", S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
     need_device("rank_eval");
     if (S == 0 || pos_ptr[S] == pos_ptr[0]) return;
     flush();   // behind whatever has been staged
@@ -120,14 +137,14 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
         long s1 = s0;
         int64_t load = 0;
         while (s1 < S) {
-            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1;
+            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1 + (fb_ptr ? fb_ptr[s1 + 1] - fb_ptr[s1] : 0);
             if (s1 > s0 && load + add > rank_eval_budget_) break;
             load += add;
             s1++;
         }
         const long nsec = s1 - s0;
         const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
-        check(npos < INT_MAX / 4 && nban < INT_MAX / 4, "rank_eval: one section with more than 2^29 entries");
+        check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
         if (npos == 0) { s0 = s1; continue; }
         // ---- rows (a section, or a slice of its positives) and tiles of rows
         std::vector<int> row_sec, row_first, row_p0, tile_r0;
@@ -145,9 +162,11 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
         }
         tile_r0.push_back(nrow);
         const int ntile = (int)tile_r0.size() - 1;
-        // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item
+        // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value]
         in.clear();
-        auto put = [&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
+        in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban +
+                   (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0));   // one allocation: the parts below never move what is already there
+        auto put =[&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         const size_t o_user = put((size_t)nsec), o_sp0 = put((size_t)nsec + 1), o_pitem = put((size_t)npos), o_psec = put((size_t)npos);
         for (long s = s0; s < s1; s++) {
             in[o_user + (size_t)(s - s0)] = (int)user[s];
@@ -169,6 +188,8 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
                 in[o_bsec + (size_t)(j - ban_first[(size_t)s0])] = (int)(s - s0);
                 in[o_bitem + (size_t)(j - ban_first[(size_t)s0])] = ban_ids[(size_t)j];
             }
+        const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
+        if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
         re_in_.upload(in.data(), in.size(), stream_);
         const size_t ncnt = 3 * (size_t)npos + (size_t)nsec;
         re_cnt_.reserve(ncnt);
@@ -177,6 +198,21 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
         RankEvalDev D;
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(re_in_.p + o_user);
+        D.user_rows = nullptr;
+        if (fb_ptr) {   // the sections' effective user rows, one more launch ahead of the sweep
+            const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
+            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
+            RankLiveRowsDev R;
+            R.nsec = (int)nsec; R.sec_user = D.sec_user;
+            R.fb_p0 = re_in_.p + o_fb;
+            R.fb_index = reinterpret_cast<const unsigned *>(re_in_.p + o_fb + (size_t)nsec + 1);
+            R.fb_value = reinterpret_cast<const float *>(re_in_.p + o_fb + (size_t)nsec + 1 + nfb);
+            R.rows = rk_rows_.p;
+            launch_rank_live_rows(P, R, stream_);
+            HIPCHECK(hipGetLastError());
+            n_launches_++;
+            D.user_rows = rk_rows_.p;
+        }
         D.sec_p0 = re_in_.p + o_sp0;
         D.npos = (long)npos;
         D.pos_item = re_in_.p + o_pitem; D.pos_sec = re_in_.p + o_psec;
@@ -202,6 +238,7 @@ void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *po
                 tied_out[j] = bad ? -1 : back[(size_t)npos + q];
             }
             n_rank_eval_sections_++;
+            if (fb_ptr) n_rank_fb_sections_++;
         }
         s0 = s1;
     }

@@ -6,14 +6,16 @@
 
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
+#include "svdf_rankfb_lists.h"
 #include "svdf_ranktopn_lists.h"
 
 namespace svdf {
 
 // what the batch ranking calls on the live model do not cover (svdf_ranker_* does); `who` is the prefix of the messages
-void Engine::rank_live_refusals(const char *who) {
+void Engine::rank_live_refusals(const char *who, bool svdpp_ok) {
     const std::string w(who);
-    if (!(!user_group() && mtype_.extend_type == 0))
+    // (svdpp_ok: the _fb calls, which also take user-group trainers of extend_type 0 / 1 -- both SVDPPFeature with one model, apex_svd.cpp:38-40)
+    if (!((!user_group() && mtype_.extend_type == 0) || (svdpp_ok && user_group() && mtype_.extend_type <= 1)))
         fail(w + ": user-group trainers (format_type = 1) and extend_type != 0 are not covered: the score has a feedback part; rank the saved model with svdf_ranker_*");
     if (!(name_feat_user_ == "NULL" && name_feat_item_ == "NULL"))
         fail(w + ": feature_user / feature_item side tables change the score and are not covered; rank the saved model with svdf_ranker_*");
@@ -24,15 +26,43 @@ void Engine::rank_live_refusals(const char *who) {
     if (!(space_allocated_ && trainer_ready_)) fail(w + ": call init_model / load_model and init_trainer first");
 }
 
+// The _fb calls: what rank_live_refusals refuses, except user-group trainers of extend_type 0 / 1, which must bring
+// feedback lists; a format_type = 0 trainer must not.  Returns whether the sections' rows are built from feedback lists.
+bool Engine::rank_live_fb_refusals(const char *who, bool has_lists) {
+    rank_live_refusals(who, true);
+    const std::string w(who);
+    if (!user_group()) {
+        if (has_lists) fail(w + ": feedback lists need a user-group trainer (format_type = 1)");
+        return false;
+    }
+    if (!has_lists)
+        fail(w + ": fb_ptr is NULL on a user-group trainer; a section without feedback must be given explicitly as an empty list "
+                 "(fb_ptr[s] == fb_ptr[s + 1]): the score has a feedback part");
+    return true;
+}
+
 void Engine::rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                        int *count_out, int *nan_out) {
     rank_live_refusals("rank_topn");
+    rank_topn_run(S, user, nullptr, nullptr, nullptr, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
+}
+
+void Engine::rank_topn_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+                          const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
+    if (!rank_live_fb_refusals("rank_topn", fb_ptr != nullptr)) fb_ptr = nullptr;
+    rank_topn_run(S, user, fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
+}
+
+// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted)
+void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+                           const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
     check(top_n >= 1 && top_n <= RANK_TOPN_MAX,
           "rank_topn: top_n must be between 1 and 256; for longer lists rank the saved model with svdf_ranker_* and top_k");
     // ---- the lists, before any device work
     check(S == 0 || (item_out && count_out && nan_out), "rank_topn: bad arguments");
     RankTopnLists L;
     rank_topn_validate(S, user, ban_ptr, ban_item, (long)mp_.num_user, (long)mp_.num_item, top_n, L);
+    if (fb_ptr) rank_fb_validate("rank_topn", S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
     need_device("rank_topn");
     if (S == 0) return;
     flush();   // behind whatever has been staged
@@ -41,14 +71,17 @@ void Engine::rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, con
     const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
-        const long s1 = rank_topn_piece(s0, S, max_lists, L.ban_first);
+        long s1 = rank_topn_piece(s0, S, max_lists, L.ban_first);
+        if (fb_ptr) s1 = rank_fb_piece("rank_topn", s0, s1, fb_ptr, rank_eval_budget_);   // ... and at most rank_eval_budget feedback entries
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
         D.nsec = (int)nsec; D.top_n = N; D.cap = cap;
         rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block);
-        // ---- one upload: sec_user | ban_p0 | ban_item
-        in.resize((size_t)nsec + (size_t)nsec + 1 + (size_t)nban);
+        // ---- one upload: sec_user | ban_p0 | ban_item [| fb_p0 | fb_index | fb_value]
+        const size_t o_fb = 2 * (size_t)nsec + 1 + (size_t)nban;
+        in.resize(o_fb + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0));
+        if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
         const size_t o_user = 0, o_bp0 = (size_t)nsec, o_ban = 2 * (size_t)nsec + 1;
         for (long s = s0; s < s1; s++) {
             in[o_user + (size_t)(s - s0)] = (int)user[s];
@@ -64,6 +97,22 @@ void Engine::rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, con
         HIPCHECK(hipMemsetAsync(tn_out_.p, 0, (nlist + (size_t)nsec) * sizeof(int), stream_));
         D.sec_user = reinterpret_cast<const unsigned *>(tn_in_.p + o_user);
         D.ban_p0 = tn_in_.p + o_bp0; D.ban_item = tn_in_.p + o_ban;
+        D.user_rows = nullptr;
+        if (fb_ptr) {   // the sections' effective user rows, one more launch ahead of the sweep
+            const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
+            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
+            RankLiveRowsDev R;
+            R.nsec = (int)nsec; R.sec_user = D.sec_user;
+            R.fb_p0 = tn_in_.p + o_fb;
+            R.fb_index = reinterpret_cast<const unsigned *>(tn_in_.p + o_fb + (size_t)nsec + 1);
+            R.fb_value = reinterpret_cast<const float *>(tn_in_.p + o_fb + (size_t)nsec + 1 + nfb);
+            R.rows = rk_rows_.p;
+            launch_rank_live_rows(P, R, stream_);
+            HIPCHECK(hipGetLastError());
+            n_launches_++;
+            n_rank_fb_sections_ += nsec;
+            D.user_rows = rk_rows_.p;
+        }
         D.list = tn_list_.p;
         D.list_cnt = tn_out_.p; D.nan_cnt = tn_out_.p + nlist; D.count_out = D.nan_cnt + nsec; D.item_out = D.count_out + nsec;
         D.score_out = reinterpret_cast<float *>(D.item_out + (size_t)nsec * N);
