@@ -655,6 +655,55 @@ int svdf_rank_eval_fb(svdf_trainer *t, long num_section, const unsigned *user, c
 int svdf_rank_topn_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                       const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
 
+/* ---- the same calls for sections that bring a USER LINE, and for trainers with feature_user / feature_item SIDE TABLES (DESIGN.md section
+ * 6z).  Each _lines entry point is its _fb twin with `user` replaced by a USER line per section: section s carries the (id, value) entries
+ * ul_index / ul_value[ul_ptr[s] .. ul_ptr[s + 1]) in line order -- a user id plus attribute ids, say.  The feedback triple, the positives, the
+ * bans and every output keep their _fb meaning, order and types.  The score of candidate i is the ranker's for that USER line and ITEM
+ * lines i:1 (proc_user / prepare_ifactor, apex_svd_base.h:687-735), with the trainer's side tables:
+ *   tu = 0 (format_type = 0), or 0 + sum_j W_ufeedback[fb_index[j]] * fb_value[j] in list order (a user-group trainer, section 6y's chain)
+ *   for each entry j of the line, in line order:   tu += W_user[uid_j] * val_j
+ *       then, if uid_j < the feature_user table's rows, for each child c of uid_j in table order:   tu += W_user[cid_c] * cval_c
+ *   -- the child is NOT scaled by val_j, and children of children are not followed: both are the reference's behaviour (:731-734).
+ *   With a feature_item table the item side is prepared once per call, for every item i:
+ *       f = 0;  f += W_item[i] * 1;  per child c of i in table order:  f += W_item[cid_c] * (float)((double)cval_c * 1.0)
+ *       b = 0 + i_bias[i] * 1;       per child:                        b = b + i_bias[cid_c] * cval_c * 1
+ *   (ids at or past a table's row count have no children); without one the sweeps read W_item / i_bias in place, exactly as the twins do.
+ *   score(i) = 0 + (b_i + <tu, f_i>) -- the dot product in the order given above.
+ * Every multiply and add is rounded separately to fp32 (no FMA), a value within 1e-6 of 1 multiplying as exactly 1 (scalar_map); a line's
+ * sum is a serial chain per element in line order, never split or reassociated.  Everything behind the two rows is svdf_rank_eval_positions'
+ * and svdf_rank_topn's, bit for bit: positions, tied, keys, the order of a list, NaN flagging, count, top_n <= 256, duplicate bans.
+ * LEGAL: an empty line (the row is the feedback sum, or 0); an id repeated inside a line (added twice, with its children twice); any float
+ * value; a child equal to its parent.  A NaN VALUE in a line is treated as section 6y treats a NaN feedback value: it reaches every element
+ * of the section's row and flags the section (the reference's scalar_map would take it for 1).  A NaN that reaches a row through the
+ * model or a table value flags like any NaN score.
+ * ACCEPTED: format_type = 0 trainers with extend_type = 0 (fb_ptr must be NULL); format_type = 1 trainers with extend_type 0 or 1 (fb_ptr is
+ * required, as in section 6y); each with or without either side table.
+ * REFUSED in the twins' words behind the prefixes "rank_eval:" / "rank_topn:": extend_type 2 / 15, common_latent_space != 0, amd:gpus > 1,
+ * rank handles, host-only handles ("needs a GPU").  REFUSED on the host, before any device work and before "needs a GPU":
+ *   a line id >= num_user                              "user feature index exceed bound" (the ranker's message, bare)
+ *   ul_ptr NULL / starting below 0 / decreasing        "ul_ptr is missing" / "ul_ptr must start at >= 0" / "ul_ptr must not decrease"
+ *   entries without ul_index or ul_value               "ul_index / ul_value is missing"
+ *   a side-table child id outside its id space         "feature_user: child index exceed bound" / "feature_item: ..." (the table loader
+ *                                                      refuses it at init_trainer too; the calls check once more, the tables are small)
+ *   and everything the _fb twins refuse about feedback lists, positives and bans, in their words.
+ * num_section == 0 launches nothing.  The six entry points above do not change: they still refuse side tables.
+ * Per piece the lines ride in the piece's one upload and k_rank_live_rows builds the sections' rows (one launch, as in section 6y).  With a
+ * feature_item table one more launch per CALL (k_rank_live_items) prepares the item matrix and bias vector into a workspace of
+ * num_item * (pitch + 1) * 4 bytes on the trainer's stream ahead of the sweeps; an allocation failure names that size.  The matrix is not
+ * kept across calls.  Line entries count towards `rank_eval_budget` like feedback entries; no result depends on a knob.
+ * Counter 41 counts, of the sections under counters 38 / 39, those ranked with a row built from a USER line, i.e. those of the _lines
+ * calls.  Counters 38 - 40 count as before (40: the sections whose row holds a feedback sum, _lines calls on user-group trainers included). */
+int svdf_rank_eval_positions_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                                   const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                   const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out,
+                                   int *ranked_out, int *nan_out);
+int svdf_rank_eval_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value, const int64_t *fb_ptr,
+                         const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
+                         const unsigned *ban_item, int num_at, const int *at, svdf_rank_metrics *out);
+int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value, const int64_t *fb_ptr,
+                         const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
+                         float *score_out, int *count_out, int *nan_out);
+
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator
  * by n draws without calling rand() n times (jump-ahead of glibc's additive-feedback table).  Host functions, no GPU needed;

@@ -249,6 +249,10 @@ def load_library():
     lib.svdf_rank_eval_positions_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_topn_fb.argtypes = [P, C.c_long, _u32p] + _fb + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    _ul = [C.c_void_p, C.c_void_p, C.c_void_p]   # ul_ptr, ul_index, ul_value in place of `user`
+    lib.svdf_rank_eval_positions_lines.argtypes = [P, C.c_long] + _ul + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
+    lib.svdf_rank_eval_lines.argtypes = [P, C.c_long] + _ul + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_rank_topn_lines.argtypes = [P, C.c_long] + _ul + _fb + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -735,14 +739,41 @@ class Trainer:
             raise SvdfError(who + ": fb_index / fb_value are shorter than fb_ptr says")
         return tuple(_opt_ptr(a) for a in keep), keep
 
-    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None):
+    @staticmethod
+    def _user_lines(who, users, lines):
+        """lines = (ul_ptr, ul_index, ul_value), section s bringing the USER line entries [ul_ptr[s], ul_ptr[s + 1]) in place of a user ->
+        (S, the three pointer arguments of the svdf_rank_*_lines calls, the arrays they point into); the section count is ul_ptr's"""
+        if users is not None:
+            raise SvdfError(who + ": with lines= the sections bring USER lines: users must be None")
+        ul_ptr, ul_index, ul_value = lines
+        if ul_ptr is None:
+            raise SvdfError(who + ": ul_ptr is missing")
+        keep = (_pad(ul_ptr, np.int64), _pad(ul_index if ul_index is not None else [], np.uint32), _pad(ul_value if ul_value is not None else [], np.float32))
+        S = len(ul_ptr) - 1
+        if S < 0:
+            raise SvdfError(who + ": ul_ptr must have one entry more than there are sections")
+        n = int(keep[0][S]) if S else 0
+        if n > 0 and (len(keep[1]) < n or len(keep[2]) < n):
+            raise SvdfError(who + ": ul_index / ul_value are shorter than ul_ptr says")
+        return S, tuple(_opt_ptr(a) for a in keep), keep
+
+    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None, lines=None):
         """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section.  feedback = (fb_ptr, fb_index, fb_value): the
-        sections' feedback lists, for user-group trainers (svdf_rank_eval_positions_fb)."""
+        sections' feedback lists, for user-group trainers (svdf_rank_eval_positions_fb).  lines = (ul_ptr, ul_index, ul_value):
+        the sections bring USER lines of several (id, value) entries and the trainer may have side tables (svdf_rank_eval_positions_lines,
+        DESIGN.md 6z); users is None then, and feedback= combines with it."""
+        if lines is not None:
+            S, ul, keep_ul = self._user_lines("rank_eval", users, lines)
+            users = np.zeros(S, np.uint32)
         users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
         S, n = len(users), int(pos_ptr[-1]) if len(users) else 0
         position, tied = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         ranked, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
-        if feedback is None:
+        if lines is not None:
+            fb, keep = self._feedback_lists("rank_eval", feedback or (None, None, None), S)
+            self._ok(self.lib.svdf_rank_eval_positions_lines(self.h, S, ul[0], ul[1], ul[2], fb[0], fb[1], fb[2], pos_ptr, pos_item, _opt_ptr(ban_ptr),
+                                                             _opt_ptr(ban_item), position, tied, ranked, nan))
+        elif feedback is None:
             self._ok(self.lib.svdf_rank_eval_positions(self.h, S, _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
                                                        position, tied, ranked, nan))
         else:
@@ -751,12 +782,19 @@ class Trainer:
                                                           _opt_ptr(ban_item), position, tied, ranked, nan))
         return position[:n], tied[:n], ranked[:S], nan[:S]
 
-    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None):
+    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None, lines=None):
         """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict).
-        feedback: as in rank_positions (svdf_rank_eval_fb)."""
+        feedback, lines: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines)."""
+        if lines is not None:
+            S, ul, keep_ul = self._user_lines("rank_eval", users, lines)
+            users = np.zeros(S, np.uint32)
         users, pos_ptr, pos_item, ban_ptr, ban_item = self._rank_lists(users, pos_ptr, pos_item, ban_ptr, ban_item)
         m = RankMetrics()
-        if feedback is None:
+        if lines is not None:
+            fb, keep = self._feedback_lists("rank_eval", feedback or (None, None, None), len(users))
+            self._ok(self.lib.svdf_rank_eval_lines(self.h, len(users), ul[0], ul[1], ul[2], fb[0], fb[1], fb[2], pos_ptr, pos_item, _opt_ptr(ban_ptr),
+                                                   _opt_ptr(ban_item), len(at), _pad(list(at), np.int32), C.byref(m)))
+        elif feedback is None:
             self._ok(self.lib.svdf_rank_eval(self.h, len(users), _pad(users, np.uint32), pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item),
                                              len(at), _pad(list(at), np.int32), C.byref(m)))
         else:
@@ -765,10 +803,14 @@ class Trainer:
                                                 _opt_ptr(ban_item), len(at), _pad(list(at), np.int32), C.byref(m)))
         return m.as_dict()
 
-    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None, feedback=None):
+    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None, feedback=None, lines=None):
         """svdf_rank_topn: the top_n best items per section among all items that are not banned, higher score first and equal
         scores by ascending id; (items [S, top_n] int32, -1 beyond count; scores [S, top_n] float32; count [S]; nan [S]).  feedback = (fb_ptr,
-        fb_index, fb_value): the sections' feedback lists, for user-group trainers (svdf_rank_topn_fb)."""
+        fb_index, fb_value): the sections' feedback lists, for user-group trainers (svdf_rank_topn_fb).  lines = (ul_ptr, ul_index,
+        ul_value): the sections bring USER lines and the trainer may have side tables (svdf_rank_topn_lines); users is None then."""
+        if lines is not None:
+            S, ul, keep_ul = self._user_lines("rank_topn", users, lines)
+            users = np.zeros(S, np.uint32)
         users, top_n = np.ascontiguousarray(users, np.uint32), int(top_n)
         S = len(users)
         if ban_ptr is not None:
@@ -780,7 +822,11 @@ class Trainer:
         n = max(top_n, 1)
         items, scores = np.full((max(S, 1), n), -1, np.int32), np.zeros((max(S, 1), n), np.float32)
         count, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
-        if feedback is None:
+        if lines is not None:
+            fb, keep = self._feedback_lists("rank_topn", feedback or (None, None, None), S)
+            self._ok(self.lib.svdf_rank_topn_lines(self.h, S, ul[0], ul[1], ul[2], fb[0], fb[1], fb[2], _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n,
+                                                   items.reshape(-1), scores.ctypes.data_as(C.c_void_p), count, nan))
+        elif feedback is None:
             self._ok(self.lib.svdf_rank_topn(self.h, S, _pad(users, np.uint32), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, items.reshape(-1),
                                              scores.ctypes.data_as(C.c_void_p), count, nan))
         else:

@@ -9,6 +9,7 @@
 
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
+#include "svdf_ranklines_lists.h"
 #include "svdf_wseq_rule.h"
 
 namespace svdf {
@@ -352,6 +353,43 @@ int svdf_rank_eval_fb(svdf_trainer *t, long num_section, const unsigned *user, c
 int svdf_rank_topn_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                       const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
     SVDF_GUARD(-1, { t->e->rank_topn_fb(num_section, user, fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out); return 0; })
+}
+/* ... for sections that bring a USER line, on trainers with or without side tables */
+int svdf_rank_eval_positions_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                                   const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                   const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out,
+                                   int *ranked_out, int *nan_out) {
+    SVDF_GUARD(-1, {
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_eval_positions_lines(num_section, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out,
+                                        nan_out);
+        return 0;
+    })
+}
+int svdf_rank_eval_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value, const int64_t *fb_ptr,
+                         const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
+                         const unsigned *ban_item, int num_at, const int *at, svdf_rank_metrics *out) {
+    SVDF_GUARD(-1, {
+        const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
+        std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_eval_positions_lines(num_section, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position.data(), tied.data(),
+                                        ranked.data(), nan.data());
+        svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
+        return 0;
+    })
+}
+int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value, const int64_t *fb_ptr,
+                         const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
+                         float *score_out, int *count_out, int *nan_out) {
+    SVDF_GUARD(-1, {
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_topn_lines(num_section, U, fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
+        return 0;
+    })
 }
 
 /* ---- ISVDRanker ---- */

@@ -221,6 +221,7 @@ int64_t Engine::counter(int what) const {
     case 38: return n_rank_eval_sections_;   // sections (with positives) ranked by svdf_rank_eval_positions' sweep (section 6w)
     case 39: return n_rank_topn_sections_;   // sections listed by svdf_rank_topn (section 6x)
     case 40: return n_rank_fb_sections_;     // of those two, the sections ranked with a row built from a feedback list (section 6y)
+    case 41: return n_rank_line_sections_;   // of those two, the sections the _lines calls ranked with a row built from a USER line (section 6z)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

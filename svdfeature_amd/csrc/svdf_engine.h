@@ -380,6 +380,7 @@ struct Dataset {
     Dataset &operator=(const Dataset &) = delete;
 };
 
+struct RankLines;   // the USER lines of the svdf_rank_*_lines calls (svdf_ranklines_lists.h)
 class Engine {
   public:
     Engine(TypeParam mtype, int device);
@@ -463,19 +464,29 @@ class Engine {
     // top-N item lists on the live model (svdf_ranktopn.cpp, svdf_k_ranktopn.hip)
     void rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                    int *count_out, int *nan_out);
-    void rank_live_refusals(const char *who, bool svdpp_ok = false);   // the configurations neither batch ranking call covers
+    void rank_live_refusals(const char *who, bool svdpp_ok = false, bool tables_ok = false);   // the configurations the batch ranking calls do not cover
     // the same calls for sections with feedback lists: user-group (SVD++) trainers (svdf_k_rankrows.hip)
     void rank_eval_positions_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                                 const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
                                 int *nan_out);
     void rank_topn_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                       const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
-    bool rank_live_fb_refusals(const char *who, bool has_lists);
+    bool rank_live_fb_refusals(const char *who, bool has_lists, bool tables_ok = false);
+    // the same calls for sections that bring a USER line (several ids, any value) and for trainers with feature_user / feature_item side
+    // tables (svdf_k_rankrows.hip)
+    void rank_eval_positions_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                   const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out,
+                                   int *ranked_out, int *nan_out);
+    void rank_topn_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+                         const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+    void rank_lines_admit(const char *who, long S, const RankLines &U);   // the lines and the tables' child ids, on the host
+    void rank_live_items(const char *who, const float **item_rows, const float **item_bias);   // the prepared item side where feature_item is set
+    // lines != nullptr: a _lines call -- `user` is not read, the rows come from the lines (and fb_ptr, where the trainer is a user-group one)
     void rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                        const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                       int *nan_out);
+                       int *nan_out, const RankLines *lines = nullptr);
     void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
-                       const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+                       const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -937,6 +948,8 @@ class Engine {
     DevBuf<unsigned long long> tn_list_;
     int64_t n_rank_fb_sections_ = 0;   // counter 40: sections the _fb calls ranked with a row built from a feedback list
     DevBuf<float> rk_rows_;            // a piece's effective user rows, [nsec][pitch]
+    int64_t n_rank_line_sections_ = 0; // counter 41: sections the _lines calls ranked with a row built from a USER line
+    DevBuf<float> rk_items_;           // a _lines call's prepared item side: [num_item][pitch] rows, then [num_item] biases
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -25,7 +25,8 @@ __global__ __launch_bounds__(256) void k_rank_eval_pos(const DevParams P, const 
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= D.npos) return;
     const int item = D.pos_item[q];
-    D.pos_score[q] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, D.pos_sec[q]), re_item_row(P, item), P.bias[P.item_off + item]);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
+    D.pos_score[q] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, D.pos_sec[q]), re_item_row(ibase, P.pitch, item), ibias[item]);
 }
 
 // what lane `lane` adds for one score against the thresholds [q0, q1) of its section; cnt[] = greater | tied | tied with a smaller id
@@ -70,6 +71,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep(const DevParams P, cons
     const int r0 = D.tile_r0[blockIdx.x], nrows = D.tile_r0[blockIdx.x + 1] - r0;
     const int P0 = D.row_p0[r0], NP = D.row_p0[r0 + nrows] - P0;
     const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
 
     for (int q = tid; q < RE_TS * nch; q += 256) {
         const int sec = q / nch, ch = q - sec * nch;
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep(const DevParams P, cons
     for (long it0 = i_begin; it0 < i_end; it0 += TI) {
         __syncthreads();   // the previous tile has been read (first trip: nothing yet)
         const int live = i_end - it0 < TI ? (int)(i_end - it0) : TI;
-        const float4 *src = re_item_row(P, it0);
+        const float4 *src = re_item_row(ibase, P.pitch, it0);
         for (int q = tid; q < TI * nch; q += 256) {
             const int row = q / nch, ch = q - row * nch;
             float4 v = zero4;   // rows past the item range are zeros, never read from memory
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep(const DevParams P, cons
             const long c = it0 + lane + 64 * ib;
             on[ib] = c < i_end;
             cid[ib] = (int)c;
-            bias[ib] = on[ib] ? P.bias[P.item_off + c] : 0.0f;
+            bias[ib] = on[ib] ? ibias[c] : 0.0f;
         }
         __syncthreads();
         for (int g = 0; g < 16 / RE_SB; g++) {
@@ -185,7 +187,8 @@ __global__ __launch_bounds__(256) void k_rank_eval_sweep_wide(const DevParams P,
     const bool on[1] = {c < (long)P.num_item};
     const int cid[1] = {(int)c};
     float s[1] = {0.0f};
-    if (on[0]) s[0] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(P, c), P.bias[P.item_off + c]);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
+    if (on[0]) s[0] = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(ibase, P.pitch, c), ibias[c]);
     re_count<1>(s, on, cid, D.row_p0[r], D.row_p0[r + 1], D.pos_score, D.pos_item, lane, [&](int q, int ngt, int neq, int nbf) {
         if (ngt) atomicAdd(&D.greater[q], ngt);
         if (neq) atomicAdd(&D.tied[q], neq);
@@ -201,7 +204,8 @@ __global__ __launch_bounds__(256) void k_rank_eval_ban(const DevParams P, const 
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= D.nban) return;
     const int sec = D.ban_sec[b], c = D.ban_item[b];
-    const float s = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(P, c), P.bias[P.item_off + c]);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
+    const float s = re_row_score(P.k, re_section_row(P, D.user_rows, D.sec_user, sec), re_item_row(ibase, P.pitch, c), ibias[c]);
     if (s != s) { atomicSub(&D.nan_cnt[sec], 1); return; }
     for (int q = D.sec_p0[sec]; q < D.sec_p0[sec + 1]; q++) {
         const float t = D.pos_score[q];

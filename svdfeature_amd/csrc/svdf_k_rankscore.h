@@ -32,8 +32,15 @@ __device__ __forceinline__ const float4 *re_user_row(const DevParams &P, unsigne
 __device__ __forceinline__ const float4 *re_section_row(const DevParams &P, const float *user_rows, const unsigned *sec_user, int sec) {
     return user_rows ? reinterpret_cast<const float4 *>(user_rows + (size_t)sec * P.pitch) : re_user_row(P, sec_user[sec]);
 }
-__device__ __forceinline__ const float4 *re_item_row(const DevParams &P, long i) {
-    return reinterpret_cast<const float4 *>(P.W + (size_t)(P.item_off + i) * P.pitch);
+// the item side a call scores with: W_item / i_bias where the model keeps them, or the matrix and bias vector k_rank_live_items prepared
+// (a trainer with a feature_item table) -- both [num_item][pitch] / [num_item].  ONE select per kernel, outside
+// its scoring loops
+__device__ __forceinline__ const float *re_item_base(const DevParams &P, const float *item_rows) {
+    return item_rows ? item_rows : P.W + (size_t)P.item_off * P.pitch;
+}
+__device__ __forceinline__ const float *re_item_bias(const DevParams &P, const float *item_bias) { return item_bias ? item_bias : P.bias + P.item_off; }
+__device__ __forceinline__ const float4 *re_item_row(const float *item_base, int pitch, long i) {
+    return reinterpret_cast<const float4 *>(item_base + (size_t)i * pitch);
 }
 
 }  // namespace svdf

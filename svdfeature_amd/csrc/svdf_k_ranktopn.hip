@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
     const int sec_base = blockIdx.x * TN_TS;
     const int nrows = D.nsec - sec_base < TN_TS ? D.nsec - sec_base : TN_TS;
     const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
 
     for (int q = tid; q < TN_TS * nch; q += 256) {
         const int sec = q / nch, ch = q - sec * nch;
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
     for (long it0 = i_begin; it0 < i_end; it0 += TI) {
         __syncthreads();   // the previous tile and its mask have been read (first trip: nothing yet)
         const int live = i_end - it0 < TI ? (int)(i_end - it0) : TI;
-        const float4 *src = re_item_row(P, it0);
+        const float4 *src = re_item_row(ibase, P.pitch, it0);
         for (int q = tid; q < TI * nch; q += 256) {
             const int row = q / nch, ch = q - row * nch;
             float4 v = zero4;   // rows past the item range are zeros, never read from memory
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
             const long c = it0 + lane + 64 * ib;
             on[ib] = c < i_end;
             cid[ib] = (int)c;
-            bias[ib] = on[ib] ? P.bias[P.item_off + c] : 0.0f;
+            bias[ib] = on[ib] ? ibias[c] : 0.0f;
         }
         __syncthreads();
         for (int g = 0; g < 16 / TN_SB; g++) {
@@ -252,6 +253,7 @@ __global__ __launch_bounds__(64) void k_rank_topn_sweep_wide(const DevParams P, 
     const long i_end = i_begin + D.items_per_block < (long)P.num_item ? i_begin + D.items_per_block : (long)P.num_item;
     const int b0 = D.ban_p0[sec], b1 = D.ban_p0[sec + 1];
     const float4 *urow = re_section_row(P, D.user_rows, D.sec_user, sec);
+    const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
     tn_key_t *list = D.list + ((size_t)sec * D.gy + blockIdx.y) * D.cap;
     int nn = 0;
     for (long c0 = i_begin; c0 < i_end; c0 += 64) {
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(64) void k_rank_topn_sweep_wide(const DevParams P, 
         }
         const int cid[1] = {(int)c};
         float s[1] = {0.0f};
-        if (ranked[0]) s[0] = re_row_score(P.k, urow, re_item_row(P, c), P.bias[P.item_off + c]);
+        if (ranked[0]) s[0] = re_row_score(P.k, urow, re_item_row(ibase, P.pitch, c), ibias[c]);
         nn += __popcll(__ballot(ranked[0] && s[0] != s[0]));
         tn_select<1>(s, ranked, cid, list, &l_cnt, &l_thr, l_scr, D.top_n, D.cap, lane);
     }

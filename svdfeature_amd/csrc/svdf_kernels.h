@@ -278,6 +278,7 @@ struct RankEvalDev {
     int nsec;                   // sections of the piece
     const unsigned *sec_user;   // [nsec]
     const float *user_rows;     // nullptr: section s scores with the W_user row of sec_user[s]; else with row s of this [nsec][pitch] workspace (RankLiveRowsDev)
+    const float *item_rows = nullptr, *item_bias = nullptr;   // nullptr: W_item / i_bias where the model keeps them; else the prepared [num_item][pitch] matrix and [num_item] biases (launch_rank_live_items)
     const int *sec_p0;          // [nsec + 1] positives of section s: [sec_p0[s], sec_p0[s + 1])
     long npos;
     const int *pos_item, *pos_sec;   // [npos]
@@ -303,6 +304,7 @@ struct RankTopnDev {
     int nsec;                        // sections of the piece
     const unsigned *sec_user;        // [nsec]
     const float *user_rows;          // nullptr: W_user rows; else the [nsec][pitch] workspace of effective user rows (RankLiveRowsDev)
+    const float *item_rows = nullptr, *item_bias = nullptr;   // nullptr: W_item / i_bias; else the prepared item matrix and biases (launch_rank_live_items)
     const int *ban_p0;               // [nsec + 1] banned ids of section s: ban_item[ban_p0[s] .. ban_p0[s + 1]), distinct, ascending
     const int *ban_item;
     int top_n, cap, gy;              // list capacity (rank_topn_cap), item ranges (rank_topn_geometry)
@@ -328,8 +330,15 @@ struct RankLiveRowsDev {
     const unsigned *fb_index;   // feedback ids, < num_ufeedback
     const float *fb_value;
     float *rows;                // [nsec][pitch]
+    // section 6z, ul_p0 != nullptr: the section brings a USER line instead of sec_user -- behind the feedback sum (fb_p0 == nullptr: 0), per entry
+    // j in [ul_p0[s], ul_p0[s + 1]) in line order: += W_user[ul_index[j]] * ul_value[j], then the children of that id in P.feat_user
+    const int *ul_p0 = nullptr;           // [nsec + 1]
+    const unsigned *ul_index = nullptr;   // user ids, < num_user
+    const float *ul_value = nullptr;
 };
 void launch_rank_live_rows(const DevParams &P, const RankLiveRowsDev &D, hipStream_t st);   // one launch
+// the prepared item side of a trainer with a feature_item table: item_rows[i] = W_item[i] * 1 + its children's rows * cval, item_bias[i] alike
+void launch_rank_live_items(const DevParams &P, float *item_rows, float *item_bias, hipStream_t st);   // one launch
 
 }  // namespace svdf
 #endif

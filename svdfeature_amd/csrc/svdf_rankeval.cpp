@@ -9,6 +9,7 @@
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
 #include "svdf_rankfb_lists.h"
+#include "svdf_ranklines_lists.h"
 
 namespace svdf {
 
@@ -81,10 +82,20 @@ void Engine::rank_eval_positions_fb(long S, const unsigned *user, const int64_t 
     rank_eval_run(S, user, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
 }
 
-// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted)
+// ... and for sections that bring a USER line, on trainers with or without side tables
+void Engine::rank_eval_positions_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                                       const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                                       int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
+    if (!rank_live_fb_refusals("rank_eval", fb_ptr != nullptr, true)) fb_ptr = nullptr;
+    const std::vector<unsigned> user((size_t)std::max<long>(S, 1), 0u);   // not read by the kernels: the rows come from the lines
+    rank_eval_run(S, user.data(), fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out, &U);
+}
+
+// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
+// lines != nullptr: from their USER lines, behind the feedback sum where there is one
 void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                            const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                           int *nan_out) {
+                           int *nan_out, const RankLines *lines) {
     // ---- the lists, before any device work
     check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
     const long num_item = mp_.num_item;
@@ -126,10 +137,13 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         }
     }
     if (fb_ptr) rank_fb_validate("rank_eval", S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
+    if (lines) rank_lines_admit("rank_eval", S, *lines);
     need_device("rank_eval");
     if (S == 0 || pos_ptr[S] == pos_ptr[0]) return;
     flush();   // behind whatever has been staged
     const DevParams &P = params();
+    const float *item_rows = nullptr, *item_bias = nullptr;
+    if (lines) rank_live_items("rank_eval", &item_rows, &item_bias);   // once per call
     const int tile_rows = rank_eval_tile_rows(P);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
@@ -137,14 +151,16 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         long s1 = s0;
         int64_t load = 0;
         while (s1 < S) {
-            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1 + (fb_ptr ? fb_ptr[s1 + 1] - fb_ptr[s1] : 0);
+            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1 + (fb_ptr ? fb_ptr[s1 + 1] - fb_ptr[s1] : 0) +
+                                (lines ? lines->ptr[s1 + 1] - lines->ptr[s1] : 0);
             if (s1 > s0 && load + add > rank_eval_budget_) break;
             load += add;
             s1++;
         }
         const long nsec = s1 - s0;
         const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
-        check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
+        check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4) &&
+                  (!lines || lines->ptr[s1] - lines->ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
         if (npos == 0) { s0 = s1; continue; }
         // ---- rows (a section, or a slice of its positives) and tiles of rows
         std::vector<int> row_sec, row_first, row_p0, tile_r0;
@@ -162,10 +178,10 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         }
         tile_r0.push_back(nrow);
         const int ntile = (int)tile_r0.size() - 1;
-        // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value]
+        // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         in.clear();
         in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban +
-                   (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0));   // one allocation: the parts below never move what is already there
+                   (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));   // one allocation: the parts below never move what is already there
         auto put =[&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         const size_t o_user = put((size_t)nsec), o_sp0 = put((size_t)nsec + 1), o_pitem = put((size_t)npos), o_psec = put((size_t)npos);
         for (long s = s0; s < s1; s++) {
@@ -190,6 +206,8 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             }
         const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
         if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
+        const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
+        if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
         re_in_.upload(in.data(), in.size(), stream_);
         const size_t ncnt = 3 * (size_t)npos + (size_t)nsec;
         re_cnt_.reserve(ncnt);
@@ -199,14 +217,24 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(re_in_.p + o_user);
         D.user_rows = nullptr;
-        if (fb_ptr) {   // the sections' effective user rows, one more launch ahead of the sweep
-            const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
+        D.item_rows = item_rows; D.item_bias = item_bias;
+        if (fb_ptr || lines) {   // the sections' effective user rows, one more launch ahead of the sweep
             rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
             RankLiveRowsDev R;
             R.nsec = (int)nsec; R.sec_user = D.sec_user;
-            R.fb_p0 = re_in_.p + o_fb;
-            R.fb_index = reinterpret_cast<const unsigned *>(re_in_.p + o_fb + (size_t)nsec + 1);
-            R.fb_value = reinterpret_cast<const float *>(re_in_.p + o_fb + (size_t)nsec + 1 + nfb);
+            R.fb_p0 = nullptr; R.fb_index = nullptr; R.fb_value = nullptr;
+            if (fb_ptr) {
+                const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
+                R.fb_p0 = re_in_.p + o_fb;
+                R.fb_index = reinterpret_cast<const unsigned *>(re_in_.p + o_fb + (size_t)nsec + 1);
+                R.fb_value = reinterpret_cast<const float *>(re_in_.p + o_fb + (size_t)nsec + 1 + nfb);
+            }
+            if (lines) {
+                const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
+                R.ul_p0 = re_in_.p + o_ul;
+                R.ul_index = reinterpret_cast<const unsigned *>(re_in_.p + o_ul + (size_t)nsec + 1);
+                R.ul_value = reinterpret_cast<const float *>(re_in_.p + o_ul + (size_t)nsec + 1 + nul);
+            }
             R.rows = rk_rows_.p;
             launch_rank_live_rows(P, R, stream_);
             HIPCHECK(hipGetLastError());
@@ -239,6 +267,7 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             }
             n_rank_eval_sections_++;
             if (fb_ptr) n_rank_fb_sections_++;
+            if (lines) n_rank_line_sections_++;
         }
         s0 = s1;
     }
