@@ -704,6 +704,57 @@ int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_pt
                          const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
                          float *score_out, int *count_out, int *nan_out);
 
+/* ---- the same rankings over PER-SECTION CANDIDATE LISTS: section s ranks over an item set the caller defines,
+ * cand_item[cand_ptr[s] .. cand_ptr[s + 1]), not over 0 .. num_item - 1 minus a ban list -- the reference's SVDFeatureRanker over the ITEM
+ * lines of a section (apex_svd_base.h:711-782).  Sampled-negative evaluation (a held-out positive among 99 or 999 sampled negatives) and
+ * re-ranking a retrieved shortlist are these calls.  Only the listed (section, item) pairs are scored; a pair costs one gathered item row.
+ * WHO THE SECTION IS: exactly one of `user` / `ul_ptr` is non-NULL ("give the sections either as users or as USER lines" otherwise).
+ *   user:    the section's row is svdf_rank_eval_positions' (the W_user row in place); on a user-group trainer section 6y's (the feedback
+ *            chain + W_user[u] * 1; fb_ptr is required there and must be NULL on a format_type = 0 trainer).  Side tables are refused in the
+ *            twins' words.
+ *   ul_ptr:  the section's row is section 6z's (a USER line of (id, value) entries, feature_user children, behind the feedback chain on a
+ *            user-group trainer); the trainer may have feature_user / feature_item side tables.
+ * The accepted and refused configurations are otherwise those of the matching twin (_fb with `user`, _lines with `ul_ptr`), in its words.
+ * WHAT IS RANKED: there are no bans -- a caller leaves out what must not be ranked.  For the positions calls the ranked set of section s is
+ * the DISTINCT ids of its candidate list together with the section's positives: a positive is a candidate by definition, and listing it
+ * among the candidates as well counts it once.  For the top-N call it is the distinct ids of the list alone.  Duplicate ids count once, as
+ * duplicate bans do.
+ * SCORE: exactly the score the twin gives that (section, item) pair, the same operations in the same order -- four serial chains over the
+ * 4-float chunks, (a0 + a2) + (a1 + a3), the scalar tail, 0 + (bias + sum), every multiply and add rounded separately to fp32; with a
+ * feature_item table the prepared item row and bias of section 6z.  It is bit for bit what svdf_ranker_* gives on the saved model.
+ * OUTPUTS: position_out / tied_out [pos_ptr[num_section]]: the twins' definition over the ranked set -- position = candidates that score
+ *   strictly higher + tied ones with a smaller id; tied = other candidates with an equal score; +0 == -0, NaN equals nothing.
+ *   ranked_out[s]: the size of the ranked set.  nan_out[s]: 1 when a RANKED candidate scores NaN (a NaN row of an item outside the
+ *   section's set does not flag); the section's positions and tied are then -1, or its list is empty with count_out[s] = 0.
+ *   item_out / score_out [num_section][top_n], count_out [num_section]: svdf_rank_topn's layout, count_out[s] = min(top_n, distinct
+ *   candidates); higher score first, equal scores by ascending id; -1 / 0 beyond count_out[s].  1 <= top_n <= 256.  score_out may be NULL.
+ * LEGAL: an empty candidate list (with positives: their positions among themselves; top-N: count_out = 0); a user in several sections with
+ * different lists; a list that covers the whole catalogue; a section without positives (ranked_out is filled, nothing of it is scored).
+ * REFUSED on the host, before any device work and before "needs a GPU", behind the prefix "rank_eval:" / "rank_topn:":
+ *   a candidate id >= num_item                           "sample item index exceed bound" (the ranker's message, bare)
+ *   cand_ptr NULL / starting below 0 / decreasing        "cand_ptr is missing" / "cand_ptr must start at >= 0" / "cand_ptr must not decrease"
+ *   entries without cand_item                            "cand_item is missing"
+ *   a positive repeated inside a section                 "rank_eval: a positive item is repeated inside a section"
+ *   and everything the twins refuse about users, lines, feedback lists, positives and top_n, in their words.
+ * num_section == 0 launches nothing; a positions call without any positive launches nothing.
+ * A call is cut into pieces of whole sections whose entries (candidate pairs, positives, feedback and line entries, one per section) stay
+ * within the knob `rank_eval_budget`, in both kinds of call; a section larger than the budget is a piece of its own.  Per piece: one upload
+ * (the deduplicated lists in ascending id order, the tile table, the rows' lists), the workspaces cand_score (4 bytes per pair) and the
+ * results; an allocation failure names the size.  No result depends on a knob (`rank_cand_form`: 0 the measured choice of the score kernel's
+ * form, 1 one lane per pair, 2 staged in LDS).  With a feature_item table the whole catalogue is still prepared once per call.
+ * Counter 42 counts the sections ranked over a candidate list; they count under 38 (positions: sections with positives) / 39 (top-N) too,
+ * and under 40 / 41 as the twins' do.  The nine entry points above do not change. */
+int svdf_rank_eval_positions_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                                  const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                  const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int *position_out, int *tied_out,
+                                  int *ranked_out, int *nan_out);
+int svdf_rank_eval_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                        const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item,
+                        const int64_t *cand_ptr, const unsigned *cand_item, int num_at, const int *at, svdf_rank_metrics *out);
+int svdf_rank_topn_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                        const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *cand_ptr, const unsigned *cand_item,
+                        int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator
  * by n draws without calling rand() n times (jump-ahead of glibc's additive-feedback table).  Host functions, no GPU needed;

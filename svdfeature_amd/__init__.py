@@ -253,6 +253,10 @@ def load_library():
     lib.svdf_rank_eval_positions_lines.argtypes = [P, C.c_long] + _ul + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_lines.argtypes = [P, C.c_long] + _ul + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_topn_lines.argtypes = [P, C.c_long] + _ul + _fb + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    _cand = [C.c_void_p] + _ul + _fb   # user or ul_ptr, ul_index, ul_value; fb_ptr, fb_index, fb_value
+    lib.svdf_rank_eval_positions_cand.argtypes = [P, C.c_long] + _cand + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
+    lib.svdf_rank_eval_cand.argtypes = [P, C.c_long] + _cand + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_rank_topn_cand.argtypes = [P, C.c_long] + _cand + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -757,11 +761,46 @@ class Trainer:
             raise SvdfError(who + ": ul_index / ul_value are shorter than ul_ptr says")
         return S, tuple(_opt_ptr(a) for a in keep), keep
 
-    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None, lines=None):
+    def _cand_call(self, who, users, feedback, lines, candidates, ban_ptr):
+        """candidates = (cand_ptr, cand_item), section s ranking over the ids cand_item[cand_ptr[s] .. cand_ptr[s + 1]) -> (S, the seven
+        pointer arguments of the svdf_rank_*_cand calls that name the sections -- user, ul_*, fb_* --, the two of the lists, the arrays they point into)"""
+        if ban_ptr is not None:
+            raise SvdfError(who + ": bans and candidates exclude each other")
+        if lines is not None:
+            S, ul, keep_ul = self._user_lines(who, users, lines)
+            who_ptr = [None] + list(ul)
+        else:
+            keep_ul = _pad(np.ascontiguousarray(users, np.uint32), np.uint32)
+            S = len(np.ascontiguousarray(users, np.uint32))
+            who_ptr = [_opt_ptr(keep_ul), None, None, None]
+        fb, keep_fb = self._feedback_lists(who, feedback or (None, None, None), S)
+        cand_ptr, cand_item = candidates
+        keep = (_pad(cand_ptr, np.int64) if cand_ptr is not None else None, _pad(cand_item if cand_item is not None else [], np.uint32))
+        if keep[0] is not None:
+            if len(keep[0]) != S + 1:
+                raise SvdfError(who + ": cand_ptr must have one entry more than there are sections")
+            if S and cand_item is not None and int(keep[0][S]) > len(keep[1]):
+                raise SvdfError(who + ": cand_item is shorter than cand_ptr says")
+        cand = [_opt_ptr(keep[0]), _opt_ptr(keep[1]) if cand_item is not None else None]
+        return S, who_ptr + list(fb), cand, (keep_ul, keep_fb, keep)
+
+    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None, lines=None, candidates=None):
         """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section.  feedback = (fb_ptr, fb_index, fb_value): the
         sections' feedback lists, for user-group trainers (svdf_rank_eval_positions_fb).  lines = (ul_ptr, ul_index, ul_value):
         the sections bring USER lines of several (id, value) entries and the trainer may have side tables (svdf_rank_eval_positions_lines,
-        DESIGN.md 6z); users is None then, and feedback= combines with it."""
+        DESIGN.md 6z); users is None then, and feedback= combines with it.  candidates = (cand_ptr, cand_item): section s ranks over its own
+        item list and its positives instead of the catalogue minus bans (svdf_rank_eval_positions_cand); it combines with
+        feedback= and lines=, and ban_ptr must be None."""
+        if candidates is not None:
+            S, who_ptr, cand, keep_c = self._cand_call("rank_eval", users, feedback, lines, candidates, ban_ptr)
+            pos_ptr, pos_item = _pad(pos_ptr, np.int64), _pad(pos_item, np.uint32)
+            if len(pos_ptr) != S + 1:
+                raise SvdfError("rank_eval: pos_ptr must have one entry more than users")
+            n = int(pos_ptr[-1]) if S else 0
+            position, tied = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+            ranked, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+            self._ok(self.lib.svdf_rank_eval_positions_cand(self.h, S, *who_ptr, pos_ptr, pos_item, cand[0], cand[1], position, tied, ranked, nan))
+            return position[:n], tied[:n], ranked[:S], nan[:S]
         if lines is not None:
             S, ul, keep_ul = self._user_lines("rank_eval", users, lines)
             users = np.zeros(S, np.uint32)
@@ -782,9 +821,17 @@ class Trainer:
                                                           _opt_ptr(ban_item), position, tied, ranked, nan))
         return position[:n], tied[:n], ranked[:S], nan[:S]
 
-    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None, lines=None):
+    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None, lines=None, candidates=None):
         """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict).
-        feedback, lines: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines)."""
+        feedback, lines, candidates: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines, svdf_rank_eval_cand)."""
+        if candidates is not None:
+            S, who_ptr, cand, keep_c = self._cand_call("rank_eval", users, feedback, lines, candidates, ban_ptr)
+            pos_ptr, pos_item = _pad(pos_ptr, np.int64), _pad(pos_item, np.uint32)
+            if len(pos_ptr) != S + 1:
+                raise SvdfError("rank_eval: pos_ptr must have one entry more than users")
+            m = RankMetrics()
+            self._ok(self.lib.svdf_rank_eval_cand(self.h, S, *who_ptr, pos_ptr, pos_item, cand[0], cand[1], len(at), _pad(list(at), np.int32), C.byref(m)))
+            return m.as_dict()
         if lines is not None:
             S, ul, keep_ul = self._user_lines("rank_eval", users, lines)
             users = np.zeros(S, np.uint32)
@@ -803,11 +850,22 @@ class Trainer:
                                                 _opt_ptr(ban_item), len(at), _pad(list(at), np.int32), C.byref(m)))
         return m.as_dict()
 
-    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None, feedback=None, lines=None):
+    def rank_topn(self, users, top_n, ban_ptr=None, ban_item=None, feedback=None, lines=None, candidates=None):
         """svdf_rank_topn: the top_n best items per section among all items that are not banned, higher score first and equal
         scores by ascending id; (items [S, top_n] int32, -1 beyond count; scores [S, top_n] float32; count [S]; nan [S]).  feedback = (fb_ptr,
         fb_index, fb_value): the sections' feedback lists, for user-group trainers (svdf_rank_topn_fb).  lines = (ul_ptr, ul_index,
-        ul_value): the sections bring USER lines and the trainer may have side tables (svdf_rank_topn_lines); users is None then."""
+        ul_value): the sections bring USER lines and the trainer may have side tables (svdf_rank_topn_lines); users is None then.
+        candidates = (cand_ptr, cand_item): the top_n best of each section's own item list (svdf_rank_topn_cand); ban_ptr must
+        be None."""
+        if candidates is not None:
+            S, who_ptr, cand, keep_c = self._cand_call("rank_topn", users, feedback, lines, candidates, ban_ptr)
+            top_n = int(top_n)
+            n = max(top_n, 1)
+            items, scores = np.full((max(S, 1), n), -1, np.int32), np.zeros((max(S, 1), n), np.float32)
+            count, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+            self._ok(self.lib.svdf_rank_topn_cand(self.h, S, *who_ptr, cand[0], cand[1], top_n, items.reshape(-1), scores.ctypes.data_as(C.c_void_p),
+                                                  count, nan))
+            return items[:S], scores[:S], count[:S], nan[:S]
         if lines is not None:
             S, ul, keep_ul = self._user_lines("rank_topn", users, lines)
             users = np.zeros(S, np.uint32)

@@ -391,6 +391,44 @@ int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_pt
         return 0;
     })
 }
+/* ... and over per-section candidate lists in place of the catalogue minus bans */
+int svdf_rank_eval_positions_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                                  const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                                  const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int *position_out, int *tied_out,
+                                  int *ranked_out, int *nan_out) {
+    SVDF_GUARD(-1, {
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_cand("rank_eval", num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, cand_ptr, cand_item, 0, position_out, tied_out,
+                        ranked_out, nullptr, nullptr, nullptr, nan_out);
+        return 0;
+    })
+}
+int svdf_rank_eval_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                        const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item,
+                        const int64_t *cand_ptr, const unsigned *cand_item, int num_at, const int *at, svdf_rank_metrics *out) {
+    SVDF_GUARD(-1, {
+        const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
+        std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_cand("rank_eval", num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, cand_ptr, cand_item, 0, position.data(),
+                        tied.data(), ranked.data(), nullptr, nullptr, nullptr, nan.data());
+        svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
+        return 0;
+    })
+}
+int svdf_rank_topn_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index, const float *ul_value,
+                        const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *cand_ptr, const unsigned *cand_item,
+                        int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
+    SVDF_GUARD(-1, {
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_cand("rank_topn", num_section, user, U, fb_ptr, fb_index, fb_value, nullptr, nullptr, cand_ptr, cand_item, top_n, nullptr, nullptr,
+                        nullptr, item_out, score_out, count_out, nan_out);
+        return 0;
+    })
+}
 
 /* ---- ISVDRanker ---- */
 svdf_ranker *svdf_ranker_create(uint8_t format_type, uint8_t active_type, uint8_t extend_type, uint8_t variant_type, int device) {

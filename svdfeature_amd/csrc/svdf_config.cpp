@@ -222,6 +222,7 @@ int64_t Engine::counter(int what) const {
     case 39: return n_rank_topn_sections_;   // sections listed by svdf_rank_topn (section 6x)
     case 40: return n_rank_fb_sections_;     // of those two, the sections ranked with a row built from a feedback list (section 6y)
     case 41: return n_rank_line_sections_;   // of those two, the sections the _lines calls ranked with a row built from a USER line (section 6z)
+    case 42: return n_rank_cand_sections_;   // of those two, the sections the _cand calls ranked over a candidate list (section 6aa)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -313,6 +314,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target")) { check(value >= 1, "window_per_target must be positive"); wseq_per_target_ = (int)value; return 0; }
     if (!strcmp(name, "rank_eval_budget")) { check(value >= 1, "rank_eval_budget must be positive"); rank_eval_budget_ = value; return 0; }
+    if (!strcmp(name, "rank_cand_form")) { check(value >= 0 && value <= 2, "rank_cand_form must be 0 (measured choice), 1 (one lane per pair) or 2 (staged)"); rank_cand_form_ = value; return 0; }
     if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }
     if (!strcmp(name, "window_slots")) { window_slots_ = value != 0; return 0; }
     if (!strcmp(name, "window_groups")) { check(value >= 0 && value <= 2, "window_groups must be 0 (auto), 1 or 2"); window_groups_ = (int)value; return 0; }

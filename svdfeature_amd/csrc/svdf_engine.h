@@ -487,6 +487,11 @@ class Engine {
                        int *nan_out, const RankLines *lines = nullptr);
     void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                        const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
+    // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md
+    // section 6aa).  Exactly one of user / U.ptr is set; top_n == 0: positions (pos_*, position_out, tied_out, ranked_out), else the top_n lists
+    void rank_cand(const char *who, long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                   const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int top_n, int *position_out,
+                   int *tied_out, int *ranked_out, int *item_out, float *score_out, int *count_out, int *nan_out);
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -950,6 +955,10 @@ class Engine {
     DevBuf<float> rk_rows_;            // a piece's effective user rows, [nsec][pitch]
     int64_t n_rank_line_sections_ = 0; // counter 41: sections the _lines calls ranked with a row built from a USER line
     DevBuf<float> rk_items_;           // a _lines call's prepared item side: [num_item][pitch] rows, then [num_item] biases
+    int64_t n_rank_cand_sections_ = 0; // counter 42: sections the _cand calls ranked over a candidate list
+    long rank_cand_form_ = 0;          // knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 the staged score kernel
+    DevBuf<int> ca_in_, ca_out_;       // a _cand piece's upload (the lists, the tile table) and its results
+    DevBuf<float> ca_score_;           // ... and the scores of its pairs
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

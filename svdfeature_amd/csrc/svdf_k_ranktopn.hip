@@ -12,54 +12,14 @@
 #include <algorithm>
 
 #include "svdf_kernels.h"
+#include "svdf_k_rankkey.h"
 #include "svdf_k_rankscore.h"
 
 namespace svdf {
 
 constexpr int TN_TS = 64;                    // sections of a tile
 constexpr int TN_SB = 4;                     // sections a lane scores at once (register block)
-constexpr int TN_SORT = RANK_TOPN_MAX_CAP;   // keys of a wave's sort buffer
-typedef unsigned long long tn_key_t;         // 0: no key (smaller than every key: -inf maps to word 0x007fffff, NaNs are never keyed)
-
-__device__ __forceinline__ tn_key_t tn_key(float s, int id) {
-    unsigned b = __float_as_uint(s);
-    if (b == 0x80000000u) b = 0u;   // -0 == +0
-    const unsigned w = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((tn_key_t)w << 32) | (tn_key_t)(~(unsigned)id);
-}
-__device__ __forceinline__ float tn_key_score(tn_key_t key) {
-    const unsigned w = (unsigned)(key >> 32);
-    return __uint_as_float((w & 0x80000000u) ? (w & 0x7fffffffu) : ~w);
-}
-__device__ __forceinline__ int tn_key_id(tn_key_t key) { return (int)(~(unsigned)key); }
-
-// the lanes of ONE wave hand LDS values to each other: LDS operations of a wave complete in order; this keeps the compiler from moving them
-__device__ __forceinline__ void tn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// buf[0 .. cnt) (cnt <= TN_SORT, one wave's LDS) sorted descending by a bitonic network over the next power of two (zeros fill the rest);
-// returns how many keys stay, min(cnt, top_n), and raises thr to the smallest of them once there are top_n
-__device__ __forceinline__ int tn_sort_keep(tn_key_t *buf, int cnt, int top_n, int lane, tn_key_t &thr) {
-    int n2 = 64;
-    while (n2 < cnt) n2 <<= 1;
-    for (int i = cnt + lane; i < n2; i += 64) buf[i] = 0ull;
-    tn_wave_sync();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = lane; t < (n2 >> 1); t += 64) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool desc = (lo & size) == 0;
-                const tn_key_t x = buf[lo], y = buf[hi];
-                if ((x < y) == desc) { buf[lo] = y; buf[hi] = x; }
-            }
-            tn_wave_sync();
-        }
-    const int keep = cnt < top_n ? cnt : top_n;
-    if (cnt >= top_n) thr = buf[top_n - 1];
-    return keep;
-}
+// tn_key_t, tn_key, tn_key_score, tn_key_id, tn_wave_sync, tn_sort_keep and TN_SORT: svdf_k_rankkey.h
 
 // What the wave that owns a list does with one step's scores (IB candidates per lane): the keys of ranked candidates that beat the
 // threshold are appended through a ballot prefix; a list without room for a whole step is first cut to its top_n largest.  `list` is the

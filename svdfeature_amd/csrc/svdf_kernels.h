@@ -340,5 +340,33 @@ void launch_rank_live_rows(const DevParams &P, const RankLiveRowsDev &D, hipStre
 // the prepared item side of a trainer with a feature_item table: item_rows[i] = W_item[i] * 1 + its children's rows * cval, item_bias[i] alike
 void launch_rank_live_items(const DevParams &P, float *item_rows, float *item_bias, hipStream_t st);   // one launch
 
+// ---- ranking over per-section candidate lists on the live model (svdf_k_rankcand.hip): one piece of whole sections.
+// Pair q of the piece is (section, cand_id[q]); a section's pairs are consecutive, its ids distinct and ascending.  Only the listed pairs
+// are scored.  Every index is local to the piece and has been validated on the host.
+struct RankCandDev {
+    int nsec;                        // sections of the piece
+    const unsigned *sec_user;        // [nsec]
+    const float *user_rows;          // nullptr: W_user rows; else the [nsec][pitch] workspace of effective user rows (RankLiveRowsDev)
+    const float *item_rows = nullptr, *item_bias = nullptr;   // nullptr: W_item / i_bias; else the prepared item matrix and biases (launch_rank_live_items)
+    const int *sec_q0;               // [nsec + 1] pairs of section s: [sec_q0[s], sec_q0[s + 1])
+    const int *cand_id;              // [npair]
+    float *cand_score;               // [npair] written by the score kernel
+    int ntile;
+    const int *tile_q0, *tile_sec;   // [ntile + 1], [ntile]: at most 64 consecutive pairs of ONE section (svdf_rankcand_lists.h)
+    // positions (top_n == 0): positive p of section s, p in [sec_p0[s], sec_p0[s + 1]), is pair pos_at[p]
+    long npos = 0;
+    const int *sec_p0 = nullptr, *pos_at = nullptr;
+    int *position_out = nullptr, *tied_out = nullptr;   // [npos] strictly higher + tied with a smaller id; tied
+    int *nan_out;                    // [nsec] 1: a pair of the section scored NaN
+    // top-N (top_n >= 1): section 6x's layout
+    int top_n = 0;
+    int *item_out = nullptr;         // [nsec][top_n] ids in rank order, -1 beyond count_out
+    float *score_out = nullptr;      // [nsec][top_n] their scores, 0 beyond count_out
+    int *count_out = nullptr;        // [nsec] entries listed; 0 for a section with a NaN among its pairs
+};
+// form: 0 the measured choice per row width, 1 one lane per pair, 2 a wave per tile staging the gathered rows in LDS (pitch <= 256 only)
+int rank_cand_form(const DevParams &P, int form);   // the form a piece's score kernel takes: 1 or 2
+void launch_rank_cand(const DevParams &P, const RankCandDev &D, int form, hipStream_t st);   // the scores, then the count or the selection: two launches
+
 }  // namespace svdf
 #endif
