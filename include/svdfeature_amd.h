@@ -755,6 +755,52 @@ int svdf_rank_topn_cand(svdf_trainer *t, long num_section, const unsigned *user,
                         const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *cand_ptr, const unsigned *cand_item,
                         int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
 
+/* ---- the positions calls against negatives the DEVICE draws: sampled-negative evaluation -- held-out positives
+ * ranked among num_neg items the user has not interacted with -- without candidate lists on the host.  The caller hands over what the
+ * full-catalogue calls take (users or USER lines, feedback lists, positives, bans = the users' training items) and two scalars.
+ * THE RULE, pure 64-bit unsigned integer arithmetic, wrapping mod 2^64:
+ *   G         = 0x9E3779B97F4A7C15
+ *   mix(z)    : z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   stream_s  = mix(seed + (s + 1) * G)                       s: the section's index IN THE CALL (never in a piece of it)
+ *   draw(s,t) = (uint32)(((mix(stream_s + (t + 1) * G) >> 32) * (uint64)num_item) >> 32)       t = 0, 1, 2, ...
+ * -- splitmix64 seeded per section from a splitmix64 of the seed, mapped onto an id by multiply-high; the bias of at most num_item / 2^32
+ * is accepted.  excluded_s is the distinct ids of the section's bans together with its positives.  THE NEGATIVES of section s are the
+ * first num_neg ids of the sequence draw(s, 0), draw(s, 1), ... that are not in excluded_s and have not occurred earlier in the sequence;
+ * they keep the order of the sequence.  THE RANKED SET is the section's positives plus its negatives; over it everything is
+ * svdf_rank_eval_positions_cand's: position, tied, ties by ascending id, +0 == -0, nan_out set only by a RANKED candidate, the score of a
+ * pair the twin's bit for bit; ranked_out[s] = npos_s + num_neg.  A section without positives is not drawn or scored: ranked_out[s] =
+ * num_neg, its neg_out row is -1, its ids are still validated.
+ * PINNED VECTORS (seed 12345, num_item 1200): stream_0 = 0x22118258a9d111a0, stream_7 = 0x6e7411b06820371c;
+ *   section 0, nothing excluded, draws t = 0 .. 5:  18, 601, 213, 846, 111, 362
+ *   section 7, excluded {25, 303}, draws t = 0 .. 7: 1196, 25, 1196, 303, 504, 615, 588, 726 (the third repeats the first);
+ *              its num_neg = 5 negatives are 1196, 504, 615, 588, 726, after 8 draws.
+ * WHO THE SECTION IS: exactly the _cand calls' rule -- one of `user` / `ul_ptr`, fb_ptr on user-group trainers, side tables only with
+ * lines; the configurations the twins refuse are refused in their words.  BANS AND POSITIVES are validated as svdf_rank_eval_positions
+ * validates them (range, the shape of ban_ptr, "each pos sample item can not occur in baned sample list", a repeated positive); ban_ptr ==
+ * NULL: no bans.  REFUSED besides, on the host, before any device work and before "needs a GPU":
+ *   num_neg outside 1 .. 4096                            "rank_eval: num_neg must be between 1 and 4096"
+ *   a section WITH positives that leaves avail = num_item - |excluded_s| ids with avail < 2 * num_neg or avail * 64 < num_item
+ *       "rank_eval: section S leaves A items to draw NUM_NEG negatives from NUM_ITEM; list its candidates instead (svdf_rank_eval_positions_cand)"
+ * -- the two conditions make every draw succeed with probability >= 1 / 128, so a section expects at most 128 * num_neg draws and no
+ * input makes the kernel run long.
+ * neg_out [num_section][num_neg], or NULL: the negatives in draw order.  num_section == 0 and a call without any positive launch nothing.
+ * Pieces of whole sections within the knob `rank_eval_budget` (entries: pairs, positives, excluded ids, feedback and line entries, one per
+ * section); no result depends on a knob or on the pieces.  Per piece one upload of the small tables, the positives, the excluded lists
+ * and the rows' lists; the candidate ids are a device workspace that k_rank_negs_draw (a wave per section) fills.  An allocation failure
+ * names the size.  Counter 43 counts the sections ranked against drawn negatives; they count under 38, and under 40 / 41 as the twins' do,
+ * not under 42.  The entry points above do not change.
+ * svdf_rank_negatives is the rule on the host -- no GPU, no handle: the same validation and refusals, neg_out as above. */
+int svdf_rank_negatives(long num_section, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                        long num_item, int num_neg, uint64_t seed, int *neg_out);
+int svdf_rank_eval_positions_sampled(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                                     const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                                     const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg,
+                                     uint64_t seed, int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out);
+int svdf_rank_eval_sampled(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                           const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                           const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed, int num_at,
+                           const int *at, svdf_rank_metrics *out);
+
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator
  * by n draws without calling rand() n times (jump-ahead of glibc's additive-feedback table).  Host functions, no GPU needed;

@@ -125,6 +125,39 @@ def rank_metrics(sec_ptr, position, ranked=None, nan=None, at=(1, 5, 10, 100)):
     return m.as_dict()
 
 
+def rank_negatives(num_item, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed):
+    """svdf_rank_negatives: the negatives Trainer.rank_positions(..., sampled=(num_neg, seed)) ranks each section's positives against, by the
+    published rule (include/svdfeature_amd.h): [S, num_neg] int32 in draw order, a row of -1 for a section without positives.
+    A host function: no GPU, no handle.  ban_ptr = None: no bans."""
+    lib = load_library()
+    S = len(_pad(pos_ptr, np.int64)) - 1
+    pos_ptr, pos_item, ban_ptr, ban_item = _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item)
+    n = max(int(num_neg), 1)
+    neg = np.full((max(S, 1), n), -1, np.int32)
+    if lib.svdf_rank_negatives(S, pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item), int(num_item), int(num_neg),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, neg.reshape(-1)) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return neg[:S]
+
+
+def _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item):
+    """the positives and bans of S sections as the arrays the sampled calls take (ban_ptr = None: two None); the library reads as many ids
+    as the pointers say, so arrays shorter than that are refused here"""
+    pos_ptr, given = _pad(pos_ptr, np.int64), len(np.atleast_1d(pos_item))
+    if len(pos_ptr) != S + 1:
+        raise SvdfError("rank_eval: pos_ptr must have one entry more than users")
+    if S and int(pos_ptr.max()) > given:
+        raise SvdfError("rank_eval: pos_item is shorter than pos_ptr says")
+    if ban_ptr is None:
+        return pos_ptr, _pad(pos_item, np.uint32), None, None
+    ban_ptr, given = _pad(ban_ptr, np.int64), len(np.atleast_1d(ban_item)) if ban_item is not None else 0
+    if len(ban_ptr) != S + 1:
+        raise SvdfError("rank_eval: ban_ptr must have one entry more than users")
+    if S and int(ban_ptr.max()) > given:
+        raise SvdfError("rank_eval: ban_item is shorter than ban_ptr says")
+    return pos_ptr, _pad(pos_item, np.uint32), ban_ptr, _pad(ban_item if ban_item is not None else [], np.uint32)
+
+
 def load_library():
     """dlopen libsvdfeature_amd.so and declare every prototype of include/svdfeature_amd.h."""
     global _lib
@@ -257,6 +290,10 @@ def load_library():
     lib.svdf_rank_eval_positions_cand.argtypes = [P, C.c_long] + _cand + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_cand.argtypes = [P, C.c_long] + _cand + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_topn_cand.argtypes = [P, C.c_long] + _cand + [C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    _lists = [_i64p, _u32p, C.c_void_p, C.c_void_p]   # pos_ptr, pos_item, ban_ptr, ban_item
+    lib.svdf_rank_negatives.argtypes = [C.c_long] + _lists + [C.c_long, C.c_int, C.c_uint64, _i32p]
+    lib.svdf_rank_eval_positions_sampled.argtypes = [P, C.c_long] + _cand + _lists + [C.c_int, C.c_uint64, _i32p, _i32p, _i32p, _i32p, C.c_void_p]
+    lib.svdf_rank_eval_sampled.argtypes = [P, C.c_long] + _cand + _lists + [C.c_int, C.c_uint64, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -784,13 +821,46 @@ class Trainer:
         cand = [_opt_ptr(keep[0]), _opt_ptr(keep[1]) if cand_item is not None else None]
         return S, who_ptr + list(fb), cand, (keep_ul, keep_fb, keep)
 
-    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None, lines=None, candidates=None):
+    def _sampled_call(self, users, feedback, lines, candidates, sampled, pos_ptr, pos_item, ban_ptr, ban_item):
+        """sampled = (num_neg, seed) -> (S, the arguments of the svdf_rank_eval*_sampled calls from `user` to `seed`, the arrays they point into)"""
+        who = "rank_eval"
+        if candidates is not None:
+            raise SvdfError(who + ": candidates and sampled exclude each other")
+        num_neg, seed = sampled
+        if lines is not None:
+            S, ul, keep_ul = self._user_lines(who, users, lines)
+            who_ptr = [None] + list(ul)
+        else:
+            keep_ul = _pad(np.ascontiguousarray(users, np.uint32), np.uint32)
+            S = len(np.ascontiguousarray(users, np.uint32))
+            who_ptr = [_opt_ptr(keep_ul), None, None, None]
+        fb, keep_fb = self._feedback_lists(who, feedback or (None, None, None), S)
+        pos_ptr, pos_item, ban_ptr, ban_item = _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item)
+        args = who_ptr + list(fb) + [pos_ptr, pos_item, _opt_ptr(ban_ptr), _opt_ptr(ban_item), int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF]
+        return S, args, (keep_ul, keep_fb, pos_ptr, pos_item, ban_ptr, ban_item)
+
+    def rank_positions(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, feedback=None, lines=None, candidates=None, sampled=None,
+                       return_negatives=False):
         """svdf_rank_eval_positions: (position, tied) per positive, (ranked, nan) per section.  feedback = (fb_ptr, fb_index, fb_value): the
         sections' feedback lists, for user-group trainers (svdf_rank_eval_positions_fb).  lines = (ul_ptr, ul_index, ul_value):
         the sections bring USER lines of several (id, value) entries and the trainer may have side tables (svdf_rank_eval_positions_lines,
         DESIGN.md 6z); users is None then, and feedback= combines with it.  candidates = (cand_ptr, cand_item): section s ranks over its own
         item list and its positives instead of the catalogue minus bans (svdf_rank_eval_positions_cand); it combines with
-        feedback= and lines=, and ban_ptr must be None."""
+        feedback= and lines=, and ban_ptr must be None.  sampled = (num_neg, seed): section s ranks its positives against num_neg negatives
+        the device draws by the published rule from (seed, s, the section's bans and positives) (svdf_rank_eval_positions_sampled, DESIGN.md
+        6ab); it combines with feedback= and lines=, never with candidates=; return_negatives=True returns the drawn ids as a fifth array,
+        [S, num_neg] int32 in draw order (-1 for a section without positives)."""
+        if sampled is not None:
+            S, args, keep_s = self._sampled_call(users, feedback, lines, candidates, sampled, pos_ptr, pos_item, ban_ptr, ban_item)
+            n = int(keep_s[2][-1]) if S else 0
+            position, tied = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+            ranked, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+            neg = np.full((max(S, 1), max(args[-2], 1)), -1, np.int32) if return_negatives else None
+            self._ok(self.lib.svdf_rank_eval_positions_sampled(self.h, S, *args, position, tied, ranked, nan, _opt_ptr(neg)))
+            out = (position[:n], tied[:n], ranked[:S], nan[:S])
+            return out + (neg[:S],) if return_negatives else out
+        if return_negatives:
+            raise SvdfError("rank_eval: return_negatives needs sampled=(num_neg, seed)")
         if candidates is not None:
             S, who_ptr, cand, keep_c = self._cand_call("rank_eval", users, feedback, lines, candidates, ban_ptr)
             pos_ptr, pos_item = _pad(pos_ptr, np.int64), _pad(pos_item, np.uint32)
@@ -821,9 +891,16 @@ class Trainer:
                                                           _opt_ptr(ban_item), position, tied, ranked, nan))
         return position[:n], tied[:n], ranked[:S], nan[:S]
 
-    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None, lines=None, candidates=None):
+    def rank_eval(self, users, pos_ptr, pos_item, ban_ptr=None, ban_item=None, at=(1, 5, 10, 100), feedback=None, lines=None, candidates=None,
+                  sampled=None):
         """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict).
-        feedback, lines, candidates: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines, svdf_rank_eval_cand)."""
+        feedback, lines, candidates, sampled: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines, svdf_rank_eval_cand,
+        svdf_rank_eval_sampled)."""
+        if sampled is not None:
+            S, args, keep_s = self._sampled_call(users, feedback, lines, candidates, sampled, pos_ptr, pos_item, ban_ptr, ban_item)
+            m = RankMetrics()
+            self._ok(self.lib.svdf_rank_eval_sampled(self.h, S, *args, len(at), _pad(list(at), np.int32), C.byref(m)))
+            return m.as_dict()
         if candidates is not None:
             S, who_ptr, cand, keep_c = self._cand_call("rank_eval", users, feedback, lines, candidates, ban_ptr)
             pos_ptr, pos_item = _pad(pos_ptr, np.int64), _pad(pos_item, np.uint32)

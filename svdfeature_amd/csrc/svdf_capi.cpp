@@ -10,6 +10,7 @@
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
 #include "svdf_ranklines_lists.h"
+#include "svdf_ranknegs_lists.h"
 #include "svdf_wseq_rule.h"
 
 namespace svdf {
@@ -426,6 +427,39 @@ int svdf_rank_topn_cand(svdf_trainer *t, long num_section, const unsigned *user,
         U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
         t->e->rank_cand("rank_topn", num_section, user, U, fb_ptr, fb_index, fb_value, nullptr, nullptr, cand_ptr, cand_item, top_n, nullptr, nullptr,
                         nullptr, item_out, score_out, count_out, nan_out);
+        return 0;
+    })
+}
+
+/* ... and against negatives drawn on the device from (seed, section, what the section excludes) */
+int svdf_rank_negatives(long num_section, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                        long num_item, int num_neg, uint64_t seed, int *neg_out) {
+    SVDF_GUARD(-1, { svdf::rank_negs_host(num_section, pos_ptr, pos_item, ban_ptr, ban_item, num_item, num_neg, seed, neg_out); return 0; })
+}
+int svdf_rank_eval_positions_sampled(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                                     const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                                     const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg,
+                                     uint64_t seed, int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out) {
+    SVDF_GUARD(-1, {
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_negs(num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position_out, tied_out,
+                        ranked_out, nan_out, neg_out);
+        return 0;
+    })
+}
+int svdf_rank_eval_sampled(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
+                           const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+                           const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed, int num_at,
+                           const int *at, svdf_rank_metrics *out) {
+    SVDF_GUARD(-1, {
+        const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
+        std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
+        svdf::RankLines U;
+        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        t->e->rank_negs(num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position.data(),
+                        tied.data(), ranked.data(), nan.data(), nullptr);
+        svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
         return 0;
     })
 }

@@ -492,6 +492,11 @@ class Engine {
     void rank_cand(const char *who, long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                    const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int top_n, int *position_out,
                    int *tied_out, int *ranked_out, int *item_out, float *score_out, int *count_out, int *nan_out);
+    // positions over the positives and num_neg negatives the device draws per section from (seed, section, what the section excludes)
+    // (svdf_ranknegs.cpp, svdf_k_ranknegs.hip).  Exactly one of user / U.ptr is set; neg_out may be nullptr
+    void rank_negs(long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+                   const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed,
+                   int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out);
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -959,6 +964,8 @@ class Engine {
     long rank_cand_form_ = 0;          // knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 the staged score kernel
     DevBuf<int> ca_in_, ca_out_;       // a _cand piece's upload (the lists, the tile table) and its results
     DevBuf<float> ca_score_;           // ... and the scores of its pairs
+    int64_t n_rank_negs_sections_ = 0; // counter 43: sections ranked against negatives drawn on the device
+    DevBuf<int> ng_id_, ng_neg_;       // a sampled piece's cand_id, filled by k_rank_negs_draw, and its neg_out rows where they are asked for
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

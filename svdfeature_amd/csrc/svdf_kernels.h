@@ -368,5 +368,25 @@ struct RankCandDev {
 int rank_cand_form(const DevParams &P, int form);   // the form a piece's score kernel takes: 1 or 2
 void launch_rank_cand(const DevParams &P, const RankCandDev &D, int form, hipStream_t st);   // the scores, then the count or the selection: two launches
 
+// ---- the negatives of sampled-negative ranking, drawn on the device (svdf_k_ranknegs.hip): one piece of whole
+// sections.  A section with positives has npos + num_neg pairs in cand_id, [sec_q0[s], sec_q0[s + 1]): its positives, then its negatives in
+// draw order; a section without positives has none.  Every index is local to the piece and has been validated on the host.
+struct RankNegsDev {
+    int nsec;                  // sections of the piece
+    long sec0;                 // the index IN THE CALL of the piece's first section: the stream of section s is that of sec0 + s
+    uint64_t seed;
+    unsigned num_item;
+    int num_neg;               // 1 .. RANK_NEGS_MAX
+    int slots, shift;          // the table of seen ids in LDS: rank_negs_table(num_neg) slots, shift = 32 - log2(slots)
+    const int *sec_q0;         // [nsec + 1]
+    const int *sec_p0;         // [nsec + 1] positives of section s: pos_id[sec_p0[s] .. sec_p0[s + 1])
+    const int *pos_id;
+    const int *ex_p0;          // [nsec + 1] excluded ids of section s (bans and positives): ex_id[ex_p0[s] .. ex_p0[s + 1]), distinct, ascending
+    const int *ex_id;
+    int *cand_id;              // [npair] written here, read by launch_rank_cand
+    int *neg_out;              // nullptr, or [nsec][num_neg]: the negatives in draw order, -1 for a section without positives
+};
+void launch_rank_negs(const RankNegsDev &D, hipStream_t st);   // one launch, a wave per section
+
 }  // namespace svdf
 #endif
