@@ -34,6 +34,7 @@ extern "C" {
 typedef struct svdf_trainer svdf_trainer; /* opaque: one ISVDTrainer instance */
 typedef struct svdf_dataset svdf_dataset; /* opaque: a scheduled, HBM-resident training set */
 typedef struct svdf_ranker svdf_ranker;   /* opaque: one ISVDRanker instance */
+typedef struct svdf_pair_source svdf_pair_source; /* opaque: positives resident in HBM, the source of rank-pair passes */
 
 /* ---- library ---- */
 const char *svdf_version(void);
@@ -364,7 +365,10 @@ int svdf_synchronize(svdf_trainer *t);
  * DESIGN.md 6u; the windows keep counting where they do without the knob),
  * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too),
  * 38 sections ranked by svdf_rank_eval_positions, 39 sections listed by svdf_rank_topn,
- * 40 of the sections under 38 / 39, those ranked with a user row built from a feedback list (the _fb calls on user-group trainers) */
+ * 40 of the sections under 38 / 39, those ranked with a user row built from a feedback list (the _fb calls on user-group trainers),
+ * 41 .. 43 see the _lines, _cand and _sampled calls below,
+ * 44 / 45 passes built from a pair source (svdf_dataset_from_pair_source) without the pair columns leaving HBM / through
+ * svdf_dataset_from_pairs' own builder on the columns copied back */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -800,6 +804,61 @@ int svdf_rank_eval_sampled(svdf_trainer *t, long num_section, const unsigned *us
                            const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                            const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed, int num_at,
                            const int *at, svdf_rank_metrics *out);
+
+/* ---- passes of rank pairs from POSITIVES ONLY, the negatives drawn on the device.  Pairwise training on implicit
+ * feedback needs a fresh negative per positive every round; svdf_dataset_from_pairs takes three finished columns, so its caller draws and
+ * uploads them every round.  A pair source keeps the positives in HBM -- one upload at creation, nothing per pass -- and a pass is two scalars.
+ * THE RULE, pure 64-bit unsigned integer arithmetic, wrapping mod 2^64; G, mix and the map onto an id are the sampled calls' above:
+ *   a source has rows r = 0 .. n-1 of (user_r, pos_r), in the caller's order; P(u) = the distinct items of ALL rows of user u
+ *   a pass has num_neg = m negatives per row: pair q = r * m + j (j = 0 .. m-1) is (user_r, pos_r, neg_q) -- the m pairs of a row are
+ *   adjacent, rows stay in source order
+ *   SALT      = 0x70616972736E6567      (ASCII "pairsneg": a pass and a sampled evaluation with one seed draw from different streams)
+ *   stream_q  = mix((seed ^ SALT) + (q + 1) * G)
+ *   draw(q,t) = (uint32)(((mix(stream_q + (t + 1) * G) >> 32) * (uint64)num_item) >> 32)       t = 0, 1, 2, ...
+ *   neg_q     = the first of draw(q, 0), draw(q, 1), ... that is not in P(user_r)
+ * The m negatives of a row are independent (repeats among them are allowed); pos != neg holds by construction.  AT MOST T = 4096 DRAWS per
+ * pair: a pair that exhausts them fails the call ("pair_source: pair Q found no negative in 4096 draws") and never loops further.  A source
+ * is refused when a user with rows has 64 * (num_item - |P(u)|) < num_item; every source that remains accepts each draw with probability
+ * >= 1 / 64, so a pair exceeds T with probability <= (63 / 64)^4096 = exp(4096 * ln(63 / 64)) < exp(-64.5) < 1e-28.
+ * PINNED VECTORS (seed 12345, num_item 1200): stream_0 = 0x6df61f806828913e, stream_7 = 0x0cee3333c9e3d7d8;
+ *   pair 0, draws t = 0 .. 5: 607, 1083, 476, 1017, 945, 510;   pair 7, draws t = 0 .. 7: 496, 554, 32, 921, 199, 15, 1103, 184
+ *   rows (user, pos) = (4, 10), (4, 700), (9, 10): num_neg 1 gives the negatives 607, 549, 766; num_neg 2 gives 607, 549, 766, 1010, 64, 448
+ *   a pair 0 whose user has 607 among its positives takes 1083, its second draw.
+ * REFUSED on the host, before any device work and before "needs a GPU" (a host-only handle creates sources and reaches every message):
+ *   at creation   n < 1                                     "pair_source: a source needs at least one row (n >= 1)"
+ *                 an id out of range, row by row            "user feature index exceed bound" / "item feature index exceed bound"
+ *                 the density rule                          "pair_source: user U has D distinct positive items of NUM_ITEM: fewer than 1 item
+ *                                                            in 64 is left to draw a negative from; draw its negatives yourself (svdf_dataset_from_pairs)"
+ *                 before init_trainer                       "pair_source: call init_model / load_model and init_trainer first"
+ *   per pass      a source of another trainer (or of one that is gone)   "pair_source: the source was created on another trainer"
+ *                 num_neg outside 1 .. 256                  "pair_source: num_neg must be between 1 and 256"
+ *                 n * num_neg >= 2^31 - 16                  "pair_source: n * num_neg must stay below 2^31 - 16"
+ * -- and what svdf_dataset_from_pairs refuses about the trainer, in its words.
+ * svdf_dataset_from_pair_source draws the pass's three columns (n * num_neg entries each) in HBM with one launch of k_pair_draw, a lane
+ * per pair, and returns the data set svdf_dataset_from_pairs returns for those columns -- the same kind, the same schedule or windows, the
+ * same trained bits.  The columns stay in HBM (counter 44) where that builder has a form that starts from device columns: under `amd:step =
+ * minibatch` on one GPU with the device window builder and window_pair_sub = 0 (the window sequence, built as section 6v builds it), and on
+ * the exact pass where it schedules on the device and the expanded user column is not user-grouped (user-run units are built on the host).
+ * "User-grouped" is svdf_dataset_from_pairs' own pretest, at least half of the adjacent pairs sharing their user; the num_neg pairs of a row
+ * are adjacent, so with num_neg >= 2 the expanded column always is.  With the default knobs the exact pass therefore stays in HBM for
+ * num_neg = 1 on a source that is not user-grouped, and only there; num_neg >= 2 stays in HBM on the exact pass only with pair_units = 0.
+ * Everywhere else -- `amd:step = auto`, amd:gpus > 1, relaxed ids, side tables, lazy decay, wide rows, window_pair_sub > 0, user-grouped
+ * orders, user-group trainers -- the columns are copied back and svdf_dataset_from_pairs builds from them (counter 45).  No result
+ * depends on the route.  An allocation failure names the size.
+ * svdf_pair_source_draw copies the negative column the device draws to neg_out[n * num_neg]; svdf_pair_negatives is the rule on the host --
+ * no GPU, no handle -- with the same validation.  svdf_pair_source_destroy is also valid after svdf_destroy of the source's trainer; data
+ * sets built from a source do not refer to it.  No older entry point changes.
+ * MEASURED (one MI355X, 100 K users x 10 K items, 20 M shuffled positives, num_factor 128, num_neg 1; medians of five rounds of build +
+ * train + synchronize + destroy; profiles/r33_pair_source.md): 0.280 s per round on the exact pass, 0.149 s under `amd:step = minibatch`,
+ * against 2.52 s / 2.34 s for svdf_pair_negatives on the host followed by svdf_dataset_from_pairs, whose draw alone takes 2.1 .. 2.3 s;
+ * k_pair_draw takes 1.4 ms.  On columns that are drawn already the exact pass gains nothing from the source.  Not measured: num_neg > 1,
+ * user-grouped orders, the fallback configurations. */
+svdf_pair_source *svdf_pair_source_create(svdf_trainer *t, long n, const unsigned *user, const unsigned *pos_item);
+void svdf_pair_source_destroy(svdf_pair_source *s);
+svdf_dataset *svdf_dataset_from_pair_source(svdf_trainer *t, svdf_pair_source *s, int num_neg, uint64_t seed);
+int svdf_pair_source_draw(svdf_trainer *t, svdf_pair_source *s, int num_neg, uint64_t seed, unsigned *neg_out);
+int svdf_pair_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, uint64_t seed,
+                        unsigned *neg_out);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

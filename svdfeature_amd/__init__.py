@@ -140,6 +140,31 @@ def rank_negatives(num_item, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed
     return neg[:S]
 
 
+def _pair_rows(user, pos_item):
+    """the rows of a pair source as the two arrays the library reads n entries of"""
+    user, pos_item = np.atleast_1d(user), np.atleast_1d(pos_item)
+    if len(user) != len(pos_item):
+        raise SvdfError("pair_source: user and pos_item must have one entry per row")
+    return len(user), _pad(user, np.uint32), _pad(pos_item, np.uint32)
+
+
+def _pass_size(n, num_neg):
+    """entries of a pass's negative column (the library refuses what is out of range before it writes)"""
+    return n * int(num_neg) if 1 <= int(num_neg) <= 256 and n * int(num_neg) < (1 << 31) - 16 else 0
+
+
+def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed):
+    """svdf_pair_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed) trains a source of these rows against, by the
+    published rule (include/svdfeature_amd.h): uint32[n * num_neg], pair r * num_neg + j belongs to row r.  A host function:
+    no GPU, no handle."""
+    lib = load_library()
+    n, user, pos_item = _pair_rows(user, pos_item)
+    neg = np.zeros(max(_pass_size(n, num_neg), 1), np.uint32)
+    if lib.svdf_pair_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF, neg) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return neg[:n * int(num_neg)]
+
+
 def _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item):
     """the positives and bans of S sections as the arrays the sampled calls take (ban_ptr = None: two None); the library reads as many ids
     as the pointers say, so arrays shorter than that are refused here"""
@@ -294,6 +319,13 @@ def load_library():
     lib.svdf_rank_negatives.argtypes = [C.c_long] + _lists + [C.c_long, C.c_int, C.c_uint64, _i32p]
     lib.svdf_rank_eval_positions_sampled.argtypes = [P, C.c_long] + _cand + _lists + [C.c_int, C.c_uint64, _i32p, _i32p, _i32p, _i32p, C.c_void_p]
     lib.svdf_rank_eval_sampled.argtypes = [P, C.c_long] + _cand + _lists + [C.c_int, C.c_uint64, C.c_int, _i32p, C.POINTER(RankMetrics)]
+    lib.svdf_pair_source_create.restype = P
+    lib.svdf_pair_source_create.argtypes = [P, C.c_long, _u32p, _u32p]
+    lib.svdf_pair_source_destroy.argtypes = [P]
+    lib.svdf_dataset_from_pair_source.restype = P
+    lib.svdf_dataset_from_pair_source.argtypes = [P, P, C.c_int, C.c_uint64]
+    lib.svdf_pair_source_draw.argtypes = [P, P, C.c_int, C.c_uint64, _u32p]
+    lib.svdf_pair_negatives.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, C.c_int, C.c_uint64, _u32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -421,6 +453,25 @@ class Dataset:
     def close(self):
         if self.h:
             self.trainer.lib.svdf_dataset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PairSource:
+    """Positives (user, item) resident in HBM, the source of rank-pair passes whose negatives the device draws (svdf_pair_source)."""
+
+    def __init__(self, trainer, handle, num_row):
+        self.trainer, self.lib, self.h, self.num_row = trainer, trainer.lib, handle, num_row
+
+    def close(self):
+        """safe after the trainer's close; data sets built from the source stay valid"""
+        if self.h:
+            self.lib.svdf_pair_source_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -703,6 +754,29 @@ class Trainer:
         if not h:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return Dataset(self, h)
+
+    # -- passes of rank pairs from positives only (svdf_pair_source_*)
+    def pair_source(self, user, pos_item):
+        """The positives (user, item) of pairwise training, uploaded once: see svdf_pair_source_create."""
+        n, user, pos_item = _pair_rows(user, pos_item)
+        h = self.lib.svdf_pair_source_create(self.h, n, user, pos_item)
+        if not h:
+            raise SvdfError(self.lib.svdf_last_error().decode())
+        return PairSource(self, h, n)
+
+    def dataset_from_pair_source(self, src, num_neg=1, seed=0):
+        """One pass over the source's rows with num_neg negatives each, drawn on the device from (seed, pair index): the data set
+        dataset_from_pairs builds from pair_negatives(...)'s column, without that column crossing PCIe where a route allows."""
+        h = self.lib.svdf_dataset_from_pair_source(self.h, src.h, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if not h:
+            raise SvdfError(self.lib.svdf_last_error().decode())
+        return Dataset(self, h)
+
+    def pair_source_draw(self, src, num_neg, seed):
+        """the negative column the device draws for such a pass: uint32[n * num_neg]"""
+        neg = np.zeros(max(_pass_size(src.num_row, num_neg), 1), np.uint32)
+        self._ok(self.lib.svdf_pair_source_draw(self.h, src.h, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF, neg))
+        return neg[:src.num_row * int(num_neg)]
 
     def dataset_from_blocks(self, blocks):
         """blocks: list of PlusBlock in file order (one pass of a user-group buffer), or a flat BlockArrays."""

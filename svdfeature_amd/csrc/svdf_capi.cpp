@@ -10,6 +10,7 @@
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
 #include "svdf_ranklines_lists.h"
+#include "svdf_pairsource_lists.h"
 #include "svdf_ranknegs_lists.h"
 #include "svdf_wseq_rule.h"
 
@@ -24,6 +25,7 @@ void note_error(const std::string &m);
 struct svdf_trainer { svdf::Engine *e; };
 struct svdf_dataset { svdf::Dataset *d; };
 struct svdf_ranker { svdf::Ranker *r; };
+struct svdf_pair_source { svdf::PairSource *s; };
 
 // In error mode 0 svdf::fail() has already printed and exited (reference behaviour); in mode 1 it
 // throws and the wrapper turns that into a status code.
@@ -462,6 +464,37 @@ int svdf_rank_eval_sampled(svdf_trainer *t, long num_section, const unsigned *us
         svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
         return 0;
     })
+}
+
+/* ---- passes of rank pairs from positives only: the negatives drawn on the device ---- */
+svdf_pair_source *svdf_pair_source_create(svdf_trainer *t, long n, const unsigned *user, const unsigned *pos_item) {
+    SVDF_GUARD(nullptr, {
+        svdf::PairSource *s = t->e->pair_source_create(n, user, pos_item);
+        svdf_pair_source *h = new svdf_pair_source();
+        h->s = s;
+        return h;
+    })
+}
+void svdf_pair_source_destroy(svdf_pair_source *s) {
+    if (!s) return;
+    try { delete s->s; } catch (...) {}
+    delete s;
+}
+svdf_dataset *svdf_dataset_from_pair_source(svdf_trainer *t, svdf_pair_source *s, int num_neg, uint64_t seed) {
+    SVDF_GUARD(nullptr, {
+        svdf::Dataset *d = t->e->dataset_from_pair_source(s ? s->s : nullptr, num_neg, seed);
+        t->e->note_dataset(d);
+        svdf_dataset *h = new svdf_dataset();
+        h->d = d;
+        return h;
+    })
+}
+int svdf_pair_source_draw(svdf_trainer *t, svdf_pair_source *s, int num_neg, uint64_t seed, unsigned *neg_out) {
+    SVDF_GUARD(-1, { t->e->pair_source_draw(s ? s->s : nullptr, num_neg, seed, neg_out); return 0; })
+}
+int svdf_pair_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, uint64_t seed,
+                        unsigned *neg_out) {
+    SVDF_GUARD(-1, { svdf::pair_src_negatives(num_user, num_item, n, user, pos_item, num_neg, seed, neg_out); return 0; })
 }
 
 /* ---- ISVDRanker ---- */

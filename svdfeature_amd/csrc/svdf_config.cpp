@@ -224,6 +224,8 @@ int64_t Engine::counter(int what) const {
     case 41: return n_rank_line_sections_;   // of those two, the sections the _lines calls ranked with a row built from a USER line (section 6z)
     case 42: return n_rank_cand_sections_;   // of those two, the sections the _cand calls ranked over a candidate list (section 6aa)
     case 43: return n_rank_negs_sections_;   // of the sections under 38, those ranked against negatives drawn on the device (section 6ab)
+    case 44: return n_pair_src_hbm_;         // passes built from a pair source without the pair columns leaving HBM (section 6ac)
+    case 45: return n_pair_src_fallback_;    // passes built from a pair source through dataset_from_pairs on the columns copied back
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

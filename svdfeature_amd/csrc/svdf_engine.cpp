@@ -121,6 +121,8 @@ Engine::~Engine() {
     rank_prefetch_drop();
     for (Dataset *ds : datasets_) ds->owner = nullptr;
     datasets_.clear();
+    for (PairSource *s : pair_sources_) s->owner = nullptr;   // (a source frees its own columns, like a data set)
+    pair_sources_.clear();
     if (getenv("SVDF_PROFILE"))
         fprintf(stderr, "[svdfeature_amd] host time: flush (schedule+upload+launch) %.3fs  model save/load %.3fs  instances %ld flushes %ld\n",
                 ns_flush_ * 1e-9, ns_model_ * 1e-9, (long)n_instances_, (long)n_flushes_);

@@ -84,13 +84,17 @@ struct DevBuf {
         cap = 0;
     }
     void reserve(size_t n) {           // grow-only, contents not preserved
-        if (n <= cap && p) return;
+        const hipError_t e = try_reserve(n);
+        if (e != hipSuccess) fail(std::string("HIP error: ") + hipGetErrorString(e) + " at hipMalloc (DevBuf::reserve)");
+    }
+    hipError_t try_reserve(size_t n) { // reserve() that hands the allocation's error to a caller with more to say about it
+        if (n <= cap && p) return hipSuccess;
         release();
         const size_t want = n ? n : 1;
         DevPool *pool = dev_pool_current();
         if (pool) {
             size_t got = 0;
-            if (void *q = pool->take(want * sizeof(T), got)) { p = static_cast<T *>(q); cap = got / sizeof(T); return; }
+            if (void *q = pool->take(want * sizeof(T), got)) { p = static_cast<T *>(q); cap = got / sizeof(T); return hipSuccess; }
         }
         hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
         if (e != hipSuccess && pool && !pool->blocks.empty()) {   // the cached blocks may be what is in the way
@@ -98,8 +102,9 @@ struct DevBuf {
             pool->drop();
             e = hipMalloc((void **)&p, want * sizeof(T));
         }
-        if (e != hipSuccess) fail(std::string("HIP error: ") + hipGetErrorString(e) + " at hipMalloc (DevBuf::reserve)");
+        if (e != hipSuccess) { p = nullptr; return e; }
         cap = want;
+        return hipSuccess;
     }
     void upload(const T *src, size_t n, hipStream_t st) {
         reserve(n);
@@ -380,6 +385,20 @@ struct Dataset {
     Dataset &operator=(const Dataset &) = delete;
 };
 
+// A resident source of positives (user, item) for passes of rank pairs whose negatives the device draws (svdf_pairsource.cpp; DESIGN.md
+// section 6ac): one upload each at creation, nothing per pass.  A host-only handle's source holds no device memory.
+struct PairSource {
+    Engine *owner = nullptr;
+    long n = 0;
+    long same = 0;                     // rows whose user is the row's before: the user-column pretest of user-run units, from the caller's column
+    DevBuf<unsigned> user, pos, uitems;   // [n], [n], every user's distinct items ascending
+    DevBuf<int> uptr;                  // [num_user + 1]
+    PairSource() = default;
+    ~PairSource();
+    PairSource(const PairSource &) = delete;
+    PairSource &operator=(const PairSource &) = delete;
+};
+
 struct RankLines;   // the USER lines of the svdf_rank_*_lines calls (svdf_ranklines_lists.h)
 class Engine {
   public:
@@ -497,6 +516,13 @@ class Engine {
     void rank_negs(long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                    const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed,
                    int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out);
+
+    // passes of rank pairs from positives only, the negatives drawn on the device (svdf_pairsource.cpp, svdf_k_pairdraw.hip; DESIGN.md
+    // section 6ac).  A source belongs to the handle it was created on and may outlive it.
+    PairSource *pair_source_create(long n, const unsigned *user, const unsigned *pos);
+    Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed);
+    void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out);
+    void pair_source_forget(PairSource *src);   // (the source is being destroyed)
 
     // multi-GPU item-side delta
     // the per-rank exchange entry points (one process per GPU) make no sense on a handle that exchanges by itself
@@ -795,6 +821,7 @@ class Engine {
     int wseq_count_actual_ = 1;           // knob "window_count_actual": 1 = the window rule is evaluated on the windows as they are cut and W raised until it holds (svdf_wseq_rule.h: wseq_actual_columns / _csr); 0 = the per-pass rule alone
     WseqKnobs wseq_knobs() const;         // the knob values the window rule reads (svdf_wseq_rule.h), amd:window among them
     bool wseq_hot_ok() const;             // the configuration has the hot lane (unit ratings, fp32 contribution rows, one GPU)
+    void resident_rows_check() const;               // what dataset_from_csr (and every caller that ends there) refuses about a user-group trainer
     void wseq_pair_check(const char *what) const;   // window_pair_sub > 0: what the lane does not cover, refused with its cause
     // the refusals common to the sub-step knobs (window_shared_sub, window_item_sub, window_pair_sub) when `knob` is on
     void wseq_sub_check(const char *what, const char *knob, const char *desc, const char *entry, const char *nrank, bool entry_only = false) const;
@@ -864,6 +891,7 @@ class Engine {
     // the same sequence from a pass of rank pairs the device sampler left in HBM (merged item entries i0 / v0 / i1 of unit-value rows, file order):
     // counts, window rule and windows without the columns visiting the host (svdf_k_rankwin.hip).  nullptr: a pair the windows do not take
     // (positive and negative row of one item, an id out of range) -- the caller falls back to the route that reports it
+    // d_v0 == nullptr: d_i0 / d_i1 ARE the positive and the negative item of every pair (a pair source's draw, section 6ac) and are cut as they are
     Dataset *wseq_from_device_pairs(long n, const unsigned *d_user, const unsigned *d_i0, const float *d_v0, const unsigned *d_i1);
     void wseq_train(Dataset *ds);
     WindowSchedule window_view(const Dataset *ds) const;
@@ -966,6 +994,11 @@ class Engine {
     DevBuf<float> ca_score_;           // ... and the scores of its pairs
     int64_t n_rank_negs_sections_ = 0; // counter 43: sections ranked against negatives drawn on the device
     DevBuf<int> ng_id_, ng_neg_;       // a sampled piece's cand_id, filled by k_rank_negs_draw, and its neg_out rows where they are asked for
+    int64_t n_pair_src_hbm_ = 0;       // counter 44: passes built from a pair source without the pair columns leaving HBM
+    int64_t n_pair_src_fallback_ = 0;  // counter 45: passes built from a pair source through dataset_from_pairs on host columns
+    std::vector<PairSource *> pair_sources_;   // the live sources of this handle: forgotten (owner = nullptr) when the handle goes
+    // the pass's columns [n * num_neg] drawn into HBM (user / pos may be nullptr); a pair that exhausted its draws fails the call
+    void pair_source_launch(const PairSource &src, int num_neg, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg);
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -35,6 +35,9 @@ inline int rw_bits(unsigned long long v) {
     return b;
 }
 
+// MERGED = false: the columns ARE the positive and the negative item of every pair (a pair source's draw, svdf_pairsource.cpp): i0 = pos, i1 = neg,
+// v0 / pos / neg unused -- the same checks, counts and keys.
+template <bool MERGED>
 __global__ __launch_bounds__(256) void k_rw_columns(long n, const unsigned *user, const unsigned *i0, const float *v0, const unsigned *i1, unsigned NU, unsigned NI,
                                                     unsigned *pos, unsigned *neg, unsigned *keys, unsigned *vals, unsigned *count, unsigned *state) {
     const long stride = (long)gridDim.x * blockDim.x;
@@ -42,14 +45,14 @@ __global__ __launch_bounds__(256) void k_rw_columns(long n, const unsigned *user
         const unsigned a = i0[r], b = i1[r];
         unsigned err = 0u;
         if (user[r] >= NU) err |= (unsigned)RW_ERR_USER;
-        if (b == SLOT_ABSENT) err |= (unsigned)RW_ERR_SAME;   // positive and negative row name one item: the merged row has ONE entry (apex_svd_data.cpp:828-860)
+        if (MERGED ? b == SLOT_ABSENT : a == b) err |= (unsigned)RW_ERR_SAME;   // positive and negative row name one item: the merged row has ONE entry (apex_svd_data.cpp:828-860)
         else if (b >= NI) err |= (unsigned)RW_ERR_ITEM;
         if (a >= NI) err |= (unsigned)RW_ERR_ITEM;
-        const bool first_pos = v0[r] > 0.0f;   // unit values: entry 0 is +1 (the positive's) or -1 (the negative's, sign flipped)
+        const bool first_pos = !MERGED || v0[r] > 0.0f;   // unit values: entry 0 is +1 (the positive's) or -1 (the negative's, sign flipped)
         unsigned p = first_pos ? a : b, q = first_pos ? b : a;
         if (err) { atomicOr(&state[0], err); p = 0u; q = 0u; }
         else { atomicAdd(&count[p], 1u); atomicAdd(&count[q], 1u); }
-        pos[r] = p; neg[r] = q;
+        if (MERGED) { pos[r] = p; neg[r] = q; }
         if (keys) { keys[2 * r] = p; keys[2 * r + 1] = q; vals[2 * r] = (unsigned)(2 * r); vals[2 * r + 1] = (unsigned)(2 * r + 1); }
     }
 }
@@ -100,7 +103,13 @@ __global__ __launch_bounds__(256) void k_rw_window_sums(const unsigned *item, co
 void launch_rank_window_columns(long n, const unsigned *user, const unsigned *i0, const float *v0, const unsigned *i1, long num_user, long num_item,
                                 unsigned *pos, unsigned *neg, unsigned *keys, unsigned *vals, unsigned *count, unsigned *state, hipStream_t st) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_rw_columns, dim3(rw_grid(n)), dim3(256), 0, st, n, user, i0, v0, i1, (unsigned)num_user, (unsigned)num_item, pos, neg, keys, vals, count, state);
+    hipLaunchKernelGGL(k_rw_columns<true>, dim3(rw_grid(n)), dim3(256), 0, st, n, user, i0, v0, i1, (unsigned)num_user, (unsigned)num_item, pos, neg, keys, vals, count, state);
+}
+void launch_rank_window_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg, long num_user, long num_item, unsigned *keys, unsigned *vals,
+                              unsigned *count, unsigned *state, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_rw_columns<false>, dim3(rw_grid(n)), dim3(256), 0, st, n, user, pos, (const float *)nullptr, neg, (unsigned)num_user, (unsigned)num_item,
+                       (unsigned *)nullptr, (unsigned *)nullptr, keys, vals, count, state);
 }
 
 size_t rank_window_sort_bytes(long E) {

@@ -209,6 +209,9 @@ void device_window_build(const WBuildIn &in, const WBuildBuffers &B, const WBuil
 enum { RW_ERR_USER = 1, RW_ERR_ITEM = 2, RW_ERR_SAME = 4 };
 void launch_rank_window_columns(long n, const unsigned *user, const unsigned *i0, const float *v0, const unsigned *i1, long num_user, long num_item,
                                 unsigned *pos, unsigned *neg, unsigned *keys, unsigned *vals, unsigned *count, unsigned *state, hipStream_t st);
+// the same kernel on columns that are pos / neg already (a pair source's draw, section 6ac): checks, counts and keys, nothing to turn back
+void launch_rank_window_pairs(long n, const unsigned *user, const unsigned *pos, const unsigned *neg, long num_user, long num_item, unsigned *keys, unsigned *vals,
+                              unsigned *count, unsigned *state, hipStream_t st);
 size_t rank_window_sort_bytes(long E);
 void rank_window_sort(void *tmp, size_t tmp_bytes, const unsigned *keys, unsigned *keys_sorted, const unsigned *vals, unsigned *vals_sorted, long E, long num_item,
                       hipStream_t st);
@@ -387,6 +390,24 @@ struct RankNegsDev {
     int *neg_out;              // nullptr, or [nsec][num_neg]: the negatives in draw order, -1 for a section without positives
 };
 void launch_rank_negs(const RankNegsDev &D, hipStream_t st);   // one launch, a wave per section
+
+// ---- the negatives of a pass of rank pairs drawn from a pair source (svdf_k_pairdraw.hip): pair q = r * num_neg + j
+// of source row r.  Every id has been validated on the host when the source was created.
+struct PairDrawDev {
+    long npair;                // n * num_neg, below 2^31 - 16
+    int num_neg;               // 1 .. PAIR_SRC_MAX_NEG
+    uint64_t seed;
+    unsigned num_item;
+    const unsigned *user;      // [n] the source's rows
+    const unsigned *pos;       // [n]
+    const int *uptr;           // [num_user + 1] the distinct items of user u: uitems[uptr[u] .. uptr[u + 1]), ascending
+    const unsigned *uitems;
+    unsigned *out_user;        // [npair] the pass's columns; out_user and out_pos may both be nullptr (svdf_pair_source_draw)
+    unsigned *out_pos;
+    unsigned *out_neg;
+    unsigned *flag;            // one word, zeroed by the caller: q + 1 of a pair (any of them) that exhausted its draws
+};
+void launch_pair_draw(const PairDrawDev &D, hipStream_t st);   // one launch, a lane per pair
 
 }  // namespace svdf
 #endif

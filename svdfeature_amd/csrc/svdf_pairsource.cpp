@@ -1,0 +1,162 @@
+// svdf_pairsource.cpp -- passes of rank pairs from positives only: the host side of svdf_pair_source_create /
+// svdf_dataset_from_pair_source / svdf_pair_source_draw.  A source keeps its rows and every user's distinct items in HBM (one upload each
+// at creation, svdf_pairsource_lists.h builds the lists); a pass draws its negatives there (svdf_k_pairdraw.hip) into three columns of
+// n * num_neg entries and is built from those columns where Engine::dataset_from_pairs has a route that starts from device columns -- the
+// window sequence of svdf_wseq.cpp (section 6v's builder) and the exact level schedule of schedule_device_columns.  Everything else copies
+// the columns back and IS dataset_from_pairs on them, so no result depends on the route.
+#include <svdfeature_amd.h>
+
+#include <memory>
+
+#include "svdf_internal.h"
+#include "svdf_kernels.h"
+#include "svdf_pairsource_lists.h"
+
+namespace svdf {
+
+template <typename T>
+static void pair_src_reserve(DevBuf<T> &buf, size_t n, const char *what) {   // (in either error mode: fail() prints or throws what it is given)
+    const hipError_t e = buf.try_reserve(n);
+    if (e != hipSuccess)
+        fail(std::string("pair_source: ") + what + " of " + std::to_string(n * sizeof(T)) + " bytes could not be allocated: " + hipGetErrorString(e) + " at hipMalloc");
+}
+
+PairSource::~PairSource() {
+    if (owner) owner->pair_source_forget(this);
+}
+void Engine::pair_source_forget(PairSource *src) {
+    pair_sources_.erase(std::remove(pair_sources_.begin(), pair_sources_.end(), src), pair_sources_.end());   // (every draw has been waited for)
+}
+
+PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsigned *pos) {
+    check(trainer_ready_, "pair_source: call init_model / load_model and init_trainer first");
+    // ---- the rows and the lists, before any device work
+    pair_src_check_rows((long)mp_.num_user, (long)mp_.num_item, n, user, pos);
+    PairSrcLists L;
+    pair_src_build((long)mp_.num_user, (long)mp_.num_item, n, user, pos, L, pair_src_threads(n));
+    std::unique_ptr<PairSource> src(new PairSource());
+    src->n = n;
+    for (long r = 1; r < n; r++) src->same += user[r] == user[r - 1];
+    if (!host_only_) {   // (a host-only handle's source reaches every refusal of a pass, then "needs a GPU")
+        need_device("pair_source");
+        pair_src_reserve(src->user, (size_t)n, "the user column");
+        pair_src_reserve(src->pos, (size_t)n, "the item column");
+        pair_src_reserve(src->uptr, L.uptr.size(), "the list offsets");
+        pair_src_reserve(src->uitems, std::max<size_t>(L.uitems.size(), 1), "the users' item lists");
+        src->user.upload(user, (size_t)n, stream_);
+        src->pos.upload(pos, (size_t)n, stream_);
+        src->uptr.upload(L.uptr.data(), L.uptr.size(), stream_);
+        src->uitems.upload(L.uitems.data(), L.uitems.size(), stream_);
+        HIPCHECK(hipStreamSynchronize(stream_));   // L goes out of scope
+    }
+    src->owner = this;
+    pair_sources_.push_back(src.get());
+    return src.release();
+}
+
+void Engine::pair_source_launch(const PairSource &src, int num_neg, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg) {
+    DevBuf<unsigned> flag;
+    pair_src_reserve(flag, 1, "the flag");
+    HIPCHECK(hipMemsetAsync(flag.p, 0, sizeof(unsigned), stream_));
+    PairDrawDev D;
+    D.npair = src.n * (long)num_neg;
+    D.num_neg = num_neg;
+    D.seed = seed;
+    D.num_item = (unsigned)mp_.num_item;
+    D.user = src.user.p; D.pos = src.pos.p; D.uptr = src.uptr.p; D.uitems = src.uitems.p;
+    D.out_user = d_user; D.out_pos = d_pos; D.out_neg = d_neg;
+    D.flag = flag.p;
+    launch_pair_draw(D, stream_);
+    HIPCHECK(hipGetLastError());
+    n_launches_++;
+    unsigned spent = 0;
+    HIPCHECK(hipMemcpyAsync(&spent, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));
+    if (spent) fail("pair_source: pair " + std::to_string((long)spent - 1) + " found no negative in " + std::to_string(PAIR_SRC_DRAWS) + " draws");
+}
+
+// what every pass refuses, on the host, before any device work
+static void pair_src_admit(const Engine *e, const PairSource *src, int num_neg) {
+    if (!src) fail("pair_source: bad arguments");
+    if (src->owner != e) fail("pair_source: the source was created on another trainer");
+    pair_src_check_pass(src->n, num_neg);
+}
+
+void Engine::pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out) {
+    pair_src_admit(this, src, num_neg);
+    check(neg_out != nullptr, "pair_source: bad arguments");
+    need_device("pair_source");
+    const size_t N = (size_t)src->n * (size_t)num_neg;
+    DevBuf<unsigned> neg;
+    pair_src_reserve(neg, N, "the negative column of a pass");
+    pair_source_launch(*src, num_neg, seed, nullptr, nullptr, neg.p);
+    HIPCHECK(hipMemcpyAsync(neg_out, neg.p, N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));
+}
+
+Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed) {
+    pair_src_admit(this, src, num_neg);
+    check(trainer_ready_, "dataset: init_trainer has not been called");
+    need_device("dataset");
+    const long N = src->n * (long)num_neg;
+    // ---- the route, in the order of dataset_from_pairs' own decisions on the same columns
+    const bool one_gpu = !multi_ && !is_peer_ && !in_multi_scope();
+    const bool to_windows = single_minibatch() && !user_group() && window_rows_allowed();          // where it takes wseq_from_pairs
+    const bool windows_hbm = one_gpu && to_windows && device_window_ready() && wseq_pair_sub_ == 0;
+    // the pretest of punit_dataset_from_pairs on the EXPANDED user column: the num_neg pairs of a row are adjacent
+    const bool to_units = punit_config_ok() && N >= 2 && N < 0x7FFFFFF0L && 2 * (src->n * (long)(num_neg - 1) + src->same) >= N;
+    const bool exact_hbm = one_gpu && !to_windows && !auto_step_active() && !to_units && device_sched_ && fused_allowed() && !user_group() && !relaxed();
+    // ---- what dataset_from_pairs refuses about the trainer whatever the columns hold, in its own words, before any device work
+    if (wseq_pair_sub_ > 0 && ((multi_ && !in_multi_scope()) || (single_minibatch() && (user_group() || window_rows_allowed())))) wseq_pair_check("dataset_from_pairs");
+    if (!(multi_ && !in_multi_scope())) resident_rows_check();   // (a user-group trainer's pairs end in dataset_from_csr)
+    DevBuf<unsigned> cu, cp, cq;
+    pair_src_reserve(cu, (size_t)N, "the user column of a pass");
+    pair_src_reserve(cp, (size_t)N, "the positive column of a pass");
+    pair_src_reserve(cq, (size_t)N, "the negative column of a pass");
+    pair_source_launch(*src, num_neg, seed, cu.p, cp.p, cq.p);
+    if (!windows_hbm && !exact_hbm) {   // dataset_from_pairs itself, on the columns copied back
+        std::vector<unsigned> hu((size_t)N), hp((size_t)N), hq((size_t)N);
+        HIPCHECK(hipMemcpyAsync(hu.data(), cu.p, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipMemcpyAsync(hp.data(), cp.p, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipMemcpyAsync(hq.data(), cq.p, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipStreamSynchronize(stream_));
+        cu.release(); cp.release(); cq.release();
+        Dataset *ds = dataset_from_pairs(N, hu.data(), hp.data(), hq.data());
+        n_pair_src_fallback_++;
+        return ds;
+    }
+    if (windows_hbm) {   // section 6v's builder on the pos / neg columns as drawn: item counts, window rule and windows from where they are
+        Dataset *seq = wseq_from_device_pairs(N, cu.p, cp.p, nullptr, cq.p);
+        if (!seq) fail("pair_source: the drawn columns hold an id the windows refuse");   // (validated ids, pos != neg: not reached)
+        n_pair_src_hbm_++;
+        return seq;
+    }
+    // ---- the merged, index-sorted form the level schedule starts from: lower / higher item id and the entries' signs (pos != neg by the rule)
+    DevBuf<unsigned> lo_, hi_, flag;
+    DevBuf<float> vlo, vhi, one;
+    pair_src_reserve(lo_, (size_t)N, "a schedule column"); pair_src_reserve(hi_, (size_t)N, "a schedule column");
+    pair_src_reserve(vlo, (size_t)N, "a schedule column"); pair_src_reserve(vhi, (size_t)N, "a schedule column");
+    pair_src_reserve(one, (size_t)N, "a schedule column"); pair_src_reserve(flag, 1, "the flag");
+    HIPCHECK(hipMemsetAsync(flag.p, 0, sizeof(unsigned), stream_));
+    launch_pairs_prepare(N, cp.p, cq.p, lo_.p, hi_.p, vlo.p, vhi.p, one.p, flag.p, stream_);
+    HIPCHECK(hipGetLastError());
+    cp.release(); cq.release();   // (stream-ordered frees: the kernel above has been enqueued)
+    std::unique_ptr<Dataset> ds(new Dataset());
+    adopt(ds.get()); ds->num_row = N; ds->kind = 2;
+    const unsigned *res[3] = {cu.p, lo_.p, hi_.p};
+    const unsigned off[3] = {0u, (unsigned)mp_.num_user, (unsigned)mp_.num_user};
+    const unsigned limit[3] = {(unsigned)mp_.num_user, (unsigned)mp_.num_item, (unsigned)mp_.num_item};
+    const char *msg[3] = {"user feature index exceed bound", "item feature index exceed bound", "item feature index exceed bound"};
+    const unsigned *key = sort_batches_ == 1 ? lo_.p : (sort_batches_ == 2 ? cu.p : nullptr);
+    FusedDev &f = ds->fused;
+    f.max_nu = 1; f.max_ni = 2; f.has_g = false; f.inline_g = false;
+    schedule_device_columns(ds.get(), N, 3, res, off, limit, msg, key, sort_batches_ == 1 ? limit[1] : limit[0],
+                            {DUCol{cu.p, &f.uidx[0]}, DUCol{lo_.p, &f.iidx[0]}, DUCol{hi_.p, &f.iidx[1]}},
+                            {DFCol{one.p, &f.label}, DFCol{one.p, &f.uval[0]}, DFCol{vlo.p, &f.ival[0]}, DFCol{vhi.p, &f.ival[1]}});
+    const long nb2 = (mp_.no_user_bias ? 0 : 1) + 2;
+    ds->algorithmic_bytes = N * (8L * mp_.num_factor * 3 + 8 * nb2 + 16 + 8 * 3);
+    n_pair_src_hbm_++;
+    return ds.release();
+}
+
+}  // namespace svdf

@@ -290,14 +290,18 @@ Dataset *Engine::wseq_from_device_pairs(long n, const unsigned *d_user, const un
     DevBuf<unsigned> d_pos, d_neg, d_cnt, d_state, k0, k1, v0, v1;
     const WseqKnobs K = wseq_knobs();
     const bool actual = K.actual_on() && n > 0;
+    const bool merged = d_v0 != nullptr;   // (else the columns are pos / neg already)
     if (n > 0) {
         need_device("dataset");
-        d_pos.reserve((size_t)n); d_neg.reserve((size_t)n); d_cnt.reserve((size_t)std::max<long>(NI, 1)); d_state.reserve(4);
+        if (merged) { d_pos.reserve((size_t)n); d_neg.reserve((size_t)n); }
+        d_cnt.reserve((size_t)std::max<long>(NI, 1)); d_state.reserve(4);
         if (actual) { k0.reserve((size_t)E); k1.reserve((size_t)E); v0.reserve((size_t)E); v1.reserve((size_t)E); }
         HIPCHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)std::max<long>(NI, 1) * sizeof(unsigned), stream_));
         HIPCHECK(hipMemsetAsync(d_state.p, 0, 4 * sizeof(unsigned), stream_));
-        launch_rank_window_columns(n, d_user, d_i0, d_v0, d_i1, mp_.num_user, NI, d_pos.p, d_neg.p, actual ? k0.p : nullptr, actual ? v0.p : nullptr, d_cnt.p, d_state.p,
-                                   stream_);
+        if (merged)
+            launch_rank_window_columns(n, d_user, d_i0, d_v0, d_i1, mp_.num_user, NI, d_pos.p, d_neg.p, actual ? k0.p : nullptr, actual ? v0.p : nullptr, d_cnt.p, d_state.p,
+                                       stream_);
+        else launch_rank_window_pairs(n, d_user, d_i0, d_i1, mp_.num_user, NI, actual ? k0.p : nullptr, actual ? v0.p : nullptr, d_cnt.p, d_state.p, stream_);
         std::vector<unsigned> hc((size_t)NI);
         unsigned hs[4] = {0u, 0u, 0u, 0u};
         if (NI > 0) HIPCHECK(hipMemcpyAsync(hc.data(), d_cnt.p, (size_t)NI * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
@@ -329,12 +333,13 @@ Dataset *Engine::wseq_from_device_pairs(long n, const unsigned *d_user, const un
     std::unique_ptr<Dataset> ds(new Dataset());
     adopt(ds.get()); ds->kind = 8; ds->num_row = n;
     ds->wseq_pair_sub = 0;
+    const unsigned *w_pos = merged ? d_pos.p : d_i0, *w_neg = merged ? d_neg.p : d_i1;
     for (long w = 0; w < W; w++) {
         const long b0 = n * w / W, b1 = n * (w + 1) / W;
         std::unique_ptr<Dataset> c(new Dataset());
         adopt(c.get());
         window_build_header(c.get(), b1 - b0, true, true);
-        if (b1 > b0) window_build_resident(c.get(), b1 - b0, d_user + b0, d_pos.p + b0, nullptr, d_neg.p + b0);   // (returns after the window's read-back: the columns outlive every read)
+        if (b1 > b0) window_build_resident(c.get(), b1 - b0, d_user + b0, w_pos + b0, nullptr, w_neg + b0);   // (returns after the window's read-back: the columns outlive every read)
         else {   // a pass that drew no pair: one window without instances, the arrays of window_build at n = 0
             need_device("dataset");
             c->win_urec.reserve(1); c->item.reserve(1); c->win_slot.reserve(1); c->win_item1.reserve(1); c->win_slot1.reserve(1); c->ival.reserve(1); c->win_ival1.reserve(1);
