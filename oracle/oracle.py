@@ -95,6 +95,9 @@ def _load(kind):
     lib.svdo_sum_sq_err.restype = C.c_double
     lib.svdo_sum_sq_err.argtypes = [_f32p, _f32p, C.c_long, C.c_float]
     lib.svdo_libm_expf.argtypes = [C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_long]
+    if hasattr(lib, "svdo_set_flush"):   # (the port only)
+        lib.svdo_set_flush.argtypes = [C.c_int]
+        lib.svdo_set_flush.restype = C.c_int
     _libs[kind] = lib
     return lib
 
@@ -203,6 +206,14 @@ class OracleTrainer:
     def set_stale_rounding(self, bf16):
         """checker steps: round row contributions to bfloat16 before summing (the HIP engine's amd:contrib = bf16)"""
         self.lib.svdo_set_stale_rounding(self.h, 1 if bf16 else 0)
+
+    def set_flush(self, on):
+        """TEST SWITCH (svdf_oracle.h: svdo_set_flush): flush-to-zero and denormals-are-zero on the calling thread for every later call into the
+        port, until it is cleared again -- the decoy a flushing kernel would match (tests/test_float_edges.py).  Clear it in a `finally`."""
+        assert self.kind == "port", "the flush switch exists in the port only"
+        have = self.lib.svdo_set_flush(1 if on else 0)   # (outside the assert: the call must happen under python -O too)
+        if have != 1:
+            raise RuntimeError("the flush switch needs x86-64")
 
     def stale_delta_zero(self):
         """zeroed delta arrays of the window-minibatch checker step for a user-group trainer:

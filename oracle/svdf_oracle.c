@@ -27,6 +27,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#if defined(__x86_64__)
+#include <xmmintrin.h>
+#endif
 
 /* ---- apex_svd_model.h:373-435 SVDModelParam: 1056-byte on-disk header ---- */
 typedef struct {
@@ -107,6 +110,17 @@ void svdo_libm_expf(const float *in, unsigned first, unsigned step, float *out, 
     }
 }
 
+/* test switch (svdf_oracle.h): MXCSR bit 15 = flush-to-zero, bit 6 = denormals-are-zero */
+int svdo_set_flush(int on) {
+#if defined(__x86_64__)
+    unsigned csr = _mm_getcsr();
+    _mm_setcsr(on ? (csr | 0x8040u) : (csr & ~0x8040u));
+    return 1;
+#else
+    (void)on;
+    return 0;
+#endif
+}
 
 /* ================= tensor micro-ops ================= */
 

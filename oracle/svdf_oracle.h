@@ -93,6 +93,10 @@ int svdo_kind(void);
 /* the host libm's expf (what active_type::map_active / cal_grad call, apex_svd_model.h:112-156) over an array, or with
  * in == NULL over the floats with bit patterns first + j*step: checker for the device's expf restatement */
 void svdo_libm_expf(const float *in, unsigned first, unsigned step, float *out, long n);
+/* TEST SWITCH, the plain-C restatement only: set (on != 0) or clear the flush-to-zero and denormals-are-zero bits of MXCSR on the calling
+ * thread, so that every later call on that thread computes the way a flushing port would.  tests/test_float_edges.py uses it to prove that
+ * its inputs tell a flushing kernel from an IEEE one; nothing else may leave it on.  Returns 1 where the switch exists (x86-64), else 0. */
+int svdo_set_flush(int on);
 
 /* ---- ISVDRanker (apex_svd.h:160-197) / SVDFeatureRanker (solvers/base-solver/apex_svd_base.h:597-813) ---- */
 typedef struct svdo_ranker svdo_ranker;
