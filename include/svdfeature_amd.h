@@ -872,6 +872,18 @@ int svdf_rand_skip(long n);
  * pattern is first_bits + j*step_bits.  Tests compare it with the host libm bit for bit.  Needs a GPU. */
 int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, float *out, long n);
 
+/* ---- probe of the launch geometry of the live-model ranking calls (DESIGN.md sections 6w, 6x), for tests: what svdf_rank_eval_positions
+ * (kind 0) or svdf_rank_topn (kind 1) would launch on this trainer, computed by the very functions those calls use.  Host function, no
+ * device work: a host-only handle answers it, before init_model too; only the parameters num_factor and num_item and the knobs
+ * rank_eval_budget / rank_topn_budget matter.
+ *   kind 0, pos_ptr == NULL: `units` is the number of row tiles of the sweep.
+ *   kind 0, pos_ptr != NULL: `units` sections with the positives pos_ptr[0 .. units] and no bans, feedback or lines: the first piece.
+ *   kind 1: `units` sections without bans and `top_n`: the first piece.
+ * out[0 .. 7] = item ranges (gy), items per range, list capacity (kind 1; else 0), rows of a tile, rows (kind 1: sections) of the piece,
+ * its tiles, its sections (0 for kind 0 without pos_ptr), launches of the sweep (the wide evaluation sweep takes one per 32768 rows).
+ * A test asserts with it that its shapes reach the geometry it is about.  -1 on bad arguments. */
+int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const int64_t *pos_ptr, long *out);
+
 /* ---- probes of the window rule of `amd:step = minibatch` (svdf_wseq_rule.h): into how many windows a pass is cut, from knob values and
  * counts alone.  Host functions, no handle and no GPU; the data-set builders reach the same functions.  Tests compare them with
  * tests/window_rule.py.

@@ -342,6 +342,7 @@ def load_library():
     lib.svdf_ranker_counter.argtypes = [P, C.c_int]
     lib.svdf_rand_peek.argtypes = [C.c_long, _i32p]
     lib.svdf_rand_skip.argtypes = [C.c_long]
+    lib.svdf_rank_geometry.argtypes = [P, C.c_int, C.c_long, C.c_int, C.c_void_p, C.POINTER(C.c_long)]
     lib.svdf_device_expf.argtypes = [C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_long]
     lib.svdf_window_rule.restype = C.c_long
     lib.svdf_window_rule.argtypes = [C.c_int, C.POINTER(WindowRuleIn)]
@@ -1122,6 +1123,19 @@ class Trainer:
 
     def set_knob(self, name, value):
         self._ok(self.lib.svdf_set_knob(self.h, name.encode(), int(value)))
+
+    def rank_geometry(self, kind, units, top_n=1, pos_ptr=None):
+        """svdf_rank_geometry, a test probe that needs no device: the launch geometry of rank_positions (kind "positions": `units` row tiles, or
+        with pos_ptr `units` sections with those positives) or of rank_topn (kind "topn": `units` sections, top_n) on this trainer, from the
+        functions the launches use.  A dict: gy, items_per_block, cap, tile_rows, rows, tiles, sections, launches."""
+        out = (C.c_long * 8)()
+        ptr = None
+        if pos_ptr is not None:
+            ptr = np.ascontiguousarray(pos_ptr, np.int64)
+            if len(ptr) != units + 1:
+                raise SvdfError("rank_geometry: pos_ptr must have one entry more than sections")
+        self._ok(self.lib.svdf_rank_geometry(self.h, {"positions": 0, "topn": 1}[kind], int(units), int(top_n), _opt_ptr(ptr), out))
+        return dict(zip(("gy", "items_per_block", "cap", "tile_rows", "rows", "tiles", "sections", "launches"), (int(v) for v in out)))
 
 
 _libc.fwrite.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]

@@ -536,6 +536,11 @@ int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, f
     SVDF_GUARD(-1, { return svdf::device_expf(in, first_bits, step_bits, out, n); })
 }
 
+// the launch geometry of the live-model ranking calls exposed for tests (tests/test_rank_geometry.py): Engine::rank_geometry
+int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const int64_t *pos_ptr, long *out) {
+    SVDF_GUARD(-1, { t->e->rank_geometry(kind, units, top_n, pos_ptr, out); return 0; })
+}
+
 // the window rule exposed for CPU tests (tests/test_window_rule.py): svdf_wseq_rule.h, the functions the data-set builders call
 long svdf_window_rule(int route, const svdf_window_rule_in *in) {
     SVDF_GUARD(-1, {

@@ -504,6 +504,7 @@ class Engine {
     void rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                        const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
                        int *nan_out, const RankLines *lines = nullptr);
+    void rank_geometry(int kind, long units, int top_n, const int64_t *pos_ptr, long *out);   // test probe (svdf_rank_geometry): host only
     void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                        const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
     // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md
@@ -566,6 +567,7 @@ class Engine {
     bool space_allocated_ = false, trainer_ready_ = false;
     // ---- geometry (SVDModel::alloc_space, apex_svd_model.h:511-556)
     int pitch_ = 0;
+    static int row_pitch(int num_factor) { return ((num_factor + 3) / 4) * 4; }   // floats of a factor row: ceil(4k/16)*16 bytes (apex_tensor_sse.h:26-27)
     long n_uiset_ = 0;
     unsigned user_off_ = 0, item_off_ = 0, fb_off_ = 0;
     int num_fb_rows() const { return mp_.common_feedback_space == 0 ? mp_.num_ufeedback : mp_.num_user; }

@@ -223,30 +223,41 @@ static size_t re_lds_bytes(int pitch, int ib) {
 }
 int rank_eval_tile_rows(const DevParams &P) { return P.pitch <= 256 ? RE_TS : 1; }
 
+static int re_ib(const DevParams &P) { return P.pitch <= 128 ? 2 : 1; }   // candidates per lane and step of the narrow sweep
+
+// The item ranges of the narrow sweep over `ntile` tiles of rows: about 2048 workgroups in all, and at least 8 item tiles per workgroup
+// where the items allow (the user rows are staged per workgroup).  The wide sweep has one range: every item lies in its grid.x.
+void rank_eval_geometry(const DevParams &P, long ntile, int *gy, long *items_per_block) {
+    if (P.pitch > 256) { *gy = 1; *items_per_block = P.num_item; return; }
+    const long ti = 64 * re_ib(P), ntile_i = (P.num_item + ti - 1) / ti;
+    long ysplit = std::max<long>(1, std::min<long>((2048 + ntile - 1) / std::max<long>(1, ntile), (ntile_i + 7) / 8));
+    ysplit = std::min<long>(ysplit, 65535);
+    const long per = ((ntile_i + ysplit - 1) / ysplit) * ti;
+    *items_per_block = per;
+    *gy = (int)((P.num_item + per - 1) / per);
+}
+
 void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st) {
     if (D.npos <= 0) return;
     hipLaunchKernelGGL(k_rank_eval_pos, dim3((unsigned)((D.npos + 255) / 256)), dim3(256), 0, st, P, D);
     if (P.pitch <= 256) {
-        const int ib = P.pitch <= 128 ? 2 : 1;
-        const long ti = 64 * ib, ntile_i = (P.num_item + ti - 1) / ti;
-        // about 2048 workgroups in all, and at least 8 item tiles per workgroup where the items allow (the user rows are staged per workgroup)
-        long ysplit = std::max<long>(1, std::min<long>((2048 + D.ntile - 1) / D.ntile, (ntile_i + 7) / 8));
-        ysplit = std::min<long>(ysplit, 65535);
-        const long per = ((ntile_i + ysplit - 1) / ysplit) * ti;
-        const unsigned gy = (unsigned)((P.num_item + per - 1) / per);
+        const int ib = re_ib(P);
+        int gy;
+        long per;
+        rank_eval_geometry(P, D.ntile, &gy, &per);
         const size_t lds = re_lds_bytes(P.pitch, ib);
         if (ib == 2) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_eval_sweep<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(k_rank_eval_sweep<2>, dim3((unsigned)D.ntile, gy), dim3(256), lds, st, P, D, per);
+            hipLaunchKernelGGL(k_rank_eval_sweep<2>, dim3((unsigned)D.ntile, (unsigned)gy), dim3(256), lds, st, P, D, per);
         } else {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_eval_sweep<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(k_rank_eval_sweep<1>, dim3((unsigned)D.ntile, gy), dim3(256), lds, st, P, D, per);
+            hipLaunchKernelGGL(k_rank_eval_sweep<1>, dim3((unsigned)D.ntile, (unsigned)gy), dim3(256), lds, st, P, D, per);
         }
     } else {
-        for (int r = 0; r < D.nrow; r += 32768) {   // grid.y is at most 65535
+        for (int r = 0; r < D.nrow; r += RANK_EVAL_WIDE_ROWS) {   // grid.y is at most 65535
             RankEvalDev E = D;
             E.row_sec += r; E.row_p0 += r; E.row_first += r;
-            hipLaunchKernelGGL(k_rank_eval_sweep_wide, dim3((unsigned)((P.num_item + 255) / 256), (unsigned)std::min(32768, D.nrow - r)), dim3(256), 0, st, P, E);
+            hipLaunchKernelGGL(k_rank_eval_sweep_wide, dim3((unsigned)((P.num_item + 255) / 256), (unsigned)std::min(RANK_EVAL_WIDE_ROWS, D.nrow - r)), dim3(256), 0, st, P, E);
         }
     }
     if (D.nban > 0) hipLaunchKernelGGL(k_rank_eval_ban, dim3((unsigned)((D.nban + 255) / 256)), dim3(256), 0, st, P, D);

@@ -272,6 +272,7 @@ static size_t tn_lds_bytes(int pitch, int ib) {
     return 16 * (nch * (64 * (size_t)ib + 1) + (size_t)TN_TS * nch) + 8 * (4 * (size_t)TN_SORT + (size_t)TN_TS + (size_t)TN_TS * ib) + 4 * 2 * (size_t)TN_TS;
 }
 static int tn_ib(const DevParams &P) { return P.pitch <= 128 ? 2 : 1; }   // candidates per lane and step; the wide sweep takes 1
+int rank_topn_tile_rows(const DevParams &P) { return P.pitch <= 256 ? TN_TS : 1; }   // sections of one workgroup (narrow) or wave (wide)
 
 // room for top_n kept keys and one step's appends, and for as many appends again between two cuts where TN_SORT allows
 int rank_topn_cap(const DevParams &P, int top_n) {
@@ -285,7 +286,7 @@ void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, 
     const long ti = P.pitch <= 256 ? 64 * tn_ib(P) : 64, ntile_i = (P.num_item + ti - 1) / ti;
     // narrow: about 2048 workgroups in all, at least 8 item tiles per workgroup where the items allow (the user rows are staged per
     // workgroup); wide: about 8192 waves
-    const long units = P.pitch <= 256 ? (nsec + TN_TS - 1) / TN_TS : nsec, want = P.pitch <= 256 ? 2048 : 8192;
+    const long ts = rank_topn_tile_rows(P), units = (nsec + ts - 1) / ts, want = P.pitch <= 256 ? 2048 : 8192;
     long ysplit = std::max<long>(1, std::min<long>((want + units - 1) / units, (ntile_i + 7) / 8));
     ysplit = std::min<long>(ysplit, std::max<long>(1, max_lists / std::max<long>(1, nsec)));
     ysplit = std::min<long>(ysplit, 65535);
@@ -299,7 +300,7 @@ void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) 
     if (P.pitch <= 256) {
         const int ib = tn_ib(P);
         const size_t lds = tn_lds_bytes(P.pitch, ib);
-        const dim3 grid((unsigned)((D.nsec + TN_TS - 1) / TN_TS), (unsigned)D.gy);
+        const dim3 grid((unsigned)((D.nsec + rank_topn_tile_rows(P) - 1) / rank_topn_tile_rows(P)), (unsigned)D.gy);
         if (ib == 2) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_topn_sweep<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(k_rank_topn_sweep<2>, grid, dim3(256), lds, st, P, D);

@@ -295,7 +295,9 @@ struct RankEvalDev {
     long nban;
     const int *ban_sec, *ban_item;   // [nban] distinct (section, banned id) pairs
 };
+constexpr int RANK_EVAL_WIDE_ROWS = 32768;   // rows of one launch of the wide sweep (grid.y is at most 65535)
 int rank_eval_tile_rows(const DevParams &P);
+void rank_eval_geometry(const DevParams &P, long ntile, int *gy, long *items_per_block);   // item ranges of the narrow sweep over ntile row tiles; wide: one
 void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st);   // positives' scores, the counting sweep, the ban correction
 
 // ---- top-N item lists on the live model (svdf_k_ranktopn.hip): one piece of whole sections.  The sweep keeps, per
@@ -320,6 +322,7 @@ struct RankTopnDev {
     int *count_out;                  // [nsec] entries listed; 0 for a section with a NaN among its ranked candidates
 };
 int rank_topn_cap(const DevParams &P, int top_n);   // capacity of one list, <= RANK_TOPN_MAX_CAP
+int rank_topn_tile_rows(const DevParams &P);        // sections that share one pass over an item range: 64 (narrow) or 1 (wide)
 void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block);   // at most max_lists / nsec (>= 1) item ranges
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep, then the merge: two launches
 

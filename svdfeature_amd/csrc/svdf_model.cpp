@@ -30,7 +30,7 @@ void Engine::compute_geometry() {  // SVDModel::alloc_space apex_svd_model.h:511
         user_off_ = item_off_ = (unsigned)ustart;
     }
     fb_off_ = mp_.common_feedback_space == 0 ? 0u : user_off_;
-    pitch_ = ((mp_.num_factor + 3) / 4) * 4;   // ceil(4k/16)*16 bytes (apex_tensor_sse.h:26-27)
+    pitch_ = row_pitch(mp_.num_factor);
     space_allocated_ = true;
 }
 void Engine::alloc_host_model() {

@@ -8,8 +8,10 @@
 
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
+#include "svdf_rankeval_lists.h"
 #include "svdf_rankfb_lists.h"
 #include "svdf_ranklines_lists.h"
+#include "svdf_ranktopn_lists.h"
 
 namespace svdf {
 
@@ -148,36 +150,20 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
         // ---- a piece of whole sections within the device budget
-        long s1 = s0;
-        int64_t load = 0;
-        while (s1 < S) {
-            const int64_t add = (pos_ptr[s1 + 1] - pos_ptr[s1]) + (ban_first[(size_t)s1 + 1] - ban_first[(size_t)s1]) + 1 + (fb_ptr ? fb_ptr[s1 + 1] - fb_ptr[s1] : 0) +
-                                (lines ? lines->ptr[s1 + 1] - lines->ptr[s1] : 0);
-            if (s1 > s0 && load + add > rank_eval_budget_) break;
-            load += add;
-            s1++;
-        }
+        const long s1 = rank_eval_piece(s0, S, rank_eval_budget_, [&](long s) {
+            return (pos_ptr[s + 1] - pos_ptr[s]) + (ban_first[(size_t)s + 1] - ban_first[(size_t)s]) + 1 + (fb_ptr ? fb_ptr[s + 1] - fb_ptr[s] : 0) +
+                   (lines ? lines->ptr[s + 1] - lines->ptr[s] : 0);
+        });
         const long nsec = s1 - s0;
         const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
         check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4) &&
                   (!lines || lines->ptr[s1] - lines->ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
         if (npos == 0) { s0 = s1; continue; }
         // ---- rows (a section, or a slice of its positives) and tiles of rows
-        std::vector<int> row_sec, row_first, row_p0, tile_r0;
-        for (long s = s0; s < s1; s++) {
-            const int p0 = (int)(pos_ptr[s] - pos_ptr[s0]), p1 = (int)(pos_ptr[s + 1] - pos_ptr[s0]);
-            for (int a = p0; a < p1; a += RANK_EVAL_TILE_POS) { row_sec.push_back((int)(s - s0)); row_first.push_back(a == p0 ? 1 : 0); row_p0.push_back(a); }
-        }
-        row_p0.push_back((int)npos);
-        const int nrow = (int)row_sec.size();
-        for (int r = 0; r < nrow;) {
-            tile_r0.push_back(r);
-            int e = r + 1;
-            while (e < nrow && e - r < tile_rows && row_p0[(size_t)e + 1] - row_p0[(size_t)r] <= RANK_EVAL_TILE_POS) e++;
-            r = e;
-        }
-        tile_r0.push_back(nrow);
-        const int ntile = (int)tile_r0.size() - 1;
+        RankEvalRows rows;
+        rank_eval_rows(pos_ptr, s0, s1, tile_rows, RANK_EVAL_TILE_POS, rows);
+        const std::vector<int> &row_sec = rows.row_sec, &row_first = rows.row_first, &row_p0 = rows.row_p0, &tile_r0 = rows.tile_r0;
+        const int nrow = rows.nrow(), ntile = rows.ntile();
         // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         in.clear();
         in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban +
@@ -271,6 +257,44 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         }
         s0 = s1;
     }
+}
+
+// The test probe svdf_rank_geometry: what the launches of the two calls would be told, from the functions they call, without a device.
+// Only the row width, the item count and the two budgets of the handle matter, so the parameters need not be followed by init_model.
+void Engine::rank_geometry(int kind, long units, int top_n, const int64_t *pos_ptr, long *out) {
+    check((kind == 0 || kind == 1) && units >= 1 && out, "rank_geometry: bad arguments");
+    check(mp_.num_factor >= 1 && mp_.num_item >= 1, "rank_geometry: set num_factor and num_item first");
+    DevParams P;
+    memset(&P, 0, sizeof(P));
+    P.pitch = row_pitch(mp_.num_factor); P.k = mp_.num_factor; P.num_item = mp_.num_item;   // before init_model too
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    int gy = 0;
+    long per = 0;
+    if (kind == 0) {
+        const int tile_rows = rank_eval_tile_rows(P);
+        long ntile = units, nrow = 0, piece = 0;
+        if (pos_ptr) {   // units sections without bans, feedback or lines: the first piece, its rows and tiles
+            check(pos_ptr[0] >= 0, "rank_geometry: pos_ptr must start at >= 0");
+            for (long s = 0; s < units; s++) check(pos_ptr[s + 1] >= pos_ptr[s], "rank_geometry: pos_ptr must not decrease");
+            piece = rank_eval_piece(0, units, rank_eval_budget_, [&](long s) { return pos_ptr[s + 1] - pos_ptr[s] + 1; });
+            RankEvalRows rows;
+            rank_eval_rows(pos_ptr, 0, piece, tile_rows, RANK_EVAL_TILE_POS, rows);
+            nrow = rows.nrow(); ntile = rows.ntile();
+        }
+        if (ntile > 0) rank_eval_geometry(P, ntile, &gy, &per);
+        out[3] = tile_rows; out[4] = nrow; out[5] = ntile; out[6] = piece;
+        out[7] = P.pitch <= 256 ? (ntile > 0 ? 1 : 0) : (nrow + RANK_EVAL_WIDE_ROWS - 1) / RANK_EVAL_WIDE_ROWS;   // launches of the sweep
+    } else {
+        check(top_n >= 1 && top_n <= RANK_TOPN_MAX, "rank_geometry: top_n must be between 1 and 256");
+        const int cap = rank_topn_cap(P, top_n);
+        const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
+        const std::vector<int64_t> no_bans((size_t)units + 1, 0);
+        const long piece = rank_topn_piece(0, units, max_lists, no_bans);   // units sections without bans: the first piece
+        rank_topn_geometry(P, piece, max_lists, &gy, &per);
+        const long ts = rank_topn_tile_rows(P);
+        out[2] = cap; out[3] = ts; out[4] = piece; out[5] = (piece + ts - 1) / ts; out[6] = piece; out[7] = 1;
+    }
+    out[0] = gy; out[1] = per;
 }
 
 }  // namespace svdf
