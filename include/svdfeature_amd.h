@@ -368,7 +368,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 40 of the sections under 38 / 39, those ranked with a user row built from a feedback list (the _fb calls on user-group trainers),
  * 41 .. 43 see the _lines, _cand and _sampled calls below,
  * 44 / 45 passes built from a pair source (svdf_dataset_from_pair_source) without the pair columns leaving HBM / through
- * svdf_dataset_from_pairs' own builder on the columns copied back */
+ * svdf_dataset_from_pairs' own builder on the columns copied back,
+ * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -480,6 +481,10 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     rank_eval_budget 4194304   svdf_rank_eval_positions: positives + distinct banned ids + sections processed per piece of whole sections (>= 1)
  *     rank_topn_budget 33554432  svdf_rank_topn: 64-bit keys (8 bytes each) of the selection's list workspace; a call that needs more takes fewer
  *                                item ranges per section first, then pieces of whole sections (>= 1; results do not depend on it)
+ *     pair_hard_form      0      the kernel of a hard pass of a pair source (svdf_dataset_from_pair_source_hard): 0 the measured
+ *                                choice (the staged form up to num_cand 16 at num_factor <= 32, up to 4 at <= 128, for 2 at <= 256, the lane form
+ *                                otherwise; profiles/r34_pair_hard.md), 1 one lane per candidate with both rows read where they lie, 2 the item
+ *                                rows staged in the wave's LDS (num_factor > 256 always takes 1).  Same bits
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
  * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
@@ -859,6 +864,57 @@ svdf_dataset *svdf_dataset_from_pair_source(svdf_trainer *t, svdf_pair_source *s
 int svdf_pair_source_draw(svdf_trainer *t, svdf_pair_source *s, int num_neg, uint64_t seed, unsigned *neg_out);
 int svdf_pair_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, uint64_t seed,
                         unsigned *neg_out);
+
+/* ---- HARD negatives for those passes: the best of num_cand draws by live score.  After a few rounds almost every
+ * uniform negative scores far below its positive and its gradient is nearly zero; dynamic negative sampling draws a handful of candidates
+ * per positive, scores them with the current model and trains against the best-scoring one.  A hard pass does that in ONE kernel in HBM.
+ * THE RULE.  A hard pass has num_neg = m pairs per row and num_cand = C candidates per pair; pair q = r * m + j of row (user_r, pos_r):
+ *   candidates  cand(q, i), i = 0 .. C-1, is the negative the rule ABOVE gives pair index q * C + i of a plain pass with m * C negatives per
+ *               row and the same seed: cand(q, i) = svdf_pair_negatives(..., num_neg = m * C, seed)[q * C + i].  No new stream, salt or
+ *               constant; candidates are outside P(user_r) by construction; repeats among them are allowed; the bound of 4096 draws and the
+ *               exhaustion message are the plain pass's, naming the plain-rule pair index q * C + i.
+ *   score       score(q, i) = the live-model score of svdf_rank_topn for user user_r and item cand(q, i): i_bias[c] + <W_user[u], W_item[c]>
+ *               in float32, every multiply and add rounded separately (no fma): four serial chains a0 .. a3 over the 4-float chunks
+ *               (a_t += p[4 j + t] * v[4 j + t]), (a0 + a2) + (a1 + a3), then the up to three tail products added in index order, then
+ *               0 + (i_bias + sum).  No user bias, no global bias.  The live model is the model as every call issued earlier on the
+ *               trainer's stream leaves it.
+ *   selection   neg_q = the candidate with the largest rank key (score, id) among the candidates whose score is not NaN: a higher score
+ *               wins; equal scores, +0 == -0, go to the SMALLER item id -- so the result is an id and does not depend on which of two equal
+ *               candidates is "first".  +-inf are ordinary scores.  If every candidate scores NaN, neg_q = cand(q, 0).
+ *   C = 1 gives the plain pass with num_neg = m, bit for bit.
+ * The chosen score (score_out) is score(q, i) of the chosen candidate as computed, -0 kept; where it is a NaN only its being a NaN is
+ * specified, not its sign or payload.
+ * PINNED VECTORS (seed 12345, num_item 1200, rows (user, pos) = (4, 10), (4, 700), (9, 10)): m = 1, C = 2 has the candidates
+ *   pair 0: 607, 549;  pair 1: 766, 1010;  pair 2: 64, 448 -- the six ids pinned above for num_neg 2 -- so with a model whose scores grow
+ *   with the item id (W = 0, i_bias[c] = c) the negatives are 607, 1010, 448, and with one whose scores fall with it 549, 766, 64.
+ * REFUSED on the host, before any device work and before "needs a GPU", each behind "pair_source: ":
+ *   num_neg outside 1 .. 256                  "pair_source: num_neg must be between 1 and 256"
+ *   num_cand outside 1 .. 256                 "pair_source: num_cand must be between 1 and 256"
+ *   num_neg * num_cand > 256                  "pair_source: num_neg * num_cand must be at most 256"
+ *   n * num_neg * num_cand >= 2^31 - 16       "pair_source: n * num_neg * num_cand must stay below 2^31 - 16"
+ *   a source of another trainer               "pair_source: the source was created on another trainer"
+ *   a trainer svdf_rank_topn does not admit on one GPU (format_type = 1 or extend_type != 0, side tables, common_latent_space, amd:gpus > 1,
+ *   a rank handle), in that call's words behind "pair_source: " -- one function admits both.  Every num_factor of the model (1 .. 1024) is
+ *   accepted.  svdf_pair_hard_negatives also refuses num_factor outside 1 .. 1024 ("pair_source: hard negatives need num_factor between 1
+ *   and 1024").
+ * svdf_dataset_from_pair_source_hard returns the data set svdf_dataset_from_pairs builds from (user, pos, neg) of the rule: the same kind,
+ * the same schedule or windows, the same trained bits.  Only the step that fills the three columns differs from the plain pass: routes,
+ * fallback, refusals and counters 44 / 45 are the plain pass's; counter 46 counts the hard passes among them.  One kernel (k_pair_hard)
+ * draws, scores and selects: candidate ids and scores never reach HBM.  Its two forms give the same bits; knob `pair_hard_form` chooses.
+ * svdf_pair_source_draw_hard copies the chosen column (and, where score_out is not NULL, the chosen scores) to the host;
+ * svdf_pair_hard_negatives is the rule on the host over dense row-major arrays W_user[num_user][num_factor], W_item[num_item][num_factor]
+ * and i_bias[num_item] -- no GPU, no handle, the same validation.  No older entry point changes.
+ * MEASURED (one MI355X, 100 K users x 10 K items, 20 M shuffled positives, num_neg 1, round against round with the plain pass of the same
+ * build, medians of five; profiles/r34_pair_hard.md): num_cand 8 at num_factor 128 adds 32 ms to the 0.280 s round of the exact pass and
+ * 36 ms to the 0.179 s round under `amd:step = minibatch`; num_cand 2 adds 13 / 20 ms, num_cand 16 78 / 63 ms.  k_pair_hard takes 29.8 ms
+ * there for num_cand 8 (82 GB of item rows from the caches at 2.75 TB/s).  On a planted set, from a cold start, num_cand 8 trained a WORSE
+ * ranker than the plain pass; hard rounds after uniform ones were not measured. */
+svdf_dataset *svdf_dataset_from_pair_source_hard(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed);
+int svdf_pair_source_draw_hard(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed,
+                               unsigned *neg_out /* [n*num_neg] */, float *score_out /* [n*num_neg] or NULL: the chosen score */);
+int svdf_pair_hard_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, int num_cand,
+                             uint64_t seed, int num_factor, const float *W_user, const float *W_item, const float *i_bias,
+                             unsigned *neg_out, float *score_out);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

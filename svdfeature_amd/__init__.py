@@ -165,6 +165,33 @@ def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed):
     return neg[:n * int(num_neg)]
 
 
+def _hard_size(n, num_neg, num_cand):
+    """entries of a hard pass's negative column (as _pass_size: the library refuses what is out of range before it writes)"""
+    ok = 1 <= int(num_cand) <= 256 and 1 <= int(num_neg) <= 256 and int(num_neg) * int(num_cand) <= 256
+    return n * int(num_neg) if ok and n * int(num_neg) * int(num_cand) < (1 << 31) - 16 else 0
+
+
+def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, seed, W_user, W_item, i_bias, return_scores=False):
+    """svdf_pair_hard_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed, hard=num_cand) trains against on the model
+    (W_user [num_user, k], W_item [num_item, k], i_bias [num_item]) -- per pair the best-scoring of num_cand candidates of the plain rule
+    (include/svdfeature_amd.h): uint32[n * num_neg], with return_scores also the chosen scores.  A host function: no GPU, no
+    handle."""
+    lib = load_library()
+    n, user, pos_item = _pair_rows(user, pos_item)
+    W_user, W_item = np.ascontiguousarray(W_user, np.float32), np.ascontiguousarray(W_item, np.float32)
+    i_bias = np.ascontiguousarray(i_bias, np.float32).reshape(-1)
+    if W_user.ndim != 2 or W_item.ndim != 2 or W_user.shape != (int(num_user), W_item.shape[1]) or W_item.shape[0] != int(num_item) or len(i_bias) != int(num_item):
+        raise SvdfError("pair_source: W_user, W_item and i_bias must be [num_user, k], [num_item, k] and [num_item]")
+    size = max(_hard_size(n, num_neg, num_cand), 1)
+    neg, score = np.zeros(size, np.uint32), np.zeros(size, np.float32)
+    if lib.svdf_pair_hard_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), int(num_cand), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    W_item.shape[1], _pad(W_user, np.float32), _pad(W_item, np.float32), _pad(i_bias, np.float32), neg,
+                                    _opt_ptr(score if return_scores else None)) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    N = n * int(num_neg)
+    return (neg[:N], score[:N]) if return_scores else neg[:N]
+
+
 def _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item):
     """the positives and bans of S sections as the arrays the sampled calls take (ban_ptr = None: two None); the library reads as many ids
     as the pointers say, so arrays shorter than that are refused here"""
@@ -326,6 +353,11 @@ def load_library():
     lib.svdf_dataset_from_pair_source.argtypes = [P, P, C.c_int, C.c_uint64]
     lib.svdf_pair_source_draw.argtypes = [P, P, C.c_int, C.c_uint64, _u32p]
     lib.svdf_pair_negatives.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, C.c_int, C.c_uint64, _u32p]
+    lib.svdf_dataset_from_pair_source_hard.restype = P
+    lib.svdf_dataset_from_pair_source_hard.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64]
+    lib.svdf_pair_source_draw_hard.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64, _u32p, C.c_void_p]
+    lib.svdf_pair_hard_negatives.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, C.c_int, C.c_int, C.c_uint64, C.c_int, _f32p, _f32p, _f32p, _u32p,
+                                             C.c_void_p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -765,19 +797,34 @@ class Trainer:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return PairSource(self, h, n)
 
-    def dataset_from_pair_source(self, src, num_neg=1, seed=0):
+    def dataset_from_pair_source(self, src, num_neg=1, seed=0, hard=None):
         """One pass over the source's rows with num_neg negatives each, drawn on the device from (seed, pair index): the data set
-        dataset_from_pairs builds from pair_negatives(...)'s column, without that column crossing PCIe where a route allows."""
-        h = self.lib.svdf_dataset_from_pair_source(self.h, src.h, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        dataset_from_pairs builds from pair_negatives(...)'s column, without that column crossing PCIe where a route allows.
+        hard=C: every negative is the best-scoring of C drawn candidates on the live model (pair_hard_negatives' column)."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if hard is None:
+            h = self.lib.svdf_dataset_from_pair_source(self.h, src.h, int(num_neg), seed)
+        else:
+            h = self.lib.svdf_dataset_from_pair_source_hard(self.h, src.h, int(num_neg), int(hard), seed)
         if not h:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return Dataset(self, h)
 
-    def pair_source_draw(self, src, num_neg, seed):
-        """the negative column the device draws for such a pass: uint32[n * num_neg]"""
-        neg = np.zeros(max(_pass_size(src.num_row, num_neg), 1), np.uint32)
-        self._ok(self.lib.svdf_pair_source_draw(self.h, src.h, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF, neg))
-        return neg[:src.num_row * int(num_neg)]
+    def pair_source_draw(self, src, num_neg, seed, hard=None, return_scores=False):
+        """the negative column the device draws for such a pass: uint32[n * num_neg]; with hard=C the best of C candidates per pair and,
+        with return_scores, (negatives, float32 scores of the chosen candidates)"""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if hard is None:
+            if return_scores:
+                raise SvdfError("pair_source: return_scores needs hard=")
+            neg = np.zeros(max(_pass_size(src.num_row, num_neg), 1), np.uint32)
+            self._ok(self.lib.svdf_pair_source_draw(self.h, src.h, int(num_neg), seed, neg))
+            return neg[:src.num_row * int(num_neg)]
+        size = max(_hard_size(src.num_row, num_neg, hard), 1)
+        neg, score = np.zeros(size, np.uint32), np.zeros(size, np.float32)
+        self._ok(self.lib.svdf_pair_source_draw_hard(self.h, src.h, int(num_neg), int(hard), seed, neg, _opt_ptr(score if return_scores else None)))
+        N = src.num_row * int(num_neg)
+        return (neg[:N], score[:N]) if return_scores else neg[:N]
 
     def dataset_from_blocks(self, blocks):
         """blocks: list of PlusBlock in file order (one pass of a user-group buffer), or a flat BlockArrays."""

@@ -10,7 +10,7 @@
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
 #include "svdf_ranklines_lists.h"
-#include "svdf_pairsource_lists.h"
+#include "svdf_pairhard_lists.h"
 #include "svdf_ranknegs_lists.h"
 #include "svdf_wseq_rule.h"
 
@@ -495,6 +495,32 @@ int svdf_pair_source_draw(svdf_trainer *t, svdf_pair_source *s, int num_neg, uin
 int svdf_pair_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, uint64_t seed,
                         unsigned *neg_out) {
     SVDF_GUARD(-1, { svdf::pair_src_negatives(num_user, num_item, n, user, pos_item, num_neg, seed, neg_out); return 0; })
+}
+/* ... and the hard pass: the best of num_cand candidates by live score */
+svdf_dataset *svdf_dataset_from_pair_source_hard(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed) {
+    SVDF_GUARD(nullptr, {
+        if (num_cand == 0) svdf::fail("pair_source: num_cand must be between 1 and 256");   // (0 selects the plain pass inside the engine)
+        svdf::Dataset *d = t->e->dataset_from_pair_source(s ? s->s : nullptr, num_neg, seed, num_cand);
+        t->e->note_dataset(d);
+        svdf_dataset *h = new svdf_dataset();
+        h->d = d;
+        return h;
+    })
+}
+int svdf_pair_source_draw_hard(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed, unsigned *neg_out, float *score_out) {
+    SVDF_GUARD(-1, {
+        if (num_cand == 0) svdf::fail("pair_source: num_cand must be between 1 and 256");
+        t->e->pair_source_draw(s ? s->s : nullptr, num_neg, seed, neg_out, num_cand, score_out);
+        return 0;
+    })
+}
+int svdf_pair_hard_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, int num_cand,
+                             uint64_t seed, int num_factor, const float *W_user, const float *W_item, const float *i_bias, unsigned *neg_out,
+                             float *score_out) {
+    SVDF_GUARD(-1, {
+        svdf::pair_hard_negatives(num_user, num_item, n, user, pos_item, num_neg, num_cand, seed, num_factor, W_user, W_item, i_bias, neg_out, score_out);
+        return 0;
+    })
 }
 
 /* ---- ISVDRanker ---- */

@@ -521,8 +521,9 @@ class Engine {
     // passes of rank pairs from positives only, the negatives drawn on the device (svdf_pairsource.cpp, svdf_k_pairdraw.hip; DESIGN.md
     // section 6ac).  A source belongs to the handle it was created on and may outlive it.
     PairSource *pair_source_create(long n, const unsigned *user, const unsigned *pos);
-    Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed);
-    void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out);
+    // num_cand = 0: the plain pass; >= 1: the hard pass, the best of num_cand candidates by live score
+    Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand = 0);
+    void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand = 0, float *score_out = nullptr);
     void pair_source_forget(PairSource *src);   // (the source is being destroyed)
 
     // multi-GPU item-side delta
@@ -999,8 +1000,14 @@ class Engine {
     int64_t n_pair_src_hbm_ = 0;       // counter 44: passes built from a pair source without the pair columns leaving HBM
     int64_t n_pair_src_fallback_ = 0;  // counter 45: passes built from a pair source through dataset_from_pairs on host columns
     std::vector<PairSource *> pair_sources_;   // the live sources of this handle: forgotten (owner = nullptr) when the handle goes
-    // the pass's columns [n * num_neg] drawn into HBM (user / pos may be nullptr); a pair that exhausted its draws fails the call
-    void pair_source_launch(const PairSource &src, int num_neg, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg);
+    int64_t n_pair_src_hard_ = 0;      // counter 46: of the passes under 44 / 45, the hard ones (section 6ad)
+    long pair_hard_form_ = 0;          // knob pair_hard_form: 0 the measured choice, 1 a lane per candidate, 2 the staged kernel
+    // what every pass refuses, on the host, before any device work (num_cand = 0: the plain pass)
+    void pair_source_admit(const PairSource *src, int num_neg, int num_cand);
+    // the pass's columns [n * num_neg] filled in HBM by the plain rule (num_cand = 0) or the hard one (user / pos may be nullptr; score only
+    // with the hard rule); an entry that exhausted its draws fails the call
+    void pair_source_launch(const PairSource &src, int num_neg, int num_cand, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg,
+                            float *d_score);
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -412,5 +412,16 @@ struct PairDrawDev {
 };
 void launch_pair_draw(const PairDrawDev &D, hipStream_t st);   // one launch, a lane per pair
 
+// ---- the hard pass of a pair source (svdf_k_pairhard.hip): pair q takes the best-scoring of its num_cand candidates,
+// candidate i of pair q being the plain rule's negative of pair index q * num_cand + i.  D.npair counts the PAIRS of the pass (n * num_neg);
+// npair * num_cand stays below 2^31 - 16.  The flag names an exhausted ENTRY: q * num_cand + i + 1.
+struct PairHardDev {
+    PairDrawDev D;
+    int num_cand;              // 1 .. PAIR_HARD_MAX_CAND
+    float *out_score;          // [npair] the chosen candidate's score, or nullptr
+};
+int pair_hard_form(const DevParams &P, int form, int num_cand);   // the form a hard pass's kernel takes: 1 (a lane per entry, rows where they lie) or 2 (staged)
+void launch_pair_hard(const DevParams &P, const PairHardDev &H, int form, hipStream_t st);   // one launch, a wave owns whole pairs
+
 }  // namespace svdf
 #endif

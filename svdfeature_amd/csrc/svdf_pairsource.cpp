@@ -3,14 +3,15 @@
 // at creation, svdf_pairsource_lists.h builds the lists); a pass draws its negatives there (svdf_k_pairdraw.hip) into three columns of
 // n * num_neg entries and is built from those columns where Engine::dataset_from_pairs has a route that starts from device columns -- the
 // window sequence of svdf_wseq.cpp (section 6v's builder) and the exact level schedule of schedule_device_columns.  Everything else copies
-// the columns back and IS dataset_from_pairs on them, so no result depends on the route.
+// the columns back and IS dataset_from_pairs on them, so no result depends on the route.  A HARD pass (section 6ad, svdf_k_pairhard.hip:
+// the best of num_cand candidates by live score) differs in the step that fills the columns and in what it admits, and in nothing else.
 #include <svdfeature_amd.h>
 
 #include <memory>
 
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
-#include "svdf_pairsource_lists.h"
+#include "svdf_pairhard_lists.h"
 
 namespace svdf {
 
@@ -54,11 +55,16 @@ PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsig
     return src.release();
 }
 
-void Engine::pair_source_launch(const PairSource &src, int num_neg, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg) {
+// The step that fills a pass's columns, and the only one that differs between the plain pass (num_cand = 0: k_pair_draw) and the hard one
+// (section 6ad: k_pair_hard draws num_cand candidates per pair, scores them with the model as every call issued earlier on the trainer's
+// stream leaves it, and keeps the best).
+void Engine::pair_source_launch(const PairSource &src, int num_neg, int num_cand, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg,
+                                float *d_score) {
     DevBuf<unsigned> flag;
     pair_src_reserve(flag, 1, "the flag");
     HIPCHECK(hipMemsetAsync(flag.p, 0, sizeof(unsigned), stream_));
-    PairDrawDev D;
+    PairHardDev H;
+    PairDrawDev &D = H.D;
     D.npair = src.n * (long)num_neg;
     D.num_neg = num_neg;
     D.seed = seed;
@@ -66,7 +72,11 @@ void Engine::pair_source_launch(const PairSource &src, int num_neg, uint64_t see
     D.user = src.user.p; D.pos = src.pos.p; D.uptr = src.uptr.p; D.uitems = src.uitems.p;
     D.out_user = d_user; D.out_pos = d_pos; D.out_neg = d_neg;
     D.flag = flag.p;
-    launch_pair_draw(D, stream_);
+    H.num_cand = num_cand; H.out_score = d_score;
+    if (num_cand > 0) {
+        flush();   // behind whatever has been staged
+        launch_pair_hard(params(), H, (int)pair_hard_form_, stream_);
+    } else launch_pair_draw(D, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_++;
     unsigned spent = 0;
@@ -75,27 +85,33 @@ void Engine::pair_source_launch(const PairSource &src, int num_neg, uint64_t see
     if (spent) fail("pair_source: pair " + std::to_string((long)spent - 1) + " found no negative in " + std::to_string(PAIR_SRC_DRAWS) + " draws");
 }
 
-// what every pass refuses, on the host, before any device work
-static void pair_src_admit(const Engine *e, const PairSource *src, int num_neg) {
+// what every pass refuses, on the host, before any device work.  A hard pass scores with svdf_rank_topn's kernels' arithmetic on the
+// trainer's own rows: its trainer is one that call admits (rank_live_refusals: format_type = 0, extend_type = 0, no side tables, one GPU).
+void Engine::pair_source_admit(const PairSource *src, int num_neg, int num_cand) {
     if (!src) fail("pair_source: bad arguments");
-    if (src->owner != e) fail("pair_source: the source was created on another trainer");
-    pair_src_check_pass(src->n, num_neg);
+    if (src->owner != this) fail("pair_source: the source was created on another trainer");
+    if (num_cand == 0) { pair_src_check_pass(src->n, num_neg); return; }
+    pair_hard_check_pass(src->n, num_neg, num_cand);
+    rank_live_refusals("pair_source");
 }
 
-void Engine::pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out) {
-    pair_src_admit(this, src, num_neg);
+void Engine::pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand, float *score_out) {
+    pair_source_admit(src, num_neg, num_cand);
     check(neg_out != nullptr, "pair_source: bad arguments");
     need_device("pair_source");
     const size_t N = (size_t)src->n * (size_t)num_neg;
     DevBuf<unsigned> neg;
+    DevBuf<float> score;
     pair_src_reserve(neg, N, "the negative column of a pass");
-    pair_source_launch(*src, num_neg, seed, nullptr, nullptr, neg.p);
+    if (score_out) pair_src_reserve(score, N, "the score column of a pass");
+    pair_source_launch(*src, num_neg, num_cand, seed, nullptr, nullptr, neg.p, score_out ? score.p : nullptr);
     HIPCHECK(hipMemcpyAsync(neg_out, neg.p, N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    if (score_out) HIPCHECK(hipMemcpyAsync(score_out, score.p, N * sizeof(float), hipMemcpyDeviceToHost, stream_));
     HIPCHECK(hipStreamSynchronize(stream_));
 }
 
-Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed) {
-    pair_src_admit(this, src, num_neg);
+Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand) {
+    pair_source_admit(src, num_neg, num_cand);
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
     const long N = src->n * (long)num_neg;
@@ -113,7 +129,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     pair_src_reserve(cu, (size_t)N, "the user column of a pass");
     pair_src_reserve(cp, (size_t)N, "the positive column of a pass");
     pair_src_reserve(cq, (size_t)N, "the negative column of a pass");
-    pair_source_launch(*src, num_neg, seed, cu.p, cp.p, cq.p);
+    pair_source_launch(*src, num_neg, num_cand, seed, cu.p, cp.p, cq.p, nullptr);
     if (!windows_hbm && !exact_hbm) {   // dataset_from_pairs itself, on the columns copied back
         std::vector<unsigned> hu((size_t)N), hp((size_t)N), hq((size_t)N);
         HIPCHECK(hipMemcpyAsync(hu.data(), cu.p, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
@@ -123,12 +139,14 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
         cu.release(); cp.release(); cq.release();
         Dataset *ds = dataset_from_pairs(N, hu.data(), hp.data(), hq.data());
         n_pair_src_fallback_++;
+        n_pair_src_hard_ += num_cand > 0;
         return ds;
     }
     if (windows_hbm) {   // section 6v's builder on the pos / neg columns as drawn: item counts, window rule and windows from where they are
         Dataset *seq = wseq_from_device_pairs(N, cu.p, cp.p, nullptr, cq.p);
         if (!seq) fail("pair_source: the drawn columns hold an id the windows refuse");   // (validated ids, pos != neg: not reached)
         n_pair_src_hbm_++;
+        n_pair_src_hard_ += num_cand > 0;
         return seq;
     }
     // ---- the merged, index-sorted form the level schedule starts from: lower / higher item id and the entries' signs (pos != neg by the rule)
@@ -156,6 +174,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     const long nb2 = (mp_.no_user_bias ? 0 : 1) + 2;
     ds->algorithmic_bytes = N * (8L * mp_.num_factor * 3 + 8 * nb2 + 16 + 8 * 3);
     n_pair_src_hbm_++;
+    n_pair_src_hard_ += num_cand > 0;
     return ds.release();
 }
 
