@@ -384,6 +384,19 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     xcd_remap           1      blockIdx -> tile mapping that keeps neighbouring tiles on one XCD's L2 (0 = plain)
  *     load_mode           2      row gathers: 0 plain, 1 nontemporal, 2 = by row size
  *     store_mode          0      row stores: 0 plain, 1 nontemporal, 2 write-through
+ *       These five shape the launch of ONE level by the level kernels; which forms each reaches (svdf_level_geometry reports it per launch):
+ *         groups_per_wave  every k_basicmf / k_basicmf_slots form takes the value as it is (auto: 4 at 16 lanes per row, 2 at 64 lanes, 1 below and
+ *                          for the sixteen-lane slots form; the eight-lane slots form min(4, max(1, (n + 7200) / 14400)) for a level of n).  k_fused
+ *                          with at most three id slots folds every value >= 2 to 2 (auto: 2 at 16 lanes, else 1); k_fused with 2 + 2 slots, its
+ *                          hot-reduce form and the few-row fast forms (k_fewrow_fast, k_fewrow_slots) ignore it: one row set per wave
+ *         block_threads    every form but k_fused's hot-reduce form (1024 threads); auto: 64, but 256 for k_basicmf off 16 lanes per row
+ *         xcd_remap        every form: the grid is padded to a multiple of 8 and the tiles permuted
+ *         load_mode        k_basicmf, k_fused and k_fewrow_fast; the slots forms (k_basicmf_slots with eight and with sixteen lanes, k_fewrow_slots)
+ *                          always gather nontemporal
+ *         store_mode       the general instruction stream of k_basicmf only: a value other than 0 leaves the FAST and slots forms of the contract
+ *                          configuration (and the chained and runs forms) for that stream; every other form stores plain and the few-row
+ *                          launchers ignore the knob
+ *       The chained launches (chain_width), the inline-global few-row form (fewrow_gslots), the runs pass and the hot-row units read none of them.
  *     sort_batches        1      order inside a conflict-free level: 0 file order, 1 by item, 2 by user
  *     chain_width         128    levels of at most this many instances are walked inside ONE launch by one workgroup (0 = a launch per level)
  *   kernel routing (0 = the more general kernel; same bits)
@@ -939,6 +952,21 @@ int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, f
  * its tiles, its sections (0 for kind 0 without pos_ptr), launches of the sweep (the wide evaluation sweep takes one per 32768 rows).
  * A test asserts with it that its shapes reach the geometry it is about.  -1 on bad arguments. */
 int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const int64_t *pos_ptr, long *out);
+
+/* ---- probe of the launch choice of the level kernels of the exact pass, for tests: what one conflict-free level of n
+ * instances would be launched as on this trainer -- by launch_basicmf (launcher 0: one user id, one item id; unit_values: every feature
+ * value is 1) or by launch_fused (launcher 1: at most max_nu and max_ni ids, each 1 or 2; has_globals: the data set has global features) --,
+ * computed by the very functions those launchers use.  Host function, no device work: a host-only handle answers it, before init_model too;
+ * only the parameters and the knobs matter.  out[0 .. 19] =
+ *    0 form: 1 k_basicmf FULL / FAST, 2 k_basicmf general stream with unit values, 3 k_basicmf with feature values, 4 k_basicmf_slots eight lanes
+ *      (k = 64), 5 k_basicmf_slots sixteen lanes (k = 256), 6 k_fused, 7 k_fused hot-reduce, 8 k_fewrow_fast, 9 k_fewrow_slots sixteen lanes (k = 128)
+ *    1 lane class of the width, 2 lanes per row, 3 chunks per lane, 4 full rows (no per-lane bounds test), 5 row sets per wave after folding,
+ *    6 threads per workgroup, 7 / 8 user / item slots of the few-row template, 9 instances per row set, 10 instances per workgroup,
+ *    11 workgroups with work, 12 workgroups launched, 13 XCD remap on, 14 row gathers (0 plain, 1 nontemporal), 15 row stores (0, 1, 2),
+ *    16 the knobs the launch reads (1 groups_per_wave, 2 block_threads, 4 xcd_remap, 8 load_mode, 16 store_mode),
+ *    17 dynamic LDS bytes, 18 the configuration has a chained form, 19 the widest level handed to it (0: none; chain_width)
+ * -1 on bad arguments. */
+int svdf_level_geometry(svdf_trainer *t, int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out);
 
 /* ---- probes of the window rule of `amd:step = minibatch` (svdf_wseq_rule.h): into how many windows a pass is cut, from knob values and
  * counts alone.  Host functions, no handle and no GPU; the data-set builders reach the same functions.  Tests compare them with

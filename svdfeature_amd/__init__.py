@@ -375,6 +375,7 @@ def load_library():
     lib.svdf_rand_peek.argtypes = [C.c_long, _i32p]
     lib.svdf_rand_skip.argtypes = [C.c_long]
     lib.svdf_rank_geometry.argtypes = [P, C.c_int, C.c_long, C.c_int, C.c_void_p, C.POINTER(C.c_long)]
+    lib.svdf_level_geometry.argtypes = [P, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long)]
     lib.svdf_device_expf.argtypes = [C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_long]
     lib.svdf_window_rule.restype = C.c_long
     lib.svdf_window_rule.argtypes = [C.c_int, C.POINTER(WindowRuleIn)]
@@ -1183,6 +1184,23 @@ class Trainer:
                 raise SvdfError("rank_geometry: pos_ptr must have one entry more than sections")
         self._ok(self.lib.svdf_rank_geometry(self.h, {"positions": 0, "topn": 1}[kind], int(units), int(top_n), _opt_ptr(ptr), out))
         return dict(zip(("gy", "items_per_block", "cap", "tile_rows", "rows", "tiles", "sections", "launches"), (int(v) for v in out)))
+
+    LEVEL_FORMS = (None, "basic_fast", "basic_unit", "basic_values", "basic_slots8", "basic_slots16", "fused", "fused_hot", "fewrow_fast", "fewrow_slots16")
+    LEVEL_KNOBS = ("groups_per_wave", "block_threads", "xcd_remap", "load_mode", "store_mode")
+
+    def level_geometry(self, launcher, n, max_nu=1, max_ni=1, unit_values=True, has_globals=False):
+        """svdf_level_geometry, a test probe that needs no device: what one conflict-free level of n instances would be launched as on this
+        trainer by launch_basicmf (launcher "basic") or launch_fused (launcher "fewrow", with the few-row shape max_nu, max_ni), from the
+        functions the launchers use.  A dict: form (a name of LEVEL_FORMS), lane_class, lanes, chunks, full, groups, block, nu, ni, per_set,
+        per_block, grid_work, grid, remap, load, store, knobs (the names of the tuning knobs the launch reads), lds, chain, chain_cap."""
+        out = (C.c_long * 20)()
+        self._ok(self.lib.svdf_level_geometry(self.h, {"basic": 0, "fewrow": 1}[launcher], int(n), int(max_nu), int(max_ni), int(bool(unit_values)),
+                                              int(bool(has_globals)), out))
+        g = dict(zip(("form", "lane_class", "lanes", "chunks", "full", "groups", "block", "nu", "ni", "per_set", "per_block", "grid_work", "grid", "remap",
+                      "load", "store", "knobs", "lds", "chain", "chain_cap"), (int(v) for v in out)))
+        g["form"] = self.LEVEL_FORMS[g["form"]]
+        g["knobs"] = tuple(name for b, name in enumerate(self.LEVEL_KNOBS) if g["knobs"] >> b & 1)
+        return g
 
 
 _libc.fwrite.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]

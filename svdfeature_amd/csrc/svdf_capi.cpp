@@ -562,6 +562,10 @@ int svdf_device_expf(const float *in, unsigned first_bits, unsigned step_bits, f
     SVDF_GUARD(-1, { return svdf::device_expf(in, first_bits, step_bits, out, n); })
 }
 
+// the launch choice of the level kernels exposed for tests (tests/test_level_geometry.py): Engine::level_geometry
+int svdf_level_geometry(svdf_trainer *t, int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out) {
+    SVDF_GUARD(-1, { t->e->level_geometry(launcher, n, max_nu, max_ni, unit_values, has_globals, out); return 0; })
+}
 // the launch geometry of the live-model ranking calls exposed for tests (tests/test_rank_geometry.py): Engine::rank_geometry
 int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const int64_t *pos_ptr, long *out) {
     SVDF_GUARD(-1, { t->e->rank_geometry(kind, units, top_n, pos_ptr, out); return 0; })

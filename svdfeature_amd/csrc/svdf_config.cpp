@@ -331,4 +331,24 @@ int Engine::set_knob(const char *name, long value) {
     return -1;
 }
 
+// The test probe svdf_level_geometry: what launch_basicmf (launcher 0) or launch_fused (launcher 1) would launch for a level of n instances
+// under this handle's configuration and knobs, from the functions the launchers call (svdf_level_geometry.h), without a device.  Only
+// parameters and knobs matter, so init_model need not have run.
+void Engine::level_geometry(int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out) {
+    check((launcher == 0 || launcher == 1) && n >= 1 && out, "level_geometry: bad arguments");
+    check(launcher == 0 || (max_nu >= 1 && max_nu <= 2 && max_ni >= 1 && max_ni <= 2), "level_geometry: the few-row shape is 1 or 2 user ids and 1 or 2 item ids");
+    check(mp_.num_factor >= 1 && mp_.num_factor <= max_fast_path_factor(), "level_geometry: set num_factor first (1 .. 256: the level kernels' widths)");
+    DevParams P;
+    memset(&P, 0, sizeof(P));
+    level_config(P, row_pitch(mp_.num_factor));
+    const LevelShape sh = launcher == 0 ? basicmf_level_shape(P, unit_values != 0, n, groups_per_wave_, block_threads_)
+                                        : fused_level_shape(P, has_globals != 0, max_nu, max_ni, n, groups_per_wave_, block_threads_);
+    // levels of at most out[19] instances go to the chained launch instead when four or more of them follow each other (train_dataset)
+    const bool chain = launcher == 0 ? basicmf_chain_applies(P, unit_values != 0) : fewrow_chain_applies(P, has_globals != 0);
+    const long cap = !chain ? 0 : (launcher == 0 ? std::min<long>(chain_width_, 128) : chain_width_);
+    const long v[20] = {sh.form, sh.lpi, sh.lanes, sh.chunks, sh.full, sh.groups, sh.block, sh.nu, sh.ni, sh.per_set, sh.per_block, sh.grid_work, sh.grid,
+                        sh.remap, sh.load, sh.store, sh.knobs, (long)sh.lds, chain ? 1 : 0, cap};
+    for (int i = 0; i < 20; i++) out[i] = v[i];
+}
+
 }  // namespace svdf

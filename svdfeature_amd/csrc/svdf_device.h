@@ -429,7 +429,8 @@ __device__ __forceinline__ void store_row(float *W, size_t row, int pitch, int L
     *reinterpret_cast<float4 *>(W + row * (size_t)pitch + (size_t)L * 4) = v;
 }
 
-// row load with the nontemporal hint (load_mode knob, k_basicmf only: rows of a level are read once)
+// row load with the nontemporal hint (load_mode knob: k_basicmf, k_fused and k_fewrow_fast read it; the slots forms always load this way:
+// rows of a level are read once)
 typedef float svdf_f4_ld __attribute__((ext_vector_type(4)));
 template <int LPI>
 __device__ __forceinline__ float4 load_row_nt(const float *W, size_t row, int pitch, int L, int k) {

@@ -208,29 +208,39 @@ void Engine::finish_round() {
     if (trainer_ready_ && !host_only_) flush();
 }
 
+// What the launch choice of the level kernels reads of a DevParams, all of it known on the host: params() and the probe level_geometry
+// (svdf_config.cpp) both fill it here.  (params() replaces the range counts by the uploaded ranges of the same counts.)
+void Engine::level_config(DevParams &P, int pitch) const {
+    P.pitch = pitch; P.k = mp_.num_factor;
+    P.active_type = mtype_.active_type; P.no_user_bias = mp_.no_user_bias; P.user_nonnegative = mp_.user_nonnegative;
+    P.store_mode = store_mode_;
+    P.load_mode = level_load_mode(load_mode_, pitch);   // auto: nontemporal row gathers for rows of two cache lines or more
+    P.basic_i8 = basic_i8_;
+    P.fewrow_i16 = fewrow_i16_;
+    P.xcd_remap = xcd_remap_;
+    P.fewrow_fast = fewrow_fast_ ? 1 : 0;
+    P.hot_reduce = hot_reduce_; P.relax_global = relax_global_ ? 1 : 0;
+    P.relax_user_from = relax_user_from_; P.relax_item_from = relax_item_from_;
+    P.reg_method = tp_.reg_method;
+    P.u_rng.n = (int)u_param_.bound.size(); P.i_rng.n = (int)i_param_.bound.size();
+}
+
 const DevParams &Engine::params() {
     if (!params_dirty_) return dev_params_;
     need_device("building kernel parameters");
     DevParams &P = dev_params_;
     memset(&P, 0, sizeof(P));
     P.W = dW_.p; P.bias = dbias_.p; P.g_bias = dg_.p; P.svdpp_state = dstate_.p;
-    P.pitch = pitch_; P.k = mp_.num_factor;
+    level_config(P, pitch_);   // the fields the launch choice of the level kernels reads (svdf_level_geometry.h); the probe fills the same
     P.user_off = user_off_; P.item_off = item_off_; P.fb_off = fb_off_;
     P.num_user = mp_.num_user; P.num_item = mp_.num_item; P.num_global = mp_.num_global; P.num_ufeedback = mp_.num_ufeedback;
     P.base_score = mp_.base_score;
-    P.active_type = mtype_.active_type; P.no_user_bias = mp_.no_user_bias; P.user_nonnegative = mp_.user_nonnegative;
     P.user_group = user_group() ? 1 : 0;
-    P.store_mode = store_mode_;
-    P.load_mode = load_mode_ == 2 ? (pitch_ >= 64 ? 1 : 0) : load_mode_;   // auto: nontemporal row gathers for rows of two cache lines or more
-    P.basic_i8 = basic_i8_;
     P.small_blocks = small_blocks_;
     P.svdpp_helpers = svdpp_helpers_;
-    P.fewrow_i16 = fewrow_i16_;
-    P.xcd_remap = xcd_remap_;
     P.imfb_disable = imfb_disable_;
     P.imfb_deep = imfb_deep_ ? 1 : 0;
-    P.fewrow_fast = fewrow_fast_ ? 1 : 0;
-    P.hot_reduce = hot_reduce_; P.relax_global = relax_global_ ? 1 : 0; P.relax_feedback = relax_feedback_ ? 1 : 0;
+    P.relax_feedback = relax_feedback_ ? 1 : 0;
     if (device_model_ && g_stride_ != wanted_g_stride() && mp_.num_global > 0) {   // relax_global switched after the upload: re-lay out
         std::vector<float> g((size_t)mp_.num_global);
         download_globals(g.data());
@@ -240,10 +250,10 @@ const DevParams &Engine::params() {
         HIPCHECK(hipStreamSynchronize(stream_));
         std::swap(g, hg_);
     }
-    P.g_stride = g_stride_; P.g_bias = dg_.p; P.relax_user_from = relax_user_from_; P.relax_item_from = relax_item_from_;
+    P.g_stride = g_stride_; P.g_bias = dg_.p;
     P.lr = tp_.learning_rate; P.wd_user = tp_.wd_user; P.wd_item = tp_.wd_item;
     P.wd_user_bias = tp_.wd_user_bias; P.wd_item_bias = tp_.wd_item_bias; P.wd_global = tp_.wd_global;
-    P.reg_method = tp_.reg_method; P.reg_global = tp_.reg_global; P.num_regfree_global = tp_.num_regfree_global;
+    P.reg_global = tp_.reg_global; P.num_regfree_global = tp_.num_regfree_global;
     check(tp_.reg_method >= 0 && tp_.reg_method <= 5, "unknown reg_method");
     check(tp_.reg_global == 0 || tp_.reg_global == 1 || tp_.reg_global == 4 || tp_.reg_global == 5, "unknown global decay method");
     if (tp_.reg_method >= 4 && !d_ref_ui_.p) {        // one word per W_uiset row: with common_latent_space users and items

@@ -505,6 +505,8 @@ class Engine {
                        const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
                        int *nan_out, const RankLines *lines = nullptr);
     void rank_geometry(int kind, long units, int top_n, const int64_t *pos_ptr, long *out);   // test probe (svdf_rank_geometry): host only
+    void level_geometry(int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out);   // test probe (svdf_level_geometry): host only
+    void level_config(DevParams &P, int pitch) const;   // the DevParams fields the launch choice of the level kernels reads
     void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                        const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
     // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md

@@ -250,9 +250,7 @@ __global__ __launch_bounds__(1024) void k_basicmf_slots_chain(const DevParams P,
 }
 // a run of narrow levels [l0, l1) in one launch; false when the configuration has no chained form (the caller launches level by level)
 bool launch_basicmf_chain(const DevParams &P, const BasicSchedule &S, const long *d_level_ptr, long l0, long l1, hipStream_t st) {
-    const bool slots_cfg = P.basic_i8 && S.uval == nullptr && P.active_type == ACT_LINEAR && P.reg_method == 0 && P.no_user_bias == 0 &&
-                           P.user_nonnegative == 0 && P.u_rng.n == 0 && P.i_rng.n == 0 && P.store_mode == 0 && P.k == 64;
-    if (!slots_cfg) return false;
+    if (!basicmf_chain_applies(P, S.uval == nullptr)) return false;
     if (d_level_ptr == nullptr) return true;   // query
     hipLaunchKernelGGL((k_basicmf_slots_chain<8, 2>), dim3(1), dim3(1024), 0, st, P, S, d_level_ptr, l0, l1);
     return true;
@@ -281,34 +279,25 @@ __global__ __launch_bounds__(256) void k_predict_basic(const DevParams P, const 
     }
 }
 
+// the launch choice is basicmf_level_shape (svdf_level_geometry.h): form, row sets per wave, workgroup size, grid; here only the template dispatch
 template <int LPI>
-static void launch_basicmf_lpi(const DevParams &P, const BasicSchedule &S, long begin, long end, int G, int block_threads, hipStream_t st) {
-    const long n = end - begin;
-    const bool unit = S.uval == nullptr;
+static void launch_basicmf_lpi(const DevParams &P, const BasicSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    const dim3 grid((unsigned)sh.grid), block((unsigned)sh.block);
     auto go = [&](auto gtag) {
         constexpr int GG = decltype(gtag)::value;
-        const long per_block = (long)(block_threads / 64) * GG * (64 / LPI);
-        int grid = (int)((n + per_block - 1) / per_block);
-        if (P.xcd_remap) grid = (grid + 7) & ~7;
-        // specialised instruction stream for the configuration of the contract workload, general one otherwise
-        const bool fast = P.active_type == ACT_LINEAR && P.reg_method == 0 && P.no_user_bias == 0 && P.user_nonnegative == 0 &&
-                          P.u_rng.n == 0 && P.i_rng.n == 0 && P.store_mode == 0;
-        auto slots = [&](auto lanes, auto vv) {   // LANES lanes per row, V chunks per lane: GG row sets of 64 / LANES instances per wave
-            constexpr int LANES = decltype(lanes)::value, V = decltype(vv)::value;
-            const long per_block8 = (long)(block_threads / 64) * GG * (64 / LANES);
-            int grid8 = (int)((n + per_block8 - 1) / per_block8);
-            if (P.xcd_remap) grid8 = (grid8 + 7) & ~7;
-            hipLaunchKernelGGL((k_basicmf_slots<LANES, V, GG>), dim3(grid8), dim3(block_threads), 0, st, P, S, begin, end);
-        };
-        if (unit && fast && LPI == 16 && P.k == 64 && P.basic_i8) {
-            slots(std::integral_constant<int, 8>(), std::integral_constant<int, 2>());
-        } else if (unit && fast && LPI == 64 && P.k == 256 && P.basic_i8) {
-            slots(std::integral_constant<int, 16>(), std::integral_constant<int, 4>());
-        } else if (unit && fast && P.k == 4 * LPI) hipLaunchKernelGGL((k_basicmf<LPI, GG, true, true, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-        else if (unit) hipLaunchKernelGGL((k_basicmf<LPI, GG, true, false, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-        else hipLaunchKernelGGL((k_basicmf<LPI, GG, false, false, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
+        switch (sh.form) {
+        case LEVEL_BASIC_SLOTS8:    // LANES lanes per row, V chunks per lane: GG row sets of 64 / LANES instances per wave
+            if constexpr (LPI == 16) hipLaunchKernelGGL((k_basicmf_slots<8, 2, GG>), grid, block, 0, st, P, S, begin, end);
+            break;
+        case LEVEL_BASIC_SLOTS16:
+            if constexpr (LPI == 64) hipLaunchKernelGGL((k_basicmf_slots<16, 4, GG>), grid, block, 0, st, P, S, begin, end);
+            break;
+        case LEVEL_BASIC_FAST: hipLaunchKernelGGL((k_basicmf<LPI, GG, true, true, true>), grid, block, 0, st, P, S, begin, end); break;
+        case LEVEL_BASIC_UNIT: hipLaunchKernelGGL((k_basicmf<LPI, GG, true, false, false>), grid, block, 0, st, P, S, begin, end); break;
+        default: hipLaunchKernelGGL((k_basicmf<LPI, GG, false, false, false>), grid, block, 0, st, P, S, begin, end); break;
+        }
     };
-    switch (G) {
+    switch (sh.groups) {
     case 1: go(std::integral_constant<int, 1>()); break;
     case 2: go(std::integral_constant<int, 2>()); break;
     case 3: go(std::integral_constant<int, 3>()); break;
@@ -321,24 +310,8 @@ static void launch_basicmf_lpi(const DevParams &P, const BasicSchedule &S, long 
 
 void launch_basicmf(const DevParams &P, const BasicSchedule &S, long begin, long end, int groups_per_wave, int block_threads, hipStream_t st) {
     if (end <= begin) return;
-    // 0 = tuned default (tools/sweep_knobs.py on MI355X with the FULL/FAST specialisation): k=64 (16 lanes per row) wants
-    // 4 row sets in flight per wave in 64-thread blocks (24.9 ms/pass; 26.3 with one row set), k=256 two row sets, every
-    // other width one row set per wave in 256-thread blocks
-    const int lpi_ = lanes_per_instance(P.k);
-    // (tools/ab_knob.py, in-process A/B: k=64 8 lanes x 2 chunks with 4 row sets 23.6 vs 24.4 ms per 100 M; k=256 16 lanes x 4 chunks with
-    // one row set 18.5 vs 20.2 ms per 25 M; k=128 16 lanes x 2 chunks 22.3 vs 22.3 ms per 50 M: no gain, the lane-group kernel stays)
-    const bool slots_cfg = P.basic_i8 && S.uval == nullptr && P.active_type == ACT_LINEAR && P.reg_method == 0 && P.no_user_bias == 0 &&
-                           P.user_nonnegative == 0 && P.u_rng.n == 0 && P.i_rng.n == 0;   // the configuration k_basicmf_slots is specialised for
-    const bool slots256 = slots_cfg && P.k == 256;
-    if (groups_per_wave <= 0) {
-        groups_per_wave = lpi_ == 16 ? 4 : (lpi_ == 64 ? (slots256 ? 1 : 2) : 1);
-        // k = 64 in the 8-lane layout: 8 instances per row set.  A full-size level (53 K instances) wants 4 row sets per wave (1.6 waves
-        // per SIMD: 23.6 ms per pass against 26.6 with 2 and 27.5 with 1), the 17 K-instance levels of one rank's window of an 8-GPU
-        // run want 1 (7.66 ms per pass against 8.09 with 2 and 9.10 with 4, tools/shard8_knobs.sh): aim at ~1 800 waves per launch
-        if (slots_cfg && P.k == 64) groups_per_wave = (int)std::min<long>(4, std::max<long>(1, (end - begin + 7200) / 14400));
-    }
-    if (block_threads <= 0) block_threads = lpi_ == 16 ? 64 : 256;
-    SVDF_DISPATCH_LPI(lanes_per_instance(P.k), launch_basicmf_lpi<LPI>(P, S, begin, end, groups_per_wave, block_threads, st));
+    const LevelShape sh = basicmf_level_shape(P, S.uval == nullptr, end - begin, groups_per_wave, block_threads);
+    SVDF_DISPATCH_LPI(sh.lpi, launch_basicmf_lpi<LPI>(P, S, begin, end, sh, st));
 }
 void launch_predict_basic(const DevParams &P, const BasicSchedule &S, long n, float *out, hipStream_t st) {
     if (n <= 0) return;

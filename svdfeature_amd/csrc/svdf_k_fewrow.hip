@@ -329,41 +329,32 @@ void launch_fewrow_gslots(const DevParams &P, const FusedSchedule &S, long begin
     }
 }
 
-template <int LANES, int V, int NU, int NI>
-static void launch_fewrow_slots_shape(const DevParams &P, const FusedSchedule &S, long begin, long end, int block_threads, hipStream_t st) {
-    const long n = end - begin;
-    const long per_block = (long)(block_threads / 64) * (64 / LANES);
-    int grid = (int)((n + per_block - 1) / per_block);
-    if (P.xcd_remap) grid = (grid + 7) & ~7;
-    hipLaunchKernelGGL((k_fewrow_slots<LANES, V, NU, NI>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-}
+// the launch choice is fewrow_level_shape (svdf_level_geometry.h): form, workgroup size, grid; here only the template dispatch
 template <int LANES, int V>
-static void launch_fewrow_slots(const DevParams &P, const FusedSchedule &S, int max_nu, int max_ni, long begin, long end, int block_threads, hipStream_t st) {
-    if (max_nu <= 1 && max_ni <= 1) launch_fewrow_slots_shape<LANES, V, 1, 1>(P, S, begin, end, block_threads, st);
-    else if (max_nu <= 1) launch_fewrow_slots_shape<LANES, V, 1, 2>(P, S, begin, end, block_threads, st);
-    else if (max_ni <= 1) launch_fewrow_slots_shape<LANES, V, 2, 1>(P, S, begin, end, block_threads, st);
-    else launch_fewrow_slots_shape<LANES, V, 2, 2>(P, S, begin, end, block_threads, st);
+static void launch_fewrow_slots(const DevParams &P, const FusedSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    const dim3 grid((unsigned)sh.grid), block((unsigned)sh.block);
+    if (sh.nu == 1 && sh.ni == 1) hipLaunchKernelGGL((k_fewrow_slots<LANES, V, 1, 1>), grid, block, 0, st, P, S, begin, end);
+    else if (sh.nu == 1) hipLaunchKernelGGL((k_fewrow_slots<LANES, V, 1, 2>), grid, block, 0, st, P, S, begin, end);
+    else if (sh.ni == 1) hipLaunchKernelGGL((k_fewrow_slots<LANES, V, 2, 1>), grid, block, 0, st, P, S, begin, end);
+    else hipLaunchKernelGGL((k_fewrow_slots<LANES, V, 2, 2>), grid, block, 0, st, P, S, begin, end);
 }
 
 template <int LPI, int NU, int NI>
-static void launch_fewrow_shape(const DevParams &P, const FusedSchedule &S, long begin, long end, int block_threads, hipStream_t st) {
-    const long n = end - begin;
-    const long per_block = (long)(block_threads / 64) * (64 / LPI);
-    int grid = (int)((n + per_block - 1) / per_block);
-    if (P.xcd_remap) grid = (grid + 7) & ~7;
-    if (P.k == 4 * LPI) hipLaunchKernelGGL((k_fewrow_fast<LPI, NU, NI, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-    else hipLaunchKernelGGL((k_fewrow_fast<LPI, NU, NI, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
+static void launch_fewrow_shape(const DevParams &P, const FusedSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    const dim3 grid((unsigned)sh.grid), block((unsigned)sh.block);
+    if (sh.full) hipLaunchKernelGGL((k_fewrow_fast<LPI, NU, NI, true>), grid, block, 0, st, P, S, begin, end);
+    else hipLaunchKernelGGL((k_fewrow_fast<LPI, NU, NI, false>), grid, block, 0, st, P, S, begin, end);
 }
 template <int LPI>
-static void launch_fewrow_lpi(const DevParams &P, const FusedSchedule &S, int nu, int ni, long begin, long end, int bt, hipStream_t st) {
-    if (nu <= 1 && ni <= 1) launch_fewrow_shape<LPI, 1, 1>(P, S, begin, end, bt, st);
-    else if (nu <= 1) launch_fewrow_shape<LPI, 1, 2>(P, S, begin, end, bt, st);
-    else if (ni <= 1) launch_fewrow_shape<LPI, 2, 1>(P, S, begin, end, bt, st);
-    else launch_fewrow_shape<LPI, 2, 2>(P, S, begin, end, bt, st);
+static void launch_fewrow_lpi(const DevParams &P, const FusedSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    if (sh.nu == 1 && sh.ni == 1) launch_fewrow_shape<LPI, 1, 1>(P, S, begin, end, sh, st);
+    else if (sh.nu == 1) launch_fewrow_shape<LPI, 1, 2>(P, S, begin, end, sh, st);
+    else if (sh.ni == 1) launch_fewrow_shape<LPI, 2, 1>(P, S, begin, end, sh, st);
+    else launch_fewrow_shape<LPI, 2, 2>(P, S, begin, end, sh, st);
 }
 // a run of narrow levels [l0, l1) in one launch (k_fewrow_slots_chain); false when the shape has no chain form (the caller launches level by level)
 bool launch_fewrow_chain(const DevParams &P, const FusedSchedule &S, int max_nu, int max_ni, const long *d_level_ptr, long l0, long l1, hipStream_t st) {
-    if (!(P.fewrow_fast && fewrow_fast_applies(P, S) && P.k == 128 && P.fewrow_i16 == 1)) return false;
+    if (!fewrow_chain_applies(P, S.gptr != nullptr)) return false;
     if (l1 <= l0) return true;
     if (max_nu <= 1 && max_ni <= 1) hipLaunchKernelGGL((k_fewrow_slots_chain<16, 2, 1, 1>), dim3(1), dim3(1024), 0, st, P, S, d_level_ptr, l0, l1);
     else if (max_nu <= 1) hipLaunchKernelGGL((k_fewrow_slots_chain<16, 2, 1, 2>), dim3(1), dim3(1024), 0, st, P, S, d_level_ptr, l0, l1);
@@ -372,18 +363,12 @@ bool launch_fewrow_chain(const DevParams &P, const FusedSchedule &S, int max_nu,
     return true;
 }
 // true when the configuration / data set is the one this kernel is specialised for
-bool fewrow_fast_applies(const DevParams &P, const FusedSchedule &S) {
-    return S.gptr == nullptr && !P.relax_global && P.relax_user_from == 0xFFFFFFFFu && P.relax_item_from == 0xFFFFFFFFu &&
-           P.reg_method == 0 && P.u_rng.n == 0 && P.i_rng.n == 0 && P.user_nonnegative == 0;
-}
+bool fewrow_fast_applies(const DevParams &P, const FusedSchedule &S) { return fewrow_fast_config(P, S.gptr != nullptr); }
 void launch_fewrow_fast(const DevParams &P, const FusedSchedule &S, int max_nu, int max_ni, long begin, long end, int block_threads, hipStream_t st) {
     if (end <= begin) return;
-    // one-wave workgroups: a level of these workloads is a few hundred to a few thousand waves, and 64-thread blocks spread them over
-    // four times as many CUs (tools/ab_knob.py: neighbourhood 87.3 vs 91.8 ms per pass with 256; rank pairs 45.2 vs 45.4: flat)
-    if (block_threads <= 0) block_threads = 64;
-    if (P.k == 128 && P.fewrow_i16 == 1) { launch_fewrow_slots<16, 2>(P, S, max_nu, max_ni, begin, end, block_threads, st); return; }
-    // (eight lanes with four chunks each measured slower at k = 128: 46.7 vs 45.2 ms per 50 M pairs; 32 lanes, one chunk: 48.9)
-    SVDF_DISPATCH_LPI(lanes_per_instance(P.k), launch_fewrow_lpi<LPI>(P, S, max_nu, max_ni, begin, end, block_threads, st));
+    const LevelShape sh = fewrow_level_shape(P, max_nu, max_ni, end - begin, block_threads);
+    if (sh.form == LEVEL_FEWROW_SLOTS16) { launch_fewrow_slots<16, 2>(P, S, begin, end, sh, st); return; }
+    SVDF_DISPATCH_LPI(sh.lpi, launch_fewrow_lpi<LPI>(P, S, begin, end, sh, st));
 }
 
 }  // namespace svdf

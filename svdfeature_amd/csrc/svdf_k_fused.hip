@@ -284,48 +284,38 @@ __global__ __launch_bounds__(256) void k_predict_fused(const DevParams P, const 
     }
 }
 
-// read-only scoring of a basicMF schedule (out[s] in schedule order)
+// the launch choice is fused_level_shape (svdf_level_geometry.h): form, row sets per wave after folding, workgroup size, grid, LDS; here only
+// the template dispatch
 template <int LPI, int NU, int NI>
-static void launch_fused_shape(const DevParams &P, const FusedSchedule &S, long begin, long end, int G, int block_threads, hipStream_t st) {
-    const long n = end - begin;
-    if (G >= 2 && NU + NI <= 3 && !(NU == 2 && P.relax_user_from != 0xFFFFFFFFu && P.hot_reduce)) {
-        const long per_block = (long)(block_threads / 64) * 2 * (64 / LPI);
-        int grid = (int)((n + per_block - 1) / per_block);
-        if (P.xcd_remap) grid = (grid + 7) & ~7;
-        if (P.k == 4 * LPI) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 2, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-        else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 2, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-    } else if (NU == 2 && P.relax_user_from != 0xFFFFFFFFu && P.hot_reduce) {
+static void launch_fused_shape(const DevParams &P, const FusedSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    const dim3 grid((unsigned)sh.grid), block((unsigned)sh.block);
+    if (sh.form == LEVEL_FUSED_HOT) {
         // relaxed shared user feature in the last user slot: big workgroups that pre-reduce its changes in LDS
-        constexpr int HB = 1024;
-        const long per_block = (long)(HB / 64) * (64 / LPI);
-        int grid = (int)((n + per_block - 1) / per_block);
-        if (P.xcd_remap) grid = (grid + 7) & ~7;
-        const size_t lds = (size_t)per_block * (LPI * 16 + 8);
-        if (P.k == 4 * LPI) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, true, NU == 2>), dim3(grid), dim3(HB), lds, st, P, S, begin, end);
-        else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, false, NU == 2>), dim3(grid), dim3(HB), lds, st, P, S, begin, end);
+        if (sh.full) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, true, NU == 2>), grid, block, sh.lds, st, P, S, begin, end);
+        else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, false, NU == 2>), grid, block, sh.lds, st, P, S, begin, end);
+    } else if (sh.groups == 2) {
+        if constexpr (NU + NI <= 3) {
+            if (sh.full) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 2, true>), grid, block, 0, st, P, S, begin, end);
+            else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 2, false>), grid, block, 0, st, P, S, begin, end);
+        }
     } else {
-        const long per_block = (long)(block_threads / 64) * (64 / LPI);
-        int grid = (int)((n + per_block - 1) / per_block);
-        if (P.xcd_remap) grid = (grid + 7) & ~7;
-        if (P.k == 4 * LPI) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
-        else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);
+        if (sh.full) hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, true>), grid, block, 0, st, P, S, begin, end);
+        else hipLaunchKernelGGL((k_fused<LPI, NU, NI, 1, false>), grid, block, 0, st, P, S, begin, end);
     }
 }
 template <int LPI>
-static void launch_fused_lpi(const DevParams &P, const FusedSchedule &S, int nu, int ni, long begin, long end, int G, int bt, hipStream_t st) {
-    if (nu <= 1 && ni <= 1) launch_fused_shape<LPI, 1, 1>(P, S, begin, end, G, bt, st);
-    else if (nu <= 1) launch_fused_shape<LPI, 1, 2>(P, S, begin, end, G, bt, st);
-    else if (ni <= 1) launch_fused_shape<LPI, 2, 1>(P, S, begin, end, G, bt, st);
-    else launch_fused_shape<LPI, 2, 2>(P, S, begin, end, G, bt, st);
+static void launch_fused_lpi(const DevParams &P, const FusedSchedule &S, long begin, long end, const LevelShape &sh, hipStream_t st) {
+    if (sh.nu == 1 && sh.ni == 1) launch_fused_shape<LPI, 1, 1>(P, S, begin, end, sh, st);
+    else if (sh.nu == 1) launch_fused_shape<LPI, 1, 2>(P, S, begin, end, sh, st);
+    else if (sh.ni == 1) launch_fused_shape<LPI, 2, 1>(P, S, begin, end, sh, st);
+    else launch_fused_shape<LPI, 2, 2>(P, S, begin, end, sh, st);
 }
 void launch_fused(const DevParams &P, const FusedSchedule &S, int max_nu, int max_ni, long begin, long end, int groups_per_wave,
                   int block_threads, hipStream_t st) {
     if (end <= begin) return;
-    if (P.fewrow_fast && fewrow_fast_applies(P, S)) { launch_fewrow_fast(P, S, max_nu, max_ni, begin, end, block_threads, st); return; }
-    const int lpi_ = lanes_per_instance(P.k);
-    if (groups_per_wave <= 0) groups_per_wave = lpi_ == 16 ? 2 : 1;
-    if (block_threads <= 0) block_threads = 64;   // one-wave workgroups, see launch_fewrow_fast
-    SVDF_DISPATCH_LPI(lanes_per_instance(P.k), launch_fused_lpi<LPI>(P, S, max_nu, max_ni, begin, end, groups_per_wave, block_threads, st));
+    const LevelShape sh = fused_level_shape(P, S.gptr != nullptr, max_nu, max_ni, end - begin, groups_per_wave, block_threads);
+    if (sh.form == LEVEL_FEWROW_FAST || sh.form == LEVEL_FEWROW_SLOTS16) { launch_fewrow_fast(P, S, max_nu, max_ni, begin, end, block_threads, st); return; }
+    SVDF_DISPATCH_LPI(sh.lpi, launch_fused_lpi<LPI>(P, S, begin, end, sh, st));
 }
 template <int LPI>
 static void launch_predict_fused_lpi(const DevParams &P, const FusedSchedule &S, int nu, int ni, long n, float *out, int grid, hipStream_t st) {

@@ -17,10 +17,7 @@ __global__ void k_delta_add(float *cur, const float *snap, const float *delta, l
 }
 
 int lanes_per_instance(int k) {
-    int chunks = (k + 3) / 4;
-    int lpi = 1;
-    while (lpi < chunks && lpi < 64) lpi <<= 1;
-    return lpi;   // 64 also for wide rows (k > 256: several float4 slots per lane)
+    return level_lane_class(k);   // 64 also for wide rows (k > 256: several float4 slots per lane)
 }
 int max_supported_factor() { return 1024; }
 int max_fast_path_factor() { return 256; }

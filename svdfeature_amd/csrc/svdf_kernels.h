@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "svdf_types.h"
+#include "svdf_level_geometry.h"
 
 namespace svdf {
 
