@@ -369,7 +369,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 41 .. 43 see the _lines, _cand and _sampled calls below,
  * 44 / 45 passes built from a pair source (svdf_dataset_from_pair_source) without the pair columns leaving HBM / through
  * svdf_dataset_from_pairs' own builder on the columns copied back,
- * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard) */
+ * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard),
+ * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -498,6 +499,10 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                choice (the staged form up to num_cand 16 at num_factor <= 32, up to 4 at <= 128, for 2 at <= 256, the lane form
  *                                otherwise; profiles/r34_pair_hard.md), 1 one lane per candidate with both rows read where they lie, 2 the item
  *                                rows staged in the wave's LDS (num_factor > 256 always takes 1).  Same bits
+ *     pair_weight_form    0      the map of a draw from a pair source with item weights (svdf_pair_source_create_weighted): 0 the
+ *                                measured choice (2 up to 10 000 items, 1 above; profiles/r36_pair_weight.md), 1 a binary search of the whole
+ *                                table of running sums, 2 a guide table indexed by the word's high bits, then a search between two of its
+ *                                entries.  Same bits
  * Returns 0 if the knob exists, -1 otherwise.  The relaxed mode is switched by CONFIG keys through svdf_set_param ("amd:relax_global",
  * "amd:relax_user_from", "amd:relax_item_from", "amd:relax_feedback"), not by knobs: it changes results.  So is
  * "amd:shared_user_from" = B (one GPU, the window step of amd:step = minibatch / auto): user ids < B are private (exactly one
@@ -929,6 +934,58 @@ int svdf_pair_hard_negatives(long num_user, long num_item, long n, const unsigne
                              uint64_t seed, int num_factor, const float *W_user, const float *W_item, const float *i_bias,
                              unsigned *neg_out, float *score_out);
 
+/* ---- ITEM-WEIGHTED negatives for those passes, plain and hard.  Uniform negatives on a skewed catalogue are almost
+ * always tail items; the usual remedy draws a negative with probability proportional to an item weight (count^0.75, or any prior of the
+ * caller's).  A weighted source is created with item_weight[num_item], uint32, and EVERY pass call above takes it with no new argument.
+ * THE RULE, in unsigned integer arithmetic only; G, mix, SALT and stream_q are the plain rule's above, unchanged -- no new stream or constant:
+ *   cdf[0]     = 0,  cdf[i + 1] = cdf[i] + item_weight[i],  W = cdf[num_item];  1 <= W <= 2^32 - 1
+ *   x(q, t)    = mix(stream_q + (t + 1) * G)                                    ALL 64 bits are used
+ *   y          = floor(x * W / 2^64)          the high 64 bits of the 64 x 64 product (__umul64hi; unsigned __int128 on the host)
+ *   wdraw(q,t) = the item i with cdf[i] <= y < cdf[i + 1]                       an item of weight 0 is never drawn
+ *   neg_q      = the first of wdraw(q, 0), wdraw(q, 1), ... that is not in P(user_r), among the same T = 4096 draws; a pair that exhausts
+ *                them fails the call with the plain pass's message.
+ * A source whose weights are all equal is NOT the uniform source: the uniform map multiplies the HIGH 32 bits of x by num_item, this one all
+ * 64 bits by W.  The two maps agree on all but about num_item of every 2^32 words, so the two sources usually draw the same ids from one
+ * seed, but nothing promises it: take the unweighted source where the uniform rule's negatives are wanted.
+ * A HARD pass on a weighted source is the hard rule above word for word, cand(q, i) being the WEIGHTED plain rule's negative of pair index
+ * q * C + i; score, selection and C = 1 are unchanged.
+ * THE DENSITY RULE, WEIGHTED, replaces the count rule for such a source, at creation, in 64-bit integers: a user with rows is refused when
+ * 64 * (W - W(P(u))) < W, W(P(u)) the weight of its distinct items (the first such user in id order is named).  Every source that remains
+ * accepts each draw with probability >= 1 / 64 less the map's bias of at most W / 2^64 < 2^-32, so the < 1e-28 bound on exhaustion above
+ * carries over and no input makes the kernel run long.  The rule bites more often than the count rule: popular items are the ones users hold.
+ * PINNED VECTORS (seed 12345, num_item 1200, item_weight[i] = 0 where i % 7 == 0 and 1 + (i * i) % 97 otherwise: W = 50185):
+ *   pair 0, draws t = 0 .. 5: 611, 1086, 472, 1016, 936, 514;   pair 7, draws t = 0 .. 7: 502, 551, 33, 918, 200, 19, 1102, 177
+ *   rows (user, pos) = (4, 10), (4, 700), (9, 10): num_neg 1 gives the negatives 611, 547, 755; num_neg 2 gives 611, 547, 755, 1006, 59, 447
+ *   W = 2^32 - 1 and x = 2^64 - 1 give y = W - 1 = 4294967294.
+ * REFUSED on the host, before any device work and before "needs a GPU", after what the plain source refuses about its rows:
+ *   a sum of 0                                "pair_source: the item weights sum to 0"
+ *   a sum S >= 2^32                           "pair_source: the item weights sum to S: the sum must stay below 2^32"
+ *   the density rule                          "pair_source: user U's positive items hold M of the total item weight W: less than 1 part in 64
+ *                                              is left to draw a negative from; draw its negatives yourself (svdf_dataset_from_pairs)"
+ * svdf_pair_source_create_weighted uploads cdf and a guide table once (two arrays of about num_item and at most 2 * num_item + 1 words); a
+ * NULL item_weight is svdf_pair_source_create.  Routes, fallback, refusals and counters 44 / 45 / 46 are untouched; counter 47 counts the
+ * passes drawn from a weighted source.  The device reads the map in one of two forms with equal bits (knob `pair_weight_form`): 1 a binary
+ * search for y over the whole cdf; 2 a guide table in x space -- Gn the smallest power of two >= max(num_item, 64), guide[g] the item that
+ * holds y = mulhi(g << (64 - log2 Gn), W), guide[Gn] the last item of positive weight; a draw reads guide[x >> (64 - log2 Gn)] and its
+ * successor and searches cdf between the two, both included.  svdf_pair_negatives_weighted and svdf_pair_hard_negatives_weighted are the
+ * rule on the host -- no GPU, no handle, the same validation; a NULL item_weight gives the unweighted calls.
+ * MEASURED (one MI355X, 100 K users, 20 M shuffled positives, num_neg 1, medians of five; profiles/r36_pair_weight.md): k_pair_draw on a
+ * weighted source takes 1.33 ms (form 2) against 1.36 ms for the uniform source at 10 K items, 1.91 ms (form 1) against 1.70 ms at 100 K
+ * items, where form 2 did not pay.  A weighted round (Zipf(0.7) counts to the 0.75, num_factor 128) takes 0.976 s on the exact pass and
+ * 0.375 s under `amd:step = minibatch` against 4.31 s / 3.77 s for svdf_pair_negatives_weighted on the host (3.3 s) followed by
+ * svdf_dataset_from_pairs -- and against 0.271 s / 0.166 s for the uniform round: negatives that concentrate on popular items make the
+ * exact pass's schedule deeper and the windows finer, whoever draws them.  On a planted set weighting did NOT help by the sampled
+ * evaluation, whose own negatives are uniform.
+ * NOT OFFERED: weighted negatives for the sampled evaluation calls, which draw DISTINCT ids in an open loop; a skewed table needs an
+ * admission rule of its own to bound that loop. */
+svdf_pair_source *svdf_pair_source_create_weighted(svdf_trainer *t, long n, const unsigned *user, const unsigned *pos_item,
+                                                   const unsigned *item_weight /* [num_item], or NULL */);
+int svdf_pair_negatives_weighted(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, const unsigned *item_weight,
+                                 int num_neg, uint64_t seed, unsigned *neg_out);
+int svdf_pair_hard_negatives_weighted(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item,
+                                      const unsigned *item_weight, int num_neg, int num_cand, uint64_t seed, int num_factor, const float *W_user,
+                                      const float *W_item, const float *i_bias, unsigned *neg_out, float *score_out);
+
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator
  * by n draws without calling rand() n times (jump-ahead of glibc's additive-feedback table).  Host functions, no GPU needed;
@@ -967,6 +1024,12 @@ int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const i
  *    17 dynamic LDS bytes, 18 the configuration has a chained form, 19 the widest level handed to it (0: none; chain_width)
  * -1 on bad arguments. */
 int svdf_level_geometry(svdf_trainer *t, int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out);
+
+/* ---- probe of the map of a weighted pair source, for tests: id_out[j] = the item the rule above gives the 64-bit
+ * word x[j] under item_weight[num_item], by the very function the draw kernels call.  form 1 or 2 as knob pair_weight_form (0: the knob's
+ * choice).  t == NULL: on the host, no GPU.  With a trainer: the tables are uploaded and the function runs on the device in one small launch
+ * (a host-only handle answers "needs a GPU").  The weights are validated as a weighted source validates them.  -1 on bad arguments. */
+int svdf_pair_weight_lookup(svdf_trainer *t, long num_item, const unsigned *item_weight, int form, long nx, const uint64_t *x, unsigned *id_out);
 
 /* ---- probes of the window rule of `amd:step = minibatch` (svdf_wseq_rule.h): into how many windows a pass is cut, from knob values and
  * counts alone.  Host functions, no handle and no GPU; the data-set builders reach the same functions.  Tests compare them with

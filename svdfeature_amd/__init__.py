@@ -153,16 +153,57 @@ def _pass_size(n, num_neg):
     return n * int(num_neg) if 1 <= int(num_neg) <= 256 and n * int(num_neg) < (1 << 31) - 16 else 0
 
 
-def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed):
+def _item_weights(item_weight, num_item):
+    """the weights of a weighted pair source as the uint32 array the library reads num_item entries of (num_item None: not known here)"""
+    w = np.atleast_1d(np.asarray(item_weight))
+    if w.ndim != 1 or (num_item is not None and len(w) != int(num_item)):
+        raise SvdfError("pair_source: item_weight must have one entry per item")
+    if w.dtype.kind not in "iu" or (w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF)):
+        raise SvdfError("pair_source: item_weight must hold integers in 0 .. 2^32 - 1")
+    return _pad(w, np.uint32)
+
+
+def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed, item_weight=None):
     """svdf_pair_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed) trains a source of these rows against, by the
     published rule (include/svdfeature_amd.h): uint32[n * num_neg], pair r * num_neg + j belongs to row r.  A host function:
-    no GPU, no handle."""
+    no GPU, no handle.  item_weight (uint32 per item): the negatives of a source created with these weights (svdf_pair_negatives_weighted,
+    DESIGN.md 6ae)."""
     lib = load_library()
     n, user, pos_item = _pair_rows(user, pos_item)
     neg = np.zeros(max(_pass_size(n, num_neg), 1), np.uint32)
-    if lib.svdf_pair_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF, neg) != 0:
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if item_weight is None:
+        rc = lib.svdf_pair_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), seed, neg)
+    else:
+        rc = lib.svdf_pair_negatives_weighted(int(num_user), int(num_item), n, user, pos_item, _item_weights(item_weight, num_item), int(num_neg), seed, neg)
+    if rc != 0:
         raise SvdfError(lib.svdf_last_error().decode())
     return neg[:n * int(num_neg)]
+
+
+def pair_weight_lookup(item_weight, x, form=1, trainer=None):
+    """svdf_pair_weight_lookup: the item ids the weighted rule maps the 64-bit words x onto under item_weight, in form 1 (binary
+    search of the running sums) or 2 (guide table); on the host, or with trainer= by the same function on that trainer's GPU."""
+    lib = load_library()
+    w = _item_weights(item_weight, None)
+    x = np.ascontiguousarray(x, np.uint64).reshape(-1)
+    ids = np.zeros(max(len(x), 1), np.uint32)
+    if lib.svdf_pair_weight_lookup(None if trainer is None else trainer.h, len(np.atleast_1d(item_weight)), w, int(form), len(x), _pad(x, np.uint64), ids) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return ids[:len(x)]
+
+
+def pair_popularity_weights(pos_item, num_item, power=0.75, unseen=1):
+    """A convenience, NOT part of the pinned rule: uint32 item weights rint(1024 * count^power) for the items among pos_item and `unseen` for
+    the rest, computed in numpy float64 (so the last unit of a weight may differ between numpy versions -- keep the array if a run is to be
+    repeated).  Raises if the sum reaches 2^32."""
+    count = np.bincount(np.asarray(pos_item, np.int64).reshape(-1), minlength=int(num_item)).astype(np.float64)
+    if len(count) != int(num_item):
+        raise SvdfError("item feature index exceed bound")
+    w = np.where(count > 0, np.rint(1024.0 * np.power(count, float(power))), float(int(unseen)))
+    if w.min() < 0 or float(w.sum()) >= 4294967296.0:
+        raise SvdfError("pair_source: the item weights sum to %d: the sum must stay below 2^32" % int(w.sum()))
+    return w.astype(np.uint32)
 
 
 def _hard_size(n, num_neg, num_cand):
@@ -171,11 +212,11 @@ def _hard_size(n, num_neg, num_cand):
     return n * int(num_neg) if ok and n * int(num_neg) * int(num_cand) < (1 << 31) - 16 else 0
 
 
-def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, seed, W_user, W_item, i_bias, return_scores=False):
+def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, seed, W_user, W_item, i_bias, return_scores=False, item_weight=None):
     """svdf_pair_hard_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed, hard=num_cand) trains against on the model
     (W_user [num_user, k], W_item [num_item, k], i_bias [num_item]) -- per pair the best-scoring of num_cand candidates of the plain rule
     (include/svdfeature_amd.h): uint32[n * num_neg], with return_scores also the chosen scores.  A host function: no GPU, no
-    handle."""
+    handle.  item_weight: the candidates are those of a source created with these weights (svdf_pair_hard_negatives_weighted)."""
     lib = load_library()
     n, user, pos_item = _pair_rows(user, pos_item)
     W_user, W_item = np.ascontiguousarray(W_user, np.float32), np.ascontiguousarray(W_item, np.float32)
@@ -184,9 +225,13 @@ def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, s
         raise SvdfError("pair_source: W_user, W_item and i_bias must be [num_user, k], [num_item, k] and [num_item]")
     size = max(_hard_size(n, num_neg, num_cand), 1)
     neg, score = np.zeros(size, np.uint32), np.zeros(size, np.float32)
-    if lib.svdf_pair_hard_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), int(num_cand), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                    W_item.shape[1], _pad(W_user, np.float32), _pad(W_item, np.float32), _pad(i_bias, np.float32), neg,
-                                    _opt_ptr(score if return_scores else None)) != 0:
+    model = (W_item.shape[1], _pad(W_user, np.float32), _pad(W_item, np.float32), _pad(i_bias, np.float32), neg, _opt_ptr(score if return_scores else None))
+    if item_weight is None:
+        rc = lib.svdf_pair_hard_negatives(int(num_user), int(num_item), n, user, pos_item, int(num_neg), int(num_cand), int(seed) & 0xFFFFFFFFFFFFFFFF, *model)
+    else:
+        rc = lib.svdf_pair_hard_negatives_weighted(int(num_user), int(num_item), n, user, pos_item, _item_weights(item_weight, num_item), int(num_neg),
+                                                   int(num_cand), int(seed) & 0xFFFFFFFFFFFFFFFF, *model)
+    if rc != 0:
         raise SvdfError(lib.svdf_last_error().decode())
     N = n * int(num_neg)
     return (neg[:N], score[:N]) if return_scores else neg[:N]
@@ -358,6 +403,12 @@ def load_library():
     lib.svdf_pair_source_draw_hard.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64, _u32p, C.c_void_p]
     lib.svdf_pair_hard_negatives.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, C.c_int, C.c_int, C.c_uint64, C.c_int, _f32p, _f32p, _f32p, _u32p,
                                              C.c_void_p]
+    lib.svdf_pair_source_create_weighted.restype = P
+    lib.svdf_pair_source_create_weighted.argtypes = [P, C.c_long, _u32p, _u32p, _u32p]
+    lib.svdf_pair_negatives_weighted.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, _u32p, C.c_int, C.c_uint64, _u32p]
+    lib.svdf_pair_hard_negatives_weighted.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, _u32p, C.c_int, C.c_int, C.c_uint64, C.c_int, _f32p, _f32p,
+                                                      _f32p, _u32p, C.c_void_p]
+    lib.svdf_pair_weight_lookup.argtypes = [P, C.c_long, _u32p, C.c_int, C.c_long, np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS"), _u32p]
     lib.svdf_ranker_create.restype = P
     lib.svdf_ranker_create.argtypes = [C.c_uint8] * 4 + [C.c_int]
     lib.svdf_ranker_destroy.argtypes = [P]
@@ -790,10 +841,16 @@ class Trainer:
         return Dataset(self, h)
 
     # -- passes of rank pairs from positives only (svdf_pair_source_*)
-    def pair_source(self, user, pos_item):
-        """The positives (user, item) of pairwise training, uploaded once: see svdf_pair_source_create."""
+    def pair_source(self, user, pos_item, item_weight=None):
+        """The positives (user, item) of pairwise training, uploaded once: see svdf_pair_source_create.  item_weight (uint32 per item): every
+        pass of the source draws its negatives with probability proportional to these weights (svdf_pair_source_create_weighted)."""
         n, user, pos_item = _pair_rows(user, pos_item)
-        h = self.lib.svdf_pair_source_create(self.h, n, user, pos_item)
+        if item_weight is None:
+            h = self.lib.svdf_pair_source_create(self.h, n, user, pos_item)
+        else:
+            rows, cols = C.c_int(-1), C.c_int()
+            known = self.lib.svdf_view_shape(self.h, VIEW["W_item"], C.byref(rows), C.byref(cols)) == 0 and rows.value > 0
+            h = self.lib.svdf_pair_source_create_weighted(self.h, n, user, pos_item, _item_weights(item_weight, rows.value if known else None))
         if not h:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return PairSource(self, h, n)

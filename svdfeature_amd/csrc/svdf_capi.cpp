@@ -522,6 +522,32 @@ int svdf_pair_hard_negatives(long num_user, long num_item, long n, const unsigne
         return 0;
     })
 }
+/* ... and item-weighted negatives, plain and hard */
+svdf_pair_source *svdf_pair_source_create_weighted(svdf_trainer *t, long n, const unsigned *user, const unsigned *pos_item, const unsigned *item_weight) {
+    SVDF_GUARD(nullptr, {
+        svdf::PairSource *s = t->e->pair_source_create(n, user, pos_item, item_weight);
+        svdf_pair_source *h = new svdf_pair_source();
+        h->s = s;
+        return h;
+    })
+}
+int svdf_pair_negatives_weighted(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, const unsigned *item_weight,
+                                 int num_neg, uint64_t seed, unsigned *neg_out) {
+    SVDF_GUARD(-1, {
+        if (!item_weight) svdf::pair_src_negatives(num_user, num_item, n, user, pos_item, num_neg, seed, neg_out);
+        else svdf::pair_weight_negatives(num_user, num_item, n, user, pos_item, item_weight, num_neg, seed, neg_out);
+        return 0;
+    })
+}
+int svdf_pair_hard_negatives_weighted(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, const unsigned *item_weight,
+                                      int num_neg, int num_cand, uint64_t seed, int num_factor, const float *W_user, const float *W_item,
+                                      const float *i_bias, unsigned *neg_out, float *score_out) {
+    SVDF_GUARD(-1, {
+        svdf::pair_hard_negatives(num_user, num_item, n, user, pos_item, num_neg, num_cand, seed, num_factor, W_user, W_item, i_bias, neg_out, score_out,
+                                  item_weight);
+        return 0;
+    })
+}
 
 /* ---- ISVDRanker ---- */
 svdf_ranker *svdf_ranker_create(uint8_t format_type, uint8_t active_type, uint8_t extend_type, uint8_t variant_type, int device) {
@@ -569,6 +595,18 @@ int svdf_level_geometry(svdf_trainer *t, int launcher, long n, int max_nu, int m
 // the launch geometry of the live-model ranking calls exposed for tests (tests/test_rank_geometry.py): Engine::rank_geometry
 int svdf_rank_geometry(svdf_trainer *t, int kind, long units, int top_n, const int64_t *pos_ptr, long *out) {
     SVDF_GUARD(-1, { t->e->rank_geometry(kind, units, top_n, pos_ptr, out); return 0; })
+}
+// the map of a weighted pair source exposed for tests (tests/test_pair_weight.py): svdf_pairweight_lists.h on the host (t == NULL), the same
+// function in one small launch on the device (Engine::pair_weight_lookup)
+int svdf_pair_weight_lookup(svdf_trainer *t, long num_item, const unsigned *item_weight, int form, long nx, const uint64_t *x, unsigned *id_out) {
+    SVDF_GUARD(-1, {
+        if (t) { t->e->pair_weight_lookup(num_item, item_weight, form, nx, x, id_out); return 0; }
+        if (form < 0 || form > 2 || nx < 0 || (nx > 0 && (!x || !id_out))) svdf::fail("pair_weight_lookup: bad arguments");
+        svdf::PairWeightLists Wt;
+        svdf::pair_weight_build(num_item, item_weight, Wt);
+        svdf::pair_weight_lookup_host(Wt.view(), form == 0 ? svdf::pair_weight_form(num_item, 0) : form, nx, x, id_out);
+        return 0;
+    })
 }
 
 // the window rule exposed for CPU tests (tests/test_window_rule.py): svdf_wseq_rule.h, the functions the data-set builders call

@@ -227,6 +227,7 @@ int64_t Engine::counter(int what) const {
     case 44: return n_pair_src_hbm_;         // passes built from a pair source without the pair columns leaving HBM (section 6ac)
     case 45: return n_pair_src_fallback_;    // passes built from a pair source through dataset_from_pairs on the columns copied back
     case 46: return n_pair_src_hard_;        // of the passes under 44 / 45, the hard ones: the best of num_cand candidates by live score (section 6ad)
+    case 47: return n_pair_src_weighted_;    // of the passes under 44 / 45, those drawn from a source with item weights (section 6ae)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -319,6 +320,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_per_target")) { check(value >= 1, "window_per_target must be positive"); wseq_per_target_ = (int)value; return 0; }
     if (!strcmp(name, "rank_eval_budget")) { check(value >= 1, "rank_eval_budget must be positive"); rank_eval_budget_ = value; return 0; }
     if (!strcmp(name, "rank_cand_form")) { check(value >= 0 && value <= 2, "rank_cand_form must be 0 (measured choice), 1 (one lane per pair) or 2 (staged)"); rank_cand_form_ = value; return 0; }
+    if (!strcmp(name, "pair_weight_form")) { check(value >= 0 && value <= 2, "pair_weight_form must be 0 (measured choice), 1 (search of the whole cdf) or 2 (guided search)"); pair_weight_form_ = value; return 0; }
     if (!strcmp(name, "pair_hard_form")) { check(value >= 0 && value <= 2, "pair_hard_form must be 0 (measured choice), 1 (one lane per candidate) or 2 (staged)"); pair_hard_form_ = value; return 0; }
     if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }
     if (!strcmp(name, "window_slots")) { window_slots_ = value != 0; return 0; }

@@ -393,6 +393,10 @@ struct PairSource {
     long same = 0;                     // rows whose user is the row's before: the user-column pretest of user-run units, from the caller's column
     DevBuf<unsigned> user, pos, uitems;   // [n], [n], every user's distinct items ascending
     DevBuf<int> uptr;                  // [num_user + 1]
+    bool weighted = false;             // created with item weights (section 6ae): negatives are drawn through the tables below
+    DevBuf<unsigned> cdf, guide;       // [num_item + 1], [Gn + 1] (svdf_pairweight_lists.h)
+    unsigned weight_sum = 0;           // W
+    int weight_shift = 0;              // 64 - log2 Gn
     PairSource() = default;
     ~PairSource();
     PairSource(const PairSource &) = delete;
@@ -522,7 +526,8 @@ class Engine {
 
     // passes of rank pairs from positives only, the negatives drawn on the device (svdf_pairsource.cpp, svdf_k_pairdraw.hip; DESIGN.md
     // section 6ac).  A source belongs to the handle it was created on and may outlive it.
-    PairSource *pair_source_create(long n, const unsigned *user, const unsigned *pos);
+    PairSource *pair_source_create(long n, const unsigned *user, const unsigned *pos, const unsigned *item_weight = nullptr);
+    void pair_weight_lookup(long num_item, const unsigned *item_weight, int form, long nx, const uint64_t *x, unsigned *id_out);   // test probe (svdf_pair_weight_lookup): the map on the device
     // num_cand = 0: the plain pass; >= 1: the hard pass, the best of num_cand candidates by live score
     Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand = 0);
     void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand = 0, float *score_out = nullptr);
@@ -1004,6 +1009,8 @@ class Engine {
     std::vector<PairSource *> pair_sources_;   // the live sources of this handle: forgotten (owner = nullptr) when the handle goes
     int64_t n_pair_src_hard_ = 0;      // counter 46: of the passes under 44 / 45, the hard ones (section 6ad)
     long pair_hard_form_ = 0;          // knob pair_hard_form: 0 the measured choice, 1 a lane per candidate, 2 the staged kernel
+    int64_t n_pair_src_weighted_ = 0;  // counter 47: of the passes under 44 / 45, those drawn from a weighted source (section 6ae)
+    long pair_weight_form_ = 0;        // knob pair_weight_form: 0 the measured choice, 1 the search of the whole cdf, 2 the guided search
     // what every pass refuses, on the host, before any device work (num_cand = 0: the plain pass)
     void pair_source_admit(const PairSource *src, int num_neg, int num_cand);
     // the pass's columns [n * num_neg] filled in HBM by the plain rule (num_cand = 0) or the hard one (user / pos may be nullptr; score only

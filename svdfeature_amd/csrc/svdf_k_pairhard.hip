@@ -19,20 +19,22 @@
 //                     read through L1 / L2, the C lanes of a pair reading one address.
 // The loop bound of a draw is the compile-time constant PAIR_SRC_DRAWS; an exhausted entry reports e + 1 through the one-word flag (plain
 // store, any writer may win) and goes on with id 0, a valid row.
+// A source with ITEM WEIGHTS (section 6ae) draws every candidate through its weight table (pair_weight_pick, svdf_pairweight_lists.h): the
+// template argument WF is 0 without weights -- the kernel as it was --, 1 for the search of the whole cdf, 2 for the guided search.
 #include <algorithm>
 
 #include "svdf_kernels.h"
 #include "svdf_k_rankkey.h"
 #include "svdf_k_rankscore.h"
-#include "svdf_pairsource_lists.h"
+#include "svdf_pairweight_lists.h"
 
 namespace svdf {
 
 constexpr int PH_NB = 8;            // 16-byte requests a lane of the staged form has in flight: 8 KiB per wave
 constexpr int PH_MAX_GRID = 8192;   // waves of a launch: 32 a CU; the rest of the units is strided over
 
-template <int SUB>
-__global__ __launch_bounds__(64) void k_pair_hard(const DevParams P, const PairHardDev H, const long nunit) {
+template <int SUB, int WF>
+__global__ __launch_bounds__(64) void k_pair_hard(const DevParams P, const PairHardDev H, const long nunit, const PairWeightDev T) {
     extern __shared__ float4 ph_item[];   // staged: [nch][SUB + 1]
     const PairDrawDev &D = H.D;
     const int lane = threadIdx.x;
@@ -55,7 +57,10 @@ __global__ __launch_bounds__(64) void k_pair_hard(const DevParams P, const PairH
                 const long q = q0 + pl;
                 const long e = q * C + t0 + li;   // the plain rule's pair index: below 2^31 - 16
                 u = D.user[(unsigned)q / (unsigned)D.num_neg];
-                if (!pair_src_pick(D.seed, (uint64_t)e, D.num_item, D.uitems, D.uptr[u], D.uptr[u + 1], PAIR_SRC_DRAWS, &cid)) *D.flag = (unsigned)(e + 1);
+                int took;
+                if constexpr (WF == 0) took = pair_src_pick(D.seed, (uint64_t)e, D.num_item, D.uitems, D.uptr[u], D.uptr[u + 1], PAIR_SRC_DRAWS, &cid);
+                else took = pair_weight_pick<WF>(D.seed, (uint64_t)e, T, D.uitems, D.uptr[u], D.uptr[u + 1], PAIR_SRC_DRAWS, &cid);
+                if (!took) *D.flag = (unsigned)(e + 1);
             }
             float s = 0.0f;
             if constexpr (SUB == 0) {
@@ -149,19 +154,27 @@ int pair_hard_form(const DevParams &P, int form, int num_cand) {
     return num_cand <= most ? 2 : 1;
 }
 
-void launch_pair_hard(const DevParams &P, const PairHardDev &H, int form, hipStream_t st) {
+template <int SUB>
+static void ph_launch(const DevParams &P, const PairHardDev &H, const PairWeightDev &T, int wf, dim3 grid, size_t lds, long nunit, hipStream_t st) {
+    if (wf == 0) hipLaunchKernelGGL((k_pair_hard<SUB, 0>), grid, dim3(64), lds, st, P, H, nunit, T);
+    else if (wf == 2) hipLaunchKernelGGL((k_pair_hard<SUB, 2>), grid, dim3(64), lds, st, P, H, nunit, T);
+    else hipLaunchKernelGGL((k_pair_hard<SUB, 1>), grid, dim3(64), lds, st, P, H, nunit, T);
+}
+
+void launch_pair_hard(const DevParams &P, const PairHardDev &H, const PairWeightDev &T, int wform, int form, hipStream_t st) {
     if (H.D.npair <= 0) return;
+    const int wf = T.cdf ? pair_weight_form((long)T.num_item, wform) : 0;
     const int ppt = H.num_cand < 64 ? 64 / H.num_cand : 1;
     const long nunit = (H.D.npair + ppt - 1) / ppt;
     const dim3 grid((unsigned)std::min<long>(nunit, PH_MAX_GRID));
     if (pair_hard_form(P, form, H.num_cand) == 2) {
         const int sub = ph_sub(P.pitch);
         const size_t lds = 16 * ((size_t)P.pitch >> 2) * ((size_t)sub + 1);
-        if (sub == 64) hipLaunchKernelGGL(k_pair_hard<64>, grid, dim3(64), lds, st, P, H, nunit);
-        else if (sub == 32) hipLaunchKernelGGL(k_pair_hard<32>, grid, dim3(64), lds, st, P, H, nunit);
-        else hipLaunchKernelGGL(k_pair_hard<16>, grid, dim3(64), lds, st, P, H, nunit);
+        if (sub == 64) ph_launch<64>(P, H, T, wf, grid, lds, nunit, st);
+        else if (sub == 32) ph_launch<32>(P, H, T, wf, grid, lds, nunit, st);
+        else ph_launch<16>(P, H, T, wf, grid, lds, nunit, st);
     } else {
-        hipLaunchKernelGGL(k_pair_hard<0>, grid, dim3(64), 0, st, P, H, nunit);
+        ph_launch<0>(P, H, T, wf, grid, 0, nunit, st);
     }
 }
 

@@ -9,6 +9,7 @@
 
 #include "svdf_types.h"
 #include "svdf_level_geometry.h"
+#include "svdf_pairweight_lists.h"
 
 namespace svdf {
 
@@ -411,7 +412,10 @@ struct PairDrawDev {
     unsigned *out_neg;
     unsigned *flag;            // one word, zeroed by the caller: q + 1 of a pair (any of them) that exhausted its draws
 };
-void launch_pair_draw(const PairDrawDev &D, hipStream_t st);   // one launch, a lane per pair
+// T: the weight table of a weighted source (section 6ae; svdf_pairweight_lists.h), T.cdf == nullptr without one; wform: knob pair_weight_form
+int pair_weight_form(long num_item, int form);   // the form a weighted draw takes: 1 (search of the whole cdf) or 2 (guided search)
+void launch_pair_draw(const PairDrawDev &D, const PairWeightDev &T, int wform, hipStream_t st);   // one launch, a lane per pair
+void launch_pair_weight_lookup(const PairWeightDev &T, int wform, long nx, const uint64_t *x, unsigned *id_out, hipStream_t st);   // the probe svdf_pair_weight_lookup
 
 // ---- the hard pass of a pair source (svdf_k_pairhard.hip): pair q takes the best-scoring of its num_cand candidates,
 // candidate i of pair q being the plain rule's negative of pair index q * num_cand + i.  D.npair counts the PAIRS of the pass (n * num_neg);
@@ -422,7 +426,7 @@ struct PairHardDev {
     float *out_score;          // [npair] the chosen candidate's score, or nullptr
 };
 int pair_hard_form(const DevParams &P, int form, int num_cand);   // the form a hard pass's kernel takes: 1 (a lane per entry, rows where they lie) or 2 (staged)
-void launch_pair_hard(const DevParams &P, const PairHardDev &H, int form, hipStream_t st);   // one launch, a wave owns whole pairs
+void launch_pair_hard(const DevParams &P, const PairHardDev &H, const PairWeightDev &T, int wform, int form, hipStream_t st);   // one launch, a wave owns whole pairs
 
 }  // namespace svdf
 #endif

@@ -9,7 +9,7 @@
 
 #include <cstring>
 
-#include "svdf_pairsource_lists.h"
+#include "svdf_pairweight_lists.h"
 
 namespace svdf {
 
@@ -50,10 +50,10 @@ static inline uint64_t pair_hard_key(float s, unsigned id) {
 
 // The sequential loop: pair q = r * num_neg + j takes the best of cand(q, 0 .. num_cand - 1), cand(q, i) the plain rule's negative of pair
 // index q * num_cand + i.  neg_out[n * num_neg]; score_out (or nullptr) the chosen candidate's score.  An exhausted entry names its
-// plain-rule pair index.
+// plain-rule pair index.  wt with a table: the candidates are the WEIGHTED plain rule's (section 6ae), in form wform (equal results).
 static inline void pair_hard_draw_host(const PairSrcLists &L, long num_item, long n, const unsigned *user, int num_neg, int num_cand, uint64_t seed,
                                        int k, const float *W_user, const float *W_item, const float *i_bias, unsigned *neg_out, float *score_out,
-                                       int max_draws = PAIR_SRC_DRAWS) {
+                                       int max_draws = PAIR_SRC_DRAWS, const PairWeightDev *wt = nullptr, int wform = 1) {
     if (!neg_out || !W_user || !W_item || !i_bias || k < 1) fail("pair_source: bad arguments");
     for (long r = 0; r < n; r++) {
         const int p0 = L.uptr[user[r]], p1 = L.uptr[(size_t)user[r] + 1];
@@ -66,7 +66,7 @@ static inline void pair_hard_draw_host(const PairSrcLists &L, long num_item, lon
             for (int i = 0; i < num_cand; i++) {
                 const long e = q * num_cand + i;
                 unsigned id;
-                if (!pair_src_pick(seed, (uint64_t)e, (unsigned)num_item, L.uitems.data(), p0, p1, max_draws, &id))
+                if (!pair_any_pick(seed, (uint64_t)e, (unsigned)num_item, L.uitems.data(), p0, p1, max_draws, &id, wt, wform))
                     fail("pair_source: pair " + std::to_string(e) + " found no negative in " + std::to_string(max_draws) + " draws");
                 const float s = pair_hard_score(k, urow, W_item + (size_t)id * (size_t)k, i_bias[id]);
                 const uint64_t key = pair_hard_key(s, id);
@@ -78,16 +78,23 @@ static inline void pair_hard_draw_host(const PairSrcLists &L, long num_item, lon
     }
 }
 
-// svdf_pair_hard_negatives: the whole rule on the host
+// svdf_pair_hard_negatives (item_weight == nullptr) and svdf_pair_hard_negatives_weighted: the whole rule on the host
 static inline void pair_hard_negatives(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, int num_neg, int num_cand,
                                        uint64_t seed, int num_factor, const float *W_user, const float *W_item, const float *i_bias, unsigned *neg_out,
-                                       float *score_out) {
+                                       float *score_out, const unsigned *item_weight = nullptr) {
     pair_src_check_rows(num_user, num_item, n, user, pos_item);
     pair_hard_check_pass(n, num_neg, num_cand);
     if (num_factor < 1 || num_factor > 1024) fail("pair_source: hard negatives need num_factor between 1 and 1024");
     PairSrcLists L;
-    pair_src_build(num_user, num_item, n, user, pos_item, L, pair_src_threads(n));
-    pair_hard_draw_host(L, num_item, n, user, num_neg, num_cand, seed, num_factor, W_user, W_item, i_bias, neg_out, score_out);
+    if (!item_weight) {
+        pair_src_build(num_user, num_item, n, user, pos_item, L, pair_src_threads(n));
+        pair_hard_draw_host(L, num_item, n, user, num_neg, num_cand, seed, num_factor, W_user, W_item, i_bias, neg_out, score_out);
+        return;
+    }
+    PairWeightLists Wt;
+    pair_weight_source(num_user, num_item, n, user, pos_item, item_weight, L, Wt);
+    const PairWeightDev T = Wt.view();
+    pair_hard_draw_host(L, num_item, n, user, num_neg, num_cand, seed, num_factor, W_user, W_item, i_bias, neg_out, score_out, PAIR_SRC_DRAWS, &T, 1);
 }
 
 }  // namespace svdf

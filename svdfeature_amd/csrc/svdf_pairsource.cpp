@@ -5,6 +5,8 @@
 // window sequence of svdf_wseq.cpp (section 6v's builder) and the exact level schedule of schedule_device_columns.  Everything else copies
 // the columns back and IS dataset_from_pairs on them, so no result depends on the route.  A HARD pass (section 6ad, svdf_k_pairhard.hip:
 // the best of num_cand candidates by live score) differs in the step that fills the columns and in what it admits, and in nothing else.
+// A WEIGHTED source (section 6ae) also keeps the running sums of its item weights and their guide table (svdf_pairweight_lists.h); both
+// kernels then draw through those tables, and nothing else about a pass changes.
 #include <svdfeature_amd.h>
 
 #include <memory>
@@ -29,14 +31,20 @@ void Engine::pair_source_forget(PairSource *src) {
     pair_sources_.erase(std::remove(pair_sources_.begin(), pair_sources_.end(), src), pair_sources_.end());   // (every draw has been waited for)
 }
 
-PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsigned *pos) {
+PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsigned *pos, const unsigned *item_weight) {
     check(trainer_ready_, "pair_source: call init_model / load_model and init_trainer first");
-    // ---- the rows and the lists, before any device work
-    pair_src_check_rows((long)mp_.num_user, (long)mp_.num_item, n, user, pos);
+    // ---- the rows, the weights and the lists, before any device work
     PairSrcLists L;
-    pair_src_build((long)mp_.num_user, (long)mp_.num_item, n, user, pos, L, pair_src_threads(n));
+    PairWeightLists Wt;
+    if (item_weight) pair_weight_source((long)mp_.num_user, (long)mp_.num_item, n, user, pos, item_weight, L, Wt);
+    else {
+        pair_src_check_rows((long)mp_.num_user, (long)mp_.num_item, n, user, pos);
+        pair_src_build((long)mp_.num_user, (long)mp_.num_item, n, user, pos, L, pair_src_threads(n));
+    }
     std::unique_ptr<PairSource> src(new PairSource());
     src->n = n;
+    src->weighted = item_weight != nullptr;
+    if (src->weighted) { src->weight_sum = Wt.cdf.back(); src->weight_shift = Wt.shift; }
     for (long r = 1; r < n; r++) src->same += user[r] == user[r - 1];
     if (!host_only_) {   // (a host-only handle's source reaches every refusal of a pass, then "needs a GPU")
         need_device("pair_source");
@@ -48,7 +56,13 @@ PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsig
         src->pos.upload(pos, (size_t)n, stream_);
         src->uptr.upload(L.uptr.data(), L.uptr.size(), stream_);
         src->uitems.upload(L.uitems.data(), L.uitems.size(), stream_);
-        HIPCHECK(hipStreamSynchronize(stream_));   // L goes out of scope
+        if (src->weighted) {
+            pair_src_reserve(src->cdf, Wt.cdf.size(), "the item weights' running sums");
+            pair_src_reserve(src->guide, Wt.guide.size(), "the item weights' guide table");
+            src->cdf.upload(Wt.cdf.data(), Wt.cdf.size(), stream_);
+            src->guide.upload(Wt.guide.data(), Wt.guide.size(), stream_);
+        }
+        HIPCHECK(hipStreamSynchronize(stream_));   // L and Wt go out of scope
     }
     src->owner = this;
     pair_sources_.push_back(src.get());
@@ -73,10 +87,12 @@ void Engine::pair_source_launch(const PairSource &src, int num_neg, int num_cand
     D.out_user = d_user; D.out_pos = d_pos; D.out_neg = d_neg;
     D.flag = flag.p;
     H.num_cand = num_cand; H.out_score = d_score;
+    PairWeightDev T;   // (without weights: no table, the uniform kernels)
+    if (src.weighted) { T.cdf = src.cdf.p; T.guide = src.guide.p; T.W = src.weight_sum; T.num_item = D.num_item; T.shift = src.weight_shift; }
     if (num_cand > 0) {
         flush();   // behind whatever has been staged
-        launch_pair_hard(params(), H, (int)pair_hard_form_, stream_);
-    } else launch_pair_draw(D, stream_);
+        launch_pair_hard(params(), H, T, (int)pair_weight_form_, (int)pair_hard_form_, stream_);
+    } else launch_pair_draw(D, T, (int)pair_weight_form_, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_++;
     unsigned spent = 0;
@@ -140,6 +156,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
         Dataset *ds = dataset_from_pairs(N, hu.data(), hp.data(), hq.data());
         n_pair_src_fallback_++;
         n_pair_src_hard_ += num_cand > 0;
+        n_pair_src_weighted_ += src->weighted;
         return ds;
     }
     if (windows_hbm) {   // section 6v's builder on the pos / neg columns as drawn: item counts, window rule and windows from where they are
@@ -147,6 +164,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
         if (!seq) fail("pair_source: the drawn columns hold an id the windows refuse");   // (validated ids, pos != neg: not reached)
         n_pair_src_hbm_++;
         n_pair_src_hard_ += num_cand > 0;
+        n_pair_src_weighted_ += src->weighted;
         return seq;
     }
     // ---- the merged, index-sorted form the level schedule starts from: lower / higher item id and the entries' signs (pos != neg by the rule)
@@ -175,7 +193,34 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     ds->algorithmic_bytes = N * (8L * mp_.num_factor * 3 + 8 * nb2 + 16 + 8 * 3);
     n_pair_src_hbm_++;
     n_pair_src_hard_ += num_cand > 0;
+    n_pair_src_weighted_ += src->weighted;
     return ds.release();
+}
+
+// The probe svdf_pair_weight_lookup on a trainer: the tables of (num_item, item_weight) built and validated as a weighted source builds them,
+// uploaded, and the map of k_pair_draw / k_pair_hard run on the caller's words in one small launch.
+void Engine::pair_weight_lookup(long num_item, const unsigned *item_weight, int form, long nx, const uint64_t *x, unsigned *id_out) {
+    check(form >= 0 && form <= 2 && nx >= 0 && (nx == 0 || (x && id_out)), "pair_weight_lookup: bad arguments");
+    PairWeightLists Wt;
+    pair_weight_build(num_item, item_weight, Wt);
+    need_device("pair_weight_lookup");
+    if (nx == 0) return;
+    DevBuf<unsigned> cdf, guide, ids;
+    DevBuf<uint64_t> words;
+    pair_src_reserve(cdf, Wt.cdf.size(), "the item weights' running sums");
+    pair_src_reserve(guide, Wt.guide.size(), "the item weights' guide table");
+    pair_src_reserve(words, (size_t)nx, "the words");
+    pair_src_reserve(ids, (size_t)nx, "the ids");
+    cdf.upload(Wt.cdf.data(), Wt.cdf.size(), stream_);
+    guide.upload(Wt.guide.data(), Wt.guide.size(), stream_);
+    words.upload(x, (size_t)nx, stream_);
+    PairWeightDev T = Wt.view();
+    T.cdf = cdf.p; T.guide = guide.p;
+    launch_pair_weight_lookup(T, form == 0 ? (int)pair_weight_form_ : form, nx, words.p, ids.p, stream_);
+    HIPCHECK(hipGetLastError());
+    n_launches_++;
+    HIPCHECK(hipMemcpyAsync(id_out, ids.p, (size_t)nx * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));
 }
 
 }  // namespace svdf

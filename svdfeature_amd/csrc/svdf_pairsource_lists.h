@@ -68,8 +68,10 @@ static inline void pair_src_check_pass(long n, int num_neg) {
 // The lists of validated rows: a counting sort of the rows by user (a user's items in row order), then every user's slice sorted and its
 // repeats dropped -- threads > 1: contiguous ranges of users with about equal numbers of rows side by side, the result that of one thread --,
 // the slices closed up, and THE DENSITY RULE: a user with rows must leave 64 * (num_item - |P(u)|) >= num_item, so that every draw of
-// every pair is accepted with probability >= 1 / 64 (the first such user in id order is named).
-static inline void pair_src_build(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, PairSrcLists &out, int threads = 1) {
+// every pair is accepted with probability >= 1 / 64 (the first such user in id order is named).  density = false leaves the rule out: a
+// weighted source applies its own to the lists (svdf_pairweight_lists.h).
+static inline void pair_src_build(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item, PairSrcLists &out, int threads = 1,
+                                  bool density = true) {
     std::vector<long> first((size_t)num_user + 1, 0);
     for (long r = 0; r < n; r++) first[(size_t)user[r] + 1]++;
     for (long u = 0; u < num_user; u++) first[(size_t)u + 1] += first[(size_t)u];
@@ -101,7 +103,7 @@ static inline void pair_src_build(long num_user, long num_item, long n, const un
     out.uptr.assign((size_t)num_user + 1, 0);
     for (long u = 0; u < num_user; u++) {
         const long d = distinct[(size_t)u];
-        if (d > 0 && 64 * (num_item - d) < num_item)
+        if (density && d > 0 && 64 * (num_item - d) < num_item)
             fail("pair_source: user " + std::to_string(u) + " has " + std::to_string(d) + " distinct positive items of " + std::to_string(num_item) +
                  ": fewer than 1 item in 64 is left to draw a negative from; draw its negatives yourself (svdf_dataset_from_pairs)");
         out.uptr[(size_t)u + 1] = out.uptr[(size_t)u] + (int)d;
