@@ -654,8 +654,9 @@ std::string Engine::path_for(const Dataset *ds) const {
     case 9: snprintf(buf, sizeof(buf), "exact, %ld levels: hot rows walked as units (k_svdpp_wave on %s parameters, %ld units) + cold ratings through the contract kernel",
                      L, ds->pv_item_pivot ? "transposed" : "plain", ds->num_units); return buf;
     case 10: {
-        char st[96] = "rows in W";
-        if (runs_staged(ds)) snprintf(st, sizeof(st), "rows handed from run to run through staging slots (runs_stage, %.1f MB)", (double)ds->rn_stage_bytes / 1048576.0);
+        char st[192] = "rows in W";
+        if (runs_staged(ds)) snprintf(st, sizeof(st), "rows handed from run to run through staging slots numbered run-major, s * %d + j, rows plane-major (runs_stage, %.1f MB), copied in from W at every pass",
+                                      1 + ds->rn_len, (double)ds->rn_stage_bytes / 1048576.0);
         else if (ds->rn_stage_state == 2) snprintf(st, sizeof(st), "rows in W (operand staging refused)");
         char hist[160] = "";
         for (int c = 1, at = 0; c <= ds->rn_len && at < (int)sizeof(hist) - 24; c++) at += snprintf(hist + at, sizeof(hist) - (size_t)at, "%s%ld", c > 1 ? " / " : "", (long)ds->rn_hist[c]);

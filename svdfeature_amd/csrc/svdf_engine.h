@@ -303,8 +303,9 @@ struct Dataset {
     // longest run = the steps the waves walk, the sets whose runs differ in length; rn_hist[length] = runs of that length
     int rn_order = 0;
     int64_t rn_wave_steps = 0, rn_mixed_sets = 0, rn_hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // ... and their operand staging (knob "runs_stage"; svdf_runs.cpp: runs_stage_build): slot j * num_units + s; rn_first[r] = the slot of row r's first touch
-    DevBuf<float> rn_stage_row, rn_stage_bias;
+    // ... and their operand staging (knob "runs_stage"; svdf_runs.cpp: runs_stage_build): slot s * (1 + rn_len) + j, run-major, indexes rn_dst and rn_stage_bias; the
+    // slot's row is row j * num_units + s of rn_stage_row; rn_first[r] = the slot of row r's first touch; rn_label_rm[s * rn_len + j] = rn_label[j][s]
+    DevBuf<float> rn_stage_row, rn_stage_bias, rn_label_rm;
     DevBuf<unsigned> rn_dst, rn_first;
     int rn_stage_state = 0;       // 0 not tried yet, 1 built, 2 refused (the gate, or no memory): the data set keeps reading and writing W
     unsigned rn_stage_row0 = 0;   // the W row of user 0 the HOME words were built against

@@ -199,8 +199,11 @@ void launch_runs_order_stats(const RunSchedule &S, const long *level_ptr, int nl
 }
 
 // ------------------------------------------------------------------------------------------------- operand staging (knob "runs_stage")
-// Every row is read and written at every touch anyway, so the write can go where the row's NEXT reader will look: slot j * nunit + s of the
-// staging buffers, s = the reader's position in level order, j = 0 its item row, 1 .. R its users' rows.  The links are a file-order fact too: runs
+// Every row is read and written at every touch anyway, so the write can go where the row's NEXT reader will look: slot s * (1 + R) + j of the
+// staging buffers, s = the reader's position in level order, j = 0 its item row, 1 .. R its users' rows.  The slot NUMBER is run-major, and so are the
+// words kept per slot (dst, bias; the labels beside them): what the runs of one wave need of each is one contiguous block.  The slot's ROW lies
+// plane-major, row j * nunit + s of stage_row (runs_row_of): rows laid out run-major cost 1.2 ms per pass (profiles/r37_runs_pack.md).  The links are a
+// file-order fact too: runs
 // are numbered by head position and a row's touches ascend in that number, so a stable sort of (row, unit number) puts every touch next to its successor.
 // pos_of[order[s]] = s: unit number -> position in level order
 __global__ __launch_bounds__(256) void k_runs_inverse(const int *order, long nunit, unsigned *pos_of) {
@@ -217,8 +220,19 @@ __global__ __launch_bounds__(256) void k_runs_operands(const RunSchedule S, cons
         const unsigned s = pos_of[un];
         const unsigned id = j == 0 ? num_user + S.item[s] : S.user[j - 1][s];
         keys[t] = (j > 0 && id == (unsigned)SLOT_ABSENT) ? 0xFFFFFFFFu : id;
-        vals[t] = (unsigned)((long)j * nunit + s);
+        vals[t] = (unsigned)((long)s * (1 + R) + j);
     }
+}
+// the labels run-major, next to the slots: out[s * R + j] = label[j][s] of the level-sorted planes (the planes stay: the pass on rows in W reads them)
+__global__ __launch_bounds__(256) void k_runs_label_rm(const RunSchedule S, long nunit, int R, float *out) {
+    const long stride = (long)gridDim.x * blockDim.x, m = nunit * R;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride) {
+        const long s = t / R;
+        out[t] = S.label[(int)(t - s * R)][s];
+    }
+}
+void launch_runs_label_rm(const RunSchedule &S, long nunit, int R, float *out, hipStream_t st) {
+    if (nunit > 0) hipLaunchKernelGGL(k_runs_label_rm, dim3(runs_grid(nunit * R)), dim3(256), 0, st, S, nunit, R, out);
 }
 // keys / vals sorted: dst of every slot, and the slot of every touched row's first touch
 __global__ __launch_bounds__(256) void k_runs_links(const unsigned *keys, const unsigned *vals, long m, unsigned row0, unsigned *dst, unsigned *first) {
@@ -242,24 +256,29 @@ void launch_runs_stage_links(const RunSchedule &S, const int *order, long nunit,
 }
 // Before level 0 of a staged pass: W is the truth between passes, so every touched row (and its bias) is copied into the slot of its first touch.
 // first[r], r in the scheduler's numbering = W row row0 + r; LPR lanes per row
+// (ns = 1 + R slots per run.)  Where the ROW of slot d = s * ns + j lies in stage_row: plane-major, row j * nunit + s
+__device__ __forceinline__ size_t runs_row_of(unsigned d, int ns, size_t nunit) {
+    const unsigned s = d / (unsigned)ns;
+    return (size_t)(d - s * (unsigned)ns) * nunit + (size_t)s;
+}
 template <int LPR>
-__global__ __launch_bounds__(256) void k_runs_stage_in(const DevParams P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias) {
+__global__ __launch_bounds__(256) void k_runs_stage_in(const DevParams P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, int ns, long nunit) {
     const int L = threadIdx.x % LPR;
     const long per = 256 / LPR, stride = (long)gridDim.x * per;
     for (long r = (long)blockIdx.x * per + threadIdx.x / LPR; r < nrow; r += stride) {
         const unsigned slot = first[r];
         if (slot == (unsigned)SLOT_ABSENT) continue;
-        store_row<LPR>(stage_row, slot, P.pitch, L, P.k, load_row_nt<LPR>(P.W, (size_t)row0 + (size_t)r, P.pitch, L, P.k));
+        store_row<LPR>(stage_row, runs_row_of(slot, ns, (size_t)nunit), P.pitch, L, P.k, load_row_nt<LPR>(P.W, (size_t)row0 + (size_t)r, P.pitch, L, P.k));
         if (L == 0) stage_bias[slot] = P.bias[(size_t)row0 + (size_t)r];
     }
 }
-void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, hipStream_t st) {
+void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, int ns, long nunit, hipStream_t st) {
     if (nrow <= 0) return;
     const long per = P.k == 128 ? 8 : 16;
     long grid = (nrow + per - 1) / per;
     if (grid > 16384) grid = 16384;
-    if (P.k == 128) hipLaunchKernelGGL(k_runs_stage_in<32>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias);
-    else hipLaunchKernelGGL(k_runs_stage_in<16>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias);
+    if (P.k == 128) hipLaunchKernelGGL(k_runs_stage_in<32>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias, ns, nunit);
+    else hipLaunchKernelGGL(k_runs_stage_in<16>, dim3((int)grid), dim3(256), 0, st, P, first, nrow, row0, stage_row, stage_bias, ns, nunit);
 }
 
 // ------------------------------------------------------------------------------------------------- the pass
@@ -317,32 +336,51 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 }
             }
         } else {
-            const size_t nun = (size_t)S.nunit, at0 = (size_t)sc;
-            ir = load_u32_nt(S.dst + at0);
+            // Slots are numbered run-major, s * (1 + R) + j: the dst words, the biases and the labels of the row set's runs are one block each -- IPS * (1 + R)
+            // / IPS * R dwords from the set's first run on, at most one per lane -- and one load instruction each; a lane past the block, or past the
+            // level's end in a partial set, loads nothing.  Every lane group takes its run's words out of the blocks with ds_bpermute (a dead group: run w0's,
+            // never used).  As planes of their own these columns were 14 of the wave's 24 load instructions, 32 bytes each (profiles/r37_runs_pack.md).
+            // The rows themselves stay plane-major, row j * nunit + s of stage_row: one load instruction of the wave reads 8 neighbouring rows, as before.
+            constexpr int NS = 1 + R;
+            static_assert(IPS * NS <= 64, "a row set's slot words must fit one dword per lane");
+            const int nrun = end - w0 < (long)IPS ? (int)(end - w0) : IPS;
+            const size_t blk = (size_t)w0 * NS, nun = (size_t)S.nunit, at0 = (size_t)sc;
+            unsigned dw = (unsigned)SLOT_ABSENT;
+            float lw = 0.0f, bw = 0.0f;
+            if (lane < nrun * NS) dw = load_u32_nt(S.dst + blk + lane);
+            if (lane < nrun * R) lw = S.label_rm[(size_t)w0 * R + lane];
+            if (lane < nrun * NS) bw = load_f32_nt(S.stage_bias + blk + lane);
 #pragma unroll
-            for (int j = 0; j < R; j++) {
-                ur[j] = load_u32_nt(S.dst + (size_t)(1 + j) * nun + at0);
-                label[j] = S.label[j][sc];
-            }
+            for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(S.stage_row, at0, pitch, m + v * LANES, K) : f4zero();
+            const int g0 = (int)(sc - w0);
+            ir = __shfl(dw, g0 * NS);
+#pragma unroll
+            for (int j = 0; j < R; j++) ur[j] = __shfl(dw, g0 * NS + 1 + j);
             // Row by row, the shape of the loads from W above: one operand per round trip, every operand under `if (j < n)`.  The addresses need no id, so
             // the whole read could leave with the dst words -- built and measured: 19.8 against 16.9 ms per pass (W) and 16.2 (this form), profiles/r26_runs_stage.md.
 #pragma unroll
             for (int j = 0; j < R; j++)
                 if (live && ur[j] != (unsigned)SLOT_ABSENT) n = j + 1;
 #pragma unroll
-            for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(S.stage_row, at0, pitch, m + v * LANES, K) : f4zero();
-            bi = live ? load_f32_nt(S.stage_bias + at0) : 0.0f;
-#pragma unroll
             for (int j = 0; j < R; j++) {
 #pragma unroll
                 for (int v = 0; v < V; v++) p[j][v] = f4zero();
-                bu[j] = 0.0f;
                 if (j < n) {
-                    const size_t at = (size_t)(1 + j) * nun + at0;
 #pragma unroll
-                    for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(S.stage_row, at, pitch, m + v * LANES, K);
-                    bu[j] = load_f32_nt(S.stage_bias + at);
+                    for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(S.stage_row, (size_t)(1 + j) * nun + at0, pitch, m + v * LANES, K);
+                    // Row j is here before row j + 1 leaves.  The per-row bias loads used to make the compiler wait like this; without them it would send
+                    // all rows at once: 15.4 against 14.8 ms per pass (profiles/r37_runs_pack.md, section 3).
+                    asm volatile("" :: "v"(p[j][0].x), "v"(p[j][V - 1].x));
                 }
+            }
+            // (the bias and label blocks left before the rows and are here before them: these moves add no memory wait)
+            const float b0 = __shfl(bw, g0 * NS);
+            bi = live ? b0 : 0.0f;
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                const float b = __shfl(bw, g0 * NS + 1 + j);
+                bu[j] = j < n ? b : 0.0f;
+                label[j] = __shfl(lw, g0 * R + j);
             }
         }
         // Every row is here before step 0 (an empty statement that reads a register of each: the compiler places its counted waits in front of
@@ -374,11 +412,12 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
             nbi = nbi * (1.0f - P.lr * P.wd_item_bias);
             const bool act = j < n;
             float *wb = P.W, *bb = P.bias;
-            size_t wr = ur[j];
+            size_t wr = ur[j], wrow = ur[j];
             if constexpr (STAGED) {   // the row's next reader's slot, or home at its last touch of the pass
                 const bool home = (ur[j] & (unsigned)RUNS_HOME) != 0u;
                 wb = home ? P.W : S.stage_row; bb = home ? P.bias : S.stage_bias;
                 wr = ur[j] & ~(unsigned)RUNS_HOME;
+                wrow = home ? wr : runs_row_of((unsigned)wr, 1 + R, (size_t)S.nunit);
             }
 #pragma unroll
             for (int v = 0; v < V; v++) {
@@ -388,7 +427,7 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 wu.x = wu.x * dec_u1; wu.y = wu.y * dec_u1; wu.z = wu.z * dec_u1; wu.w = wu.w * dec_u1;
                 wi.x = wi.x * dec_i1; wi.y = wi.y * dec_i1; wi.z = wi.z * dec_i1; wi.w = wi.w * dec_i1;
                 if (act) {
-                    store_row<K / 4>(wb, wr, pitch, m + v * LANES, K, wu);
+                    store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, wu);
                     q[v] = wi;
                 }
             }
@@ -399,14 +438,15 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
         }
         if (live) {
             float *wb = P.W, *bb = P.bias;
-            size_t wr = ir;
+            size_t wr = ir, wrow = ir;
             if constexpr (STAGED) {
                 const bool home = (ir & (unsigned)RUNS_HOME) != 0u;
                 wb = home ? P.W : S.stage_row; bb = home ? P.bias : S.stage_bias;
                 wr = ir & ~(unsigned)RUNS_HOME;
+                wrow = home ? wr : runs_row_of((unsigned)wr, 1 + R, (size_t)S.nunit);
             }
 #pragma unroll
-            for (int v = 0; v < V; v++) store_row<K / 4>(wb, wr, pitch, m + v * LANES, K, q[v]);
+            for (int v = 0; v < V; v++) store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, q[v]);
             bb[wr] = bi;
         }
     }

@@ -145,9 +145,12 @@ void launch_runs_iota(unsigned *v, long n, hipStream_t st);
 void launch_runs_fill_u32(unsigned *v, long n, unsigned x, hipStream_t st);
 // operand staging of a runs data set (knob "runs_stage"): dst[] / first[] from the level-sorted columns S and the schedule's order (ka .. vb: (1 + R) * nunit
 // words each, pos_of: nunit; first: nrow = num_user + num_item words; row0 = the W row of user 0), and the copy of every touched row into its first slot
+// (ns = 1 + R: slot s * ns + j, its row at row j * nunit + s of stage_row)
 void launch_runs_stage_links(const RunSchedule &S, const int *order, long nunit, int R, unsigned num_user, unsigned row0, unsigned *pos_of, unsigned *ka, unsigned *kb,
                              unsigned *va, unsigned *vb, void **tmp, size_t *tmp_bytes, unsigned *dst, unsigned *first, long nrow, hipStream_t st);
-void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, hipStream_t st);
+void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, unsigned row0, float *stage_row, float *stage_bias, int ns, long nunit, hipStream_t st);
+// ... and the labels next to the run-major slots: out[s * R + j] = S.label[j][s]
+void launch_runs_label_rm(const RunSchedule &S, long nunit, int R, float *out, hipStream_t st);
 // in-level order of the runs (knob "runs_order"): key[un] = (R - length) * num_item + item over the columns in unit-number order; over the level-sorted
 // columns S: tot[0] = sum over the aligned sets of `ips` runs (from each level's begin) of the set's longest run, tot[1] = sets whose runs differ in length,
 // tot[1 + length] = runs of that length

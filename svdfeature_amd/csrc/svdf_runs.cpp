@@ -151,7 +151,8 @@ Dataset *Engine::runs_dataset_from_triples(long n, const unsigned *user, const u
 }
 
 // Operand staging (knob "runs_stage"): (1 + R) * nunit slots of one row + one bias, the dst word of each, the first slot of every
-// row.  Built once per data set from the level-sorted columns and the schedule's order; refused -- the data set then keeps reading and writing W, the
+// row, and the labels once more in the slots' order.  Slot s * (1 + R) + j = operand j of the run at position s of the level order (run-major: what one
+// wave needs of the dst words, biases and labels is contiguous; the rows stay plane-major, row j * nunit + s).  Built once per data set from the level-sorted columns and the schedule's order; refused -- the data set then keeps reading and writing W, the
 // same bits -- when the slots do not fit 31 bits, half of the free device memory or the knob "runs_stage_max_mb", or when the allocation fails.
 namespace {
 template <typename T>
@@ -169,9 +170,9 @@ void Engine::runs_stage_build(Dataset *ds) {
     const int R = ds->rn_len;
     const long m = (long)(1 + R) * nunit;
     if (nunit <= 0) return;
-    const int64_t bytes = (int64_t)m * ((int64_t)pitch_ * 4 + 8) + (int64_t)nrow * 4;
+    const int64_t bytes = (int64_t)m * ((int64_t)pitch_ * 4 + 8) + (int64_t)R * nunit * 4 + (int64_t)nrow * 4;   // rows, biases + dst words, labels, first[]
     auto refuse = [&](const char *why) {
-        ds->rn_stage_row.release(); ds->rn_stage_bias.release(); ds->rn_dst.release(); ds->rn_first.release();
+        ds->rn_stage_row.release(); ds->rn_stage_bias.release(); ds->rn_dst.release(); ds->rn_first.release(); ds->rn_label_rm.release();
         if (!getenv("SVDF_QUIET"))
             fprintf(stderr, "[svdfeature_amd] data set of %ld rows: no operand staging (%.1f MB: %s); its runs keep reading and writing W\n", (long)ds->num_row, (double)bytes / 1048576.0, why);
     };
@@ -182,7 +183,7 @@ void Engine::runs_stage_build(Dataset *ds) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); refuse("hipMemGetInfo failed"); return; }
     if ((uint64_t)bytes > (uint64_t)free_b / 2) { refuse("more than half of the free device memory"); return; }
     if (!try_reserve(ds->rn_stage_row, (size_t)m * (size_t)pitch_) || !try_reserve(ds->rn_stage_bias, (size_t)m) || !try_reserve(ds->rn_dst, (size_t)m) ||
-        !try_reserve(ds->rn_first, (size_t)nrow)) { refuse("hipMalloc failed"); return; }
+        !try_reserve(ds->rn_first, (size_t)nrow) || !try_reserve(ds->rn_label_rm, (size_t)R * (size_t)nunit)) { refuse("hipMalloc failed"); return; }
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
     struct FreeTmp { void *&p; ~FreeTmp() { if (p) (void)hipFree(p); } } free_tmp{tmp};
@@ -195,9 +196,10 @@ void Engine::runs_stage_build(Dataset *ds) {
         RunSchedule S;
         memset(&S, 0, sizeof(S));
         S.item = ds->rn_item.p;
-        for (int j = 0; j < R; j++) S.user[j] = ds->rn_user[j].p;
+        for (int j = 0; j < R; j++) { S.user[j] = ds->rn_user[j].p; S.label[j] = ds->rn_label[j].p; }
         launch_runs_stage_links(S, ds->order_dev.p, nunit, R, (unsigned)mp_.num_user, user_off_, pos_of.p, ka.p, kb.p, va.p, vb.p, &tmp, &tmp_bytes, ds->rn_dst.p,
                                 ds->rn_first.p, nrow, stream_);
+        launch_runs_label_rm(S, nunit, R, ds->rn_label_rm.p, stream_);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(stream_));
     } catch (const std::exception &ex) {
@@ -220,8 +222,8 @@ void Engine::runs_train(Dataset *ds) {
     if (runs_stage_ && ds->rn_stage_state == 0) runs_stage_build(ds);   // a data set built while the knob was off
     if (runs_staged(ds)) {
         // W is the truth between passes: every touched row goes to the slot of its first touch, the levels hand it on from slot to slot, its last touch writes it home
-        S.dst = ds->rn_dst.p; S.stage_row = ds->rn_stage_row.p; S.stage_bias = ds->rn_stage_bias.p; S.nunit = ds->num_units;
-        launch_runs_stage_in(P, ds->rn_first.p, (long)mp_.num_user + (long)mp_.num_item, user_off_, S.stage_row, S.stage_bias, stream_);
+        S.dst = ds->rn_dst.p; S.stage_row = ds->rn_stage_row.p; S.stage_bias = ds->rn_stage_bias.p; S.label_rm = ds->rn_label_rm.p; S.nunit = ds->num_units;
+        launch_runs_stage_in(P, ds->rn_first.p, (long)mp_.num_user + (long)mp_.num_item, user_off_, S.stage_row, S.stage_bias, 1 + ds->rn_len, ds->num_units, stream_);
         n_launches_++;
     }
     for (size_t l = 0; l < sc.num_levels(); l++) launch_basicmf_runs_soa(P, S, sc.level_ptr[l], sc.level_ptr[l + 1], ds->rn_len, runs_sets_, runs_block_, stream_);

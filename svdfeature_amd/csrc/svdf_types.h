@@ -121,11 +121,15 @@ struct RunSchedule {
     const unsigned *user[8];
     const float *label[8];
     // operand staging (knob "runs_stage"): operand (j, s) -- j = 0 the item row of run s, j = 1 .. R its users' rows -- lies in
-    // slot j * nunit + s of stage_row (pitch floats each) / stage_bias; dst[slot] = the slot of the row's NEXT touch, RUNS_HOME | W row at its
-    // last touch of the pass, SLOT_ABSENT for a hole (never read or written).  nullptr: rows are read from and written to W.
+    // slot s * (1 + R) + j.  Slots are numbered RUN-MAJOR, and dst[], stage_bias[] and the labels (label_rm[s * R + j], a copy of label[j][s]) are
+    // indexed by that number: what the 64 / LANES runs a wave carries need of each is one contiguous block and one load instruction.  The slot's ROW
+    // lies plane-major, row j * nunit + s of stage_row (pitch floats each): one load instruction of a wave reads neighbouring rows.  dst[slot] = the
+    // slot of the row's NEXT touch, RUNS_HOME | W row at its last touch of the pass, SLOT_ABSENT for a hole (its row and bias are never written; the
+    // bias word is read with the block and ignored).  dst == nullptr: rows are read from and written to W.
     const unsigned *dst;
     float *stage_row;
     float *stage_bias;
+    const float *label_rm;
     long nunit;
 };
 enum : unsigned { RUNS_HOME = 0x80000000u };
