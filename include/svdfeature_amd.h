@@ -370,7 +370,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 44 / 45 passes built from a pair source (svdf_dataset_from_pair_source) without the pair columns leaving HBM / through
  * svdf_dataset_from_pairs' own builder on the columns copied back,
  * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard),
- * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted) */
+ * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted),
+ * 48 of the passes under 44 / 45, the shuffled ones (svdf_dataset_from_pair_source_shuffled) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -985,6 +986,58 @@ int svdf_pair_negatives_weighted(long num_user, long num_item, long n, const uns
 int svdf_pair_hard_negatives_weighted(long num_user, long num_item, long n, const unsigned *user, const unsigned *pos_item,
                                       const unsigned *item_weight, int num_neg, int num_cand, uint64_t seed, int num_factor, const float *W_user,
                                       const float *W_item, const float *i_bias, unsigned *neg_out, float *score_out);
+
+/* ---- SHUFFLED passes: the rows of a source in a fresh order every round, on the device.  SGD on implicit feedback
+ * visits its examples in a new order each epoch; the passes above train the rows in the caller's order, the same every round.  A shuffled
+ * pass takes one more scalar, order_seed; nothing is permuted on the host, no table is built and nothing is sorted.
+ * THE RULE, in unsigned 64-bit arithmetic wrapping mod 2^64; mix and G are the sampled calls' above.  Position p = 0 .. n-1 of the pass holds
+ * source row sigma(p), and THE SHUFFLED PASS IS, BIT FOR BIT, THE PASS OF THE SAME KIND (plain, hard, on a weighted source) ON A SOURCE WHOSE
+ * ROWS ARE (user[sigma(p)], pos[sigma(p)]), with the same num_neg, num_cand, seed and weights.  P(u), the density rules and the weight table
+ * do not depend on the order of the rows; the pair index q = p * num_neg + j counts POSITIONS and the streams are the plain rule's;
+ * order_seed and seed are independent (they may be equal).  sigma is a keyed bijection on [0, n): a 4-round unbalanced Feistel network over
+ * b bits with cycle walking, O(1) per position:
+ *   SALT_ORDER = 0x706169726F726472                  (ASCII "pairordr")
+ *   K_i  = mix((order_seed ^ SALT_ORDER) + (i + 1) * G)          i = 0 .. 3
+ *   b    = the smallest integer >= 2 with 2^b >= n
+ *   E(x): wl = b / 2 (rounded down), wr = b - wl;  L = x >> wr;  R = x & (2^wr - 1)
+ *         for i = 0 .. 3:  f = mix(K_i + (R + 1) * G) >> (64 - wl);   (L, R) = (R, L ^ f);   swap(wl, wr)
+ *         return (L << wr) | R                                   (after four rounds the widths are the first ones again)
+ *   sigma(p): x = p;  repeat x = E(x) until x < n               (at least one application; AT MOST WALKS = 128)
+ * Every round maps (L, R) to (R, L ^ f(R)), which is undone by (R', L') -> (L' ^ f(R'), R'): E is a bijection on [0, 2^b), and following E from
+ * p until it re-enters [0, n) is one on [0, n).  THE WALK BOUND: for n >= 3, 2^b < 2 n, so a step leaves the range with probability below
+ * 1 / 2; if E behaved as a random permutation, some position would need more than 128 steps with probability below n * 2^-128 < 2^-97.  That
+ * is a heuristic, not a proof, so the bound is a compile-time constant (as T = 4096 is for the draws): a position that exhausts it fails
+ * the call -- on the device through a one-word flag, on the host in the same words -- with
+ *   "pair_source: order_seed S needs more than 128 steps at position P; take another order_seed"
+ * and no input makes the kernel run long.  WHAT IS PROMISED is the bijection and these bits, NOT a statistically perfect shuffle: four
+ * rounds of a hash are not a uniform draw from the n! orders, and at n <= 4 the 24 orders are visibly not equally likely.
+ * PINNED VECTORS (order_seed 12345): K_0 .. K_3 = 0x55f0c474c3817246, 0x212e2874c5b74625, 0x1b12a40bba019e32, 0xdbe2e77f7d83df15;
+ *   n = 10: sigma = 2, 4, 8, 3, 7, 1, 6, 9, 0, 5;   order_seed 12346, n = 10: 0, 8, 1, 6, 3, 9, 7, 5, 2, 4;
+ *   n = 1200, the first eight: 648, 161, 507, 552, 509, 792, 1082, 757;   n = 3: 1, 2, 0;   n = 2: 1, 0;   n = 1: 0 (after four applications)
+ *   rows (user, pos) = (4, 10), (4, 700), (9, 10), seed 12345, num_item 1200, num_neg 1: the pass is (4, 700, 607), (9, 10, 549), (4, 10, 766)
+ *   -- the negatives pinned above for the plain pass, which belong to positions, on the rows in the order 1, 2, 0.
+ * svdf_dataset_from_pair_source_shuffled is svdf_dataset_from_pair_source (num_cand = 0) or svdf_dataset_from_pair_source_hard (num_cand >= 1;
+ * num_cand = 1 equals plain) on the permuted rows.  One more kernel (k_pair_order, a lane per position) gathers the rows in the order sigma
+ * into two scratch columns of n words, which the draw kernels read in place of the source's; it also counts the adjacent positions that share
+ * a user, and ROUTES, FALLBACK, REFUSALS AND COUNTERS 44 .. 47 ARE THE PLAIN PASS'S, DECIDED ON THE PERMUTED ORDER: a shuffled pass over a
+ * user-grouped source stays in HBM wherever an ungrouped one does.  Counter 48 counts the shuffled passes among those under 44 / 45.
+ * svdf_pair_source_draw_shuffled copies the pass's own three columns (n * num_neg entries each; user_out and pos_out say which row a negative
+ * belongs to) and, for num_cand >= 1 with score_out not NULL, the chosen scores.  svdf_pair_order is sigma on the host -- no GPU, no handle;
+ * the host rules of a shuffled pass are svdf_pair_negatives* / svdf_pair_hard_negatives* on (user[sigma], pos[sigma]).
+ * REFUSED on the host, before any device work and before "needs a GPU": what the plain pass (num_cand = 0) or the hard pass refuses, word
+ * for word; svdf_pair_order refuses n < 1 ("pair_source: a source needs at least one row (n >= 1)") and n >= 2^31 - 16 ("pair_source: n *
+ * num_neg must stay below 2^31 - 16").  No older entry point changes.
+ * MEASURED (one MI355X, 100 K users x 10 K items, 20 M positives, num_factor 128, num_neg 1, medians of five alternating rounds;
+ * profiles/r38_pair_order.md): a shuffled round takes 0.272 s on the exact pass and 0.164 s under `amd:step = minibatch`, against 1.33 s /
+ * 1.31 s for a host permutation + a new source + a plain pass per round and 3.38 s / 3.28 s for a host permutation + svdf_pair_negatives +
+ * svdf_dataset_from_pairs, with bit-equal models; against the unshuffled pass of the same build the order costs 0.4 / 1.6 ms, inside the
+ * spreads; k_pair_order takes 0.75 ms.  A user-grouped source takes 14.3 s per unshuffled round (user-run units through the fallback) and
+ * 0.281 s per shuffled one -- different passes.  On a planted set a fresh order per round did NOT change the sampled AUC. */
+svdf_dataset *svdf_dataset_from_pair_source_shuffled(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed, uint64_t order_seed);
+int svdf_pair_source_draw_shuffled(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed, uint64_t order_seed,
+                                   unsigned *user_out /* [n*num_neg] */, unsigned *pos_out /* [n*num_neg] */, unsigned *neg_out /* [n*num_neg] */,
+                                   float *score_out /* [n*num_neg] or NULL: the chosen score of a hard pass */);
+int svdf_pair_order(long n, uint64_t order_seed, unsigned *sigma_out /* [n] */);   /* host only: no GPU, no handle */
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

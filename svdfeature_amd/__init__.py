@@ -167,7 +167,8 @@ def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed, item_weigh
     """svdf_pair_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed) trains a source of these rows against, by the
     published rule (include/svdfeature_amd.h): uint32[n * num_neg], pair r * num_neg + j belongs to row r.  A host function:
     no GPU, no handle.  item_weight (uint32 per item): the negatives of a source created with these weights (svdf_pair_negatives_weighted,
-    DESIGN.md 6ae)."""
+    DESIGN.md 6ae).  The negatives of a SHUFFLED pass (shuffle=s) are this call on the rows user[sigma], pos_item[sigma] with
+    sigma = pair_order(n, s)."""
     lib = load_library()
     n, user, pos_item = _pair_rows(user, pos_item)
     neg = np.zeros(max(_pass_size(n, num_neg), 1), np.uint32)
@@ -179,6 +180,18 @@ def pair_negatives(num_user, num_item, user, pos_item, num_neg, seed, item_weigh
     if rc != 0:
         raise SvdfError(lib.svdf_last_error().decode())
     return neg[:n * int(num_neg)]
+
+
+def pair_order(n, order_seed):
+    """svdf_pair_order: the order of a shuffled pass (Trainer.dataset_from_pair_source(..., shuffle=order_seed)) -- uint32[n],
+    position p of the pass holds source row sigma[p]; a permutation of 0 .. n-1 by the published rule (include/svdfeature_amd.h).  A host
+    function: no GPU, no handle."""
+    lib = load_library()
+    n = int(n)
+    sigma = np.zeros(n if 1 <= n < (1 << 31) - 16 else 1, np.uint32)
+    if lib.svdf_pair_order(n, int(order_seed) & 0xFFFFFFFFFFFFFFFF, sigma) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return sigma
 
 
 def pair_weight_lookup(item_weight, x, form=1, trainer=None):
@@ -212,11 +225,18 @@ def _hard_size(n, num_neg, num_cand):
     return n * int(num_neg) if ok and n * int(num_neg) * int(num_cand) < (1 << 31) - 16 else 0
 
 
+def _shuffled_cand(hard):
+    """num_cand of the _shuffled entry points for hard=C: there 0 selects the plain pass, so a hard=0 is passed on as what the hard pass refuses"""
+    return int(hard) if int(hard) != 0 else -1
+
+
 def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, seed, W_user, W_item, i_bias, return_scores=False, item_weight=None):
     """svdf_pair_hard_negatives: the negatives Trainer.dataset_from_pair_source(src, num_neg, seed, hard=num_cand) trains against on the model
     (W_user [num_user, k], W_item [num_item, k], i_bias [num_item]) -- per pair the best-scoring of num_cand candidates of the plain rule
     (include/svdfeature_amd.h): uint32[n * num_neg], with return_scores also the chosen scores.  A host function: no GPU, no
-    handle.  item_weight: the candidates are those of a source created with these weights (svdf_pair_hard_negatives_weighted)."""
+    handle.  item_weight: the candidates are those of a source created with these weights (svdf_pair_hard_negatives_weighted).
+    The negatives of a SHUFFLED hard pass (shuffle=s) are this call on the rows user[sigma], pos_item[sigma] with
+    sigma = pair_order(n, s)."""
     lib = load_library()
     n, user, pos_item = _pair_rows(user, pos_item)
     W_user, W_item = np.ascontiguousarray(W_user, np.float32), np.ascontiguousarray(W_item, np.float32)
@@ -403,6 +423,10 @@ def load_library():
     lib.svdf_pair_source_draw_hard.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64, _u32p, C.c_void_p]
     lib.svdf_pair_hard_negatives.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, C.c_int, C.c_int, C.c_uint64, C.c_int, _f32p, _f32p, _f32p, _u32p,
                                              C.c_void_p]
+    lib.svdf_dataset_from_pair_source_shuffled.restype = P
+    lib.svdf_dataset_from_pair_source_shuffled.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64, C.c_uint64]
+    lib.svdf_pair_source_draw_shuffled.argtypes = [P, P, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _u32p, _u32p, _u32p, C.c_void_p]
+    lib.svdf_pair_order.argtypes = [C.c_long, C.c_uint64, _u32p]
     lib.svdf_pair_source_create_weighted.restype = P
     lib.svdf_pair_source_create_weighted.argtypes = [P, C.c_long, _u32p, _u32p, _u32p]
     lib.svdf_pair_negatives_weighted.argtypes = [C.c_long, C.c_long, C.c_long, _u32p, _u32p, _u32p, C.c_int, C.c_uint64, _u32p]
@@ -855,12 +879,17 @@ class Trainer:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return PairSource(self, h, n)
 
-    def dataset_from_pair_source(self, src, num_neg=1, seed=0, hard=None):
+    def dataset_from_pair_source(self, src, num_neg=1, seed=0, hard=None, shuffle=None):
         """One pass over the source's rows with num_neg negatives each, drawn on the device from (seed, pair index): the data set
         dataset_from_pairs builds from pair_negatives(...)'s column, without that column crossing PCIe where a route allows.
-        hard=C: every negative is the best-scoring of C drawn candidates on the live model (pair_hard_negatives' column)."""
+        hard=C: every negative is the best-scoring of C drawn candidates on the live model (pair_hard_negatives' column).
+        shuffle=order_seed: the rows in the order pair_order(n, order_seed), permuted on the device -- the pass of a source created from
+        user[sigma], pos_item[sigma]; None: the source's own order."""
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        if hard is None:
+        if shuffle is not None:
+            h = self.lib.svdf_dataset_from_pair_source_shuffled(self.h, src.h, int(num_neg), 0 if hard is None else _shuffled_cand(hard), seed,
+                                                                int(shuffle) & 0xFFFFFFFFFFFFFFFF)
+        elif hard is None:
             h = self.lib.svdf_dataset_from_pair_source(self.h, src.h, int(num_neg), seed)
         else:
             h = self.lib.svdf_dataset_from_pair_source_hard(self.h, src.h, int(num_neg), int(hard), seed)
@@ -868,13 +897,21 @@ class Trainer:
             raise SvdfError(self.lib.svdf_last_error().decode())
         return Dataset(self, h)
 
-    def pair_source_draw(self, src, num_neg, seed, hard=None, return_scores=False):
+    def pair_source_draw(self, src, num_neg, seed, hard=None, return_scores=False, shuffle=None):
         """the negative column the device draws for such a pass: uint32[n * num_neg]; with hard=C the best of C candidates per pair and,
-        with return_scores, (negatives, float32 scores of the chosen candidates)"""
+        with return_scores, (negatives, float32 scores of the chosen candidates).  shuffle=order_seed: the three columns (user, pos, neg) of
+        the shuffled pass and, with return_scores, the scores as a fourth."""
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if hard is None and return_scores:
+            raise SvdfError("pair_source: return_scores needs hard=")
+        if shuffle is not None:
+            size = max(_pass_size(src.num_row, num_neg) if hard is None else _hard_size(src.num_row, num_neg, hard), 1)
+            user, pos, neg, score = np.zeros(size, np.uint32), np.zeros(size, np.uint32), np.zeros(size, np.uint32), np.zeros(size, np.float32)
+            self._ok(self.lib.svdf_pair_source_draw_shuffled(self.h, src.h, int(num_neg), 0 if hard is None else _shuffled_cand(hard), seed,
+                                                             int(shuffle) & 0xFFFFFFFFFFFFFFFF, user, pos, neg, _opt_ptr(score if return_scores else None)))
+            N = src.num_row * int(num_neg)
+            return (user[:N], pos[:N], neg[:N], score[:N]) if return_scores else (user[:N], pos[:N], neg[:N])
         if hard is None:
-            if return_scores:
-                raise SvdfError("pair_source: return_scores needs hard=")
             neg = np.zeros(max(_pass_size(src.num_row, num_neg), 1), np.uint32)
             self._ok(self.lib.svdf_pair_source_draw(self.h, src.h, int(num_neg), seed, neg))
             return neg[:src.num_row * int(num_neg)]

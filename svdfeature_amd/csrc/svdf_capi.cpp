@@ -522,6 +522,26 @@ int svdf_pair_hard_negatives(long num_user, long num_item, long n, const unsigne
         return 0;
     })
 }
+/* ... and the shuffled pass: the rows in the order sigma of an order_seed; num_cand = 0 is the plain pass */
+svdf_dataset *svdf_dataset_from_pair_source_shuffled(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed, uint64_t order_seed) {
+    SVDF_GUARD(nullptr, {
+        svdf::Dataset *d = t->e->dataset_from_pair_source(s ? s->s : nullptr, num_neg, seed, num_cand, &order_seed);
+        t->e->note_dataset(d);
+        svdf_dataset *h = new svdf_dataset();
+        h->d = d;
+        return h;
+    })
+}
+int svdf_pair_source_draw_shuffled(svdf_trainer *t, svdf_pair_source *s, int num_neg, int num_cand, uint64_t seed, uint64_t order_seed, unsigned *user_out,
+                                   unsigned *pos_out, unsigned *neg_out, float *score_out) {
+    SVDF_GUARD(-1, {
+        t->e->pair_source_draw(s ? s->s : nullptr, num_neg, seed, neg_out, num_cand, num_cand > 0 ? score_out : nullptr, &order_seed, user_out, pos_out);
+        return 0;
+    })
+}
+int svdf_pair_order(long n, uint64_t order_seed, unsigned *sigma_out) {
+    SVDF_GUARD(-1, { svdf::pair_order_host(n, order_seed, sigma_out); return 0; })
+}
 /* ... and item-weighted negatives, plain and hard */
 svdf_pair_source *svdf_pair_source_create_weighted(svdf_trainer *t, long n, const unsigned *user, const unsigned *pos_item, const unsigned *item_weight) {
     SVDF_GUARD(nullptr, {

@@ -228,6 +228,7 @@ int64_t Engine::counter(int what) const {
     case 45: return n_pair_src_fallback_;    // passes built from a pair source through dataset_from_pairs on the columns copied back
     case 46: return n_pair_src_hard_;        // of the passes under 44 / 45, the hard ones: the best of num_cand candidates by live score (section 6ad)
     case 47: return n_pair_src_weighted_;    // of the passes under 44 / 45, those drawn from a source with item weights (section 6ae)
+    case 48: return n_pair_src_shuffled_;    // of the passes under 44 / 45, the shuffled ones: rows in the order sigma of an order_seed (section 6af)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

@@ -530,8 +530,11 @@ class Engine {
     PairSource *pair_source_create(long n, const unsigned *user, const unsigned *pos, const unsigned *item_weight = nullptr);
     void pair_weight_lookup(long num_item, const unsigned *item_weight, int form, long nx, const uint64_t *x, unsigned *id_out);   // test probe (svdf_pair_weight_lookup): the map on the device
     // num_cand = 0: the plain pass; >= 1: the hard pass, the best of num_cand candidates by live score
-    Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand = 0);
-    void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand = 0, float *score_out = nullptr);
+    // order: the order_seed of a shuffled pass (section 6af), nullptr for the source's own order; the shuffled draw also returns the pass's
+    // user and item columns [n * num_neg]
+    Dataset *dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand = 0, const uint64_t *order = nullptr);
+    void pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand = 0, float *score_out = nullptr,
+                          const uint64_t *order = nullptr, unsigned *user_out = nullptr, unsigned *pos_out = nullptr);
     void pair_source_forget(PairSource *src);   // (the source is being destroyed)
 
     // multi-GPU item-side delta
@@ -1016,8 +1019,11 @@ class Engine {
     void pair_source_admit(const PairSource *src, int num_neg, int num_cand);
     // the pass's columns [n * num_neg] filled in HBM by the plain rule (num_cand = 0) or the hard one (user / pos may be nullptr; score only
     // with the hard rule); an entry that exhausted its draws fails the call
+    // order (section 6af; nullptr: the source's own order): the rows are taken in the order sigma of this order_seed, and *same_out is the number
+    // of adjacent positions that share their user in the order the pass has (src.same without one)
     void pair_source_launch(const PairSource &src, int num_neg, int num_cand, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg,
-                            float *d_score);
+                            float *d_score, const uint64_t *order = nullptr, long *same_out = nullptr);
+    int64_t n_pair_src_shuffled_ = 0;  // counter 48: of the passes under 44 / 45, the shuffled ones (section 6af)
     int64_t n_kind_[3] = {0, 0, 0};   // launches of k_basicmf / k_general / k_fused
     DeltaRanges delta_ranges();
     friend struct Dataset;

@@ -10,6 +10,7 @@
 #include "svdf_types.h"
 #include "svdf_level_geometry.h"
 #include "svdf_pairweight_lists.h"
+#include "svdf_pairorder_lists.h"
 
 namespace svdf {
 
@@ -430,6 +431,20 @@ struct PairHardDev {
 };
 int pair_hard_form(const DevParams &P, int form, int num_cand);   // the form a hard pass's kernel takes: 1 (a lane per entry, rows where they lie) or 2 (staged)
 void launch_pair_hard(const DevParams &P, const PairHardDev &H, const PairWeightDev &T, int wform, int form, hipStream_t st);   // one launch, a wave owns whole pairs
+
+// ---- the rows of a shuffled pass of a pair source (svdf_k_pairorder.hip): position p holds source row sigma(p)
+// (svdf_pairorder_lists.h).  The two columns written here are the `user` and `pos` of the PairDrawDev of the pass.
+struct PairOrderDev {
+    long n;                    // rows of the source, below 2^31 - 16
+    PairOrderKeys K;           // pair_order_keys(order_seed, n)
+    const unsigned *user;      // [n] the source's rows
+    const unsigned *pos;       // [n]
+    unsigned *out_user;        // [n] user[sigma(p)]
+    unsigned *out_pos;         // [n] pos[sigma(p)]
+    unsigned *flag;            // one word, zeroed by the caller: p + 1 of a position (any of them) that exhausted its walk
+    unsigned *same;            // one word, zeroed by the caller: positions p >= 1 whose user is that of position p - 1
+};
+void launch_pair_order(const PairOrderDev &D, hipStream_t st);   // one launch, a lane per position
 
 }  // namespace svdf
 #endif

@@ -6,7 +6,9 @@
 // the columns back and IS dataset_from_pairs on them, so no result depends on the route.  A HARD pass (section 6ad, svdf_k_pairhard.hip:
 // the best of num_cand candidates by live score) differs in the step that fills the columns and in what it admits, and in nothing else.
 // A WEIGHTED source (section 6ae) also keeps the running sums of its item weights and their guide table (svdf_pairweight_lists.h); both
-// kernels then draw through those tables, and nothing else about a pass changes.
+// kernels then draw through those tables, and nothing else about a pass changes.  A SHUFFLED pass (section 6af) takes an order_seed: one more
+// kernel (svdf_k_pairorder.hip) gathers the rows in the order sigma (svdf_pairorder_lists.h) before the draw, and the route is decided on
+// the permuted order.
 #include <svdfeature_amd.h>
 
 #include <memory>
@@ -71,19 +73,35 @@ PairSource *Engine::pair_source_create(long n, const unsigned *user, const unsig
 
 // The step that fills a pass's columns, and the only one that differs between the plain pass (num_cand = 0: k_pair_draw) and the hard one
 // (section 6ad: k_pair_hard draws num_cand candidates per pair, scores them with the model as every call issued earlier on the trainer's
-// stream leaves it, and keeps the best).
+// stream leaves it, and keeps the best).  With an ORDER (section 6af) k_pair_order runs first: it gathers the source's rows in the order
+// sigma into two scratch columns, which the draw kernels then read in place of the source's -- they are launched as they are without one --,
+// and counts the adjacent positions that share their user into *same_out.  Its flag and count come back with the draw's flag.
 void Engine::pair_source_launch(const PairSource &src, int num_neg, int num_cand, uint64_t seed, unsigned *d_user, unsigned *d_pos, unsigned *d_neg,
-                                float *d_score) {
-    DevBuf<unsigned> flag;
-    pair_src_reserve(flag, 1, "the flag");
-    HIPCHECK(hipMemsetAsync(flag.p, 0, sizeof(unsigned), stream_));
+                                float *d_score, const uint64_t *order, long *same_out) {
+    DevBuf<unsigned> flag, ou, op;   // flag[0] the draw's; with an order flag[1] the walk's and flag[2] the count
+    const size_t words = order ? 3 : 1;
+    pair_src_reserve(flag, words, "the flag");
+    HIPCHECK(hipMemsetAsync(flag.p, 0, words * sizeof(unsigned), stream_));
+    if (order) {
+        pair_src_reserve(ou, (size_t)src.n, "the user column of a shuffled pass");
+        pair_src_reserve(op, (size_t)src.n, "the item column of a shuffled pass");
+        PairOrderDev O;
+        O.n = src.n;
+        O.K = pair_order_keys(*order, src.n);
+        O.user = src.user.p; O.pos = src.pos.p;
+        O.out_user = ou.p; O.out_pos = op.p;
+        O.flag = flag.p + 1; O.same = flag.p + 2;
+        launch_pair_order(O, stream_);
+        HIPCHECK(hipGetLastError());
+        n_launches_++;
+    }
     PairHardDev H;
     PairDrawDev &D = H.D;
     D.npair = src.n * (long)num_neg;
     D.num_neg = num_neg;
     D.seed = seed;
     D.num_item = (unsigned)mp_.num_item;
-    D.user = src.user.p; D.pos = src.pos.p; D.uptr = src.uptr.p; D.uitems = src.uitems.p;
+    D.user = order ? ou.p : src.user.p; D.pos = order ? op.p : src.pos.p; D.uptr = src.uptr.p; D.uitems = src.uitems.p;
     D.out_user = d_user; D.out_pos = d_pos; D.out_neg = d_neg;
     D.flag = flag.p;
     H.num_cand = num_cand; H.out_score = d_score;
@@ -95,10 +113,12 @@ void Engine::pair_source_launch(const PairSource &src, int num_neg, int num_cand
     } else launch_pair_draw(D, T, (int)pair_weight_form_, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_++;
-    unsigned spent = 0;
-    HIPCHECK(hipMemcpyAsync(&spent, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
-    HIPCHECK(hipStreamSynchronize(stream_));
-    if (spent) fail("pair_source: pair " + std::to_string((long)spent - 1) + " found no negative in " + std::to_string(PAIR_SRC_DRAWS) + " draws");
+    unsigned spent[3] = {0, 0, 0};
+    HIPCHECK(hipMemcpyAsync(spent, flag.p, words * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));   // (the scratch columns have been read)
+    if (spent[1]) fail(pair_order_spent(*order, (long)spent[1] - 1));
+    if (spent[0]) fail("pair_source: pair " + std::to_string((long)spent[0] - 1) + " found no negative in " + std::to_string(PAIR_SRC_DRAWS) + " draws");
+    if (same_out) *same_out = order ? (long)spent[2] : src.same;
 }
 
 // what every pass refuses, on the host, before any device work.  A hard pass scores with svdf_rank_topn's kernels' arithmetic on the
@@ -111,22 +131,31 @@ void Engine::pair_source_admit(const PairSource *src, int num_neg, int num_cand)
     rank_live_refusals("pair_source");
 }
 
-void Engine::pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand, float *score_out) {
+void Engine::pair_source_draw(PairSource *src, int num_neg, uint64_t seed, unsigned *neg_out, int num_cand, float *score_out, const uint64_t *order,
+                              unsigned *user_out, unsigned *pos_out) {
     pair_source_admit(src, num_neg, num_cand);
-    check(neg_out != nullptr, "pair_source: bad arguments");
+    check(neg_out != nullptr && (!order || (user_out && pos_out)), "pair_source: bad arguments");
     need_device("pair_source");
     const size_t N = (size_t)src->n * (size_t)num_neg;
-    DevBuf<unsigned> neg;
+    DevBuf<unsigned> neg, cu, cp;
     DevBuf<float> score;
     pair_src_reserve(neg, N, "the negative column of a pass");
     if (score_out) pair_src_reserve(score, N, "the score column of a pass");
-    pair_source_launch(*src, num_neg, num_cand, seed, nullptr, nullptr, neg.p, score_out ? score.p : nullptr);
+    if (order) {   // a caller of the shuffled draw needs the pass's own user and item columns to know which row a negative belongs to
+        pair_src_reserve(cu, N, "the user column of a pass");
+        pair_src_reserve(cp, N, "the positive column of a pass");
+    }
+    pair_source_launch(*src, num_neg, num_cand, seed, cu.p, cp.p, neg.p, score_out ? score.p : nullptr, order);
     HIPCHECK(hipMemcpyAsync(neg_out, neg.p, N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
     if (score_out) HIPCHECK(hipMemcpyAsync(score_out, score.p, N * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (order) {
+        HIPCHECK(hipMemcpyAsync(user_out, cu.p, N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+        HIPCHECK(hipMemcpyAsync(pos_out, cp.p, N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    }
     HIPCHECK(hipStreamSynchronize(stream_));
 }
 
-Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand) {
+Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t seed, int num_cand, const uint64_t *order) {
     pair_source_admit(src, num_neg, num_cand);
     check(trainer_ready_, "dataset: init_trainer has not been called");
     need_device("dataset");
@@ -136,8 +165,9 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     const bool to_windows = single_minibatch() && !user_group() && window_rows_allowed();          // where it takes wseq_from_pairs
     const bool windows_hbm = one_gpu && to_windows && device_window_ready() && wseq_pair_sub_ == 0;
     // the pretest of punit_dataset_from_pairs on the EXPANDED user column: the num_neg pairs of a row are adjacent
-    const bool to_units = punit_config_ok() && N >= 2 && N < 0x7FFFFFF0L && 2 * (src->n * (long)(num_neg - 1) + src->same) >= N;
-    const bool exact_hbm = one_gpu && !to_windows && !auto_step_active() && !to_units && device_sched_ && fused_allowed() && !user_group() && !relaxed();
+    // -- with an order on the PERMUTED rows: the adjacent positions that share their user are counted by k_pair_order, so these two wait for it
+    const bool units_ok = punit_config_ok() && N >= 2 && N < 0x7FFFFFF0L;
+    const bool exact_ok = one_gpu && !to_windows && !auto_step_active() && device_sched_ && fused_allowed() && !user_group() && !relaxed();
     // ---- what dataset_from_pairs refuses about the trainer whatever the columns hold, in its own words, before any device work
     if (wseq_pair_sub_ > 0 && ((multi_ && !in_multi_scope()) || (single_minibatch() && (user_group() || window_rows_allowed())))) wseq_pair_check("dataset_from_pairs");
     if (!(multi_ && !in_multi_scope())) resident_rows_check();   // (a user-group trainer's pairs end in dataset_from_csr)
@@ -145,7 +175,10 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     pair_src_reserve(cu, (size_t)N, "the user column of a pass");
     pair_src_reserve(cp, (size_t)N, "the positive column of a pass");
     pair_src_reserve(cq, (size_t)N, "the negative column of a pass");
-    pair_source_launch(*src, num_neg, num_cand, seed, cu.p, cp.p, cq.p, nullptr);
+    long same = 0;
+    pair_source_launch(*src, num_neg, num_cand, seed, cu.p, cp.p, cq.p, nullptr, order, &same);
+    const bool to_units = units_ok && 2 * (src->n * (long)(num_neg - 1) + same) >= N;
+    const bool exact_hbm = exact_ok && !to_units;
     if (!windows_hbm && !exact_hbm) {   // dataset_from_pairs itself, on the columns copied back
         std::vector<unsigned> hu((size_t)N), hp((size_t)N), hq((size_t)N);
         HIPCHECK(hipMemcpyAsync(hu.data(), cu.p, (size_t)N * sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
@@ -157,6 +190,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
         n_pair_src_fallback_++;
         n_pair_src_hard_ += num_cand > 0;
         n_pair_src_weighted_ += src->weighted;
+        n_pair_src_shuffled_ += order != nullptr;
         return ds;
     }
     if (windows_hbm) {   // section 6v's builder on the pos / neg columns as drawn: item counts, window rule and windows from where they are
@@ -165,6 +199,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
         n_pair_src_hbm_++;
         n_pair_src_hard_ += num_cand > 0;
         n_pair_src_weighted_ += src->weighted;
+        n_pair_src_shuffled_ += order != nullptr;
         return seq;
     }
     // ---- the merged, index-sorted form the level schedule starts from: lower / higher item id and the entries' signs (pos != neg by the rule)
@@ -194,6 +229,7 @@ Dataset *Engine::dataset_from_pair_source(PairSource *src, int num_neg, uint64_t
     n_pair_src_hbm_++;
     n_pair_src_hard_ += num_cand > 0;
     n_pair_src_weighted_ += src->weighted;
+    n_pair_src_shuffled_ += order != nullptr;
     return ds.release();
 }
 
