@@ -410,6 +410,8 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     runs_stage          1      a run writes every row into its next reader's schedule slot instead of W (W is written at the row's last touch of a
  *                                pass and is the truth between passes; same bits).  Costs (1 + R) * runs * (4 k + 8) bytes of device memory, taken
  *                                only when that is at most half of the free memory and at most runs_stage_max_mb (-1 = no cap); 0 = rows live in W
+ *     runs_store          1      cache policy of the staged runs kernel's stores (runs_stage 1 only; same bits): 0 = all plain; 1 = the 4-byte bias
+ *                                words nontemporal, the rows plain; 2 = rows and bias words sc1 write-through.  Read at every pass
  *     runs_order          1      order of the runs inside a level, honoured with sort_batches 1: 1 = by length, longest first, then by item, the level's
  *                                row sets dealt round robin into the eight contiguous shares the XCDs take (a wave walks as many steps as its
  *                                longest run; same bits); 0 = by item.  Read when a data set is BUILT: changing it later does not touch an existing

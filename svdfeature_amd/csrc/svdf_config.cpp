@@ -266,6 +266,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "runs_block")) { check(value == 64 || value == 128 || value == 256, "runs_block must be 64, 128 or 256"); runs_block_ = (int)value; return 0; }
     if (!strcmp(name, "runs_min_rows")) { check(value >= 0, "runs_min_rows must not be negative"); runs_min_rows_ = value; return 0; }
     if (!strcmp(name, "runs_stage")) { check(value == 0 || value == 1, "runs_stage must be 0 or 1"); runs_stage_ = (int)value; return 0; }
+    if (!strcmp(name, "runs_store")) { check(value >= 0 && value <= 2, "runs_store must be 0 (plain), 1 (nontemporal bias words) or 2 (sc1 write-through)"); runs_store_ = (int)value; return 0; }
     if (!strcmp(name, "runs_stage_max_mb")) { check(value >= -1, "runs_stage_max_mb must be -1 (no cap) or a size in MB"); runs_stage_max_mb_ = value; return 0; }
     if (!strcmp(name, "pair_units")) { check(value == 0 || value == 1, "pair_units must be 0 or 1"); pair_units_ = (int)value; return 0; }
     if (!strcmp(name, "pair_unit_cap")) { check(value >= 1 && value <= 4096, "pair_unit_cap must be in 1 .. 4096"); pair_unit_cap_ = (int)value; return 0; }

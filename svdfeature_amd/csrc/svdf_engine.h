@@ -857,7 +857,11 @@ class Engine {
     bool runs_config_ok() const;
     Dataset *runs_dataset_from_triples(long n, const unsigned *user, const unsigned *item, const float *label);
     void runs_train(Dataset *ds);
+#ifdef SVDF_RUNS_STAMPS
+    bool runs_probe_pass(Dataset *ds, const DevParams &P, RunSchedule &S);   // timing build: one stamped pass (svdf_runs.cpp)
+#endif
     int runs_stage_ = 1;                  // knob "runs_stage": 1 = a run's rows are written into their next reader's schedule slot (where the gate allows), 0 = rows live in W
+    int runs_store_ = 1;                  // knob "runs_store": how the staged runs kernel stores: 0 plainly, 1 the bias words nontemporal, 2 rows and bias words sc1 write-through
     long runs_stage_max_mb_ = -1;         // knob "runs_stage_max_mb": cap on a data set's staging buffers (-1: half of the free device memory is the only limit)
     void runs_stage_build(Dataset *ds);
     bool runs_staged(const Dataset *ds) const { return runs_stage_ != 0 && ds->rn_stage_state == 1 && ds->rn_stage_row0 == user_off_; }

@@ -287,8 +287,40 @@ void launch_runs_stage_in(const DevParams &P, const unsigned *first, long nrow, 
 // first -- and written to the slots of their next readers (S.dst), home to W / P.bias at a row's last touch of the pass.  The steps are the same lines.
 __device__ __forceinline__ unsigned load_u32_nt(const unsigned *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ float load_f32_nt(const float *p) { return __builtin_nontemporal_load(p); }
-template <int LANES, int V, int R, int G, bool STAGED>
+// Store policy of the STAGED form (knob "runs_store", profiles/r39_runs_store.md).  A staged launch writes every row to a line nobody has read -- its next
+// reader's slot -- and a plain store leaves that line dirty in the XCD's L2 until the kernel ends: up to an L2's worth of write-back that nothing overlaps.
+// SP is the knob's value.  The rows (whole 128-byte lines) and the 4-byte bias words do not want the same policy, and the knob names the best measured
+// combination of each kind: 0 = all plain; 1 = the bias words nontemporal, the rows plain (nontemporal rows are slower than plain ones with every kind
+// of bias store); 2 = rows and bias words sc1 write-through (sc1 rows with plain or nontemporal bias words lose to 0).  A row's store is one instruction
+// whether it goes to a slot or home to W (the target is chosen per lane): a policy of their own for the home rows costs a divergent branch and lost.
+// (a row of the STAGED form: L < K / 4 always, K = 4 * LANES * V, so no lane is masked)
+template <int SP>
+__device__ __forceinline__ void runs_store_row(float *W, size_t row, int pitch, int L, const float4 v) {
+    float *ptr = W + row * (size_t)pitch + (size_t)L * 4;
+    if constexpr (SP != 2) {
+        *reinterpret_cast<float4 *>(ptr) = v;
+    } else {
+        // (the s_nop 1: on gfx950 a store of more than 64 bits needs two wait states before a VALU instruction overwrites its data registers.  The compiler
+        // keeps that distance behind its own stores but does not look inside an asm statement, and it does place such a write right behind this one.)
+        svdf_f4 x = {v.x, v.y, v.z, v.w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(x) : "memory");
+    }
+}
+template <int SP>
+__device__ __forceinline__ void runs_store_bias(float *ptr, float x) {
+    if constexpr (SP == 0) *ptr = x;
+    else if constexpr (SP == 1) __builtin_nontemporal_store(x, ptr);
+    else asm volatile("global_store_dword %0, %1, off sc1" ::"v"(ptr), "v"(x) : "memory");
+}
+#ifdef SVDF_RUNS_STAMPS   // timing build only (never set by the Makefile): wall_clock64() stamps of lane 0 of every wave, 8 per wave, ordinary vector stores
+#define RUNS_STAMP(i_) do { if (S.stamps && lane == 0) S.stamps[((size_t)S.stamp_wave0 + (size_t)wave) * 8 + (i_)] = wall_clock64(); } while (0)
+#else
+#define RUNS_STAMP(i_) do { } while (0)
+#endif
+// SP: the store policy, the value of the knob "runs_store" (STAGED only)
+template <int LANES, int V, int R, int G, bool STAGED, int SP = 0>
 __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, const RunSchedule S, long begin, long end) {
+    static_assert(STAGED || SP == 0, "the form on rows in W stores plainly");
     constexpr int T = 16 / LANES;
     constexpr int IPS = 64 / LANES;    // runs per wave and row set
     constexpr int K = 4 * LANES * V;
@@ -300,6 +332,7 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
     const int gslot = (lane >> 4) * T + (lane & (T - 1));
     const int pitch = P.pitch;
     const float dec_u1 = snap_to_one(1.0f - P.lr * P.wd_user), dec_i1 = snap_to_one(1.0f - P.lr * P.wd_item);
+    RUNS_STAMP(0);
 #pragma unroll 1
     for (int g = 0; g < G; g++) {
         const long w0 = begin + (wave * G + g) * IPS;
@@ -353,11 +386,18 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
 #pragma unroll
             for (int v = 0; v < V; v++) q[v] = live ? load_row_nt<K / 4>(S.stage_row, at0, pitch, m + v * LANES, K) : f4zero();
             const int g0 = (int)(sc - w0);
+#ifdef SVDF_RUNS_STAMPS
+            asm volatile("" :: "v"(q[0].x), "v"(q[V - 1].x), "v"(dw), "v"(lw), "v"(bw));
+            RUNS_STAMP(1);
+#endif
             ir = __shfl(dw, g0 * NS);
 #pragma unroll
             for (int j = 0; j < R; j++) ur[j] = __shfl(dw, g0 * NS + 1 + j);
-            // Row by row, the shape of the loads from W above: one operand per round trip, every operand under `if (j < n)`.  The addresses need no id, so
-            // the whole read could leave with the dst words -- built and measured: 19.8 against 16.9 ms per pass (W) and 16.2 (this form), profiles/r26_runs_stage.md.
+            // One operand per `if (j < n)`, the shape of the loads from W above, but two rows in flight: row j - 1 is waited for after row j has left
+            // (14.57 against 14.82 ms per pass with one row in flight, profiles/r37_runs_pack.md section 3; again in profiles/r39_runs_store.md).  The
+            // addresses need no id, so the whole read could leave with the dst words -- built and measured: 19.8 against 16.9 ms per pass (W) and 16.2
+            // (one row in flight), profiles/r26_runs_stage.md; all user rows at once behind the item row: 15.4 (r37).  The waits are the compiler's,
+            // placed in front of an empty statement that reads the row's registers: without one it sends all rows at once.
 #pragma unroll
             for (int j = 0; j < R; j++)
                 if (live && ur[j] != (unsigned)SLOT_ABSENT) n = j + 1;
@@ -368,9 +408,7 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 if (j < n) {
 #pragma unroll
                     for (int v = 0; v < V; v++) p[j][v] = load_row_nt<K / 4>(S.stage_row, (size_t)(1 + j) * nun + at0, pitch, m + v * LANES, K);
-                    // Row j is here before row j + 1 leaves.  The per-row bias loads used to make the compiler wait like this; without them it would send
-                    // all rows at once: 15.4 against 14.8 ms per pass (profiles/r37_runs_pack.md, section 3).
-                    asm volatile("" :: "v"(p[j][0].x), "v"(p[j][V - 1].x));
+                    if (j > 0) { asm volatile("" :: "v"(p[j - 1][0].x), "v"(p[j - 1][V - 1].x)); if (j < 4) RUNS_STAMP(1 + j); }
                 }
             }
             // (the bias and label blocks left before the rows and are here before them: these moves add no memory wait)
@@ -390,6 +428,7 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
         // pass, profiles/r13_runs_gather.md -- the row-by-row gather stays.)
 #pragma unroll
         for (int j = 0; j < R; j++) asm volatile("" :: "v"(p[j][0].x), "v"(p[j][V - 1].x), "v"(bu[j]));
+        RUNS_STAMP(5);
 #pragma unroll
         for (int j = 0; j < R; j++) {
             if (!__any(j < n)) break;   // the wave walks as many steps as its longest run (dot_slots is a wave-wide operation)
@@ -427,12 +466,14 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 wu.x = wu.x * dec_u1; wu.y = wu.y * dec_u1; wu.z = wu.z * dec_u1; wu.w = wu.w * dec_u1;
                 wi.x = wi.x * dec_i1; wi.y = wi.y * dec_i1; wi.z = wi.z * dec_i1; wi.w = wi.w * dec_i1;
                 if (act) {
-                    store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, wu);
+                    if constexpr (STAGED) runs_store_row<SP>(wb, wrow, pitch, m + v * LANES, wu);
+                    else store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, wu);
                     q[v] = wi;
                 }
             }
             if (act) {
-                bb[wr] = nbu;
+                if constexpr (STAGED) runs_store_bias<SP>(bb + wr, nbu);
+                else bb[wr] = nbu;
                 bi = nbi;
             }
         }
@@ -446,11 +487,17 @@ __global__ __launch_bounds__(256) void k_basicmf_runs_soa(const DevParams P, con
                 wrow = home ? wr : runs_row_of((unsigned)wr, 1 + R, (size_t)S.nunit);
             }
 #pragma unroll
-            for (int v = 0; v < V; v++) store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, q[v]);
-            bb[wr] = bi;
+            for (int v = 0; v < V; v++) {
+                if constexpr (STAGED) runs_store_row<SP>(wb, wrow, pitch, m + v * LANES, q[v]);
+                else store_row<K / 4>(wb, wrow, pitch, m + v * LANES, K, q[v]);
+            }
+            if constexpr (STAGED) runs_store_bias<SP>(bb + wr, bi);
+            else bb[wr] = bi;
         }
+        RUNS_STAMP(6);
     }
 }
+#undef RUNS_STAMP
 bool basicmf_runs_soa_applies(const DevParams &P) {
     return P.basic_i8 && P.active_type == ACT_LINEAR && P.reg_method == 0 && P.no_user_bias == 0 && P.user_nonnegative == 0 && P.u_rng.n == 0 && P.i_rng.n == 0 &&
            P.store_mode == 0 && (P.k == 64 || P.k == 128);
@@ -464,16 +511,20 @@ void launch_basicmf_runs_soa(const DevParams &P, const RunSchedule &S, long begi
     const long per_block = (long)(block_threads / 64) * G * per_wave;
     int grid = (int)((end - begin + per_block - 1) / per_block);
     if (P.xcd_remap) grid = (grid + 7) & ~7;
+#define RUNS_STAGED(L_, R_, G_, SP_) hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, true, SP_>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end)
 #define RUNS_LAUNCH(L_, R_, G_)                                                                                                                          \
     do {                                                                                                                                                \
-        if (S.dst) hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, true>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);              \
-        else hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);                   \
+        if (!S.dst) hipLaunchKernelGGL((k_basicmf_runs_soa<L_, 2, R_, G_, false>), dim3(grid), dim3(block_threads), 0, st, P, S, begin, end);            \
+        else if (S.store == 1) RUNS_STAGED(L_, R_, G_, 1);                                                                                              \
+        else if (S.store == 2) RUNS_STAGED(L_, R_, G_, 2);                                                                                              \
+        else RUNS_STAGED(L_, R_, G_, 0);                                                                                                                \
     } while (0)
 #define RUNS_BY_R(L_)                                                                                                          \
     if (R == 2) { if (G >= 2) RUNS_LAUNCH(L_, 2, 2); else RUNS_LAUNCH(L_, 2, 1); }      /* R = user / label columns of the schedule: 2, 4 or 7 */ \
     else if (R == 4) { if (G >= 2) RUNS_LAUNCH(L_, 4, 2); else RUNS_LAUNCH(L_, 4, 1); }                                       \
     else { if (G >= 2) RUNS_LAUNCH(L_, 7, 2); else RUNS_LAUNCH(L_, 7, 1); }
     if (P.k == 128) { RUNS_BY_R(16) } else { RUNS_BY_R(8) }
+#undef RUNS_STAGED
 #undef RUNS_BY_R
 #undef RUNS_LAUNCH
 }

@@ -3,6 +3,10 @@
 // Nothing of SVDFeature::update_inner (apex_svd_base.h:456-462) changes: same instances, every row's touches in file order, the item's row
 // kept in registers across a run instead of being written and read back between two of its ratings.
 #include <algorithm>
+#include <array>
+#include <vector>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -212,6 +216,96 @@ void Engine::runs_stage_build(Dataset *ds) {
     ds->rn_stage_bytes = bytes;
 }
 
+#ifdef SVDF_RUNS_STAMPS
+// Timing build only (the Makefile never sets SVDF_RUNS_STAMPS; profiles/r39_runs_store.md, part 0).  With SVDF_RUNS_STAMPS=<pass number, from 1> in the environment that
+// staged pass of the engine runs with clock stamps: lane 0 of every wave writes wall_clock64() at 0 entry, 1 slot words + item row here, 2 .. 4 user rows
+// 0 .. 2 here (where the gather waits for them one by one), 5 every row here, 6 last store issued.  Reduced per launch over the waves that had work and
+// printed; SVDF_RUNS_STAMPS_OUT=<file> also gets one line per launch.  -> true: the pass's launches are done
+bool Engine::runs_probe_pass(Dataset *ds, const DevParams &P, RunSchedule &S) {
+    const char *e = getenv("SVDF_RUNS_STAMPS");
+    if (!e || !S.dst || n_runs_passes_ + 1 != (int64_t)atol(e)) return false;
+    const Schedule &sc = ds->sched;
+    const size_t nlev = sc.num_levels();
+    const int G = runs_sets_ >= 2 ? 2 : 1, wpb = runs_block_ / 64, per_wave = P.k == 128 ? 4 : 8;
+    std::vector<long> w0(nlev + 1, 0);
+    for (size_t l = 0; l < nlev; l++) {
+        const long per_block = (long)wpb * G * per_wave;
+        long grid = (sc.level_ptr[l + 1] - sc.level_ptr[l] + per_block - 1) / per_block;
+        if (P.xcd_remap) grid = (grid + 7) & ~7L;
+        w0[l + 1] = w0[l] + grid * wpb;
+    }
+    DevBuf<unsigned long long> buf;
+    buf.reserve((size_t)w0[nlev] * 8);
+    HIPCHECK(hipMemsetAsync(buf.p, 0, (size_t)w0[nlev] * 64, stream_));
+    S.stamps = buf.p;
+    for (size_t l = 0; l < nlev; l++) {
+        S.stamp_wave0 = w0[l];
+        launch_basicmf_runs_soa(P, S, sc.level_ptr[l], sc.level_ptr[l + 1], ds->rn_len, runs_sets_, runs_block_, stream_);
+    }
+    HIPCHECK(hipGetLastError());
+    std::vector<unsigned long long> h((size_t)w0[nlev] * 8);
+    HIPCHECK(hipMemcpyAsync(h.data(), buf.p, h.size() * 8, hipMemcpyDeviceToHost, stream_));
+    HIPCHECK(hipStreamSynchronize(stream_));
+    S.stamps = nullptr;
+    int dev = 0, khz = 100000;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
+    const double us = 1000.0 / (double)khz;
+    FILE *out = getenv("SVDF_RUNS_STAMPS_OUT") ? fopen(getenv("SVDF_RUNS_STAMPS_OUT"), "w") : nullptr;
+    if (out) fprintf(out, "launch,waves,ramp_us,span_us,gap_after_us,head_us,gather_us,steps_us,row0_us,row1_us,row2_us,rest_us\n");
+    enum { NC = 10 };
+    std::vector<double> col[NC];   // over the launches of at least 4000 live waves
+    unsigned long long prev_last = 0;
+    std::vector<double> rowv[NC];
+    std::vector<std::array<double, NC>> rows(nlev);
+    for (size_t l = 0; l < nlev; l++) {
+        unsigned long long emin = ~0ull, emax = 0, smax = 0;
+        double sum[7] = {0, 0, 0, 0, 0, 0, 0};
+        long cnt[7] = {0, 0, 0, 0, 0, 0, 0}, live = 0;
+        for (long w = w0[l]; w < w0[l + 1]; w++) {
+            const unsigned long long *t = &h[(size_t)w * 8];
+            if (!t[6]) continue;
+            live++;
+            emin = std::min(emin, t[0]); emax = std::max(emax, t[0]); smax = std::max(smax, t[6]);
+            sum[0] += (double)(t[1] - t[0]); sum[1] += (double)(t[5] - t[1]); sum[2] += (double)(t[6] - t[5]);
+            unsigned long long at = t[1];
+            for (int r = 0; r < 3; r++)
+                if (t[2 + r]) { sum[3 + r] += (double)(t[2 + r] - at); cnt[3 + r]++; at = t[2 + r]; }
+            sum[6] += (double)(t[5] - at);
+        }
+        std::array<double, NC> v{};
+        if (live) {
+            v[0] = (double)(emax - emin) * us; v[1] = (double)(smax - emin) * us;
+            for (int c = 0; c < 3; c++) v[3 + c] = sum[c] / (double)live * us;
+            for (int r = 0; r < 3; r++) v[6 + r] = cnt[3 + r] ? sum[3 + r] / (double)cnt[3 + r] * us : 0.0;
+            v[9] = sum[6] / (double)live * us;
+            if (l > 0 && prev_last) rows[l - 1][2] = ((double)emin - (double)prev_last) * us;   // the gap BEHIND the previous launch
+        }
+        rows[l] = v;
+        rows[l][2] = 0.0;
+        prev_last = live ? smax : 0;
+        rowv[0].push_back((double)live);
+    }
+    for (size_t l = 0; l < nlev; l++) {
+        if (out) { fprintf(out, "%zu,%.0f", l, rowv[0][l]); for (int c = 0; c < NC; c++) fprintf(out, ",%.3f", rows[l][c]); fprintf(out, "\n"); }
+        if (rowv[0][l] >= 4000.0 && l + 1 < nlev)
+            for (int c = 0; c < NC; c++) col[c].push_back(rows[l][c]);
+    }
+    if (out) fclose(out);
+    static const char *names[NC] = {"entry ramp (first to last wave's entry)", "span (first entry to last store issued)", "gap to the next launch's first entry", "head: slot words + item row", "gather of the user rows", "steps and stores", "user row 0", "user row 1", "user row 2", "the rest of the gather"};
+    fprintf(stderr, "[svdfeature_amd] runs stamps, pass %s, runs_store %d: %zu launches, %zu of them with >= 4000 live waves; over those, microseconds (mean / median):\n", e, runs_store_, nlev, col[0].size());
+    for (int c = 0; c < NC; c++) {
+        std::vector<double> &x = col[c];
+        if (x.empty()) continue;
+        double m = 0.0;
+        for (double y : x) m += y;
+        std::sort(x.begin(), x.end());
+        fprintf(stderr, "[svdfeature_amd]   %-44s %8.3f / %8.3f\n", names[c], m / (double)x.size(), x[x.size() / 2]);
+    }
+    return true;
+}
+#endif
+
 void Engine::runs_train(Dataset *ds) {
     const DevParams &P = params();
     RunSchedule S;
@@ -223,9 +317,13 @@ void Engine::runs_train(Dataset *ds) {
     if (runs_staged(ds)) {
         // W is the truth between passes: every touched row goes to the slot of its first touch, the levels hand it on from slot to slot, its last touch writes it home
         S.dst = ds->rn_dst.p; S.stage_row = ds->rn_stage_row.p; S.stage_bias = ds->rn_stage_bias.p; S.label_rm = ds->rn_label_rm.p; S.nunit = ds->num_units;
+        S.store = runs_store_;
         launch_runs_stage_in(P, ds->rn_first.p, (long)mp_.num_user + (long)mp_.num_item, user_off_, S.stage_row, S.stage_bias, 1 + ds->rn_len, ds->num_units, stream_);
         n_launches_++;
     }
+#ifdef SVDF_RUNS_STAMPS
+    if (!runs_probe_pass(ds, P, S))
+#endif
     for (size_t l = 0; l < sc.num_levels(); l++) launch_basicmf_runs_soa(P, S, sc.level_ptr[l], sc.level_ptr[l + 1], ds->rn_len, runs_sets_, runs_block_, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_ += (int64_t)sc.num_levels();

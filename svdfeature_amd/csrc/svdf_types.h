@@ -131,6 +131,11 @@ struct RunSchedule {
     float *stage_bias;
     const float *label_rm;
     long nunit;
+    int store;   // knob "runs_store": the store policy of the staged form (0 plain, 1 bias words nontemporal, 2 rows and bias words sc1 write-through)
+#ifdef SVDF_RUNS_STAMPS   // timing build (svdf_k_runs.hip: RUNS_STAMP): 8 clock stamps per wave, the launch's first wave at stamp_wave0
+    unsigned long long *stamps;
+    long stamp_wave0;
+#endif
 };
 enum : unsigned { RUNS_HOME = 0x80000000u };
 
