@@ -371,7 +371,8 @@ int svdf_synchronize(svdf_trainer *t);
  * svdf_dataset_from_pairs' own builder on the columns copied back,
  * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard),
  * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted),
- * 48 of the passes under 44 / 45, the shuffled ones (svdf_dataset_from_pair_source_shuffled) */
+ * 48 of the passes under 44 / 45, the shuffled ones (svdf_dataset_from_pair_source_shuffled),
+ * 49 sections listed by svdf_item_topn */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -1040,6 +1041,65 @@ int svdf_pair_source_draw_shuffled(svdf_trainer *t, svdf_pair_source *s, int num
                                    unsigned *user_out /* [n*num_neg] */, unsigned *pos_out /* [n*num_neg] */, unsigned *neg_out /* [n*num_neg] */,
                                    float *score_out /* [n*num_neg] or NULL: the chosen score of a hard pass */);
 int svdf_pair_order(long n, uint64_t order_seed, unsigned *sigma_out /* [n] */);   /* host only: no GPU, no handle */
+
+/* ---- SIMILAR-ITEM lists on the live model: dot and cosine top-N per item.  The calls above answer "which items
+ * for this user?"; this one answers "which items are most like this one?" -- related-item shelves, shortlist expansion, a check that the
+ * factors mean something -- on the trainer's own model, without an item x item matrix and in the engine's pinned float32 order.
+ * Section s of num_section is the QUERY ITEM item[s].  The candidates are all item ids 0 .. num_item - 1; a candidate is RANKED unless it is
+ * item[s] itself or is in the section's ban list ban_item[ban_ptr[s] .. ban_ptr[s + 1]) (ban_ptr == NULL: no section has bans).  The query
+ * is always excluded; listing it among its own bans is legal; duplicate ban ids count once.
+ * THE SCORE of candidate i for query q, by `metric`:
+ *   SVDF_ITEM_DOT     0 + (0 + <W_item[q], W_item[i]>), the dot in the pinned order of svdf_rank_topn's score: four serial chains over the
+ *                     4-float chunks, each started as 0 + product, then (a0 + a2) + (a1 + a3), then the up to three tail products added in
+ *                     index order; every multiply and add rounded separately (no fma).  i_bias is not part of it.
+ *   SVDF_ITEM_COSINE  the same expression on the UNIT ROWS R in place of W_item, on both sides: 0 + (0 + <R[q], R[i]>).  For every item i
+ *                       ss      = <W_item[i], W_item[i]>   in that same pinned order
+ *                       n       = sqrt(ss)                 correctly rounded
+ *                       R[i][j] = W_item[i][j] / n         correctly rounded, a DIVISION per element -- not a multiply by a reciprocal,
+ *                                                          not rsqrt; denormals are kept, in ss, n and R
+ *                     ss == 0 (a zero row, or squares that all underflow) gives R[i] = +0 in every element: such an item scores 0 against
+ *                     everything and flags nothing.  Every other input takes the IEEE result of those operations: an overflowing ss gives
+ *                     n = inf and elements +-0, or NaN where the element itself is +-inf; a NaN in a row makes its whole unit row NaN, its
+ *                     scores NaN, and flags the sections that rank it.  A unit row's self-score is within a few ulp of 1, not 1.
+ * OUTPUTS, ORDER AND FLAGS are svdf_rank_topn's word for word: higher score first, equal scores by ASCENDING ITEM ID, +0 == -0;
+ *   count_out[s] = min(top_n, num_item - distinct(bans + {item[s]})); item_out / score_out [s * top_n + r] the id and score at rank r, -1 /
+ *   0.0f beyond the count; nan_out[s] = 1 empties the list when a ranked candidate scores NaN (a banned NaN row does not flag); score_out
+ *   may be NULL; 1 <= top_n <= 256.  Both scores are symmetric in (q, i) bit for bit: the products commute and the order of the sums does
+ *   not depend on the side.
+ * PINNED VECTORS of the unit rows, bit patterns of the float32 inputs and outputs (tests/test_item_topn.py holds them against the numpy
+ * statement of the rule and against svdf_item_unit_rows):
+ *   k = 3:  in 3f800000 40000000 c0000000  out 3eaaaaab 3f2aaaab bf2aaaab
+ *   k = 5:  in 3dcccccd be4ccccd 3e99999a 3ecccccd bf000000  out 3e0a137d be8a137d 3ecf1d3c 3f0a137d bf2c985c
+ *   k = 9:  in 3a83126f 40400000 c0e00000 3f000000 1e3ce508 40200000 be000000 41100000 3e99999a  out 38adcbe3 3e7e95a9 bf1481f8 3d29b91b 1c7a7790 3e542762 bc29b91b 3f3ef03f 3ccbaaee
+ *   k = 2:  in 000116c2 80022d85  out 00000000 00000000
+ *   k = 3:  in 1a111234 9a911234 1ad99b4d  out 3e81c16b bf01c16b 3f42a220
+ *   k = 3:  in 7f61b1e6 bf800000 5f8ac723  out 00000000 80000000 00000000
+ * (1, 2, -2; 0.1 .. -0.5; nine mixed magnitudes; two denormals whose squares underflow: the +0 row; three values whose squares are
+ * denormal; 3e38, -1, 2e19, whose sum of squares overflows: +-0 elements)
+ * REFUSED on the host, before any device work and before "needs a GPU", each behind "item_topn: ":
+ *   metric other than 0 / 1                   "item_topn: metric must be 0 (SVDF_ITEM_DOT) or 1 (SVDF_ITEM_COSINE)"
+ *   top_n outside 1 .. 256                    "item_topn: top_n must be between 1 and 256"
+ *   an id >= num_item in item or ban_item     "sample item index exceed bound" (the ranker's message, as svdf_rank_topn gives it)
+ *   ban_ptr not ascending                     "item_topn: ban_ptr must not decrease" ("... must start at >= 0", "ban_item is missing")
+ *   NULL outputs with num_section > 0         "item_topn: bad arguments"
+ *   a feature_item side table                 "item_topn: a feature_item side table changes an item's effective row ... and is not covered"
+ *                                             (a feature_user table does not touch an item row and is admitted)
+ *   extend_type 2 / 15, common_latent_space != 0, amd:gpus > 1, a rank handle, a model that is not initialised: svdf_rank_topn_fb's words
+ *   behind the new prefix.  format_type = 1 (user-group, SVD++) trainers with extend_type 0 / 1 are ADMITTED: W_item is the same table
+ *   there and no feedback list is involved.
+ * num_section == 0 returns 0 and launches nothing.  An item may be queried in several sections.  The call runs on the trainer's stream
+ * behind whatever is queued and returns when the results are on the host.  The selecting sweeps are svdf_rank_topn's, untouched: they read
+ * the sections' query rows (gathered by k_item_query_rows, one launch per piece) in place of W_user rows, for cosine the unit rows (built by
+ * k_item_unit_rows, ONE launch per call, never kept across calls -- the model may have moved) in place of W_item, and a zero vector in
+ * place of i_bias.  `rank_topn_budget` bounds the list workspace exactly as for svdf_rank_topn; the result does not depend on it.  Counter 49
+ * counts the sections listed; counter 39 does not move.
+ * svdf_item_unit_rows is the unit-row rule on the host over dense rows[num_row][num_factor] -- no GPU, no handle.
+ * MEASURED: profiles/r40_item_topn.md. */
+#define SVDF_ITEM_DOT 0
+#define SVDF_ITEM_COSINE 1
+int svdf_item_topn(svdf_trainer *t, long num_section, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
+                   int *item_out, float *score_out, int *count_out, int *nan_out);
+int svdf_item_unit_rows(long num_row, int num_factor, const float *rows, float *out);   /* host function: no GPU, no handle */
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

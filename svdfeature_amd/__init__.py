@@ -257,6 +257,23 @@ def pair_hard_negatives(num_user, num_item, user, pos_item, num_neg, num_cand, s
     return (neg[:N], score[:N]) if return_scores else neg[:N]
 
 
+def item_unit_rows(W):
+    """svdf_item_unit_rows: the unit rows of the cosine metric of Trainer.similar_items (include/svdfeature_amd.h) for the
+    rows W [n, k] -- W[i] / sqrt(<W[i], W[i]>) element by element, the sum of squares in the pinned float32 order, +0 rows where it is 0.
+    A host function: no GPU, no handle."""
+    lib = load_library()
+    W = np.ascontiguousarray(W, np.float32)
+    if W.ndim != 2 or W.shape[1] < 1:
+        raise SvdfError("item_unit_rows: W must be [n, k] with k >= 1")
+    out = np.zeros(max(W.size, 1), np.float32)
+    if lib.svdf_item_unit_rows(W.shape[0], W.shape[1], _pad(W, np.float32), out) != 0:
+        raise SvdfError(lib.svdf_last_error().decode())
+    return out[:W.size].reshape(W.shape)
+
+
+ITEM_METRICS = {"dot": 0, "cosine": 1}
+
+
 def _sampled_lists(S, pos_ptr, pos_item, ban_ptr, ban_item):
     """the positives and bans of S sections as the arrays the sampled calls take (ban_ptr = None: two None); the library reads as many ids
     as the pointers say, so arrays shorter than that are refused here"""
@@ -395,6 +412,8 @@ def load_library():
     lib.svdf_rank_eval_metrics.argtypes = [C.c_long, _i64p, _i32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_eval.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
     lib.svdf_rank_topn.argtypes = [P, C.c_long, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    lib.svdf_item_topn.argtypes = [P, C.c_long, _u32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
+    lib.svdf_item_unit_rows.argtypes = [C.c_long, C.c_int, _f32p, _f32p]
     _fb = [C.c_void_p, C.c_void_p, C.c_void_p]   # fb_ptr, fb_index, fb_value behind `user`
     lib.svdf_rank_eval_positions_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
@@ -1186,6 +1205,34 @@ class Trainer:
             self._ok(self.lib.svdf_rank_topn_fb(self.h, S, _pad(users, np.uint32), fb[0], fb[1], fb[2], _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n,
                                                 items.reshape(-1), scores.ctypes.data_as(C.c_void_p), count, nan))
         return items[:S], scores[:S], count[:S], nan[:S]
+
+    def similar_items(self, items, top_n, metric="cosine", ban_ptr=None, ban_item=None):
+        """svdf_item_topn: per query item the top_n items most like it on the live model, by the dot product or the cosine of
+        the W_item rows in the pinned float32 order; the query itself and the section's banned items are excluded.  items = None: every item
+        in id order.  metric: "dot", "cosine" or the integers 0 / 1.  Returns (items [S, top_n] int32, -1 beyond count; scores [S, top_n]
+        float32; count [S]; nan [S]) as rank_topn does."""
+        if items is None:
+            shape = (C.c_int(), C.c_int())
+            self._ok(self.lib.svdf_view_shape(self.h, VIEW["W_item"], C.byref(shape[0]), C.byref(shape[1])))
+            items = np.arange(max(shape[0].value, 0), dtype=np.uint32)
+        items, top_n = np.ascontiguousarray(items, np.uint32).reshape(-1), int(top_n)
+        if isinstance(metric, str):
+            if metric not in ITEM_METRICS:
+                raise SvdfError("item_topn: metric must be \"dot\", \"cosine\", 0 or 1")
+            metric = ITEM_METRICS[metric]
+        S = len(items)
+        if ban_ptr is not None:
+            ban_ptr, ban_item = _pad(ban_ptr, np.int64), _pad(ban_item if ban_item is not None else [], np.uint32)
+            if len(ban_ptr) != S + 1:
+                raise SvdfError("item_topn: ban_ptr must have one entry more than items")
+        else:
+            ban_item = None
+        n = max(top_n, 1)
+        out, scores = np.full((max(S, 1), n), -1, np.int32), np.zeros((max(S, 1), n), np.float32)
+        count, nan = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32)
+        self._ok(self.lib.svdf_item_topn(self.h, S, _pad(items, np.uint32), int(metric), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, out.reshape(-1),
+                                         scores.ctypes.data_as(C.c_void_p), count, nan))
+        return out[:S], scores[:S], count[:S], nan[:S]
 
     # -- multi-GPU item-side delta
     def item_delta_begin(self):

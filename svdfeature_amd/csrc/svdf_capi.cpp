@@ -9,6 +9,7 @@
 
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
+#include "svdf_itemtopn_lists.h"
 #include "svdf_ranklines_lists.h"
 #include "svdf_pairhard_lists.h"
 #include "svdf_ranknegs_lists.h"
@@ -352,6 +353,14 @@ int svdf_rank_eval_fb(svdf_trainer *t, long num_section, const unsigned *user, c
         svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
         return 0;
     })
+}
+/* similar-item lists on the live model */
+int svdf_item_topn(svdf_trainer *t, long num_section, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
+                   int *item_out, float *score_out, int *count_out, int *nan_out) {
+    SVDF_GUARD(-1, { t->e->item_topn(num_section, item, metric, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out); return 0; })
+}
+int svdf_item_unit_rows(long num_row, int num_factor, const float *rows, float *out) {
+    SVDF_GUARD(-1, { svdf::item_unit_rows(num_row, num_factor, rows, out); return 0; })
 }
 int svdf_rank_topn_fb(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                       const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {

@@ -229,6 +229,7 @@ int64_t Engine::counter(int what) const {
     case 46: return n_pair_src_hard_;        // of the passes under 44 / 45, the hard ones: the best of num_cand candidates by live score (section 6ad)
     case 47: return n_pair_src_weighted_;    // of the passes under 44 / 45, those drawn from a source with item weights (section 6ae)
     case 48: return n_pair_src_shuffled_;    // of the passes under 44 / 45, the shuffled ones: rows in the order sigma of an order_seed (section 6af)
+    case 49: return n_item_topn_sections_;   // sections listed by svdf_item_topn (section 6ag)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

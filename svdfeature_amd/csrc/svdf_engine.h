@@ -405,6 +405,7 @@ struct PairSource {
 };
 
 struct RankLines;   // the USER lines of the svdf_rank_*_lines calls (svdf_ranklines_lists.h)
+struct RankTopnLists;   // the validated ban lists of the top-N calls (svdf_ranktopn_lists.h)
 class Engine {
   public:
     Engine(TypeParam mtype, int device);
@@ -514,6 +515,13 @@ class Engine {
     void level_config(DevParams &P, int pitch) const;   // the DevParams fields the launch choice of the level kernels reads
     void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                        const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
+    // the body of the top-N calls behind their validated lists (pieces, workspace, launches, copy-back); query_base: an item call
+    void rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
+                          const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
+                          int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+    // similar-item lists on the live model: dot and cosine top-N per query item (svdf_itemtopn.cpp, svdf_k_itemrows.hip)
+    void item_topn(long S, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
+                   float *score_out, int *count_out, int *nan_out);
     // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md
     // section 6aa).  Exactly one of user / U.ptr is set; top_n == 0: positions (pos_*, position_out, tied_out, ranked_out), else the top_n lists
     void rank_cand(const char *who, long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
@@ -1006,6 +1014,7 @@ class Engine {
     DevBuf<float> rk_rows_;            // a piece's effective user rows, [nsec][pitch]
     int64_t n_rank_line_sections_ = 0; // counter 41: sections the _lines calls ranked with a row built from a USER line
     DevBuf<float> rk_items_;           // a _lines call's prepared item side: [num_item][pitch] rows, then [num_item] biases
+    int64_t n_item_topn_sections_ = 0; // counter 49: sections listed by svdf_item_topn (its unit rows and zero biases live in rk_items_)
     int64_t n_rank_cand_sections_ = 0; // counter 42: sections the _cand calls ranked over a candidate list
     long rank_cand_form_ = 0;          // knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 the staged score kernel
     DevBuf<int> ca_in_, ca_out_;       // a _cand piece's upload (the lists, the tile table) and its results

@@ -352,6 +352,12 @@ void launch_rank_live_rows(const DevParams &P, const RankLiveRowsDev &D, hipStre
 // the prepared item side of a trainer with a feature_item table: item_rows[i] = W_item[i] * 1 + its children's rows * cval, item_bias[i] alike
 void launch_rank_live_items(const DevParams &P, float *item_rows, float *item_bias, hipStream_t st);   // one launch
 
+// ---- the item side of svdf_item_topn (svdf_k_itemrows.hip)
+// unit[i] = W_item[i] / sqrt(<W_item[i], W_item[i]>) element by element, +0 where the sum of squares is 0; [num_item][pitch], pads 0
+void launch_item_unit_rows(const DevParams &P, float *unit, hipStream_t st);   // one launch
+// rows[s] = base[item[s]] for the nsec sections of a piece; base is a [num_item][pitch] matrix (W_item or the unit rows), item[s] < num_item
+void launch_item_query_rows(const DevParams &P, const float *base, const unsigned *item, int nsec, float *rows, hipStream_t st);   // one launch
+
 // ---- ranking over per-section candidate lists on the live model (svdf_k_rankcand.hip): one piece of whole sections.
 // Pair q of the piece is (section, cand_id[q]); a section's pairs are consecutive, its ids distinct and ascending.  Only the listed pairs
 // are scored.  Every index is local to the piece and has been validated on the host.

@@ -104,16 +104,26 @@ void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, 
     need_device("rank_topn");
     if (S == 0) return;
     flush();   // behind whatever has been staged
-    const DevParams &P = params();
     const float *item_rows = nullptr, *item_bias = nullptr;
     if (lines) rank_live_items("rank_topn", &item_rows, &item_bias);   // once per call
+    rank_topn_sweeps("rank_topn", S, user, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, nullptr, top_n, item_out, score_out, count_out, nan_out);
+}
+
+// The body the top-N calls share from the upload of the validated lists onward: pieces, geometry, workspace, the launches, the copy-back
+// and the count check.  sec_id is the user of each section, or -- query_base != nullptr, svdf_item_topn (svdf_itemtopn.cpp) -- its query
+// item, whose row of the [num_item][pitch] matrix query_base is gathered into the piece's row workspace by one more launch.
+void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
+                              const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
+                              int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
+    const unsigned *user = sec_id;
+    const DevParams &P = params();
     const int N = top_n, cap = rank_topn_cap(P, N);
     const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
         long s1 = rank_topn_piece(s0, S, max_lists, L.ban_first);
-        if (fb_ptr) s1 = rank_fb_piece("rank_topn", s0, s1, fb_ptr, rank_eval_budget_);   // ... and at most rank_eval_budget feedback entries
-        if (lines) s1 = rank_lines_piece("rank_topn", s0, s1, lines->ptr, rank_eval_budget_);   // ... and as many line entries
+        if (fb_ptr) s1 = rank_fb_piece(who, s0, s1, fb_ptr, rank_eval_budget_);   // ... and at most rank_eval_budget feedback entries
+        if (lines) s1 = rank_lines_piece(who, s0, s1, lines->ptr, rank_eval_budget_);   // ... and as many line entries
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
@@ -165,6 +175,12 @@ void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             HIPCHECK(hipGetLastError());
             n_launches_++;
             D.user_rows = rk_rows_.p;
+        } else if (query_base) {   // an item call: the sections' query rows, one more launch ahead of the sweep
+            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
+            launch_item_query_rows(P, query_base, D.sec_user, (int)nsec, rk_rows_.p, stream_);
+            HIPCHECK(hipGetLastError());
+            n_launches_++;
+            D.user_rows = rk_rows_.p;
         }
         D.list = tn_list_.p;
         D.list_cnt = tn_out_.p; D.nan_cnt = tn_out_.p + nlist; D.count_out = D.nan_cnt + nsec; D.item_out = D.count_out + nsec;
@@ -183,11 +199,11 @@ void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         for (long s = s0; s < s1; s++) {
             const size_t q = (size_t)(s - s0);
             const bool bad = b_nan[q] != 0;
-            check(b_cnt[q] == (bad ? 0 : L.count[(size_t)s]), "rank_topn: internal error: a section's list is not as long as its candidates allow");
+            if (b_cnt[q] != (bad ? 0 : L.count[(size_t)s])) fail(std::string(who) + ": internal error: a section's list is not as long as its candidates allow");
             nan_out[s] = bad ? 1 : 0;
             count_out[s] = b_cnt[q];
         }
-        n_rank_topn_sections_ += nsec;
+        (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
         s0 = s1;
     }
 }
