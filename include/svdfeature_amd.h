@@ -372,10 +372,11 @@ int svdf_synchronize(svdf_trainer *t);
  * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard),
  * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted),
  * 48 of the passes under 44 / 45, the shuffled ones (svdf_dataset_from_pair_source_shuffled),
- * 49 sections listed by svdf_item_topn */
+ * 49 sections listed by svdf_item_topn,
+ * 50 of the sections under 39 / 49 (and 40 / 41), those listed by the sweep on the matrix cores (knob rank_topn_scores = 1) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
- * OPT-IN window step only.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
+ * OPT-IN window step only, and the one marked (+), which replaces the pinned score of the top-N lists by one within a published bound.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
  *   staging / launches
  *     stage_window        2^21   instances staged by svdf_update_* before an automatic flush (also set by the config key amd:window)
  *     async_flush         1      full staged windows are scheduled on a background thread
@@ -499,6 +500,27 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *     rank_eval_budget 4194304   svdf_rank_eval_positions: positives + distinct banned ids + sections processed per piece of whole sections (>= 1)
  *     rank_topn_budget 33554432  svdf_rank_topn: 64-bit keys (8 bytes each) of the selection's list workspace; a call that needs more takes fewer
  *                                item ranges per section first, then pieces of whole sections (>= 1; results do not depend on it)
+ *     rank_topn_scores (+) 0     how the selecting sweeps of svdf_rank_topn, svdf_rank_topn_fb, svdf_rank_topn_lines (the prepared item matrix of a
+ *                                feature_item trainer included) and svdf_item_topn (dot and cosine) take a score: 0 PINNED, the default -- four serial
+ *                                fp32 chains, no FMA, bit for bit the reference ranker's; 1 MATRIX, OPT-IN -- one selecting sweep on
+ *                                the matrix cores (v_mfma_f32_16x16x4_f32: fp32 in, fp32 accumulate, one accumulator per score, K ascending) at
+ *                                every num_factor 1 .. 1024 (profiles/r41_rank_matrix.md).  Any other value is refused:
+ *                                "rank_topn_scores must be 0 (pinned) or 1 (matrix)".  The unit rows and query rows of svdf_item_topn and the
+ *                                effective user rows of the _fb / _lines calls stay the pinned kernels'; only the dot changes.
+ *                                THE RULE under 1, for a ranked candidate i of section s with effective user row u, item row v and bias b, all
+ *                                finite and with no denormal product or partial sum:
+ *                                    |score - (b + sum_j u_j v_j)| <= 2 (k + 2) 2^-24 (|b| + sum_j |u_j v_j|),
+ *                                both sides in real arithmetic: (k + 2) 2^-24 (..) bounds any fp32 summation order with fused or separately
+ *                                rounded products plus the bias add; the factor 2 is margin (the rounding inside one MFMA step is not published).
+ *                                The bits of a score are a function of its two rows, the bias and k alone -- not of the grid, the item range,
+ *                                the piece, the position in a tile, rank_topn_budget or the call.  Inf and NaN propagate as IEEE has them; a NaN
+ *                                score of a ranked candidate flags the section.  Nothing is promised about denormals, nor about symmetry of
+ *                                svdf_item_topn scores in (query, item).  Order, ties by ascending id, counts, padding, flags, top_n <= 256,
+ *                                refusals and messages are section 6x's word for word.  Counter 50 counts the sections listed this way.
+ *                                NOT reached, whatever the knob: the _cand calls, svdf_rank_eval* (positions, metrics, sampled), the hard passes
+ *                                svdf_*_pair_source*_hard (their published rule names the pinned score) and svdf_ranker_*.  svdf_rank_geometry
+ *                                (kind "topn") answers for the mode the knob selects: 64 sections per workgroup and tiles of 128 items at every
+ *                                width under 1
  *     pair_hard_form      0      the kernel of a hard pass of a pair source (svdf_dataset_from_pair_source_hard): 0 the measured
  *                                choice (the staged form up to num_cand 16 at num_factor <= 32, up to 4 at <= 128, for 2 at <= 256, the lane form
  *                                otherwise; profiles/r34_pair_hard.md), 1 one lane per candidate with both rows read where they lie, 2 the item

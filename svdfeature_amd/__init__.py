@@ -1169,7 +1169,8 @@ class Trainer:
         fb_index, fb_value): the sections' feedback lists, for user-group trainers (svdf_rank_topn_fb).  lines = (ul_ptr, ul_index,
         ul_value): the sections bring USER lines and the trainer may have side tables (svdf_rank_topn_lines); users is None then.
         candidates = (cand_ptr, cand_item): the top_n best of each section's own item list (svdf_rank_topn_cand); ban_ptr must
-        be None."""
+        be None.  set_knob("rank_topn_scores", 1) scores on the matrix cores within a published bound instead of bit for bit (DESIGN.md 6ah;
+        not the candidates call)."""
         if candidates is not None:
             S, who_ptr, cand, keep_c = self._cand_call("rank_topn", users, feedback, lines, candidates, ban_ptr)
             top_n = int(top_n)
@@ -1210,7 +1211,8 @@ class Trainer:
         """svdf_item_topn: per query item the top_n items most like it on the live model, by the dot product or the cosine of
         the W_item rows in the pinned float32 order; the query itself and the section's banned items are excluded.  items = None: every item
         in id order.  metric: "dot", "cosine" or the integers 0 / 1.  Returns (items [S, top_n] int32, -1 beyond count; scores [S, top_n]
-        float32; count [S]; nan [S]) as rank_topn does."""
+        float32; count [S]; nan [S]) as rank_topn does.  set_knob("rank_topn_scores", 1) takes the dots on the matrix cores within a published
+        bound instead of the pinned order; the unit rows stay pinned."""
         if items is None:
             shape = (C.c_int(), C.c_int())
             self._ok(self.lib.svdf_view_shape(self.h, VIEW["W_item"], C.byref(shape[0]), C.byref(shape[1])))

@@ -1008,6 +1008,8 @@ class Engine {
     DevBuf<float> re_ps_;
     int64_t n_rank_topn_sections_ = 0;   // counter 39: sections listed by svdf_rank_topn
     long rank_topn_budget_ = 1L << 25;   // knob rank_topn_budget: 64-bit keys of the list workspace of one piece (256 MiB)
+    int rank_topn_scores_ = 0;           // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
+    int64_t n_rank_matrix_sections_ = 0; // counter 50: of the sections under 39 / 49, those listed by the matrix sweep
     DevBuf<int> tn_in_, tn_out_;
     DevBuf<unsigned long long> tn_list_;
     int64_t n_rank_fb_sections_ = 0;   // counter 40: sections the _fb calls ranked with a row built from a feedback list

@@ -272,21 +272,23 @@ static size_t tn_lds_bytes(int pitch, int ib) {
     return 16 * (nch * (64 * (size_t)ib + 1) + (size_t)TN_TS * nch) + 8 * (4 * (size_t)TN_SORT + (size_t)TN_TS + (size_t)TN_TS * ib) + 4 * 2 * (size_t)TN_TS;
 }
 static int tn_ib(const DevParams &P) { return P.pitch <= 128 ? 2 : 1; }   // candidates per lane and step; the wide sweep takes 1
-int rank_topn_tile_rows(const DevParams &P) { return P.pitch <= 256 ? TN_TS : 1; }   // sections of one workgroup (narrow) or wave (wide)
+// sections of one workgroup (narrow, matrix) or wave (wide)
+int rank_topn_tile_rows(const DevParams &P, int matrix) { return matrix || P.pitch <= 256 ? TN_TS : 1; }
+static long tn_item_tile(const DevParams &P, int matrix) { return matrix ? RANK_TOPN_MATRIX_TILE : (P.pitch <= 256 ? 64 * tn_ib(P) : 64); }
 
 // room for top_n kept keys and one step's appends, and for as many appends again between two cuts where TN_SORT allows
-int rank_topn_cap(const DevParams &P, int top_n) {
-    const int ti = P.pitch <= 256 ? 64 * tn_ib(P) : 64;
+int rank_topn_cap(const DevParams &P, int top_n, int matrix) {
+    const int ti = (int)tn_item_tile(P, matrix);
     int cap = 128;
     while (cap < 2 * top_n + ti) cap <<= 1;
     return std::min(std::max(cap, top_n + ti), TN_SORT);
 }
 
-void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block) {
-    const long ti = P.pitch <= 256 ? 64 * tn_ib(P) : 64, ntile_i = (P.num_item + ti - 1) / ti;
-    // narrow: about 2048 workgroups in all, at least 8 item tiles per workgroup where the items allow (the user rows are staged per
+void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block, int matrix) {
+    const long ti = tn_item_tile(P, matrix), ntile_i = (P.num_item + ti - 1) / ti;
+    // narrow, matrix: about 2048 workgroups in all, at least 8 item tiles per workgroup where the items allow (the user rows are staged per
     // workgroup); wide: about 8192 waves
-    const long ts = rank_topn_tile_rows(P), units = (nsec + ts - 1) / ts, want = P.pitch <= 256 ? 2048 : 8192;
+    const long ts = rank_topn_tile_rows(P, matrix), units = (nsec + ts - 1) / ts, want = matrix || P.pitch <= 256 ? 2048 : 8192;
     long ysplit = std::max<long>(1, std::min<long>((want + units - 1) / units, (ntile_i + 7) / 8));
     ysplit = std::min<long>(ysplit, std::max<long>(1, max_lists / std::max<long>(1, nsec)));
     ysplit = std::min<long>(ysplit, 65535);
@@ -297,7 +299,9 @@ void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, 
 
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) {
     if (D.nsec <= 0) return;
-    if (P.pitch <= 256) {
+    if (D.matrix) {
+        launch_rank_topn_sweep_mfma(P, D, st);
+    } else if (P.pitch <= 256) {
         const int ib = tn_ib(P);
         const size_t lds = tn_lds_bytes(P.pitch, ib);
         const dim3 grid((unsigned)((D.nsec + rank_topn_tile_rows(P) - 1) / rank_topn_tile_rows(P)), (unsigned)D.gy);

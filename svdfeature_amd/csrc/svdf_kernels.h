@@ -311,6 +311,7 @@ void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st);
 // top_n largest keys of a section's gy lists.  Every index is local to the piece and has been validated on the host.
 constexpr int RANK_TOPN_MAX = 256;       // largest top_n
 constexpr int RANK_TOPN_MAX_CAP = 512;   // keys one wave sorts in LDS: the largest list capacity
+constexpr int RANK_TOPN_MATRIX_TILE = 128;   // items of one tile of the matrix sweep (svdf_k_ranktopn_mfma.hip), at every width
 struct RankTopnDev {
     int nsec;                        // sections of the piece
     const unsigned *sec_user;        // [nsec]
@@ -326,11 +327,15 @@ struct RankTopnDev {
     int *item_out;                   // [nsec][top_n] ids in rank order, -1 beyond count_out
     float *score_out;                // [nsec][top_n] their scores, 0 beyond count_out
     int *count_out;                  // [nsec] entries listed; 0 for a section with a NaN among its ranked candidates
+    int matrix = 0;                  // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
 };
-int rank_topn_cap(const DevParams &P, int top_n);   // capacity of one list, <= RANK_TOPN_MAX_CAP
-int rank_topn_tile_rows(const DevParams &P);        // sections that share one pass over an item range: 64 (narrow) or 1 (wide)
-void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block);   // at most max_lists / nsec (>= 1) item ranges
-void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep, then the merge: two launches
+// `matrix` is the knob rank_topn_scores; with 0 the four answer for the pinned sweeps, with 1 for the matrix sweep (64 sections per
+// workgroup and tiles of RANK_TOPN_MATRIX_TILE items at every width)
+int rank_topn_cap(const DevParams &P, int top_n, int matrix = 0);   // capacity of one list, <= RANK_TOPN_MAX_CAP
+int rank_topn_tile_rows(const DevParams &P, int matrix = 0);        // sections that share one pass over an item range: 64 (narrow, matrix) or 1 (wide)
+void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block, int matrix = 0);   // at most max_lists / nsec (>= 1) item ranges
+void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep (by D.matrix), then the merge: two launches
+void launch_rank_topn_sweep_mfma(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // svdf_k_ranktopn_mfma.hip: the matrix sweep alone
 
 // ---- the effective user rows of a piece's sections on a user-group trainer (svdf_k_rankrows.hip):
 // rows[s] = (0 + sum_j W_ufeedback[fb_index[j]] * fb_value[j], j in [fb_p0[s], fb_p0[s + 1]) in list order) + W_user[sec_user[s]] * 1, in the

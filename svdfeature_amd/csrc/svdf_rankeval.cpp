@@ -286,12 +286,12 @@ void Engine::rank_geometry(int kind, long units, int top_n, const int64_t *pos_p
         out[7] = P.pitch <= 256 ? (ntile > 0 ? 1 : 0) : (nrow + RANK_EVAL_WIDE_ROWS - 1) / RANK_EVAL_WIDE_ROWS;   // launches of the sweep
     } else {
         check(top_n >= 1 && top_n <= RANK_TOPN_MAX, "rank_geometry: top_n must be between 1 and 256");
-        const int cap = rank_topn_cap(P, top_n);
+        const int matrix = rank_topn_scores_, cap = rank_topn_cap(P, top_n, matrix);
         const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
         const std::vector<int64_t> no_bans((size_t)units + 1, 0);
         const long piece = rank_topn_piece(0, units, max_lists, no_bans);   // units sections without bans: the first piece
-        rank_topn_geometry(P, piece, max_lists, &gy, &per);
-        const long ts = rank_topn_tile_rows(P);
+        rank_topn_geometry(P, piece, max_lists, &gy, &per, matrix);
+        const long ts = rank_topn_tile_rows(P, matrix);
         out[2] = cap; out[3] = ts; out[4] = piece; out[5] = (piece + ts - 1) / ts; out[6] = piece; out[7] = 1;
     }
     out[0] = gy; out[1] = per;

@@ -117,7 +117,7 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
                               int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
     const unsigned *user = sec_id;
     const DevParams &P = params();
-    const int N = top_n, cap = rank_topn_cap(P, N);
+    const int N = top_n, matrix = rank_topn_scores_, cap = rank_topn_cap(P, N, matrix);
     const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
@@ -127,8 +127,8 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
-        D.nsec = (int)nsec; D.top_n = N; D.cap = cap;
-        rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block);
+        D.nsec = (int)nsec; D.top_n = N; D.cap = cap; D.matrix = matrix;
+        rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block, matrix);
         // ---- one upload: sec_user | ban_p0 | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         const size_t o_fb = 2 * (size_t)nsec + 1 + (size_t)nban, o_ul = o_fb + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0);
         in.resize(o_ul + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));
@@ -204,6 +204,7 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
             count_out[s] = b_cnt[q];
         }
         (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
+        if (matrix) n_rank_matrix_sections_ += nsec;
         s0 = s1;
     }
 }
