@@ -66,6 +66,7 @@ def assert_bounded(got, rows, W, bias, on, top_n, k):
             assert (ref[s, rest] - ref[s, last] <= bound[s, rest] + bound[s, last]).all()
     print("largest |error| / bound at k = %d: %.4f" % (k, worst))
     assert worst <= 1.0
+    return worst
 
 
 CASES = [(k, S, NI) for k in (1, 3, 4, 33, 64, 130, 256, 257, 1024) for S in (1, 65, 203)] + [(64, 65, 129)]
