@@ -373,7 +373,9 @@ int svdf_synchronize(svdf_trainer *t);
  * 47 of the passes under 44 / 45, those drawn from a source with item weights (svdf_pair_source_create_weighted),
  * 48 of the passes under 44 / 45, the shuffled ones (svdf_dataset_from_pair_source_shuffled),
  * 49 sections listed by svdf_item_topn,
- * 50 of the sections under 39 / 49 (and 40 / 41), those listed by the sweep on the matrix cores (knob rank_topn_scores = 1) */
+ * 50 of the sections under 39 / 49 (and 40 / 41), those listed by the sweep on the matrix cores (knob rank_topn_scores = 1),
+ * 51 / 52 of the sections under 39 / 49 (and 40 / 41), those the certified prefilter listed (knob rank_topn_prefilter = 1) /
+ * those it left to the pinned sweep, which listed them again; 50 does not move under the prefilter */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only, and the one marked (+), which replaces the pinned score of the top-N lists by one within a published bound.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -521,6 +523,28 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                svdf_*_pair_source*_hard (their published rule names the pinned score) and svdf_ranker_*.  svdf_rank_geometry
  *                                (kind "topn") answers for the mode the knob selects: 64 sections per workgroup and tiles of 128 items at every
  *                                width under 1
+ *     rank_topn_prefilter 0      1: the PINNED lists, bit for bit, through the matrix sweep (svdf_k_ranktopn_exact.hip;
+ *                                profiles/r43_rank_prefilter.md).  Acts only while rank_topn_scores is 0 (with rank_topn_scores = 1 the 6ah lists are
+ *                                returned as before and the counters 51 / 52 do not move) and reaches what rank_topn_scores reaches.  Any other
+ *                                value is refused: "rank_topn_prefilter must be 0 or 1".  The matrix sweep keeps M = top_n +
+ *                                rank_topn_prefilter_slack approximate keys per section; one wave per section re-scores those M ids in the pinned
+ *                                order and certifies the section or leaves it to the pinned sweep.
+ *                                THE RULE.  For a section s with effective user row u (W_user, the _fb / _lines row or the query row) let
+ *                                m_j = max_i |v_ij| over ALL rows of the item side the call scores with, B = max_i |b_i|,
+ *                                    H_s = B + sum_j |u_j| m_j,   Delta_s = 4 (k + 2) 2^-24 H_s + (k + 2) 2^-124,
+ *                                in float64 on the device.  (k + 2) 2^-24 (..) bounds any fp32 summation order, so the pinned one too; with
+ *                                6ah's 2 (k + 2) 2^-24 (..) that makes 3, and the 4 pays for evaluating the envelope; the absolute term covers
+ *                                products and partial sums either path flushes below 2^-126.  A section is CERTIFIED iff (a) every entry of the
+ *                                item side (rows up to k, biases) and of u is finite and zero or normal, (b) H_s <= 2^126, (c) the matrix sweep
+ *                                flagged no NaN for it, (d) its M-key list holds every ranked candidate (fewer than M keys), or p_N > t + Delta_s
+ *                                strictly, t the approximate score of the M-th kept key and p_N the N-th largest pinned score among the M
+ *                                re-scored candidates; a NaN among the re-scored pinned scores also leaves it uncertified.  Then every unlisted
+ *                                candidate has a pinned score <= t + Delta_s < p_N, the pinned top N (ties by id included) lies inside the M
+ *                                ids, and sorting their pinned keys gives the pinned list.  A section that is not certified is listed again by
+ *                                the pinned sweep; flags, counts, padding and order are 6x's either way.  Counters 51 / 52.  svdf_rank_geometry
+ *                                (kind "topn") answers the matrix rule at top_n + slack
+ *     rank_topn_prefilter_slack 32   keys the matrix sweep keeps beyond top_n under the prefilter, 1 .. 128 (else refused: "rank_topn_prefilter_slack
+ *                                must be between 1 and 128"); changes how many sections the pinned sweep lists again, never an answer
  *     pair_hard_form      0      the kernel of a hard pass of a pair source (svdf_dataset_from_pair_source_hard): 0 the measured
  *                                choice (the staged form up to num_cand 16 at num_factor <= 32, up to 4 at <= 128, for 2 at <= 256, the lane form
  *                                otherwise; profiles/r34_pair_hard.md), 1 one lane per candidate with both rows read where they lie, 2 the item

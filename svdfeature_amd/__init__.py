@@ -1170,7 +1170,9 @@ class Trainer:
         ul_value): the sections bring USER lines and the trainer may have side tables (svdf_rank_topn_lines); users is None then.
         candidates = (cand_ptr, cand_item): the top_n best of each section's own item list (svdf_rank_topn_cand); ban_ptr must
         be None.  set_knob("rank_topn_scores", 1) scores on the matrix cores within a published bound instead of bit for bit (DESIGN.md 6ah;
-        not the candidates call)."""
+        not the candidates call).  set_knob("rank_topn_prefilter", 1) keeps the pinned lists bit for bit and takes them through the matrix sweep:
+        top_n + rank_topn_prefilter_slack (32) approximate winners per section are re-scored in the pinned order, a section the published rule
+        does not certify is listed again by the pinned sweep (counters 51 / 52; acts while rank_topn_scores is 0)."""
         if candidates is not None:
             S, who_ptr, cand, keep_c = self._cand_call("rank_topn", users, feedback, lines, candidates, ban_ptr)
             top_n = int(top_n)
@@ -1212,7 +1214,8 @@ class Trainer:
         the W_item rows in the pinned float32 order; the query itself and the section's banned items are excluded.  items = None: every item
         in id order.  metric: "dot", "cosine" or the integers 0 / 1.  Returns (items [S, top_n] int32, -1 beyond count; scores [S, top_n]
         float32; count [S]; nan [S]) as rank_topn does.  set_knob("rank_topn_scores", 1) takes the dots on the matrix cores within a published
-        bound instead of the pinned order; the unit rows stay pinned."""
+        bound instead of the pinned order; the unit rows stay pinned.  set_knob("rank_topn_prefilter", 1): the pinned lists, bit
+        for bit, through the matrix sweep and a certified re-score, as for rank_topn."""
         if items is None:
             shape = (C.c_int(), C.c_int())
             self._ok(self.lib.svdf_view_shape(self.h, VIEW["W_item"], C.byref(shape[0]), C.byref(shape[1])))

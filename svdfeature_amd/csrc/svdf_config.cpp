@@ -231,6 +231,8 @@ int64_t Engine::counter(int what) const {
     case 48: return n_pair_src_shuffled_;    // of the passes under 44 / 45, the shuffled ones: rows in the order sigma of an order_seed (section 6af)
     case 49: return n_item_topn_sections_;   // sections listed by svdf_item_topn (section 6ag)
     case 50: return n_rank_matrix_sections_; // of the sections under 39 / 49, those listed by the matrix sweep (knob rank_topn_scores = 1, section 6ah)
+    case 51: return n_rank_certified_sections_;   // of the sections under 39 / 49, those certified under the prefilter (knob rank_topn_prefilter = 1, section 6ai)
+    case 52: return n_rank_relisted_sections_;    // ... and those the pinned sweep listed again
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -327,6 +329,8 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "pair_weight_form")) { check(value >= 0 && value <= 2, "pair_weight_form must be 0 (measured choice), 1 (search of the whole cdf) or 2 (guided search)"); pair_weight_form_ = value; return 0; }
     if (!strcmp(name, "pair_hard_form")) { check(value >= 0 && value <= 2, "pair_hard_form must be 0 (measured choice), 1 (one lane per candidate) or 2 (staged)"); pair_hard_form_ = value; return 0; }
     if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }
+    if (!strcmp(name, "rank_topn_prefilter")) { check(value == 0 || value == 1, "rank_topn_prefilter must be 0 or 1"); rank_topn_prefilter_ = (int)value; return 0; }
+    if (!strcmp(name, "rank_topn_prefilter_slack")) { check(value >= 1 && value <= 128, "rank_topn_prefilter_slack must be between 1 and 128"); rank_topn_slack_ = (int)value; return 0; }
     if (!strcmp(name, "rank_topn_scores")) { check(value == 0 || value == 1, "rank_topn_scores must be 0 (pinned) or 1 (matrix)"); rank_topn_scores_ = (int)value; return 0; }
     if (!strcmp(name, "window_slots")) { window_slots_ = value != 0; return 0; }
     if (!strcmp(name, "window_groups")) { check(value >= 0 && value <= 2, "window_groups must be 0 (auto), 1 or 2"); window_groups_ = (int)value; return 0; }

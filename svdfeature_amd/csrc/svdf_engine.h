@@ -519,6 +519,12 @@ class Engine {
     void rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
                           const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
                           int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+    // one pass of that body over all S sections.  mode 0: the pinned sweeps; 1: the matrix sweep; 2: the certified prefilter (section 6ai),
+    // which also fills certified[S] and leaves the outputs of a section that is not certified to the caller; counted: the sections count
+    // under 39 / 49 (40 / 41) -- not when the pinned sweep lists the sections again that the prefilter did not certify
+    void rank_topn_pass(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
+                        const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
+                        int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, int mode, int *certified, bool counted);
     // similar-item lists on the live model: dot and cosine top-N per query item (svdf_itemtopn.cpp, svdf_k_itemrows.hip)
     void item_topn(long S, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
                    float *score_out, int *count_out, int *nan_out);
@@ -1010,6 +1016,11 @@ class Engine {
     long rank_topn_budget_ = 1L << 25;   // knob rank_topn_budget: 64-bit keys of the list workspace of one piece (256 MiB)
     int rank_topn_scores_ = 0;           // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
     int64_t n_rank_matrix_sections_ = 0; // counter 50: of the sections under 39 / 49, those listed by the matrix sweep
+    int rank_topn_prefilter_ = 0;        // knob rank_topn_prefilter: 1 the pinned lists through the certified matrix-core prefilter (section 6ai); acts while rank_topn_scores is 0
+    int rank_topn_slack_ = 32;           // knob rank_topn_prefilter_slack: keys the matrix sweep keeps beyond top_n under the prefilter, 1 .. 128
+    int64_t n_rank_certified_sections_ = 0;   // counter 51: of the sections under 39 / 49, those certified under the prefilter
+    int64_t n_rank_relisted_sections_ = 0;    // counter 52: ... and those the pinned sweep listed again
+    DevBuf<unsigned> tn_env_;            // the item side's envelope of one prefilter call, RANK_ENV_WORDS words
     DevBuf<int> tn_in_, tn_out_;
     DevBuf<unsigned long long> tn_list_;
     int64_t n_rank_fb_sections_ = 0;   // counter 40: sections the _fb calls ranked with a row built from a feedback list

@@ -7,22 +7,31 @@
 
 namespace svdf {
 
-// one candidate against one user by ONE lane, both rows row-major in HBM
-__device__ __forceinline__ float re_row_score(int k, const float4 *__restrict__ p4, const float4 *__restrict__ q4, float bias) {
-    const int nfull = k >> 2, ntail = k & 3;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (int j = 0; j < nfull; j++) {
+// The order in two parts, for a kernel that walks K in chunks (svdf_k_ranktopn_exact.hip): the four serial chains over n consecutive full
+// float4s of both rows, carried in `a` from chunk to chunk ...
+__device__ __forceinline__ void re_row_chains(float4 &a, const float4 *__restrict__ p4, const float4 *__restrict__ q4, int n) {
+    for (int j = 0; j < n; j++) {
         const float4 p = p4[j], v = q4[j];
-        a0 = a0 + p.x * v.x; a1 = a1 + p.y * v.y; a2 = a2 + p.z * v.z; a3 = a3 + p.w * v.w;
+        a.x = a.x + p.x * v.x; a.y = a.y + p.y * v.y; a.z = a.z + p.z * v.z; a.w = a.w + p.w * v.w;
     }
-    float sum = (a0 + a2) + (a1 + a3);
+}
+// ... and the end: (a0 + a2) + (a1 + a3), the ntail (0 .. 3) elements of the rows' last float4s p, v in index order, the bias
+__device__ __forceinline__ float re_row_finish(const float4 &a, int ntail, const float4 &p, const float4 &v, float bias) {
+    float sum = (a.x + a.z) + (a.y + a.w);
     if (ntail) {
-        const float4 p = p4[nfull], v = q4[nfull];
         sum = sum + p.x * v.x;
         if (ntail > 1) sum = sum + p.y * v.y;
         if (ntail > 2) sum = sum + p.z * v.z;
     }
     return 0.0f + (bias + sum);   // k_rank_score: item_score (0) + (bias + dot)
+}
+// one candidate against one user by ONE lane, both rows row-major in HBM
+__device__ __forceinline__ float re_row_score(int k, const float4 *__restrict__ p4, const float4 *__restrict__ q4, float bias) {
+    const int nfull = k >> 2, ntail = k & 3;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p = a, v = a;
+    re_row_chains(a, p4, q4, nfull);
+    if (ntail) { p = p4[nfull]; v = q4[nfull]; }
+    return re_row_finish(a, ntail, p, v, bias);
 }
 __device__ __forceinline__ const float4 *re_user_row(const DevParams &P, unsigned u) {
     return reinterpret_cast<const float4 *>(P.W + (size_t)(P.user_off + u) * P.pitch);

@@ -299,6 +299,11 @@ void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, 
 
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) {
     if (D.nsec <= 0) return;
+    if (D.exact_n > 0) {   // the certified prefilter (section 6ai): the matrix sweep with top_n + slack keys, then the pinned re-score
+        launch_rank_topn_sweep_mfma(P, D, st);
+        launch_rank_topn_exact(P, D, st);
+        return;
+    }
     if (D.matrix) {
         launch_rank_topn_sweep_mfma(P, D, st);
     } else if (P.pitch <= 256) {

@@ -328,13 +328,23 @@ struct RankTopnDev {
     float *score_out;                // [nsec][top_n] their scores, 0 beyond count_out
     int *count_out;                  // [nsec] entries listed; 0 for a section with a NaN among its ranked candidates
     int matrix = 0;                  // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
+    // the certified prefilter (knob rank_topn_prefilter, svdf_k_ranktopn_exact.hip), exact_n > 0: the matrix sweep keeps
+    // top_n = exact_n + slack keys per list, and k_rank_topn_exact writes item_out / score_out as [nsec][exact_n]
+    int exact_n = 0;                 // the caller's top_n
+    const unsigned *envelope = nullptr;   // [RANK_ENV_WORDS] written by launch_rank_item_envelope for the item side of this call
+    int *certified = nullptr;        // [nsec] 1: the section's list is the pinned list; 0: the pinned sweep has to list it
 };
+// The item side's envelope: words 0 .. k - 1 the bit patterns of m_j = max_i |v_ij|, then (RANK_ENV_BIAS) of B = max_i |b_i|, then
+// (RANK_ENV_FLAGS) bit 0: an entry is inf or NaN, bit 1: an entry is denormal.  The caller zeroes the words; one launch.
+constexpr int RANK_ENV_BIAS = 1024, RANK_ENV_FLAGS = 1025, RANK_ENV_WORDS = 1026;
+void launch_rank_item_envelope(const DevParams &P, const float *item_rows, const float *item_bias, unsigned *envelope, hipStream_t st);
+void launch_rank_topn_exact(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // in the merge's place under the prefilter
 // `matrix` is the knob rank_topn_scores; with 0 the four answer for the pinned sweeps, with 1 for the matrix sweep (64 sections per
 // workgroup and tiles of RANK_TOPN_MATRIX_TILE items at every width)
 int rank_topn_cap(const DevParams &P, int top_n, int matrix = 0);   // capacity of one list, <= RANK_TOPN_MAX_CAP
 int rank_topn_tile_rows(const DevParams &P, int matrix = 0);        // sections that share one pass over an item range: 64 (narrow, matrix) or 1 (wide)
 void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block, int matrix = 0);   // at most max_lists / nsec (>= 1) item ranges
-void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep (by D.matrix), then the merge: two launches
+void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep (by D.matrix), then the merge -- D.exact_n > 0: the matrix sweep, then k_rank_topn_exact: two launches
 void launch_rank_topn_sweep_mfma(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // svdf_k_ranktopn_mfma.hip: the matrix sweep alone
 
 // ---- the effective user rows of a piece's sections on a user-group trainer (svdf_k_rankrows.hip):

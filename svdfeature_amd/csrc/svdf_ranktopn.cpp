@@ -109,15 +109,89 @@ void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, 
     rank_topn_sweeps("rank_topn", S, user, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, nullptr, top_n, item_out, score_out, count_out, nan_out);
 }
 
-// The body the top-N calls share from the upload of the validated lists onward: pieces, geometry, workspace, the launches, the copy-back
-// and the count check.  sec_id is the user of each section, or -- query_base != nullptr, svdf_item_topn (svdf_itemtopn.cpp) -- its query
-// item, whose row of the [num_item][pitch] matrix query_base is gathered into the piece's row workspace by one more launch.
+// The body the top-N calls share from the upload of the validated lists onward.  sec_id is the user of each section, or -- query_base !=
+// nullptr, svdf_item_topn (svdf_itemtopn.cpp) -- its query item.  Under the knob rank_topn_prefilter (and rank_topn_scores = 0; DESIGN.md
+// section 6ai) the sections go through the matrix sweep and the pinned re-score first; those the rule does not certify are gathered --
+// ids, validated ban lists, feedback lists, USER lines -- into contiguous copies, listed once more by the pinned sweeps and scattered to
+// their places.  Either way every section's list is the pinned one.
 void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
                               const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
                               int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
+    if (!(rank_topn_prefilter_ && !rank_topn_scores_)) {
+        rank_topn_pass(who, S, sec_id, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, query_base, top_n, item_out, score_out, count_out,
+                       nan_out, rank_topn_scores_, nullptr, true);
+        return;
+    }
+    const DevParams &P = params();
+    // ---- the envelope of the item side this call scores with, once, ahead of the first piece
+    tn_env_.reserve(RANK_ENV_WORDS);
+    HIPCHECK(hipMemsetAsync(tn_env_.p, 0, RANK_ENV_WORDS * sizeof(unsigned), stream_));
+    launch_rank_item_envelope(P, item_rows, item_bias, tn_env_.p, stream_);
+    HIPCHECK(hipGetLastError());
+    n_launches_++;
+    std::vector<int> certified((size_t)S, 0);
+    rank_topn_pass(who, S, sec_id, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, query_base, top_n, item_out, score_out, count_out, nan_out,
+                   2, certified.data(), true);
+    std::vector<long> again;
+    for (long s = 0; s < S; s++)
+        if (!certified[(size_t)s]) again.push_back(s);
+    const long A = (long)again.size();
+    n_rank_certified_sections_ += S - A;
+    n_rank_relisted_sections_ += A;
+    if (A == 0) return;
+    // ---- the sections left: contiguous copies of what they bring, the pinned sweeps, the results back to their places
+    const size_t N = (size_t)top_n;
+    std::vector<unsigned> ids((size_t)A);
+    RankTopnLists LA;
+    LA.ban_first.assign((size_t)A + 1, 0);
+    LA.count.resize((size_t)A);
+    auto gather = [&](const int64_t *ptr, const unsigned *index, const float *value, std::vector<int64_t> &p, std::vector<unsigned> &ix, std::vector<float> &v) {
+        p.assign((size_t)A + 1, 0);
+        for (long a = 0; a < A; a++) {
+            const long s = again[(size_t)a];
+            ix.insert(ix.end(), index + ptr[s], index + ptr[s + 1]);
+            v.insert(v.end(), value + ptr[s], value + ptr[s + 1]);
+            p[(size_t)a + 1] = (int64_t)ix.size();
+        }
+    };
+    std::vector<int64_t> fbp, ulp;
+    std::vector<unsigned> fbi, uli;
+    std::vector<float> fbv, ulv;
+    for (long a = 0; a < A; a++) {
+        const size_t s = (size_t)again[(size_t)a];
+        ids[(size_t)a] = sec_id[s];
+        LA.ban_ids.insert(LA.ban_ids.end(), L.ban_ids.begin() + (long)L.ban_first[s], L.ban_ids.begin() + (long)L.ban_first[s + 1]);
+        LA.ban_first[(size_t)a + 1] = (int64_t)LA.ban_ids.size();
+        LA.count[(size_t)a] = L.count[s];
+    }
+    if (fb_ptr) gather(fb_ptr, fb_index, fb_value, fbp, fbi, fbv);
+    RankLines UA;
+    if (lines) {
+        gather(lines->ptr, lines->index, lines->value, ulp, uli, ulv);
+        UA.ptr = ulp.data(); UA.index = uli.data(); UA.value = ulv.data();
+    }
+    std::vector<int> a_item((size_t)A * N), a_count((size_t)A), a_nan((size_t)A);
+    std::vector<float> a_score(score_out ? (size_t)A * N : 0);
+    rank_topn_pass(who, A, ids.data(), LA, fb_ptr ? fbp.data() : nullptr, fbi.data(), fbv.data(), lines ? &UA : nullptr, item_rows, item_bias, query_base,
+                   top_n, a_item.data(), score_out ? a_score.data() : nullptr, a_count.data(), a_nan.data(), 0, nullptr, false);
+    for (long a = 0; a < A; a++) {
+        const size_t s = (size_t)again[(size_t)a];
+        std::copy(a_item.begin() + (long)((size_t)a * N), a_item.begin() + (long)((size_t)(a + 1) * N), item_out + s * N);
+        if (score_out) std::copy(a_score.begin() + (long)((size_t)a * N), a_score.begin() + (long)((size_t)(a + 1) * N), score_out + s * N);
+        count_out[s] = a_count[(size_t)a];
+        nan_out[s] = a_nan[(size_t)a];
+    }
+}
+
+// One pass over all S sections: pieces, geometry, workspace, the launches, the copy-back and the count check.  An item call's query rows
+// are gathered from the [num_item][pitch] matrix query_base into the piece's row workspace by one more launch.
+void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
+                            const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
+                            int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, int mode, int *certified, bool counted) {
     const unsigned *user = sec_id;
     const DevParams &P = params();
-    const int N = top_n, matrix = rank_topn_scores_, cap = rank_topn_cap(P, N, matrix);
+    // under the prefilter the sweep keeps `keep` = top_n + slack keys per list, and the cap, the geometry and the pieces follow it
+    const int N = top_n, matrix = mode != 0, keep = mode == 2 ? N + rank_topn_slack_ : N, cap = rank_topn_cap(P, keep, matrix);
     const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
@@ -127,7 +201,7 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
-        D.nsec = (int)nsec; D.top_n = N; D.cap = cap; D.matrix = matrix;
+        D.nsec = (int)nsec; D.top_n = keep; D.cap = cap; D.matrix = matrix;
         rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block, matrix);
         // ---- one upload: sec_user | ban_p0 | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         const size_t o_fb = 2 * (size_t)nsec + 1 + (size_t)nban, o_ul = o_fb + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0);
@@ -142,8 +216,8 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
         in[o_bp0 + (size_t)nsec] = (int)nban;
         std::copy(L.ban_ids.begin() + (long)L.ban_first[(size_t)s0], L.ban_ids.begin() + (long)L.ban_first[(size_t)s1], in.begin() + (long)o_ban);
         tn_in_.upload(in.data(), in.size(), stream_);
-        // ---- the workspace: list_cnt | nan_cnt | count | items | scores, and the lists
-        const size_t nlist = (size_t)nsec * (size_t)D.gy, nres = (size_t)nsec * (2 + 2 * (size_t)N);
+        // ---- the workspace: list_cnt | nan_cnt | count | certified | items | scores, and the lists
+        const size_t nlist = (size_t)nsec * (size_t)D.gy, nres = (size_t)nsec * (3 + 2 * (size_t)N);
         tn_out_.reserve(nlist + nres);
         tn_list_.reserve(nlist * (size_t)cap);
         HIPCHECK(hipMemsetAsync(tn_out_.p, 0, (nlist + (size_t)nsec) * sizeof(int), stream_));
@@ -161,14 +235,14 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
                 R.fb_p0 = tn_in_.p + o_fb;
                 R.fb_index = reinterpret_cast<const unsigned *>(tn_in_.p + o_fb + (size_t)nsec + 1);
                 R.fb_value = reinterpret_cast<const float *>(tn_in_.p + o_fb + (size_t)nsec + 1 + nfb);
-                n_rank_fb_sections_ += nsec;
+                if (counted) n_rank_fb_sections_ += nsec;
             }
             if (lines) {
                 const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
                 R.ul_p0 = tn_in_.p + o_ul;
                 R.ul_index = reinterpret_cast<const unsigned *>(tn_in_.p + o_ul + (size_t)nsec + 1);
                 R.ul_value = reinterpret_cast<const float *>(tn_in_.p + o_ul + (size_t)nsec + 1 + nul);
-                n_rank_line_sections_ += nsec;
+                if (counted) n_rank_line_sections_ += nsec;
             }
             R.rows = rk_rows_.p;
             launch_rank_live_rows(P, R, stream_);
@@ -183,28 +257,30 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
             D.user_rows = rk_rows_.p;
         }
         D.list = tn_list_.p;
-        D.list_cnt = tn_out_.p; D.nan_cnt = tn_out_.p + nlist; D.count_out = D.nan_cnt + nsec; D.item_out = D.count_out + nsec;
+        D.list_cnt = tn_out_.p; D.nan_cnt = tn_out_.p + nlist; D.count_out = D.nan_cnt + nsec; D.certified = D.count_out + nsec; D.item_out = D.certified + nsec;
         D.score_out = reinterpret_cast<float *>(D.item_out + (size_t)nsec * N);
+        if (mode == 2) { D.exact_n = N; D.envelope = tn_env_.p; }
         launch_rank_topn(P, D, stream_);
         HIPCHECK(hipGetLastError());
         n_launches_ += 2;
         // the merge has written the lists as the caller gets them (-1 / 0 beyond a section's count, all of a flagged section): they go
         // straight into the caller's arrays
-        back.resize(2 * (size_t)nsec);
-        HIPCHECK(hipMemcpyAsync(back.data(), D.nan_cnt, 2 * (size_t)nsec * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        back.resize(3 * (size_t)nsec);
+        HIPCHECK(hipMemcpyAsync(back.data(), D.nan_cnt, (mode == 2 ? 3 : 2) * (size_t)nsec * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipMemcpyAsync(item_out + (size_t)s0 * N, D.item_out, (size_t)nsec * N * sizeof(int), hipMemcpyDeviceToHost, stream_));
         if (score_out) HIPCHECK(hipMemcpyAsync(score_out + (size_t)s0 * N, D.score_out, (size_t)nsec * N * sizeof(float), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
-        const int *b_nan = back.data(), *b_cnt = b_nan + nsec;
+        const int *b_nan = back.data(), *b_cnt = b_nan + nsec, *b_cert = b_cnt + nsec;
         for (long s = s0; s < s1; s++) {
             const size_t q = (size_t)(s - s0);
+            if (certified && !(certified[s] = b_cert[q])) continue;   // the pinned sweep lists it, and is checked then
             const bool bad = b_nan[q] != 0;
             if (b_cnt[q] != (bad ? 0 : L.count[(size_t)s])) fail(std::string(who) + ": internal error: a section's list is not as long as its candidates allow");
             nan_out[s] = bad ? 1 : 0;
             count_out[s] = b_cnt[q];
         }
-        (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
-        if (matrix) n_rank_matrix_sections_ += nsec;
+        if (counted) (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
+        if (mode == 1) n_rank_matrix_sections_ += nsec;
         s0 = s1;
     }
 }
