@@ -545,6 +545,29 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                (kind "topn") answers the matrix rule at top_n + slack
  *     rank_topn_prefilter_slack 32   keys the matrix sweep keeps beyond top_n under the prefilter, 1 .. 128 (else refused: "rank_topn_prefilter_slack
  *                                must be between 1 and 128"); changes how many sections the pinned sweep lists again, never an answer
+ *     rank_eval_prefilter 0      1: the PINNED positions, count for count, through a counting sweep on the matrix cores and an exact band pass
+ *                                (svdf_k_rankeval_mfma.hip; profiles/r44_rank_eval_prefilter.md).  Any other value is refused:
+ *                                "rank_eval_prefilter must be 0 or 1".  Reaches svdf_rank_eval_positions, _fb, _lines and with them svdf_rank_eval,
+ *                                _fb, _lines; NOT the _cand and _sampled calls, svdf_ranker_*, the top-N calls, amd:gpus > 1.  With 0 nothing changes.
+ *                                THE RULE.  For a section s, Delta_s is rank_topn_prefilter's above, in float64 on the device from the envelope
+ *                                of the item side the call scores with.  For positive t of s with pinned score p_t (k_rank_eval_pos):
+ *                                    lo_t = float32(p_t - Delta_s) rounded down,   hi_t = float32(p_t + Delta_s) rounded up,
+ *                                both formed in float64 and direction-corrected.  A ranked candidate with approximate score a (the matrix
+ *                                sweep's, rank_topn_scores = 1) has a pinned score strictly greater than p_t where a > hi_t, strictly smaller
+ *                                where a < lo_t, and is otherwise in the BAND of t.  A candidate in the band of any positive of its row (a
+ *                                section, or a slice of 28 of its positives in ascending order of pinned score) is counted by no approximate
+ *                                comparison: it goes to the row's band list, and the band pass compares its pinned score and id with every
+ *                                positive of the row by the documented rule (greater; tied, +0 == -0; tied with a smaller id).  A positive is
+ *                                always in its own band.  A section is CERTIFIED iff (a) every entry of the item side and of its effective user
+ *                                row is finite and zero or normal, (b) H_s <= 2^126, (c) the matrix sweep saw no NaN among its ranked candidates
+ *                                (nor the pinned kernels among its positives and band candidates), (d) none of its rows overflowed its band
+ *                                list.  Every other section is ranked again by the pinned sweep from gathered copies of what it brings; the NaN
+ *                                flag and the -1 positions are always the pinned route's.  Counters: 53 certified sections, 54 sections ranked
+ *                                again (each section still once under 38, and 40 / 41); 55 rows swept, 56 band candidates met, 57 the longest
+ *                                band of one row.  svdf_rank_geometry (kind "positions") answers for the mode the handle is in: rows of 28
+ *                                positives in units of 64, the matrix rule's item ranges, cap = the band capacity
+ *     rank_eval_prefilter_band 1024   item ids a row's band list holds, 64 .. 65536 (else refused: "rank_eval_prefilter_band must be between 64 and
+ *                                65536"); a row's list counts into rank_eval_budget; changes how many sections are ranked again, never an answer
  *     pair_hard_form      0      the kernel of a hard pass of a pair source (svdf_dataset_from_pair_source_hard): 0 the measured
  *                                choice (the staged form up to num_cand 16 at num_factor <= 32, up to 4 at <= 128, for 2 at <= 256, the lane form
  *                                otherwise; profiles/r34_pair_hard.md), 1 one lane per candidate with both rows read where they lie, 2 the item

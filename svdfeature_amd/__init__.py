@@ -1085,7 +1085,10 @@ class Trainer:
         feedback= and lines=, and ban_ptr must be None.  sampled = (num_neg, seed): section s ranks its positives against num_neg negatives
         the device draws by the published rule from (seed, s, the section's bans and positives) (svdf_rank_eval_positions_sampled, DESIGN.md
         6ab); it combines with feedback= and lines=, never with candidates=; return_negatives=True returns the drawn ids as a fifth array,
-        [S, num_neg] int32 in draw order (-1 for a section without positives)."""
+        [S, num_neg] int32 in draw order (-1 for a section without positives).  set_knob("rank_eval_prefilter", 1) returns the same four
+        arrays, count for count, through a counting sweep on the matrix cores and an exact pass over the candidates too close to a positive to
+        call (DESIGN.md 6aj); a section the published rule does not certify is ranked again by the pinned sweep (counters 53 / 54;
+        rank_eval_prefilter_band, 1024, is the room of a row's band list).  It reaches feedback= and lines=, not candidates= or sampled=."""
         if sampled is not None:
             S, args, keep_s = self._sampled_call(users, feedback, lines, candidates, sampled, pos_ptr, pos_item, ban_ptr, ban_item)
             n = int(keep_s[2][-1]) if S else 0
@@ -1131,7 +1134,8 @@ class Trainer:
                   sampled=None):
         """svdf_rank_eval: positions on the GPU, then the reference's metrics of them on the host; a dict (see RankMetrics.as_dict).
         feedback, lines, candidates, sampled: as in rank_positions (svdf_rank_eval_fb, svdf_rank_eval_lines, svdf_rank_eval_cand,
-        svdf_rank_eval_sampled)."""
+        svdf_rank_eval_sampled).  set_knob("rank_eval_prefilter", 1): the same positions, hence the same metrics, through the certified counting
+        sweep on the matrix cores."""
         if sampled is not None:
             S, args, keep_s = self._sampled_call(users, feedback, lines, candidates, sampled, pos_ptr, pos_item, ban_ptr, ban_item)
             m = RankMetrics()

@@ -233,6 +233,11 @@ int64_t Engine::counter(int what) const {
     case 50: return n_rank_matrix_sections_; // of the sections under 39 / 49, those listed by the matrix sweep (knob rank_topn_scores = 1, section 6ah)
     case 51: return n_rank_certified_sections_;   // of the sections under 39 / 49, those certified under the prefilter (knob rank_topn_prefilter = 1, section 6ai)
     case 52: return n_rank_relisted_sections_;    // ... and those the pinned sweep listed again
+    case 53: return n_rank_eval_certified_;   // of the sections under 38, those certified under the counting prefilter (knob rank_eval_prefilter = 1, section 6aj)
+    case 54: return n_rank_eval_again_;       // ... and those the pinned sweep ranked again
+    case 55: return n_rank_eval_band_rows_;   // rows the counting sweep has swept (a section, or a slice of 28 of its positives) ...
+    case 56: return n_rank_eval_band_ids_;    // ... the band candidates it met on them, beyond the capacity included ...
+    case 57: return n_rank_eval_band_max_;    // ... and the longest band of one row: what rank_eval_prefilter_band has to hold
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -325,6 +330,8 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "window_per_target_max")) { check(value >= 1, "window_per_target_max must be positive"); wseq_per_target_max_ = (int)value; return 0; }
     if (!strcmp(name, "window_per_target")) { check(value >= 1, "window_per_target must be positive"); wseq_per_target_ = (int)value; return 0; }
     if (!strcmp(name, "rank_eval_budget")) { check(value >= 1, "rank_eval_budget must be positive"); rank_eval_budget_ = value; return 0; }
+    if (!strcmp(name, "rank_eval_prefilter")) { check(value == 0 || value == 1, "rank_eval_prefilter must be 0 or 1"); rank_eval_prefilter_ = (int)value; return 0; }
+    if (!strcmp(name, "rank_eval_prefilter_band")) { check(value >= 64 && value <= 65536, "rank_eval_prefilter_band must be between 64 and 65536"); rank_eval_band_ = (int)value; return 0; }
     if (!strcmp(name, "rank_cand_form")) { check(value >= 0 && value <= 2, "rank_cand_form must be 0 (measured choice), 1 (one lane per pair) or 2 (staged)"); rank_cand_form_ = value; return 0; }
     if (!strcmp(name, "pair_weight_form")) { check(value >= 0 && value <= 2, "pair_weight_form must be 0 (measured choice), 1 (search of the whole cdf) or 2 (guided search)"); pair_weight_form_ = value; return 0; }
     if (!strcmp(name, "pair_hard_form")) { check(value >= 0 && value <= 2, "pair_hard_form must be 0 (measured choice), 1 (one lane per candidate) or 2 (staged)"); pair_hard_form_ = value; return 0; }

@@ -509,7 +509,7 @@ class Engine {
     // lines != nullptr: a _lines call -- `user` is not read, the rows come from the lines (and fb_ptr, where the trainer is a user-group one)
     void rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                        const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                       int *nan_out, const RankLines *lines = nullptr);
+                       int *nan_out, const RankLines *lines = nullptr, bool prefilter_ok = true);
     void rank_geometry(int kind, long units, int top_n, const int64_t *pos_ptr, long *out);   // test probe (svdf_rank_geometry): host only
     void level_geometry(int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out);   // test probe (svdf_level_geometry): host only
     void level_config(DevParams &P, int pitch) const;   // the DevParams fields the launch choice of the level kernels reads
@@ -1012,6 +1012,12 @@ class Engine {
     long rank_eval_budget_ = 1L << 22;   // knob rank_eval_budget: positives + distinct bans + sections of one piece
     DevBuf<int> re_in_, re_cnt_;
     DevBuf<float> re_ps_;
+    int rank_eval_prefilter_ = 0;        // knob rank_eval_prefilter: 1 the pinned positions through the certified counting sweep on the matrix cores (section 6aj)
+    int rank_eval_band_ = 1024;          // knob rank_eval_prefilter_band: item ids a row's band list holds, 64 .. 65536
+    int64_t n_rank_eval_certified_ = 0;  // counter 53: of the sections under 38, those certified under rank_eval_prefilter
+    int64_t n_rank_eval_again_ = 0;      // counter 54: ... and those the pinned sweep ranked again
+    int64_t n_rank_eval_band_rows_ = 0, n_rank_eval_band_ids_ = 0, n_rank_eval_band_max_ = 0;   // counters 55 .. 57: rows swept, band candidates met, the longest band
+    DevBuf<int> re_band_;                // a piece's sorted order of the positives, then its rows' band lists
     int64_t n_rank_topn_sections_ = 0;   // counter 39: sections listed by svdf_rank_topn
     long rank_topn_budget_ = 1L << 25;   // knob rank_topn_budget: 64-bit keys of the list workspace of one piece (256 MiB)
     int rank_topn_scores_ = 0;           // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)

@@ -237,9 +237,13 @@ void rank_eval_geometry(const DevParams &P, long ntile, int *gy, long *items_per
     *gy = (int)((P.num_item + per - 1) / per);
 }
 
+void launch_rank_eval_pos(const DevParams &P, const RankEvalDev &D, hipStream_t st) {
+    hipLaunchKernelGGL(k_rank_eval_pos, dim3((unsigned)((D.npos + 255) / 256)), dim3(256), 0, st, P, D);
+}
+
 void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st) {
     if (D.npos <= 0) return;
-    hipLaunchKernelGGL(k_rank_eval_pos, dim3((unsigned)((D.npos + 255) / 256)), dim3(256), 0, st, P, D);
+    launch_rank_eval_pos(P, D, st);
     if (P.pitch <= 256) {
         const int ib = re_ib(P);
         int gy;

@@ -13,13 +13,12 @@
 // k_rank_topn_exact, one wave per section, in the merge's place: merges the section's gy lists to the M largest approximate keys, reads
 // the section's row u once (H_s and the checks on u, float64, one wave reduction), re-scores the at most M listed ids in the pinned order
 // and certifies the section or leaves it to the pinned sweep.  The re-scoring walks the candidates 64 at a time and K in chunks of 64
-// floats: the wave gathers the chunk of its 64 rows coalesced -- 16 lanes a row, four rows a load, all 16 loads of a lane in flight --
-// into LDS at a pitch of 17 float4s (16 consecutive lanes then touch every bank once, writing and reading), and lane l carries candidate
-// l's four chains across the chunks (re_row_chains / re_row_finish, the operations of re_row_score).  u is read from LDS as a broadcast.
+// floats through LDS: tx_pinned_scores (svdf_k_rankgather.h), which the band pass of the counting sweep shares (section 6aj).
 #include <algorithm>
 #include <cstdlib>
 
 #include "svdf_kernels.h"
+#include "svdf_k_rankgather.h"
 #include "svdf_k_rankkey.h"
 #include "svdf_k_rankscore.h"
 
@@ -113,18 +112,13 @@ void launch_rank_item_envelope(const DevParams &P, const float *item_rows, const
     else hipLaunchKernelGGL(k_rank_item_envelope<4>, grid, dim3(256), 0, st, P, item_rows, item_bias, envelope);
 }
 
-constexpr int TX_QC = 16;              // float4s of a K chunk (64 floats)
-constexpr int TX_LP = TX_QC + 1;       // float4s between two candidate rows of the stage
-constexpr int TX_LD = 64 * TX_QC / 64; // float4 loads of a lane per (64 candidates, chunk): 16, rows 4 t + lane / 16
-
 __global__ __launch_bounds__(64) void k_rank_topn_exact(const DevParams P, const RankTopnDev D) {
     __shared__ tn_key_t l_app[TN_SORT];   // the section's largest approximate keys, in rank order once merged
     __shared__ tn_key_t l_pin[TN_SORT];   // the pinned keys of the same candidates
     __shared__ float4 l_rows[64 * TX_LP];
     __shared__ float4 l_u[256];
     const int sec = blockIdx.x, lane = threadIdx.x, N = D.exact_n, M = D.top_n;
-    const int k = P.k, nq = P.pitch >> 2, nfull = k >> 2, ntail = k & 3;
-    const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const int k = P.k, nq = P.pitch >> 2;
     const float *ibase = re_item_base(P, D.item_rows), *ibias = re_item_bias(P, D.item_bias);
 
     // ---- the M largest approximate keys over the section's gy lists: k_rank_topn_merge's streaming with M for N
@@ -172,38 +166,12 @@ __global__ __launch_bounds__(64) void k_rank_topn_exact(const DevParams P, const
     tn_wave_sync();
 
     // ---- the pinned scores of the listed candidates, 64 at a time, K in chunks through LDS
-    const int grp = lane >> 4, gq = lane & 15;
-    const int nchunk = (nq + TX_QC - 1) / TX_QC;
     bool pnan = false;
     for (int r0 = 0; r0 < cnt; r0 += 64) {
         const int ci = r0 + lane;
-        const bool on = ci < cnt;
-        const int id = on ? tn_key_id(l_app[ci]) : 0;
-        const float bias = on ? ibias[id] : 0.0f;
-        const float4 *src[TX_LD];   // the rows this lane loads from: candidate r0 + 4 t + grp
-#pragma unroll
-        for (int t = 0; t < TX_LD; t++) {
-            const int row = r0 + 4 * t + grp;
-            src[t] = row < cnt ? re_item_row(ibase, P.pitch, tn_key_id(l_app[row])) : nullptr;
-        }
-        float4 a = zero4, pt = zero4, vt = zero4;
-        for (int c = 0; c < nchunk; c++) {
-            const int qb = c * TX_QC;
-            float4 g[TX_LD];
-#pragma unroll
-            for (int t = 0; t < TX_LD; t++) {
-                g[t] = zero4;
-                if (src[t] && qb + gq < nq) g[t] = src[t][qb + gq];
-            }
-            tn_wave_sync();   // the previous chunk has been read
-#pragma unroll
-            for (int t = 0; t < TX_LD; t++) l_rows[(4 * t + grp) * TX_LP + gq] = g[t];
-            tn_wave_sync();
-            const int left = nfull - qb, n = left < 0 ? 0 : (left < TX_QC ? left : TX_QC);
-            re_row_chains(a, l_u + qb, l_rows + lane * TX_LP, n);
-            if (ntail && left >= 0 && left < TX_QC) { pt = l_u[nfull]; vt = l_rows[lane * TX_LP + left]; }
-        }
-        const float s = re_row_finish(a, ntail, pt, vt, bias);
+        bool on;
+        int id;
+        const float s = tx_pinned_scores(P, ibase, ibias, l_u, l_rows, r0, cnt, lane, [&](int i) { return tn_key_id(l_app[i]); }, on, id);
         if (on) {
             pnan = pnan || s != s;
             l_pin[ci] = s == s ? tn_key(s, id) : 0ull;   // a NaN leaves the section to the pinned sweep, which flags it

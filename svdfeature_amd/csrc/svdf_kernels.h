@@ -305,6 +305,28 @@ constexpr int RANK_EVAL_WIDE_ROWS = 32768;   // rows of one launch of the wide s
 int rank_eval_tile_rows(const DevParams &P);
 void rank_eval_geometry(const DevParams &P, long ntile, int *gy, long *items_per_block);   // item ranges of the narrow sweep over ntile row tiles; wide: one
 void launch_rank_eval(const DevParams &P, const RankEvalDev &D, hipStream_t st);   // positives' scores, the counting sweep, the ban correction
+void launch_rank_eval_pos(const DevParams &P, const RankEvalDev &D, hipStream_t st);   // k_rank_eval_pos alone: the positives' pinned scores
+
+// ---- the same counts through the certified counting sweep on the matrix cores (knob rank_eval_prefilter, svdf_k_rankeval_mfma.hip, DESIGN.md
+// section 6aj).  The rows (row_sec, row_first, row_p0) are slices of at most RANK_EVAL_MX_POS positives in the SORTED order of their
+// section; tile_r0, ban_sec are not read.  64 rows a workgroup, tiles of RANK_TOPN_MATRIX_TILE items: rank_topn_geometry(.., matrix = 1).
+// 28 positives a row: the stage (54 KiB), the ban masks and [64][28] lo, hi plus the [64][29] histogram come to 77.8 KiB of LDS, two
+// workgroups per CU with room for the allocation granule; 30 would fit by 768 bytes, 32 would not.
+constexpr int RANK_EVAL_MX_POS = 28;
+struct RankEvalMxDev : RankEvalDev {
+    const int *ban_p0;               // [nsec + 1] banned ids of section s: ban_list[ban_p0[s] .. ban_p0[s + 1]), distinct, ascending (ban_item of the base)
+    const unsigned *envelope;        // [RANK_ENV_WORDS] of the item side of this call (launch_rank_item_envelope)
+    int gy;                          // item ranges
+    long items_per_block;
+    int *srt;                        // [npos] srt[sec_p0[s] + r]: the positive of section s with the r-th smallest (pinned score, id)
+    float *lo, *hi;                  // [npos] the certain-below / certain-above thresholds, in sorted order
+    int *sec_ok;                     // [nsec] conditions (a), (b) and no NaN among the positives' own scores
+    int band_cap;                    // knob rank_eval_prefilter_band: ids a row's band list holds
+    int *band_cursor;                // [nrow] band candidates the sweep met, zeroed by the caller; above band_cap: overflow
+    int *band_list;                  // [nrow][band_cap]
+    int *row_cert;                   // [nrow] written by k_rank_eval_band: 1 the row's counts are the pinned counts
+};
+void launch_rank_eval_mx(const DevParams &P, const RankEvalMxDev &D, hipStream_t st);   // k_rank_eval_pos, prep, the counting sweep, the band pass: four launches
 
 // ---- top-N item lists on the live model (svdf_k_ranktopn.hip): one piece of whole sections.  The sweep keeps, per
 // (section, item range y), a list of up to `cap` 64-bit keys (order-preserving score word << 32 | ~item id) in `list`; the merge selects the

@@ -94,10 +94,15 @@ void Engine::rank_eval_positions_lines(long S, const RankLines &U, const int64_t
 }
 
 // fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
-// lines != nullptr: from their USER lines, behind the feedback sum where there is one
+// lines != nullptr: from their USER lines, behind the feedback sum where there is one.
+// Under the knob rank_eval_prefilter (prefilter_ok: not the second run below) the pieces go through the counting sweep
+// on the matrix cores and the band pass (launch_rank_eval_mx); the sections the rule does not certify are gathered -- users, positives, the
+// validated ban lists, feedback lists, USER lines -- into contiguous copies, ranked once more by this function with the route off and
+// scattered to their places.  Either way every count is the pinned sweep's.
 void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                            const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                           int *nan_out, const RankLines *lines) {
+                           int *nan_out, const RankLines *lines, bool prefilter_ok) {
+    const bool mx = prefilter_ok && rank_eval_prefilter_ != 0;
     // ---- the lists, before any device work
     check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
     const long num_item = mp_.num_item;
@@ -133,6 +138,7 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
                 check(stamp[p] != 2 * s + 2, "rank_eval: a positive item is repeated inside a section");
                 stamp[p] = 2 * s + 2;
             }
+            if (mx) std::sort(ban_ids.begin() + (long)ban_first[(size_t)s], ban_ids.end());   // the matrix sweep walks a section's bans by ascending cursors
             ban_first[(size_t)s + 1] = (int64_t)ban_ids.size();
             ranked_out[s] = (int)(num_item - nban);
             nan_out[s] = 0;
@@ -146,13 +152,31 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
     const DevParams &P = params();
     const float *item_rows = nullptr, *item_bias = nullptr;
     if (lines) rank_live_items("rank_eval", &item_rows, &item_bias);   // once per call
-    const int tile_rows = rank_eval_tile_rows(P);
+    const int tile_rows = mx ? 64 : rank_eval_tile_rows(P), tile_pos = mx ? RANK_EVAL_MX_POS : RANK_EVAL_TILE_POS;
+    const int64_t row_cost = mx ? (int64_t)rank_eval_band_ + 2 : 0;   // a row's band list, cursor and `certified` word count into the piece budget
+    if (mx) {   // the envelope of the item side this call scores with, once, ahead of the first piece (section 6ai)
+        tn_env_.reserve(RANK_ENV_WORDS);
+        HIPCHECK(hipMemsetAsync(tn_env_.p, 0, RANK_ENV_WORDS * sizeof(unsigned), stream_));
+        launch_rank_item_envelope(P, item_rows, item_bias, tn_env_.p, stream_);
+        HIPCHECK(hipGetLastError());
+        n_launches_++;
+    }
+    std::vector<long> again;   // sections the rule did not certify
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
+        // a piece always takes its first section: one whose band lists alone exceed the budget (rows x capacity ids) is ranked by the
+        // pinned route, not given a workspace of that size
+        if (mx && row_cost * ((pos_ptr[s0 + 1] - pos_ptr[s0] + tile_pos - 1) / tile_pos) > (int64_t)rank_eval_budget_) {
+            n_rank_eval_sections_++; n_rank_eval_again_++;
+            if (fb_ptr) n_rank_fb_sections_++;
+            if (lines) n_rank_line_sections_++;
+            again.push_back(s0++);
+            continue;
+        }
         // ---- a piece of whole sections within the device budget
         const long s1 = rank_eval_piece(s0, S, rank_eval_budget_, [&](long s) {
             return (pos_ptr[s + 1] - pos_ptr[s]) + (ban_first[(size_t)s + 1] - ban_first[(size_t)s]) + 1 + (fb_ptr ? fb_ptr[s + 1] - fb_ptr[s] : 0) +
-                   (lines ? lines->ptr[s + 1] - lines->ptr[s] : 0);
+                   (lines ? lines->ptr[s + 1] - lines->ptr[s] : 0) + row_cost * ((pos_ptr[s + 1] - pos_ptr[s] + tile_pos - 1) / tile_pos);
         });
         const long nsec = s1 - s0;
         const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
@@ -161,12 +185,13 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         if (npos == 0) { s0 = s1; continue; }
         // ---- rows (a section, or a slice of its positives) and tiles of rows
         RankEvalRows rows;
-        rank_eval_rows(pos_ptr, s0, s1, tile_rows, RANK_EVAL_TILE_POS, rows);
+        rank_eval_rows(pos_ptr, s0, s1, tile_rows, tile_pos, rows);
         const std::vector<int> &row_sec = rows.row_sec, &row_first = rows.row_first, &row_p0 = rows.row_p0, &tile_r0 = rows.tile_r0;
         const int nrow = rows.nrow(), ntile = rows.ntile();
+        // (under the prefilter ban_p0 [nsec + 1] stands in ban_sec's place and the ids are ascending inside a section)
         // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         in.clear();
-        in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban +
+        in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban + (mx ? (size_t)nsec + 1 : 0) +
                    (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));   // one allocation: the parts below never move what is already there
         auto put =[&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         const size_t o_user = put((size_t)nsec), o_sp0 = put((size_t)nsec + 1), o_pitem = put((size_t)npos), o_psec = put((size_t)npos);
@@ -184,22 +209,27 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         std::copy(row_first.begin(), row_first.end(), in.begin() + (long)o_rfirst);
         std::copy(row_p0.begin(), row_p0.end(), in.begin() + (long)o_rp0);
         std::copy(tile_r0.begin(), tile_r0.end(), in.begin() + (long)o_tile);
-        const size_t o_bsec = put((size_t)nban), o_bitem = put((size_t)nban);
-        for (long s = s0; s < s1; s++)
+        const size_t o_bsec = put(mx ? (size_t)nsec + 1 : (size_t)nban), o_bitem = put((size_t)nban);
+        for (long s = s0; s < s1; s++) {
+            if (mx) in[o_bsec + (size_t)(s - s0)] = (int)(ban_first[(size_t)s] - ban_first[(size_t)s0]);
             for (int64_t j = ban_first[(size_t)s]; j < ban_first[(size_t)s + 1]; j++) {
-                in[o_bsec + (size_t)(j - ban_first[(size_t)s0])] = (int)(s - s0);
+                if (!mx) in[o_bsec + (size_t)(j - ban_first[(size_t)s0])] = (int)(s - s0);
                 in[o_bitem + (size_t)(j - ban_first[(size_t)s0])] = ban_ids[(size_t)j];
             }
+        }
+        if (mx) in[o_bsec + (size_t)nsec] = (int)nban;
         const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
         if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
         const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
         if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
         re_in_.upload(in.data(), in.size(), stream_);
-        const size_t ncnt = 3 * (size_t)npos + (size_t)nsec;
+        // the counts: greater | tied | before [npos] | nan_cnt [nsec]; under the prefilter also sec_ok [nsec] | row_cert [nrow] | band_cursor [nrow]
+        const size_t ncnt = 3 * (size_t)npos + (size_t)nsec + (mx ? (size_t)nsec + 2 * (size_t)nrow : 0);
         re_cnt_.reserve(ncnt);
-        re_ps_.reserve((size_t)npos);
+        re_ps_.reserve((mx ? 3 : 1) * (size_t)npos);
+        if (mx) re_band_.reserve((size_t)npos + (size_t)nrow * (size_t)rank_eval_band_);
         HIPCHECK(hipMemsetAsync(re_cnt_.p, 0, ncnt * sizeof(int), stream_));
-        RankEvalDev D;
+        RankEvalMxDev D;
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(re_in_.p + o_user);
         D.user_rows = nullptr;
@@ -236,15 +266,49 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         D.row_sec = re_in_.p + o_rsec; D.row_first = re_in_.p + o_rfirst; D.row_p0 = re_in_.p + o_rp0; D.tile_r0 = re_in_.p + o_tile;
         D.nban = (long)nban;
         D.ban_sec = re_in_.p + o_bsec; D.ban_item = re_in_.p + o_bitem;
-        launch_rank_eval(P, D, stream_);
-        HIPCHECK(hipGetLastError());
-        n_launches_ += 2 + (nban > 0 ? 1 : 0);
+        if (mx) {
+            D.ban_sec = nullptr; D.ban_p0 = re_in_.p + o_bsec;
+            D.envelope = tn_env_.p;
+            rank_topn_geometry(P, nrow, LONG_MAX, &D.gy, &D.items_per_block, 1);   // 64-row units, tiles of 128 items, about 2 048 workgroups
+            D.srt = re_band_.p; D.band_list = re_band_.p + npos; D.band_cap = rank_eval_band_;
+            D.lo = re_ps_.p + npos; D.hi = re_ps_.p + 2 * npos;
+            D.sec_ok = D.nan_cnt + nsec; D.row_cert = D.sec_ok + nsec; D.band_cursor = D.row_cert + nrow;
+            launch_rank_eval_mx(P, D, stream_);
+            HIPCHECK(hipGetLastError());
+            n_launches_ += 4;
+        } else {
+            launch_rank_eval(P, D, stream_);
+            HIPCHECK(hipGetLastError());
+            n_launches_ += 2 + (nban > 0 ? 1 : 0);
+        }
         back.resize(ncnt);
         HIPCHECK(hipMemcpyAsync(back.data(), re_cnt_.p, ncnt * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
+        if (mx)
+            for (size_t i = 0; i < (size_t)nrow; i++) {
+                const int64_t len = back[3 * (size_t)npos + 2 * (size_t)nsec + (size_t)nrow + i];
+                n_rank_eval_band_rows_++; n_rank_eval_band_ids_ += len;
+                n_rank_eval_band_max_ = std::max(n_rank_eval_band_max_, len);
+            }
+        size_t r = 0;   // the first row of section s
         for (long s = s0; s < s1; s++) {
             if (pos_ptr[s + 1] == pos_ptr[s]) continue;
             const bool bad = back[3 * (size_t)npos + (size_t)(s - s0)] != 0;
+            if (mx) {   // certified: (a), (b) by k_rank_eval_prep, (c) no NaN in the sweep, (d) and the pinned NaN check by every row's word
+                bool cert = !bad && back[3 * (size_t)npos + (size_t)nsec + (size_t)(s - s0)] != 0;
+                for (; r < (size_t)nrow && row_sec[r] == (int)(s - s0); r++) cert = cert && back[3 * (size_t)npos + 2 * (size_t)nsec + r] != 0;
+                n_rank_eval_sections_++;
+                if (fb_ptr) n_rank_fb_sections_++;
+                if (lines) n_rank_line_sections_++;
+                (cert ? n_rank_eval_certified_ : n_rank_eval_again_)++;
+                if (!cert) { again.push_back(s); continue; }
+                for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
+                    const size_t q = (size_t)(j - pos_ptr[s0]);
+                    position_out[j] = back[q] + back[2 * (size_t)npos + q];
+                    tied_out[j] = back[(size_t)npos + q];
+                }
+                continue;
+            }
             nan_out[s] = bad ? 1 : 0;
             for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
                 const size_t q = (size_t)(j - pos_ptr[s0]);
@@ -256,6 +320,46 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             if (lines) n_rank_line_sections_++;
         }
         s0 = s1;
+    }
+    if (again.empty()) return;
+    // ---- the sections left: contiguous copies of what they bring, this function with the route off, the results back to their places
+    const long A = (long)again.size();
+    std::vector<unsigned> a_user((size_t)A), a_pos, a_ban, fbi, uli;
+    std::vector<int64_t> a_pp((size_t)A + 1, 0), a_bp((size_t)A + 1, 0), fbp, ulp;
+    std::vector<float> fbv, ulv;
+    auto gather = [&](const int64_t *ptr, const unsigned *index, const float *value, std::vector<int64_t> &p, std::vector<unsigned> &ix, std::vector<float> &v) {
+        p.assign((size_t)A + 1, 0);
+        for (long a = 0; a < A; a++) {
+            const long s = again[(size_t)a];
+            ix.insert(ix.end(), index + ptr[s], index + ptr[s + 1]);
+            v.insert(v.end(), value + ptr[s], value + ptr[s + 1]);
+            p[(size_t)a + 1] = (int64_t)ix.size();
+        }
+    };
+    for (long a = 0; a < A; a++) {
+        const size_t s = (size_t)again[(size_t)a];
+        a_user[(size_t)a] = user[s];
+        a_pos.insert(a_pos.end(), pos_item + pos_ptr[s], pos_item + pos_ptr[s + 1]);
+        a_pp[(size_t)a + 1] = (int64_t)a_pos.size();
+        a_ban.insert(a_ban.end(), ban_ids.begin() + (long)ban_first[s], ban_ids.begin() + (long)ban_first[s + 1]);
+        a_bp[(size_t)a + 1] = (int64_t)a_ban.size();
+    }
+    if (fb_ptr) gather(fb_ptr, fb_index, fb_value, fbp, fbi, fbv);
+    RankLines UA;
+    if (lines) {
+        gather(lines->ptr, lines->index, lines->value, ulp, uli, ulv);
+        UA.ptr = ulp.data(); UA.index = uli.data(); UA.value = ulv.data();
+    }
+    std::vector<int> a_position(a_pos.size()), a_tied(a_pos.size()), a_ranked((size_t)A), a_nan((size_t)A);
+    const int64_t c38 = n_rank_eval_sections_, c40 = n_rank_fb_sections_, c41 = n_rank_line_sections_;   // each section counts once
+    rank_eval_run(A, a_user.data(), fb_ptr ? fbp.data() : nullptr, fbi.data(), fbv.data(), a_pp.data(), a_pos.data(), a_bp.data(), a_ban.data(),
+                  a_position.data(), a_tied.data(), a_ranked.data(), a_nan.data(), lines ? &UA : nullptr, false);
+    n_rank_eval_sections_ = c38; n_rank_fb_sections_ = c40; n_rank_line_sections_ = c41;
+    for (long a = 0; a < A; a++) {
+        const size_t s = (size_t)again[(size_t)a];
+        std::copy(a_position.begin() + (long)a_pp[(size_t)a], a_position.begin() + (long)a_pp[(size_t)a + 1], position_out + pos_ptr[s]);
+        std::copy(a_tied.begin() + (long)a_pp[(size_t)a], a_tied.begin() + (long)a_pp[(size_t)a + 1], tied_out + pos_ptr[s]);
+        nan_out[s] = a_nan[(size_t)a];
     }
 }
 
@@ -270,7 +374,22 @@ void Engine::rank_geometry(int kind, long units, int top_n, const int64_t *pos_p
     for (int i = 0; i < 8; i++) out[i] = 0;
     int gy = 0;
     long per = 0;
-    if (kind == 0) {
+    if (kind == 0 && rank_eval_prefilter_) {   // section 6aj: rows of RANK_EVAL_MX_POS positives in units of 64, the matrix rule over them
+        long nrow = units, piece = 0;
+        if (pos_ptr) {
+            check(pos_ptr[0] >= 0, "rank_geometry: pos_ptr must start at >= 0");
+            for (long s = 0; s < units; s++) check(pos_ptr[s + 1] >= pos_ptr[s], "rank_geometry: pos_ptr must not decrease");
+            const int64_t row_cost = (int64_t)rank_eval_band_ + 2;
+            piece = rank_eval_piece(0, units, rank_eval_budget_, [&](long s) {
+                return pos_ptr[s + 1] - pos_ptr[s] + 1 + row_cost * ((pos_ptr[s + 1] - pos_ptr[s] + RANK_EVAL_MX_POS - 1) / RANK_EVAL_MX_POS);
+            });
+            RankEvalRows rows;
+            rank_eval_rows(pos_ptr, 0, piece, 64, RANK_EVAL_MX_POS, rows);
+            nrow = rows.nrow();
+        }
+        if (nrow > 0) rank_topn_geometry(P, nrow, LONG_MAX, &gy, &per, 1);
+        out[2] = rank_eval_band_; out[3] = 64; out[4] = nrow; out[5] = (nrow + 63) / 64; out[6] = piece; out[7] = nrow > 0 ? 1 : 0;
+    } else if (kind == 0) {
         const int tile_rows = rank_eval_tile_rows(P);
         long ntile = units, nrow = 0, piece = 0;
         if (pos_ptr) {   // units sections without bans, feedback or lines: the first piece, its rows and tiles
