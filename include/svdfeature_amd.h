@@ -366,7 +366,7 @@ int svdf_synchronize(svdf_trainer *t);
  * 37 rank passes of a candidate file (svdf_dataset_from_rank_buffer_file) built as window sequences in HBM (they count under 7 too),
  * 38 sections ranked by svdf_rank_eval_positions, 39 sections listed by svdf_rank_topn,
  * 40 of the sections under 38 / 39, those ranked with a user row built from a feedback list (the _fb calls on user-group trainers),
- * 41 .. 43 see the _lines, _cand and _sampled calls below,
+ * 41 .. 43 see the _lines, _cand and _sampled calls below, 58 .. 60 the _cand calls' sets built on the device (knob rank_cand_build),
  * 44 / 45 passes built from a pair source (svdf_dataset_from_pair_source) without the pair columns leaving HBM / through
  * svdf_dataset_from_pairs' own builder on the columns copied back,
  * 46 of the passes under 44 / 45, the hard ones (svdf_dataset_from_pair_source_hard),
@@ -843,7 +843,20 @@ int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_pt
  * results; an allocation failure names the size.  No result depends on a knob (`rank_cand_form`: 0 the measured choice of the score kernel's
  * form, 1 one lane per pair, 2 staged in LDS).  With a feature_item table the whole catalogue is still prepared once per call.
  * Counter 42 counts the sections ranked over a candidate list; they count under 38 (positions: sections with positives) / 39 (top-N) too,
- * and under 40 / 41 as the twins' do.  The nine entry points above do not change. */
+ * and under 40 / 41 as the twins' do.  The nine entry points above do not change.
+ * THE SETS ON THE DEVICE (opt-in, no output changes by a bit).  Knob `rank_cand_build`: 0 (default) the host turns
+ * every list into its set as above; 1 the device does -- per piece one upload of the RAW lists (per section its candidates, then its
+ * positives), k_rank_cand_sets leaves every section's distinct ids in ascending order in place, the sets' sizes come back (4 bytes per
+ * section, one synchronize), the host makes ranked_out, the dense offsets and the tile table from them, k_rank_cand_pack moves the kept sets
+ * to their places and finds every positive's pair, and the kernels above run as they are.  Everything listed under REFUSED is still refused
+ * on the host, before any device work, in the same words and order; the pieces are cut on the raw counts (candidates + positives), which
+ * bound the sets.  Any other value is refused.  Knob `rank_cand_build_form` picks the kernel's form per section of n raw ids: 0 (default)
+ * the bitmap form (one bit per item in LDS; num_item <= 524 288) when n > 8 192 or 8 n >= ceil(num_item / 64), the host's own threshold,
+ * else the sort form (a bitonic network in LDS; n <= 8 192); 1 / 2 the sort / bitmap form wherever it is possible, else the other.  An
+ * empty section is the sort form's.  FALLBACK: a call that holds one section neither form can take (n > 8 192 on a catalogue of more than
+ * 524 288 items) takes the host build whole.  Counters 58 / 59: sections whose set the sort / bitmap form built (in a positions call the
+ * sections without positives too: ranked_out needs their sets); 60: calls under `rank_cand_build` = 1 that took the host build (58 / 59 do
+ * not move for them).  Under the knob a positions call without any positive still launches k_rank_cand_sets, for ranked_out. */
 int svdf_rank_eval_positions_cand(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ul_ptr, const unsigned *ul_index,
                                   const float *ul_value, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                                   const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int *position_out, int *tied_out,

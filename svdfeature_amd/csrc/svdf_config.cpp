@@ -238,6 +238,9 @@ int64_t Engine::counter(int what) const {
     case 55: return n_rank_eval_band_rows_;   // rows the counting sweep has swept (a section, or a slice of 28 of its positives) ...
     case 56: return n_rank_eval_band_ids_;    // ... the band candidates it met on them, beyond the capacity included ...
     case 57: return n_rank_eval_band_max_;    // ... and the longest band of one row: what rank_eval_prefilter_band has to hold
+    case 58: return n_rank_cand_sort_;        // sections of the _cand calls whose set the device built (knob rank_cand_build = 1, section 6ak): the sort form ...
+    case 59: return n_rank_cand_bitmap_;      // ... the bitmap form
+    case 60: return n_rank_cand_host_;        // _cand calls under that knob that took the host build: a section neither form can take
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -333,6 +336,8 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "rank_eval_prefilter")) { check(value == 0 || value == 1, "rank_eval_prefilter must be 0 or 1"); rank_eval_prefilter_ = (int)value; return 0; }
     if (!strcmp(name, "rank_eval_prefilter_band")) { check(value >= 64 && value <= 65536, "rank_eval_prefilter_band must be between 64 and 65536"); rank_eval_band_ = (int)value; return 0; }
     if (!strcmp(name, "rank_cand_form")) { check(value >= 0 && value <= 2, "rank_cand_form must be 0 (measured choice), 1 (one lane per pair) or 2 (staged)"); rank_cand_form_ = value; return 0; }
+    if (!strcmp(name, "rank_cand_build")) { check(value == 0 || value == 1, "rank_cand_build must be 0 (the host builds the sets) or 1 (the device)"); rank_cand_build_ = value; return 0; }
+    if (!strcmp(name, "rank_cand_build_form")) { check(value >= 0 && value <= 2, "rank_cand_build_form must be 0 (the rule), 1 (sort) or 2 (bitmap)"); rank_cand_build_form_ = value; return 0; }
     if (!strcmp(name, "pair_weight_form")) { check(value >= 0 && value <= 2, "pair_weight_form must be 0 (measured choice), 1 (search of the whole cdf) or 2 (guided search)"); pair_weight_form_ = value; return 0; }
     if (!strcmp(name, "pair_hard_form")) { check(value >= 0 && value <= 2, "pair_hard_form must be 0 (measured choice), 1 (one lane per candidate) or 2 (staged)"); pair_hard_form_ = value; return 0; }
     if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }

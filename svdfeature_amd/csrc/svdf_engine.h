@@ -1038,6 +1038,12 @@ class Engine {
     long rank_cand_form_ = 0;          // knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 the staged score kernel
     DevBuf<int> ca_in_, ca_out_;       // a _cand piece's upload (the lists, the tile table) and its results
     DevBuf<float> ca_score_;           // ... and the scores of its pairs
+    long rank_cand_build_ = 0;         // knob rank_cand_build: 0 the host builds the sections' sets, 1 the device (section 6ak)
+    long rank_cand_build_form_ = 0;    // knob rank_cand_build_form: 0 the rule of rank_cand_set_form, 1 / 2 the sort / bitmap form wherever possible
+    int64_t n_rank_cand_sort_ = 0;     // counter 58: sections whose set k_rank_cand_sets' sort form built
+    int64_t n_rank_cand_bitmap_ = 0;   // counter 59: ... its bitmap form
+    int64_t n_rank_cand_host_ = 0;     // counter 60: _cand calls that asked for the device build and took the host build
+    DevBuf<int> cb_in_;                // a piece's upload under the device build: the raw lists (the sets, once built), the rows' lists
     int64_t n_rank_negs_sections_ = 0; // counter 43: sections ranked against negatives drawn on the device
     DevBuf<int> ng_id_, ng_neg_;       // a sampled piece's cand_id, filled by k_rank_negs_draw, and its neg_out rows where they are asked for
     int64_t n_pair_src_hbm_ = 0;       // counter 44: passes built from a pair source without the pair columns leaving HBM

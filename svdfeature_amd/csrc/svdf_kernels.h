@@ -423,6 +423,41 @@ struct RankCandDev {
 int rank_cand_form(const DevParams &P, int form);   // the form a piece's score kernel takes: 1 or 2
 void launch_rank_cand(const DevParams &P, const RankCandDev &D, int form, hipStream_t st);   // the scores, then the count or the selection: two launches
 
+// ---- the sections' sets of those calls built on the device (svdf_k_rankcandsets.hip): one piece of whole sections.
+// Section s brings its raw ids -- its candidates, then its positives, repeats and all -- in raw[sec_r0[s] .. sec_r0[s + 1]); k_rank_cand_sets
+// leaves its distinct ids, ascending, at raw + sec_r0[s] and their number in set_size[s].  k_rank_cand_pack then copies the sets of the
+// sections the host kept (sec_q0) to their dense places in cand_id and finds every positive's pair.  Every id has been validated on the host.
+constexpr int RANK_CAND_SORT_MAX = 8192;        // raw ids the sort form takes: 32 KiB of LDS
+constexpr int RANK_CAND_BITMAP_WORDS = 16384;   // 32-bit words the bitmap form has: 64 KiB of LDS, catalogues of up to 524 288 items
+// The form that builds a section of n raw ids over num_item items: 1 sort, 2 bitmap, 0 neither (the call takes the host build).  force: knob
+// rank_cand_build_form -- 0 the host's threshold (mark a bitmap from num_item / 512 ids on), 1 / 2 that form wherever it is possible.  An
+// empty section is the sort form's, which touches nothing for it.
+static inline int rank_cand_set_form(int64_t n, int64_t num_item, int force) {
+    const bool sort = n <= RANK_CAND_SORT_MAX, bitmap = n > 0 && n < ((int64_t)1 << 29) && (num_item + 31) / 32 <= RANK_CAND_BITMAP_WORDS;
+    const bool first = force == 2 || (force == 0 && (n > RANK_CAND_SORT_MAX || 8 * n >= (num_item + 63) / 64));
+    if (bitmap && (first || !sort)) return 2;
+    return sort ? 1 : 0;
+}
+struct RankCandSetsDev {
+    int nsec;
+    unsigned num_item;
+    const int *sec_r0;          // [nsec + 1]
+    const int *sec_form;        // [nsec] rank_cand_set_form of the section: 1 or 2
+    int *raw;                   // [sec_r0[nsec]] in: the raw ids; out: the sets
+    int *set_size;              // [nsec]
+    int lds_words;              // the LDS the launch needs: the largest section's padded length or the bitmap's words
+    // k_rank_cand_pack: the kept sets to cand_id[sec_q0[s] .. sec_q0[s + 1]) (a section that is not kept has no pairs there); positive p of
+    // section s, p in [sec_p0[s], sec_p0[s + 1]), is the pair pos_at[p].  flag[0] becomes 1 when a positive is in no set (it never is)
+    const int *sec_q0 = nullptr;
+    int *cand_id = nullptr;
+    const int *sec_p0 = nullptr, *pos_id = nullptr;   // nullptr: a top-N call
+    int *pos_at = nullptr;
+    int *flag = nullptr;
+};
+int rank_cand_sets_lds_words(int64_t n, int64_t num_item, int form);   // the LDS words a section of that form needs
+void launch_rank_cand_sets(const RankCandSetsDev &D, hipStream_t st);   // one launch, a workgroup per section
+void launch_rank_cand_pack(const RankCandSetsDev &D, hipStream_t st);   // one launch, a wave per section
+
 // ---- the negatives of sampled-negative ranking, drawn on the device (svdf_k_ranknegs.hip): one piece of whole
 // sections.  A section with positives has npos + num_neg pairs in cand_id, [sec_q0[s], sec_q0[s + 1]): its positives, then its negatives in
 // draw order; a section without positives has none.  Every index is local to the piece and has been validated on the host.

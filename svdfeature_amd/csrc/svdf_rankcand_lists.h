@@ -146,6 +146,20 @@ static inline void rank_cand_build(long S, const int64_t *cand_ptr, const unsign
     }
 }
 
+// What rank_cand_build refuses about the positives, in its order (section by section: out of bound, then repeated), for the route that builds
+// the sets on the device: a sorted copy of each section's positives, which are few.
+static inline void rank_cand_check_positives(long S, const int64_t *pos_ptr, const unsigned *pos_item, long num_item) {
+    std::vector<unsigned> pos;
+    for (long s = 0; s < S; s++) {
+        if (pos_ptr[s + 1] <= pos_ptr[s]) continue;
+        pos.assign(pos_item + pos_ptr[s], pos_item + pos_ptr[s + 1]);
+        for (unsigned p : pos)
+            if ((long)p >= num_item) fail("sample item index exceed bound");
+        std::sort(pos.begin(), pos.end());
+        if (std::adjacent_find(pos.begin(), pos.end()) != pos.end()) fail("rank_eval: a positive item is repeated inside a section");
+    }
+}
+
 // The piece that starts at section s0: whole sections whose entries -- per section its pairs, one word, and what `extra` names (positives,
 // feedback and line entries; nullptr: none) -- stay within `budget`; a section larger than the budget is a piece of its own.  A piece holds
 // fewer than 2^29 pairs unless one section alone has more, which is refused.  Returns its end.

@@ -11,8 +11,11 @@ offsets rotated by a per-section base, as tools/rank_eval.py draws its lists), t
                  warm-up of each; medians with min .. max; every output of both routes is compared in the same run.
 --mode workload  (10 000 sections x 100 000 items): the new calls alone, the time per call and the bytes/s of the gather per call, counting
                  pairs x pitch x 4; beside them the full-catalogue call on the same sections (no bans) -- a DIFFERENT answer, for scale.
---mode kernel    the new top-10 call alone with the score kernel's form forced by --form (1 one lane per pair, 2 staged): the program to
-                 put behind `rocprofv3 --kernel-trace --stats --` in a run of its own.
+--mode build     (the workload's shape): the candidate calls with the host build of the sections' sets (knob rank_cand_build = 0) and with the
+                 device build (1; DESIGN.md section 6ak, --build-form its form knob) alternating --reps times after a warm-up of each; medians
+                 with min .. max, every output of both compared.  Results in profiles/r45_rank_cand_device.md.
+--mode kernel    the new top-10 call alone with the score kernel's form forced by --form (1 one lane per pair, 2 staged) and the sets built as --build says:
+                 the program to put behind `rocprofv3 --kernel-trace --stats --` in a run of its own.
 
 One invocation is one GPU step; run each under its own time limit and chain them:
 
@@ -33,7 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from rank_feedback import spread, timed      # noqa: E402
 
-SHAPES = {"same": (2000, 20000, 20000), "workload": (10000, 100000, 20000), "kernel": (10000, 100000, 20000)}   # sections, items, users
+SHAPES = {"same": (2000, 20000, 20000), "workload": (10000, 100000, 20000), "build": (10000, 100000, 20000), "kernel": (10000, 100000, 20000)}   # sections, items, users
 
 
 def lists(S, nu, ni, L, seed):
@@ -68,6 +71,8 @@ def main():
     ap.add_argument("--users", type=int, default=0)
     ap.add_argument("--train-pairs", type=int, default=200000)
     ap.add_argument("--form", type=int, default=0, help="knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 staged")
+    ap.add_argument("--build", type=int, default=0, help="knob rank_cand_build outside --mode build: 0 the host builds the sets, 1 the device")
+    ap.add_argument("--build-form", type=int, default=0, help="knob rank_cand_build_form: 0 the rule, 1 sort, 2 bitmap")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="file the JSON record is also written to")
     a = ap.parse_args()
@@ -86,7 +91,10 @@ def main():
         t.train_dataset(t.dataset_from_pairs(*cases.planted_pairs(a.train_pairs, nu, ni, seed=3)))
     t.synchronize()
     t.set_knob("rank_cand_form", a.form)
-    rec = {"mode": a.mode, "k": k, "pitch": pitch, "sections": S, "items": ni, "top_n": N, "form": a.form, "reps": a.reps, "lists": {}}
+    t.set_knob("rank_cand_build", a.build)
+    t.set_knob("rank_cand_build_form", a.build_form)
+    rec = {"mode": a.mode, "k": k, "pitch": pitch, "sections": S, "items": ni, "top_n": N, "form": a.form, "build": a.build,
+           "build_form": a.build_form, "reps": a.reps, "lists": {}}
     ok = True
     for L in [int(x) for x in a.list_len.split(",")]:
         users, pos_ptr, pos_item, cand_ptr, cand_item = lists(S, nu, ni, L, seed=11 + L)
@@ -97,6 +105,23 @@ def main():
         if a.mode == "kernel":
             new_top()
             e["topn_s"] = spread([timed(new_top)[1] for _ in range(a.reps)])
+        elif a.mode == "build":
+            def under(build, call):
+                t.set_knob("rank_cand_build", build)
+                return timed(call)
+            for name, call in (("positions", new_pos), ("topn", new_top)):
+                host, dev = under(0, call)[0], under(1, call)[0]           # warm-up of each
+                host_s, dev_s = [], []
+                for _ in range(a.reps):
+                    host, dt = under(0, call)
+                    host_s.append(dt)
+                    dev, dt = under(1, call)
+                    dev_s.append(dt)
+                hm, dm = spread(host_s), spread(dev_s)
+                e[name] = {"host_build_s": hm, "device_build_s": dm, "ratio": hm["median"] / dm["median"],
+                           "device_slower": bool(dm["median"] > hm["median"]), "equal": bool(same(dev, host))}
+                ok = ok and e[name]["equal"]
+            t.set_knob("rank_cand_build", a.build)
         elif a.mode == "workload":
             for name, call in (("positions", new_pos), ("topn", new_top), ("full_catalogue_positions", lambda: t.rank_positions(users, pos_ptr, pos_item)),
                                ("full_catalogue_topn", lambda: t.rank_topn(users, N))):
@@ -122,6 +147,7 @@ def main():
                 ok = ok and e[name]["equal"]
         rec["lists"][str(L)] = e
     rec["counter_42"] = t.counter(42)
+    rec["counters_58_59_60"] = [t.counter(c) for c in (58, 59, 60)]
     line = json.dumps(rec)
     print(line)
     if a.out:
@@ -129,7 +155,7 @@ def main():
         with open(a.out, "w") as f:
             f.write(line + "\n")
     if not ok:
-        sys.exit("rank_cand: the candidate call and the old call under complement bans disagree")
+        sys.exit("rank_cand: the two routes to the same answer disagree")
 
 
 if __name__ == "__main__":
