@@ -375,7 +375,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 49 sections listed by svdf_item_topn,
  * 50 of the sections under 39 / 49 (and 40 / 41), those listed by the sweep on the matrix cores (knob rank_topn_scores = 1),
  * 51 / 52 of the sections under 39 / 49 (and 40 / 41), those the certified prefilter listed (knob rank_topn_prefilter = 1) /
- * those it left to the pinned sweep, which listed them again; 50 does not move under the prefilter */
+ * those it left to the pinned sweep, which listed them again; 50 does not move under the prefilter,
+ * 61 of the sections under 39 / 49 (and 40 / 41, 50), those listed by the deep path (knob rank_topn_deep = 1 and top_n > 256) */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only, and the one marked (+), which replaces the pinned score of the top-N lists by one within a published bound.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -543,6 +544,21 @@ int64_t svdf_counter(svdf_trainer *t, int what);
  *                                ids, and sorting their pinned keys gives the pinned list.  A section that is not certified is listed again by
  *                                the pinned sweep; flags, counts, padding and order are 6x's either way.  Counters 51 / 52.  svdf_rank_geometry
  *                                (kind "topn") answers the matrix rule at top_n + slack
+ *     rank_topn_deep      0      1, OPT-IN: svdf_rank_topn, svdf_rank_topn_fb, svdf_rank_topn_lines and svdf_item_topn (dot and cosine) admit
+ *                                257 <= top_n <= 4096 -- DEEP lists (svdf_k_ranktopn_deep.hip; profiles/r46_rank_deep.md), in both
+ *                                scoring modes (rank_topn_scores 0 and 1).  Any other value is refused: "rank_topn_deep must be 0 or 1".  With
+ *                                0 every call, message and bit is what it was (top_n > 256 is refused in the words above).  With 1 a top_n
+ *                                outside 1 .. 4096 is refused: "top_n must be between 1 and 4096 (knob rank_topn_deep = 1); for longer lists rank the
+ *                                saved model with svdf_ranker_* and top_k"; top_n <= 256 takes the path it always took, bit for bit.  A deep
+ *                                call scores with the same loops (so a score has the bits it has in a short list: the first 256 entries of a
+ *                                deep pinned list are the top_n = 256 list); what differs is the selection: a list holds 2 top_n keys in whole
+ *                                128s (at most 8192) in the HBM workspace and is cut where it lies by a wave's radix select, and a workgroup
+ *                                per section selects over the section's lists and sorts the survivors.  Order, ties by ascending id, bans,
+ *                                counts, padding (-1 / 0.0f), the NaN flag, refusals about ids and pieces are section 6x's.  The larger lists
+ *                                mean fewer item ranges and more pieces under rank_topn_budget; svdf_rank_geometry (kind "topn") answers the deep
+ *                                capacity and geometry for top_n > 256 under the knob.  Counter 61.  NOT reached: the _cand top-N call (it
+ *                                keeps its 256), amd:gpus > 1; rank_topn_prefilter = 1 has no effect on a deep call (its M = top_n + slack <= 384
+ *                                is its design; the counters 51 / 52 do not move)
  *     rank_topn_prefilter_slack 32   keys the matrix sweep keeps beyond top_n under the prefilter, 1 .. 128 (else refused: "rank_topn_prefilter_slack
  *                                must be between 1 and 128"); changes how many sections the pinned sweep lists again, never an answer
  *     rank_eval_prefilter 0      1: the PINNED positions, count for count, through a counting sweep on the matrix cores and an exact band pass
@@ -701,7 +717,8 @@ int svdf_rank_eval(svdf_trainer *t, long num_section, const unsigned *user, cons
  *   score_out[s * top_n + r]  = that item's score, 0.0f beyond; score_out may be NULL
  *   nan_out[s]                = 1 when a RANKED candidate scores NaN: the section's whole list is -1 / 0.0f and count_out[s] = 0 (a banned
  *                               NaN row does not flag)
- * 1 <= top_n <= 256; a larger top_n is refused ("top_n must be between 1 and 256"): rank the saved model with svdf_ranker_* and top_k.
+ * 1 <= top_n <= 256; a larger top_n is refused ("top_n must be between 1 and 256"): rank the saved model with svdf_ranker_* and top_k --
+ * or set the knob rank_topn_deep, which admits top_n up to 4096.
  * Ids out of range are refused with the ranker's messages ("user feature index exceed bound", "sample item index exceed bound"); all
  * validation runs on the host before any device work.  num_section == 0 returns 0 and launches nothing.  A user may appear in several
  * sections.  The call runs on the trainer's stream behind whatever is queued and returns when the results are on the host; a stand-alone
@@ -1160,7 +1177,7 @@ int svdf_pair_order(long n, uint64_t order_seed, unsigned *sigma_out /* [n] */);
  * denormal; 3e38, -1, 2e19, whose sum of squares overflows: +-0 elements)
  * REFUSED on the host, before any device work and before "needs a GPU", each behind "item_topn: ":
  *   metric other than 0 / 1                   "item_topn: metric must be 0 (SVDF_ITEM_DOT) or 1 (SVDF_ITEM_COSINE)"
- *   top_n outside 1 .. 256                    "item_topn: top_n must be between 1 and 256"
+ *   top_n outside 1 .. 256                    "item_topn: top_n must be between 1 and 256" (knob rank_topn_deep = 1: .. 4096)
  *   an id >= num_item in item or ban_item     "sample item index exceed bound" (the ranker's message, as svdf_rank_topn gives it)
  *   ban_ptr not ascending                     "item_topn: ban_ptr must not decrease" ("... must start at >= 0", "ban_item is missing")
  *   NULL outputs with num_section > 0         "item_topn: bad arguments"

@@ -1176,7 +1176,9 @@ class Trainer:
         be None.  set_knob("rank_topn_scores", 1) scores on the matrix cores within a published bound instead of bit for bit (DESIGN.md 6ah;
         not the candidates call).  set_knob("rank_topn_prefilter", 1) keeps the pinned lists bit for bit and takes them through the matrix sweep:
         top_n + rank_topn_prefilter_slack (32) approximate winners per section are re-scored in the pinned order, a section the published rule
-        does not certify is listed again by the pinned sweep (counters 51 / 52; acts while rank_topn_scores is 0)."""
+        does not certify is listed again by the pinned sweep (counters 51 / 52; acts while rank_topn_scores is 0).
+        top_n is 1 .. 256; set_knob("rank_topn_deep", 1) admits up to 4096 here and in similar_items (counter 61; not the
+        candidates call, and the prefilter does not act on such a call)."""
         if candidates is not None:
             S, who_ptr, cand, keep_c = self._cand_call("rank_topn", users, feedback, lines, candidates, ban_ptr)
             top_n = int(top_n)

@@ -241,6 +241,7 @@ int64_t Engine::counter(int what) const {
     case 58: return n_rank_cand_sort_;        // sections of the _cand calls whose set the device built (knob rank_cand_build = 1, section 6ak): the sort form ...
     case 59: return n_rank_cand_bitmap_;      // ... the bitmap form
     case 60: return n_rank_cand_host_;        // _cand calls under that knob that took the host build: a section neither form can take
+    case 61: return n_rank_deep_sections_;    // of the sections under 39 / 49 (and 40 / 41, 50), those listed by the deep path (knob rank_topn_deep = 1, top_n > 256; section 6al)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }
@@ -342,6 +343,7 @@ int Engine::set_knob(const char *name, long value) {
     if (!strcmp(name, "pair_hard_form")) { check(value >= 0 && value <= 2, "pair_hard_form must be 0 (measured choice), 1 (one lane per candidate) or 2 (staged)"); pair_hard_form_ = value; return 0; }
     if (!strcmp(name, "rank_topn_budget")) { check(value >= 1, "rank_topn_budget must be positive"); rank_topn_budget_ = value; return 0; }
     if (!strcmp(name, "rank_topn_prefilter")) { check(value == 0 || value == 1, "rank_topn_prefilter must be 0 or 1"); rank_topn_prefilter_ = (int)value; return 0; }
+    if (!strcmp(name, "rank_topn_deep")) { check(value == 0 || value == 1, "rank_topn_deep must be 0 or 1"); rank_topn_deep_ = (int)value; return 0; }
     if (!strcmp(name, "rank_topn_prefilter_slack")) { check(value >= 1 && value <= 128, "rank_topn_prefilter_slack must be between 1 and 128"); rank_topn_slack_ = (int)value; return 0; }
     if (!strcmp(name, "rank_topn_scores")) { check(value == 0 || value == 1, "rank_topn_scores must be 0 (pinned) or 1 (matrix)"); rank_topn_scores_ = (int)value; return 0; }
     if (!strcmp(name, "window_slots")) { window_slots_ = value != 0; return 0; }

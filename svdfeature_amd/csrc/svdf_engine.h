@@ -489,6 +489,7 @@ class Engine {
     // top-N item lists on the live model (svdf_ranktopn.cpp, svdf_k_ranktopn.hip)
     void rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                    int *count_out, int *nan_out);
+    void rank_topn_admit(const char *who, int top_n, const char *tail);   // top_n of a top-N call: 1 .. 256, or .. 4096 under the knob rank_topn_deep
     void rank_live_refusals(const char *who, bool svdpp_ok = false, bool tables_ok = false);   // the configurations the batch ranking calls do not cover
     // the same calls for sections with feedback lists: user-group (SVD++) trainers (svdf_k_rankrows.hip)
     void rank_eval_positions_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
@@ -1023,6 +1024,8 @@ class Engine {
     int rank_topn_scores_ = 0;           // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
     int64_t n_rank_matrix_sections_ = 0; // counter 50: of the sections under 39 / 49, those listed by the matrix sweep
     int rank_topn_prefilter_ = 0;        // knob rank_topn_prefilter: 1 the pinned lists through the certified matrix-core prefilter (section 6ai); acts while rank_topn_scores is 0
+    int rank_topn_deep_ = 0;             // knob rank_topn_deep: 1 admits top_n 257 .. 4096 to the top-N calls (section 6al); top_n <= 256 is untouched
+    int64_t n_rank_deep_sections_ = 0;   // counter 61: of the sections under 39 / 49, those listed by the deep path
     int rank_topn_slack_ = 32;           // knob rank_topn_prefilter_slack: keys the matrix sweep keeps beyond top_n under the prefilter, 1 .. 128
     int64_t n_rank_certified_sections_ = 0;   // counter 51: of the sections under 39 / 49, those certified under the prefilter
     int64_t n_rank_relisted_sections_ = 0;    // counter 52: ... and those the pinned sweep listed again

@@ -17,7 +17,7 @@ void Engine::item_topn(long S, const unsigned *item, int metric, const int64_t *
         fail("item_topn: a feature_item side table changes an item's effective row (its children's rows are added) and is not covered");
     rank_live_refusals("item_topn", true, true);
     check(metric == SVDF_ITEM_DOT || metric == SVDF_ITEM_COSINE, "item_topn: metric must be 0 (SVDF_ITEM_DOT) or 1 (SVDF_ITEM_COSINE)");
-    check(top_n >= 1 && top_n <= RANK_TOPN_MAX, "item_topn: top_n must be between 1 and 256");
+    rank_topn_admit("item_topn", top_n, "");
     // ---- the lists, before any device work
     check(S == 0 || (item_out && count_out && nan_out), "item_topn: bad arguments");
     RankTopnLists L;

@@ -10,6 +10,7 @@
 // its N largest by a bitonic sort in a wave-private LDS buffer, which raises the threshold.  The merge kernel selects over a section's lists.
 // Banned candidates are excluded in the sweep.  Integer atomics only (the NaN count).
 #include <algorithm>
+#include <cstdlib>
 
 #include "svdf_kernels.h"
 #include "svdf_k_rankkey.h"
@@ -24,16 +25,21 @@ constexpr int TN_SB = 4;                     // sections a lane scores at once (
 // What the wave that owns a list does with one step's scores (IB candidates per lane): the keys of ranked candidates that beat the
 // threshold are appended through a ballot prefix; a list without room for a whole step is first cut to its top_n largest.  `list` is the
 // (section, item range)'s slice of the workspace, *cnt_p and *thr_p its state in LDS, `scratch` the wave's sort buffer.  cap >= top_n + 64 IB.
-template <int IB>
+// DEEP (section 6al): the list is cut where it lies by tn_select_keep, `scratch` the wave's histogram, and what is kept is not in order.
+template <int IB, bool DEEP = false>
 __device__ __forceinline__ void tn_select(const float (&s)[IB], const bool (&on)[IB], const int (&cid)[IB], tn_key_t *list, int *cnt_p, tn_key_t *thr_p,
                                           tn_key_t *scratch, int top_n, int cap, int lane) {
     int cnt = __builtin_amdgcn_readfirstlane(*cnt_p);
     tn_key_t thr = *thr_p;
     if (cnt + 64 * IB > cap) {   // wave-uniform
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the wave's own appends, by other lanes, are read back below
-        for (int i = lane; i < cnt; i += 64) scratch[i] = list[i];
-        cnt = tn_sort_keep(scratch, cnt, top_n, lane, thr);
-        for (int i = lane; i < cnt; i += 64) list[i] = scratch[i];
+        if constexpr (DEEP) {
+            cnt = tn_select_keep(list, cnt, top_n, lane, reinterpret_cast<int *>(scratch), thr);
+        } else {
+            for (int i = lane; i < cnt; i += 64) scratch[i] = list[i];
+            cnt = tn_sort_keep(scratch, cnt, top_n, lane, thr);
+            for (int i = lane; i < cnt; i += 64) list[i] = scratch[i];
+        }
         if (lane == 0) *thr_p = thr;
         tn_wave_sync();
     }
@@ -63,16 +69,17 @@ __device__ __forceinline__ int tn_lower_bound(const int *__restrict__ ban, int b
 // + 63 and the item range blockIdx.y; wave w scores sections 16 w .. 16 w + 15, four at a time, against 64 IB candidates (lane l owns
 // candidates l, l + 64, ..).  User rows stay in LDS; each tile of item rows is staged once, chunk-major.  Thread t < 64 walks the sorted ban
 // list of section t with a cursor in a register and sets, per item tile, the section's bits of a [64][64 IB] mask; the scoring loop is
-// mask-free.  The list state of a section (count, threshold) belongs to the wave that owns the section.
-template <int IB>
+// mask-free.  The list state of a section (count, threshold) belongs to the wave that owns the section.  DEEP: a wave's scratch is a
+// histogram of TN_HIST bins, not a sort buffer -- 12 KiB of LDS less per workgroup.
+template <int IB, bool DEEP = false>
 __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, const RankTopnDev D) {
-    constexpr int TI = 64 * IB;
+    constexpr int TI = 64 * IB, SCR = tn_scratch_keys(DEEP);
     extern __shared__ float4 tn_lds[];
     const int nch = P.pitch >> 2, nfull = P.k >> 2, ntail = P.k & 3;
     float4 *l_item = tn_lds;                                   // [nch][TI + 1]
     float4 *l_user = l_item + (size_t)nch * (TI + 1);          // [TN_TS][nch]
-    tn_key_t *l_scr = reinterpret_cast<tn_key_t *>(l_user + (size_t)TN_TS * nch);   // [4][TN_SORT]
-    tn_key_t *l_thr = l_scr + 4 * TN_SORT;                     // [TN_TS]
+    tn_key_t *l_scr = reinterpret_cast<tn_key_t *>(l_user + (size_t)TN_TS * nch);   // [4][SCR]
+    tn_key_t *l_thr = l_scr + 4 * SCR;                         // [TN_TS]
     tn_key_t *l_mask = l_thr + TN_TS;                          // [TN_TS][IB]
     int *l_cnt = reinterpret_cast<int *>(l_mask + TN_TS * IB); // [TN_TS]
     int *l_nan = l_cnt + TN_TS;                                // [TN_TS]
@@ -186,8 +193,8 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
 #pragma unroll
                     for (int ib = 0; ib < IB; ib++) nn += __popcll(__ballot(ranked[ib] && s[ib] != s[ib]));
                     if (lane == 0 && nn) l_nan[sec] += nn;   // the section's state belongs to this wave alone
-                    tn_select<IB>(s, ranked, cid, D.list + ((size_t)(sec_base + sec) * D.gy + blockIdx.y) * D.cap, &l_cnt[sec], &l_thr[sec],
-                                  l_scr + wave * TN_SORT, D.top_n, D.cap, lane);
+                    tn_select<IB, DEEP>(s, ranked, cid, D.list + ((size_t)(sec_base + sec) * D.gy + blockIdx.y) * D.cap, &l_cnt[sec], &l_thr[sec],
+                                        l_scr + wave * SCR, D.top_n, D.cap, lane);
                 }
             }
         }
@@ -202,8 +209,9 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep(const DevParams P, cons
 // The same selection for wide rows (num_factor 257 .. 1024), which no LDS tile holds 64 of: one wave per (section, item range) walks its
 // range 64 candidates at a time, both factor rows read from HBM / L2 where they lie; a ban is looked up in the section's sorted list.
 // Right, not fast.
+template <bool DEEP = false>
 __global__ __launch_bounds__(64) void k_rank_topn_sweep_wide(const DevParams P, const RankTopnDev D) {
-    __shared__ tn_key_t l_scr[TN_SORT];
+    __shared__ tn_key_t l_scr[tn_scratch_keys(DEEP)];
     __shared__ tn_key_t l_thr;
     __shared__ int l_cnt;
     const int sec = blockIdx.x, lane = threadIdx.x;
@@ -227,7 +235,7 @@ __global__ __launch_bounds__(64) void k_rank_topn_sweep_wide(const DevParams P, 
         float s[1] = {0.0f};
         if (ranked[0]) s[0] = re_row_score(P.k, urow, re_item_row(ibase, P.pitch, c), ibias[c]);
         nn += __popcll(__ballot(ranked[0] && s[0] != s[0]));
-        tn_select<1>(s, ranked, cid, list, &l_cnt, &l_thr, l_scr, D.top_n, D.cap, lane);
+        tn_select<1, DEEP>(s, ranked, cid, list, &l_cnt, &l_thr, l_scr, D.top_n, D.cap, lane);
     }
     if (lane == 0) {
         D.list_cnt[(size_t)sec * D.gy + blockIdx.y] = l_cnt;
@@ -267,9 +275,9 @@ __global__ __launch_bounds__(64) void k_rank_topn_merge(const RankTopnDev D) {
     if (lane == 0) D.count_out[sec] = cnt;
 }
 
-static size_t tn_lds_bytes(int pitch, int ib) {
+static size_t tn_lds_bytes(int pitch, int ib, bool deep) {
     const size_t nch = (size_t)pitch >> 2;
-    return 16 * (nch * (64 * (size_t)ib + 1) + (size_t)TN_TS * nch) + 8 * (4 * (size_t)TN_SORT + (size_t)TN_TS + (size_t)TN_TS * ib) + 4 * 2 * (size_t)TN_TS;
+    return 16 * (nch * (64 * (size_t)ib + 1) + (size_t)TN_TS * nch) + 8 * (4 * (size_t)tn_scratch_keys(deep) + (size_t)TN_TS + (size_t)TN_TS * ib) + 4 * 2 * (size_t)TN_TS;
 }
 static int tn_ib(const DevParams &P) { return P.pitch <= 128 ? 2 : 1; }   // candidates per lane and step; the wide sweep takes 1
 // sections of one workgroup (narrow, matrix) or wave (wide)
@@ -284,6 +292,9 @@ int rank_topn_cap(const DevParams &P, int top_n, int matrix) {
     return std::min(std::max(cap, top_n + ti), TN_SORT);
 }
 
+// a deep list: top_n kept keys and as many appends between two cuts, in whole 128s -- at least a step more than top_n, as top_n > 256
+int rank_topn_deep_cap(int top_n) { return (2 * top_n + 127) / 128 * 128; }
+
 void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block, int matrix) {
     const long ti = tn_item_tile(P, matrix), ntile_i = (P.num_item + ti - 1) / ti;
     // narrow, matrix: about 2048 workgroups in all, at least 8 item tiles per workgroup where the items allow (the user rows are staged per
@@ -297,6 +308,30 @@ void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, 
     *gy = (int)((P.num_item + per - 1) / per);
 }
 
+// The deep forms of the pinned sweeps and of the matrix sweep, then k_rank_topn_merge_deep.  A list takes top_n kept keys and one step's
+// appends, and no more than the merge and the workspace were sized for: rank_topn_deep_cap says so; another capacity would write past a list.
+static void launch_rank_topn_deep(const DevParams &P, const RankTopnDev &D, hipStream_t st) {
+    const int step = (int)tn_item_tile(P, D.matrix);
+    if (D.top_n <= RANK_TOPN_MAX || D.top_n > RANK_TOPN_DEEP_MAX || D.cap < D.top_n + step || D.cap > RANK_TOPN_DEEP_MAX_CAP || D.exact_n > 0) abort();
+    if (D.matrix) {
+        launch_rank_topn_sweep_mfma(P, D, st);
+    } else if (P.pitch <= 256) {
+        const int ib = tn_ib(P);
+        const size_t lds = tn_lds_bytes(P.pitch, ib, true);
+        const dim3 grid((unsigned)((D.nsec + TN_TS - 1) / TN_TS), (unsigned)D.gy);
+        if (ib == 2) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_topn_sweep<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((k_rank_topn_sweep<2, true>), grid, dim3(256), lds, st, P, D);
+        } else {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_topn_sweep<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((k_rank_topn_sweep<1, true>), grid, dim3(256), lds, st, P, D);
+        }
+    } else {
+        hipLaunchKernelGGL(k_rank_topn_sweep_wide<true>, dim3((unsigned)D.nsec, (unsigned)D.gy), dim3(64), 0, st, P, D);
+    }
+    launch_rank_topn_merge_deep(D, st);
+}
+
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) {
     if (D.nsec <= 0) return;
     if (D.exact_n > 0) {   // the certified prefilter (section 6ai): the matrix sweep with top_n + slack keys, then the pinned re-score
@@ -304,11 +339,15 @@ void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) 
         launch_rank_topn_exact(P, D, st);
         return;
     }
+    if (D.deep) {   // section 6al: the same three sweeps with the cut in place, and the merge of a workgroup per section
+        launch_rank_topn_deep(P, D, st);
+        return;
+    }
     if (D.matrix) {
         launch_rank_topn_sweep_mfma(P, D, st);
     } else if (P.pitch <= 256) {
         const int ib = tn_ib(P);
-        const size_t lds = tn_lds_bytes(P.pitch, ib);
+        const size_t lds = tn_lds_bytes(P.pitch, ib, false);
         const dim3 grid((unsigned)((D.nsec + rank_topn_tile_rows(P) - 1) / rank_topn_tile_rows(P)), (unsigned)D.gy);
         if (ib == 2) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rank_topn_sweep<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -318,7 +357,7 @@ void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st) 
             hipLaunchKernelGGL(k_rank_topn_sweep<1>, grid, dim3(256), lds, st, P, D);
         }
     } else {
-        hipLaunchKernelGGL(k_rank_topn_sweep_wide, dim3((unsigned)D.nsec, (unsigned)D.gy), dim3(64), 0, st, P, D);
+        hipLaunchKernelGGL(k_rank_topn_sweep_wide<false>, dim3((unsigned)D.nsec, (unsigned)D.gy), dim3(64), 0, st, P, D);
     }
     hipLaunchKernelGGL(k_rank_topn_merge, dim3((unsigned)D.nsec), dim3(64), 0, st, D);
 }

@@ -13,9 +13,11 @@
 
 namespace svdf {
 
+// DEEP (section 6al): a list that cannot take a tile is cut where it lies by tn_select_keep; a wave's scratch is its histogram.
+template <bool DEEP>
 __global__ __launch_bounds__(256) void k_rank_topn_sweep_mfma(const DevParams P, const RankTopnDev D) {
     __shared__ MxLds L;
-    __shared__ tn_key_t l_scr[4][TN_SORT];
+    __shared__ tn_key_t l_scr[4][tn_scratch_keys(DEEP)];
     __shared__ tn_key_t l_thr[MX_TS];
     __shared__ int l_cnt[MX_TS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -54,9 +56,13 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep_mfma(const DevParams P,
                     tn_key_t thr = l_thr[sec];
                     if (cnt + MX_TI > D.cap) {   // no room for a whole step: cut to the top_n largest, which raises the threshold
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the wave's own appends, by other lanes, are read back
-                        for (int i = lane; i < cnt; i += 64) scratch[i] = list[i];
-                        cnt = tn_sort_keep(scratch, cnt, D.top_n, lane, thr);
-                        for (int i = lane; i < cnt; i += 64) list[i] = scratch[i];
+                        if constexpr (DEEP) {
+                            cnt = tn_select_keep(list, cnt, D.top_n, lane, reinterpret_cast<int *>(scratch), thr);
+                        } else {
+                            for (int i = lane; i < cnt; i += 64) scratch[i] = list[i];
+                            cnt = tn_sort_keep(scratch, cnt, D.top_n, lane, thr);
+                            for (int i = lane; i < cnt; i += 64) list[i] = scratch[i];
+                        }
                         if (lane == 0) l_thr[sec] = thr;
                         tn_wave_sync();
                     }
@@ -83,9 +89,11 @@ __global__ __launch_bounds__(256) void k_rank_topn_sweep_mfma(const DevParams P,
 void launch_rank_topn_sweep_mfma(const DevParams &P, const RankTopnDev &D, hipStream_t st) {
     // a list takes top_n kept keys and one tile's appends, and a wave's sort buffer a whole list: rank_topn_cap(.., matrix = 1) says so;
     // a launch with another capacity would write past a list
-    if (D.nsec <= 0 || D.cap < D.top_n + MX_TI || D.cap > TN_SORT) abort();
+    // (a deep list is cut in place, so only the workspace bounds it: rank_topn_deep_cap)
+    if (D.nsec <= 0 || D.cap < D.top_n + MX_TI || D.cap > (D.deep ? RANK_TOPN_DEEP_MAX_CAP : TN_SORT)) abort();
     const dim3 grid((unsigned)((D.nsec + MX_TS - 1) / MX_TS), (unsigned)D.gy);
-    hipLaunchKernelGGL(k_rank_topn_sweep_mfma, grid, dim3(256), 0, st, P, D);
+    if (D.deep) hipLaunchKernelGGL(k_rank_topn_sweep_mfma<true>, grid, dim3(256), 0, st, P, D);
+    else hipLaunchKernelGGL(k_rank_topn_sweep_mfma<false>, grid, dim3(256), 0, st, P, D);
 }
 
 }  // namespace svdf

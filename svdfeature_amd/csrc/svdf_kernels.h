@@ -333,6 +333,8 @@ void launch_rank_eval_mx(const DevParams &P, const RankEvalMxDev &D, hipStream_t
 // top_n largest keys of a section's gy lists.  Every index is local to the piece and has been validated on the host.
 constexpr int RANK_TOPN_MAX = 256;       // largest top_n
 constexpr int RANK_TOPN_MAX_CAP = 512;   // keys one wave sorts in LDS: the largest list capacity
+constexpr int RANK_TOPN_DEEP_MAX = 4096;       // largest top_n of a deep call (knob rank_topn_deep)
+constexpr int RANK_TOPN_DEEP_MAX_CAP = 8192;   // ... and the largest capacity of its lists, which are cut in place (tn_select_keep)
 constexpr int RANK_TOPN_MATRIX_TILE = 128;   // items of one tile of the matrix sweep (svdf_k_ranktopn_mfma.hip), at every width
 struct RankTopnDev {
     int nsec;                        // sections of the piece
@@ -350,6 +352,7 @@ struct RankTopnDev {
     float *score_out;                // [nsec][top_n] their scores, 0 beyond count_out
     int *count_out;                  // [nsec] entries listed; 0 for a section with a NaN among its ranked candidates
     int matrix = 0;                  // knob rank_topn_scores: 0 the pinned sweeps, 1 the sweep on the matrix cores (section 6ah)
+    int deep = 0;                    // 1: top_n 257 .. RANK_TOPN_DEEP_MAX, cap = rank_topn_deep_cap: the deep sweeps and k_rank_topn_merge_deep (section 6al)
     // the certified prefilter (knob rank_topn_prefilter, svdf_k_ranktopn_exact.hip), exact_n > 0: the matrix sweep keeps
     // top_n = exact_n + slack keys per list, and k_rank_topn_exact writes item_out / score_out as [nsec][exact_n]
     int exact_n = 0;                 // the caller's top_n
@@ -364,10 +367,12 @@ void launch_rank_topn_exact(const DevParams &P, const RankTopnDev &D, hipStream_
 // `matrix` is the knob rank_topn_scores; with 0 the four answer for the pinned sweeps, with 1 for the matrix sweep (64 sections per
 // workgroup and tiles of RANK_TOPN_MATRIX_TILE items at every width)
 int rank_topn_cap(const DevParams &P, int top_n, int matrix = 0);   // capacity of one list, <= RANK_TOPN_MAX_CAP
+int rank_topn_deep_cap(int top_n);   // ... of a deep call (256 < top_n <= RANK_TOPN_DEEP_MAX) at every width and in both modes: 2 top_n in whole 128s
 int rank_topn_tile_rows(const DevParams &P, int matrix = 0);        // sections that share one pass over an item range: 64 (narrow, matrix) or 1 (wide)
 void rank_topn_geometry(const DevParams &P, long nsec, long max_lists, int *gy, long *items_per_block, int matrix = 0);   // at most max_lists / nsec (>= 1) item ranges
 void launch_rank_topn(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // the selecting sweep (by D.matrix), then the merge -- D.exact_n > 0: the matrix sweep, then k_rank_topn_exact: two launches
-void launch_rank_topn_sweep_mfma(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // svdf_k_ranktopn_mfma.hip: the matrix sweep alone
+void launch_rank_topn_sweep_mfma(const DevParams &P, const RankTopnDev &D, hipStream_t st);   // svdf_k_ranktopn_mfma.hip: the matrix sweep alone (by D.deep)
+void launch_rank_topn_merge_deep(const RankTopnDev &D, hipStream_t st);   // svdf_k_ranktopn_deep.hip: the merge of a deep call
 
 // ---- the effective user rows of a piece's sections on a user-group trainer (svdf_k_rankrows.hip):
 // rows[s] = (0 + sum_j W_ufeedback[fb_index[j]] * fb_value[j], j in [fb_p0[s], fb_p0[s + 1]) in list order) + W_user[sec_user[s]] * 1, in the

@@ -404,10 +404,11 @@ void Engine::rank_geometry(int kind, long units, int top_n, const int64_t *pos_p
         out[3] = tile_rows; out[4] = nrow; out[5] = ntile; out[6] = piece;
         out[7] = P.pitch <= 256 ? (ntile > 0 ? 1 : 0) : (nrow + RANK_EVAL_WIDE_ROWS - 1) / RANK_EVAL_WIDE_ROWS;   // launches of the sweep
     } else {
-        check(top_n >= 1 && top_n <= RANK_TOPN_MAX, "rank_geometry: top_n must be between 1 and 256");
-        // the prefilter (section 6ai) acts while rank_topn_scores is 0: the matrix rule at top_n + slack
-        const bool prefilter = rank_topn_prefilter_ && !rank_topn_scores_;
-        const int matrix = rank_topn_scores_ || prefilter, cap = rank_topn_cap(P, prefilter ? top_n + rank_topn_slack_ : top_n, matrix);
+        rank_topn_admit("rank_geometry", top_n, "");
+        // the prefilter (section 6ai) acts while rank_topn_scores is 0, and on no deep call (section 6al): the matrix rule at top_n + slack
+        const bool deep = top_n > RANK_TOPN_MAX, prefilter = rank_topn_prefilter_ && !rank_topn_scores_ && !deep;
+        const int matrix = rank_topn_scores_ || prefilter;
+        const int cap = deep ? rank_topn_deep_cap(top_n) : rank_topn_cap(P, prefilter ? top_n + rank_topn_slack_ : top_n, matrix);
         const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
         const std::vector<int64_t> no_bans((size_t)units + 1, 0);
         const long piece = rank_topn_piece(0, units, max_lists, no_bans);   // units sections without bans: the first piece

@@ -43,6 +43,14 @@ bool Engine::rank_live_fb_refusals(const char *who, bool has_lists, bool tables_
     return true;
 }
 
+// top_n of a top-N call: 1 .. 256, and up to 4096 under the knob rank_topn_deep; `tail` ends the message of today's bound
+void Engine::rank_topn_admit(const char *who, int top_n, const char *tail) {
+    const std::string w(who);
+    if (!rank_topn_deep_ && !(top_n >= 1 && top_n <= RANK_TOPN_MAX)) fail(w + ": top_n must be between 1 and 256" + tail);
+    if (!(top_n >= 1 && top_n <= RANK_TOPN_DEEP_MAX))
+        fail(w + ": top_n must be between 1 and 4096 (knob rank_topn_deep = 1); for longer lists rank the saved model with svdf_ranker_* and top_k");
+}
+
 void Engine::rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                        int *count_out, int *nan_out) {
     rank_live_refusals("rank_topn");
@@ -93,8 +101,7 @@ void Engine::rank_live_items(const char *who, const float **item_rows, const flo
 // lines != nullptr: from their USER lines, behind the feedback sum where there is one
 void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                            const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines) {
-    check(top_n >= 1 && top_n <= RANK_TOPN_MAX,
-          "rank_topn: top_n must be between 1 and 256; for longer lists rank the saved model with svdf_ranker_* and top_k");
+    rank_topn_admit("rank_topn", top_n, "; for longer lists rank the saved model with svdf_ranker_* and top_k");
     // ---- the lists, before any device work
     check(S == 0 || (item_out && count_out && nan_out), "rank_topn: bad arguments");
     RankTopnLists L;
@@ -117,7 +124,7 @@ void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, 
 void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
                               const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
                               int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
-    if (!(rank_topn_prefilter_ && !rank_topn_scores_)) {
+    if (!(rank_topn_prefilter_ && !rank_topn_scores_) || top_n > RANK_TOPN_MAX) {   // (the prefilter's M = top_n + slack <= 384 is its design: a deep call goes without)
         rank_topn_pass(who, S, sec_id, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, query_base, top_n, item_out, score_out, count_out,
                        nan_out, rank_topn_scores_, nullptr, true);
         return;
@@ -191,7 +198,9 @@ void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, con
     const unsigned *user = sec_id;
     const DevParams &P = params();
     // under the prefilter the sweep keeps `keep` = top_n + slack keys per list, and the cap, the geometry and the pieces follow it
-    const int N = top_n, matrix = mode != 0, keep = mode == 2 ? N + rank_topn_slack_ : N, cap = rank_topn_cap(P, keep, matrix);
+    // a deep call (section 6al; never under the prefilter): the deep cap, hence fewer item ranges and more pieces, and the deep launchers
+    const int N = top_n, matrix = mode != 0, keep = mode == 2 ? N + rank_topn_slack_ : N, deep = N > RANK_TOPN_MAX;
+    const int cap = deep ? rank_topn_deep_cap(N) : rank_topn_cap(P, keep, matrix);
     const long max_lists = std::max<long>(1, rank_topn_budget_ / cap);
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
@@ -201,7 +210,7 @@ void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, con
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
-        D.nsec = (int)nsec; D.top_n = keep; D.cap = cap; D.matrix = matrix;
+        D.nsec = (int)nsec; D.top_n = keep; D.cap = cap; D.matrix = matrix; D.deep = deep;
         rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block, matrix);
         // ---- one upload: sec_user | ban_p0 | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         const size_t o_fb = 2 * (size_t)nsec + 1 + (size_t)nban, o_ul = o_fb + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0);
@@ -281,6 +290,7 @@ void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, con
         }
         if (counted) (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
         if (mode == 1) n_rank_matrix_sections_ += nsec;
+        if (deep) n_rank_deep_sections_ += nsec;
         s0 = s1;
     }
 }
