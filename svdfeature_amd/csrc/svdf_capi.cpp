@@ -10,7 +10,7 @@
 #include "svdf_engine.h"
 #include "svdf_kernels.h"
 #include "svdf_itemtopn_lists.h"
-#include "svdf_ranklines_lists.h"
+#include "svdf_rankrows_lists.h"
 #include "svdf_pairhard_lists.h"
 #include "svdf_ranknegs_lists.h"
 #include "svdf_wseq_rule.h"
@@ -372,8 +372,7 @@ int svdf_rank_eval_positions_lines(svdf_trainer *t, long num_section, const int6
                                    const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out,
                                    int *ranked_out, int *nan_out) {
     SVDF_GUARD(-1, {
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        const svdf::RankList U{ul_ptr, ul_index, ul_value};
         t->e->rank_eval_positions_lines(num_section, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out,
                                         nan_out);
         return 0;
@@ -385,8 +384,7 @@ int svdf_rank_eval_lines(svdf_trainer *t, long num_section, const int64_t *ul_pt
     SVDF_GUARD(-1, {
         const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
         std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        const svdf::RankList U{ul_ptr, ul_index, ul_value};
         t->e->rank_eval_positions_lines(num_section, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position.data(), tied.data(),
                                         ranked.data(), nan.data());
         svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
@@ -397,8 +395,7 @@ int svdf_rank_topn_lines(svdf_trainer *t, long num_section, const int64_t *ul_pt
                          const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
                          float *score_out, int *count_out, int *nan_out) {
     SVDF_GUARD(-1, {
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
+        const svdf::RankList U{ul_ptr, ul_index, ul_value};
         t->e->rank_topn_lines(num_section, U, fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
         return 0;
     })
@@ -409,9 +406,9 @@ int svdf_rank_eval_positions_cand(svdf_trainer *t, long num_section, const unsig
                                   const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int *position_out, int *tied_out,
                                   int *ranked_out, int *nan_out) {
     SVDF_GUARD(-1, {
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
-        t->e->rank_cand("rank_eval", num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, cand_ptr, cand_item, 0, position_out, tied_out,
+        svdf::RankRowSource R;
+        R.user = user; R.lines = svdf::RankList{ul_ptr, ul_index, ul_value}; R.fb = svdf::RankList{fb_ptr, fb_index, fb_value};
+        t->e->rank_cand("rank_eval", num_section, R, pos_ptr, pos_item, cand_ptr, cand_item, 0, position_out, tied_out,
                         ranked_out, nullptr, nullptr, nullptr, nan_out);
         return 0;
     })
@@ -422,9 +419,9 @@ int svdf_rank_eval_cand(svdf_trainer *t, long num_section, const unsigned *user,
     SVDF_GUARD(-1, {
         const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
         std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
-        t->e->rank_cand("rank_eval", num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, cand_ptr, cand_item, 0, position.data(),
+        svdf::RankRowSource R;
+        R.user = user; R.lines = svdf::RankList{ul_ptr, ul_index, ul_value}; R.fb = svdf::RankList{fb_ptr, fb_index, fb_value};
+        t->e->rank_cand("rank_eval", num_section, R, pos_ptr, pos_item, cand_ptr, cand_item, 0, position.data(),
                         tied.data(), ranked.data(), nullptr, nullptr, nullptr, nan.data());
         svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
         return 0;
@@ -434,9 +431,9 @@ int svdf_rank_topn_cand(svdf_trainer *t, long num_section, const unsigned *user,
                         const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *cand_ptr, const unsigned *cand_item,
                         int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
     SVDF_GUARD(-1, {
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
-        t->e->rank_cand("rank_topn", num_section, user, U, fb_ptr, fb_index, fb_value, nullptr, nullptr, cand_ptr, cand_item, top_n, nullptr, nullptr,
+        svdf::RankRowSource R;
+        R.user = user; R.lines = svdf::RankList{ul_ptr, ul_index, ul_value}; R.fb = svdf::RankList{fb_ptr, fb_index, fb_value};
+        t->e->rank_cand("rank_topn", num_section, R, nullptr, nullptr, cand_ptr, cand_item, top_n, nullptr, nullptr,
                         nullptr, item_out, score_out, count_out, nan_out);
         return 0;
     })
@@ -452,9 +449,9 @@ int svdf_rank_eval_positions_sampled(svdf_trainer *t, long num_section, const un
                                      const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg,
                                      uint64_t seed, int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out) {
     SVDF_GUARD(-1, {
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
-        t->e->rank_negs(num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position_out, tied_out,
+        svdf::RankRowSource R;
+        R.user = user; R.lines = svdf::RankList{ul_ptr, ul_index, ul_value}; R.fb = svdf::RankList{fb_ptr, fb_index, fb_value};
+        t->e->rank_negs(num_section, R, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position_out, tied_out,
                         ranked_out, nan_out, neg_out);
         return 0;
     })
@@ -466,9 +463,9 @@ int svdf_rank_eval_sampled(svdf_trainer *t, long num_section, const unsigned *us
     SVDF_GUARD(-1, {
         const size_t S = (size_t)std::max<long>(num_section, 0), np = S && pos_ptr ? (size_t)std::max<int64_t>(pos_ptr[S], 0) : 0;
         std::vector<int> position(np + 1), tied(np + 1), ranked(S + 1), nan(S + 1);
-        svdf::RankLines U;
-        U.ptr = ul_ptr; U.index = ul_index; U.value = ul_value;
-        t->e->rank_negs(num_section, user, U, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position.data(),
+        svdf::RankRowSource R;
+        R.user = user; R.lines = svdf::RankList{ul_ptr, ul_index, ul_value}; R.fb = svdf::RankList{fb_ptr, fb_index, fb_value};
+        t->e->rank_negs(num_section, R, pos_ptr, pos_item, ban_ptr, ban_item, num_neg, seed, position.data(),
                         tied.data(), ranked.data(), nan.data(), nullptr);
         svdf::rank_eval_metrics(num_section, pos_ptr, position.data(), ranked.data(), nan.data(), num_at, at, out);
         return 0;

@@ -113,6 +113,15 @@ struct DevBuf {
         if (e != hipSuccess) fail(std::string("HIP error: ") + hipGetErrorString(e) + " at hipMemcpyAsync (DevBuf::upload)");
     }
 };
+// reserve() whose failure says whose workspace it was: "<who>: <what> of N bytes could not be allocated: ..." (every reserve of the ranking calls)
+template <typename T>
+static inline void reserve_or_fail(const char *who, DevBuf<T> &buf, size_t n, const char *what) {
+    try {
+        buf.reserve(n);
+    } catch (const std::exception &e) {
+        fail(std::string(who) + ": " + what + " of " + std::to_string(n * sizeof(T)) + " bytes could not be allocated: " + e.what());
+    }
+}
 
 // --------------------------------------------------------------------------- scheduler (pure host)
 // Assigns every unit (instance or SVD++ user) the earliest batch in which none of its parameter
@@ -404,7 +413,9 @@ struct PairSource {
     PairSource &operator=(const PairSource &) = delete;
 };
 
-struct RankLines;   // the USER lines of the svdf_rank_*_lines calls (svdf_ranklines_lists.h)
+struct RankList;        // a ragged list per section: the feedback lists and USER lines of the svdf_rank_* calls (svdf_rankrows_lists.h)
+struct RankRowSource;   // what the sections of such a call score with: users, row lists, the item side
+struct RankRowsAt;      // where a piece's row lists lie in its upload
 struct RankTopnLists;   // the validated ban lists of the top-N calls (svdf_ranktopn_lists.h)
 class Engine {
   public:
@@ -500,45 +511,52 @@ class Engine {
     bool rank_live_fb_refusals(const char *who, bool has_lists, bool tables_ok = false);
     // the same calls for sections that bring a USER line (several ids, any value) and for trainers with feature_user / feature_item side
     // tables (svdf_k_rankrows.hip)
-    void rank_eval_positions_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
+    void rank_eval_positions_lines(long S, const RankList &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
                                    const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out,
                                    int *ranked_out, int *nan_out);
-    void rank_topn_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+    void rank_topn_lines(long S, const RankList &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                          const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
-    void rank_lines_admit(const char *who, long S, const RankLines &U);   // the lines and the tables' child ids, on the host
-    void rank_live_items(const char *who, const float **item_rows, const float **item_bias);   // the prepared item side where feature_item is set
-    // lines != nullptr: a _lines call -- `user` is not read, the rows come from the lines (and fb_ptr, where the trainer is a user-group one)
-    void rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
-                       const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                       int *nan_out, const RankLines *lines = nullptr, bool prefilter_ok = true);
+    void rank_live_items(const char *who, RankRowSource &R);   // the prepared item side where feature_item is set
+    // ---- what the five ranking paths share about their sections' rows (svdf_rankrows.cpp); only the first two know the word layout
+    RankRowsAt rank_rows_pack(const RankRowSource &R, long s0, long s1, std::vector<int> &in);   // appends the piece's row lists to its upload
+    // the effective user rows of the piece [s0, s1) from the device copy `base` of that upload, one more launch; nullptr: W_user rows
+    const float *rank_rows_launch(const char *who, const RankRowSource &R, const int *base, const RankRowsAt &at, const unsigned *sec_user, long s0,
+                                  long s1);
+    void rank_rows_validate(const char *who, long S, const RankRowSource &R);   // the feedback lists, the lines and the tables' child ids, on the host
+    void rank_item_envelope(const char *who, const RankRowSource &R);   // the envelope of the item side a prefilter call scores with, one launch
+    void rank_sections_counted(const RankRowSource &R, long n);   // counters 38 / 40 / 41
+    // a piece's position | tied | nan words into the caller's arrays; returns its sections with positives, counted under 38 / 40 / 41
+    long rank_positions_back(const RankRowSource &R, const int64_t *pos_ptr, long s0, long s1, const int *position, const int *tied, const int *nan,
+                             int *position_out, int *tied_out, int *nan_out);
+    // R.lines given: a _lines call -- R.user may be nullptr, the rows come from the lines (and R.fb, where the trainer is a user-group one)
+    void rank_eval_run(long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                       int *position_out, int *tied_out, int *ranked_out, int *nan_out, bool prefilter_ok = true);
     void rank_geometry(int kind, long units, int top_n, const int64_t *pos_ptr, long *out);   // test probe (svdf_rank_geometry): host only
     void level_geometry(int launcher, long n, int max_nu, int max_ni, int unit_values, int has_globals, long *out);   // test probe (svdf_level_geometry): host only
     void level_config(DevParams &P, int pitch) const;   // the DevParams fields the launch choice of the level kernels reads
-    void rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
-                       const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines = nullptr);
-    // the body of the top-N calls behind their validated lists (pieces, workspace, launches, copy-back); query_base: an item call
-    void rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
-                          const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
-                          int top_n, int *item_out, float *score_out, int *count_out, int *nan_out);
+    void rank_topn_run(long S, RankRowSource R, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
+                       int *count_out, int *nan_out);
+    // the body of the top-N calls behind their validated lists (pieces, workspace, launches, copy-back); R.query_base: an item call, whose
+    // R.user holds the sections' query items
+    void rank_topn_sweeps(const char *who, long S, const RankRowSource &R, const RankTopnLists &L, int top_n, int *item_out, float *score_out,
+                          int *count_out, int *nan_out);
     // one pass of that body over all S sections.  mode 0: the pinned sweeps; 1: the matrix sweep; 2: the certified prefilter (section 6ai),
     // which also fills certified[S] and leaves the outputs of a section that is not certified to the caller; counted: the sections count
     // under 39 / 49 (40 / 41) -- not when the pinned sweep lists the sections again that the prefilter did not certify
-    void rank_topn_pass(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
-                        const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
-                        int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, int mode, int *certified, bool counted);
+    void rank_topn_pass(const char *who, long S, const RankRowSource &R, const RankTopnLists &L, int top_n, int *item_out, float *score_out,
+                        int *count_out, int *nan_out, int mode, int *certified, bool counted);
     // similar-item lists on the live model: dot and cosine top-N per query item (svdf_itemtopn.cpp, svdf_k_itemrows.hip)
     void item_topn(long S, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
                    float *score_out, int *count_out, int *nan_out);
     // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md
-    // section 6aa).  Exactly one of user / U.ptr is set; top_n == 0: positions (pos_*, position_out, tied_out, ranked_out), else the top_n lists
-    void rank_cand(const char *who, long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                   const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int top_n, int *position_out,
-                   int *tied_out, int *ranked_out, int *item_out, float *score_out, int *count_out, int *nan_out);
+    // section 6aa).  Exactly one of R.user / R.lines is set; top_n == 0: positions (pos_*, position_out, tied_out, ranked_out), else the top_n lists
+    void rank_cand(const char *who, long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr,
+                   const unsigned *cand_item, int top_n, int *position_out, int *tied_out, int *ranked_out, int *item_out, float *score_out,
+                   int *count_out, int *nan_out);
     // positions over the positives and num_neg negatives the device draws per section from (seed, section, what the section excludes)
-    // (svdf_ranknegs.cpp, svdf_k_ranknegs.hip).  Exactly one of user / U.ptr is set; neg_out may be nullptr
-    void rank_negs(long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                   const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed,
-                   int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out);
+    // (svdf_ranknegs.cpp, svdf_k_ranknegs.hip).  Exactly one of R.user / R.lines is set; neg_out may be nullptr
+    void rank_negs(long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                   int num_neg, uint64_t seed, int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out);
 
     // passes of rank pairs from positives only, the negatives drawn on the device (svdf_pairsource.cpp, svdf_k_pairdraw.hip; DESIGN.md
     // section 6ac).  A source belongs to the handle it was created on and may outlive it.

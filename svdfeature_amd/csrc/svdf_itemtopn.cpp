@@ -6,6 +6,7 @@
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
 #include "svdf_itemtopn_lists.h"
+#include "svdf_rankrows_lists.h"
 
 namespace svdf {
 
@@ -29,22 +30,20 @@ void Engine::item_topn(long S, const unsigned *item, int metric, const int64_t *
     // ---- the item side of the sweeps, once per call and never kept: the model may have moved since the last one.  Cosine: the unit rows
     // [num_item][pitch] on both sides; dot: W_item where it lies.  Either way a zero vector [num_item] stands in for i_bias.
     const size_t ni = (size_t)mp_.num_item, nrow = metric == SVDF_ITEM_COSINE ? ni * (size_t)P.pitch : 0;
-    try {
-        rk_items_.reserve(nrow + ni);
-    } catch (const std::exception &e) {
-        fail("item_topn: the item side of " + std::to_string((nrow + ni) * sizeof(float)) + " bytes could not be allocated: " + e.what());
-    }
+    reserve_or_fail("item_topn", rk_items_, nrow + ni, "the item side");
     float *unit = rk_items_.p, *zero_bias = rk_items_.p + nrow;
     HIPCHECK(hipMemsetAsync(zero_bias, 0, ni * sizeof(float), stream_));
-    const float *item_rows = nullptr;
-    const float *base = P.W + (size_t)P.item_off * (size_t)P.pitch;
+    RankRowSource R;   // the sections' ids are their query items
+    R.user = item;
+    R.item_bias = zero_bias;
+    R.query_base = P.W + (size_t)P.item_off * (size_t)P.pitch;
     if (metric == SVDF_ITEM_COSINE) {
         launch_item_unit_rows(P, unit, stream_);
         HIPCHECK(hipGetLastError());
         n_launches_++;
-        item_rows = base = unit;
+        R.item_rows = R.query_base = unit;
     }
-    rank_topn_sweeps("item_topn", S, item, L, nullptr, nullptr, nullptr, nullptr, item_rows, zero_bias, base, top_n, item_out, score_out, count_out, nan_out);
+    rank_topn_sweeps("item_topn", S, R, L, top_n, item_out, score_out, count_out, nan_out);
 }
 
 }  // namespace svdf

@@ -10,30 +10,19 @@
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
 #include "svdf_rankcand_lists.h"
-#include "svdf_rankfb_lists.h"
-#include "svdf_ranklines_lists.h"
+#include "svdf_rankrows_lists.h"
 
 namespace svdf {
 
-template <typename T>
-static void rank_cand_reserve(const char *who, DevBuf<T> &buf, size_t n, const char *what) {
-    try {
-        buf.reserve(n);
-    } catch (const std::exception &e) {
-        fail(std::string(who) + ": " + what + " of " + std::to_string(n * sizeof(T)) + " bytes could not be allocated: " + e.what());
-    }
-}
-
-void Engine::rank_cand(const char *who, long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index,
-                       const float *fb_value, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr, const unsigned *cand_item, int top_n,
-                       int *position_out, int *tied_out, int *ranked_out, int *item_out, float *score_out, int *count_out, int *nan_out) {
+void Engine::rank_cand(const char *who, long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr,
+                       const unsigned *cand_item, int top_n, int *position_out, int *tied_out, int *ranked_out, int *item_out, float *score_out,
+                       int *count_out, int *nan_out) {
     const std::string w(who);
     const bool topn = !strcmp(who, "rank_topn");
-    if ((user != nullptr) == (U.ptr != nullptr)) fail(w + ": give the sections either as users or as USER lines");
-    const RankLines *lines = U.ptr ? &U : nullptr;
+    if ((R.user != nullptr) == (R.lines.ptr != nullptr)) fail(w + ": give the sections either as users or as USER lines");
     // what the twin refuses: with users the _fb call's configurations (a format_type = 0 trainer without lists: the plain call's), with
     // USER lines the _lines call's
-    if (!rank_live_fb_refusals(who, fb_ptr != nullptr, lines != nullptr)) fb_ptr = nullptr;
+    if (!rank_live_fb_refusals(who, R.fb.ptr != nullptr, R.lines.ptr != nullptr)) R.fb = RankList();
     // ---- the lists, before any device work
     if (topn) {
         check(top_n >= 1 && top_n <= RANK_TOPN_MAX,
@@ -49,8 +38,8 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
         }
     }
     rank_cand_validate(who, S, cand_ptr, cand_item, (long)mp_.num_item);
-    if (user)
-        for (long s = 0; s < S; s++) check(user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
+    if (R.user)
+        for (long s = 0; s < S; s++) check(R.user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
     RankCandLists L;
     // knob rank_cand_build = 1: the device builds the sets (section 6ak).  What rank_cand_build refuses about the positives is refused here;
     // raw_first counts a section's raw ids, candidates + positives, which bound its set: the pieces are cut on them
@@ -74,8 +63,7 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
         const int threads = entries < (1 << 18) ? 1 : (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         rank_cand_build(S, cand_ptr, cand_item, pos_ptr, pos_item, (long)mp_.num_item, L, threads);
     }
-    if (fb_ptr) rank_fb_validate(who, S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
-    if (lines) rank_lines_admit(who, S, *lines);
+    rank_rows_validate(who, S, R);
     for (long s = 0; s < S; s++) {
         nan_out[s] = 0;
         if (topn) count_out[s] = 0;
@@ -89,10 +77,9 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
     const std::vector<int64_t> &first = dev ? raw_first : L.first;   // what the pieces are cut on
     const int *ranked = dev ? dev_ranked.data() : L.ranked.data();
     const DevParams &P = params();
-    const float *item_rows = nullptr, *item_bias = nullptr;
-    if (lines) rank_live_items(who, &item_rows, &item_bias);   // once per call: the whole catalogue, whatever the lists name
+    if (R.lines.ptr) rank_live_items(who, R);   // once per call: the whole catalogue, whatever the lists name
     const int N = top_n;
-    const int64_t *extra[3] = {pos_ptr, fb_ptr, lines ? lines->ptr : nullptr};
+    const int64_t *extra[3] = {pos_ptr, R.fb.ptr, R.lines.ptr};
     std::vector<int> in, back, tile_q0, tile_sec, sizes;
     std::vector<int64_t> dense;
     for (long s0 = 0; s0 < S;) {
@@ -100,14 +87,15 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
         const long s1 = rank_cand_piece(who, s0, S, first, extra, 3, rank_eval_budget_);
         const long nsec = s1 - s0;
         const int64_t npos = topn ? 0 : pos_ptr[s1] - pos_ptr[s0];
-        check(npos < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4) && (!lines || lines->ptr[s1] - lines->ptr[s0] < INT_MAX / 4),
+        check(npos < INT_MAX / 4 && (!R.fb.ptr || R.fb.ptr[s1] - R.fb.ptr[s0] < INT_MAX / 4) && (!R.lines.ptr || R.lines.ptr[s1] - R.lines.ptr[s0] < INT_MAX / 4),
               (w + ": one section with more than 2^29 entries").c_str());
         if (!dev && !topn && npos == 0) { s0 = s1; continue; }
         auto put = [&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         // what the kernels read, wherever the piece's build has put it
         int64_t npair = 0;
         int ntile = 0;
-        const int *d_user, *d_q0, *d_id, *d_tq0, *d_tsec, *d_p0 = nullptr, *d_at = nullptr, *d_fb = nullptr, *d_ul = nullptr, *d_flag = nullptr;
+        const int *d_in, *d_user, *d_q0, *d_id, *d_tq0, *d_tsec, *d_p0 = nullptr, *d_at = nullptr, *d_flag = nullptr;
+        RankRowsAt o_rows;   // the row lists end either build's first upload, d_in
         if (!dev) {
             npair = L.first[(size_t)s1] - L.first[(size_t)s0];
             rank_cand_tiles(s0, s1, L.first, tile_q0, tile_sec);
@@ -115,10 +103,10 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
             // ---- one upload: sec_user | sec_q0 | cand_id | tile_q0 | tile_sec [| sec_p0 | pos_at] [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
             in.clear();
             in.reserve(2 * (size_t)nsec + 1 + (size_t)npair + 2 * (size_t)ntile + 1 + (topn ? 0 : (size_t)nsec + 1 + (size_t)npos) +
-                       (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));
+                       rank_rows_words(R, s0, s1));
             const size_t o_user = put((size_t)nsec), o_q0 = put((size_t)nsec + 1), o_id = put((size_t)npair);
             for (long s = s0; s <= s1; s++) {
-                if (s < s1) in[o_user + (size_t)(s - s0)] = user ? (int)user[s] : 0;   // (with lines the rows do not read it)
+                if (s < s1) in[o_user + (size_t)(s - s0)] = R.user_of(s);   // (with lines the rows do not read it)
                 in[o_q0 + (size_t)(s - s0)] = (int)(L.first[(size_t)s] - L.first[(size_t)s0]);
             }
             std::copy(L.ids.begin() + (long)L.first[(size_t)s0], L.ids.begin() + (long)L.first[(size_t)s1], in.begin() + (long)o_id);
@@ -133,23 +121,20 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
                 for (int64_t j = pos_ptr[s0]; j < pos_ptr[s1]; j++)
                     in[o_at + (size_t)(j - pos_ptr[s0])] = (int)(L.pos_at[(size_t)(j - pos_ptr[0])] - L.first[(size_t)s0]);
             }
-            const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
-            if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
-            const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
-            if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
-            rank_cand_reserve(who, ca_in_, in.size(), "the lists of a piece");
+            o_rows = rank_rows_pack(R, s0, s1, in);
+            reserve_or_fail(who, ca_in_, in.size(), "the lists of a piece");
             ca_in_.upload(in.data(), in.size(), stream_);
+            d_in = ca_in_.p;
             d_user = ca_in_.p + o_user; d_q0 = ca_in_.p + o_q0; d_id = ca_in_.p + o_id;
             d_tq0 = ca_in_.p + o_tq0; d_tsec = ca_in_.p + o_tsec;
             d_p0 = ca_in_.p + o_p0; d_at = ca_in_.p + o_at;
-            d_fb = ca_in_.p + o_fb; d_ul = ca_in_.p + o_ul;
         } else {
             // ---- the device build.  One upload: sec_user | sec_r0 | sec_form | set_size | flag | the raw ids, per section its candidates, then
             // its positives [| sec_p0 | pos_id] [| fb ...] [| ul ...]
             const int64_t nraw = raw_first[(size_t)s1] - raw_first[(size_t)s0];
             in.clear();
             in.reserve(4 * (size_t)nsec + 2 + (size_t)nraw + (topn ? 0 : (size_t)nsec + 1 + (size_t)npos) +
-                       (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));
+                       rank_rows_words(R, s0, s1));
             const size_t o_user = put((size_t)nsec), o_r0 = put((size_t)nsec + 1), o_form = put((size_t)nsec), o_size = put((size_t)nsec), o_flag = put(1),
                          o_raw = put((size_t)nraw);
             in[o_flag] = 0;
@@ -159,7 +144,7 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
                 const size_t q = (size_t)(s - s0);
                 const int64_t n = raw_first[(size_t)s + 1] - raw_first[(size_t)s];
                 const int form = rank_cand_set_form(n, (int64_t)mp_.num_item, (int)rank_cand_build_form_);
-                in[o_user + q] = user ? (int)user[s] : 0;
+                in[o_user + q] = R.user_of(s);
                 in[o_r0 + q] = (int)(raw_first[(size_t)s] - raw_first[(size_t)s0]);
                 in[o_form + q] = form;
                 in[o_size + q] = 0;
@@ -177,11 +162,8 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
                 for (long s = s0; s <= s1; s++) in[o_p0 + (size_t)(s - s0)] = (int)(pos_ptr[s] - pos_ptr[s0]);
                 if (npos > 0) std::copy(pos_item + pos_ptr[s0], pos_item + pos_ptr[s1], in.begin() + (long)o_pid);
             }
-            const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
-            if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
-            const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
-            if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
-            rank_cand_reserve(who, cb_in_, in.size(), "the lists of a piece");
+            o_rows = rank_rows_pack(R, s0, s1, in);
+            reserve_or_fail(who, cb_in_, in.size(), "the lists of a piece");
             cb_in_.upload(in.data(), in.size(), stream_);
             // ---- the sets, in place; their sizes come back: the host needs them for ranked_out, the dense offsets and the tile table
             RankCandSetsDev B;
@@ -218,7 +200,7 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
             std::copy(tile_q0.begin(), tile_q0.end(), in.begin() + (long)o_tq0);
             std::copy(tile_sec.begin(), tile_sec.end(), in.begin() + (long)o_tsec);
             const size_t o_id = in.size(), o_at = o_id + (size_t)npair;
-            rank_cand_reserve(who, ca_in_, o_at + (size_t)npos, "the sets of a piece");
+            reserve_or_fail(who, ca_in_, o_at + (size_t)npos, "the sets of a piece");
             ca_in_.upload(in.data(), in.size(), stream_);
             B.sec_q0 = ca_in_.p + o_q0;
             B.cand_id = ca_in_.p + o_id;
@@ -230,40 +212,17 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
             d_user = cb_in_.p + o_user; d_q0 = B.sec_q0; d_id = B.cand_id;
             d_tq0 = ca_in_.p + o_tq0; d_tsec = ca_in_.p + o_tsec;
             d_p0 = B.sec_p0; d_at = B.pos_at; d_flag = B.flag;
-            d_fb = cb_in_.p + o_fb; d_ul = cb_in_.p + o_ul;
+            d_in = cb_in_.p;
         }
         // ---- the workspaces: the pairs' scores; position | tied | nan, or nan | count | items | scores
         const size_t nres = topn ? (size_t)nsec * (2 + 2 * (size_t)N) : 2 * (size_t)npos + (size_t)nsec;
-        rank_cand_reserve(who, ca_score_, (size_t)npair, "the candidate scores of a piece");
-        rank_cand_reserve(who, ca_out_, nres, "the results of a piece");
+        reserve_or_fail(who, ca_score_, (size_t)npair, "the candidate scores of a piece");
+        reserve_or_fail(who, ca_out_, nres, "the results of a piece");
         RankCandDev D;
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(d_user);
-        D.user_rows = nullptr;
-        D.item_rows = item_rows; D.item_bias = item_bias;
-        if (fb_ptr || lines) {   // the sections' effective user rows, one more launch ahead of the scores
-            rank_cand_reserve(who, rk_rows_, (size_t)nsec * (size_t)P.pitch, "the user rows of a piece");
-            RankLiveRowsDev R;
-            R.nsec = (int)nsec; R.sec_user = D.sec_user;
-            R.fb_p0 = nullptr; R.fb_index = nullptr; R.fb_value = nullptr;
-            if (fb_ptr) {
-                const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
-                R.fb_p0 = d_fb;
-                R.fb_index = reinterpret_cast<const unsigned *>(d_fb + (size_t)nsec + 1);
-                R.fb_value = reinterpret_cast<const float *>(d_fb + (size_t)nsec + 1 + nfb);
-            }
-            if (lines) {
-                const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
-                R.ul_p0 = d_ul;
-                R.ul_index = reinterpret_cast<const unsigned *>(d_ul + (size_t)nsec + 1);
-                R.ul_value = reinterpret_cast<const float *>(d_ul + (size_t)nsec + 1 + nul);
-            }
-            R.rows = rk_rows_.p;
-            launch_rank_live_rows(P, R, stream_);
-            HIPCHECK(hipGetLastError());
-            n_launches_++;
-            D.user_rows = rk_rows_.p;
-        }
+        D.item_rows = R.item_rows; D.item_bias = R.item_bias;
+        D.user_rows = rank_rows_launch(who, R, d_in, o_rows, D.sec_user, s0, s1);
         D.sec_q0 = d_q0;
         D.cand_id = d_id;
         D.cand_score = ca_score_.p;
@@ -298,8 +257,8 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
             }
             n_rank_topn_sections_ += nsec;
             n_rank_cand_sections_ += nsec;
-            if (fb_ptr) n_rank_fb_sections_ += nsec;
-            if (lines) n_rank_line_sections_ += nsec;
+            if (R.fb.ptr) n_rank_fb_sections_ += nsec;
+            if (R.lines.ptr) n_rank_line_sections_ += nsec;
         } else {
             back.resize(nres);
             HIPCHECK(hipMemcpyAsync(back.data(), ca_out_.p, nres * sizeof(int), hipMemcpyDeviceToHost, stream_));
@@ -307,19 +266,8 @@ void Engine::rank_cand(const char *who, long S, const unsigned *user, const Rank
             if (d_flag) HIPCHECK(hipMemcpyAsync(&lost, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_));
             HIPCHECK(hipStreamSynchronize(stream_));
             check(lost == 0, "rank_eval: internal error: a positive is not in its section's set");
-            for (long s = s0; s < s1; s++) {
-                if (pos_ptr[s + 1] == pos_ptr[s]) continue;
-                nan_out[s] = back[2 * (size_t)npos + (size_t)(s - s0)] != 0 ? 1 : 0;
-                for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
-                    const size_t q = (size_t)(j - pos_ptr[s0]);
-                    position_out[j] = back[q];
-                    tied_out[j] = back[(size_t)npos + q];
-                }
-                n_rank_eval_sections_++;
-                n_rank_cand_sections_++;
-                if (fb_ptr) n_rank_fb_sections_++;
-                if (lines) n_rank_line_sections_++;
-            }
+            n_rank_cand_sections_ += rank_positions_back(R, pos_ptr, s0, s1, back.data(), back.data() + npos, back.data() + 2 * npos, position_out,
+                                                         tied_out, nan_out);
         }
         s0 = s1;
     }

@@ -9,8 +9,7 @@
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
 #include "svdf_rankeval_lists.h"
-#include "svdf_rankfb_lists.h"
-#include "svdf_ranklines_lists.h"
+#include "svdf_rankrows_lists.h"
 #include "svdf_ranktopn_lists.h"
 
 namespace svdf {
@@ -73,38 +72,42 @@ void rank_eval_metrics(long S, const int64_t *sec_ptr, const int *position, cons
 void Engine::rank_eval_positions(long S, const unsigned *user, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr,
                                  const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
     rank_live_refusals("rank_eval");   // what the batch call does not cover (svdf_ranker_* does): svdf_ranktopn.cpp
-    rank_eval_run(S, user, nullptr, nullptr, nullptr, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
+    RankRowSource R;
+    R.user = user;
+    rank_eval_run(S, R, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
 }
 
 // the same on a user-group trainer, whose sections bring feedback lists; without lists on a format_type = 0 trainer: the call above
 void Engine::rank_eval_positions_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                                     const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out,
                                     int *tied_out, int *ranked_out, int *nan_out) {
-    if (!rank_live_fb_refusals("rank_eval", fb_ptr != nullptr)) fb_ptr = nullptr;
-    rank_eval_run(S, user, fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
+    RankRowSource R;
+    R.user = user;
+    if (rank_live_fb_refusals("rank_eval", fb_ptr != nullptr)) R.fb = RankList{fb_ptr, fb_index, fb_value};
+    rank_eval_run(S, R, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
 }
 
 // ... and for sections that bring a USER line, on trainers with or without side tables
-void Engine::rank_eval_positions_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
+void Engine::rank_eval_positions_lines(long S, const RankList &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
                                        const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
                                        int *position_out, int *tied_out, int *ranked_out, int *nan_out) {
-    if (!rank_live_fb_refusals("rank_eval", fb_ptr != nullptr, true)) fb_ptr = nullptr;
-    const std::vector<unsigned> user((size_t)std::max<long>(S, 1), 0u);   // not read by the kernels: the rows come from the lines
-    rank_eval_run(S, user.data(), fb_ptr, fb_index, fb_value, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out, &U);
+    RankRowSource R;   // no users: the rows come from the lines
+    R.lines = U; R.by_lines = true;
+    if (rank_live_fb_refusals("rank_eval", fb_ptr != nullptr, true)) R.fb = RankList{fb_ptr, fb_index, fb_value};
+    rank_eval_run(S, R, pos_ptr, pos_item, ban_ptr, ban_item, position_out, tied_out, ranked_out, nan_out);
 }
 
-// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
-// lines != nullptr: from their USER lines, behind the feedback sum where there is one.
+// R.fb given: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
+// R.lines given: from their USER lines, behind the feedback sum where there is one.
 // Under the knob rank_eval_prefilter (prefilter_ok: not the second run below) the pieces go through the counting sweep
 // on the matrix cores and the band pass (launch_rank_eval_mx); the sections the rule does not certify are gathered -- users, positives, the
 // validated ban lists, feedback lists, USER lines -- into contiguous copies, ranked once more by this function with the route off and
 // scattered to their places.  Either way every count is the pinned sweep's.
-void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *pos_ptr,
-                           const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int *position_out, int *tied_out, int *ranked_out,
-                           int *nan_out, const RankLines *lines, bool prefilter_ok) {
+void Engine::rank_eval_run(long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                           int *position_out, int *tied_out, int *ranked_out, int *nan_out, bool prefilter_ok) {
     const bool mx = prefilter_ok && rank_eval_prefilter_ != 0;
     // ---- the lists, before any device work
-    check(S >= 0 && (S == 0 || (user && pos_ptr)), "rank_eval: bad arguments");
+    check(S >= 0 && (S == 0 || ((R.user || R.by_lines) && pos_ptr)), "rank_eval: bad arguments");
     const long num_item = mp_.num_item;
     std::vector<int64_t> ban_first((size_t)S + 1, 0);   // distinct (section, banned id) pairs of sections WITH positives: [ban_first[s], ban_first[s + 1])
     std::vector<int> ban_ids;
@@ -119,7 +122,7 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         check(!ban_ptr || ban_ptr[S] == 0 || ban_item, "rank_eval: ban_item is missing");
         std::vector<long> stamp((size_t)num_item, 0);   // 2 s + 1: banned in section s, 2 s + 2: positive of section s
         for (long s = 0; s < S; s++) {
-            check(user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
+            check(!R.user || R.user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
             long nban = 0;
             const bool keep = pos_ptr[s + 1] > pos_ptr[s];
             if (ban_ptr)
@@ -144,44 +147,36 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             nan_out[s] = 0;
         }
     }
-    if (fb_ptr) rank_fb_validate("rank_eval", S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
-    if (lines) rank_lines_admit("rank_eval", S, *lines);
+    rank_rows_validate("rank_eval", S, R);
     need_device("rank_eval");
     if (S == 0 || pos_ptr[S] == pos_ptr[0]) return;
     flush();   // behind whatever has been staged
     const DevParams &P = params();
-    const float *item_rows = nullptr, *item_bias = nullptr;
-    if (lines) rank_live_items("rank_eval", &item_rows, &item_bias);   // once per call
+    if (R.lines.ptr) rank_live_items("rank_eval", R);   // once per call
     const int tile_rows = mx ? 64 : rank_eval_tile_rows(P), tile_pos = mx ? RANK_EVAL_MX_POS : RANK_EVAL_TILE_POS;
-    const int64_t row_cost = mx ? (int64_t)rank_eval_band_ + 2 : 0;   // a row's band list, cursor and `certified` word count into the piece budget
-    if (mx) {   // the envelope of the item side this call scores with, once, ahead of the first piece (section 6ai)
-        tn_env_.reserve(RANK_ENV_WORDS);
-        HIPCHECK(hipMemsetAsync(tn_env_.p, 0, RANK_ENV_WORDS * sizeof(unsigned), stream_));
-        launch_rank_item_envelope(P, item_rows, item_bias, tn_env_.p, stream_);
-        HIPCHECK(hipGetLastError());
-        n_launches_++;
-    }
+    // under the prefilter a section's band lists count into the piece budget
+    auto band_cost = [&](long s) { return mx ? rank_eval_band_cost(pos_ptr[s + 1] - pos_ptr[s], rank_eval_band_, tile_pos) : 0; };
+    if (mx) rank_item_envelope("rank_eval", R);
     std::vector<long> again;   // sections the rule did not certify
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
         // a piece always takes its first section: one whose band lists alone exceed the budget (rows x capacity ids) is ranked by the
         // pinned route, not given a workspace of that size
-        if (mx && row_cost * ((pos_ptr[s0 + 1] - pos_ptr[s0] + tile_pos - 1) / tile_pos) > (int64_t)rank_eval_budget_) {
-            n_rank_eval_sections_++; n_rank_eval_again_++;
-            if (fb_ptr) n_rank_fb_sections_++;
-            if (lines) n_rank_line_sections_++;
+        if (band_cost(s0) > (int64_t)rank_eval_budget_) {
+            rank_sections_counted(R, 1);
+            n_rank_eval_again_++;
             again.push_back(s0++);
             continue;
         }
         // ---- a piece of whole sections within the device budget
         const long s1 = rank_eval_piece(s0, S, rank_eval_budget_, [&](long s) {
-            return (pos_ptr[s + 1] - pos_ptr[s]) + (ban_first[(size_t)s + 1] - ban_first[(size_t)s]) + 1 + (fb_ptr ? fb_ptr[s + 1] - fb_ptr[s] : 0) +
-                   (lines ? lines->ptr[s + 1] - lines->ptr[s] : 0) + row_cost * ((pos_ptr[s + 1] - pos_ptr[s] + tile_pos - 1) / tile_pos);
+            return (pos_ptr[s + 1] - pos_ptr[s]) + (ban_first[(size_t)s + 1] - ban_first[(size_t)s]) + 1 + (R.fb.ptr ? R.fb.ptr[s + 1] - R.fb.ptr[s] : 0) +
+                   (R.lines.ptr ? R.lines.ptr[s + 1] - R.lines.ptr[s] : 0) + band_cost(s);
         });
         const long nsec = s1 - s0;
         const int64_t npos = pos_ptr[s1] - pos_ptr[s0], nban = ban_first[(size_t)s1] - ban_first[(size_t)s0];
-        check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4) &&
-                  (!lines || lines->ptr[s1] - lines->ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
+        check(npos < INT_MAX / 4 && nban < INT_MAX / 4 && (!R.fb.ptr || R.fb.ptr[s1] - R.fb.ptr[s0] < INT_MAX / 4) &&
+                  (!R.lines.ptr || R.lines.ptr[s1] - R.lines.ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
         if (npos == 0) { s0 = s1; continue; }
         // ---- rows (a section, or a slice of its positives) and tiles of rows
         RankEvalRows rows;
@@ -192,11 +187,11 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         // ---- one upload: sec_user | sec_p0 | pos_item | pos_sec | row_sec | row_first | row_p0 | tile_r0 | ban_sec | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         in.clear();
         in.reserve(2 * (size_t)nsec + 1 + 2 * (size_t)npos + 3 * (size_t)nrow + 1 + (size_t)ntile + 1 + 2 * (size_t)nban + (mx ? (size_t)nsec + 1 : 0) +
-                   (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));   // one allocation: the parts below never move what is already there
+                   rank_rows_words(R, s0, s1));   // one allocation: the parts below never move what is already there
         auto put =[&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         const size_t o_user = put((size_t)nsec), o_sp0 = put((size_t)nsec + 1), o_pitem = put((size_t)npos), o_psec = put((size_t)npos);
         for (long s = s0; s < s1; s++) {
-            in[o_user + (size_t)(s - s0)] = (int)user[s];
+            in[o_user + (size_t)(s - s0)] = R.user_of(s);
             in[o_sp0 + (size_t)(s - s0)] = (int)(pos_ptr[s] - pos_ptr[s0]);
             for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
                 in[o_pitem + (size_t)(j - pos_ptr[s0])] = (int)pos_item[j];
@@ -218,45 +213,20 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
             }
         }
         if (mx) in[o_bsec + (size_t)nsec] = (int)nban;
-        const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
-        if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
-        const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
-        if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
+        const RankRowsAt o_rows = rank_rows_pack(R, s0, s1, in);
+        reserve_or_fail("rank_eval", re_in_, in.size(), "the lists of a piece");
         re_in_.upload(in.data(), in.size(), stream_);
         // the counts: greater | tied | before [npos] | nan_cnt [nsec]; under the prefilter also sec_ok [nsec] | row_cert [nrow] | band_cursor [nrow]
         const size_t ncnt = 3 * (size_t)npos + (size_t)nsec + (mx ? (size_t)nsec + 2 * (size_t)nrow : 0);
-        re_cnt_.reserve(ncnt);
-        re_ps_.reserve((mx ? 3 : 1) * (size_t)npos);
-        if (mx) re_band_.reserve((size_t)npos + (size_t)nrow * (size_t)rank_eval_band_);
+        reserve_or_fail("rank_eval", re_cnt_, ncnt, "the counts of a piece");
+        reserve_or_fail("rank_eval", re_ps_, (mx ? 3 : 1) * (size_t)npos, "the positives' scores of a piece");
+        if (mx) reserve_or_fail("rank_eval", re_band_, (size_t)npos + (size_t)nrow * (size_t)rank_eval_band_, "the band lists of a piece");
         HIPCHECK(hipMemsetAsync(re_cnt_.p, 0, ncnt * sizeof(int), stream_));
         RankEvalMxDev D;
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(re_in_.p + o_user);
-        D.user_rows = nullptr;
-        D.item_rows = item_rows; D.item_bias = item_bias;
-        if (fb_ptr || lines) {   // the sections' effective user rows, one more launch ahead of the sweep
-            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
-            RankLiveRowsDev R;
-            R.nsec = (int)nsec; R.sec_user = D.sec_user;
-            R.fb_p0 = nullptr; R.fb_index = nullptr; R.fb_value = nullptr;
-            if (fb_ptr) {
-                const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
-                R.fb_p0 = re_in_.p + o_fb;
-                R.fb_index = reinterpret_cast<const unsigned *>(re_in_.p + o_fb + (size_t)nsec + 1);
-                R.fb_value = reinterpret_cast<const float *>(re_in_.p + o_fb + (size_t)nsec + 1 + nfb);
-            }
-            if (lines) {
-                const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
-                R.ul_p0 = re_in_.p + o_ul;
-                R.ul_index = reinterpret_cast<const unsigned *>(re_in_.p + o_ul + (size_t)nsec + 1);
-                R.ul_value = reinterpret_cast<const float *>(re_in_.p + o_ul + (size_t)nsec + 1 + nul);
-            }
-            R.rows = rk_rows_.p;
-            launch_rank_live_rows(P, R, stream_);
-            HIPCHECK(hipGetLastError());
-            n_launches_++;
-            D.user_rows = rk_rows_.p;
-        }
+        D.item_rows = R.item_rows; D.item_bias = R.item_bias;
+        D.user_rows = rank_rows_launch("rank_eval", R, re_in_.p, o_rows, D.sec_user, s0, s1);
         D.sec_p0 = re_in_.p + o_sp0;
         D.npos = (long)npos;
         D.pos_item = re_in_.p + o_pitem; D.pos_sec = re_in_.p + o_psec;
@@ -284,83 +254,62 @@ void Engine::rank_eval_run(long S, const unsigned *user, const int64_t *fb_ptr, 
         back.resize(ncnt);
         HIPCHECK(hipMemcpyAsync(back.data(), re_cnt_.p, ncnt * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
-        if (mx)
-            for (size_t i = 0; i < (size_t)nrow; i++) {
-                const int64_t len = back[3 * (size_t)npos + 2 * (size_t)nsec + (size_t)nrow + i];
-                n_rank_eval_band_rows_++; n_rank_eval_band_ids_ += len;
-                n_rank_eval_band_max_ = std::max(n_rank_eval_band_max_, len);
+        // the position of a positive is greater + before; all of a flagged section: -1
+        int *const b_pos = back.data(), *const b_tied = b_pos + npos, *const b_before = b_tied + npos, *const b_nan = b_before + npos;
+        for (long s = s0; s < s1; s++)
+            for (int64_t q = pos_ptr[s] - pos_ptr[s0]; q < pos_ptr[s + 1] - pos_ptr[s0]; q++) {
+                b_pos[q] = b_nan[s - s0] ? -1 : b_pos[q] + b_before[q];
+                if (b_nan[s - s0]) b_tied[q] = -1;
             }
+        if (!mx) {
+            rank_positions_back(R, pos_ptr, s0, s1, b_pos, b_tied, b_nan, position_out, tied_out, nan_out);
+            s0 = s1;
+            continue;
+        }
+        const int *const b_ok = b_nan + nsec, *const b_cert = b_ok + nsec, *const b_cursor = b_cert + nrow;
+        for (size_t i = 0; i < (size_t)nrow; i++) {
+            n_rank_eval_band_rows_++; n_rank_eval_band_ids_ += b_cursor[i];
+            n_rank_eval_band_max_ = std::max<int64_t>(n_rank_eval_band_max_, b_cursor[i]);
+        }
         size_t r = 0;   // the first row of section s
         for (long s = s0; s < s1; s++) {
             if (pos_ptr[s + 1] == pos_ptr[s]) continue;
-            const bool bad = back[3 * (size_t)npos + (size_t)(s - s0)] != 0;
-            if (mx) {   // certified: (a), (b) by k_rank_eval_prep, (c) no NaN in the sweep, (d) and the pinned NaN check by every row's word
-                bool cert = !bad && back[3 * (size_t)npos + (size_t)nsec + (size_t)(s - s0)] != 0;
-                for (; r < (size_t)nrow && row_sec[r] == (int)(s - s0); r++) cert = cert && back[3 * (size_t)npos + 2 * (size_t)nsec + r] != 0;
-                n_rank_eval_sections_++;
-                if (fb_ptr) n_rank_fb_sections_++;
-                if (lines) n_rank_line_sections_++;
-                (cert ? n_rank_eval_certified_ : n_rank_eval_again_)++;
-                if (!cert) { again.push_back(s); continue; }
-                for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
-                    const size_t q = (size_t)(j - pos_ptr[s0]);
-                    position_out[j] = back[q] + back[2 * (size_t)npos + q];
-                    tied_out[j] = back[(size_t)npos + q];
-                }
-                continue;
+            // certified: (a), (b) by k_rank_eval_prep, (c) no NaN in the sweep, (d) and the pinned NaN check by every row's word
+            bool cert = !b_nan[s - s0] && b_ok[s - s0] != 0;
+            for (; r < (size_t)nrow && row_sec[r] == (int)(s - s0); r++) cert = cert && b_cert[r] != 0;
+            if (cert) {
+                n_rank_eval_certified_++;
+                // section s as a piece of its own: with pos_ptr and nan_out shifted to s, the routine's s0 = 0 reads pos_ptr[s], pos_ptr[s + 1]
+                // and writes nan_out[s], and its sources start at the section's first positive and at its nan word (0: certified)
+                rank_positions_back(R, pos_ptr + s, 0, 1, b_pos + (pos_ptr[s] - pos_ptr[s0]), b_tied + (pos_ptr[s] - pos_ptr[s0]), b_nan + (s - s0),
+                                    position_out, tied_out, nan_out + s);
+            } else {
+                rank_sections_counted(R, 1);
+                n_rank_eval_again_++;
+                again.push_back(s);
             }
-            nan_out[s] = bad ? 1 : 0;
-            for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
-                const size_t q = (size_t)(j - pos_ptr[s0]);
-                position_out[j] = bad ? -1 : back[q] + back[2 * (size_t)npos + q];
-                tied_out[j] = bad ? -1 : back[(size_t)npos + q];
-            }
-            n_rank_eval_sections_++;
-            if (fb_ptr) n_rank_fb_sections_++;
-            if (lines) n_rank_line_sections_++;
         }
         s0 = s1;
     }
     if (again.empty()) return;
     // ---- the sections left: contiguous copies of what they bring, this function with the route off, the results back to their places
+    const RankRelist X(again, R, ban_first, ban_ids);
     const long A = (long)again.size();
-    std::vector<unsigned> a_user((size_t)A), a_pos, a_ban, fbi, uli;
-    std::vector<int64_t> a_pp((size_t)A + 1, 0), a_bp((size_t)A + 1, 0), fbp, ulp;
-    std::vector<float> fbv, ulv;
-    auto gather = [&](const int64_t *ptr, const unsigned *index, const float *value, std::vector<int64_t> &p, std::vector<unsigned> &ix, std::vector<float> &v) {
-        p.assign((size_t)A + 1, 0);
-        for (long a = 0; a < A; a++) {
-            const long s = again[(size_t)a];
-            ix.insert(ix.end(), index + ptr[s], index + ptr[s + 1]);
-            v.insert(v.end(), value + ptr[s], value + ptr[s + 1]);
-            p[(size_t)a + 1] = (int64_t)ix.size();
-        }
-    };
+    std::vector<unsigned> a_pos;
+    std::vector<int64_t> a_pp((size_t)A + 1, 0);
     for (long a = 0; a < A; a++) {
-        const size_t s = (size_t)again[(size_t)a];
-        a_user[(size_t)a] = user[s];
-        a_pos.insert(a_pos.end(), pos_item + pos_ptr[s], pos_item + pos_ptr[s + 1]);
+        a_pos.insert(a_pos.end(), pos_item + pos_ptr[again[(size_t)a]], pos_item + pos_ptr[again[(size_t)a] + 1]);
         a_pp[(size_t)a + 1] = (int64_t)a_pos.size();
-        a_ban.insert(a_ban.end(), ban_ids.begin() + (long)ban_first[s], ban_ids.begin() + (long)ban_first[s + 1]);
-        a_bp[(size_t)a + 1] = (int64_t)a_ban.size();
-    }
-    if (fb_ptr) gather(fb_ptr, fb_index, fb_value, fbp, fbi, fbv);
-    RankLines UA;
-    if (lines) {
-        gather(lines->ptr, lines->index, lines->value, ulp, uli, ulv);
-        UA.ptr = ulp.data(); UA.index = uli.data(); UA.value = ulv.data();
     }
     std::vector<int> a_position(a_pos.size()), a_tied(a_pos.size()), a_ranked((size_t)A), a_nan((size_t)A);
     const int64_t c38 = n_rank_eval_sections_, c40 = n_rank_fb_sections_, c41 = n_rank_line_sections_;   // each section counts once
-    rank_eval_run(A, a_user.data(), fb_ptr ? fbp.data() : nullptr, fbi.data(), fbv.data(), a_pp.data(), a_pos.data(), a_bp.data(), a_ban.data(),
-                  a_position.data(), a_tied.data(), a_ranked.data(), a_nan.data(), lines ? &UA : nullptr, false);
+    rank_eval_run(A, X.rows, a_pp.data(), a_pos.data(), X.ban_first.data(), reinterpret_cast<const unsigned *>(X.ban_ids.data()), a_position.data(),
+                  a_tied.data(), a_ranked.data(), a_nan.data(), false);
     n_rank_eval_sections_ = c38; n_rank_fb_sections_ = c40; n_rank_line_sections_ = c41;
-    for (long a = 0; a < A; a++) {
-        const size_t s = (size_t)again[(size_t)a];
-        std::copy(a_position.begin() + (long)a_pp[(size_t)a], a_position.begin() + (long)a_pp[(size_t)a + 1], position_out + pos_ptr[s]);
-        std::copy(a_tied.begin() + (long)a_pp[(size_t)a], a_tied.begin() + (long)a_pp[(size_t)a + 1], tied_out + pos_ptr[s]);
-        nan_out[s] = a_nan[(size_t)a];
-    }
+    auto one = [](long i) { return i; };
+    X.scatter(a_position.data(), [&](long a) { return a_pp[(size_t)a]; }, position_out, [&](long s) { return pos_ptr[s]; });
+    X.scatter(a_tied.data(), [&](long a) { return a_pp[(size_t)a]; }, tied_out, [&](long s) { return pos_ptr[s]; });
+    X.scatter(a_nan.data(), one, nan_out, one);
 }
 
 // The test probe svdf_rank_geometry: what the launches of the two calls would be told, from the functions they call, without a device.
@@ -379,9 +328,8 @@ void Engine::rank_geometry(int kind, long units, int top_n, const int64_t *pos_p
         if (pos_ptr) {
             check(pos_ptr[0] >= 0, "rank_geometry: pos_ptr must start at >= 0");
             for (long s = 0; s < units; s++) check(pos_ptr[s + 1] >= pos_ptr[s], "rank_geometry: pos_ptr must not decrease");
-            const int64_t row_cost = (int64_t)rank_eval_band_ + 2;
             piece = rank_eval_piece(0, units, rank_eval_budget_, [&](long s) {
-                return pos_ptr[s + 1] - pos_ptr[s] + 1 + row_cost * ((pos_ptr[s + 1] - pos_ptr[s] + RANK_EVAL_MX_POS - 1) / RANK_EVAL_MX_POS);
+                return pos_ptr[s + 1] - pos_ptr[s] + 1 + rank_eval_band_cost(pos_ptr[s + 1] - pos_ptr[s], rank_eval_band_, RANK_EVAL_MX_POS);
             });
             RankEvalRows rows;
             rank_eval_rows(pos_ptr, 0, piece, 64, RANK_EVAL_MX_POS, rows);

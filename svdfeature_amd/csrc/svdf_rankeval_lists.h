@@ -24,6 +24,10 @@ static inline long rank_eval_piece(long s0, long S, int64_t budget, Load load) {
     return s1;
 }
 
+// What a section of npos positives adds to a piece's load under the prefilter: per row of tile_pos positives the
+// row's band list of `band` ids, its cursor and its `certified` word.
+static inline int64_t rank_eval_band_cost(int64_t npos, int band, int tile_pos) { return ((int64_t)band + 2) * ((npos + tile_pos - 1) / tile_pos); }
+
 struct RankEvalRows {
     std::vector<int> row_sec, row_first, row_p0, tile_r0;   // [nrow] [nrow] [nrow + 1] [ntile + 1], every index local to the piece
     int nrow() const { return (int)row_sec.size(); }

@@ -10,28 +10,16 @@
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
 #include "svdf_rankcand_lists.h"
-#include "svdf_rankfb_lists.h"
-#include "svdf_ranklines_lists.h"
+#include "svdf_rankrows_lists.h"
 #include "svdf_ranknegs_lists.h"
 
 namespace svdf {
 
-template <typename T>
-static void rank_negs_reserve(DevBuf<T> &buf, size_t n, const char *what) {
-    try {
-        buf.reserve(n);
-    } catch (const std::exception &e) {
-        fail(std::string("rank_eval: ") + what + " of " + std::to_string(n * sizeof(T)) + " bytes could not be allocated: " + e.what());
-    }
-}
-
-void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value,
-                       const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item, int num_neg, uint64_t seed,
-                       int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out) {
+void Engine::rank_negs(long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *ban_ptr, const unsigned *ban_item,
+                       int num_neg, uint64_t seed, int *position_out, int *tied_out, int *ranked_out, int *nan_out, int *neg_out) {
     const char *who = "rank_eval";
-    if ((user != nullptr) == (U.ptr != nullptr)) fail("rank_eval: give the sections either as users or as USER lines");
-    const RankLines *lines = U.ptr ? &U : nullptr;
-    if (!rank_live_fb_refusals(who, fb_ptr != nullptr, lines != nullptr)) fb_ptr = nullptr;   // the twins' refusals, in their words
+    if ((R.user != nullptr) == (R.lines.ptr != nullptr)) fail("rank_eval: give the sections either as users or as USER lines");
+    if (!rank_live_fb_refusals(who, R.fb.ptr != nullptr, R.lines.ptr != nullptr)) R.fb = RankList();   // the twins' refusals, in their words
     // ---- the lists, before any device work
     check(S >= 0 && (S == 0 || (pos_ptr && position_out && tied_out && ranked_out && nan_out)), "rank_eval: bad arguments");
     RankNegsLists L;
@@ -39,10 +27,9 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
     const int64_t entries = S > 0 && pos_ptr && ban_ptr && pos_ptr[S] >= pos_ptr[0] && ban_ptr[S] >= ban_ptr[0] ? pos_ptr[S] - pos_ptr[0] + ban_ptr[S] - ban_ptr[0] : 0;
     const int threads = entries < (1 << 18) ? 1 : (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     rank_negs_build(S, pos_ptr, pos_item, ban_ptr, ban_item, (long)mp_.num_item, num_neg, L, threads);
-    if (user)
-        for (long s = 0; s < S; s++) check(user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
-    if (fb_ptr) rank_fb_validate(who, S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
-    if (lines) rank_lines_admit(who, S, *lines);
+    if (R.user)
+        for (long s = 0; s < S; s++) check(R.user[s] < (unsigned)mp_.num_user, "user feature index exceed bound");
+    rank_rows_validate(who, S, R);
     for (long s = 0; s < S; s++) {
         nan_out[s] = 0;
         ranked_out[s] = L.ranked[(size_t)s];
@@ -54,12 +41,11 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
     }
     flush();   // behind whatever has been staged
     const DevParams &P = params();
-    const float *item_rows = nullptr, *item_bias = nullptr;
-    if (lines) rank_live_items(who, &item_rows, &item_bias);   // once per call
+    if (R.lines.ptr) rank_live_items(who, R);   // once per call
     const int slots = rank_negs_table(num_neg);
     int shift = 32;
     for (int n = slots; n > 1; n >>= 1) shift--;
-    const int64_t *extra[4] = {pos_ptr, L.ex_first.data(), fb_ptr, lines ? lines->ptr : nullptr};
+    const int64_t *extra[4] = {pos_ptr, L.ex_first.data(), R.fb.ptr, R.lines.ptr};
     std::vector<int> in, back, tile_q0, tile_sec;
     for (long s0 = 0; s0 < S;) {
         // ---- a piece of whole sections within the entry budget: pairs, positives, excluded ids, feedback and line entries, one per section
@@ -67,8 +53,8 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
         const long nsec = s1 - s0;
         const int64_t npair = L.first[(size_t)s1] - L.first[(size_t)s0], npos = pos_ptr[s1] - pos_ptr[s0];
         const int64_t nex = L.ex_first[(size_t)s1] - L.ex_first[(size_t)s0];
-        check(npos < INT_MAX / 4 && nex < INT_MAX / 4 && (!fb_ptr || fb_ptr[s1] - fb_ptr[s0] < INT_MAX / 4) &&
-                  (!lines || lines->ptr[s1] - lines->ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
+        check(npos < INT_MAX / 4 && nex < INT_MAX / 4 && (!R.fb.ptr || R.fb.ptr[s1] - R.fb.ptr[s0] < INT_MAX / 4) &&
+                  (!R.lines.ptr || R.lines.ptr[s1] - R.lines.ptr[s0] < INT_MAX / 4), "rank_eval: one section with more than 2^29 entries");
         if (npos == 0) {
             if (neg_out) std::fill(neg_out + (size_t)s0 * (size_t)num_neg, neg_out + (size_t)s1 * (size_t)num_neg, -1);
             s0 = s1;
@@ -78,8 +64,7 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
         const int ntile = (int)tile_sec.size();
         // ---- one upload: sec_user | sec_q0 | tile_q0 | tile_sec | sec_p0 | pos_at | pos_id | ex_p0 | ex_id [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
         in.clear();
-        in.reserve(4 * ((size_t)nsec + 1) + 2 * (size_t)ntile + 1 + 2 * (size_t)npos + (size_t)nex + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0) +
-                   (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));
+        in.reserve(4 * ((size_t)nsec + 1) + 2 * (size_t)ntile + 1 + 2 * (size_t)npos + (size_t)nex + rank_rows_words(R, s0, s1));
         auto put = [&in](size_t n) { const size_t at = in.size(); in.resize(at + n); return at; };
         const size_t o_user = put((size_t)nsec), o_q0 = put((size_t)nsec + 1), o_tq0 = put((size_t)ntile + 1), o_tsec = put((size_t)ntile);
         const size_t o_p0 = put((size_t)nsec + 1), o_at = put((size_t)npos), o_pid = put((size_t)npos), o_e0 = put((size_t)nsec + 1), o_ex = put((size_t)nex);
@@ -87,7 +72,7 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
         std::copy(tile_sec.begin(), tile_sec.end(), in.begin() + (long)o_tsec);
         for (long s = s0; s <= s1; s++) {
             const size_t q = (size_t)(s - s0);
-            if (s < s1) in[o_user + q] = user ? (int)user[s] : 0;   // (with lines the rows do not read it)
+            if (s < s1) in[o_user + q] = R.user_of(s);   // (with lines the rows do not read it)
             in[o_q0 + q] = (int)(L.first[(size_t)s] - L.first[(size_t)s0]);
             in[o_p0 + q] = (int)(pos_ptr[s] - pos_ptr[s0]);
             in[o_e0 + q] = (int)(L.ex_first[(size_t)s] - L.ex_first[(size_t)s0]);
@@ -98,46 +83,20 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
                 }
         }
         std::copy(L.ex_ids.begin() + (long)L.ex_first[(size_t)s0], L.ex_ids.begin() + (long)L.ex_first[(size_t)s1], in.begin() + (long)o_ex);
-        const size_t o_fb = fb_ptr ? put(rank_fb_words(s0, s1, fb_ptr)) : 0;
-        if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
-        const size_t o_ul = lines ? put(rank_lines_words(s0, s1, lines->ptr)) : 0;
-        if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
-        rank_negs_reserve(ca_in_, in.size(), "the lists of a piece");
+        const RankRowsAt o_rows = rank_rows_pack(R, s0, s1, in);
+        reserve_or_fail(who, ca_in_, in.size(), "the lists of a piece");
         ca_in_.upload(in.data(), in.size(), stream_);
         // ---- the workspaces: the pairs' ids and scores, position | tied | nan, the negatives where they are asked for
         const size_t nres = 2 * (size_t)npos + (size_t)nsec;
-        rank_negs_reserve(ng_id_, (size_t)npair, "the candidate ids of a piece");
-        rank_negs_reserve(ca_score_, (size_t)npair, "the candidate scores of a piece");
-        rank_negs_reserve(ca_out_, nres, "the results of a piece");
-        if (neg_out) rank_negs_reserve(ng_neg_, (size_t)nsec * (size_t)num_neg, "the negatives of a piece");
+        reserve_or_fail(who, ng_id_, (size_t)npair, "the candidate ids of a piece");
+        reserve_or_fail(who, ca_score_, (size_t)npair, "the candidate scores of a piece");
+        reserve_or_fail(who, ca_out_, nres, "the results of a piece");
+        if (neg_out) reserve_or_fail(who, ng_neg_, (size_t)nsec * (size_t)num_neg, "the negatives of a piece");
         RankCandDev D;
         D.nsec = (int)nsec;
         D.sec_user = reinterpret_cast<const unsigned *>(ca_in_.p + o_user);
-        D.user_rows = nullptr;
-        D.item_rows = item_rows; D.item_bias = item_bias;
-        if (fb_ptr || lines) {   // the sections' effective user rows, as rank_cand builds them
-            rank_negs_reserve(rk_rows_, (size_t)nsec * (size_t)P.pitch, "the user rows of a piece");
-            RankLiveRowsDev R;
-            R.nsec = (int)nsec; R.sec_user = D.sec_user;
-            R.fb_p0 = nullptr; R.fb_index = nullptr; R.fb_value = nullptr;
-            if (fb_ptr) {
-                const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
-                R.fb_p0 = ca_in_.p + o_fb;
-                R.fb_index = reinterpret_cast<const unsigned *>(ca_in_.p + o_fb + (size_t)nsec + 1);
-                R.fb_value = reinterpret_cast<const float *>(ca_in_.p + o_fb + (size_t)nsec + 1 + nfb);
-            }
-            if (lines) {
-                const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
-                R.ul_p0 = ca_in_.p + o_ul;
-                R.ul_index = reinterpret_cast<const unsigned *>(ca_in_.p + o_ul + (size_t)nsec + 1);
-                R.ul_value = reinterpret_cast<const float *>(ca_in_.p + o_ul + (size_t)nsec + 1 + nul);
-            }
-            R.rows = rk_rows_.p;
-            launch_rank_live_rows(P, R, stream_);
-            HIPCHECK(hipGetLastError());
-            n_launches_++;
-            D.user_rows = rk_rows_.p;
-        }
+        D.item_rows = R.item_rows; D.item_bias = R.item_bias;
+        D.user_rows = rank_rows_launch(who, R, ca_in_.p, o_rows, D.sec_user, s0, s1);   // the sections' effective user rows, as rank_cand builds them
         RankNegsDev G;
         G.nsec = (int)nsec;
         G.sec0 = s0;
@@ -171,19 +130,8 @@ void Engine::rank_negs(long S, const unsigned *user, const RankLines &U, const i
         if (neg_out)
             HIPCHECK(hipMemcpyAsync(neg_out + (size_t)s0 * (size_t)num_neg, ng_neg_.p, (size_t)nsec * (size_t)num_neg * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
-        for (long s = s0; s < s1; s++) {
-            if (pos_ptr[s + 1] == pos_ptr[s]) continue;
-            nan_out[s] = back[2 * (size_t)npos + (size_t)(s - s0)] != 0 ? 1 : 0;
-            for (int64_t j = pos_ptr[s]; j < pos_ptr[s + 1]; j++) {
-                const size_t q = (size_t)(j - pos_ptr[s0]);
-                position_out[j] = back[q];
-                tied_out[j] = back[(size_t)npos + q];
-            }
-            n_rank_eval_sections_++;
-            n_rank_negs_sections_++;
-            if (fb_ptr) n_rank_fb_sections_++;
-            if (lines) n_rank_line_sections_++;
-        }
+        n_rank_negs_sections_ += rank_positions_back(R, pos_ptr, s0, s1, back.data(), back.data() + npos, back.data() + 2 * npos, position_out, tied_out,
+                                                     nan_out);
         s0 = s1;
     }
 }

@@ -6,8 +6,7 @@
 
 #include "svdf_internal.h"
 #include "svdf_kernels.h"
-#include "svdf_rankfb_lists.h"
-#include "svdf_ranklines_lists.h"
+#include "svdf_rankrows_lists.h"
 #include "svdf_ranktopn_lists.h"
 
 namespace svdf {
@@ -54,91 +53,73 @@ void Engine::rank_topn_admit(const char *who, int top_n, const char *tail) {
 void Engine::rank_topn(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
                        int *count_out, int *nan_out) {
     rank_live_refusals("rank_topn");
-    rank_topn_run(S, user, nullptr, nullptr, nullptr, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
+    RankRowSource R;
+    R.user = user;
+    rank_topn_run(S, R, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
 }
 
 void Engine::rank_topn_fb(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                           const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
-    if (!rank_live_fb_refusals("rank_topn", fb_ptr != nullptr)) fb_ptr = nullptr;
-    rank_topn_run(S, user, fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
+    RankRowSource R;
+    R.user = user;
+    if (rank_live_fb_refusals("rank_topn", fb_ptr != nullptr)) R.fb = RankList{fb_ptr, fb_index, fb_value};
+    rank_topn_run(S, R, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
 }
 
 // The _lines calls: what the _fb calls cover, with or without side tables, every section bringing a USER line.
-void Engine::rank_topn_lines(long S, const RankLines &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
+void Engine::rank_topn_lines(long S, const RankList &U, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
                              const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
-    if (!rank_live_fb_refusals("rank_topn", fb_ptr != nullptr, true)) fb_ptr = nullptr;
-    const std::vector<unsigned> user((size_t)std::max<long>(S, 1), 0u);   // not read by the kernels: the rows come from the lines
-    rank_topn_run(S, user.data(), fb_ptr, fb_index, fb_value, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out, &U);
-}
-
-// what a _lines call refuses about its lines and the trainer's tables, on the host
-void Engine::rank_lines_admit(const char *who, long S, const RankLines &U) {
-    rank_lines_validate(who, S, U, (long)mp_.num_user);
-    rank_lines_check_children(who, "feature_user", feat_user_.index, (long)mp_.num_user);
-    rank_lines_check_children(who, "feature_item", feat_item_.index, (long)mp_.num_item);
+    RankRowSource R;   // no users: the rows come from the lines
+    R.lines = U; R.by_lines = true;
+    if (rank_live_fb_refusals("rank_topn", fb_ptr != nullptr, true)) R.fb = RankList{fb_ptr, fb_index, fb_value};
+    rank_topn_run(S, R, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out);
 }
 
 // The item side of a _lines call: the model's own (nullptr) or, where a feature_item table is set, the matrix and bias vector that one
 // launch of k_rank_live_items prepares on the trainer's stream ahead of the sweeps.
-void Engine::rank_live_items(const char *who, const float **item_rows, const float **item_bias) {
-    *item_rows = *item_bias = nullptr;
+void Engine::rank_live_items(const char *who, RankRowSource &R) {
+    R.item_rows = R.item_bias = nullptr;
     if (feat_item_.num_row() == 0) return;
     const DevParams &P = params();
-    const size_t n = (size_t)mp_.num_item * ((size_t)P.pitch + 1);
-    try {
-        rk_items_.reserve(n);
-    } catch (const std::exception &e) {
-        fail(std::string(who) + ": the prepared item matrix of " + std::to_string(n * sizeof(float)) + " bytes could not be allocated: " + e.what());
-    }
+    reserve_or_fail(who, rk_items_, (size_t)mp_.num_item * ((size_t)P.pitch + 1), "the prepared item matrix");
     launch_rank_live_items(P, rk_items_.p, rk_items_.p + (size_t)mp_.num_item * (size_t)P.pitch, stream_);
     HIPCHECK(hipGetLastError());
     n_launches_++;
-    *item_rows = rk_items_.p;
-    *item_bias = rk_items_.p + (size_t)mp_.num_item * (size_t)P.pitch;
+    R.item_rows = rk_items_.p;
+    R.item_bias = rk_items_.p + (size_t)mp_.num_item * (size_t)P.pitch;
 }
 
-// fb_ptr != nullptr: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
-// lines != nullptr: from their USER lines, behind the feedback sum where there is one
-void Engine::rank_topn_run(long S, const unsigned *user, const int64_t *fb_ptr, const unsigned *fb_index, const float *fb_value, const int64_t *ban_ptr,
-                           const unsigned *ban_item, int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, const RankLines *lines) {
+// R.fb given: the sections score with the rows k_rank_live_rows builds from their feedback lists (the configuration has been admitted);
+// R.lines given: from their USER lines, behind the feedback sum where there is one
+void Engine::rank_topn_run(long S, RankRowSource R, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out, float *score_out,
+                           int *count_out, int *nan_out) {
     rank_topn_admit("rank_topn", top_n, "; for longer lists rank the saved model with svdf_ranker_* and top_k");
     // ---- the lists, before any device work
     check(S == 0 || (item_out && count_out && nan_out), "rank_topn: bad arguments");
     RankTopnLists L;
-    rank_topn_validate(S, user, ban_ptr, ban_item, (long)mp_.num_user, (long)mp_.num_item, top_n, L);
-    if (fb_ptr) rank_fb_validate("rank_topn", S, fb_ptr, fb_index, fb_value, std::min<long>(mp_.num_ufeedback, num_fb_rows()));
-    if (lines) rank_lines_admit("rank_topn", S, *lines);
+    rank_topn_validate(S, R.user, ban_ptr, ban_item, (long)mp_.num_user, (long)mp_.num_item, top_n, L, R.by_lines);
+    rank_rows_validate("rank_topn", S, R);
     need_device("rank_topn");
     if (S == 0) return;
     flush();   // behind whatever has been staged
-    const float *item_rows = nullptr, *item_bias = nullptr;
-    if (lines) rank_live_items("rank_topn", &item_rows, &item_bias);   // once per call
-    rank_topn_sweeps("rank_topn", S, user, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, nullptr, top_n, item_out, score_out, count_out, nan_out);
+    if (R.lines.ptr) rank_live_items("rank_topn", R);   // once per call
+    rank_topn_sweeps("rank_topn", S, R, L, top_n, item_out, score_out, count_out, nan_out);
 }
 
-// The body the top-N calls share from the upload of the validated lists onward.  sec_id is the user of each section, or -- query_base !=
-// nullptr, svdf_item_topn (svdf_itemtopn.cpp) -- its query item.  Under the knob rank_topn_prefilter (and rank_topn_scores = 0; DESIGN.md
+// The body the top-N calls share from the upload of the validated lists onward.  R.user is the user of each section, or -- R.query_base
+// given, svdf_item_topn (svdf_itemtopn.cpp) -- its query item.  Under the knob rank_topn_prefilter (and rank_topn_scores = 0; DESIGN.md
 // section 6ai) the sections go through the matrix sweep and the pinned re-score first; those the rule does not certify are gathered --
 // ids, validated ban lists, feedback lists, USER lines -- into contiguous copies, listed once more by the pinned sweeps and scattered to
 // their places.  Either way every section's list is the pinned one.
-void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
-                              const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
-                              int top_n, int *item_out, float *score_out, int *count_out, int *nan_out) {
+void Engine::rank_topn_sweeps(const char *who, long S, const RankRowSource &R, const RankTopnLists &L, int top_n, int *item_out, float *score_out,
+                              int *count_out, int *nan_out) {
     if (!(rank_topn_prefilter_ && !rank_topn_scores_) || top_n > RANK_TOPN_MAX) {   // (the prefilter's M = top_n + slack <= 384 is its design: a deep call goes without)
-        rank_topn_pass(who, S, sec_id, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, query_base, top_n, item_out, score_out, count_out,
-                       nan_out, rank_topn_scores_, nullptr, true);
+        rank_topn_pass(who, S, R, L, top_n, item_out, score_out, count_out, nan_out, rank_topn_scores_, nullptr, true);
         return;
     }
-    const DevParams &P = params();
-    // ---- the envelope of the item side this call scores with, once, ahead of the first piece
-    tn_env_.reserve(RANK_ENV_WORDS);
-    HIPCHECK(hipMemsetAsync(tn_env_.p, 0, RANK_ENV_WORDS * sizeof(unsigned), stream_));
-    launch_rank_item_envelope(P, item_rows, item_bias, tn_env_.p, stream_);
-    HIPCHECK(hipGetLastError());
-    n_launches_++;
+    rank_item_envelope(who, R);
     std::vector<int> certified((size_t)S, 0);
-    rank_topn_pass(who, S, sec_id, L, fb_ptr, fb_index, fb_value, lines, item_rows, item_bias, query_base, top_n, item_out, score_out, count_out, nan_out,
-                   2, certified.data(), true);
+    rank_topn_pass(who, S, R, L, top_n, item_out, score_out, count_out, nan_out, 2, certified.data(), true);
     std::vector<long> again;
     for (long s = 0; s < S; s++)
         if (!certified[(size_t)s]) again.push_back(s);
@@ -147,55 +128,27 @@ void Engine::rank_topn_sweeps(const char *who, long S, const unsigned *sec_id, c
     n_rank_relisted_sections_ += A;
     if (A == 0) return;
     // ---- the sections left: contiguous copies of what they bring, the pinned sweeps, the results back to their places
-    const size_t N = (size_t)top_n;
-    std::vector<unsigned> ids((size_t)A);
+    const long N = top_n;
+    const RankRelist X(again, R, L.ban_first, L.ban_ids);
     RankTopnLists LA;
-    LA.ban_first.assign((size_t)A + 1, 0);
-    LA.count.resize((size_t)A);
-    auto gather = [&](const int64_t *ptr, const unsigned *index, const float *value, std::vector<int64_t> &p, std::vector<unsigned> &ix, std::vector<float> &v) {
-        p.assign((size_t)A + 1, 0);
-        for (long a = 0; a < A; a++) {
-            const long s = again[(size_t)a];
-            ix.insert(ix.end(), index + ptr[s], index + ptr[s + 1]);
-            v.insert(v.end(), value + ptr[s], value + ptr[s + 1]);
-            p[(size_t)a + 1] = (int64_t)ix.size();
-        }
-    };
-    std::vector<int64_t> fbp, ulp;
-    std::vector<unsigned> fbi, uli;
-    std::vector<float> fbv, ulv;
-    for (long a = 0; a < A; a++) {
-        const size_t s = (size_t)again[(size_t)a];
-        ids[(size_t)a] = sec_id[s];
-        LA.ban_ids.insert(LA.ban_ids.end(), L.ban_ids.begin() + (long)L.ban_first[s], L.ban_ids.begin() + (long)L.ban_first[s + 1]);
-        LA.ban_first[(size_t)a + 1] = (int64_t)LA.ban_ids.size();
-        LA.count[(size_t)a] = L.count[s];
-    }
-    if (fb_ptr) gather(fb_ptr, fb_index, fb_value, fbp, fbi, fbv);
-    RankLines UA;
-    if (lines) {
-        gather(lines->ptr, lines->index, lines->value, ulp, uli, ulv);
-        UA.ptr = ulp.data(); UA.index = uli.data(); UA.value = ulv.data();
-    }
-    std::vector<int> a_item((size_t)A * N), a_count((size_t)A), a_nan((size_t)A);
-    std::vector<float> a_score(score_out ? (size_t)A * N : 0);
-    rank_topn_pass(who, A, ids.data(), LA, fb_ptr ? fbp.data() : nullptr, fbi.data(), fbv.data(), lines ? &UA : nullptr, item_rows, item_bias, query_base,
-                   top_n, a_item.data(), score_out ? a_score.data() : nullptr, a_count.data(), a_nan.data(), 0, nullptr, false);
-    for (long a = 0; a < A; a++) {
-        const size_t s = (size_t)again[(size_t)a];
-        std::copy(a_item.begin() + (long)((size_t)a * N), a_item.begin() + (long)((size_t)(a + 1) * N), item_out + s * N);
-        if (score_out) std::copy(a_score.begin() + (long)((size_t)a * N), a_score.begin() + (long)((size_t)(a + 1) * N), score_out + s * N);
-        count_out[s] = a_count[(size_t)a];
-        nan_out[s] = a_nan[(size_t)a];
-    }
+    LA.ban_first = X.ban_first;
+    LA.ban_ids = X.ban_ids;
+    for (long s : again) LA.count.push_back(L.count[(size_t)s]);
+    std::vector<int> a_item((size_t)(A * N)), a_count((size_t)A), a_nan((size_t)A);
+    std::vector<float> a_score(score_out ? (size_t)(A * N) : 0);
+    rank_topn_pass(who, A, X.rows, LA, top_n, a_item.data(), score_out ? a_score.data() : nullptr, a_count.data(), a_nan.data(), 0, nullptr, false);
+    auto one = [](long i) { return i; };
+    auto list = [N](long i) { return i * N; };
+    X.scatter(a_item.data(), list, item_out, list);
+    if (score_out) X.scatter(a_score.data(), list, score_out, list);
+    X.scatter(a_count.data(), one, count_out, one);
+    X.scatter(a_nan.data(), one, nan_out, one);
 }
 
 // One pass over all S sections: pieces, geometry, workspace, the launches, the copy-back and the count check.  An item call's query rows
-// are gathered from the [num_item][pitch] matrix query_base into the piece's row workspace by one more launch.
-void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, const RankTopnLists &L, const int64_t *fb_ptr, const unsigned *fb_index,
-                            const float *fb_value, const RankLines *lines, const float *item_rows, const float *item_bias, const float *query_base,
-                            int top_n, int *item_out, float *score_out, int *count_out, int *nan_out, int mode, int *certified, bool counted) {
-    const unsigned *user = sec_id;
+// are gathered from the [num_item][pitch] matrix R.query_base into the piece's row workspace by one more launch.
+void Engine::rank_topn_pass(const char *who, long S, const RankRowSource &R, const RankTopnLists &L, int top_n, int *item_out, float *score_out,
+                            int *count_out, int *nan_out, int mode, int *certified, bool counted) {
     const DevParams &P = params();
     // under the prefilter the sweep keeps `keep` = top_n + slack keys per list, and the cap, the geometry and the pieces follow it
     // a deep call (section 6al; never under the prefilter): the deep cap, hence fewer item ranges and more pieces, and the deep launchers
@@ -205,66 +158,38 @@ void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, con
     std::vector<int> in, back;
     for (long s0 = 0; s0 < S;) {
         long s1 = rank_topn_piece(s0, S, max_lists, L.ban_first);
-        if (fb_ptr) s1 = rank_fb_piece(who, s0, s1, fb_ptr, rank_eval_budget_);   // ... and at most rank_eval_budget feedback entries
-        if (lines) s1 = rank_lines_piece(who, s0, s1, lines->ptr, rank_eval_budget_);   // ... and as many line entries
+        if (R.fb.ptr) s1 = rank_list_piece(RANK_FB_LISTS, who, s0, s1, R.fb, rank_eval_budget_);   // ... and at most rank_eval_budget feedback entries
+        if (R.lines.ptr) s1 = rank_list_piece(RANK_USER_LINES, who, s0, s1, R.lines, rank_eval_budget_);   // ... and as many line entries
         const long nsec = s1 - s0;
         const int64_t nban = L.ban_first[(size_t)s1] - L.ban_first[(size_t)s0];
         RankTopnDev D;
         D.nsec = (int)nsec; D.top_n = keep; D.cap = cap; D.matrix = matrix; D.deep = deep;
         rank_topn_geometry(P, nsec, max_lists, &D.gy, &D.items_per_block, matrix);
         // ---- one upload: sec_user | ban_p0 | ban_item [| fb_p0 | fb_index | fb_value] [| ul_p0 | ul_index | ul_value]
-        const size_t o_fb = 2 * (size_t)nsec + 1 + (size_t)nban, o_ul = o_fb + (fb_ptr ? rank_fb_words(s0, s1, fb_ptr) : 0);
-        in.resize(o_ul + (lines ? rank_lines_words(s0, s1, lines->ptr) : 0));
-        if (fb_ptr) rank_fb_pack(s0, s1, fb_ptr, fb_index, fb_value, in.data() + o_fb);
-        if (lines) rank_lines_pack(s0, s1, *lines, in.data() + o_ul);
         const size_t o_user = 0, o_bp0 = (size_t)nsec, o_ban = 2 * (size_t)nsec + 1;
+        in.clear();
+        in.reserve(o_ban + (size_t)nban + rank_rows_words(R, s0, s1));
+        in.resize(o_ban + (size_t)nban);
         for (long s = s0; s < s1; s++) {
-            in[o_user + (size_t)(s - s0)] = (int)user[s];
+            in[o_user + (size_t)(s - s0)] = R.user_of(s);
             in[o_bp0 + (size_t)(s - s0)] = (int)(L.ban_first[(size_t)s] - L.ban_first[(size_t)s0]);
         }
         in[o_bp0 + (size_t)nsec] = (int)nban;
         std::copy(L.ban_ids.begin() + (long)L.ban_first[(size_t)s0], L.ban_ids.begin() + (long)L.ban_first[(size_t)s1], in.begin() + (long)o_ban);
+        const RankRowsAt o_rows = rank_rows_pack(R, s0, s1, in);
+        reserve_or_fail(who, tn_in_, in.size(), "the lists of a piece");
         tn_in_.upload(in.data(), in.size(), stream_);
         // ---- the workspace: list_cnt | nan_cnt | count | certified | items | scores, and the lists
         const size_t nlist = (size_t)nsec * (size_t)D.gy, nres = (size_t)nsec * (3 + 2 * (size_t)N);
-        tn_out_.reserve(nlist + nres);
-        tn_list_.reserve(nlist * (size_t)cap);
+        reserve_or_fail(who, tn_out_, nlist + nres, "the results of a piece");
+        reserve_or_fail(who, tn_list_, nlist * (size_t)cap, "the list workspace of a piece");
         HIPCHECK(hipMemsetAsync(tn_out_.p, 0, (nlist + (size_t)nsec) * sizeof(int), stream_));
         D.sec_user = reinterpret_cast<const unsigned *>(tn_in_.p + o_user);
         D.ban_p0 = tn_in_.p + o_bp0; D.ban_item = tn_in_.p + o_ban;
-        D.user_rows = nullptr;
-        D.item_rows = item_rows; D.item_bias = item_bias;
-        if (fb_ptr || lines) {   // the sections' effective user rows, one more launch ahead of the sweep
-            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
-            RankLiveRowsDev R;
-            R.nsec = (int)nsec; R.sec_user = D.sec_user;
-            R.fb_p0 = nullptr; R.fb_index = nullptr; R.fb_value = nullptr;
-            if (fb_ptr) {
-                const size_t nfb = (size_t)(fb_ptr[s1] - fb_ptr[s0]);
-                R.fb_p0 = tn_in_.p + o_fb;
-                R.fb_index = reinterpret_cast<const unsigned *>(tn_in_.p + o_fb + (size_t)nsec + 1);
-                R.fb_value = reinterpret_cast<const float *>(tn_in_.p + o_fb + (size_t)nsec + 1 + nfb);
-                if (counted) n_rank_fb_sections_ += nsec;
-            }
-            if (lines) {
-                const size_t nul = (size_t)(lines->ptr[s1] - lines->ptr[s0]);
-                R.ul_p0 = tn_in_.p + o_ul;
-                R.ul_index = reinterpret_cast<const unsigned *>(tn_in_.p + o_ul + (size_t)nsec + 1);
-                R.ul_value = reinterpret_cast<const float *>(tn_in_.p + o_ul + (size_t)nsec + 1 + nul);
-                if (counted) n_rank_line_sections_ += nsec;
-            }
-            R.rows = rk_rows_.p;
-            launch_rank_live_rows(P, R, stream_);
-            HIPCHECK(hipGetLastError());
-            n_launches_++;
-            D.user_rows = rk_rows_.p;
-        } else if (query_base) {   // an item call: the sections' query rows, one more launch ahead of the sweep
-            rk_rows_.reserve((size_t)nsec * (size_t)P.pitch);
-            launch_item_query_rows(P, query_base, D.sec_user, (int)nsec, rk_rows_.p, stream_);
-            HIPCHECK(hipGetLastError());
-            n_launches_++;
-            D.user_rows = rk_rows_.p;
-        }
+        D.item_rows = R.item_rows; D.item_bias = R.item_bias;
+        D.user_rows = rank_rows_launch(who, R, tn_in_.p, o_rows, D.sec_user, s0, s1);
+        if (counted && R.fb.ptr) n_rank_fb_sections_ += nsec;
+        if (counted && R.lines.ptr) n_rank_line_sections_ += nsec;
         D.list = tn_list_.p;
         D.list_cnt = tn_out_.p; D.nan_cnt = tn_out_.p + nlist; D.count_out = D.nan_cnt + nsec; D.certified = D.count_out + nsec; D.item_out = D.certified + nsec;
         D.score_out = reinterpret_cast<float *>(D.item_out + (size_t)nsec * N);
@@ -288,7 +213,7 @@ void Engine::rank_topn_pass(const char *who, long S, const unsigned *sec_id, con
             nan_out[s] = bad ? 1 : 0;
             count_out[s] = b_cnt[q];
         }
-        if (counted) (query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
+        if (counted) (R.query_base ? n_item_topn_sections_ : n_rank_topn_sections_) += nsec;
         if (mode == 1) n_rank_matrix_sections_ += nsec;
         if (deep) n_rank_deep_sections_ += nsec;
         s0 = s1;

@@ -19,10 +19,11 @@ struct RankTopnLists {
 };
 
 // Everything svdf_rank_topn refuses about its lists, in the ranker's words where the ranker has them; nothing is written before all of it holds.
+// by_lines: a _lines call, whose sections come without users.
 static inline void rank_topn_validate(long S, const unsigned *user, const int64_t *ban_ptr, const unsigned *ban_item, long num_user, long num_item,
-                                      int top_n, RankTopnLists &out) {
+                                      int top_n, RankTopnLists &out, bool by_lines = false) {
     auto need = [](bool ok, const char *msg) { if (!ok) fail(msg); };
-    need(S >= 0 && (S == 0 || user), "rank_topn: bad arguments");
+    need(S >= 0 && (S == 0 || user || by_lines), "rank_topn: bad arguments");
     out.ban_first.assign((size_t)S + 1, 0);
     out.ban_ids.clear();
     out.count.assign((size_t)S, 0);
@@ -34,7 +35,7 @@ static inline void rank_topn_validate(long S, const unsigned *user, const int64_
     }
     std::vector<long> stamp((size_t)num_item, 0);   // s + 1: banned in section s
     for (long s = 0; s < S; s++) {
-        need((long)user[s] < num_user, "user feature index exceed bound");
+        need(!user || (long)user[s] < num_user, "user feature index exceed bound");
         const size_t first = out.ban_ids.size();
         if (ban_ptr)
             for (int64_t j = ban_ptr[s]; j < ban_ptr[s + 1]; j++) {

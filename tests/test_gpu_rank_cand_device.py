@@ -118,11 +118,25 @@ def test_three_pieces_give_the_same():
 
 
 @pytest.mark.parametrize("force", [1, 2])
-@pytest.mark.parametrize("kind", ["feedback", "lines"])
+@pytest.mark.parametrize("kind", ["feedback", "lines", "feedback+lines"])
 def test_the_rows_lists_travel_with_the_raw_lists(kind, force):
-    """a user-group trainer with feedback= and a plain one with lines=: the offsets of the rows' lists behind the raw ids in the upload"""
-    t = lines_trainer(NU, NI, 16, 1 if kind == "feedback" else 0)
+    """a user-group trainer with feedback= (and with both lists) and a plain one with lines=: the offsets of the rows' lists behind the raw
+    ids in the upload -- of one piece, and of every piece where rank_eval_budget cuts the call into three or more"""
+    t = lines_trainer(NU, NI, 16, 1 if "feedback" in kind else 0)
     users, pos_ptr, pos_item, cand_ptr, cand_item = make_candidates(NS, NU, NI, seed=21)
-    kw = dict(feedback=make_feedback(NS, NFB, seed=5)) if kind == "feedback" else dict(lines=make_lines(NS, NU, 9))
-    c = dict(users=None if kind == "lines" else users, kw=kw, pos_ptr=pos_ptr, pos_item=pos_item, cand_ptr=cand_ptr, cand_item=cand_item)
+    kw = dict(feedback=make_feedback(NS, NFB, seed=5)) if "feedback" in kind else {}
+    if "lines" in kind:
+        kw["lines"] = make_lines(NS, NU, 9)
+    c = dict(users=None if "lines" in kind else users, kw=kw, pos_ptr=pos_ptr, pos_item=pos_item, cand_ptr=cand_ptr, cand_item=cand_item)
+    launches = t.counter(1)
     assert both_builds(t, c, NI, force)[2] == 0
+    one_piece = t.counter(1) - launches
+    # a quarter of the raw ids a piece, and no section alone holds more: four pieces or more.  The host build's calls run at the default
+    # budget both times, so the launches that come on top are the device build's further pieces: sets, pack, rows and one or two of the
+    # ranking, 4 or 5 a piece and call -- two pieces would add at most 2 * 5, three add at least 2 * 2 * 4
+    raw = np.diff(cand_ptr) + np.diff(pos_ptr)
+    budget = int(raw.sum()) // 4
+    assert raw.max() <= budget
+    launches = t.counter(1)
+    assert both_builds(t, c, NI, force, budget=budget)[2] == 0
+    assert t.counter(1) - launches - one_piece >= 2 * 2 * 4

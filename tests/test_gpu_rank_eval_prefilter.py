@@ -8,7 +8,8 @@ import svdfeature_amd as sa
 from rank_rounding import cluster, score_fp32
 from test_gpu_rank_eval import make_sections, new_trainer, ranked_count, rule_positions
 from test_gpu_rank_matrix import model
-from test_rank_feedback import NFB, fb_conf
+from test_gpu_rank_prefilter import relisted_pieces_case, relisted_rule_rows
+from test_rank_feedback import NFB, fb_conf, rule_pos
 from test_rank_lines import lines_conf
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,39 @@ def test_item_ranges_tiles_and_pieces():
     assert S // 3 < t.rank_geometry("positions", S, pos_ptr=lists[1])["sections"] < S
     for a, b in zip(both(t, lambda: t.rank_positions(*lists), lists[1])[0], got):
         np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.parametrize("k", [12, 300])
+@pytest.mark.parametrize("rows", ["fb", "lines", "fb+lines"])
+def test_relisted_sections_of_several_pieces(rows, k):
+    """seven sections (tests/test_gpu_rank_prefilter.py: ragged lists, an empty one at the start and at the end, three sections that cannot
+    be certified) in at least three pieces: the positions of the numpy rule and the outputs of the one-piece call with the knob at 0 --
+    the offsets of a second piece and of the relisted subset are what is on trial"""
+    S = 7
+    t, users, kw, hot, m = relisted_pieces_case(rows, k)
+    _, pos_ptr, pos_item, ban_ptr, ban_item = make_sections(S, NU, NI, seed=k, big=2, empty=5, full_ban=-1, npos_big=40)
+    call = lambda: t.rank_positions(users, pos_ptr, pos_item, ban_ptr, ban_item, **kw)
+    t.set_knob("rank_eval_prefilter", 0)
+    want = call()
+    position, tied = rule_pos(relisted_rule_rows(users, kw, m), m[1], m[2], pos_ptr, pos_item, ban_ptr, ban_item)   # the numpy rule
+    np.testing.assert_array_equal(want[0], position)
+    np.testing.assert_array_equal(want[1], tied)
+    np.testing.assert_array_equal(want[2], ranked_count(NI, ban_ptr, ban_item))
+    assert not want[3].any()
+    # a row of up to 28 positives costs its band list and two words, 1 026; a section adds at most 5 positives, 40 bans, 12 list entries and
+    # 1: two sections with positives fit a piece, three do not -- sections 0 - 1, the two rows of section 2, 3 - 5, 6
+    t.set_knob("rank_eval_budget", 2 * 1026 + 200)
+    t.set_knob("rank_eval_prefilter", 1)
+    assert t.rank_geometry("positions", S, pos_ptr=pos_ptr)["sections"] == 2
+    got, moved = both(t, call, pos_ptr)
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g, w)
+    assert moved == [S - 1 - len(hot), len(hot)]           # section 5 has no positives
+    t.set_knob("rank_eval_budget", 1026)                   # section 2 alone exceeds the budget: ranked by the pinned route at once
+    got, moved = both(t, call, pos_ptr)
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g, w)
+    assert moved == [S - 2 - len(hot), len(hot) + 1]
 
 
 @pytest.mark.parametrize("integer", [False, True], ids=["float", "integer"])

@@ -9,8 +9,9 @@ from rank_rounding import cluster, score_fp32
 from test_gpu_rank_eval import new_trainer
 from test_gpu_rank_matrix import allowed, model, plain_topn
 from test_gpu_rank_topn import assert_same, make_bans, ptr_of
-from test_rank_feedback import NFB, fb_conf
-from test_rank_lines import lines_conf
+from item_topn_rule import rule_similar
+from test_rank_feedback import NFB, fb_conf, rule_lists, rule_user_rows
+from test_rank_lines import lines_conf, rule_line_rows
 
 pytestmark = pytest.mark.gpu
 F32, NU, NI = np.float32, 90, 517
@@ -126,6 +127,105 @@ def test_routes(route, integer, tmp_path):
     rose = [t.counter(c) - b for c, b in zip((39, 49, 40, 41), before)]
     assert rose[0] + rose[1] == 2 * S and rose[2] + rose[3] == (2 * S if route in ("fb", "lines") else 0)   # two calls, each section once
     assert moved[0 if not integer or route == "cosine" else 1] > 0
+
+
+def relisted_pieces_case(rows, k, S=7, hot=(1, 3, 4)):
+    """S sections on a float model whose rows come from ragged lists of 0 - 6 entries -- `rows`: "fb", "lines" or "fb+lines" -- with an
+    empty list in section 0 (the start of the first piece) and in section S - 1 (the end of the call).  Column 0 of W_user and of
+    W_ufeedback is zero but for the denormal U[5, 0]: the row of a section that brings user 5 (as its user, or with value 1 in its line)
+    holds a denormal and is not certified (a condition on the inputs, tests above); the sections `hot` bring it, the others cannot.
+    Returns (trainer, users or None, the keyword lists, hot, the model: U, W, bias, W_ufeedback)."""
+    rng = np.random.default_rng(k + len(rows))
+    U, W, bias = model(NU, NI, k, seed=k, integer=False)
+    Wfb = rng.standard_normal((NFB, k)).astype(F32)
+    U[:, 0], Wfb[:, 0] = 0, 0
+    U[5, 0] = F32(1e-40)
+    fmt = int("fb" in rows)
+    t = sa.Trainer(fmt, 0)
+    for kk, v in lines_conf(NU, NI, k, fmt):
+        t.set_param(kk, v)
+    t.init_model(); t.init_trainer()
+    trainer_of(U, W, bias, t)
+    if fmt:
+        t.set_view("W_ufeedback", Wfb)
+
+    def ragged(n_id, with_5):
+        lists = []
+        for s in range(S):
+            ids = rng.integers(6, n_id, 0 if s in (0, S - 1) else int(rng.integers(1, 7)))   # never id 5 by chance
+            if with_5 and s in hot:
+                ids[len(ids) // 2] = 5
+            lists.append(ids.astype(np.uint32))
+        idx = np.concatenate(lists)
+        return ptr_of(lists), idx, np.where(idx == 5, 1, rng.standard_normal(len(idx))).astype(F32)
+
+    kw = {}
+    if "fb" in rows:
+        kw["feedback"] = ragged(NFB, False)
+    if "lines" in rows:
+        kw["lines"] = ragged(NU, True)
+        return t, None, kw, hot, (U, W, bias, Wfb)
+    users = rng.integers(6, NU, S).astype(np.uint32)
+    users[list(hot)] = 5
+    return t, users, kw, hot, (U, W, bias, Wfb)
+
+
+def relisted_rule_rows(users, kw, model_):
+    """the sections' effective user rows by the numpy rules of tests/test_rank_feedback.py and tests/test_rank_lines.py"""
+    U, _, _, Wfb = model_
+    if "lines" in kw:
+        return rule_line_rows(U, kw["lines"], None, Wfb, kw.get("feedback"))
+    return rule_user_rows(U, Wfb, users, *kw["feedback"])
+
+
+def relisted_items_case(k, S=7, hot=(1, 3, 4)):
+    """an integer item matrix for svdf_item_topn whose ties are known: the query items 0 .. S - 1 are e_0 (e_1 for the sections `hot`), the
+    items 100 .. 119 are 50 e_1, every other item i is (i + 10) e_0 + c_i e_2.  A hot query scores the twenty items 50 (dot) or 1 (cosine)
+    and the rest below: rank top_n ties with rank top_n + 1, so at slack 1 the section is listed again.  Any other query scores item i
+    i + 10 under dot: no tie, certified."""
+    W = np.zeros((NI, k), F32)
+    W[:, 0], W[:, 2] = np.arange(NI) + 10, np.arange(NI) * 7 % 13 + 1
+    W[100:120] = 0
+    W[100:120, 1] = 50
+    W[:S] = 0
+    W[:S, 0] = 1
+    W[list(hot)] = 0
+    W[list(hot), 1] = 1
+    return W, np.arange(S, dtype=np.uint32), hot
+
+
+@pytest.mark.parametrize("k", [12, 300])
+@pytest.mark.parametrize("rows", ["fb", "lines", "fb+lines", "dot", "cosine"])
+def test_relisted_sections_of_several_pieces(rows, k):
+    """seven sections in at least three pieces, some certified and some listed again from the gathered copies of what they bring -- their
+    ragged lists, or (dot, cosine: svdf_item_topn) their query items: the lists of the numpy rule and of the one-piece call with the knob
+    at 0; the offsets of a second piece and of the relisted subset are what is on trial"""
+    S, top_n = 7, 10
+    _, ban_ptr, ban_item = make_bans(S, NU, NI, seed=k, almost_all=-1)
+    if rows in ("dot", "cosine"):
+        W, users, hot = relisted_items_case(k)
+        t = trainer_of(np.zeros((NU, k), F32), W, np.zeros(NI, F32))
+        t.set_knob("rank_topn_prefilter_slack", 1)
+        call = lambda: t.similar_items(users, top_n, rows, ban_ptr, ban_item)
+        rule = rule_similar(W, users, top_n, rows, ban_ptr, ban_item)
+    else:
+        t, users, kw, hot, m = relisted_pieces_case(rows, k)
+        call = lambda: t.rank_topn(users, top_n, ban_ptr, ban_item, **kw)
+        rule = rule_lists(relisted_rule_rows(users, kw, m), m[1], m[2], top_n, ban_ptr, ban_item)
+    t.set_knob("rank_topn_prefilter", 0)
+    want = call()
+    assert_same(want, rule)
+    t.set_knob("rank_topn_prefilter", 1)
+    t.set_knob("rank_topn_budget", 3 * t.rank_geometry("topn", S, top_n)["cap"])    # three lists a piece
+    assert t.rank_geometry("topn", S, top_n)["sections"] == 3
+    got, moved = both(t, call, S)
+    assert_same(got, want)
+    if rows == "cosine":    # the hot sections by their ties; the others' unit scores may lie within Delta_s of each other
+        assert moved[1] >= len(hot)
+    else:
+        assert moved == [S - len(hot), len(hot)]
+    t.set_knob("rank_eval_budget", 6)                                               # ... and cut once more by the entries of the lists
+    assert_same(both(t, call, S)[0], want)
 
 
 def test_item_ranges_and_pieces():

@@ -3,6 +3,8 @@ statement of the effective user row and of the prepared item side that tests/tes
 orders a kernel could take by mistake; the conditions on the inputs that test shares (found and asserted here, on the CPU); and every refusal
 of the svdf_rank_*_lines calls that is decided before the device, on a host-only handle."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -502,10 +504,21 @@ def test_configuration_refusals_of_the_lines_calls(tmp_path):
 
 
 def test_a_table_with_a_child_outside_its_id_space_is_refused_when_the_trainer_starts(tmp_path):
-    """the table loader's own refusal, which the calls repeat once per call (svdf_ranklines_lists.h; tools/check_ranklines_lists.cpp)"""
+    """the table loader's own refusal, which the calls repeat once per call (svdf_rankrows_lists.h; tools/check_rankrows_lists.cpp)"""
     table = tmp_path / "feat.txt"
     table.write_text("1 30:0.5\n")
     with pytest.raises(sa.SvdfError, match="feature_item: child index exceed bound"):
         host_trainer(extra=[("feature_item", str(table))])
     with pytest.raises(sa.SvdfError, match="feature_user: child index exceed bound"):
         host_trainer(extra=[("feature_user", str(table))])
+
+
+def test_the_stand_alone_tool_of_the_row_lists(tmp_path):
+    """tools/check_rankrows_lists.cpp over the host-only header of the feedback lists and USER lines, built plain here; its header comment
+    gives the sanitizer line for running it by hand"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "check_rankrows_lists")
+    subprocess.run(["c++", "-std=c++17", "-O1", "-I" + os.path.join(root, "svdfeature_amd", "csrc"),
+                    os.path.join(root, "tools", "check_rankrows_lists.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
