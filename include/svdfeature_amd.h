@@ -376,7 +376,8 @@ int svdf_synchronize(svdf_trainer *t);
  * 50 of the sections under 39 / 49 (and 40 / 41), those listed by the sweep on the matrix cores (knob rank_topn_scores = 1),
  * 51 / 52 of the sections under 39 / 49 (and 40 / 41), those the certified prefilter listed (knob rank_topn_prefilter = 1) /
  * those it left to the pinned sweep, which listed them again; 50 does not move under the prefilter,
- * 61 of the sections under 39 / 49 (and 40 / 41, 50), those listed by the deep path (knob rank_topn_deep = 1 and top_n > 256) */
+ * 61 of the sections under 39 / 49 (and 40 / 41, 50), those listed by the deep path (knob rank_topn_deep = 1 and top_n > 256),
+ * 62 sections solved by svdf_fold_in */
 int64_t svdf_counter(svdf_trainer *t, int what);
 /* Tuning knobs (not part of the reference surface).  None changes a result bit except those marked (*), which move the windows of the
  * OPT-IN window step only, and the one marked (+), which replaces the pinned score of the top-N lists by one within a published bound.  Every knob, its default, what other values select (round 6: knobs no test or tool sets were deleted).
@@ -1199,6 +1200,46 @@ int svdf_pair_order(long n, uint64_t order_seed, unsigned *sigma_out /* [n] */);
 int svdf_item_topn(svdf_trainer *t, long num_section, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n,
                    int *item_out, float *score_out, int *count_out, int *nan_out);
 int svdf_item_unit_rows(long num_row, int num_factor, const float *rows, float *out);   /* host function: no GPU, no handle */
+
+/* ---- FOLD-IN on the live model: fit user rows to their ratings with the item side held fixed.  A new or barely
+ * seen user arrives with a handful of ratings and needs a row now; a training pass is the wrong tool (it moves the item side too, and one
+ * pass does not converge a cold row).  The call solves the ridge least-squares problem for the row -- one user-side half-step of
+ * alternating least squares -- on the trainer's own W_item, which never leaves the device.
+ * Section s of num_section is the user u = user[s] with the ratings j in [ptr[s], ptr[s + 1]) of item / label.  With q_j = W_item[item[j]]:
+ *   y_j = label[j] - (base_score + u_bias[u] + i_bias[item[j]])   the residual of the trainer's own linear prediction with the factor
+ *                                                                 term left out (u_bias[u] counts as 0 under no_user_bias); u_bias is
+ *                                                                 read and never written
+ *   A   = sum_j q_j q_j^T + reg I
+ *   b   = sum_j y_j q_j
+ *   rows_out[s] = A^-1 b                                          [num_section][num_factor] float32
+ * An item listed twice counts twice.  An empty section gives the zero row, +0 in every element.  reg > 0 makes A symmetric positive
+ * definite.  write = 1 also stores the row into W_user[u] on the device, behind whatever is queued on the trainer's stream: the next
+ * svdf_rank_topn, svdf_rank_eval or predict sees it.  write = 0 leaves the model untouched.  A user may appear in several sections
+ * with write = 0.
+ * ARITHMETIC: float32 with float32 accumulation.  The call publishes NO bit pattern: the Gram sum runs on the matrix cores
+ * (v_mfma_f32_16x16x4_f32), whose internal order is not specified, and A is factorised as L D L^T (the Cholesky factorisation without its
+ * square roots) in LDS.  The contract is accuracy: for every non-empty section the relative 2-norm error against the float64 solution of
+ * the same float32 inputs is at most 4 times that of numpy's float32 route on them (Q^T Q, Q^T y and numpy.linalg.solve in float32),
+ * the latter floored at 2^-20 (tests/test_gpu_fold_in.py; measured: at most 1.82 times, profiles/r48_fold_in.md).  Non-finite inputs give
+ * whatever IEEE gives; no flag is reported.
+ * REFUSED on the host, before any device work and before "needs a GPU", each behind "fold_in: ":
+ *   active_type != 0                          "fold_in: active_type != 0 is not covered: the rule solves the linear link's least squares"
+ *   format_type = 1                           "fold_in: user-group trainers (format_type = 1) are not covered: the score has a feedback part"
+ *   extend_type 2 / 15, common_latent_space != 0, a feature_user or feature_item side table, amd:gpus > 1, a rank handle, a model that is
+ *   not initialised: svdf_item_topn's / svdf_rank_topn's words behind the new prefix
+ *   num_factor > 128                          "fold_in: num_factor must be at most 128"
+ *   reg not finite or <= 0                    "fold_in: reg must be finite and > 0"
+ *   ptr not ascending                         "fold_in: ptr must not decrease" ("... must start at >= 0")
+ *   an id >= num_user in user                 "user feature index exceed bound" (the ranker's messages, as svdf_rank_topn gives them)
+ *   an id >= num_item in item                 "sample item index exceed bound"
+ *   NULL arrays with num_section > 0          "fold_in: bad arguments"
+ *   write = 1 and a user in two sections      "fold_in: user %u is written by two sections"
+ * num_section == 0 returns 0 and launches nothing.  A legal call on a host-only handle says "fold_in needs a GPU".  The call is one packed
+ * upload and ONE launch of k_fold_in (svdf_k_foldin.hip), a section per workgroup from its first rating to its row, and returns when the
+ * rows are on the host.  Counter 62 counts the sections solved.
+ * MEASURED: profiles/r48_fold_in.md. */
+int svdf_fold_in(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ptr, const unsigned *item, const float *label, float reg,
+                 int write, float *rows_out /* [num_section][num_factor] */);
 
 /* ---- libc rand() as a random-access stream (the reference draws rank pairs with rand(), apex-tensor/apex_random.h:42-67;
  * SURVEY 8f2).  svdf_rand_peek writes the next n rand() results WITHOUT consuming them, svdf_rand_skip advances the generator

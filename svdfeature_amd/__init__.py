@@ -414,6 +414,7 @@ def load_library():
     lib.svdf_rank_topn.argtypes = [P, C.c_long, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_item_topn.argtypes = [P, C.c_long, _u32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.c_void_p, _i32p, _i32p]
     lib.svdf_item_unit_rows.argtypes = [C.c_long, C.c_int, _f32p, _f32p]
+    lib.svdf_fold_in.argtypes = [P, C.c_long, _u32p, _i64p, _u32p, _f32p, C.c_float, C.c_int, _f32p]
     _fb = [C.c_void_p, C.c_void_p, C.c_void_p]   # fb_ptr, fb_index, fb_value behind `user`
     lib.svdf_rank_eval_positions_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, _i32p, _i32p, _i32p, _i32p]
     lib.svdf_rank_eval_fb.argtypes = [P, C.c_long, _u32p] + _fb + [_i64p, _u32p, C.c_void_p, C.c_void_p, C.c_int, _i32p, C.POINTER(RankMetrics)]
@@ -1244,6 +1245,29 @@ class Trainer:
         self._ok(self.lib.svdf_item_topn(self.h, S, _pad(items, np.uint32), int(metric), _opt_ptr(ban_ptr), _opt_ptr(ban_item), top_n, out.reshape(-1),
                                          scores.ctypes.data_as(C.c_void_p), count, nan))
         return out[:S], scores[:S], count[:S], nan[:S]
+
+    def fold_in(self, users, ptr, item, label, reg, write=False):
+        """svdf_fold_in: fit the rows of new or barely seen users to their ratings with the item side held fixed -- the ridge
+        least-squares row p = (sum q q^T + reg I)^-1 sum y q over section s's ratings item / label [ptr[s] : ptr[s + 1]], q = W_item[item],
+        y = label - (base_score + u_bias[user] + i_bias[item]); one user-side half-step of alternating least squares on the live model.
+        An item listed twice counts twice, an empty section gives the zero row, reg must be > 0.  write=True also stores each row into
+        W_user on the device, so the next rank_topn / rank_eval / predict sees it (a user may then appear in one section only); write=False
+        leaves the model untouched.  float32 on the matrix cores: no pinned bits, an accuracy bound against the float64 solution (see the
+        header).  Needs active_type 0, format_type 0, num_factor <= 128.  Returns rows [S, num_factor] float32."""
+        users, ptr = np.ascontiguousarray(users, np.uint32).reshape(-1), _pad(ptr, np.int64).reshape(-1)
+        item, label = np.ascontiguousarray(item, np.uint32).reshape(-1), np.ascontiguousarray(label, np.float32).reshape(-1)
+        S = len(users)
+        if len(ptr) != S + 1:
+            raise SvdfError("fold_in: ptr must have one entry more than users")
+        if len(item) != len(label) or int(ptr.max()) > len(item):
+            raise SvdfError("fold_in: item and label must be equally long and hold ptr[-1] entries")
+        shape = (C.c_int(), C.c_int())
+        self._ok(self.lib.svdf_view_shape(self.h, VIEW["W_user"], C.byref(shape[0]), C.byref(shape[1])))
+        k = max(shape[1].value, 0)
+        rows = np.zeros((max(S, 1), max(k, 1)), np.float32)
+        self._ok(self.lib.svdf_fold_in(self.h, S, _pad(users, np.uint32), ptr, _pad(item, np.uint32), _pad(label, np.float32), float(reg),
+                                       1 if write else 0, rows.reshape(-1)))
+        return rows[:S, :k]
 
     # -- multi-GPU item-side delta
     def item_delta_begin(self):

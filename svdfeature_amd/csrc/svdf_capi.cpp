@@ -359,6 +359,11 @@ int svdf_item_topn(svdf_trainer *t, long num_section, const unsigned *item, int 
                    int *item_out, float *score_out, int *count_out, int *nan_out) {
     SVDF_GUARD(-1, { t->e->item_topn(num_section, item, metric, ban_ptr, ban_item, top_n, item_out, score_out, count_out, nan_out); return 0; })
 }
+/* fold-in: a user's ridge least-squares row against the fixed item side */
+int svdf_fold_in(svdf_trainer *t, long num_section, const unsigned *user, const int64_t *ptr, const unsigned *item, const float *label, float reg,
+                 int write, float *rows_out) {
+    SVDF_GUARD(-1, { t->e->fold_in(num_section, user, ptr, item, label, reg, write, rows_out); return 0; })
+}
 int svdf_item_unit_rows(long num_row, int num_factor, const float *rows, float *out) {
     SVDF_GUARD(-1, { svdf::item_unit_rows(num_row, num_factor, rows, out); return 0; })
 }

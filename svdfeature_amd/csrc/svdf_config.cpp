@@ -242,6 +242,7 @@ int64_t Engine::counter(int what) const {
     case 59: return n_rank_cand_bitmap_;      // ... the bitmap form
     case 60: return n_rank_cand_host_;        // _cand calls under that knob that took the host build: a section neither form can take
     case 61: return n_rank_deep_sections_;    // of the sections under 39 / 49 (and 40 / 41, 50), those listed by the deep path (knob rank_topn_deep = 1, top_n > 256; section 6al)
+    case 62: return n_fold_in_sections_;      // sections solved by svdf_fold_in (section 6an)
     case 21: return 0;   // (was: passes of the in-launch DAG executor, removed in round 6 -- DESIGN_APPENDIX.md section K)
     default: return -1;
     }

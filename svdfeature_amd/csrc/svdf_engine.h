@@ -548,6 +548,8 @@ class Engine {
     // similar-item lists on the live model: dot and cosine top-N per query item (svdf_itemtopn.cpp, svdf_k_itemrows.hip)
     void item_topn(long S, const unsigned *item, int metric, const int64_t *ban_ptr, const unsigned *ban_item, int top_n, int *item_out,
                    float *score_out, int *count_out, int *nan_out);
+    // fold-in: the ridge least-squares row of each section's user against the fixed item side (svdf_foldin.cpp, svdf_k_foldin.hip)
+    void fold_in(long S, const unsigned *user, const int64_t *ptr, const unsigned *item, const float *label, float reg, int write, float *rows_out);
     // the same rankings over per-section candidate lists instead of the catalogue minus bans (svdf_rankcand.cpp, svdf_k_rankcand.hip; DESIGN.md
     // section 6aa).  Exactly one of R.user / R.lines is set; top_n == 0: positions (pos_*, position_out, tied_out, ranked_out), else the top_n lists
     void rank_cand(const char *who, long S, RankRowSource R, const int64_t *pos_ptr, const unsigned *pos_item, const int64_t *cand_ptr,
@@ -1055,6 +1057,9 @@ class Engine {
     int64_t n_rank_line_sections_ = 0; // counter 41: sections the _lines calls ranked with a row built from a USER line
     DevBuf<float> rk_items_;           // a _lines call's prepared item side: [num_item][pitch] rows, then [num_item] biases
     int64_t n_item_topn_sections_ = 0; // counter 49: sections listed by svdf_item_topn (its unit rows and zero biases live in rk_items_)
+    DevBuf<int64_t> fi_in_;            // a fold-in call's upload: ptr | user | item | label
+    DevBuf<float> fi_out_;             // ... and its rows, [S][num_factor]
+    int64_t n_fold_in_sections_ = 0;   // counter 62: sections solved by svdf_fold_in
     int64_t n_rank_cand_sections_ = 0; // counter 42: sections the _cand calls ranked over a candidate list
     long rank_cand_form_ = 0;          // knob rank_cand_form: 0 the measured choice, 1 one lane per pair, 2 the staged score kernel
     DevBuf<int> ca_in_, ca_out_;       // a _cand piece's upload (the lists, the tile table) and its results

@@ -400,6 +400,22 @@ void launch_item_unit_rows(const DevParams &P, float *unit, hipStream_t st);   /
 // rows[s] = base[item[s]] for the nsec sections of a piece; base is a [num_item][pitch] matrix (W_item or the unit rows), item[s] < num_item
 void launch_item_query_rows(const DevParams &P, const float *base, const unsigned *item, int nsec, float *rows, hipStream_t st);   // one launch
 
+// ---- fold-in on the live model (svdf_k_foldin.hip): section s is user[s] with the ratings ptr[s] .. ptr[s + 1] of
+// item / label; rows_out[s] = (sum q q^T + reg I)^-1 sum y q over them, and W_user[user[s]] too with `write`.  Every id is in bounds and
+// ptr starts at 0 and does not decrease (fold_in_validate); with `write` no user appears twice.
+struct FoldInDev {
+    long nsec;
+    const int64_t *ptr;
+    const unsigned *user;
+    const unsigned *item;
+    const float *label;
+    float reg;
+    int write;
+    float *rows_out;   // [nsec][k]
+};
+int fold_in_width_class(int k);   // NB of k_fold_in<NB>: 1 / 2 / 4 / 8 blocks of 16 columns; k <= 128
+void launch_fold_in(const DevParams &P, const FoldInDev &D, hipStream_t st);   // one launch
+
 // ---- ranking over per-section candidate lists on the live model (svdf_k_rankcand.hip): one piece of whole sections.
 // Pair q of the piece is (section, cand_id[q]); a section's pairs are consecutive, its ids distinct and ascending.  Only the listed pairs
 // are scored.  Every index is local to the piece and has been validated on the host.
